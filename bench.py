@@ -6,13 +6,15 @@ torch.distributed.run, one rank per GPU.  One "step" = one pass of the hot path 
 index build + initial pass (probe/verify/extension + reciprocal) + reduce + sort/convert, i.e. the timed
 region T of SURVEY.md 8(d) ("packed unique reads resident in HBM" -> "canonical edge list resident").
 value = N_ov / T, N_ov = verified suffix-prefix overlaps (sum of the reference's `connections`).
-Workload at N=1: BASELINE.json configs[2], the north-star target (50 M x 150 bp, k=40, 150 Mb genome, seed 3: SURVEY 8d); configs[1]
-(10 M reads, seed 2) is timed beside it as `c2`.  N>1: the same read set (configs[3]), read ids range-partitioned over the ranks
+Workload at N=1: BASELINE.json configs[2], the north-star target (50 M x 150 bp, k=40, 150 Mb genome, seed 3: SURVEY 8d); with --full,
+configs[1] (10 M reads, seed 2) is timed beside it as `c2`.  N>1: the same read set (configs[3]), read ids range-partitioned over the ranks
 (strong scaling), records/flags/edge buckets exchanged over RCCL.  The result of every workload that has an oracle-generated digest
 (tests/golden/*_digest.json: N_ov, crc32 of the edge list, ...) is asserted against it before anything is printed.
 
-Adds to the JSON line: "roofline" (dominant kernel = k_probe, HIP-event timed inside the library) and
-"cpu_baseline" (the reference itself, oracle/_ref, on a bounded sample of the same workload, rank 0, N=1 only).
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs if --dump-outputs DIR is given, and prints the JSON line:
+the headline, its phases and "roofline" (dominant kernel = k_probe, HIP-event timed inside the library during the timed steps).  --full adds
+what takes runs of its own: "scaling_model", "step4", the side workloads "c2" / "noisy_variant" / "repeat_variant", and "cpu_baseline" (the
+reference itself, oracle/_ref, on a bounded sample of the same workload, rank 0, N=1 only).
 """
 import argparse
 import ctypes as C
@@ -193,6 +195,24 @@ def cpu_baseline_subprocess(args):
     return None
 
 
+DUMP_ROWS = 1 << 20            # sampled rows of the edge list: six float64 columns (five fields + the row numbers) = 48 MB at most
+
+
+def dump_outputs(d, ost, ed, edges_crc):
+    """--dump-outputs: what the timed path hands its caller after its last step -- the overlap stats and the canonical edge list -- as float64 .npy
+    files (every field is an integer below 2^53: exact).  The whole list is 1.4 GB at configs[2], so the columns hold a fixed sample of rows (seed 0:
+    the same rows in every build that finds the same number of edges), the rows' numbers are written beside them and the crc32 of the whole list too."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    n = len(ed)
+    rows = np.arange(n) if n <= DUMP_ROWS else np.unique(np.random.default_rng(0).integers(0, n, DUMP_ROWS))
+    np.save(os.path.join(d, "overlap_stats.npy"), np.array([getattr(ost, f) for f, _ in ost._fields_], dtype=np.float64))
+    np.save(os.path.join(d, "edges_crc32.npy"), np.array([edges_crc], dtype=np.float64))
+    np.save(os.path.join(d, "edges_rows.npy"), rows.astype(np.float64))
+    for col in ("from", "to", "type", "length", "length_twin"):
+        np.save(os.path.join(d, f"edges_{col}.npy"), ed[col][rows].astype(np.float64))
+
+
 def spawn_ranks(n):
     """One child process per rank (fresh interpreters; the parent initialises no GPU runtime, so nothing is ever exec'ed over a live HIP
     context), rendezvous on 127.0.0.1.  Returns the first non-zero exit code; a rank that fails takes the others down with it."""
@@ -252,8 +272,16 @@ def main():
     ap.add_argument("--cpu-full", action="store_true", help="cpu_baseline on the WHOLE of BASELINE.json configs[1] (10 M reads) instead of the bounded sample: several minutes of host time, one-thread leg skipped")
     ap.add_argument("--no-scaling-model", action="store_true", help="skip the multi-GPU model and the extra build + probe pass without minimiser groups it measures (profiling runs)")
     ap.add_argument("--no-noisy-variant", action="store_true", help="skip the secondary line: the same workload with 0.1 %% substitution errors (SURVEY 8d)")
+    ap.add_argument("--full", action="store_true", help="besides the headline, the secondary figures: the multi-GPU model, step 4, configs[1] and its noisy / repeat variants, "
+                                                        "the CPU reference baseline (each can still be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy: the overlap stats, the edge-list crc32 "
+                                                         "and the columns of the edge list (a fixed, seeded sample of at most 2^20 rows, and the rows it took)")
     ap.add_argument("--cpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.cpu_full:       # asks for the CPU baseline, which only a --full run has
+        args.full = True
     if not args.genome:
         args.genome = 3 * args.reads
     if not args.seed:
@@ -365,7 +393,6 @@ def main():
     import digests as dg
     ed = ctx.edges()
     edges_crc = dg.edges_digest(ed["from"], ed["to"], ed["type"], ed["length"], ed["length_twin"])["edges_crc32"]   # canonical edge list: same at every N
-    del ed
     # the oracle's numbers for this exact input (tests/golden/*_digest.json, oracle/make_digests.py): N, N_ov, edge count and edge-list crc32
     dname, want = dg.lookup(args.k, pd)
     digest_checked, bad = None, []
@@ -381,6 +408,9 @@ def main():
         assert cmin == cmax == edges_crc, "ranks disagree on the final edge list"
         assert all_ok == 1 or bad, f"another rank's result differs from the oracle digest {dname}"
     assert not bad, f"result differs from the oracle digest {dname}: " + "; ".join(bad)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, ost, ed, edges_crc)
+    del ed
     ms_per_step = 1e3 * elapsed / args.steps
     value = ost.verified_overlaps / (elapsed / args.steps)
 
@@ -477,7 +507,7 @@ def main():
             t4 = time.perf_counter(); c.graph_simplify(); w4 = time.perf_counter() - t4; s4 = c.simplify_stats()     # (the second call first frees the first one's result)
             return {"device_ms": s4.device_ms, "wall_ms_first_call": 1e3 * w41, "wall_ms": 1e3 * w4, "nodes_contracted": s4.nodes_contracted, "removed": s4.removed, "loop_iterations": s4.loop_iterations,
                     "edges_left": s4.edges, "reads_on_edges": s4.reads_on_edges}
-        if world == 1 and not sharded and not args.no_scaling_model:
+        if args.full and world == 1 and not sharded and not args.no_scaling_model:
             # what a rank of a multi-GPU run would do differently: nothing at this coverage; if this run forces the minimiser groups on (SAGE2OV_MINIMIZER_INDEX=1), the pass without them is measured here (one untimed build + probe pass with the groups switched off), then the model
             alt = None
             if os.environ.get("SAGE2OV_MINIMIZER_INDEX") == "1" and args.err_ppm == 0:
@@ -497,7 +527,7 @@ def main():
             res["scaling_model"] = scaling_model(st.unique_reads, ost.edges, ms_per_step, res["phases_ms"], alt)
             if alt:
                 res["scaling_model"]["without_minimiser_groups_ms"] = alt
-        if world == 1 and not args.no_step4:
+        if args.full and world == 1 and not args.no_step4:
             res["step4"] = step4_of(ctx)
         def side_workload(spd, nsteps, with_step4=False):
             """a secondary workload on its own context, outside the headline's timed region: one warm-up step, `nsteps` timed steps (same
@@ -534,18 +564,18 @@ def main():
             return out
         side = dict(seed=2, genome_len=30_000_000, n_reads=10_000_000, read_len=args.read_len) if args.reads == 50_000_000 else dict(pd)
         side.pop("err_ppm", None)
-        if world == 1 and args.err_ppm == 0 and (not args.no_c2 or not args.no_noisy_variant):
+        if args.full and world == 1 and args.err_ppm == 0 and (not args.no_c2 or not args.no_noisy_variant):
             ctx.close()
-        if world == 1 and not args.no_c2 and args.err_ppm == 0 and args.reads == 50_000_000:
+        if args.full and world == 1 and not args.no_c2 and args.err_ppm == 0 and args.reads == 50_000_000:
             # BASELINE.json configs[1] (the configuration round 1 reported as the headline), three timed steps
             res["c2"] = side_workload(side, 3)
-        if world == 1 and not args.no_noisy_variant and args.err_ppm == 0:
+        if args.full and world == 1 and not args.no_noisy_variant and args.err_ppm == 0:
             # secondary workload of SURVEY 8(d): configs[1] with 0.1 % substitution errors (98 % of the reads then go through the reduce phase)
             res["noisy_variant"] = side_workload(dict(side, err_ppm=1000), 2, with_step4=True)
             # third workload: read errors AND high-copy repeats (k-mers with >= 100 copies are hidden by the index, hashTable.cpp:111-123, which
             # makes discovery one-sided: the reduce phase then needs the exploration order); one timed step
             res["repeat_variant"] = side_workload(dict(side, err_ppm=1000, n_repeat_families=10, repeat_copies=300, repeat_len=400), 1)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             ctx.close()
             res["cpu_baseline"] = cpu_baseline_subprocess(args)
             if res["cpu_baseline"]:
