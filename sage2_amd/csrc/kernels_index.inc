@@ -102,10 +102,7 @@ constexpr int IXW_CNT_BITS_DEFAULT = 20, IXW_CNT_BITS_WIDE = 30;
 // fingerprint of the claiming key (20 bits of its minimiser hash).  Tests shrink it (SAGE2OV_TEST_FP_BITS) the way they shrink the tags: a second
 // key that merges into a bucket AND shares the fingerprint files no group record -- 2^-20 per merge, a merge about once per ten million reads.
 __device__ u32 g_fp_mask = 0xFFFFFu;
-#ifndef SAGE2OV_IXW_THREADS
-#define SAGE2OV_IXW_THREADS 256
-#endif
-constexpr int IXW_T = SAGE2OV_IXW_THREADS;       // threads of a window's workgroup.  With 256 a thread carries 12 tuples (161 VGPRs: three waves per SIMD, which is also what 51 KB of LDS per
+constexpr int IXW_T = 256;                       // threads of a window's workgroup.  With 256 a thread carries 12 tuples (161 VGPRs: three waves per SIMD, which is also what 51 KB of LDS per
                                                  // workgroup allow); 512 threads carry 6 each (110 VGPRs, four waves) and 1024 carry 3 (93) -- measured at BASELINE configs[2]: index build
                                                  // 19.6-19.8 / 19.5-19.7 / 20.4 ms.  The kernel is bound by its LDS atomics, not by occupancy: 256 stays.
 constexpr int IXW_R = 3072 / IXW_T;              // tuples a thread carries in registers from the counting pass to the placing pass (IXW_T x IXW_R = 3072 per window; mean 2048)
@@ -121,10 +118,8 @@ struct IxWinArgs {
     u64* wh; u64 wh_cap;               // scratch for windows with more than 256 * IXW_R tuples (a key in thousands of reads): such a window draws one word per surplus
                                        // tuple from the buffer (counters[9] is the cursor; round 2 kept a word per tuple position: 32 bytes per read)
 };
-#ifndef SAGE2OV_IXW_WAVES
-#define SAGE2OV_IXW_WAVES 1
-#endif
-__global__ __launch_bounds__(IXW_T, SAGE2OV_IXW_WAVES) void k_ix_window(IxWinArgs A) {
+constexpr int IXW_WAVES = 1;           // occupancy bound of k_ix_window's __launch_bounds__ (the registers are not squeezed: 161 VGPRs, see IXW_T)
+__global__ __launch_bounds__(IXW_T, IXW_WAVES) void k_ix_window(IxWinArgs A) {
     __shared__ u64 tbl[IX_W];
     __shared__ u32 csrL[IXW_CSR_CAP];
     __shared__ unsigned short csrT[IXW_CSR_CAP];   // tuple index (relative to the window) of every staged entry: the order inside a bucket

@@ -17,18 +17,10 @@
 template <int NWAVES> __device__ __forceinline__ u32 block_excl_scan(u32 v, u32* sh, u32& total);
 // Tile of a radix pass.  Round 3: 8192 tuples / 512 threads (one workgroup of eight waves per CU, 146 KB of LDS with 16-byte tuples) instead of
 // 4096 / 256 (two workgroups of four): the runs a (tile, digit) pair writes are twice as long -- 5.2 -> 4.75 ms for the two table passes at configs[2].
-#ifndef SAGE2OV_PT_TILE
-#define SAGE2OV_PT_TILE 8192
-#endif
-#ifndef SAGE2OV_PT_THREADS
-#define SAGE2OV_PT_THREADS 512
-#endif
-#ifndef SAGE2OV_PT_SC_THREADS
-#define SAGE2OV_PT_SC_THREADS 1024     // (round 3: sixteen waves on the one tile a CU holds instead of eight -- 100 VGPRs, same LDS with 16-bit counters: index build -0.8 ms, convert -0.1 ms at configs[2])
-#endif
-// (PT_THREADS: the histogram kernel and the tuple kernel; PT_SC_*: the scatter kernel -- same tile)
-constexpr int PT_TILE = SAGE2OV_PT_TILE, PT_THREADS = SAGE2OV_PT_THREADS, PT_NB_MAX = 512;
-constexpr int PT_SC_THREADS = SAGE2OV_PT_SC_THREADS, PT_WAVES = PT_SC_THREADS / 64, PT_ROUNDS = PT_TILE / PT_SC_THREADS;
+// (PT_THREADS: the histogram kernel and the tuple kernel; PT_SC_*: the scatter kernel -- same tile.  Round 3, PT_SC_THREADS: sixteen waves on the one tile a CU holds
+//  instead of eight -- 100 VGPRs, same LDS with 16-bit counters: index build -0.8 ms, convert -0.1 ms at configs[2])
+constexpr int PT_TILE = 8192, PT_THREADS = 512, PT_NB_MAX = 512;
+constexpr int PT_SC_THREADS = 1024, PT_WAVES = PT_SC_THREADS / 64, PT_ROUNDS = PT_TILE / PT_SC_THREADS;
 constexpr int PT_DPT = PT_NB_MAX / PT_SC_THREADS > 0 ? PT_NB_MAX / PT_SC_THREADS : 1;       // digits a thread owns in the (digit, wave) scan (threads beyond the digits own none)
 static_assert(PT_TILE <= 65536 && PT_TILE % PT_SC_THREADS == 0 && PT_TILE % PT_THREADS == 0 && PT_TILE / PT_WAVES <= 65535, "partition tile");
 typedef unsigned short pt_cnt_t;                     // per wave and digit: at most PT_TILE / PT_WAVES tuples, then a position inside the tile (< 65536)

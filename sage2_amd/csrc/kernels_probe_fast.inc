@@ -33,28 +33,20 @@ constexpr int FAST_CAP = 128;
 // (round 3: the 16-word layout keeps whole-candidate overhangs -- a 300-base read overhangs by up to 260 bases, and with the 255-base limit of the
 // 16-dword form nearly every inconsistent 300-base read went to the sequential kernel -- and the packed geometry 10 bits of the length)
 template <int NW> struct TailOvw { static constexpr int value = NW <= 10 ? 8 : (NW <= 16 ? 16 : NW); };
-#ifndef SAGE2OV_FAST_CHUNK
-#define SAGE2OV_FAST_CHUNK 128
-#endif
-constexpr int FAST_CHUNK = SAGE2OV_FAST_CHUNK;     // reads per block visit, the small size (ProbeArgs::chunkShift = log2 of the launch's size: this one or twice as many).
+constexpr int FAST_CHUNK = 128;                    // reads per block visit, the small size (ProbeArgs::chunkShift = log2 of the launch's size: this one or twice as many).
                                                    // A wave's first read of a visit has no predecessor to take windows over from; with the locality order on 32 hash bits and
                                                    // every look-up through the uniform table such a read costs 111 random table lines: 128 / 256 / 512 positions per visit ->
                                                    // 60.0 / 59.1 / 59.9 ms per pass at BASELINE configs[2], but 11.8 / 13.0 at configs[1] (coarser grid): the host picks per launch
 constexpr int FAST_CHUNK_LOG = FAST_CHUNK == 64 ? 6 : (FAST_CHUNK == 128 ? 7 : (FAST_CHUNK == 256 ? 8 : 9));
 static_assert((1 << FAST_CHUNK_LOG) == FAST_CHUNK, "FAST_CHUNK: 64, 128, 256 or 512");
-#ifndef SAGE2OV_SCAN_U
-#define SAGE2OV_SCAN_U 3        // (round 3: 8 records per window in flight were the kernel's register peak -- 16 x u64 per lane; with 3 the 10-dword layouts fit 96 VGPRs = five waves per SIMD)
-#endif
 #ifdef SAGE2OV_CUT     // diagnostic builds: a read is dropped after stage SAGE2OV_CUT (its live values go to a sink that never fires): instruction counts per stage by PMC difference
 #define CUT(n, expr) if (SAGE2OV_CUT == (n)) { const u32 sk_ = (u32)(expr); if (sk_ == 0x9E3779B9u) A.conn[0] = sk_; continue; } else (void)0    /* (no do-while: `continue` must reach the read loop) */
 #else
 #define CUT(n, expr) do { } while (0)
 #endif
-constexpr int SCAN_U = SAGE2OV_SCAN_U;
-#ifndef SAGE2OV_DIRECT_MAX
-#define SAGE2OV_DIRECT_MAX 16
-#endif
-constexpr int DIRECT_MAX = SAGE2OV_DIRECT_MAX;     // a reuse read with at most this many windows left looks them up in the uniform table directly             // group records a lane compares per round of the scan (all loads of a round in flight)
+constexpr int SCAN_U = 3;                          // group records a lane compares per round of the scan (all loads of a round in flight).  (Round 3: 8 records per window in flight
+                                                   // were the kernel's register peak -- 16 x u64 per lane; with 3 the 10-dword layouts fit 96 VGPRs = five waves per SIMD)
+constexpr int DIRECT_MAX = 16;                     // a reuse read with at most this many windows left looks them up in the uniform table directly
 // RUN MODE (round 4; the sequential-groups form only: one read length).  The locality order lines the reads of one stretch of genome up, each starting a few bases after
 // the one before; the per-read algorithm above re-derives for every one of them what its predecessor already knew: 58 of its 62 candidates, all verified against the same
 // bases.  In run mode a wave keeps, across the reads of a run, (1) a FRAME: the genome as far as it has been verified, forward (G) and reverse complement (RCG), anchored
@@ -69,31 +61,15 @@ constexpr int DIRECT_MAX = SAGE2OV_DIRECT_MAX;     // a reuse read with at most 
 // statement, and the records follow from the list by the same tie rules (first window / last window, bucket order).  Anything else -- a candidate that does not verify, a
 // read whose entry is not where it should be, a long shift, k > 64 (gates that depend on the window), a palindromic own entry -- ends the run and the read takes the
 // general path, whose successful end starts the next run.  DESIGN.md 5.2.
-#ifndef SAGE2OV_PAR_MAXIT
-#define SAGE2OV_PAR_MAXIT 8          // rounds of the state machine's parallel form before a read is handed to the steps
-#endif
+constexpr int PAR_MAXIT = 8;                       // rounds of the state machine's parallel form before a read is handed to the steps
 constexpr int RUN_OFF = 160;                       // frame position of the run's first read (>= L - k: the furthest start of a left neighbour)
 constexpr int RUN_FD = 64, RUN_F = 16 * RUN_FD;    // dwords / bases of a frame: RUN_OFF + read + the shifts of a run (minimiser offsets: < read) + right overhang -- and, after a mirror
                                                    // (the second strand of the minimiser), the same again from the other end: 1024 bases, one dword per lane
-#ifndef SAGE2OV_RUN_DMAX
-#define SAGE2OV_RUN_DMAX 64
-#endif
-#ifndef SAGE2OV_RUN_NMAX
-#define SAGE2OV_RUN_NMAX 64
-#endif
-#ifndef SAGE2OV_RUN_NPRE
-#define SAGE2OV_RUN_NPRE 3
-#endif
-#ifndef SAGE2OV_RUN_PF
-#define SAGE2OV_RUN_PF 16
-#endif
-#ifndef SAGE2OV_RUN_MMAX
-#define SAGE2OV_RUN_MMAX 16
-#endif
-constexpr int RUN_DMAX = SAGE2OV_RUN_DMAX;         // largest shift of a step in run mode (lanes that look the new windows up: at most 64)
-constexpr u32 RUN_NMAX = SAGE2OV_RUN_NMAX;         // most new slots per step (compared four per pass; at most 64)
-constexpr u32 RUN_MMAX = SAGE2OV_RUN_MMAX;         // most reads per step (the plan: 2 words each in LDS)
-constexpr int RUN_PF = SAGE2OV_RUN_PF;             // windows behind a step's whose table pairs are fetched ahead
+constexpr int RUN_DMAX = 64;                       // largest shift of a step in run mode (lanes that look the new windows up: at most 64)
+constexpr u32 RUN_NMAX = 64;                       // most new slots per step (compared four per pass; at most 64)
+constexpr int RUN_NPRE = 3;                        // passes of a step's new-slot compare whose dwords are loaded up front (a pass beyond them is one more dependent round trip)
+constexpr u32 RUN_MMAX = 16;                       // most reads per step (the plan: 2 words each in LDS)
+constexpr int RUN_PF = 16;                         // windows behind a step's whose table pairs are fetched ahead
 constexpr int RUN_PW = 256;                        // window numbers are told apart mod this: the <= 128 windows of a read + the RUN_DMAX of a step fit
 static_assert(RUN_DMAX <= 64 && RUN_NMAX <= 64 && RUN_MMAX >= 1 && RUN_MMAX <= 64 && 128 + RUN_DMAX <= RUN_PW, "run mode limits");
 // SPEC: the form speculates (extended strings e[], the two furthest-reaching reads m[]); the form that sends every read through the state machine (TAIL = 2) does not,
@@ -195,20 +171,14 @@ __device__ __forceinline__ u32 any_mismatch(const u32 (&Y)[NW], const u32* E, in
     return acc;
 }
 
-#ifndef SAGE2OV_FAST_WPB
-#define SAGE2OV_FAST_WPB 4      // (round 3: blocks of four waves, five blocks per CU; eight: +3.5 % at the same occupancy)
-#endif
+constexpr int FAST_WPB = 4;    // waves per block of k_probe_fast (round 3: blocks of four waves, five blocks per CU; eight: +3.5 % at the same occupancy)
 // Kernel arguments of the RARE paths (containment marks, the list of reads handed to the other kernels) are read from the kernel-argument segment where they are used
 // instead of living in scalar registers for the whole kernel: the kernel holds ~50 dwords of arguments and spills ~40 SGPRs to VGPR lanes (v_writelane / v_readlane
 // on the hot path).  The asm makes the pointer opaque, so the scalar loads cannot be hoisted out of the rare branch.  (Round 2 did this to the per-read result
 // pointers too: +7 %, their loads wait in line with the LDS traffic -- those stay in registers.)
-#ifndef SAGE2OV_NO_COLD_ARGS
 typedef const __attribute__((address_space(4))) ProbeArgs* ColdArgs;
 __device__ __forceinline__ ColdArgs cold_args() { ColdArgs p = (ColdArgs)__builtin_amdgcn_kernarg_segment_ptr(); asm volatile("" : "+s"(p)); return p; }
 #define COLD(A, f) (cold_args()->f)
-#else
-#define COLD(A, f) ((A).f)
-#endif
 // HITS = 1: the same look-up and gather machinery emits the directional hit lists of the status-0 reads for the reduce phase
 // (economyGraph.cpp:591-633) instead of extension records: every candidate is compared directly with this read.
 constexpr u32 HITS_CHUNK = 2048;   // hit slots a wave reserves at a time (one atomic per ~30 reads instead of one per read)
@@ -220,23 +190,11 @@ constexpr u32 HITS_CHUNK = 2048;   // hit slots a wave reserves at a time (one a
 // SEQ: the groups are gathered and compared ONE AFTER THE OTHER into the same registers -- the reach of every candidate is known from its window and the common length before
 // anything is fetched, the two speculated reads are fetched by lanes 0-2 straight into LDS -- so a read's candidates cost 10 dwords per lane however many groups there are
 // (the wide form, QN = 4, for the reads of high-coverage data the 128-slot forms hand over: tests/diag/coverage_sweep.py).  UNI clean-data form only.
-template <int S, int NW, int WPL, int WPB, int HITS, int TAIL, bool UNI = false, int QN = 2, bool SEQ = false>
-#ifndef SAGE2OV_FAST_WAVES
-#define SAGE2OV_FAST_WAVES 4
-#endif
-#ifndef SAGE2OV_FAST_WAVES_CLEAN
-#define SAGE2OV_FAST_WAVES_CLEAN 7
-#endif
-#ifndef SAGE2OV_FAST_WAVES_SEQ
-#define SAGE2OV_FAST_WAVES_SEQ 8
-#endif
 // (waves per SIMD the register allocator must leave room for: four for the 10-dword layouts = 128 VGPRs; the 16-dword layouts hold 32 more
 // candidate dwords per lane and were spilling ~46 VGPRs and ~25 SGPRs at that budget -- slow, and the one place where a hit's overhang length came
 // out of a reload wrong (found by the stress generator, 161-bp reads in repeats): they get two waves' worth of registers and spill nothing)
 // Likewise three waves' worth for the instantiations that still spilled a few VGPRs at four (three windows per lane; the hit-list form).
-#ifdef SAGE2OV_EXP_OLD_BUDGET      // diagnostic build only (DESIGN section 10): the register budget of the build that returned wrong overhang lengths out of its spills
-__global__ __launch_bounds__(64 * WPB, SAGE2OV_FAST_WAVES) void k_probe_fast(ProbeArgs A) {
-#else
+constexpr int FAST_WAVES = 4;
 // Round 3: SIX waves per SIMD for the form that carries neither the state machine nor the hit lists (TAIL = 0, HITS = 0: the clean-data kernel) with the 8- and
 // 10-dword layouts.  After two rounds of instruction diet the kernel waited more than it issued (71 % VALU busy at four waves per SIMD, 123 VGPRs):
 //   * the record scan keeps 3 instead of 8 records per window in flight (its 16 x u64 were the register peak): 95 VGPRs = five waves, 87.5 -> 76.7 ms per pass at configs[2];
@@ -244,8 +202,9 @@ __global__ __launch_bounds__(64 * WPB, SAGE2OV_FAST_WAVES) void k_probe_fast(Pro
 //     addresses, half-wave indices, masks) out of the loop, each a register for the whole kernel -- 95 -> 79 VGPRs, SGPR spills 20 -> 3: six waves, 67.9 ms;
 //   * shuffles as plain ds_bpermute (shfl64), the previous read's slot words in LDS instead of registers (psl): 77 VGPRs.
 // Seven waves (72 VGPRs) still spill 3 registers in the compare loop: 72.5 ms with 5 spilled -- spills cost more than the occupancy returns.
-__global__ __launch_bounds__(64 * WPB, (NW > 20 ? 1 : (NW > 10 ? 2 : (WPL >= 3 ? 3 : ((HITS == 0 && TAIL == 0) ? (SEQ ? (QN <= 2 ? SAGE2OV_FAST_WAVES_SEQ : 6) : ((NW <= 8 && UNI) ? 8 : SAGE2OV_FAST_WAVES_CLEAN)) : SAGE2OV_FAST_WAVES))))) void k_probe_fast(ProbeArgs A) {      // (32-dword candidates, two per lane: one wave's worth of registers per SIMD, or the kernel spills)
-#endif
+constexpr int FAST_WAVES_CLEAN = 7, FAST_WAVES_SEQ = 8;
+template <int S, int NW, int WPL, int WPB, int HITS, int TAIL, bool UNI = false, int QN = 2, bool SEQ = false>
+__global__ __launch_bounds__(64 * WPB, (NW > 20 ? 1 : (NW > 10 ? 2 : (WPL >= 3 ? 3 : ((HITS == 0 && TAIL == 0) ? (SEQ ? (QN <= 2 ? FAST_WAVES_SEQ : 6) : ((NW <= 8 && UNI) ? 8 : FAST_WAVES_CLEAN)) : FAST_WAVES))))) void k_probe_fast(ProbeArgs A) {      // (32-dword candidates, two per lane: one wave's worth of registers per SIMD, or the kernel spills)
     // the in-kernel state machine for inconsistent reads needs 6.7 KB of LDS per wave at NW = 10; the long-read layouts keep their
     // occupancy instead and hand such reads to the sequential kernel
     constexpr bool TAILED = (HITS == 0) && (TAIL != 0);
@@ -257,11 +216,7 @@ __global__ __launch_bounds__(64 * WPB, (NW > 20 ? 1 : (NW > 10 ? 2 : (WPL >= 3 ?
     static_assert(QN == 2 || (HITS == 0 && TAIL == 0 && UNI), "more than two slot groups: clean-data uniform-length form only");
     static_assert(!SEQ || (HITS == 0 && TAIL == 0 && UNI), "sequential slot groups: clean-data uniform-length form only");
     constexpr int CAP = 64 * QN, NY = SEQ ? 1 : QN;      // candidate slots of a read; candidates a lane holds at a time
-#ifdef SAGE2OV_NO_RUN
-    constexpr bool RUN = false;
-#else
     constexpr bool RUN = SEQ;                            // run mode (see FastLds)
-#endif
     constexpr bool SPEC = !ALWAYS_TAIL;                  // (speculation strings in LDS: see FastLds)
     __shared__ FastLds<S, NW, TAILED, WPL, CAP, RUN, SPEC> lds_all[WPB];
     FastLds<S, NW, TAILED, WPL, CAP, RUN, SPEC>& L = lds_all[threadIdx.x >> 6];
@@ -372,13 +327,11 @@ __global__ __launch_bounds__(64 * WPB, (NW > 20 ? 1 : (NW > 10 ? 2 : (WPL >= 3 ?
         return nh;
     };
     for (;;) {
-#ifndef SAGE2OV_NO_LANE_BARRIER
         // (the lane number behind an optimisation barrier, once per read: expressions derived from it -- LDS addresses, lane masks, half-wave indices: some twenty of them --
         //  are then recomputed where they are used instead of being hoisted out of the read loop, where each holds a vector register for the whole kernel)
         // (recomputed per read from an opaque zero: the two mbcnt are loop-invariant, and the compiler otherwise computes them once in front of the loop and keeps -- or
         //  spills -- the result: found in round 4 when the eight-wave form was 3 registers over its 64; every instantiation lost 3 registers)
         u32 lane; { u32 z_ = 0u; asm volatile("" : "+v"(z_)); lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, z_)); }
-#endif
         // (the wave's LDS block behind an optimisation barrier too, once per read: the address of every array of it that is indexed at run time -- e[][], the ring's tables --
         //  is otherwise computed in front of the loop and holds a vector register for the whole kernel; round 4, run mode: five of them were spilled)
         u32 wq_ = wib; asm volatile("" : "+s"(wq_));
@@ -500,10 +453,9 @@ __global__ __launch_bounds__(64 * WPB, (NW > 20 ? 1 : (NW > 10 ? 2 : (WPL >= 3 ?
                     if (nNew) {
                         // (the new slots' dwords for the first two passes of (e): issued now, in flight while the frame is extended)
                         constexpr u32 CP = 64u / (u32)NW;                      // candidates of a pass: NW lanes each (6 of 10 dwords, 8 of 8)
-                        constexpr int NPRE = SAGE2OV_RUN_NPRE;               // passes whose dwords are loaded up front (a pass beyond them is one more dependent round trip)
-                        u32 yv[NPRE];
+                        u32 yv[RUN_NPRE];
 #pragma unroll
-                        for (int p_ = 0; p_ < NPRE; p_++) {
+                        for (int p_ = 0; p_ < RUN_NPRE; p_++) {
                             yv[p_] = 0u;
                             if (CP * p_ >= nNew) continue;
                             const u32 xl = lane / (u32)NW; const u32 x = CP * p_ + xl, c = lane - xl * (u32)NW; const bool a0 = x < nNew && xl < CP;
@@ -559,9 +511,9 @@ __global__ __launch_bounds__(64 * WPB, (NW > 20 ? 1 : (NW > 10 ? 2 : (WPL >= 3 ?
                             const bool fw = t2 < 2; const bool inside = st_ >= gstart && st_ + Lr <= glen;
                             const int pos = inside ? (fw ? st_ : RUN_F - (st_ + Lr)) : 0;
                             u32 y;
-                            if (p_ < (u32)NPRE) { y = yv[0];
+                            if (p_ < (u32)RUN_NPRE) { y = yv[0];
 #pragma unroll
-                                                  for (int z = 1; z < NPRE; z++) if (p_ == (u32)z) y = yv[z]; }
+                                                  for (int z = 1; z < RUN_NPRE; z++) if (p_ == (u32)z) y = yv[z]; }
                             else y = reads32[(act ? (u64)(e2 >> 2) : 0ull) * D + ((act ? c : 0u) ^ 1u)];
                             if (NW == D && c == (u32)(NW - 1)) y &= ~SLOT_LEN_MASK;
                             const u32* row = fw ? Gp : Rp;
@@ -799,7 +751,6 @@ __global__ __launch_bounds__(64 * WPB, (NW > 20 ? 1 : (NW > 10 ? 2 : (WPL >= 3 ?
             // after a reuse only the last few windows are left: their w-mers fit ONE register (positions base .. base+63), the sliding minimum
             // runs on that register alone and a shuffle hands window j the value of lane j - base
             const int baseW = reuse ? max(prevNwin - dsh, 0) : 0;
-#ifndef SAGE2OV_NO_COMPACT_MIN
             if (reuse && (nwin - baseW) + m - 1 <= 64) {
                 const int p0 = baseW + (int)lane;
                 u32 a = p0 < npos ? wmer_hash(get32(X0, 2 * p0) >> (32 - 2 * w)) : ~0u;
@@ -809,7 +760,6 @@ __global__ __launch_bounds__(64 * WPB, (NW > 20 ? 1 : (NW > 10 ? 2 : (WPL >= 3 ?
 #pragma unroll
                 for (int q = 0; q < WPL; q++) winMin[q] = (u32)shfl64((int)a, (jj[q] - baseW) & 63);
             } else
-#endif
             {
                 constexpr int NC = (16 * NW - 15 + 63) / 64;                      // 64-position chunks that can hold a w-mer start
                 u32 a[NC];
@@ -1064,14 +1014,8 @@ __global__ __launch_bounds__(64 * WPB, (NW > 20 ? 1 : (NW > 10 ? 2 : (WPL >= 3 ?
 #pragma unroll                                                   // the other into the same registers: 128 VGPRs are its budget for four waves per SIMD)
                 for (int q = 0; q < QN; q++) { if (q >= 1 && total <= 64u * q) continue; gather(q, Y[q]); }
             }
-            // (the first group is in flight while the reach is found and the strings are built -- not in the form with run mode: one read in sixteen takes this path there, and
-            //  the ten registers of a candidate, held across the string building and the compares, are what the form's eight waves per SIMD cannot spare: it streams, see 4.)
-#ifdef SAGE2OV_RUN_STREAM
-            constexpr bool STREAMC = RUN;
-#else
-            constexpr bool STREAMC = false;
-#endif
-            if constexpr (SEQ && !STREAMC) gather(0, Y[0]);
+            // (the first group is in flight while the reach is found and the strings are built)
+            if constexpr (SEQ) gather(0, Y[0]);
             STAMP(6);
             CUT(6, Y[0][0] ^ Y[0][NW - 1] ^ Y[1][0] ^ Y[1][NW - 1] ^ Y[0][NW / 2] ^ Y[1][NW / 2] ^ (u32)L2of(0) ^ (u32)L2of(1) ^ myEnt[0] ^ myEnt[1]);
             if constexpr (HITS != 0) {
@@ -1253,64 +1197,9 @@ __global__ __launch_bounds__(64 * WPB, (NW > 20 ? 1 : (NW > 10 ? 2 : (WPL >= 3 ?
 #pragma unroll
                 for (int q = 0; q < QN; q++) {
                     if (q >= 1 && total <= 64u * q) continue;
-                    if constexpr (SEQ && !STREAMC) { if (q >= 1) gather(q, Y[0]); }      // (the next group into the same registers)
+                    if constexpr (SEQ) { if (q >= 1) gather(q, Y[0]); }      // (the next group into the same registers)
                     u32 (&Yq)[NW] = Y[SEQ ? 0 : q];
                     bool hit = false;
-                    if constexpr (STREAMC) {
-                        // STREAMED compare (the form with run mode): the candidate's 16-byte pieces are loaded and compared one after the other -- four registers instead of
-                        // ten, three dependent round trips instead of one.  Same predicates as below: acc == 0 = equals the extended string over its whole length; otherwise the
-                        // direct compare over the overlap decides between "not an overlap" and "overlap, but inconsistent" (containments cannot occur with one read length).
-                        if (gate[q]) {
-                            bool cont; u32 acc;
-                            {   // (what the whole-length compare needs, and nothing else, is live while it streams)
-                                const int t = myEnt[q] & 3, j = myJ[q];
-                                cont = L1 <= (((t & 1) == 0) ? (L1 - j) : (j + h));
-                                const int off = L1 - j - h;
-                                const int d = t == 0 ? j : (t == 2 ? LR - j - L1 : (t == 3 ? off : LL - off - L1));
-                                const bool usable = !cont && d >= 0; const int du = usable ? d : 0;
-                                const u32* E = L.e[t == 0 ? 0 : (t == 2 ? 1 : (t == 3 ? 2 : 3))] + 1 + ((2 * du - 1) >> 5); const u32 sh = (u32)(-2 * du) & 31u;
-                                const uint4* yp = (const uint4*)(A.reads + (u64)(myEnt[q] >> 2) * S);
-                                acc = usable ? 0u : 1u;
-#pragma unroll 1
-                                for (int ch = 0; ch < (NW + 3) / 4; ch++) {              // (not unrolled: unrolled, the scheduler issues all the loads first and the registers are back)
-                                    const uint4 v = yp[ch]; const u32 w4[4] = {v.y, v.x, v.w, v.z};
-#pragma unroll
-                                    for (int k4 = 0; k4 < 4; k4++) {
-                                        const int c = 4 * ch + k4;
-                                        u32 y = w4[k4]; if (NW == D && c == NW - 1) y &= ~SLOT_LEN_MASK;
-                                        const u32 mk = c >= NW ? 0u : (c < clU ? ~0u : (c == clU ? tailU : 0u));
-                                        acc |= (y ^ __builtin_amdgcn_alignbit(E[min(c, NW - 1)], E[min(c, NW - 1) + 1], sh)) & mk;
-                                    }
-                                }
-                            }
-                            u32 diff = 0;
-                            if (acc != 0) {                                           // rare: the direct compare over the overlap, streamed the same way
-                                const int t = myEnt[q] & 3, j = myJ[q];
-                                const int n = cont ? L1 : (((t & 1) == 0) ? (L1 - j) : (j + h));
-                                const int off = L1 - j - h;
-                                const u32* X = (t == 0 || t == 1) ? X0 : X1;
-                                int dd, lo, hi;
-                                if (t == 0) { dd = j; lo = 0; hi = n; } else if (t == 3) { dd = off; lo = 0; hi = n; }
-                                else if (t == 2) { dd = L1 - j - L1; lo = L1 - n; hi = L1; } else { dd = j + h - L1; lo = L1 - n; hi = L1; }
-                                const uint4* yp = (const uint4*)(A.reads + (u64)(myEnt[q] >> 2) * S);
-#pragma unroll 1
-                                for (int ch = 0; ch < (NW + 3) / 4; ch++) {
-                                    const uint4 v = yp[ch]; const u32 w4[4] = {v.y, v.x, v.w, v.z};
-#pragma unroll
-                                    for (int k4 = 0; k4 < 4; k4++) {
-                                        const int c = 4 * ch + k4;
-                                        u32 y = w4[k4]; if (NW == D && c == NW - 1) y &= ~SLOT_LEN_MASK;
-                                        if (c < NW) diff |= (y ^ get32(X, min(max(2 * (16 * c + dd), -32), 32 * D))) & range_mask32(lo - 16 * c, hi - 16 * c);
-                                    }
-                                }
-                            }
-                            if (acc == 0) hit = true;
-                            else if (diff == 0) {
-                                if (cont) { const u32* io_ = COLD(A, idOf); const u32 id2 = io_[myEnt[q] >> 2], id1 = NEED_IID ? iid : io_[i]; atomicOr(&COLD(A, cflag)[myEnt[q] >> 2], id1 > id2 ? 1u : 2u); }   // economyGraph.cpp:735
-                                else bad = true;
-                            }
-                        }
-                    } else
                     if (gate[q]) {
                         const int t = myEnt[q] & 3, j = myJ[q], L2 = L2of(q);
                         const bool rightSide = (t == 0 || t == 2);
@@ -1503,7 +1392,6 @@ __global__ __launch_bounds__(64 * WPB, (NW > 20 ? 1 : (NW > 10 ? 2 : (WPL >= 3 ?
                         auto par_form = [&](auto half_c, const u32 fs, u32& oId, u32& oO, u32& oLen, bool& oAmb) -> bool {       // fs: the side of a whole-wave pass
                             constexpr bool HALF = decltype(half_c)::value;
                             constexpr u32 XB = HALF ? 5u : 6u, XM = (1u << XB) - 1u;
-                            constexpr int PAR_MAXIT = SAGE2OV_PAR_MAXIT;
                             const u32 sd = HALF ? side : fs;
                             const u32 x = HALF ? l5 : lane, nn = sd ? nL : nR; const bool hv = x < nn;
                             const u32 hx = (sd ? (u32)(FAST_CAP - 1) - x : x) & (u32)(FAST_CAP - 1);

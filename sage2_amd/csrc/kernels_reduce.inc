@@ -133,13 +133,8 @@ template <int CAP, int HTLOG> __device__ __forceinline__ u32 ra_find(const RaLds
 // give up: the sequential rule matters) --, eliminate C(a); a node without potential markers is final; one with potential markers needs a witness: its marker nearest the end is read
 // the same way.  When no unknown node is left the marks are those of the walk: 3-6 lists per read instead of all.  Anything unexpected (an earlier marker, two entries to one node,
 // a mark on a node proven unmarkable = lists that are not symmetric, too many lists) leaves the read to the walk, marks reset.  mk: 1 unknown, 2 eliminated, 3 proven not eliminated.
-#ifndef SAGE2OV_RA_SC_PRE
-#define SAGE2OV_RA_SC_PRE 8
-#endif
-constexpr int RA_SC_PRE = SAGE2OV_RA_SC_PRE;      // neighbours at the end of the order whose list extents the short cut fetches up front
-#ifndef SAGE2OV_RA_SHORTCUT_LISTS
-#define SAGE2OV_RA_SHORTCUT_LISTS 24
-#endif
+constexpr int RA_SC_PRE = 8;                      // neighbours at the end of the order whose list extents the short cut fetches up front
+constexpr int RA_SHORTCUT_LISTS = 24;             // most lists the short cut reads for one read before it leaves the read to the walk
 template <int CAP, int HTLOG>
 __device__ __forceinline__ bool ra_shortcut(RaLds<CAP, HTLOG>& L, u32 n, u32 lane, bool dupNode, u32 dgP, u32 ofP, const u32* __restrict__ deg, const u32* __restrict__ offs, const u32* __restrict__ ent32, u64& listsRead) {
     constexpr int RA_HT = 1 << HTLOG;
@@ -191,7 +186,7 @@ __device__ __forceinline__ bool ra_shortcut(RaLds<CAP, HTLOG>& L, u32 n, u32 lan
         const u64 b0 = __ballot(lane < n && L.mk[L.slot[lane < n ? lane : 0]] == 1), b1 = __ballot(lane + 64 < n && L.mk[L.slot[lane + 64 < n ? lane + 64 : 0]] == 1);
         if ((b0 | b1) == 0) break;
         const u32 x = b1 ? 64u + 63u - (u32)__builtin_clzll(b1) : 63u - (u32)__builtin_clzll(b0);
-        if (++lists > (u32)SAGE2OV_RA_SHORTCUT_LISTS) { bad = true; break; }
+        if (++lists > (u32)RA_SHORTCUT_LISTS) { bad = true; break; }
         bool pm = false; u32 w = 0;
         if (!one(x, pm, w)) { bad = true; break; }
         const u32 sx = L.slot[x];
@@ -199,7 +194,7 @@ __device__ __forceinline__ bool ra_shortcut(RaLds<CAP, HTLOG>& L, u32 n, u32 lan
         if (L.mk[sx] == 2) continue;                            // (its own list eliminated it: a self edge, in play at its turn)
         // a witness: its marker nearest the end of the order must be in play at ITS turn
         if (w <= x || L.mk[L.slot[w]] != 2) { bad = true; break; }
-        if (++lists > (u32)SAGE2OV_RA_SHORTCUT_LISTS) { bad = true; break; }
+        if (++lists > (u32)RA_SHORTCUT_LISTS) { bad = true; break; }
         bool pmw = false; u32 ww = 0;
         if (!one(w, pmw, ww) || L.mk[sx] != 2) { bad = true; break; }
     }
@@ -209,15 +204,10 @@ __device__ __forceinline__ bool ra_shortcut(RaLds<CAP, HTLOG>& L, u32 n, u32 lan
 }
 // counters: [0] lists longer than RA_CAP (-> host replay), [1] removed entries.  svn[w] = survivors with to > r of the w-th read.
 // The reads whose list has more than NLO and at most CAP entries (NLO = 0: empty lists too); the last size class hands longer lists over.
-#ifndef SAGE2OV_RA_BATCH
-#define SAGE2OV_RA_BATCH 6
-#endif
-#ifndef SAGE2OV_RA_BLOCKS
-#define SAGE2OV_RA_BLOCKS 8
-#endif
-constexpr int RA_B = SAGE2OV_RA_BATCH;            // neighbour lists fetched and looked up together
+constexpr int RA_B = 6;                           // neighbour lists fetched and looked up together
+constexpr int RA_BLOCKS = 8;                      // occupancy bound of k_ra_mark's __launch_bounds__ for lists of at most 128 entries (longer lists: 4)
 template <int CAP, int HTLOG, int NLO, bool LAST>
-__global__ __launch_bounds__(256, (CAP <= 128 ? SAGE2OV_RA_BLOCKS : 4)) void k_ra_mark(const u32* __restrict__ ids, u64 nids, const u32* __restrict__ offs, const u32* __restrict__ deg,
+__global__ __launch_bounds__(256, (CAP <= 128 ? RA_BLOCKS : 4)) void k_ra_mark(const u32* __restrict__ ids, u64 nids, const u32* __restrict__ offs, const u32* __restrict__ deg,
                                                  const u64* __restrict__ ent, const u32* __restrict__ ent32, uint8_t* rm, u32* svn, u64* counters, u32* heavy, u64 heavyCap, u32 noShortcut, u32* mid) {
     constexpr int RA_HT = 1 << HTLOG;
     __shared__ RaLds<CAP, HTLOG> lds[4];

@@ -437,7 +437,7 @@ static int build_locality_store(Device* d, std::string& err) {
     WS(me, unsigned short, WS_LOC_META, N + 2);
     d->readsLoc = rl; d->idOf = io; d->posOf = po; d->statusP = sp; d->metaP = me;
     const u32* order = nullptr;
-    if (N && !d->opt.get("SAGE2OV_NO_LOCALITY")) { int rc = build_locality_order(d, 1, N + 1, &order, err); if (rc) return rc; }
+    if (N) { int rc = build_locality_order(d, 1, N + 1, &order, err); if (rc) return rc; }
     HIPCHK(hipMemsetAsync(d->d_runStarts, 0, 64 * sizeof(u64), d->stream));                   // run starts of the order (k_loc_index)
     hipLaunchKernelGGL(k_loc_index, dim3(grid_for(std::max<u64>(N, 1), 256)), dim3(256), 0, d->stream, order, (u64)N, io, po, me, (unsigned long long*)d->d_runStarts);
     d->runStartsValid = order != nullptr;
@@ -539,7 +539,7 @@ int dev_build_index(Device* d, uint64_t* slots_out, uint64_t* keys_out, uint64_t
     bool wantMI = !d->diet && N >= 2000000ull && d->probeShare * sizeFactor * RUN_START_RULE(f_) >= 1.0;
     if (d->opt.get("SAGE2OV_TIMING")) fprintf(stderr, "[index] reads without a predecessor in the locality order: %.1f %% -> minimiser groups %s\n", 100.0 * f_, wantMI ? "built" : "not built");
     if (const char* ev = d->opt.get("SAGE2OV_MINIMIZER_INDEX")) wantMI = atoi(ev) != 0;
-    if (d->opt.get("SAGE2OV_NO_MINIMIZER_INDEX") || (d->h - std::min(d->h, 16) + 1) < 8) wantMI = false;
+    if ((d->h - std::min(d->h, 16) + 1) < 8) wantMI = false;
     u64 TL = 0; int tlBits = 0; u64 gW = 0;
     // >= 3N group words (round 3; 2N before): a group window takes 256 x MIW_R = 2048 group tuples in registers and ~3N distinct keys spread over TL / 2048 windows, so with
     // TL in [2N, 3N) most windows overflowed into the global scratch, the scratch ran out, and the groups were built and then given up ("crowded") for every read set
@@ -585,8 +585,7 @@ int dev_build_index(Device* d, uint64_t* slots_out, uint64_t* keys_out, uint64_t
         // one word per SURPLUS tuple of a heavy window (more than 3072 tuples where the mean is 2048: keys in thousands of reads); small inputs get the
         // worst case (every tuple in one window), big ones an eighth of it
         { const u64 whCap = n <= (64u << 20) ? nAlloc : nAlloc / 8; WS(whs, u64, WS_WHERE, whCap); A.wh = whs; A.wh_cap = whCap; }
-        const u64 ixPerCu = d->opt.get("SAGE2OV_IXW_GRID_PER_CU") ? std::max(1, atoi(d->opt.get("SAGE2OV_IXW_GRID_PER_CU"))) : 6;
-        hipLaunchKernelGGL(k_ix_window, dim3((unsigned)std::min<u64>(nW, 256ull * ixPerCu)), dim3(IXW_T), 0, d->stream, A);      // persistent: two rounds of 3 workgroups per CU, each with ONE pair of statistics atomics
+        hipLaunchKernelGGL(k_ix_window, dim3((unsigned)std::min<u64>(nW, 256ull * 6)), dim3(IXW_T), 0, d->stream, A);      // persistent: two rounds of 3 workgroups per CU, each with ONE pair of statistics atomics
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(c, d->d_counters + 8, sizeof c, hipMemcpyDeviceToHost, d->stream));
         u64 c9 = 0; HIPCHK(hipMemcpyAsync(&c9, d->d_counters + 8 + 9, sizeof c9, hipMemcpyDeviceToHost, d->stream));
@@ -615,8 +614,7 @@ int dev_build_index(Device* d, uint64_t* slots_out, uint64_t* keys_out, uint64_t
                 lap("partition by group window");
                 MiWinArgs MA; MA.G = G.E[gcur]; MA.gOff = gOff; MA.gW = (u32)gW; MA.tlBits = tlBits; MA.mi1 = mi1; MA.krec = krec; MA.counters = d->d_counters + 8; MA.wh = A.wh; MA.wh_cap = A.wh_cap;
                 HIPCHK(hipMemsetAsync(d->d_counters + 8 + 9, 0, sizeof(u64), d->stream));                  // (the scratch cursor starts over)
-                const u64 miPerCu = d->opt.get("SAGE2OV_MIW_GRID_PER_CU") ? std::max(1, atoi(d->opt.get("SAGE2OV_MIW_GRID_PER_CU"))) : 8;
-                hipLaunchKernelGGL(k_mi_window, dim3((unsigned)std::min<u64>(gW, 256ull * miPerCu)), dim3(256), 0, d->stream, MA);
+                hipLaunchKernelGGL(k_mi_window, dim3((unsigned)std::min<u64>(gW, 256ull * 8)), dim3(256), 0, d->stream, MA);
                 // the probe scan may run past the last group: empty records behind ALL records
                 u64 mc[3];
                 HIPCHK(hipMemcpyAsync(mc, d->d_counters + 8 + 5, sizeof mc, hipMemcpyDeviceToHost, d->stream));
@@ -690,8 +688,7 @@ static int build_locality_order(Device* d, u64 lo, u64 hi, const u32** order_out
     // ALL 32 bits of the hash since the end of round 3 (four passes of 8 bits; 27 bits = three passes of 9 before): two minimisers that share a bucket interleave
     // their reads and break each other's runs of shifted reads (window reuse, 5.2) -- hash bits -> probe pass at configs[2]: 18 -> 97.2 ms, 24 -> 78.8, 27 -> 62.5,
     // 30 -> 57.2, 32 -> 56.5, for 0.3 ms more of index build.
-    int lg = 32;
-    if (const char* ev = d->opt.get("SAGE2OV_ORDER_BITS")) lg = std::max(1, std::min(32, atoi(ev)));
+    constexpr int lg = 32;
     const u32 ntiles = (u32)((n + PT_TILE - 1) / PT_TILE);
     PtBufs B; B.W = 3;                                                        // {hash, id, meta}
     { WS(a, u32, WS_MINH, 3 * (n + 4)); B.E[0] = a; } { WS(a, u32, WS_OCUR, 3 * (n + 4)); B.E[1] = a; }
@@ -709,7 +706,7 @@ static int build_locality_order(Device* d, u64 lo, u64 hi, const u32** order_out
 }
 static ProbeArgs base_args(Device* d) {
     ProbeArgs A; memset(&A, 0, sizeof A);
-    A.reads = d->readsLoc; A.idOf = d->idOf; A.statusP = d->statusP; A.meta = d->opt.get("SAGE2OV_NO_WINDOW_REUSE") ? nullptr : d->metaP; A.N = d->N; A.S = d->S; A.k = d->k; A.h = d->h; A.slots = d->slots; A.T = d->T; A.csr = d->csr; A.seed = d->seed;
+    A.reads = d->readsLoc; A.idOf = d->idOf; A.statusP = d->statusP; A.meta = d->metaP; A.N = d->N; A.S = d->S; A.k = d->k; A.h = d->h; A.slots = d->slots; A.T = d->T; A.csr = d->csr; A.seed = d->seed;
     A.right = d->right; A.left = d->left; A.conn = d->conn; A.cflag = d->cflag; A.status = d->status; A.counters = d->d_counters;
     A.mi1 = d->mi1; A.TL = d->TL; A.krec = d->krec; A.uniL = d->uniL;
     A.chunkShift = (u32)FAST_CHUNK_LOG;      // (plan_fast_grid may double the positions per block visit)
@@ -727,7 +724,7 @@ static void launch_fast(Device* d, ProbeArgs& A, unsigned blocks) {
 // The sequential-groups form of the clean-data kernel (k_probe_fast<..., UNI, QN, SEQ>): read sets of one length in the 4- and 8-word layouts only; qn = 2 (128 candidates,
 // as the standard form) or 4 (256: the reads of high-coverage data the standard form lists).  false: no such instantiation for these reads.
 static bool launch_fast_seq_any(Device* d, ProbeArgs& A, unsigned blocks, int qn) {
-    constexpr int FW = SAGE2OV_FAST_WPB;
+    constexpr int FW = FAST_WPB;
     const int nwinMax = d->maxL - d->h + 1;
     if (!d->uniL || nwinMax > 128) return false;
     if (d->S == 4) { if (qn == 4) hipLaunchKernelGGL((k_probe_fast<4, 8, 2, FW, 0, 0, true, 4, true>), dim3(blocks), dim3(64 * FW), 0, d->stream, A);
@@ -739,7 +736,7 @@ static bool launch_fast_seq_any(Device* d, ProbeArgs& A, unsigned blocks, int qn
 // picks the instantiation for the resident reads; false: the 32-word layout (505 .. 1018 bases) has no fast kernel
 template <int HITS, int TAIL>
 static bool launch_fast_any(Device* d, ProbeArgs& A, unsigned blocks) {
-    constexpr int FW = SAGE2OV_FAST_WPB;      // waves per block: a whole CU's worth works on one locality chunk
+    constexpr int FW = FAST_WPB;      // waves per block: a whole CU's worth works on one locality chunk
     const int nwinMax = d->maxL - d->h + 1;                               // windows of the longest read
     if (d->S == 4 && nwinMax <= 128) launch_fast<4, 8, 2, FW, HITS, TAIL>(d, A, blocks);
     else if (d->S == 8 && d->maxL <= 160 && nwinMax <= 128) launch_fast<8, 10, 2, FW, HITS, TAIL>(d, A, blocks);
@@ -759,11 +756,8 @@ static bool launch_fast_any(Device* d, ProbeArgs& A, unsigned blocks) {
 // (rounds 1-2), 32 -> 88.7, 64 -> 88.0, 256 -> 88.4, one chunk per block -> 93.2 (a block's start and drain cost ~5 us).  Hence a TAPERED grid: up to three phases of 4096
 // blocks that take 3/4 of what is left each (60 / 15 / ... rounds at configs[2]), then the rest in blocks of a few chunks -- the blocks the hardware dispatches last are short.
 // Launches that write hits out reserve a 2048-slot chunk of the hit buffer per wave at a time: they keep one phase of 16 blocks per CU, or the buffer's slack quadruples.
-// SAGE2OV_FAST_BLOCKS_PER_CU=<n>: one uniform phase of n blocks per CU (diagnostic).
-// SAGE2OV_FAST_BLOCKS_PER_CU=<n>: one uniform phase of n blocks per CU (diagnostic); SAGE2OV_TEST_PHASE_BLOCKS=<b>: phases of b blocks instead of 4096 (tests: several
-// phases on a few thousand reads).
+// SAGE2OV_TEST_PHASE_BLOCKS=<b>: phases of b blocks instead of 4096 (tests: several phases on a few thousand reads).
 static unsigned plan_fast_grid(const Options& O, ProbeArgs& A, u64 n, bool writesHits = false) {
-    const char* eu = O.get("SAGE2OV_FAST_BLOCKS_PER_CU"); const int uniform = eu ? std::max(1, atoi(eu)) : 0;
     const char* ep = O.get("SAGE2OV_TEST_PHASE_BLOCKS"); const u64 PB = ep ? (u64)std::max(1, atoi(ep)) : 4096;
     memset(A.phase, 0, sizeof A.phase);
     // positions per block visit: twice FAST_CHUNK for launches big enough that the coarser grid does not show (kernels_probe_fast.inc: 24 M positions and more;
@@ -772,9 +766,8 @@ static unsigned plan_fast_grid(const Options& O, ProbeArgs& A, u64 n, bool write
     if (const char* ec = O.get("SAGE2OV_FAST_CHUNK_SHIFT")) cs = (u32)std::max(FAST_CHUNK_LOG, std::min(FAST_CHUNK_LOG + 3, atoi(ec)));
     A.chunkShift = cs;
     const u64 CH = 1ull << cs, C = (n + CH - 1) / CH;
-    if (writesHits || uniform || C <= PB * 8) {
-        const char* eh = O.get("SAGE2OV_FAST_HITS_BLOCKS_PER_CU"); const int hitsPerCu = eh ? std::max(1, atoi(eh)) : 16;
-        const u64 nb = std::max<u64>(1, std::min<u64>(C, 256ull * (writesHits ? hitsPerCu : (uniform ? uniform : 16))));
+    if (writesHits || C <= PB * 8) {
+        const u64 nb = std::max<u64>(1, std::min<u64>(C, 256ull * 16));
         A.phase[0][0] = 0; A.phase[0][1] = (u32)nb; A.phase[0][2] = (u32)((C + nb - 1) / nb); A.phase[0][3] = 0;
         return (unsigned)nb;
     }
@@ -804,8 +797,7 @@ int dev_probe(Device* d, uint64_t lo, uint64_t hi, std::string& err) {
     ProbeArgs A = base_args(d); A.lo = lo; A.hi = hi;
     const u64 nreads = hi > lo ? hi - lo : 0;
     d->pre.valid = false;
-    const bool seq_only = d->opt.get("SAGE2OV_SEQUENTIAL_PROBE") != nullptr;
-    if (nreads && !seq_only) {
+    if (nreads) {
         WS(slow, u32, WS_SLOW, nreads);
         A.slow = slow; A.slow_cap = nreads;
         // (positions [lo, hi) of the locality order: consecutive items are neighbours in the genome AND in the read store)
@@ -844,7 +836,7 @@ int dev_probe(Device* d, uint64_t lo, uint64_t hi, std::string& err) {
         auto arm_prehits = [&](ProbeArgs& P, u64 nr, unsigned nb, bool& armed) -> int {
             armed = false;
             if (!(tailKernel == 2 && d->probeShare == 1.0 && lo == 1 && hi == N + 1 && !d->opt.get("SAGE2OV_NO_PREHITS"))) return 0;
-            const u64 hcap = nr * 72 + (u64)nb * SAGE2OV_FAST_WPB * HITS_CHUNK;
+            const u64 hcap = nr * 72 + (u64)nb * FAST_WPB * HITS_CHUNK;
             Hit* hb = (Hit*)ws_get(d, WS_HITS, hcap * sizeof(Hit));                  // (72 hits per read: 49 GB at 42 M reads -- no room: the reduce phase makes its own lists)
             if (!hb) { (void)hipGetLastError(); return 0; }
             WS(hbase, u64, WS_PRE_BASE, N + 2); WS(hcnt, u32, WS_RA_CUR, N + 2);
@@ -923,12 +915,6 @@ int dev_probe(Device* d, uint64_t lo, uint64_t hi, std::string& err) {
             ProbeArgs B = base_args(d); B.ids = list; B.n_ids = nslow;
             int rc = launch_probe<0>(d, B, err); if (rc) return rc;
         }
-    } else if (nreads) {
-        HIPCHK(hipEventRecord(d->ev[2], d->stream));
-        int rc = launch_probe<0>(d, A, err); if (rc) return rc;
-        HIPCHK(hipEventRecord(d->ev[3], d->stream));
-        HIPCHK(hipStreamSynchronize(d->stream));
-        float ms = 0; hipEventElapsedTime(&ms, d->ev[2], d->ev[3]); d->tm.probe_kernel_ms += ms; d->tm.probe_launches++;
     }
     HIPCHK(hipEventRecord(d->ev[1], d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
@@ -1169,7 +1155,7 @@ int dev_reduce_device(Device* d, uint64_t min_unresolved, uint64_t* n_unresolved
     auto lap = [&](const char* what) { if (!timing) return; hipStreamSynchronize(d->stream); auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[reduce/device] %-30s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(t - tp).count()); tp = t; };
     // directional hits of the unresolved reads, device resident: the fast kernel in its hit-list form (locality order, minimiser
     // groups), the sequential kernel for the few reads it hands over (> 128 candidates, ambiguous tags) and for the 16-word layout
-    Hit* dh = nullptr; u64 nh = 0, nslots = 0; u64 dbgFastEnd = 0;
+    Hit* dh = nullptr; u64 nh = 0, nslots = 0;
     WS(hitcount, u32, WS_RA_CUR, N + 2);
     u32* locDev = nullptr;                                                       // ranked form: read id -> 1-based position in the locality order
     {
@@ -1186,7 +1172,7 @@ int dev_reduce_device(Device* d, uint64_t min_unresolved, uint64_t* n_unresolved
         }
         WS(slow, u32, WS_SLOW, N + 1);
         const unsigned blocks = (unsigned)std::min<u64>((N + FAST_CHUNK - 1) / FAST_CHUNK, 256ull * 16);
-        u64 cap = std::max<u64>(1 << 16, nun * 80) + (u64)blocks * SAGE2OV_FAST_WPB * HITS_CHUNK; bool ok = false;
+        u64 cap = std::max<u64>(1 << 16, nun * 80) + (u64)blocks * FAST_WPB * HITS_CHUNK; bool ok = false;
         if (d->opt.get("SAGE2OV_TEST_SMALL_BUFFERS")) cap = 8192;                      // tests: start far too small, the sizing loop must recover
         // The initial pass may have written every read's hits out already (dev_probe, noisy data): drop the ones with a resolved end, in place, and
         // run the hit-list kernel only for the unresolved reads that pass did not cover (its sample, hand-overs).  Any shortage of room: the
@@ -1227,7 +1213,6 @@ int dev_reduce_device(Device* d, uint64_t min_unresolved, uint64_t* n_unresolved
                 HIPCHK(hipGetLastError());
                 HIPCHK(hipMemcpyAsync(c3, d->d_counters + 4, sizeof c3, hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
                 if (c3[0] > cap) { cap = c3[0] + c3[0] / 8 + 1024; continue; }            // some chunk did not fit: everything again
-                dbgFastEnd = c3[0];
                 if (c3[2]) {                                                                  // handed over: exact sequential kernel, appends behind
                     ProbeArgs B = base_args(d); B.hits = dh; B.hits_cap = cap; B.hitcount = hitcount; B.ids = slow; B.n_ids = c3[2];
                     int rc = launch_probe<1>(d, B, err); if (rc) return rc;
@@ -1245,13 +1230,6 @@ int dev_reduce_device(Device* d, uint64_t min_unresolved, uint64_t* n_unresolved
     }
     *n_hits = nh;
     lap("hit lists");
-    if (d->opt.get("SAGE2OV_DEBUG_HITS") && nslots) {                                    // diagnostic: an order-independent checksum of the hit lists
-        std::vector<Hit> hh(nslots); HIPCHK(hipMemcpy(hh.data(), dh, nslots * sizeof(Hit), hipMemcpyDeviceToHost));
-        u64 sum = 0, cnt = 0, sumseq = 0, sumF = 0, cntF = 0; u64 idx = 0;
-        for (const Hit& h : hh) { const bool fastPart = idx++ < dbgFastEnd; if (h.from) { u64 x = ((u64)h.from << 32) ^ ((u64)h.to * 0x9E3779B97F4A7C15ull) ^ ((u64)(u32)h.len << 8) ^ h.type; x ^= x >> 29; x *= 0xBF58476D1CE4E5B9ull; sum += x; sumseq += h.seq; cnt++; if (fastPart) { sumF += x; cntF++; } } }
-        if (const char* path = d->opt.get("SAGE2OV_DEBUG_HITS_FILE")) { FILE* f = fopen(path, "wb"); if (f) { fwrite(hh.data(), sizeof(Hit), (size_t)std::min<u64>(dbgFastEnd, nslots), f); fclose(f); } }
-        fprintf(stderr, "[reduce/device] hits %llu in %llu slots, checksum %016llx, seq sum %llu, nh %llu; fast kernel's part: %llu hits, checksum %016llx\n", (unsigned long long)cnt, (unsigned long long)nslots, (unsigned long long)sum, (unsigned long long)sumseq, (unsigned long long)nh, (unsigned long long)cntF, (unsigned long long)sumF);
-    }
     const u64 nc = d->n_cand;
     WS(deg, u32, WS_RA_DEG, N + 2); WS(offs, u32, WS_RA_OFF, N + 2); WS(cur, u32, WS_CURSOR, N + 2);
     HIPCHK(hipMemsetAsync(deg, 0, (N + 2) * sizeof(u32), d->stream)); HIPCHK(hipMemsetAsync(cur, 0, (N + 2) * sizeof(u32), d->stream));
@@ -1359,8 +1337,7 @@ int dev_reduce_device(Device* d, uint64_t min_unresolved, uint64_t* n_unresolved
     const u32* const idsAll = ids; ids = ids + wlo; const u64 nunAll = nun; nun = whi - wlo; (void)idsAll; (void)nunAll;
     WS(svn, u32, WS_NEED, nun + 2); WS(svoff, u32, WS_OWNER, nun + 2);
     // (the marks' grid: a wave per read, blocks walk the list round-robin; blocks per CU -> reduce phase at configs[1] + 0.1 % errors: 16 -> 69.5 ms, 64 -> 66.0, 256 -> 65.2, 1024 -> 65.2: the tail again)
-    const u64 raPerCu = d->opt.get("SAGE2OV_RA_GRID_PER_CU") ? std::max(1, atoi(d->opt.get("SAGE2OV_RA_GRID_PER_CU"))) : 256;
-    const unsigned gb = (unsigned)std::max<u64>(1, std::min<u64>((nun + 3) / 4, 256ull * raPerCu));
+    const unsigned gb = (unsigned)std::max<u64>(1, std::min<u64>((nun + 3) / 4, 256ull * 256));
     const u64 heavyCap = 1 << 16; WS(heavy, u32, WS_RA_HEAVY, heavyCap);
     lap("  final lists filled");
     HIPCHK(hipEventRecord(d->ev[5], d->stream));                          // (marks_ms: the sharded part of the phase -- marks, removals, re-emission)

@@ -106,23 +106,22 @@ static void explore_order_impl(const Options& O, const std::vector<u32>& pos, co
     // long evicted) and of the rank[] lines around it -- a pointer chase along the genome, one DRAM latency per pop.  A second thread, on
     // a neighbouring core of this thread's core complex (shared L3) where it can be placed, replays the second loop READ-ONLY for the reads a few pops ahead of the
     // walk (racy reads of rank[]: only hints) and touches the lists it would scan, so that they are in the shared caches when the walk
-    // arrives.  It changes nothing the walk reads; SAGE2OV_WALK_HELPER=0 turns it off.
+    // arrives.  It changes nothing the walk reads; it runs wherever the host has a second hardware thread.
     std::thread helper; cpu_set_t savedMask; CPU_ZERO(&savedMask); bool pinnedMain = false;
-    { const char* ev = O.get("SAGE2OV_WALK_HELPER"); const bool want = ev ? atoi(ev) != 0 : std::thread::hardware_concurrency() > 1;
-      if (want) {
+    if (std::thread::hardware_concurrency() > 1) {
         int sib = -1; const int me = sched_getcpu();
         if (me >= 0) { char path[128]; snprintf(path, sizeof path, "/sys/devices/system/cpu/cpu%d/topology/thread_siblings_list", me);
             if (FILE* f = fopen(path, "r")) { int a = -1, b = -1; char sep = 0; if (fscanf(f, "%d%c%d", &a, &sep, &b) >= 3) sib = a == me ? b : a; fclose(f); }
             // measured (EPYC 9575F, 10 M reads): helper on the next core of the same 8-core complex (shared L3) 1.9 s, on the SMT sibling 2.3 s
             // (it shares the walk's issue slots), no helper 3.3 s -- so the neighbour core is tried first
-            if (!O.get("SAGE2OV_WALK_SMT_SIBLING")) { const int nb = (me & ~7) | ((me + 1) & 7); cpu_set_t al; CPU_ZERO(&al); if (sched_getaffinity(0, sizeof al, &al) == 0 && CPU_ISSET(nb, &al)) sib = nb; } }
+            const int nb = (me & ~7) | ((me + 1) & 7); cpu_set_t al; CPU_ZERO(&al); if (sched_getaffinity(0, sizeof al, &al) == 0 && CPU_ISSET(nb, &al)) sib = nb; }
         cpu_set_t allowed; CPU_ZERO(&allowed); if (sib >= 0 && (sched_getaffinity(0, sizeof allowed, &allowed) != 0 || !CPU_ISSET(sib, &allowed))) sib = -1;
         // Pinning (this thread to its current core for the duration of the walk, the helper to a neighbour) is what the 1.9 s were measured with, but a library
-        // call should not fight over cores with other ranks of the same job: off by default when a launcher started several local ranks
-        // (LOCAL_WORLD_SIZE > 1), SAGE2OV_WALK_PIN=0/1 decides otherwise.  Without it the helper still runs, wherever the scheduler puts it.
-        { const char* pe = O.get("SAGE2OV_WALK_PIN"); const char* lw = O.get("LOCAL_WORLD_SIZE"); const bool pin = pe ? atoi(pe) != 0 : !(lw && atoi(lw) > 1); if (!pin) sib = -1; }
+        // call should not fight over cores with other ranks of the same job: off when a launcher started several local ranks
+        // (LOCAL_WORLD_SIZE > 1).  Without it the helper still runs, wherever the scheduler puts it.
+        { const char* lw = O.get("LOCAL_WORLD_SIZE"); if (lw && atoi(lw) > 1) sib = -1; }
         if (sib >= 0 && pthread_getaffinity_np(pthread_self(), sizeof savedMask, &savedMask) == 0) { cpu_set_t one; CPU_ZERO(&one); CPU_SET(me, &one); pinnedMain = pthread_setaffinity_np(pthread_self(), sizeof one, &one) == 0; }   // (restored when the walk ends)
-        const int AHEAD = O.get("SAGE2OV_WALK_AHEAD") ? atoi(O.get("SAGE2OV_WALK_AHEAD")) : 4, WINDOW = 24;
+        constexpr int AHEAD = 4, WINDOW = 24;
         helper = std::thread([&, sib]() {
             if (sib >= 0) { cpu_set_t one; CPU_ZERO(&one); CPU_SET(sib, &one); pthread_setaffinity_np(pthread_self(), sizeof one, &one); }
             size_t done = 0; u32 sink = 0;
@@ -141,7 +140,7 @@ static void explore_order_impl(const Options& O, const std::vector<u32>& pos, co
             }
             if (sink == 0x9E3779B9u) fprintf(stderr, " ");                        // (keeps the loads alive)
         });
-      } }
+    }
     struct HelperJoin { std::thread& t; std::atomic<bool>& d; cpu_set_t& m; bool& pinned;
                         ~HelperJoin() { d.store(true, std::memory_order_release); if (t.joinable()) t.join(); if (pinned) pthread_setaffinity_np(pthread_self(), sizeof m, &m); } } helperJoin{helper, walkDone, savedMask, pinnedMain};
     u64 tcA = 0, tcB = 0, tcC = 0, tcD = 0;
@@ -151,8 +150,7 @@ static void explore_order_impl(const Options& O, const std::vector<u32>& pos, co
         const u64 t0_ = stats ? xo_ticks() : 0;
         for (u32 x = F::next_unexplored(plist, 0, en, rank); x < en; x = F::next_unexplored(plist, x + 1, en, rank)) {
             const u32 to = plist[x] & XO_IDM; __atomic_store_n(&rank[to], ++ctr, __ATOMIC_RELAXED); queue.push_back(to);
-            const int PFE = O.get("SAGE2OV_WALK_PFE") ? atoi(O.get("SAGE2OV_WALK_PFE")) : 1;
-            if (PFE) { const PL& t = pl[to]; if (t.p) { __builtin_prefetch(t.p); __builtin_prefetch(t.p + 16); __builtin_prefetch(t.p + 32); __builtin_prefetch(t.p + 48); } }   // it is marked (its list scanned) within a few pops
+            const PL& t = pl[to]; if (t.p) { __builtin_prefetch(t.p); __builtin_prefetch(t.p + 16); __builtin_prefetch(t.p + 32); __builtin_prefetch(t.p + 48); }   // it is marked (its list scanned) within a few pops
         }
         if (stats) tcA += xo_ticks() - t0_;
     };
@@ -196,7 +194,7 @@ static void explore_order_impl(const Options& O, const std::vector<u32>& pos, co
 void explore_order(const Options& O, const std::vector<u32>& pos, const std::vector<const u32*>& lists, const std::vector<u32>& lenp, const std::vector<uint8_t>& hasCand,
                           u64 N, const std::vector<u32>& startOrder, std::vector<u32>& rank) {
 #if defined(__x86_64__)
-    if (__builtin_cpu_supports("avx2") && !O.get("SAGE2OV_WALK_SCALAR")) { explore_order_impl<XoAvx2>(O, pos, lists, lenp, hasCand, N, startOrder, rank); return; }
+    if (__builtin_cpu_supports("avx2")) { explore_order_impl<XoAvx2>(O, pos, lists, lenp, hasCand, N, startOrder, rank); return; }
 #endif
     explore_order_impl<XoScalar>(O, pos, lists, lenp, hasCand, N, startOrder, rank);
 }

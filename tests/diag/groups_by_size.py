@@ -1,6 +1,6 @@
 """diagnostic: do the minimiser groups pay at this size?  index build + probe pass with and without them (SAGE2OV_TIMING=1 prints the group table's load)"""
 import os, sys
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import fixtures as fx, sage2_amd as s2
 for n in [int(x) for x in sys.argv[1:]]:
     p = fx.synth_params(dict(seed=3, genome_len=3 * n, n_reads=n, read_len=150))

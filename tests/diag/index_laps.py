@@ -1,5 +1,5 @@
-import sys
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+import os, sys
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import fixtures as fx, sage2_amd as s2
 n = 50_000_000
 p = fx.synth_params(dict(seed=3, genome_len=3 * n, n_reads=n, read_len=150))

@@ -1,6 +1,6 @@
 """diagnostic: phase timing of the 0.1 %-error variant of configs[1] (SAGE2OV_TIMING=1 prints the parts of the reduce phase)"""
-import sys, time
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+import os, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import fixtures as fx, sage2_amd as s2
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 10_000_000
 err = int(sys.argv[2]) if len(sys.argv) > 2 else 1000

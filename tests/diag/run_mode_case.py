@@ -1,6 +1,6 @@
 """diagnostic: for the reads whose records differ between run mode and the general path (tests/diag/run_mode_diff.py), the buckets of the windows involved"""
 import os, sys
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import fixtures as fx, sage2_amd as s2
 n = int(sys.argv[1]); k = 40; L = 150

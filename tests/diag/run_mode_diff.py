@@ -1,7 +1,7 @@
 """diagnostic: the probe pass with run mode (default) and without (SAGE2OV_NO_RUN_MODE=1) on the same context -- which reads' records differ, and how.
 usage: python tests/diag/run_mode_diff.py <reads> [k] ; SAGE2OV_MINIMIZER_INDEX etc. are taken from the environment"""
 import os, sys
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import fixtures as fx, sage2_amd as s2
 n = int(sys.argv[1]); k = int(sys.argv[2]) if len(sys.argv) > 2 else 40

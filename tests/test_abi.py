@@ -28,6 +28,29 @@ def test_library_exports_every_declared_symbol():
     assert b"gfx950" in L.sage2ov_version()
 
 
+# switches that the Python binding or bench.py read, not the library
+NON_LIBRARY_SWITCHES = re.compile(r"SAGE2OV_(LIB|NO_TORCH_HIP|BENCH_\w+)$")
+
+
+def test_switch_table_lists_every_switch_the_library_reads():
+    """INTEGRATION.md section 5 documents exactly the SAGE2OV_* names the library sources read (Options::get/flag/num, getenv)"""
+    csrc = os.path.join(fx.ROOT, "sage2_amd", "csrc")
+    read = set()
+    for name in os.listdir(csrc):
+        if name.endswith((".cpp", ".hip", ".h", ".hpp", ".inc")):
+            txt = open(os.path.join(csrc, name)).read()
+            read |= set(re.findall(r'\b(?:opt|O)\.(?:get|flag|num)\(\s*"(SAGE2OV_\w+)"', txt))
+            read |= set(re.findall(r'\bgetenv\(\s*"(SAGE2OV_\w+)"', txt))
+    doc = open(os.path.join(fx.ROOT, "INTEGRATION.md")).read()
+    section = doc[doc.index("## 5. Environment switches"):]
+    section = section[:section.index("\n#", 1)]
+    rows = [line.split("|")[1] for line in section.splitlines() if line.startswith("| `")]
+    table = set(re.findall(r"SAGE2OV_\w+", " ".join(rows)))
+    assert len(read) >= 30
+    assert read - table == set(), "read by the library but not in INTEGRATION.md section 5"
+    assert {n for n in table - read if not NON_LIBRARY_SWITCHES.match(n)} == set(), "in INTEGRATION.md section 5 but read nowhere"
+
+
 def test_step1_host_path_reproduces_reference_reads_file(tmp_path):
     for name in ("g1_clean100_k21", "g5_mixedlen_k21", "g6_k70_150"):
         m = fx.golden(name)
