@@ -198,6 +198,12 @@ static void mem_sample(Device* d) { size_t fr = 0, to = 0; if (hipMemGetInfo(&fr
 // builds by the limit checks of the callers: reads < 2^30, tuples < 2^32); kernels whose item count can pass it are grid-stride and use grid_for_capped.
 static inline unsigned grid_for(u64 n, unsigned block) { return (unsigned)std::max<u64>(1, (n + block - 1) / block); }
 static inline unsigned grid_for_capped(u64 n, unsigned block) { return (unsigned)std::max<u64>(1, std::min<u64>((n + block - 1) / block, ((1ull << 32) / block) - 1)); }
+// out[0, n) = d_counters[first, first + n), once the stream has finished (the slots mean different things in different phases: see the callers)
+static int read_counters(Device* d, int first, int n, u64* out, std::string& err) {
+    HIPCHK(hipMemcpyAsync(out, d->d_counters + first, n * sizeof(u64), hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    return 0;
+}
 
 void dev_set_options(Device* d, const Options& opt) { d->opt = opt; }
 Device* dev_create(int ordinal, const Options& opt, std::string& err) {
@@ -307,7 +313,7 @@ int dev_organize_reads(Device* d, const uint64_t* pool, uint64_t pool_words, con
         HIPCHK(hipMemcpyAsync(doffA, ascii->off, (nin + 1) * sizeof(u64), hipMemcpyHostToDevice, d->stream));
         u64 init[6] = {0, 0, 0, 0, ~0ull, 0}; HIPCHK(hipMemcpyAsync(d->d_counters + 16, init, sizeof init, hipMemcpyHostToDevice, d->stream));
         if (nin) hipLaunchKernelGGL(k_org_classify, dim3(grid_for(nin, 256)), dim3(256), 0, d->stream, dbases, doffA, (u64)nin, (u32)k, 1018u, gflag, d->d_counters + 16);
-        u64 cc[6]; HIPCHK(hipMemcpyAsync(cc, d->d_counters + 16, sizeof cc, hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
+        u64 cc[6]; { int rc = read_counters(d, 16, 6, cc, err); if (rc) return rc; }
         if (cc[5]) { err = "reads longer than 1018 bases are not supported"; return SAGE2OV_ERR_LIMIT; }
         ascii->good = cc[1]; ascii->total_bp = cc[2]; ascii->small = cc[3]; ascii->maxL = (int)cc[0]; ascii->minL = cc[1] ? (int)cc[4] : 0;
         n = cc[1]; maxL = ascii->maxL; minL = ascii->minL;
@@ -751,6 +757,27 @@ static bool launch_fast_any(Device* d, ProbeArgs& A, unsigned blocks) {
     else return false;
     return true;
 }
+// The forms of the fast kernel that the passes ask for:
+//   Clean  TAIL = 0: inconsistent reads and reads with more candidates than slots are listed; the sequential-groups form where it exists (eight waves per SIMD:
+//          -2.4 % at configs[2]), unless SAGE2OV_PROBE_SEQ=0
+//   Wide   the sequential-groups form with 256 candidate slots (QN = 4), no state machine
+//   Tail1  TAIL = 1: the state machine for inconsistent reads          Tail2  TAIL = 2: every read through the state machine
+//   Hits   the hit-list form of the reduce phase (HITS = 1)
+enum class Form { Clean, Wide, Tail1, Tail2, Hits };
+// false: the resident layout has no instantiation of that form (nothing was launched)
+static bool launch_form(Device* d, Form f, ProbeArgs& A, unsigned blocks) {
+    switch (f) {
+        case Form::Clean: {
+            const char* ev = d->opt.get("SAGE2OV_PROBE_SEQ");
+            return ((!ev || atoi(ev) != 0) && launch_fast_seq_any(d, A, blocks, 2)) || launch_fast_any<0, 0>(d, A, blocks);
+        }
+        case Form::Wide: return launch_fast_seq_any(d, A, blocks, 4);
+        case Form::Tail1: return launch_fast_any<0, 1>(d, A, blocks);
+        case Form::Tail2: return launch_fast_any<0, 2>(d, A, blocks);
+        case Form::Hits: return launch_fast_any<1, 0>(d, A, blocks);
+    }
+    return false;
+}
 // The grid of the fast kernel.  Every block walks its chunks in a fixed round-robin order and is resident until its slowest wave is done, so the grid's granularity
 // decides how long CUs idle at the end of the launch.  Measured at BASELINE configs[2] (round 3, uniform grids, blocks per CU -> kernel ms): 4 -> 92.2, 8 -> 90.8, 16 -> 89.6
 // (rounds 1-2), 32 -> 88.7, 64 -> 88.0, 256 -> 88.4, one chunk per block -> 93.2 (a block's start and drain cost ~5 us).  Hence a TAPERED grid: up to three phases of 4096
@@ -785,6 +812,47 @@ static unsigned plan_fast_grid(const Options& O, ProbeArgs& A, u64 n, bool write
 void dev_set_probe_share(Device* d, double share) { d->probeShare = share; }
 bool dev_has_minimiser_groups(Device* d) { return d->mi1 != nullptr && d->TL != 0; }
 
+// What dev_probe runs, decided on the host (no device calls).  The TAIL = 1 form is 10 % slower on every read, and on error-free data a read in a thousand
+// needs it.  So the first 1/128 of the range (nsample) runs the clean form, which lists such reads; the share it listed picks the main form for the rest
+// (plan_after_sample).  The listed reads then go through the passes over the list: the wide form when there are many (high coverage:
+// tests/diag/coverage_sweep.py), the TAIL = 1 form, and what that cannot settle either (more than 128 candidates, overhangs beyond its rows) ends in the
+// sequential kernel.
+struct ProbePlan {
+    u64 nsample = 0;          // reads of the sample pass at the start of the range (0: no sample, the main pass takes the whole range)
+    Form main = Form::Tail1;  // the main pass's form (Wide: the clean form where the layout has no wide one)
+    bool listed = false;      // the main pass lists reads for the passes over the list
+    bool wide = false;        // ... and the wide pass runs over the list first when it holds wideMin reads or more
+    u64 wideMin = 4096;
+};
+static void plan_wide_pass(const Options& O, int uniL, ProbePlan& P) {
+    P.wide = P.listed && P.main != Form::Tail2 && P.main != Form::Wide && uniL != 0 && !O.get("SAGE2OV_NO_WIDE");
+    if (const char* ev = O.get("SAGE2OV_PROBE_WIDE_MIN")) P.wideMin = strtoull(ev, nullptr, 10);
+}
+static ProbePlan plan_probe(const Options& O, int uniL, u64 nreads) {
+    ProbePlan P;
+    const char* evs = O.get("SAGE2OV_PROBE_SAMPLE_MIN");                       // tests: sample on small inputs too
+    const u64 sampleMin = evs ? strtoull(evs, nullptr, 10) : (128u << 10);
+    const char* evt = O.get("SAGE2OV_PROBE_TAIL");                             // "0" / "1" / "2": no sample, that form for everything
+    u64 ns = (nreads >= 4 * sampleMin && !evt) ? std::max<u64>(nreads / 128, sampleMin) : 0;      // (on noisy data the sample is work done twice)
+    ns = (ns + 2 * FAST_CHUNK - 1) / (2 * FAST_CHUNK) * (2 * FAST_CHUNK);
+    P.nsample = ns < nreads ? ns : 0;
+    const int tail = evt ? atoi(evt) : 1;
+    P.main = tail == 2 ? Form::Tail2 : (tail == 1 ? Form::Tail1 : Form::Clean);
+    P.listed = evt && tail == 0;
+    plan_wide_pass(O, uniL, P);
+    return P;
+}
+// The sample listed `listed` reads, `capped` of them for having more candidates than slots.  Inconsistent reads: more than half -> the state machine for every
+// read; more than 1/32 -> the form that carries it.  Capped reads, more than 1/32 (one-length read sets): the rest runs the wide form right away instead of
+// listing a fifth of the reads again.
+static void plan_after_sample(const Options& O, int uniL, ProbePlan& P, u64 listed, u64 capped) {
+    const u64 ns = P.nsample, nInc = listed - std::min(listed, capped);
+    P.main = nInc * 2 > ns ? Form::Tail2 : (nInc * 32 > ns ? Form::Tail1 : Form::Clean);
+    if (P.main == Form::Clean && capped * 32 > ns && uniL != 0 && !O.get("SAGE2OV_NO_WIDE")) P.main = Form::Wide;
+    P.listed = true;
+    plan_wide_pass(O, uniL, P);
+}
+
 int dev_probe(Device* d, uint64_t lo, uint64_t hi, std::string& err) {
     HIPCHK(hipSetDevice(d->ordinal));
     if (!d->slots) { err = "index not built"; return SAGE2OV_ERR_ARG; }
@@ -806,101 +874,87 @@ int dev_probe(Device* d, uint64_t lo, uint64_t hi, std::string& err) {
         if (!d_stamps) HIPCHK(hipMalloc(&d_stamps, 32 * sizeof(u64)));
         HIPCHK(hipMemsetAsync(d_stamps, 0, 32 * sizeof(u64), d->stream)); A.stamps = d_stamps;
 #endif
-        // Which kernel?  The one that carries the state machine for inconsistent reads (TAIL = 1) is 10 % slower on every read; on error-free
-        // data a read in a thousand needs it.  So the first 1/128 of the range runs without it (TAIL = 0: such reads are listed), the share of
-        // listed reads decides for the rest, and the listed reads go through the TAIL = 1 kernel as an id list afterwards; what that one
-        // cannot settle either (more than 128 candidates, overhangs beyond its rows) ends in the sequential kernel, as before.
-        const char* evs = d->opt.get("SAGE2OV_PROBE_SAMPLE_MIN");                 // tests: sample on small inputs too
-        const u64 sampleMin = evs ? strtoull(evs, nullptr, 10) : (128u << 10);
-        const char* evt = d->opt.get("SAGE2OV_PROBE_TAIL");                       // "0" / "1" / "2": no sampling, that kernel for everything
-        u64 nsample = (nreads >= 4 * sampleMin && !evt) ? std::max<u64>(nreads / 128, sampleMin) : 0;   // (on noisy data the sample is work done twice)
-        nsample = (nsample + 2 * FAST_CHUNK - 1) / (2 * FAST_CHUNK) * (2 * FAST_CHUNK);
-        int tailKernel = evt ? atoi(evt) : 1; bool anyListed = evt && tailKernel == 0;       // 0 / 1 / 2: see k_probe_fast
-        bool launched = true, mainWide = false;
-        u64 nslow = 0, ncap = 0; float kms = 0;
-        // the clean-data launches of one-length read sets run the sequential-groups form (eight waves per SIMD: -2.4 % at configs[2]); SAGE2OV_PROBE_SEQ=0: the standard form
-        const bool seqForm = !(d->opt.get("SAGE2OV_PROBE_SEQ") && atoi(d->opt.get("SAGE2OV_PROBE_SEQ")) == 0);
-        auto timed = [&](auto&& launch) -> int {                              // one launch of the fast kernel between two events
+        ProbePlan P = plan_probe(d->opt, d->uniL, nreads);
+        float kms = 0;
+        // noisy data, and this context probes every read: the hits of the unresolved reads ARE the verified hits of this pass -- written out
+        // now (the main pass in its TAIL = 2 form, with hitBase), filtered by the final statuses in the reduce phase (k_hits_filter)
+        const bool prehits = d->probeShare == 1.0 && lo == 1 && hi == N + 1 && !d->opt.get("SAGE2OV_NO_PREHITS");
+        struct FastPass { bool launched = false; u64 listed = 0, capped = 0; };
+        // One timed pass of the fast kernel in form f over B's range or id list of n reads: its grid, the launch between two events, what it listed
+        // (d_counters[6..7]).  The main pass: its wide form falls back to the clean one, its TAIL = 2 form writes the hits out (prehits).
+        auto pass = [&](Form f, ProbeArgs& B, u64 n, bool mainPass, FastPass& r) -> int {
+            const unsigned nb = plan_fast_grid(d->opt, B, n, f == Form::Tail2);
+            bool armed = false;
+            if (mainPass && f == Form::Tail2 && prehits) {
+                const u64 hcap = n * 72 + (u64)nb * FAST_WPB * HITS_CHUNK;
+                Hit* hb = (Hit*)ws_get(d, WS_HITS, hcap * sizeof(Hit));                  // (72 hits per read: 49 GB at 42 M reads -- no room: the reduce phase makes its own lists)
+                if (!hb) (void)hipGetLastError();
+                else {
+                    WS(hbase, u64, WS_PRE_BASE, N + 2); WS(hcnt, u32, WS_RA_CUR, N + 2);
+                    HIPCHK(hipMemsetAsync(hbase, 0xFF, (N + 2) * sizeof(u64), d->stream)); HIPCHK(hipMemsetAsync(hcnt, 0, (N + 2) * sizeof(u32), d->stream));
+                    HIPCHK(hipMemsetAsync(d->d_counters + 4, 0, 2 * sizeof(u64), d->stream));
+                    B.hits = hb; B.hits_cap = hcap; B.hitBase = hbase; B.hitcount = hcnt; armed = true;
+                    d->pre.hits = hb; d->pre.cap = hcap; d->pre.base = hbase;
+                }
+            }
             HIPCHK(hipEventRecord(d->ev[2], d->stream));
-            launch();
+            r.launched = launch_form(d, f, B, nb) || (mainPass && f == Form::Wide && launch_form(d, Form::Clean, B, nb));
             HIPCHK(hipGetLastError());
             HIPCHK(hipEventRecord(d->ev[3], d->stream));
-            u64 c2_[2] = {0, 0}; HIPCHK(hipMemcpyAsync(c2_, d->d_counters + 6, sizeof c2_, hipMemcpyDeviceToHost, d->stream));
-            HIPCHK(hipStreamSynchronize(d->stream)); nslow = c2_[0]; ncap = c2_[1];
-            float ms = 0; hipEventElapsedTime(&ms, d->ev[2], d->ev[3]); kms += ms; d->tm.probe_fast_launches++;
-            if (d->opt.get("SAGE2OV_TIMING")) fprintf(stderr, "[probe] fast kernel launch %.3f ms, listed so far %llu\n", ms, (unsigned long long)nslow);
-            return 0;
-        };
-        // noisy data, and this context probes every read: the hits of the unresolved reads ARE the verified hits of this pass -- written out
-        // now (k_probe_fast<..., 2> with hitBase), filtered by the final statuses in the reduce phase (k_hits_filter)
-        auto arm_prehits = [&](ProbeArgs& P, u64 nr, unsigned nb, bool& armed) -> int {
-            armed = false;
-            if (!(tailKernel == 2 && d->probeShare == 1.0 && lo == 1 && hi == N + 1 && !d->opt.get("SAGE2OV_NO_PREHITS"))) return 0;
-            const u64 hcap = nr * 72 + (u64)nb * FAST_WPB * HITS_CHUNK;
-            Hit* hb = (Hit*)ws_get(d, WS_HITS, hcap * sizeof(Hit));                  // (72 hits per read: 49 GB at 42 M reads -- no room: the reduce phase makes its own lists)
-            if (!hb) { (void)hipGetLastError(); return 0; }
-            WS(hbase, u64, WS_PRE_BASE, N + 2); WS(hcnt, u32, WS_RA_CUR, N + 2);
-            HIPCHK(hipMemsetAsync(hbase, 0xFF, (N + 2) * sizeof(u64), d->stream)); HIPCHK(hipMemsetAsync(hcnt, 0, (N + 2) * sizeof(u32), d->stream));
-            HIPCHK(hipMemsetAsync(d->d_counters + 4, 0, 2 * sizeof(u64), d->stream));
-            P.hits = hb; P.hits_cap = hcap; P.hitBase = hbase; P.hitcount = hcnt; armed = true;
-            d->pre.hits = hb; d->pre.cap = hcap; d->pre.base = hbase;
-            return 0;
-        };
-        auto close_prehits = [&]() -> int {
-            u64 used = 0; HIPCHK(hipMemcpyAsync(&used, d->d_counters + 4, sizeof used, hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
-            d->pre.used = used; d->pre.valid = used <= d->pre.cap;                   // (a chunk beyond the buffer: hits were dropped, the reduce phase makes its own lists)
-            return 0;
-        };
-        if (nsample && nsample < nreads) {
-            ProbeArgs As = A; As.hi = lo + nsample;
-            int rc = timed([&] { const unsigned nbs = plan_fast_grid(d->opt, As, nsample); launched = (seqForm && launch_fast_seq_any(d, As, nbs, 2)) || launch_fast_any<0, 0>(d, As, nbs); }); if (rc) return rc;
-            if (launched) {
-                anyListed = true;
-                // listed for being inconsistent: more than half -> state machine for every read; more than 3 % -> kernel that carries it.  Listed for having more candidates
-                // than slots (high coverage), more than 3 %: the rest runs the WIDE form (256 slots) right away instead of listing a fifth of the reads again
-                const u64 nInc = nslow - std::min(nslow, ncap);
-                tailKernel = nInc * 2 > nsample ? 2 : (nInc * 32 > nsample ? 1 : 0);
-                mainWide = tailKernel == 0 && ncap * 32 > nsample && d->uniL != 0 && !d->opt.get("SAGE2OV_NO_WIDE");
-                ProbeArgs Ar = A; Ar.lo = lo + nsample; const unsigned nb = plan_fast_grid(d->opt, Ar, nreads - nsample, tailKernel == 2);
-                bool armed = false; { int rca = arm_prehits(Ar, nreads - nsample, nb, armed); if (rca) return rca; }
-                rc = timed([&] { if (tailKernel == 2) launch_fast_any<0, 2>(d, Ar, nb); else if (tailKernel == 1) launch_fast_any<0, 1>(d, Ar, nb); else if (!((mainWide && launch_fast_seq_any(d, Ar, nb, 4)) || (seqForm && launch_fast_seq_any(d, Ar, nb, 2)))) launch_fast_any<0, 0>(d, Ar, nb); }); if (rc) return rc;
-                if (armed) { int rca = close_prehits(); if (rca) return rca; }
+            u64 c[2]; { int rc = read_counters(d, 6, 2, c, err); if (rc) return rc; } r.listed = c[0]; r.capped = c[1];
+            float ms = 0; hipEventElapsedTime(&ms, d->ev[2], d->ev[3]); kms += ms; d->tm.probe_fast_launches++;      // (counted even when nothing was launched)
+            if (d->opt.get("SAGE2OV_TIMING")) fprintf(stderr, "[probe] fast kernel launch %.3f ms, listed so far %llu\n", ms, (unsigned long long)r.listed);
+            if (armed && r.launched) {
+                u64 used = 0; { int rc = read_counters(d, 4, 1, &used, err); if (rc) return rc; }
+                d->pre.used = used; d->pre.valid = used <= d->pre.cap;                  // (a chunk beyond the buffer: hits were dropped, the reduce phase makes its own lists)
             }
-        } else {
-            ProbeArgs Aw = A; const unsigned nb = plan_fast_grid(d->opt, Aw, nreads, tailKernel == 2); bool armed = false; { int rca = arm_prehits(Aw, nreads, nb, armed); if (rca) return rca; }
-            int rc = timed([&] { launched = tailKernel == 2 ? launch_fast_any<0, 2>(d, Aw, nb) : (tailKernel == 1 ? launch_fast_any<0, 1>(d, Aw, nb) : ((seqForm && launch_fast_seq_any(d, Aw, nb, 2)) || launch_fast_any<0, 0>(d, Aw, nb))); }); if (rc) return rc;
-            if (armed && launched) { int rca = close_prehits(); if (rca) return rca; }
-        }
-        if (!launched) {                                                       // 32-word layout: sequential kernel only
-            HIPCHK(hipEventRecord(d->ev[2], d->stream));
-            int rc = launch_probe<0>(d, A, err); if (rc) return rc;
-            HIPCHK(hipEventRecord(d->ev[3], d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
-            float ms = 0; hipEventElapsedTime(&ms, d->ev[2], d->ev[3]); kms += ms; nslow = 0;
-        }
-        u32* list = slow;
-        // Reads the 128-slot forms listed, many of them (high coverage: more than 128 candidates; tests/diag/coverage_sweep.py): first the WIDE sequential-groups form
-        // (256 candidate slots, no state machine); what it lists in turn -- inconsistent reads, more than 256 candidates -- goes on as before.
-        const u64 wideMin = d->opt.get("SAGE2OV_PROBE_WIDE_MIN") ? strtoull(d->opt.get("SAGE2OV_PROBE_WIDE_MIN"), nullptr, 10) : 4096;
-        if (launched && anyListed && nslow >= wideMin && tailKernel != 2 && !mainWide && d->uniL && !d->opt.get("SAGE2OV_NO_WIDE")) {
-            WS(slow2, u32, WS_SLOW2, nslow);
-            HIPCHK(hipMemsetAsync(d->d_counters + 6, 0, 2 * sizeof(u64), d->stream));
-            ProbeArgs B = base_args(d); B.ids = slow; B.n_ids = nslow; B.slow = slow2; B.slow_cap = nslow;
-            const u64 nl = nslow; const unsigned nbl = plan_fast_grid(d->opt, B, nl); bool wide = false;
-            int rc = timed([&] { wide = launch_fast_seq_any(d, B, nbl, 4); }); if (rc) return rc;
-            if (wide) {                                                          // (the survivors' list becomes the list: copied back so that the steps below find it where they expect it)
-                if (nslow) HIPCHK(hipMemcpyAsync(slow, slow2, nslow * sizeof(u32), hipMemcpyDeviceToDevice, d->stream));
-            } else nslow = nl;
-        }
-        if (launched && anyListed && nslow) {                                  // listed by the TAIL = 0 kernel: the state machine, in the TAIL = 1 kernel
+            return 0;
+        };
+        // a pass over the listed reads (slow): what it cannot settle in turn is listed in WS_SLOW2
+        u32* list = slow; u64 nslow = 0;
+        auto list_pass = [&](Form f, u32** out, FastPass& r) -> int {
             WS(slow2, u32, WS_SLOW2, nslow);
             HIPCHK(hipMemsetAsync(d->d_counters + 6, 0, 2 * sizeof(u64), d->stream));
             ProbeArgs B = base_args(d); B.ids = slow; B.n_ids = nslow; B.slow = slow2; B.slow_cap = nslow;
 #ifdef SAGE2OV_STAMPS
-            B.stamps = A.stamps;
+            if (f == Form::Tail1) B.stamps = A.stamps;
 #endif
-            const u64 nl = nslow;
-            const unsigned nbl = plan_fast_grid(d->opt, B, nl); int rc = timed([&] { launch_fast_any<0, 1>(d, B, nbl); }); if (rc) return rc;
-            list = slow2;
+            *out = slow2;
+            return pass(f, B, nslow, false, r);
+        };
+        bool launched = false;
+        {
+            FastPass r;
+            if (P.nsample) {
+                ProbeArgs As = A; As.hi = lo + P.nsample;
+                { int rc = pass(Form::Clean, As, P.nsample, false, r); if (rc) return rc; }
+                launched = r.launched;
+                if (launched) {
+                    plan_after_sample(d->opt, d->uniL, P, r.listed, r.capped);
+                    ProbeArgs Ar = A; Ar.lo = lo + P.nsample;
+                    int rc = pass(P.main, Ar, nreads - P.nsample, true, r); if (rc) return rc;
+                }
+            } else {
+                ProbeArgs Aw = A;
+                int rc = pass(P.main, Aw, nreads, true, r); if (rc) return rc;
+                launched = r.launched;
+            }
+            nslow = r.listed;
+        }
+        if (!launched) {                                                       // 32-word layout: no fast form, the sequential kernel for every read
+            HIPCHK(hipEventRecord(d->ev[2], d->stream));
+            int rc = launch_probe<0>(d, A, err); if (rc) return rc;
+            HIPCHK(hipEventRecord(d->ev[3], d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
+            float ms = 0; hipEventElapsedTime(&ms, d->ev[2], d->ev[3]); kms += ms; nslow = 0;
+        } else {
+            if (P.wide && nslow >= P.wideMin) {                                   // many listed: the wide form first; the survivors' list becomes the list
+                u32* slow2 = nullptr; FastPass r; { int rc = list_pass(Form::Wide, &slow2, r); if (rc) return rc; }
+                if (r.launched) { nslow = r.listed; if (nslow) HIPCHK(hipMemcpyAsync(slow, slow2, nslow * sizeof(u32), hipMemcpyDeviceToDevice, d->stream)); }
+            }
+            if (P.listed && nslow) {                                              // the state machine, in the TAIL = 1 form
+                FastPass r; { int rc = list_pass(Form::Tail1, &list, r); if (rc) return rc; }
+                nslow = r.listed;
+            }
         }
         d->tm.probe_kernel_ms += kms; d->tm.probe_launches++;
         d->tm.slow_reads += nslow;
@@ -911,7 +965,7 @@ int dev_probe(Device* d, uint64_t lo, uint64_t hi, std::string& err) {
           fprintf(stderr, "; window reuse: %llu of %llu reads (same minimiser strand as the previous read: %llu), mean shift %.1f\n", (unsigned long long)st[11], (unsigned long long)st[10], (unsigned long long)st[13], st[11] ? (double)st[12] / (double)st[11] : 0.0);
           fprintf(stderr, "[stamps] run mode: %llu reads off the frame, %llu runs ended on a read the general path took; strand changes carried over by mirroring the ring: %llu (refused: %llu -- too far %llu, own entry not in the ring %llu, a window with one read twice %llu), steps: %llu\n", (unsigned long long)st[24], (unsigned long long)st[25], (unsigned long long)st[26], (unsigned long long)st[27], (unsigned long long)st[29], (unsigned long long)st[30], (unsigned long long)st[31], (unsigned long long)st[28]); }
 #endif
-        if (launched && nslow) {                                              // ambiguous / overflowing reads: sequential state machine
+        if (nslow) {                                                          // the end of the cascade: what is still listed, in the sequential state machine
             ProbeArgs B = base_args(d); B.ids = list; B.n_ids = nslow;
             int rc = launch_probe<0>(d, B, err); if (rc) return rc;
         }
@@ -1014,7 +1068,7 @@ int dev_reciprocal(Device* d, uint64_t emit_lo, uint64_t emit_hi, uint64_t* n_ov
     HIPCHK(hipEventRecord(d->ev[4], d->stream));
     if (d->diet && emit_hi > emit_lo) {                                     // the list is sized by a counting pass (capacity 0: nothing is written, the cursor counts)
         hipLaunchKernelGGL(k_recip_emit, dim3(grid_for(emit_hi - emit_lo, 256 * EMIT_PER_THREAD)), dim3(256), 0, d->stream, N, d->readsLoc, d->S, d->uniL, d->right, d->left, d->statusP, d->idOf, (EdgeCand*)nullptr, (u64)0, d->d_counters, (u64)emit_lo, (u64)emit_hi);
-        u64 want = 0; HIPCHK(hipMemcpyAsync(&want, d->d_counters, sizeof want, hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
+        u64 want = 0; { int rc = read_counters(d, 0, 1, &want, err); if (rc) return rc; }
         if (want + 1024 > d->cand_cap || !d->cand) { int rc = cand_resize(d, want + 1024, 0, err); if (rc) return rc; }
         HIPCHK(hipMemsetAsync(d->d_counters, 0, sizeof(u64), d->stream));
     }
@@ -1054,6 +1108,19 @@ int dev_download_status(Device* d, std::vector<uint8_t>& status, std::string& er
     return 0;
 }
 
+// the unresolved reads (status 0), any order, left in WS_IDS: *ids, *n (a second try with the exact count when the first guess of room was short)
+static int collect_unresolved(Device* d, u32** ids, u64* n, std::string& err) {
+    u64 cap = 1 << 20;
+    for (int attempt = 0; attempt < 2; attempt++) {
+        WS(buf, u32, WS_IDS, cap);
+        HIPCHK(hipMemsetAsync(d->d_counters + 5, 0, sizeof(u64), d->stream));
+        hipLaunchKernelGGL(k_red_unresolved, dim3(grid_for(d->N, 256 * UNRES_PER_THREAD)), dim3(256), 0, d->stream, (u64)d->N, d->status, buf, cap, d->d_counters + 5);
+        u64 cnt = 0; { int rc = read_counters(d, 5, 1, &cnt, err); if (rc) return rc; }
+        if (cnt <= cap) { *ids = buf; *n = cnt; return 0; }
+        cap = cnt;
+    }
+    err = "unresolved id collection failed"; return SAGE2OV_ERR_INTERNAL;
+}
 int dev_unresolved_ids(Device* d, std::vector<uint32_t>& ids, std::string& err);
 int dev_unresolved_hits(Device* d, std::vector<Hit>& hits, uint64_t* n_unresolved, std::string& err, std::vector<uint32_t>* ids_out) {
     HIPCHK(hipSetDevice(d->ordinal));
@@ -1070,9 +1137,7 @@ int dev_unresolved_hits(Device* d, std::vector<Hit>& hits, uint64_t* n_unresolve
         { WS(idbuf, u32, WS_IDS, nun); WS(pbuf, u32, WS_SLOW, nun + 1);      // the list dev_unresolved_ids left on the device, as positions: only these reads are probed
           hipLaunchKernelGGL(k_ids_to_pos, dim3(grid_for(nun, 256)), dim3(256), 0, d->stream, idbuf, (u64)nun, d->posOf, pbuf); A.ids = pbuf; A.n_ids = nun; }
         rc = launch_probe<1>(d, A, err); if (rc) return rc;
-        u64 nh = 0;
-        HIPCHK(hipMemcpyAsync(&nh, d->d_counters + 4, sizeof nh, hipMemcpyDeviceToHost, d->stream));
-        HIPCHK(hipStreamSynchronize(d->stream));
+        u64 nh = 0; rc = read_counters(d, 4, 1, &nh, err); if (rc) return rc;
         if (nh <= cap) {
             hits.resize(nh);
             if (nh) HIPCHK(hipMemcpy(hits.data(), dh, nh * sizeof(Hit), hipMemcpyDeviceToHost));
@@ -1085,6 +1150,25 @@ int dev_unresolved_hits(Device* d, std::vector<Hit>& hits, uint64_t* n_unresolve
     err = "hit buffer sizing failed"; return SAGE2OV_ERR_INTERNAL;
 }
 
+// The hit-list pass over A's range or id list (A.hits, A.hitcount set; d_counters[4..6] preset by the caller): the fast kernel's hit-list form, then the exact
+// sequential kernel, appending behind, for the reads it handed over into A.slow -- or for all of A when the layout has no such form.  c[0..2] = d_counters[4..6]
+// after the fast kernel (its cursor in the hit buffer, its count of real hits, the reads it handed over; the caller's preset when there was no fast kernel),
+// *used = d_counters[4] at the end.  A cursor beyond A.hits_cap: the sequential kernel does not run, *used = c[0].
+static int hit_list_pass(Device* d, ProbeArgs& A, unsigned blocks, u64 c[3], u64* used, std::string& err) {
+    if (launch_form(d, Form::Hits, A, blocks)) {
+        HIPCHK(hipGetLastError());
+        { int rc = read_counters(d, 4, 3, c, err); if (rc) return rc; }
+        if (c[0] > A.hits_cap) { *used = c[0]; return 0; }                        // some chunk did not fit
+        if (c[2]) {
+            ProbeArgs B = base_args(d); B.hits = A.hits; B.hits_cap = A.hits_cap; B.hitcount = A.hitcount; B.ids = A.slow; B.n_ids = c[2];
+            int rc = launch_probe<1>(d, B, err); if (rc) return rc;
+        }
+    } else {
+        A.slow = nullptr;
+        int rc = launch_probe<1>(d, A, err); if (rc) return rc;
+    }
+    return read_counters(d, 4, 1, used, err);
+}
 // Reduce phase on the device (see k_ra_mark).  *done = 0 when the preconditions do not hold (long buckets, too few
 // unresolved reads to be worth it, a list longer than RA_CAP, 32-bit offsets exhausted): the caller then runs the
 // serial replay on the host; nothing but the idempotent 0x80 flags has been changed in that case.
@@ -1134,19 +1218,8 @@ int dev_reduce_device(Device* d, uint64_t min_unresolved, uint64_t* n_unresolved
     *done = 0; *inserted = 0; *removed = 0; *n_hits = 0;
     const u64 N = d->N;
     HIPCHK(hipEventRecord(d->ev[0], d->stream));
-    // unresolved reads (status 0), any order
     u32* ids = nullptr; u64 nun = 0;
-    {
-        u64 cap = 1 << 20;
-        for (int attempt = 0; attempt < 2; attempt++) {
-            WS(buf, u32, WS_IDS, cap); ids = buf;
-            HIPCHK(hipMemsetAsync(d->d_counters + 5, 0, sizeof(u64), d->stream));
-            hipLaunchKernelGGL(k_red_unresolved, dim3(grid_for(N, 256 * UNRES_PER_THREAD)), dim3(256), 0, d->stream, (u64)N, d->status, buf, cap, d->d_counters + 5);
-            HIPCHK(hipMemcpyAsync(&nun, d->d_counters + 5, sizeof nun, hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
-            if (nun <= cap) break;
-            cap = nun;
-        }
-    }
+    { int rc = collect_unresolved(d, &ids, &nun, err); if (rc) return rc; }
     *n_unresolved = nun;
     if (nun == 0) { *done = 1; return 0; }
     if (nun < min_unresolved) return 0;
@@ -1183,22 +1256,15 @@ int dev_reduce_device(Device* d, uint64_t min_unresolved, uint64_t* n_unresolved
             WS(noneList, u32, WS_PRE_NONE, N + 2);
             HIPCHK(hipMemsetAsync(d->d_counters + 22, 0, 2 * sizeof(u64), d->stream));
             hipLaunchKernelGGL(k_hits_filter, dim3((unsigned)std::min<u64>((N + 3) / 4, 256ull * 64)), dim3(256), 0, d->stream, dh, d->pre.base, d->status, d->statusP, d->idOf, d->posOf, (u64)N, hitcount, noneList, d->d_counters + 22);
-            u64 fc[2] = {0, 0}; HIPCHK(hipMemcpyAsync(fc, d->d_counters + 22, sizeof fc, hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
+            u64 fc[2] = {0, 0}; { int rc = read_counters(d, 22, 2, fc, err); if (rc) return rc; }
             HIPCHK(hipGetLastError());
             nh = fc[0]; ok = true;
-            if (fc[1]) {                                                              // unresolved reads without written hits: the hit-list kernel over their positions, appending
+            if (fc[1]) {                                                              // unresolved reads without written hits: the hit-list pass over their positions, appending
                 u64 c3[3] = {used, 0, 0}; HIPCHK(hipMemcpyAsync(d->d_counters + 4, c3, sizeof c3, hipMemcpyHostToDevice, d->stream));
                 ProbeArgs A = base_args(d); A.ids = noneList; A.n_ids = fc[1]; A.hits = dh; A.hits_cap = pcap; A.hitcount = hitcount; A.slow = slow; A.slow_cap = N + 1;
-                if (launch_fast_any<1, 0>(d, A, plan_fast_grid(d->opt, A, fc[1], true))) {
-                    HIPCHK(hipGetLastError());
-                    HIPCHK(hipMemcpyAsync(c3, d->d_counters + 4, sizeof c3, hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
-                    if (c3[0] > pcap) ok = false;
-                    else if (c3[2]) { ProbeArgs B = base_args(d); B.hits = dh; B.hits_cap = pcap; B.hitcount = hitcount; B.ids = slow; B.n_ids = c3[2]; int rc = launch_probe<1>(d, B, err); if (rc) return rc; }
-                } else { A.slow = nullptr; int rc = launch_probe<1>(d, A, err); if (rc) return rc; }
-                if (ok) {
-                    u64 used2 = 0; HIPCHK(hipMemcpyAsync(&used2, d->d_counters + 4, sizeof used2, hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
-                    if (used2 > pcap) ok = false; else { nh += c3[1] + (used2 - std::max(c3[0], used)); used = used2; }
-                }
+                const unsigned nb = plan_fast_grid(d->opt, A, fc[1], true);
+                u64 used2 = 0; { int rc = hit_list_pass(d, A, nb, c3, &used2, err); if (rc) return rc; }
+                if (used2 > pcap) ok = false; else { nh += c3[1] + (used2 - std::max(c3[0], used)); used = used2; }
             }
             if (ok) nslots = used;
         }
@@ -1208,22 +1274,9 @@ int dev_reduce_device(Device* d, uint64_t min_unresolved, uint64_t* n_unresolved
             HIPCHK(hipMemsetAsync(hitcount, 0, (N + 2) * sizeof(u32), d->stream));
             ProbeArgs A = base_args(d); A.lo = 1; A.hi = N + 1; A.hits = dh; A.hits_cap = cap; A.hitcount = hitcount;
             A.slow = slow; A.slow_cap = N + 1;                                       // (all positions; the kernel skips what is not status 0)
-            u64 c3[3] = {0, 0, 0};
-            if (launch_fast_any<1, 0>(d, A, blocks)) {
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipMemcpyAsync(c3, d->d_counters + 4, sizeof c3, hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
-                if (c3[0] > cap) { cap = c3[0] + c3[0] / 8 + 1024; continue; }            // some chunk did not fit: everything again
-                if (c3[2]) {                                                                  // handed over: exact sequential kernel, appends behind
-                    ProbeArgs B = base_args(d); B.hits = dh; B.hits_cap = cap; B.hitcount = hitcount; B.ids = slow; B.n_ids = c3[2];
-                    int rc = launch_probe<1>(d, B, err); if (rc) return rc;
-                }
-            } else {
-                A.slow = nullptr;
-                int rc = launch_probe<1>(d, A, err); if (rc) return rc;
-            }
-            u64 used = 0;
-            HIPCHK(hipMemcpyAsync(&used, d->d_counters + 4, sizeof used, hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
-            if (used > cap) { cap = used + used / 8 + 1024; continue; }
+            u64 c3[3] = {0, 0, 0}, used = 0;
+            { int rc = hit_list_pass(d, A, blocks, c3, &used, err); if (rc) return rc; }
+            if (used > cap) { cap = used + used / 8 + 1024; continue; }                  // some chunk or the appended hits did not fit: everything again
             nslots = used; nh = c3[1] + (used - c3[0]); ok = true;                           // real hits: fast kernel's count + what the sequential kernel appended
         }
         if (!ok) { err = "hit buffer sizing failed"; return SAGE2OV_ERR_INTERNAL; }
@@ -1330,7 +1383,7 @@ int dev_reduce_device(Device* d, uint64_t min_unresolved, uint64_t* n_unresolved
     if (nc) hipLaunchKernelGGL(k_ra_fill_c, dim3(grid_for(nc, 256)), dim3(256), 0, d->stream, d->cand, (u64)nc, d->reads, d->S, d->uniL, offs, cur, ent, ent32);
     if (ranked) { if (nslots) hipLaunchKernelGGL(k_rr_fill_h, dim3(grid_for(nslots, 256)), dim3(256), 0, d->stream, dh, (u64)nslots, rankDev, d->reads, d->S, d->uniL, offs, cur, ent, ent32); }
     else if (nslots) hipLaunchKernelGGL(k_ra_fill_h, dim3(grid_for(nslots, 256)), dim3(256), 0, d->stream, dh, (u64)nslots, offs, deg, hitcount, ent, ent32);
-    if (ranked) { u64 c3[3]; HIPCHK(hipMemcpyAsync(c3, d->d_counters + 8, sizeof c3, hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream)); present = c3[2]; }
+    if (ranked) { u64 c3[3]; int rc = read_counters(d, 8, 3, c3, err); if (rc) return rc; present = c3[2]; }
     HIPCHK(hipMemsetAsync(d->d_counters + 8, 0, 5 * sizeof(u64), d->stream));
     // this rank's share of the unresolved reads: entries [wlo, whi) of the list (any contiguous cut is exact: a read's marks depend on the lists only)
     const u64 wlo = shareWorld > 1 ? nun * shareRank / shareWorld : 0, whi = shareWorld > 1 ? nun * (shareRank + 1) / shareWorld : nun;
@@ -1348,7 +1401,7 @@ int dev_reduce_device(Device* d, uint64_t min_unresolved, uint64_t* n_unresolved
     hipLaunchKernelGGL((k_ra_mark<RA_CAP, 10, 128, true>), dim3(gb), dim3(256), 0, d->stream, ids, (u64)nun, offs, deg, ent, ent32, rm, svn, d->d_counters + 8, heavy, heavyCap, noShortcut, mid);   // 129 .. RA_CAP (the reads the first launch listed); longer: k_ra_mark_big
     }
     u64 c[4];
-    HIPCHK(hipMemcpyAsync(c, d->d_counters + 8, sizeof c, hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
+    { int rc = read_counters(d, 8, 4, c, err); if (rc) return rc; }
     HIPCHK(hipGetLastError());
     if (timing) fprintf(stderr, "[reduce/device] marks of %llu of %llu reads by the short cut (k_ra_mark: ra_shortcut), %.2f lists read per read\n", (unsigned long long)c[3], (unsigned long long)nun, nun ? (double)c[2] / (double)nun : 0.0);
     if (c[0] > heavyCap) { if (shareWorld > 1) { err = "reduce: too many oversized lists in this rank's share"; return SAGE2OV_ERR_LIMIT; } return 0; }   // (never seen) that many oversized lists: serial replay (a rank of many cannot decide that alone)
@@ -1407,7 +1460,7 @@ int dev_collect_reduce_edges(Device* d, const std::vector<uint32_t>& unresolved,
         HIPCHK(hipMemsetAsync(d->d_counters + 5, 0, sizeof(u64), d->stream));
         hipLaunchKernelGGL(k_red_collect_few, dim3(blocks), dim3(256), 0, d->stream, d->cand, (u64)n, dNeed, (u32)need.size(), dIds, nUn, buf, cap, d->d_counters + 5);
         HIPCHK(hipGetLastError());
-        u64 cnt = 0; HIPCHK(hipMemcpyAsync(&cnt, d->d_counters + 5, sizeof cnt, hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
+        u64 cnt = 0; { int rc = read_counters(d, 5, 1, &cnt, err); if (rc) return rc; }
         if (cnt <= cap) {                                                  // (else: the general form below -- the 0x80 flags are idempotent)
             out.resize(cnt); if (cnt) HIPCHK(hipMemcpy(out.data(), buf, cnt * sizeof(EdgeCand), hipMemcpyDeviceToHost));
             return 0;
@@ -1418,7 +1471,7 @@ int dev_collect_reduce_edges(Device* d, const std::vector<uint32_t>& unresolved,
     // first a dry count (cap 0 keeps the flagging idempotent), then the real collection
     HIPCHK(hipMemsetAsync(d->d_counters + 5, 0, sizeof(u64), d->stream));
     hipLaunchKernelGGL(k_red_collect, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, d->cand, (u64)n, d->status, need, (EdgeCand*)nullptr, (u64)0, d->d_counters + 5);
-    u64 cnt = 0; HIPCHK(hipMemcpyAsync(&cnt, d->d_counters + 5, sizeof cnt, hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
+    u64 cnt = 0; { int rc = read_counters(d, 5, 1, &cnt, err); if (rc) return rc; }
     if (cnt) {
         cap = cnt; { WS(nb_, EdgeCand, WS_NEAR, cap); buf = nb_; }
         HIPCHK(hipMemsetAsync(d->d_counters + 5, 0, sizeof(u64), d->stream));
@@ -1429,18 +1482,13 @@ int dev_collect_reduce_edges(Device* d, const std::vector<uint32_t>& unresolved,
     }
     return 0;
 }
-int dev_unresolved_ids(Device* d, std::vector<uint32_t>& ids, std::string& err) {
+int dev_unresolved_ids(Device* d, std::vector<uint32_t>& ids, std::string& err) {      // (the list stays in WS_IDS: dev_unresolved_hits probes it)
     HIPCHK(hipSetDevice(d->ordinal));
-    ids.clear(); u64 cap = 1 << 20; 
-    for (int attempt = 0; attempt < 2; attempt++) {
-        WS(buf, u32, WS_IDS, cap);
-        HIPCHK(hipMemsetAsync(d->d_counters + 5, 0, sizeof(u64), d->stream));
-        hipLaunchKernelGGL(k_red_unresolved, dim3(grid_for(d->N, 256 * UNRES_PER_THREAD)), dim3(256), 0, d->stream, (u64)d->N, d->status, buf, cap, d->d_counters + 5);
-        u64 cnt = 0; HIPCHK(hipMemcpyAsync(&cnt, d->d_counters + 5, sizeof cnt, hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
-        if (cnt <= cap) { ids.resize(cnt); if (cnt) HIPCHK(hipMemcpy(ids.data(), buf, cnt * sizeof(u32), hipMemcpyDeviceToHost)); std::sort(ids.begin(), ids.end()); return 0; }
-        cap = cnt;
-    }
-    err = "unresolved id collection failed"; return SAGE2OV_ERR_INTERNAL;
+    ids.clear();
+    u32* buf = nullptr; u64 cnt = 0; { int rc = collect_unresolved(d, &buf, &cnt, err); if (rc) return rc; }
+    ids.resize(cnt); if (cnt) HIPCHK(hipMemcpy(ids.data(), buf, cnt * sizeof(u32), hipMemcpyDeviceToHost));
+    std::sort(ids.begin(), ids.end());
+    return 0;
 }
 
 int dev_meminfo(Device* d, uint64_t* out4, std::string& err) {
@@ -1484,7 +1532,7 @@ int dev_debug_all_hits(Device* d, std::vector<Hit>& hits, std::string& err) {
     ProbeArgs A = base_args(d); A.lo = 1; A.hi = N + 1; A.hits = dh; A.hits_cap = cap;
     int rc = refresh_status_by_pos(d, err); if (!rc) rc = launch_probe<1>(d, A, err);
     u64 nh = 0;
-    if (!rc) { HIPCHK(hipMemcpyAsync(&nh, d->d_counters + 4, sizeof nh, hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream)); }
+    if (!rc) { int rcr = read_counters(d, 4, 1, &nh, err); if (rcr) return rcr; }
     if (!rc && nh > cap) { err = "debug hit buffer too small"; rc = SAGE2OV_ERR_LIMIT; }
     if (!rc) { hits.resize(nh); if (nh) HIPCHK(hipMemcpy(hits.data(), dh, nh * sizeof(Hit), hipMemcpyDeviceToHost)); }
     HIPCHK(hipMemcpyAsync(d->status, saved, N + 1, hipMemcpyDeviceToDevice, d->stream));
