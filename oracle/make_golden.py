@@ -41,8 +41,18 @@ FIXTURES = {
                                        n_repeat_families=6, repeat_copies=250, repeat_len=350)),
     # reads of 520..900 bases with errors: the 32-word slot layout (505 .. 1018 bases, 11-bit length field), sequential probe kernel only
     "g10_long900_k55":   (55, 8, dict(seed=10, genome_len=150000, n_reads=16000, read_len=900, read_len_min=520, err_ppm=800)),
+    # reads of 260..300 bases with errors and a few repeats: the 16-word slot layout (252 .. 504 bases), fast kernel with 20-dword compares.  One reference thread, like g5:
+    # many reads here are contained AND pass the connection limit, and with several threads the reference's log counter of the former depends on which of its threads
+    # writes such a read's status last (economyGraph.cpp:444 against :735; 5732 with 8 threads where one thread counts 5715) -- the files do not
+    "g13_noisy300_k55":  (55, 1, dict(seed=13, genome_len=70000, n_reads=15000, read_len=300, read_len_min=260, err_ppm=1200,
+                                      n_repeat_families=2, repeat_copies=5, repeat_len=450)),
     # hand-made input (tests/fixtures.py::recipe_reads): palindromic region, tandem repeat, mirrored duplicates
     "g7_palindrome_tandem_k21": (21, 8, dict(recipe="palindrome_tandem", seed=7, half=700, flank=24000, tandem_units=60, read_len=100, step=3)),
+    # three reads given 65 535, 65 536 and 65 537 times in a tiling of 13 000: the reference's uint16_t frequency (readLoader.cpp:232) wraps to 65 535, 0 and 1 in P.reads
+    "g11_freqwrap_k21": (21, 8, dict(recipe="heavy_duplicates", seed=11, n_unique=13000, read_len=100, step=7)),
+    # poly-A / poly-T, (AT)n and microsatellites of period 2, 3 and 6, each longer than a read, between random flanks: homopolymer keys, reads equal to their own
+    # reverse complement, one key at many windows of one read, long buckets
+    "g12_lowcomplexity_k21": (21, 8, dict(recipe="low_complexity", seed=12, read_len=100, block=200, flank=4500, step=2)),
 }
 
 def md5(path):

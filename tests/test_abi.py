@@ -294,3 +294,38 @@ def test_step4_needs_the_gpu():
             call()
         assert ei.value.code == -3
     ctx.close()
+
+
+@pytest.mark.parametrize("top,words_per_read", [(123, 4), (251, 8), (504, 16), (1018, 32)])
+def test_word_image_hand_over_round_trip(top, words_per_read, tmp_path):
+    """sage2ov_reads_export_words -> sage2ov_reads_import_words on a fresh context (how the ranks above 0 of `sage2ov -G n` and of bench.py --gpus n get their
+    reads): the importer rebuilds the lengths from each slot's last word -- 9 bits, 11 in the 32-word layout -- so every layout is run with its longest read
+    present (bases and length share the last word there), next to the shortest legal reads and a frequency above 255.  Packed bytes, lengths and frequencies of
+    the importer must equal the exporter's, its P.reads must be the same file, and a second hand-over from the importer must give the same image."""
+    k = 21
+    bases, off = fx.make_reads(dict(recipe="short_reads", seed=500 + top, k=k, top=top, step=11, n_reads=900))
+    seqs = [bytes(bases[int(off[i]):int(off[i + 1])]) for i in range(len(off) - 1)]
+    seqs += [seqs[2]] * 299 + [b"T" * top, b"A" * (k + 1)]                           # a frequency of 300; all-ones bases up to the length field; the shortest read
+    flat = np.frombuffer(b"".join(seqs), dtype=np.uint8).copy()
+    o2 = np.zeros(len(seqs) + 1, dtype=np.uint64); o2[1:] = np.cumsum([len(s) for s in seqs])
+    a = s2.Context(k, device=-2); a.reads_add_ascii(flat, o2); a.reads_organize()
+    st = a.reads_stats()
+    assert (st.words_per_read, st.max_read_length) == (words_per_read, top)
+    words, freq = a.reads_export_words()
+    assert words.size == (st.unique_reads + 1) * words_per_read
+    b = s2.Context(k, device=-2)
+    b.reads_import_words(words, st.unique_reads, st.words_per_read, st.max_read_length, freq, st.good_reads, st.total_bp)
+    sb = b.reads_stats()
+    assert (sb.unique_reads, sb.words_per_read, sb.max_read_length, sb.good_reads, sb.total_bp) == (st.unique_reads, st.words_per_read, st.max_read_length, st.good_reads, st.total_bp)
+    (pa, la, fa), (pb, lb, fb) = a.reads_export(), b.reads_export()
+    assert int(la.max()) == top and int((la == top).sum()) >= 300 and int(la[1:].min()) == k + 1 and int(fa.max()) == 300
+    assert np.array_equal(la, lb) and np.array_equal(fa, fb) and np.array_equal(pa, pb)
+    ra, rb = str(tmp_path / "a.reads"), str(tmp_path / "b.reads")
+    a.reads_save(ra); b.reads_save(rb)
+    assert fx.md5_file(ra) == fx.md5_file(rb)
+    w2, f2 = b.reads_export_words()
+    assert np.array_equal(w2, words) and np.array_equal(f2, freq)
+    # the lengths read straight out of the image, the way the importer has to: the layout's own mask
+    last = words.reshape(-1, words_per_read)[:, -1]
+    assert np.array_equal((last & np.uint64(0x7FF if words_per_read == 32 else 0x1FF)).astype(np.uint16)[1:], la[1:])
+    a.close(); b.close()

@@ -11,7 +11,8 @@ pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("minimiser_groups_on")]  
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.mark.parametrize("name,world", [("g5_mixedlen_k21", 2), ("g5_mixedlen_k21", 3), ("g3_noisy_rep_k21", 2), ("g4_highcopy_k21", 3)])
+@pytest.mark.parametrize("name,world", [("g5_mixedlen_k21", 2), ("g5_mixedlen_k21", 3), ("g3_noisy_rep_k21", 2), ("g4_highcopy_k21", 3),
+                                        ("g10_long900_k55", 2)])                # (900-base reads: the 32-word layout, sequential probe kernel only)
 def test_run_steps23_sharded_matches_reference(name, world, tmp_path):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
@@ -66,11 +67,14 @@ def test_bench_starts_its_own_ranks_without_a_launcher():
 
 
 @pytest.mark.parametrize("name,gpus,flags", [("g5_mixedlen_k21", 2, ["--share-gpu"]), ("g3_noisy_rep_k21", 3, ["--share-gpu"]), ("g4_highcopy_k21", 2, ["--share-gpu"]),
-                                             ("g2_clean150_k40", 1, ["--force-multi"]), ("g3_noisy_rep_k21", 1, ["--force-multi"])])
+                                             ("g2_clean150_k40", 1, ["--force-multi"]), ("g3_noisy_rep_k21", 1, ["--force-multi"]),
+                                             ("g10_long900_k55", 2, ["--share-gpu"])])      # (32-word layout: the importing rank rebuilds lengths from an 11-bit field)
 def test_cli_multi_gpu_mode_writes_reference_files(name, gpus, flags, tmp_path):
     """`sage2ov --gpus G`: the C++ host driver of the multi-GPU path (sage2_amd/csrc/sage2ov_multi.cpp: one thread and one context per rank, the four
     exchanges).  With --share-gpu all ranks run on the one GPU of the test box and exchange by device copies; with --force-multi one rank goes through
-    RCCL itself (ncclCommInitAll, ncclAllGather, ncclAllReduce).  P.reads and P.graph3 must be the reference's files either way."""
+    RCCL itself (ncclCommInitAll, ncclAllGather, ncclAllReduce).  P.reads and P.graph3 must be the reference's files either way.  Only rank 0 writes files; the
+    ranks above it get their reads as a word image (sage2ov_reads_export_words / _import_words), so the same hand-over is repeated here on a context of rank 1 and
+    the P.reads written from THAT context must be the reference's too (the lengths of an importing rank come out of the slots' last words)."""
     import fixtures as fx, sage2_amd as s2
     m = fx.golden(name)
     fa = str(tmp_path / "x.fa"); s2.synth_write_fasta(fx.synth_params(m["synth"]), fa)
@@ -86,6 +90,17 @@ def test_cli_multi_gpu_mode_writes_reference_files(name, gpus, flags, tmp_path):
     for key, lab in (("contained_extension", "Total contained by extension"), ("transitive_removed", "Transitive edge removed")):
         if key in m["counters"]:
             assert f"{lab}: {m['counters'][key]}" in log
+    if gpus > 1:                                                      # an importing rank's context, as the CLI makes it (sage2ov_cli.cpp)
+        bases, off = fx.make_reads(m["synth"])
+        c0 = s2.Context(m["k"], device=0, rank=0, world=gpus); c0.reads_add_ascii(bases, off); c0.reads_organize()
+        st = c0.reads_stats(); words, freq = c0.reads_export_words()
+        c1 = s2.Context(m["k"], device=0, rank=1, world=gpus)
+        c1.reads_import_words(words, st.unique_reads, st.words_per_read, st.max_read_length, freq, st.good_reads, st.total_bp)
+        rp = str(tmp_path / "rank1.reads"); c1.reads_save(rp)
+        assert fx.md5_file(rp) == m["reads_md5"]
+        for a, b in zip(c0.reads_export(), c1.reads_export()):
+            assert (a == b).all()
+        c0.close(); c1.close()
 
 
 @pytest.mark.parametrize("gpus,flags,fail_rank", [(3, ["--share-gpu"], 1), (2, ["--share-gpu"], 0), (1, ["--force-multi"], 0)])

@@ -220,7 +220,10 @@ class _Hip:
 
 
 @pytest.mark.parametrize("name,world,device_reduce", [("g2_clean150_k40", 2, False), ("g5_mixedlen_k21", 3, False), ("g3_noisy_rep_k21", 2, False), ("g4_highcopy_k21", 2, False),
-                                                      ("g3_noisy_rep_k21", 3, True), ("g4_highcopy_k21", 3, True), ("g9_repeats160k_k40", 2, True), ("g5_mixedlen_k21", 2, True)])
+                                                      ("g3_noisy_rep_k21", 3, True), ("g4_highcopy_k21", 3, True), ("g9_repeats160k_k40", 2, True), ("g5_mixedlen_k21", 2, True),
+                                                      # the long layouts: 8 words with 16-dword compares (250 bases), 16 words (300 bases), 32 words and the sequential-only path (900 bases)
+                                                      ("g8_noisy250_k45", 2, False), ("g8_noisy250_k45", 3, True), ("g13_noisy300_k55", 3, False), ("g13_noisy300_k55", 2, True),
+                                                      ("g10_long900_k55", 2, False), ("g10_long900_k55", 3, True)])
 def test_sharded_contexts_on_one_gpu_match_reference(name, world, device_reduce, tmp_path, monkeypatch):
     if device_reduce:                                                  # the device forms of the reduce phase (symmetric / ranked), their marks sharded over the ranks
         monkeypatch.setenv("SAGE2OV_DEVICE_REDUCE_MIN", "1")
@@ -846,8 +849,37 @@ def test_table_beyond_2_to_32_slots(monkeypatch):
     g.close(); o.close()
 
 
+PROBE_KERNEL_MODES = ["sample", "tail0", "tail1", "tail2", "tail2_own_hit_lists"]
+
+
+def force_probe_kernel(mode, monkeypatch):
+    """the switches of test_probe_kernel_choice_is_exact (shared with tests/test_gpu_edges.py)"""
+    if mode == "sample":
+        monkeypatch.setenv("SAGE2OV_PROBE_SAMPLE_MIN", "2048")
+    else:
+        monkeypatch.setenv("SAGE2OV_PROBE_TAIL", "2" if mode.startswith("tail2") else mode[-1])
+        if mode == "tail2_own_hit_lists":                                            # TAIL = 2 writes its hits out for the reduce phase: here the reduce phase makes its own
+            monkeypatch.setenv("SAGE2OV_NO_PREHITS", "1")
+
+
+GROUPS_FORM_MODES = ["wide_pass", "sequential_form", "both", "standard_form", "sampled_route"]
+
+
+def force_groups_form(mode, monkeypatch):
+    """the switches of test_sequential_groups_form_and_wide_pass_are_exact (shared with tests/test_gpu_edges.py)"""
+    if mode in ("wide_pass", "both"):
+        monkeypatch.setenv("SAGE2OV_PROBE_WIDE_MIN", "1")
+    elif mode != "sampled_route":
+        monkeypatch.setenv("SAGE2OV_NO_WIDE", "1")
+    monkeypatch.setenv("SAGE2OV_PROBE_SEQ", "1" if mode in ("sequential_form", "both", "sampled_route") else "0")   # (0: the standard form, both groups in flight together)
+    if mode == "sampled_route":                                                     # the host's own route: a sample counts the reads with too many candidates and picks the wide form for the rest
+        monkeypatch.setenv("SAGE2OV_PROBE_SAMPLE_MIN", "1024"); monkeypatch.setenv("SAGE2OV_PROBE_WIDE_MIN", "1")
+    else:
+        monkeypatch.setenv("SAGE2OV_PROBE_TAIL", "0")                               # (the form that lists what it cannot settle: the wide pass works on that list)
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("mode", ["sample", "tail0", "tail1", "tail2", "tail2_own_hit_lists"])
+@pytest.mark.parametrize("mode", PROBE_KERNEL_MODES)
 @pytest.mark.parametrize("pd,k", [
     (dict(seed=71, genome_len=60000, n_reads=20000, read_len=150, err_ppm=0), 40),                          # clean: the sample keeps the kernel without the state machine
     (dict(seed=72, genome_len=60000, n_reads=20000, read_len=150, err_ppm=1500), 40),                       # noisy: the sample switches to the kernel with it
@@ -860,12 +892,7 @@ def test_probe_kernel_choice_is_exact(pd, k, mode, monkeypatch):
     reads (TAIL = 0) from a sample of the range; listed reads go through the TAIL = 1 kernel as an id list, its leftovers through the
     sequential kernel; TAIL = 2 sends every read through the state machine.  Every route gives the oracle's records: the sampled route
     (forced on a small input), and each kernel alone."""
-    if mode == "sample":
-        monkeypatch.setenv("SAGE2OV_PROBE_SAMPLE_MIN", "2048")
-    else:
-        monkeypatch.setenv("SAGE2OV_PROBE_TAIL", "2" if mode.startswith("tail2") else mode[-1])
-        if mode == "tail2_own_hit_lists":                                            # TAIL = 2 writes its hits out for the reduce phase: here the reduce phase makes its own
-            monkeypatch.setenv("SAGE2OV_NO_PREHITS", "1")
+    force_probe_kernel(mode, monkeypatch)
     bases, off = fx.make_reads(pd)
     m = dict(k=k)
     g, o = run_gpu(m, bases, off), run_oracle(m, bases, off)
@@ -917,7 +944,7 @@ def test_tapered_grid_of_the_fast_kernel_is_exact(pd, k, phase_blocks, chunk_shi
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("mode", ["wide_pass", "sequential_form", "both", "standard_form", "sampled_route"])
+@pytest.mark.parametrize("mode", GROUPS_FORM_MODES)
 @pytest.mark.parametrize("pd,k", [
     (dict(seed=91, genome_len=16000, n_reads=16000, read_len=150, err_ppm=0), 40),       # 150x: most reads have 129 .. 256 candidates
     (dict(seed=92, genome_len=9000, n_reads=14000, read_len=100, err_ppm=0), 31),        # 155x of 100-base reads (4-word layout)
@@ -928,15 +955,7 @@ def test_sequential_groups_form_and_wide_pass_are_exact(pd, k, mode, monkeypatch
     """The clean-data probe kernel has a form that gathers and compares its 64-slot candidate groups one after the other (k_probe_fast<..., UNI, QN, SEQ>): with two
     groups it replaces the standard form (SAGE2OV_PROBE_SEQ), with four it takes the reads of high-coverage data that the 128-slot forms list (more than 128 candidates)
     before anything goes to the state machine or the sequential kernel.  Same records, counters and edges as the oracle either way."""
-    if mode in ("wide_pass", "both"):
-        monkeypatch.setenv("SAGE2OV_PROBE_WIDE_MIN", "1")
-    elif mode != "sampled_route":
-        monkeypatch.setenv("SAGE2OV_NO_WIDE", "1")
-    monkeypatch.setenv("SAGE2OV_PROBE_SEQ", "1" if mode in ("sequential_form", "both", "sampled_route") else "0")   # (0: the standard form, both groups in flight together)
-    if mode == "sampled_route":                                                     # the host's own route: a sample counts the reads with too many candidates and picks the wide form for the rest
-        monkeypatch.setenv("SAGE2OV_PROBE_SAMPLE_MIN", "1024"); monkeypatch.setenv("SAGE2OV_PROBE_WIDE_MIN", "1")
-    else:
-        monkeypatch.setenv("SAGE2OV_PROBE_TAIL", "0")                               # (the form that lists what it cannot settle: the wide pass works on that list)
+    force_groups_form(mode, monkeypatch)
     bases, off = fx.make_reads(pd)
     m = dict(k=k)
     g, o = run_gpu(m, bases, off), run_oracle(m, bases, off)
