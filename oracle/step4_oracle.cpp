@@ -35,6 +35,7 @@ struct Edge {
 struct Graph {
     uint64_t N = 0; std::string header[3];
     std::vector<Edge> pool; std::vector<int> head;                                   // head[i]: newest edge of node i, -1 if none
+    unsigned long long* ex = nullptr;                                                // branch counters (orc4_run_files_ex), layout at the entry point
 
     int new_edge() { pool.emplace_back(); Edge& e = pool.back(); e.next = e.prev = e.twin = -1; e.alive = true; return (int)pool.size() - 1; }
     // overlapGraph.cpp:191-204 insertIntoList: at the head
@@ -113,13 +114,13 @@ struct Graph {
             if (head[i] < 0) continue;
             int in = 0, out = 0; bool keep = false;
             for (int v = head[i]; v >= 0; v = pool[v].next) {
-                if ((int64_t)pool[v].reads.size() > threshold) { keep = true; break; }       // :77-85 a composite edge with more than `threshold` reads
-                if (pool[v].from == pool[v].to) { keep = true; break; }                      // :86-91 a loop
+                if ((int64_t)pool[v].reads.size() > threshold) { keep = true; if (ex && pool[v].reads.size() <= 3) ex[5]++; break; }   // :77-85 a composite edge with more than `threshold` reads
+                if (pool[v].from == pool[v].to) { keep = true; if (ex) ex[4]++; break; }     // :86-91 a loop
                 if (pool[v].type == 0 || pool[v].type == 1) in++; else out++;
             }
             if (!keep && ((in == 0 && out > 0) || (in > 0 && out == 0))) {
                 for (int v = head[i], nx; v >= 0; v = nx) { nx = pool[v].next; unlink(pool[v].twin); unlink(v); }
-                deleted++;
+                deleted++; if (ex) ex[threshold < 3 ? threshold : 3]++;
             }
         }
         return deleted;
@@ -140,6 +141,15 @@ struct Graph {
                 if (pool[v].to != b) continue;
                 const int64_t d2 = pool[v].len;
                 const int64_t n1 = 1 + (int64_t)pool[inE].reads.size() + (int64_t)pool[outE].reads.size(), n2 = (int64_t)pool[v].reads.size();
+                if (ex) {                                                                    // counted before anything is unlinked
+                    const int tier = closeLength >= 50 ? 4 : (int)(closeLength / 10) - 1; int same = 0;
+                    for (int w = head[a]; w >= 0; w = pool[w].next) same += pool[w].to == b;
+                    ex[6]++; if (same > 1) ex[7]++;
+                    if (llabs(d1 - d2) >= closeLength) ex[21]++;
+                    else if (n1 < n2 / 2) { ex[8]++; ex[10 + tier]++; }
+                    else if (n2 < n1 / 2) { ex[9]++; ex[15 + tier]++; }
+                    else ex[20]++;
+                }
                 if (llabs(d1 - d2) < closeLength) {
                     if (n1 < n2 / 2) { unlink(pool[inE].twin); unlink(inE); unlink(pool[outE].twin); unlink(outE); deleted++; }
                     if (n2 < n1 / 2) { unlink(pool[v].twin); unlink(v); deleted++; }
@@ -199,8 +209,8 @@ struct Graph {
 extern "C" {
 // main.cpp:150-172: contract, dead ends (0), bubbles (10), contract; then dead ends / bubbles / contract with growing thresholds until nothing changes.
 // counters: [0] N, [1] loop iterations, [2] nodes contracted, [3] dead ends + bubbles removed, [4] surviving directed edges
-int orc4_run_files(const char* graph3_path, unsigned long long n_unique, const char* graph4_path, unsigned long long* counters) {
-    Graph g; g.N = n_unique;
+static int run_files(const char* graph3_path, unsigned long long n_unique, const char* graph4_path, unsigned long long* counters, unsigned long long* ex) {
+    Graph g; g.N = n_unique; g.ex = ex;
     if (!g.load(graph3_path)) return -1;
     int threshold = 0, closeValue = 10; unsigned long long contracted = 0, removed = 0, iters = 0;
     contracted += g.contract(); removed += g.dead_ends(threshold); removed += g.bubbles(closeValue); contracted += g.contract();
@@ -214,5 +224,15 @@ int orc4_run_files(const char* graph3_path, unsigned long long n_unique, const c
     if (graph4_path && !g.save(graph4_path)) return -2;
     if (counters) { counters[0] = g.N; counters[1] = iters; counters[2] = contracted; counters[3] = removed; unsigned long long alive = 0; for (const Edge& e : g.pool) alive += e.alive; counters[4] = alive; }
     return 0;
+}
+int orc4_run_files(const char* graph3_path, unsigned long long n_unique, const char* graph4_path, unsigned long long* counters) { return run_files(graph3_path, n_unique, graph4_path, counters, nullptr); }
+// the same run, and which branches of the two removal sweeps it took -- ex[0..ORC4_EX): [0..3] nodes removed by dead_ends at threshold 0..3,
+// [4] nodes kept by the loop test, [5] nodes kept by an edge of 1..3 reads that exceeds the threshold, [6] bubble candidates (one in, one out,
+// an edge a -> b exists), [7] candidates with more than one edge a -> b, [8] candidates whose own two edges went (n1 < n2/2), [9] whose edge
+// a -> b went (n2 < n1/2), [10..14] and [15..19] the same two per closeLength 10, 20, 30, 40, 50, [20] close but neither side light enough,
+// [21] too far apart.  Counted per visit: a node that is judged again in a later sweep counts again.
+int orc4_run_files_ex(const char* graph3_path, unsigned long long n_unique, const char* graph4_path, unsigned long long* counters, unsigned long long* ex) {
+    if (ex) memset(ex, 0, 22 * sizeof *ex);
+    return run_files(graph3_path, n_unique, graph4_path, counters, ex);
 }
 }

@@ -140,14 +140,19 @@ def test_plain_jumping_path_equals_splitter_ranking(monkeypatch, tmp_path):
     assert outs["plain"] == want, _first_diff(outs["plain"], want)
 
 
-def _run_imported(N, e, tmp_path, tag):
+def _run_imported(N, e, tmp_path, tag, again=False):
     rng = np.random.default_rng(N); reads = set()
     while len(reads) < N:
         reads.add("".join(rng.choice(list("ACGT"), size=60)))
     bases = np.frombuffer("".join(sorted(reads)).encode(), dtype=np.uint8).copy(); off = np.arange(0, (N + 1) * 60, 60, dtype=np.uint64)
     ctx = s2.Context(40); ctx.reads_add_ascii(bases, off); ctx.reads_organize(); ctx.edges_import(e)
     g3 = str(tmp_path / f"{tag}.graph3"); ctx.graph_save(g3)
-    ctx.graph_simplify(); st = ctx.simplify_stats(); out = str(tmp_path / f"{tag}.graph4"); ctx.graph4_save(out); ctx.close()
+    ctx.graph_simplify(); st = ctx.simplify_stats(); out = str(tmp_path / f"{tag}.graph4"); ctx.graph4_save(out)
+    if again:                                                  # the same context once more: nothing a run keeps on the device may leak into the next
+        ctx.graph_simplify(); st2 = ctx.simplify_stats(); out2 = str(tmp_path / f"{tag}.again4"); ctx.graph4_save(out2)
+        assert (st2.nodes_contracted, st2.removed, st2.loop_iterations) == (st.nodes_contracted, st.removed, st.loop_iterations)
+        assert open(out2, "rb").read() == open(out, "rb").read()
+    ctx.close()
     c = (ctypes.c_ulonglong * 5)(); ref = str(tmp_path / f"{tag}.ref4")
     assert _oracle4().orc4_run_files(g3.encode(), N, ref.encode(), c) == 0
     got, want = open(out, "rb").read(), open(ref, "rb").read()
@@ -263,3 +268,44 @@ def test_cli_end_to_end_fastq_250bp_against_both_oracles(tmp_path):
     assert _oracle4().orc4_run_files(str(tmp_path / "o.graph3").encode(), n, ref.encode(), c) == 0
     got, want = open(os.path.join(out, "t.graph4"), "rb").read(), open(ref, "rb").read()
     assert got == want, _first_diff(got, want)
+
+
+# ---- graphs built to reach the branches of the dead-end and bubble sweeps (tests/graphgen.py, the directed families).  That they do reach
+# them is asserted without a device, on the restatement's branch counters, in tests/test_step4_oracle.py; the same builders are used here.
+@pytest.mark.parametrize("name", ["B", "BL", "BM", "BC", "D", "DC", "TB", "TL"])
+@pytest.mark.parametrize("seed", [0, 1])
+def test_directed_family(name, seed, tmp_path):
+    """B: both bubble sides around n1 < n2/2 and n2 < n1/2 with odd and even counts; BL: one bubble per length difference 0, 9, 10, ..., 50,
+    51, each leaving at the closeLength that first admits it; BM: several edges a -> b, the first seen decides, also after a lower id
+    took the first away in the same sweep; BC: bubble nodes that become candidates by the decision before them; D: tips of 0..4 reads
+    against thresholds 0..3, nodes only a loop keeps; DC: a 300-node spine that falls in one sweep (300 rounds of the fixed point) and one
+    that loses a node per loop iteration (300 iterations); TB, TL: B and BL with the two lengths of every pair unequal, so that a length read
+    from the other half of a pair changes the tier.  Seed 0 lays the instances out in sequence, seed 1 interleaved (the order inside an
+    instance stays)."""
+    import graphgen as gg
+    N, e = gg.compose([name], seed, interleave=bool(seed))
+    st = _run_imported(N, e, tmp_path, name)
+    assert st.loop_iterations == {"B": 1, "BL": 6, "BM": 1, "BC": 4, "D": 5, "DC": 300, "TB": 1, "TL": 6}[name]
+
+
+@pytest.fixture(scope="module")
+def composed_graph():
+    import graphgen as gg
+    L = gg.composed_layout(seed=11, copies=80)
+    assert 80000 < L.N < 200000 and all(L.built.get(k, 0) >= 80 for k in gg.COUNTERS)
+    return L
+
+
+def test_all_families_composed_and_simplified_twice(composed_graph, tmp_path):
+    """every family 80 times over interleaved ids, about 10^5 nodes: neighbours in id belong to different instances, so one sweep's
+    decisions cross blocks, and the bubbles that share an edge a -> b race for it in the removal map; a second graph_simplify() on the
+    same context gives the same bytes"""
+    L = composed_graph
+    _run_imported(L.N, L.edges, tmp_path, "all", again=True)
+
+
+def test_all_families_composed_plain_jumping(composed_graph, monkeypatch, tmp_path):
+    """the read counts every tier above rests on come from the contraction, which must be exact in both ranking forms"""
+    monkeypatch.setenv("SAGE2OV_S4_PLAIN_JUMPING", "1")
+    L = composed_graph
+    _run_imported(L.N, L.edges, tmp_path, "plain")
