@@ -6,8 +6,9 @@
 //
 // The uniform table (slots[T], linear probing, slot = tag:24 | cnt:7 | payload:33) is cut into WINDOWS of IX_W slots; a probe
 // sequence wraps inside its window (ix_next_pair), so a window is a closed hash table small enough for LDS.  Build:
-//   k_ix_tuples   one thread per read: its four keys (hashTable.cpp:96-104) -> hash -> tuple {K = home pair index, P = tag | entry,
-//                 M = hash of the key's minimiser}, written in read order (coalesced), + the first digit histogram
+//   k_ix_tuples   the four keys of every read (hashTable.cpp:96-104) -> hash -> tuple {K = home pair index, P = tag | entry, M = hash of the key's minimiser},
+//                 written in read order, + the first digit histogram.  8-word layout: a quad of lanes per read, one key per lane (other layouts: one thread
+//                 per read); k_ix_tuples_loc is the same visit of the id-ordered store that also writes the locality-ordered copy
 //   k_pt_*        LSD radix passes over the window id (kernels_partition.inc) until every window's tuples are contiguous
 //   k_ix_window   one workgroup per window: claim / count with LDS atomics, CSR space for the window's multi-entry buckets drawn with
 //                 ONE global atomic, entries placed and sorted by (id,type) in LDS, the window's slot words and CSR segment written
@@ -27,7 +28,67 @@ __device__ __forceinline__ void entry_key(const u64* __restrict__ reads, int S, 
     if (t >= 2) rc_key(phi, plo, h, hi, lo); else { hi = phi; lo = plo; }   // hashTable.cpp:96-104
 }
 
-// ---- tuples.  One workgroup = 1024 reads = one 4096-tuple tile of the first radix pass (its histogram is taken on the fly).
+// ---- tuples, quad form (8-word layout).  A slot is four 16-byte pieces and a quad of lanes holds one slot, lane c piece c (words 2c, 2c + 1): the access
+// pattern of k_loc_scatter, every load coalesced.  Lane t builds key t of hashTable.cpp:96-104 and writes tuple 4 (id - 1) + t, so a wave writes 64 consecutive
+// tuples (768 or 1024 contiguous bytes) where one thread per read put the four tuples of 64 reads at 64 places 48 bytes apart; the tuple index, and with
+// it the (id, type) order inside every bucket, is what it was.
+__device__ __forceinline__ u64 quad_word(const ulonglong2& v, int q) {         // word q (0..7) of the quad's slot (all four lanes of the quad are here)
+    const u64 a = __shfl(v.x, q >> 1, 4), b = __shfl(v.y, q >> 1, 4);
+    return (q & 1) ? b : a;
+}
+// the h-base key at base j of the quad's slot, as key_at gives it: its 2h bits lie in three consecutive words at most
+__device__ __forceinline__ void quad_key_at(const ulonglong2& v, int j, int h, u64& hi, u64& lo) {
+    const int q = (2 * j) >> 6, r = (2 * j) & 63;
+    const u64 w0 = quad_word(v, q);
+    u64 w1 = quad_word(v, q + 1 < 8 ? q + 1 : q); w1 = q + 1 < 8 ? w1 : 0ull;          // (words beyond the slot read as 0: bits64)
+    const u64 a = (w0 << r) | ((w1 >> 1) >> (63 - r));                                   // bits [2j, 2j + 64)
+    if (h <= 32) { hi = 0; lo = a >> (64 - 2 * h); return; }                             // (h is uniform)
+    u64 w2 = quad_word(v, q + 2 < 8 ? q + 2 : q); w2 = q + 2 < 8 ? w2 : 0ull;
+    const u64 b = (w1 << r) | ((w2 >> 1) >> (63 - r));                                   // bits [2j + 64, 2j + 128)
+    const int d = 2 * h - 64;                                                            // 1..64
+    hi = a >> (64 - d); lo = d == 64 ? b : ((a << d) | (b >> (64 - d)));                 // lo = bits [2j + 2h - 64, 2j + 2h)
+}
+// one tuple per lane: v = this lane's piece of read id0 + 1 (position pos of the locality order), t = lane in the quad = the key's type
+__device__ __forceinline__ void ix_quad_tuple(const ulonglong2& v, u32 id0, u32 pos, int t, int h, u64 seed, u32 Th, int wantMI, int shift0, u32 mask0, int doHist, u32* T, u32* hst) {
+    const int L = (int)(__shfl((u32)v.y, 3, 4) & slot_len_mask(8));                     // the slot's last word is in lane 3's piece
+    u64 phi, plo, khi, klo;
+    quad_key_at(v, (t == 0 || t == 3) ? 0 : L - h, h, phi, plo);                        // prefix (types 0, 3) or suffix (1, 2) of the forward strand
+    rc_key(phi, plo, h, khi, klo);
+    if (t < 2) { khi = phi; klo = plo; }                                                // types 2, 3: the reverse complement (hashTable.cpp:96-104)
+    const u64 hv = hash_key(khi, klo, h, seed);
+    const u32 kk = __umulhi((u32)(hv >> 32), Th), tag = tag_of(hv), entry = (u32)((u64)pos * 4 + (u64)t);
+    if (doHist) atomicAdd(&hst[pt_digit(kk, shift0, mask0)], 1u);
+    const u64 ti = 4 * (u64)id0 + (u64)t;
+    if (wantMI) { u32 k0, k1, k2, k3; key_left_align(khi, klo, h, k0, k1, k2, k3);
+                  ((uint4*)T)[ti] = make_uint4(kk, minim_hash(key_min_hash(k0, k1, k2, k3, h), (u32)seed), entry, tag); }
+    else { u32* o = T + 3 * ti; o[0] = kk; o[1] = entry; o[2] = tag; }
+}
+// one tile of PT_TILE tuples = PT_TILE / 4 reads by one workgroup, PT_THREADS / 4 reads per step, two steps' loads in flight.  COPY: the slot also goes to its
+// position in the locality-ordered store (k_loc_scatter's job) in the same visit.
+template <bool COPY>
+__device__ __forceinline__ void ix_quad_tile(const u64* __restrict__ reads, const u32* __restrict__ posOf, int byPos, u32 N, int h, u64 seed, u32 Th, int wantMI, int shift0, u32 mask0, int doHist,
+                                             u32* T, u32* hst, u64* loc) {
+    constexpr int RPS = PT_THREADS / 4, STEPS = PT_TILE / 4 / RPS, U = 2;
+    static_assert(STEPS % U == 0 && PT_THREADS % 64 == 0, "quad tile");
+    const int c = (int)(threadIdx.x & 3u);
+#pragma unroll 1
+    for (int j = 0; j < STEPS; j += U) {
+        ulonglong2 v[U]; u32 id0[U], pos[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            id0[u] = blockIdx.x * (u32)(PT_TILE / 4) + (u32)((j + u) * RPS) + (threadIdx.x >> 2);
+            if (id0[u] < N) { pos[u] = posOf[id0[u] + 1u]; v[u] = ((const ulonglong2*)reads)[(u64)(byPos ? pos[u] : id0[u] + 1u) * 4 + c]; }
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            if (id0[u] >= N) continue;                                                  // (a quad is one read: in or out as a whole)
+            if (COPY) ((ulonglong2*)loc)[(u64)pos[u] * 4 + c] = v[u];
+            ix_quad_tuple(v[u], id0[u], pos[u], c, h, seed, Th, wantMI, shift0, mask0, doHist, T, hst);
+        }
+    }
+}
+
+// ---- tuples.  One workgroup = PT_TILE / 4 reads = one tile of the first radix pass (its histogram is taken on the fly).
 // Reads are visited in ID order and the entry carries the read's POSITION in the locality-ordered store (what the probe kernels gather
 // from): the radix passes are stable, so inside a window the tuples of one key stay in (id, type) order -- the bucket order of
 // hashTable.cpp:94-109 -- and k_ix_window orders a bucket by tuple index, without ever looking an id up.
@@ -36,6 +97,8 @@ __global__ __launch_bounds__(PT_THREADS) void k_ix_tuples(const u64* __restrict_
                                                          u32* T, u32* cnt, u32 ntiles) {      // T: tuples of 4 dwords {K, M, entry, tag} with the minimiser hash, else 3 {K, entry, tag}
     __shared__ u32 hst[PT_NB_MAX];
     if (doHist) { for (u32 x = threadIdx.x; x <= mask0; x += PT_THREADS) hst[x] = 0; __syncthreads(); }
+    if (S == 8) ix_quad_tile<false>(reads, posOf, byPos, N, h, seed, Th, wantMI, shift0, mask0, doHist, T, hst, nullptr);      // (S is uniform; the other layouts: one thread per read)
+    else {
 #pragma unroll 1
     for (int j = 0; j < PT_TILE / 4 / PT_THREADS; j++) {
         const u32 id0 = blockIdx.x * (PT_TILE / 4) + j * PT_THREADS + threadIdx.x;
@@ -66,6 +129,17 @@ __global__ __launch_bounds__(PT_THREADS) void k_ix_tuples(const u64* __restrict_
             for (int t = 0; t < 4; t++) { o[3 * t] = kk[t]; o[3 * t + 1] = (u32)pp[t]; o[3 * t + 2] = (u32)(pp[t] >> 32); }
         }
     }
+    }
+    if (doHist) { __syncthreads(); for (u32 x = threadIdx.x; x <= mask0; x += PT_THREADS) cnt[(u64)x * ntiles + blockIdx.x] = hst[x]; }
+}
+// k_loc_scatter and k_ix_tuples in one visit of the id-ordered store (8-word layout, first attempt of a build): every slot is loaded once, goes to its position in
+// the locality-ordered store `loc` and gives its four tuples.  Workgroup b has the reads b * PT_TILE / 4 + 1 .., workgroup 0 also slot 0 (all zero, position 0).
+__global__ __launch_bounds__(PT_THREADS) void k_ix_tuples_loc(const u64* __restrict__ reads, const u32* __restrict__ posOf, u32 N, int h, u64 seed, u32 Th, int wantMI, int shift0, u32 mask0, int doHist,
+                                                             u32* T, u32* cnt, u32 ntiles, u64* loc) {
+    __shared__ u32 hst[PT_NB_MAX];
+    if (doHist) { for (u32 x = threadIdx.x; x <= mask0; x += PT_THREADS) hst[x] = 0; __syncthreads(); }
+    if (blockIdx.x == 0 && threadIdx.x < 4) ((ulonglong2*)loc)[(u64)posOf[0] * 4 + threadIdx.x] = ((const ulonglong2*)reads)[threadIdx.x];
+    ix_quad_tile<true>(reads, posOf, 0, N, h, seed, Th, wantMI, shift0, mask0, doHist, T, hst, loc);
     if (doHist) { __syncthreads(); for (u32 x = threadIdx.x; x <= mask0; x += PT_THREADS) cnt[(u64)x * ntiles + blockIdx.x] = hst[x]; }
 }
 

@@ -11,7 +11,7 @@
 //   k_pt_hist     per-tile digit histogram, cnt[digit * ntiles + tile] (digit-major: ONE exclusive scan gives every base)
 //   k_pt_scatter  stable scatter: a wave ranks 64 consecutive tuples with one ballot per digit bit (match-any), waves of a tile are
 //                 ordered through LDS, so equal digits keep their input order and the previous (lower) digits' order survives
-//   k_pt_bounds   first position of every window id in the sorted keys
+//   k_pt_bounds_search   first position of every window id in the sorted keys, by binary search (k_pt_bounds: by a pass over all keys, A/B runs)
 // Tuples are arrays of structures of 3 or 4 dwords (see k_pt_scatter); the digit is (dword KEYW >> shift) & mask.
 // =============================================================================================
 template <int NWAVES> __device__ __forceinline__ u32 block_excl_scan(u32 v, u32* sh, u32& total);
@@ -124,6 +124,17 @@ __global__ void k_pt_bounds(const u32* __restrict__ K, u32 n, int shiftW, u32 nW
     const u32 lo = i ? (shiftW >= 32 ? 0u : (K[(u64)(i - 1) * stride] >> shiftW)) + 1u : 0u;
     for (u32 x = lo; x <= w; x++) off[x] = i;
     if (i == n - 1) for (u32 x = w + 1; x <= nW; x++) off[x] = n;
+}
+
+// the same off[] by search: one thread per window id w in [0, nW] finds the lower bound of w among the n sorted window ids -- log2(n) dependent loads per
+// window (83 k windows at BASELINE configs[2]) where k_pt_bounds reads all 170 M keys again at the tuples' stride
+__global__ void k_pt_bounds_search(const u32* __restrict__ K, u32 n, int shiftW, u32 nW, u32* off, u32 stride) {
+    const u32 w = blockIdx.x * blockDim.x + threadIdx.x; if (w > nW) return;
+    u32 lo = 0, hi = n;
+    if (w == nW) lo = n;
+    else if (shiftW >= 32) lo = w ? n : 0u;                        // (every key is in window 0)
+    else while (lo < hi) { const u32 mid = lo + ((hi - lo) >> 1); if ((K[(u64)mid * stride] >> shiftW) < w) lo = mid + 1u; else hi = mid; }
+    off[w] = lo;
 }
 
 // self-check (SAGE2OV_VERIFY_PARTITION): the window ids of the sorted tuples must not decrease; out[0] = violations, out[1] = largest window population

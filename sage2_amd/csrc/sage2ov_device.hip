@@ -437,7 +437,8 @@ __global__ void k_status_by_pos(const u32* __restrict__ idOf, const uint8_t* __r
     const u64 p = (u64)blockIdx.x * blockDim.x + threadIdx.x; if (p > N) return; statusP[p] = p ? status[idOf[p]] : (uint8_t)0xFF;
 }
 __global__ void k_ids_to_pos(const u32* __restrict__ ids, u64 n, const u32* __restrict__ posOf, u32* out) { const u64 x = (u64)blockIdx.x * blockDim.x + threadIdx.x; if (x < n) out[x] = posOf[ids[x]]; }
-static int build_locality_store(Device* d, std::string& err) {
+// deferCopy: the caller writes the copy itself, in the same visit of the id-ordered store that makes the index tuples (k_ix_tuples_loc, dev_build_index)
+static int build_locality_store(Device* d, bool deferCopy, std::string& err) {
     const u64 N = d->N;
     WS(rl, u64, WS_LOC_READS, (N + 1) * d->S); WS(io, u32, WS_LOC_IDOF, N + 2); WS(po, u32, WS_LOC_POSOF, N + 2); WS(sp, uint8_t, WS_LOC_STATUS, N + 2);
     WS(me, unsigned short, WS_LOC_META, N + 2);
@@ -451,7 +452,7 @@ static int build_locality_store(Device* d, std::string& err) {
     // (the count travels to a pinned word while k_loc_scatter below runs: dev_build_index waits for the copy's event, not for the stream)
     if (d->runStartsValid) { HIPCHK(hipMemcpyAsync(d->h_runStarts, d->d_runStarts, 64 * sizeof(u64), hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipEventRecord(d->evRunStarts, d->stream)); }
     if (d->diet) { HIPCHK(hipStreamSynchronize(d->stream)); ph_begin(d, false); }       // the order's sort buffers (24 bytes per read) go before the tuples come: a phase of their own
-    hipLaunchKernelGGL(k_loc_scatter, dim3(grid_for_capped((N + 1) * (d->S / 2), 256)), dim3(256), 0, d->stream, d->reads, po, (u64)N, d->S, rl);
+    if (!deferCopy) hipLaunchKernelGGL(k_loc_scatter, dim3(grid_for_capped((N + 1) * (d->S / 2), 256)), dim3(256), 0, d->stream, d->reads, po, (u64)N, d->S, rl);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -487,7 +488,9 @@ static int partition_by_window(Device* d, PtBufs& B, int keyw, u32 n, int shiftW
             else { err = "partition: unsupported tuple format"; return SAGE2OV_ERR_INTERNAL; }
             cur = o; in = B.E[o];
         }
-        if (off) hipLaunchKernelGGL(k_pt_bounds, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, B.E[cur] + keyw, n, shiftW, (u32)nWin, off, (u32)B.W);
+        // window boundaries: a binary search per window (SAGE2OV_INDEX_SEPARATE_PASSES, A/B runs: the pass over all keys)
+        if (off && d->opt.get("SAGE2OV_INDEX_SEPARATE_PASSES")) hipLaunchKernelGGL(k_pt_bounds, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, B.E[cur] + keyw, n, shiftW, (u32)nWin, off, (u32)B.W);
+        else if (off) hipLaunchKernelGGL(k_pt_bounds_search, dim3(grid_for(nWin + 1, 256)), dim3(256), 0, d->stream, B.E[cur] + keyw, n, shiftW, (u32)nWin, off, (u32)B.W);
     } else if (off) HIPCHK(hipMemsetAsync(off, 0, (nWin + 1) * sizeof(u32), d->stream));
     HIPCHK(hipGetLastError());
     *cur_out = cur;
@@ -513,7 +516,12 @@ int dev_build_index(Device* d, uint64_t* slots_out, uint64_t* keys_out, uint64_t
                              d->right = d->left = nullptr; d->conn = d->cflag = nullptr; d->status = nullptr; d->cand = nullptr; d->cand_cap = 0; d->n_cand = 0; }
         ph_begin(d);
     }
-    if (d->reads) { int rc = build_locality_store(d, err); if (rc) return rc; }
+    // One visit of the id-ordered store writes the locality-ordered copy AND the tuples of the first attempt (k_ix_tuples_loc) where that store is resident, the
+    // layout has 8 words and the context is not on the diet; everything else -- reseed attempts, diet mode (byPos), other layouts, SAGE2OV_INDEX_SEPARATE_PASSES --
+    // keeps k_loc_scatter and k_ix_tuples.  (The fused launch is one workgroup per tile of 4N < 2^32 tuples: 2^28 threads at most, far inside the 2^32-thread rule.)
+    const u64 fusedThreads = ((4 * N + PT_TILE - 1) / PT_TILE) * PT_THREADS;
+    bool copyPending = d->reads && d->S == 8 && !d->diet && N > 0 && fusedThreads < (1ull << 32) && !d->opt.get("SAGE2OV_INDEX_SEPARATE_PASSES");
+    if (d->reads) { int rc = build_locality_store(d, copyPending, err); if (rc) return rc; }
     // (diet mode, second and later builds: the id-ordered store was released after the first one; the locality-ordered store and its tables are what
     //  this build would produce again -- the order is a function of the reads -- so they are kept)
     if (d->diet && d->reads && d->uniL) { HIPCHK(hipStreamSynchronize(d->stream)); hipFree(d->reads); d->reads = nullptr; }      // every later reader takes lengths from uniL
@@ -522,7 +530,9 @@ int dev_build_index(Device* d, uint64_t* slots_out, uint64_t* keys_out, uint64_t
     d->T = std::max<u64>(IX_W, (8 * N + IX_W - 1) / IX_W * IX_W);            // load <= 0.5, as hashTable.cpp:83 sizes it; whole windows
     // (tests: SAGE2OV_TEST_TABLE_SLOTS forces a larger table, e.g. beyond 2^32 slots -- slot indices are 64-bit, pair indices and window ids 32-bit)
     if (const char* ev = d->opt.get("SAGE2OV_TEST_TABLE_SLOTS")) { const u64 want = strtoull(ev, nullptr, 10); if (want > d->T) d->T = (want + IX_W - 1) / IX_W * IX_W; }
-    if ((d->T >> 1) >= (1ull << 32)) { err = "table too large: more than 2^32 slot pairs"; return SAGE2OV_ERR_LIMIT; }
+    if ((d->T >> 1) >= (1ull << 32)) {
+        if (copyPending) hipLaunchKernelGGL(k_loc_scatter, dim3(grid_for_capped((N + 1) * (d->S / 2), 256)), dim3(256), 0, d->stream, d->reads, d->posOf, (u64)N, d->S, d->readsLoc);    // (the store stays whole)
+        err = "table too large: more than 2^32 slot pairs"; return SAGE2OV_ERR_LIMIT; }
     const u64 nW = d->T / IX_W; const u32 n = (u32)(4 * N);
     const u32 big_cap = 1u << 20;
     WS(slots_ws, u64, WS_SLOTS, d->T); d->slots = slots_ws;
@@ -535,6 +545,7 @@ int dev_build_index(Device* d, uint64_t* slots_out, uint64_t* keys_out, uint64_t
     // coverage 30.5 % -> 35.3 / 6.2, 18.8 % -> 13.0 / 5.8, 13.9 % -> 6.6 / 5.5, 9.4 % -> 2.0 / 5.2; 8.5-9.7 M reads 32.2 % -> 6.8 / 1.7, 19.4 % -> 2.2 / 1.5, 14.2 % -> 0.9 / 1.4,
     // 9.5 % -> -0.1 / 1.3; 50x (9.5 %) at 42.5 M, 68 M and 102 M reads 4.2 / 6.1, 8.5 / 10.0 and 12.1 / 16.2.  The ratio is close to 27 (f - 0.1) from 20 M reads on and 0.72
     // of that below (RUN_START_RULE); the saving scales with the share of the reads this context probes, the build does not: built iff share x ratio >= 1.
+    // (with the fused kernel this wait is in front of its launch -- the tuple width depends on wantMI -- and the GPU idles for the event's round trip; k_loc_scatter used to cover it)
     if (d->runStartsValid) {
         HIPCHK(hipEventSynchronize(d->evRunStarts));
         u64 rs = 0; for (int x = 0; x < 64; x++) rs += d->h_runStarts[x];
@@ -571,7 +582,9 @@ int dev_build_index(Device* d, uint64_t* slots_out, uint64_t* keys_out, uint64_t
         HIPCHK(hipMemsetAsync(d->d_counters + 8, 0, 10 * sizeof(u64), d->stream));
         // ---- tuples of the 4N entries, sorted by the window of their home slot
         int shift0, doHist; u32 mask0; pt_first_digit(nW, IX_WPLOG, &shift0, &mask0, &doHist);
-        if (n) hipLaunchKernelGGL(k_ix_tuples, dim3(ntiles), dim3(PT_THREADS), 0, d->stream, byPos ? d->readsLoc : d->reads, d->posOf, byPos ? 1 : 0, (u32)N, d->S, d->h, d->seed, (u32)(d->T >> 1), wantMI ? 1 : 0, shift0, mask0, doHist,
+        if (copyPending) { hipLaunchKernelGGL(k_ix_tuples_loc, dim3(ntiles), dim3(PT_THREADS), 0, d->stream, d->reads, d->posOf, (u32)N, d->h, d->seed, (u32)(d->T >> 1), wantMI ? 1 : 0, shift0, mask0, doHist,
+                                              B.E[0], cnt, ntiles, d->readsLoc); copyPending = false; }
+        else if (n) hipLaunchKernelGGL(k_ix_tuples, dim3(ntiles), dim3(PT_THREADS), 0, d->stream, byPos ? d->readsLoc : d->reads, d->posOf, byPos ? 1 : 0, (u32)N, d->S, d->h, d->seed, (u32)(d->T >> 1), wantMI ? 1 : 0, shift0, mask0, doHist,
                                   B.E[0], cnt, ntiles);
         lap("tuples");
         int cur = 0;
