@@ -107,6 +107,28 @@ int sage2ov_reads_export_words(const sage2ov_ctx* ctx, uint64_t* words, uint64_t
 int sage2ov_reads_import_words(sage2ov_ctx* ctx, const uint64_t* words, uint64_t n_unique, uint32_t words_per_read,
                                uint32_t max_read_length, const uint16_t* frequency, uint64_t good_reads, uint64_t total_bp);
 
+/* ReadLoader::getIdOfRead (readLoader.cpp:319-353), batched: query r is bases[offsets[r] .. offsets[r+1]).
+ * ids[r] = +id  the read as given is its own canonical form (read < reverse complement, strictly: :325)
+ *          -id  its reverse complement is (a read equal to its reverse complement gets -id, as :325-334 do)
+ *           0   not in the store, or not a good read (utils.cpp:144-166: length <= minOverlap, a character outside ACGTacgt)
+ * Needs organised reads (reads_organize / reads_load / reads_import_words); usable at any later point and
+ * changes nothing the steps read or write.  A query longer than the store's longest read is simply not found.  With a GPU context
+ * the queries are classified, packed and searched on the device against the resident read store; a device-less
+ * context searches its host copy (the reference's method). */
+int sage2ov_reads_find_ids(sage2ov_ctx* ctx, const char* bases, const uint64_t* offsets, uint64_t n, int64_t* ids);
+typedef struct sage2ov_find_stats {
+    uint64_t queries, found, not_good, not_found;
+    uint32_t directory_bits, launches;     /* bits of the first-word directory; chunks the batch went through (0, 0 on the host route) */
+    double device_ms, directory_ms;        /* HIP events: classify + pack + search of all chunks; the directory build (0 when it was cached) */
+    double pack_ms, search_ms;             /* the two parts of device_ms */
+    uint32_t route;                        /* SAGE2OV_FIND_ROUTE_*: which copy of the reads the search read */
+    uint32_t reserved;
+} sage2ov_find_stats;
+#define SAGE2OV_FIND_ROUTE_HOST     0u   /* host copy (device-less context, or no store resident on the device) */
+#define SAGE2OV_FIND_ROUTE_ID_STORE 1u   /* the id-ordered store in HBM */
+#define SAGE2OV_FIND_ROUTE_LOCALITY 2u   /* the locality-ordered store through posOf[] (memory-diet mode after an index build: the id-ordered store is released) */
+int sage2ov_reads_find_stats_get(const sage2ov_ctx* ctx, sage2ov_find_stats* out);   /* of the last find call */
+
 /* ---- STEP 2: HashTable (economyGraph/hashTable.h:20-43) ---- */
 typedef struct sage2ov_index_stats {
     uint64_t slots;          /* open-addressed 8-byte slots in HBM           */

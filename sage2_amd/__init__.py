@@ -34,6 +34,15 @@ class IndexStats(C.Structure):
                 ("hash_string_length", C.c_uint32), ("rebuilds", C.c_uint32), ("minimiser_groups", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class FindStats(C.Structure):
+    _fields_ = [("queries", C.c_uint64), ("found", C.c_uint64), ("not_good", C.c_uint64), ("not_found", C.c_uint64),
+                ("directory_bits", C.c_uint32), ("launches", C.c_uint32), ("device_ms", C.c_double), ("directory_ms", C.c_double),
+                ("pack_ms", C.c_double), ("search_ms", C.c_double), ("route", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+FIND_ROUTE_HOST, FIND_ROUTE_ID_STORE, FIND_ROUTE_LOCALITY = 0, 1, 2
+
+
 class OverlapStats(C.Structure):
     _fields_ = [("verified_overlaps", C.c_uint64), ("contained_extension", C.c_uint64), ("contained_size", C.c_uint64),
                 ("left_to_explore", C.c_uint64), ("edges_inserted", C.c_uint64), ("transitive_removed", C.c_uint64),
@@ -202,6 +211,21 @@ class Context:
 
     def reads_set_totals(self, good_reads, total_bp):
         self._chk(lib().sage2ov_reads_set_totals(self._h, C.c_uint64(good_reads), C.c_uint64(total_bp)))
+
+    def reads_find_ids(self, bases, offsets) -> np.ndarray:
+        """ReadLoader::getIdOfRead for a batch: query r = bases[offsets[r]:offsets[r+1]] -> +id (the read as given is the stored, canonical form),
+        -id (its reverse complement is) or 0 (not stored, or not a good read)."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = max(len(offsets) - 1, 0)
+        ids = np.zeros(n, dtype=np.int64)
+        self._chk(lib().sage2ov_reads_find_ids(self._h, C.c_void_p(bases.ctypes.data), C.c_void_p(offsets.ctypes.data), C.c_uint64(n), C.c_void_p(ids.ctypes.data)))
+        return ids
+
+    def reads_find_stats(self) -> FindStats:
+        s = FindStats()
+        self._chk(lib().sage2ov_reads_find_stats_get(self._h, C.byref(s)))
+        return s
 
     # ---- step 2
     def index_build(self):

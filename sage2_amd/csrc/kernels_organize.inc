@@ -62,28 +62,42 @@ __global__ void k_org_classify(const unsigned char* __restrict__ bases, const u6
         if (ms) atomicAdd(&counters[3], (u64)__popcll(ms));
     }
 }
+// Word c of a read given as ASCII (32 bases from base 32c on, the first one in the top bits, zero padded), or of its reverse complement (RC): straight from
+// the characters, so that neither strand is ever held as an array (no scratch memory: registers only, whatever the layout)
+template <bool RC> __device__ __forceinline__ u64 org_ascii_word(const unsigned char* __restrict__ bases, u64 a, int L, int c) {
+    const int p0 = 32 * c, m = min(32, L - p0); u64 w = 0;
+    for (int x = 0; x < m; x++) {
+        const u32 cd = RC ? 3u - base_code(bases[a + (u64)(L - 1 - p0 - x)]) : base_code(bases[a + (u64)(p0 + x)]);
+        w |= (u64)cd << (62 - 2 * x);
+    }
+    return w;
+}
+// charsToBytes of the good read bases[a, a + L) in canonical orientation as an S-word slot at o (the length in the low bits of the last word); true: the read as
+// given is the canonical form (read < reverse complement, readLoader.cpp:195, :325), false: its reverse complement is -- a tie is never decided and stays with
+// the reverse complement (same bytes).  Shared by the organiser (k_org_pack) and the read-id lookup (k_find_pack, kernels_find.inc); w0 = word 0 as written.
+__device__ __forceinline__ bool org_pack_slot(const unsigned char* __restrict__ bases, u64 a, int L, int S, u64* o, u64& w0) {
+    const int nw = (L + 31) / 32;
+    bool useF = false;
+#pragma unroll 1
+    for (int c = 0; c < nw; c++) {
+        const u64 f = org_ascii_word<false>(bases, a, L, c), r = org_ascii_word<true>(bases, a, L, c);
+        if (f != r) { useF = f < r; break; }
+    }
+#pragma unroll 1
+    for (int c = 0; c < S; c++) {
+        u64 v = c < nw ? (useF ? org_ascii_word<false>(bases, a, L, c) : org_ascii_word<true>(bases, a, L, c)) : 0ull;
+        if (c == S - 1) v |= (u64)L;
+        o[c] = v; if (c == 0) w0 = v;
+    }
+    return useF;
+}
 __global__ void k_org_pack(const unsigned char* __restrict__ bases, const u64* __restrict__ off, u64 n, const u32* __restrict__ flag, const u32* __restrict__ pos, int S,
                            u64* img, u64* key0, u32* val) {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; if (i >= n || !flag[i]) return;
-    const u64 a = off[i]; const int L = (int)(off[i + 1] - a), nw = (L + 31) / 32;
-    u64 fw[SLOT_MAX_WORDS + 1], rw[SLOT_MAX_WORDS];
-#pragma unroll 1
-    for (int c = 0; c < SLOT_MAX_WORDS + 1; c++) fw[c] = 0ull;
-#pragma unroll 1
-    for (int x = 0; x < L; x++) fw[x >> 5] |= (u64)base_code(bases[a + x]) << (62 - 2 * (x & 31));
-    bool useF = false, decided = false;                                   // readLoader.cpp:195 (tie: the reverse complement, same bytes)
-#pragma unroll 1
-    for (int c = 0; c < nw; c++) {
-        const int rem = L - 32 * c; u64 r;
-        if (rem >= 32) r = ~rev2(bits64(fw, SLOT_MAX_WORDS + 1, 2 * (rem - 32)));
-        else r = (~rev2(fw[0] >> (64 - 2 * rem))) & mask_top(rem);
-        rw[c] = r;
-        if (!decided && fw[c] != r) { useF = fw[c] < r; decided = true; }
-    }
-    const u64 o0 = pos[i]; u64* o = img + o0 * S;
-#pragma unroll 1
-    for (int c = 0; c < S; c++) { u64 v = c < nw ? (useF ? fw[c] : rw[c]) : 0ull; if (c == S - 1) v |= (u64)L; o[c] = v; if (c == 0) key0[o0] = v; }
-    val[o0] = (u32)o0;
+    const u64 a = off[i]; const int L = (int)(off[i + 1] - a);
+    const u64 o0 = pos[i]; u64 w0 = 0;
+    org_pack_slot(bases, a, L, S, img + o0 * S, w0);
+    key0[o0] = w0; val[o0] = (u32)o0;
 }
 __global__ __launch_bounds__(64) void k_rs_hist(const u64* __restrict__ keys, u64 n, int shift, u32* hist, u32 nb) {
     __shared__ u32 h[256];

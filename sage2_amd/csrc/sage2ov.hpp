@@ -5,6 +5,7 @@
 #pragma once
 #include <stdexcept>
 #include <string>
+#include <vector>
 #include "sage2ov.h"
 
 namespace sage2ov {
@@ -37,6 +38,17 @@ public:
     void organizeReads() { ctx_.check(sage2ov_reads_organize(ctx_.get())); refresh(); }
     void saveReadsInFile(const std::string& path) { ctx_.check(sage2ov_reads_save(ctx_.get(), path.c_str())); }
     void loadReadsFromFile(const std::string& path) { ctx_.check(sage2ov_reads_load(ctx_.get(), path.c_str())); refresh(); }
+    // readLoader.cpp:319-353: +id the read as given is the stored form, -id its reverse complement is, 0 not in the list
+    int64_t getIdOfRead(const std::string& read) {
+        const uint64_t off[2] = {0, read.size()}; int64_t id = 0;
+        ctx_.check(sage2ov_reads_find_ids(ctx_.get(), read.data(), off, 1, &id)); return id;
+    }
+    // the same for many reads in one call (one search pass on the device instead of one per read)
+    std::vector<int64_t> getIdOfRead(const std::vector<std::string>& reads) {
+        std::string bases; std::vector<uint64_t> off(reads.size() + 1, 0); std::vector<int64_t> ids(reads.size(), 0);
+        for (size_t r = 0; r < reads.size(); r++) { bases += reads[r]; off[r + 1] = bases.size(); }
+        ctx_.check(sage2ov_reads_find_ids(ctx_.get(), bases.data(), off.data(), reads.size(), ids.data())); return ids;
+    }
     sage2ov_read_stats stats() const { sage2ov_read_stats s{}; ctx_.check(sage2ov_reads_stats(ctx_.get(), &s)); return s; }
     Context& context() { return ctx_; }
 private:

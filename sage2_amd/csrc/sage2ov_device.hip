@@ -50,6 +50,7 @@ struct Device {
     u64 N = 0; int S = 0, maxL = 0, k = 0, h = 0; double probeShare = 1.0;
     u64* d_runStarts = nullptr; u64* h_runStarts = nullptr; hipEvent_t evRunStarts = nullptr; bool runStartsValid = false; double runStartFrac = 0.0;      // share of the reads without a predecessor in the locality order (counted by k_loc_index into d_runStarts)
     u64* reads = nullptr;        // (N+1)*S words, slot i = read id i
+    u32* findDir = nullptr; int findDirBits = 0;      // read-id lookup (dev_find_ids): first id per value of the top bits of word 0, built by the first call, dropped with the read set
     // the same reads in LOCALITY order (slot p = the read at position p of the order by global minimiser): what the index entries point at and
     // what the probe kernels gather from -- a read's overlap partners are neighbours in the genome, hence (mostly) neighbours here
     u64* readsLoc = nullptr; u32* idOf = nullptr; u32* posOf = nullptr; uint8_t* statusP = nullptr; unsigned short* metaP = nullptr;
@@ -189,6 +190,7 @@ static void mem_sample(Device* d) { size_t fr = 0, to = 0; if (hipMemGetInfo(&fr
 #include "kernels_reduce.inc"
 #include "kernels_convert.inc"
 #include "kernels_simplify.inc"
+#include "kernels_find.inc"
 
 // =============================================================================================
 // host-side launchers
@@ -237,6 +239,7 @@ static void rr_staging_release(Device* d);
 static void free_reads(Device* d) {
     rr_staging_release(d);                     // (pinned host buffers sized by the previous read set)
     hipFree(d->reads);
+    hipFree(d->findDir); d->findDir = nullptr; d->findDirBits = 0;      // (the lookup directory describes the read set that goes)
     if (!d->resCarved) { hipFree(d->right); hipFree(d->left); hipFree(d->conn); hipFree(d->cflag); hipFree(d->status); hipFree(d->cand); }     // slots / csr / final_edges live in the workspace arena
     ph_release(d);                                                              // (diet mode: the phase block and what was carved out of it)
     for (auto& b : d->ws) { if (b.p && !b.epoch) hipFree(b.p); b.p = nullptr; b.cap = 0; b.epoch = 0; }
@@ -1501,6 +1504,78 @@ int dev_unresolved_ids(Device* d, std::vector<uint32_t>& ids, std::string& err) 
     u32* buf = nullptr; u64 cnt = 0; { int rc = collect_unresolved(d, &buf, &cnt, err); if (rc) return rc; }
     ids.resize(cnt); if (cnt) HIPCHK(hipMemcpy(ids.data(), buf, cnt * sizeof(u32), hipMemcpyDeviceToHost));
     std::sort(ids.begin(), ids.end());
+    return 0;
+}
+
+// ReadLoader::getIdOfRead for a batch (kernels_find.inc).  Queries go through in chunks bounded in queries and in bytes, so a launch stays far below 2^32 threads
+// and the staging is bounded (a chunk always takes one query at least: a single query larger than the bound is staged whole).  Every buffer but the directory is a
+// transient allocation of this call; the steps' results, their phase blocks and the workspace arena are not touched.  Returns 1 when no read store is resident
+// (the caller searches its host copy instead).
+constexpr u64 FIND_CHUNK_BYTES = 256ull << 20;      // ASCII per chunk, and the chunk's packed image
+int dev_find_ids(Device* d, const char* bases, const uint64_t* off, uint64_t n, int64_t* ids, FindStats* st, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    const bool byPos = d->reads == nullptr;
+    if (byPos && !(d->readsLoc && d->posOf)) return 1;
+    const u64* store = byPos ? d->readsLoc : d->reads; const int S = d->S; const u64 N = d->N;
+    if (S != 4 && S != 8 && S != 16 && S != 32) { err = "unsupported words-per-read"; return SAGE2OV_ERR_INTERNAL; }
+    struct Tmp {                                                                     // (freed on every return path)
+        hipEvent_t ev[3] = {}; void* p[7] = {}; size_t cap[7] = {};
+        ~Tmp() { for (auto e : ev) if (e) hipEventDestroy(e); for (auto q : p) if (q) hipFree(q); }
+        void* get(int i, size_t bytes) { if (cap[i] >= bytes && p[i]) return p[i]; if (p[i]) hipFree(p[i]); p[i] = nullptr; cap[i] = 0;
+                                         if (hipMalloc(&p[i], bytes) != hipSuccess) { (void)hipGetLastError(); p[i] = nullptr; return nullptr; } cap[i] = bytes; return p[i]; }
+    } T;
+    for (auto& e : T.ev) HIPCHK(hipEventCreate(&e));
+    *st = FindStats(); st->byPos = byPos;
+    if (!d->findDir) {                                                               // the directory: once per read set
+        int B = 0; while ((1ull << B) < N) B++;                                      // ceil(log2 N)
+        B = std::min(FIND_B_MAX, std::max(FIND_B_MIN, B - 1));
+        u32* dir = nullptr; HIPCHK(hipMalloc(&dir, ((size_t)(1u << B) + 1) * sizeof(u32)));
+        HIPCHK(hipEventRecord(T.ev[0], d->stream));
+        if (byPos) hipLaunchKernelGGL(k_find_dir<true>, dim3(grid_for((1u << B) + 1, 256)), dim3(256), 0, d->stream, store, d->posOf, (u32)N, S, B, dir);
+        else hipLaunchKernelGGL(k_find_dir<false>, dim3(grid_for((1u << B) + 1, 256)), dim3(256), 0, d->stream, store, d->posOf, (u32)N, S, B, dir);
+        hipError_t e = hipGetLastError(); if (e == hipSuccess) e = hipEventRecord(T.ev[1], d->stream); if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+        if (e != hipSuccess) { hipFree(dir); err = std::string("read-id directory: ") + hipGetErrorString(e); return SAGE2OV_ERR_DEVICE; }
+        float ms = 0; hipEventElapsedTime(&ms, T.ev[0], T.ev[1]); st->dir_ms = ms;
+        d->findDir = dir; d->findDirBits = B;
+    }
+    st->dirBits = (u32)d->findDirBits;
+    const long long forced = d->opt.num("SAGE2OV_TEST_FIND_BATCH", 0);             // test-only: queries per chunk
+    const u64 qcap = forced > 0 ? (u64)forced : std::min<u64>(1ull << 22, FIND_CHUNK_BYTES / ((u64)S * sizeof(u64)));
+    const u32 lenCap = (u32)((64 * S - (S > 16 ? 11 : 9)) / 2);                    // bases a slot of this layout holds
+    const u32 maxLen = std::min<u32>((u32)std::max(d->maxL, 0), lenCap);
+    std::vector<u64> ho;
+    for (u64 r0 = 0; r0 < n;) {
+        u64 r1 = r0 + 1; const u64 lastQ = std::min<u64>(n, r0 + qcap);
+        while (r1 < lastQ && off[r1 + 1] - off[r0] <= FIND_CHUNK_BYTES) r1++;
+        const u64 q = r1 - r0, nbytes = off[r1] - off[r0];
+        ho.resize(q + 1); for (u64 x = 0; x <= q; x++) ho[x] = off[r0 + x] - off[r0];
+        unsigned char* db = (unsigned char*)T.get(0, nbytes + 64); u64* dof = (u64*)T.get(1, (q + 1) * sizeof(u64)); u32* flag = (u32*)T.get(2, q * sizeof(u32));
+        u64* img = (u64*)T.get(3, q * S * sizeof(u64)); signed char* sign = (signed char*)T.get(4, q); long long* dids = (long long*)T.get(5, q * sizeof(long long));
+        u64* cnt = (u64*)T.get(6, 8 * sizeof(u64));
+        if (!db || !dof || !flag || !img || !sign || !dids || !cnt) { err = "read-id lookup: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+        if (nbytes) HIPCHK(hipMemcpyAsync(db, bases + off[r0], nbytes, hipMemcpyHostToDevice, d->stream));
+        HIPCHK(hipMemcpyAsync(dof, ho.data(), (q + 1) * sizeof(u64), hipMemcpyHostToDevice, d->stream));
+        const u64 init[8] = {0, 0, 0, 0, ~0ull, 0, 0, 0}; HIPCHK(hipMemcpyAsync(cnt, init, sizeof init, hipMemcpyHostToDevice, d->stream));      // [0..5] k_org_classify, [6] found
+        HIPCHK(hipEventRecord(T.ev[0], d->stream));
+        hipLaunchKernelGGL(k_org_classify, dim3(grid_for(q, 256)), dim3(256), 0, d->stream, db, dof, (u64)q, (u32)d->k, maxLen, flag, cnt);
+        hipLaunchKernelGGL(k_find_pack, dim3(grid_for(q, 256)), dim3(256), 0, d->stream, db, dof, (u64)q, flag, S, img, sign);
+        HIPCHK(hipEventRecord(T.ev[1], d->stream));
+        const dim3 grid(grid_for(q * (u64)(S / 2), 256)), block(256); unsigned long long* fnd = (unsigned long long*)(cnt + 6);
+#define S2_FIND(SS) do { if (byPos) hipLaunchKernelGGL((k_find_search<SS, true>), grid, block, 0, d->stream, store, d->posOf, d->findDir, d->findDirBits, img, sign, (u32)q, dids, fnd); \
+                         else hipLaunchKernelGGL((k_find_search<SS, false>), grid, block, 0, d->stream, store, d->posOf, d->findDir, d->findDirBits, img, sign, (u32)q, dids, fnd); } while (0)
+        if (S == 4) S2_FIND(4); else if (S == 8) S2_FIND(8); else if (S == 16) S2_FIND(16); else S2_FIND(32);
+#undef S2_FIND
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(T.ev[2], d->stream));
+        u64 hc[8];
+        HIPCHK(hipMemcpyAsync(ids + r0, dids, q * sizeof(long long), hipMemcpyDeviceToHost, d->stream));
+        HIPCHK(hipMemcpyAsync(hc, cnt, sizeof hc, hipMemcpyDeviceToHost, d->stream));
+        HIPCHK(hipStreamSynchronize(d->stream));
+        float a = 0, b = 0; hipEventElapsedTime(&a, T.ev[0], T.ev[1]); hipEventElapsedTime(&b, T.ev[1], T.ev[2]);
+        st->pack_ms += a; st->search_ms += b; st->launches++;
+        st->found += hc[6]; st->not_good += q - hc[1] - hc[5];                       // hc[1]: good and no longer than the store's longest; hc[5]: good but longer
+        r0 = r1;
+    }
     return 0;
 }
 

@@ -105,6 +105,7 @@ struct sage2ov_ctx {
     // ---- step 2/3 state
     bool indexBuilt = false, probed = false, reciprocalDone = false, reduced = false, converted = false;
     sage2ov_index_stats istats{};
+    sage2ov_find_stats fstats{};                       // of the last sage2ov_reads_find_ids
     sage2ov_overlap_stats ostats{};
     std::vector<FinalEdge> edges; bool edgesOnHost = false;
     SimplifiedGraph g4; bool g4Valid = false;
@@ -935,6 +936,62 @@ int sage2ov_reads_import_words(sage2ov_ctx* c, const uint64_t* words, uint64_t n
     c->goodReads = good_reads; c->totalBP = total_bp; c->totalReads = good_reads; c->organized = false;
     return upload(c);
 }
+// ReadLoader::getIdOfRead (readLoader.cpp:319-353) on the host copy of the store: isGoodRead, canonical orientation, pack, binary search with the slot compare
+// (words in order, the last one carrying the length = stringCompareInBytes, utils.cpp:224).  The route of a device-less context, and of a GPU context
+// whose device holds no read store.
+static void find_ids_host(const sage2ov_ctx* c, const char* bases, const uint64_t* off, uint64_t n, int64_t* ids, sage2ov_find_stats& st) {
+    const int S = c->S; const uint64_t N = c->N; const uint64_t* words = c->words.data();
+    const uint64_t k = c->cfg.min_overlap, maxL = std::min<uint64_t>((uint64_t)std::max(c->maxL, 0), (64 * (uint64_t)S - (S > 16 ? 11 : 9)) / 2);
+    uint64_t found = 0, notGood = 0;
+    #pragma omp parallel for num_threads(io_threads(c)) schedule(dynamic, 1024) reduction(+ : found, notGood)
+    for (uint64_t r = 0; r < n; r++) {
+        const unsigned char* b = (const unsigned char*)bases + off[r]; const uint64_t Ls = off[r + 1] - off[r];
+        ids[r] = 0;
+        if (Ls <= k) { notGood++; continue; }
+        bool valid = true; for (uint64_t i = 0; i < Ls && valid; i++) valid = g_code[b[i]] <= 3;
+        if (!valid) { notGood++; continue; }
+        if (Ls > maxL) continue;                                                       // longer than every read of the store: not found
+        const int L = (int)Ls, nw = (L + 31) / 32; uint64_t f[34], rc[34], q[32];
+        for (int w = 0; w < nw; w++) f[w] = 0;
+        for (int i = 0; i < L; i++) f[i >> 5] |= (uint64_t)g_code[b[i]] << (62 - 2 * (i & 31));
+        revcomp_words(f, nw, L, rc);
+        bool useF = false;                                                             // :325: strictly smaller, else the reverse complement (a tie too)
+        for (int w = 0; w < nw; w++) if (f[w] != rc[w]) { useF = f[w] < rc[w]; break; }
+        for (int w = 0; w < S; w++) q[w] = w < nw ? (useF ? f[w] : rc[w]) : 0;
+        q[S - 1] |= (uint64_t)L;
+        uint64_t lb = 1, ub = N;                                                       // :335-348
+        while (lb <= ub) {
+            const uint64_t mid = (lb + ub) >> 1; const uint64_t* s = words + mid * S; int cmp = 0;
+            for (int w = 0; w < S; w++) if (q[w] != s[w]) { cmp = q[w] < s[w] ? -1 : 1; break; }
+            if (cmp == 0) { ids[r] = useF ? (int64_t)mid : -(int64_t)mid; found++; break; }
+            if (cmp > 0) lb = mid + 1; else ub = mid - 1;
+        }
+    }
+    st.found = found; st.not_good = notGood; st.route = SAGE2OV_FIND_ROUTE_HOST;
+}
+int sage2ov_reads_find_ids(sage2ov_ctx* c, const char* bases, const uint64_t* off, uint64_t n, int64_t* ids) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    if (!c->organized) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_reads_find_ids: organise (or load) the reads first");
+    c->fstats = sage2ov_find_stats{}; c->fstats.queries = n;
+    if (n == 0) return SAGE2OV_OK;
+    if (!bases || !off || !ids) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_reads_find_ids: null argument");
+    for (uint64_t r = 0; r < n; r++) if (off[r + 1] < off[r]) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_reads_find_ids: offsets must not decrease");
+    if (c->gpu() && !c->device()) return c->fail(SAGE2OV_ERR_DEVICE, c->devErr);
+    int route = 1;                                                                     // 1: nothing resident on a device (or no device): search the host copy
+    if (Device* d = c->device()) {
+        FindStats fs; route = dev_find_ids(d, bases, off, n, ids, &fs, c->err);
+        if (route < 0) return route;
+        if (route == 0) {
+            c->fstats.found = fs.found; c->fstats.not_good = fs.not_good; c->fstats.directory_bits = fs.dirBits; c->fstats.launches = fs.launches;
+            c->fstats.pack_ms = fs.pack_ms; c->fstats.search_ms = fs.search_ms; c->fstats.device_ms = fs.pack_ms + fs.search_ms; c->fstats.directory_ms = fs.dir_ms;
+            c->fstats.route = fs.byPos ? SAGE2OV_FIND_ROUTE_LOCALITY : SAGE2OV_FIND_ROUTE_ID_STORE;
+        }
+    }
+    if (route == 1) find_ids_host(c, bases, off, n, ids, c->fstats);
+    c->fstats.not_found = n - c->fstats.found - c->fstats.not_good;
+    return SAGE2OV_OK;
+}
+int sage2ov_reads_find_stats_get(const sage2ov_ctx* c, sage2ov_find_stats* o) { if (!c || !o) return SAGE2OV_ERR_ARG; *o = c->fstats; return SAGE2OV_OK; }
 int sage2ov_reads_set_totals(sage2ov_ctx* c, uint64_t good, uint64_t bp) { if (!c) return SAGE2OV_ERR_ARG; c->goodReads = good; c->totalBP = bp; return SAGE2OV_OK; }
 
 // ------------------------------------------------------------------------------------------ step 2

@@ -130,6 +130,10 @@ int dev_replace_cand_tail(Device* d, uint64_t keep, const void* dev_src, uint64_
 // append host-computed edge candidates (from the reduce replay) to the device candidate list
 int dev_debug_table(Device* d, uint64_t* out5, std::string& err);
 int dev_meminfo(Device* d, uint64_t* out4, std::string& err);
+// ReadLoader::getIdOfRead, batched (sage2ov_reads_find_ids): query r = bases[off[r], off[r + 1]) -> ids[r] = +-id or 0.  Returns 1 (and does nothing) when neither
+// read store is resident: the caller then searches the host copy
+struct FindStats { uint64_t found = 0, not_good = 0; uint32_t dirBits = 0, launches = 0; double pack_ms = 0, dir_ms = 0, search_ms = 0; bool byPos = false; };
+int dev_find_ids(Device* d, const char* bases, const uint64_t* off, uint64_t n, int64_t* ids, FindStats* st, std::string& err);
 int dev_debug_keys(Device* d, uint64_t* out, std::string& err);
 int dev_debug_all_hits(Device* d, std::vector<Hit>& hits, std::string& err);
 int dev_append_edges(Device* d, const EdgeCand* e, uint64_t n, std::string& err);
