@@ -129,6 +129,42 @@ typedef struct sage2ov_find_stats {
 #define SAGE2OV_FIND_ROUTE_LOCALITY 2u   /* the locality-ordered store through posOf[] (memory-diet mode after an index build: the id-ordered store is released) */
 int sage2ov_reads_find_stats_get(const sage2ov_ctx* ctx, sage2ov_find_stats* out);   /* of the last find call */
 
+/* MatePair::mapMatePairs / processMatePairs (matePair.cpp:125-239), as run with one thread: the table of mate links between read ids.
+ * A call hands over reads 0 .. n-1 (layout of sage2ov_reads_add_ascii) and a library number 1 .. 127; its pairs are (2j, 2j+1) for 2j+1 < n, a trailing
+ * odd read is dropped (:172), pairs never span two calls.  A pair is skipped when either mate is not a good read (:176), and -- a DELIBERATE DIFFERENCE
+ * from the reference -- when either mate is a good read that is not in the store (id 0): the reference files such a pair under read 0 with type 0, which
+ * its own log line at readLoader.cpp:350 calls an accident.  With id1 = |ids[2j]|, type1 = ids[2j] > 0, id2 = |ids[2j+1]|, type2 = ids[2j+1] > 0 a
+ * surviving pair adds two directed records: (from id1, to id2, type1, type2) with side 0 and its twin (from id2, to id1, type2, type1) with side 1.
+ * The table of a library holds one entry per distinct (from, to, type1, type2) among all records given to that library so far:
+ *   count  records with that key;  freq = count & 255 (the reference's uint8_t freq starts at 1 and wraps: 256 records give 0)
+ *   first  the smallest record ordinal 2 * p + side with that key, p = ordinal of the pair among ALL pairs given to this library so far (skipped
+ *          ones included, counted across calls).  matePairList[a] of the reference is the entries of from == a in DESCENDING first (head insertion).
+ * Entries of different libraries never merge.  The `flag` field of MatePairInfo (set later by mapReadsToEdges) is not part of this.
+ * All calls need organised reads; the table is dropped with the read set and by sage2ov_mates_clear, and changes nothing steps 2-4 read or write.
+ * With a GPU context the ids are found, the records written, sorted and reduced and the table merged on the device; a device-less
+ * context builds the same table on the host. */
+typedef struct sage2ov_mate { uint32_t from, to; uint64_t count, first; uint8_t freq, type1, type2, library; uint8_t pad[4]; } sage2ov_mate;   /* 32 bytes */
+int sage2ov_mates_add_ascii(sage2ov_ctx* ctx, const char* bases, const uint64_t* offsets, uint64_t n, int library);   /* processMatePairs for one readsArray */
+int sage2ov_mates_add_file(sage2ov_ctx* ctx, const char* path1, const char* path2 /* may be NULL */, int library);    /* mapMatePairs (matePair.cpp:125): one interleaved file, or two files read in turn */
+int sage2ov_mates_add_list(sage2ov_ctx* ctx, const char* list_path);   /* mapMatePairsFromList (:70-120): `f=` or `f1=` then `f2=` per dataset; dataset i is library i */
+int sage2ov_mates_count(sage2ov_ctx* ctx, int library, uint64_t* n);
+/* entries of one library in ascending (from, to, type1, type2); offsets (N + 2 values, may be NULL): the entries of read a are [offsets[a], offsets[a+1]),
+ * offsets[N+1] is the entry count.  cap < count: SAGE2OV_ERR_ARG, nothing written */
+int sage2ov_mates_export(sage2ov_ctx* ctx, int library, sage2ov_mate* out, uint64_t cap, uint64_t* offsets);
+int sage2ov_mates_clear(sage2ov_ctx* ctx);
+typedef struct sage2ov_mate_stats {
+    uint64_t pairs_seen, pairs_added, pairs_not_good, pairs_not_found;   /* seen = added + not_good + not_found */
+    uint64_t records;                        /* 2 * pairs_added */
+    uint64_t entries_before, entries_after;  /* of the call's library (add_list: of its last dataset) */
+    uint32_t library, libraries;             /* the call's library; the highest library in use (numberOfLibrary) */
+    uint32_t chunks, sort_passes;            /* id look-up chunks; 8-bit radix passes run (record sorts and merges); 0, 0 on the host route */
+    uint32_t flushes, route;                 /* sort + reduce + merge rounds; SAGE2OV_MATE_ROUTE_* */
+    double find_ms, records_ms, sort_ms, reduce_ms, merge_ms;   /* HIP events (0 on the host route) */
+} sage2ov_mate_stats;
+#define SAGE2OV_MATE_ROUTE_HOST   0u
+#define SAGE2OV_MATE_ROUTE_DEVICE 1u
+int sage2ov_mates_stats_get(const sage2ov_ctx* ctx, sage2ov_mate_stats* out);   /* of the last add call */
+
 /* ---- STEP 2: HashTable (economyGraph/hashTable.h:20-43) ---- */
 typedef struct sage2ov_index_stats {
     uint64_t slots;          /* open-addressed 8-byte slots in HBM           */

@@ -43,6 +43,19 @@ class FindStats(C.Structure):
 FIND_ROUTE_HOST, FIND_ROUTE_ID_STORE, FIND_ROUTE_LOCALITY = 0, 1, 2
 
 
+class MateStats(C.Structure):
+    _fields_ = [("pairs_seen", C.c_uint64), ("pairs_added", C.c_uint64), ("pairs_not_good", C.c_uint64), ("pairs_not_found", C.c_uint64),
+                ("records", C.c_uint64), ("entries_before", C.c_uint64), ("entries_after", C.c_uint64),
+                ("library", C.c_uint32), ("libraries", C.c_uint32), ("chunks", C.c_uint32), ("sort_passes", C.c_uint32), ("flushes", C.c_uint32), ("route", C.c_uint32),
+                ("find_ms", C.c_double), ("records_ms", C.c_double), ("sort_ms", C.c_double), ("reduce_ms", C.c_double), ("merge_ms", C.c_double)]
+
+
+MATE_ROUTE_HOST, MATE_ROUTE_DEVICE = 0, 1
+# sage2ov_mate (32 bytes)
+MATE_DTYPE = np.dtype([("from", np.uint32), ("to", np.uint32), ("count", np.uint64), ("first", np.uint64), ("freq", np.uint8), ("type1", np.uint8),
+                       ("type2", np.uint8), ("library", np.uint8), ("pad", np.uint8, (4,))])
+
+
 class OverlapStats(C.Structure):
     _fields_ = [("verified_overlaps", C.c_uint64), ("contained_extension", C.c_uint64), ("contained_size", C.c_uint64),
                 ("left_to_explore", C.c_uint64), ("edges_inserted", C.c_uint64), ("transitive_removed", C.c_uint64),
@@ -225,6 +238,42 @@ class Context:
     def reads_find_stats(self) -> FindStats:
         s = FindStats()
         self._chk(lib().sage2ov_reads_find_stats_get(self._h, C.byref(s)))
+        return s
+
+    # ---- the mate-pair table (MatePair::mapMatePairs, matePair.cpp:125-239)
+    def mates_add_ascii(self, bases, offsets, library):
+        """processMatePairs for one array of reads: pairs (2j, 2j+1), a trailing odd read is dropped"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = max(len(offsets) - 1, 0)
+        self._chk(lib().sage2ov_mates_add_ascii(self._h, C.c_void_p(bases.ctypes.data), C.c_void_p(offsets.ctypes.data), C.c_uint64(n), C.c_int(library)))
+
+    def mates_add_file(self, path1, path2=None, library=1):
+        self._chk(lib().sage2ov_mates_add_file(self._h, os.fsencode(path1), os.fsencode(path2) if path2 else None, C.c_int(library)))
+
+    def mates_add_list(self, list_path):
+        self._chk(lib().sage2ov_mates_add_list(self._h, os.fsencode(list_path)))
+
+    def mates_count(self, library) -> int:
+        n = C.c_uint64(0)
+        self._chk(lib().sage2ov_mates_count(self._h, C.c_int(library), C.byref(n)))
+        return int(n.value)
+
+    def mates(self, library):
+        """(entries, offsets): the library's entries (MATE_DTYPE) in ascending (from, to, type1, type2); the entries of read a are
+        entries[offsets[a]:offsets[a + 1]], offsets[N + 1] is the entry count"""
+        n = self.mates_count(library)
+        out = np.zeros(n, dtype=MATE_DTYPE)
+        offsets = np.zeros(self.reads_stats().unique_reads + 2, dtype=np.uint64)
+        self._chk(lib().sage2ov_mates_export(self._h, C.c_int(library), C.c_void_p(out.ctypes.data), C.c_uint64(n), C.c_void_p(offsets.ctypes.data)))
+        return out, offsets
+
+    def mates_clear(self):
+        self._chk(lib().sage2ov_mates_clear(self._h))
+
+    def mates_stats(self) -> MateStats:
+        s = MateStats()
+        self._chk(lib().sage2ov_mates_stats_get(self._h, C.byref(s)))
         return s
 
     # ---- step 2

@@ -3,6 +3,7 @@
 // the reference (inputReader/readLoader.h:44-55, economyGraph/hashTable.h:34-43, economyGraph/economyGraph.h:43-53,
 // overlapGraph/overlapGraph.h:54-67); errors become exceptions instead of exit() (utils.cpp:36).
 #pragma once
+#include <algorithm>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -54,6 +55,42 @@ public:
 private:
     void refresh() { auto s = stats(); numberOfUniqueReads = s.unique_reads; numberOfReads = s.good_reads; totalBP = s.total_bp; averageReadLength = s.average_read_length; }
     Context& ctx_;
+};
+
+// MatePair (matePair/matePair.h): the part that builds the lists, mapMatePairs / processMatePairs (matePair.cpp:70-239).  The table lives in the
+// context (on the device when it has one); list() fetches a library once and caches it until the next add call.
+class MatePair {
+public:
+    explicit MatePair(ReadLoader* loader1) : loaderObj(loader1) {}
+    void mapMatePairs(const std::string& mateFile1, const std::string& mateFile2, int library) {
+        ctx().check(sage2ov_mates_add_file(ctx().get(), mateFile1.c_str(), mateFile2.empty() ? nullptr : mateFile2.c_str(), library)); cachedLibrary_ = 0;
+    }
+    void mapMatePairsFromList(const std::string& listPath) { ctx().check(sage2ov_mates_add_list(ctx().get(), listPath.c_str())); cachedLibrary_ = 0; }
+    void processMatePairs(const std::vector<std::string>& readsArray, int library) {
+        std::string bases; std::vector<uint64_t> off(readsArray.size() + 1, 0);
+        for (size_t r = 0; r < readsArray.size(); r++) { bases += readsArray[r]; off[r + 1] = bases.size(); }
+        ctx().check(sage2ov_mates_add_ascii(ctx().get(), bases.data(), off.data(), readsArray.size(), library)); cachedLibrary_ = 0;
+    }
+    int numberOfLibrary() const { return (int)stats().libraries; }
+    // matePairList[readId] of the reference, entries of `library` only, in the reference's serial list order: head insertion (matePair.cpp:210-211,
+    // :233-234) = descending `first`
+    std::vector<sage2ov_mate> list(uint64_t readId, int library) {
+        if (cachedLibrary_ != library) {
+            uint64_t n = 0; ctx().check(sage2ov_mates_count(ctx().get(), library, &n));
+            sage2ov_read_stats rs{}; ctx().check(sage2ov_reads_stats(ctx().get(), &rs));
+            entries_.assign(n, sage2ov_mate{}); offsets_.assign(rs.unique_reads + 2, 0);
+            ctx().check(sage2ov_mates_export(ctx().get(), library, entries_.data(), n, offsets_.data())); cachedLibrary_ = library;
+        }
+        if (readId + 1 >= offsets_.size()) return {};
+        std::vector<sage2ov_mate> out(entries_.begin() + offsets_[readId], entries_.begin() + offsets_[readId + 1]);
+        std::sort(out.begin(), out.end(), [](const sage2ov_mate& a, const sage2ov_mate& b) { return a.first > b.first; });
+        return out;
+    }
+    sage2ov_mate_stats stats() const { sage2ov_mate_stats s{}; ctx().check(sage2ov_mates_stats_get(ctx().get(), &s)); return s; }
+    ReadLoader* loaderObj;
+private:
+    Context& ctx() const { return loaderObj->context(); }
+    std::vector<sage2ov_mate> entries_; std::vector<uint64_t> offsets_; int cachedLibrary_ = 0;
 };
 
 // HashTable (hashTable.h:20-43)

@@ -41,6 +41,8 @@ typedef unsigned int u32;
 enum { WS_SLOTS, WS_CNT, WS_WHERE, WS_BIG, WS_CSR, WS_SLOW, WS_NEED, WS_DEG, WS_OFFS, WS_CURSOR, WS_KEYS, WS_KEEP, WS_POS, WS_OWNER, WS_FINAL,
        WS_PARTIAL, WS_IDS, WS_NEAR, WS_HITS, WS_MINH, WS_OCNT, WS_OOFF, WS_OCUR, WS_ORDER, WS_MI1, WS_MICNT, WS_MICUR, WS_KREC, WS_SLOTMH, WS_RA_DEG, WS_RA_OFF, WS_RA_CUR, WS_RA_ENT, WS_RA_RM, WS_ORG_POOL, WS_ORG_OFF, WS_ORG_LEN, WS_ORG_IMG, WS_ORG_K0, WS_ORG_K1, WS_ORG_V0, WS_ORG_V1, WS_ORG_HIST, WS_ORG_HSCAN, WS_ORG_FLAG, WS_ORG_UID, WS_ORG_HEAD, WS_RR_IN, WS_RR_DEGP, WS_RR_OFFP, WS_RR_ENTP, WS_RR_OUTP, WS_RR_WIDX, WS_RR_RANK, WS_RR_CUR, WS_RA_HEAVY, WS_RA_HSIZE, WS_RA_HSCR, WS_RR_LEN, WS_RR_COFF, WS_RR_OUTC,
        WS_PT_K0, WS_PT_K1, WS_PT_P0, WS_PT_P1, WS_PT_M0, WS_PT_M1, WS_PT_CNT, WS_PT_BASE, WS_PT_OFF, WS_PT_GOFF, WS_RR_LOC, WS_RR_RANKL, WS_LOC_READS, WS_LOC_IDOF, WS_LOC_POSOF, WS_LOC_STATUS, WS_ORG_GFLAG, WS_ORG_GPOS, WS_LOC_META, WS_SLOW2, WS_RA_ENT32, WS_RA_SPLIT, WS_PRE_BASE, WS_PRE_NONE, WS_COUNT };   // ids of the workspace arena (Device::ws)
+struct MateLib { u64* key = nullptr; u64* cnt = nullptr; u64* first = nullptr; u64 n = 0; };      // one library's mate table: sorted by key, unique (kernels_mates.inc)
+struct Mates { MateLib lib[128]; u64* pkey = nullptr; u64* pord = nullptr; u64 pn = 0, pcap = 0; };   // + the pending records of the call in progress (keys, record ordinals)
 struct Device {
     int ordinal = 0;
     Options opt;                 // the environment switches, as the context read them when it was created (sage2ov_internal.h)
@@ -50,6 +52,7 @@ struct Device {
     u64 N = 0; int S = 0, maxL = 0, k = 0, h = 0; double probeShare = 1.0;
     u64* d_runStarts = nullptr; u64* h_runStarts = nullptr; hipEvent_t evRunStarts = nullptr; bool runStartsValid = false; double runStartFrac = 0.0;      // share of the reads without a predecessor in the locality order (counted by k_loc_index into d_runStarts)
     u64* reads = nullptr;        // (N+1)*S words, slot i = read id i
+    Mates* mates = nullptr;      // the mate-pair table (dev_mates_add): allocations of its own, dropped with the read set
     u32* findDir = nullptr; int findDirBits = 0;      // read-id lookup (dev_find_ids): first id per value of the top bits of word 0, built by the first call, dropped with the read set
     // the same reads in LOCALITY order (slot p = the read at position p of the order by global minimiser): what the index entries point at and
     // what the probe kernels gather from -- a read's overlap partners are neighbours in the genome, hence (mostly) neighbours here
@@ -191,6 +194,7 @@ static void mem_sample(Device* d) { size_t fr = 0, to = 0; if (hipMemGetInfo(&fr
 #include "kernels_convert.inc"
 #include "kernels_simplify.inc"
 #include "kernels_find.inc"
+#include "kernels_mates.inc"
 
 // =============================================================================================
 // host-side launchers
@@ -236,10 +240,12 @@ Device* dev_create(int ordinal, const Options& opt, std::string& err) {
     return d;
 }
 static void rr_staging_release(Device* d);
+static void mates_release(Device* d);
 static void free_reads(Device* d) {
     rr_staging_release(d);                     // (pinned host buffers sized by the previous read set)
     hipFree(d->reads);
     hipFree(d->findDir); d->findDir = nullptr; d->findDirBits = 0;      // (the lookup directory describes the read set that goes)
+    mates_release(d);                                                   // (so do the ids of the mate table)
     if (!d->resCarved) { hipFree(d->right); hipFree(d->left); hipFree(d->conn); hipFree(d->cflag); hipFree(d->status); hipFree(d->cand); }     // slots / csr / final_edges live in the workspace arena
     ph_release(d);                                                              // (diet mode: the phase block and what was carved out of it)
     for (auto& b : d->ws) { if (b.p && !b.epoch) hipFree(b.p); b.p = nullptr; b.cap = 0; b.epoch = 0; }
@@ -1512,27 +1518,29 @@ int dev_unresolved_ids(Device* d, std::vector<uint32_t>& ids, std::string& err) 
 // transient allocation of this call; the steps' results, their phase blocks and the workspace arena are not touched.  Returns 1 when no read store is resident
 // (the caller searches its host copy instead).
 constexpr u64 FIND_CHUNK_BYTES = 256ull << 20;      // ASCII per chunk, and the chunk's packed image
-int dev_find_ids(Device* d, const char* bases, const uint64_t* off, uint64_t n, int64_t* ids, FindStats* st, std::string& err) {
-    HIPCHK(hipSetDevice(d->ordinal));
-    const bool byPos = d->reads == nullptr;
-    if (byPos && !(d->readsLoc && d->posOf)) return 1;
-    const u64* store = byPos ? d->readsLoc : d->reads; const int S = d->S; const u64 N = d->N;
+struct FindTmp {                                                                     // transient buffers and events of one call (freed on every return path)
+    hipEvent_t ev[3] = {}; void* p[7] = {}; size_t cap[7] = {};
+    ~FindTmp() { for (auto e : ev) if (e) hipEventDestroy(e); for (auto q : p) if (q) hipFree(q); }
+    void* get(int i, size_t bytes) { if (cap[i] >= bytes && p[i]) return p[i]; if (p[i]) hipFree(p[i]); p[i] = nullptr; cap[i] = 0;
+                                     if (hipMalloc(&p[i], bytes) != hipSuccess) { (void)hipGetLastError(); p[i] = nullptr; return nullptr; } cap[i] = bytes; return p[i]; }
+};
+struct FindRun { const u64* store = nullptr; bool byPos = false; int S = 0; u64 qcap = 0; u32 maxLen = 0; };
+struct FindChunk { u64 q = 0; unsigned char* db = nullptr; u64* dof = nullptr; signed char* sign = nullptr; long long* dids = nullptr; u64* cnt = nullptr; };
+// what every call does once: which store, the directory (once per read set), the chunk bound.  Returns 1 when no read store is resident.
+static int find_begin(Device* d, FindTmp& T, FindRun& R, FindStats* st, std::string& err) {
+    R.byPos = d->reads == nullptr;
+    if (R.byPos && !(d->readsLoc && d->posOf)) return 1;
+    R.store = R.byPos ? d->readsLoc : d->reads; R.S = d->S; const int S = d->S; const u64 N = d->N;
     if (S != 4 && S != 8 && S != 16 && S != 32) { err = "unsupported words-per-read"; return SAGE2OV_ERR_INTERNAL; }
-    struct Tmp {                                                                     // (freed on every return path)
-        hipEvent_t ev[3] = {}; void* p[7] = {}; size_t cap[7] = {};
-        ~Tmp() { for (auto e : ev) if (e) hipEventDestroy(e); for (auto q : p) if (q) hipFree(q); }
-        void* get(int i, size_t bytes) { if (cap[i] >= bytes && p[i]) return p[i]; if (p[i]) hipFree(p[i]); p[i] = nullptr; cap[i] = 0;
-                                         if (hipMalloc(&p[i], bytes) != hipSuccess) { (void)hipGetLastError(); p[i] = nullptr; return nullptr; } cap[i] = bytes; return p[i]; }
-    } T;
     for (auto& e : T.ev) HIPCHK(hipEventCreate(&e));
-    *st = FindStats(); st->byPos = byPos;
+    *st = FindStats(); st->byPos = R.byPos;
     if (!d->findDir) {                                                               // the directory: once per read set
         int B = 0; while ((1ull << B) < N) B++;                                      // ceil(log2 N)
         B = std::min(FIND_B_MAX, std::max(FIND_B_MIN, B - 1));
         u32* dir = nullptr; HIPCHK(hipMalloc(&dir, ((size_t)(1u << B) + 1) * sizeof(u32)));
         HIPCHK(hipEventRecord(T.ev[0], d->stream));
-        if (byPos) hipLaunchKernelGGL(k_find_dir<true>, dim3(grid_for((1u << B) + 1, 256)), dim3(256), 0, d->stream, store, d->posOf, (u32)N, S, B, dir);
-        else hipLaunchKernelGGL(k_find_dir<false>, dim3(grid_for((1u << B) + 1, 256)), dim3(256), 0, d->stream, store, d->posOf, (u32)N, S, B, dir);
+        if (R.byPos) hipLaunchKernelGGL(k_find_dir<true>, dim3(grid_for((1u << B) + 1, 256)), dim3(256), 0, d->stream, R.store, d->posOf, (u32)N, S, B, dir);
+        else hipLaunchKernelGGL(k_find_dir<false>, dim3(grid_for((1u << B) + 1, 256)), dim3(256), 0, d->stream, R.store, d->posOf, (u32)N, S, B, dir);
         hipError_t e = hipGetLastError(); if (e == hipSuccess) e = hipEventRecord(T.ev[1], d->stream); if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
         if (e != hipSuccess) { hipFree(dir); err = std::string("read-id directory: ") + hipGetErrorString(e); return SAGE2OV_ERR_DEVICE; }
         float ms = 0; hipEventElapsedTime(&ms, T.ev[0], T.ev[1]); st->dir_ms = ms;
@@ -1540,42 +1548,267 @@ int dev_find_ids(Device* d, const char* bases, const uint64_t* off, uint64_t n, 
     }
     st->dirBits = (u32)d->findDirBits;
     const long long forced = d->opt.num("SAGE2OV_TEST_FIND_BATCH", 0);             // test-only: queries per chunk
-    const u64 qcap = forced > 0 ? (u64)forced : std::min<u64>(1ull << 22, FIND_CHUNK_BYTES / ((u64)S * sizeof(u64)));
+    R.qcap = forced > 0 ? (u64)forced : std::min<u64>(1ull << 22, FIND_CHUNK_BYTES / ((u64)S * sizeof(u64)));
     const u32 lenCap = (u32)((64 * S - (S > 16 ? 11 : 9)) / 2);                    // bases a slot of this layout holds
-    const u32 maxLen = std::min<u32>((u32)std::max(d->maxL, 0), lenCap);
-    std::vector<u64> ho;
-    for (u64 r0 = 0; r0 < n;) {
-        u64 r1 = r0 + 1; const u64 lastQ = std::min<u64>(n, r0 + qcap);
-        while (r1 < lastQ && off[r1 + 1] - off[r0] <= FIND_CHUNK_BYTES) r1++;
-        const u64 q = r1 - r0, nbytes = off[r1] - off[r0];
-        ho.resize(q + 1); for (u64 x = 0; x <= q; x++) ho[x] = off[r0 + x] - off[r0];
-        unsigned char* db = (unsigned char*)T.get(0, nbytes + 64); u64* dof = (u64*)T.get(1, (q + 1) * sizeof(u64)); u32* flag = (u32*)T.get(2, q * sizeof(u32));
-        u64* img = (u64*)T.get(3, q * S * sizeof(u64)); signed char* sign = (signed char*)T.get(4, q); long long* dids = (long long*)T.get(5, q * sizeof(long long));
-        u64* cnt = (u64*)T.get(6, 8 * sizeof(u64));
-        if (!db || !dof || !flag || !img || !sign || !dids || !cnt) { err = "read-id lookup: out of device memory"; return SAGE2OV_ERR_NOMEM; }
-        if (nbytes) HIPCHK(hipMemcpyAsync(db, bases + off[r0], nbytes, hipMemcpyHostToDevice, d->stream));
-        HIPCHK(hipMemcpyAsync(dof, ho.data(), (q + 1) * sizeof(u64), hipMemcpyHostToDevice, d->stream));
-        const u64 init[8] = {0, 0, 0, 0, ~0ull, 0, 0, 0}; HIPCHK(hipMemcpyAsync(cnt, init, sizeof init, hipMemcpyHostToDevice, d->stream));      // [0..5] k_org_classify, [6] found
-        HIPCHK(hipEventRecord(T.ev[0], d->stream));
-        hipLaunchKernelGGL(k_org_classify, dim3(grid_for(q, 256)), dim3(256), 0, d->stream, db, dof, (u64)q, (u32)d->k, maxLen, flag, cnt);
-        hipLaunchKernelGGL(k_find_pack, dim3(grid_for(q, 256)), dim3(256), 0, d->stream, db, dof, (u64)q, flag, S, img, sign);
-        HIPCHK(hipEventRecord(T.ev[1], d->stream));
-        const dim3 grid(grid_for(q * (u64)(S / 2), 256)), block(256); unsigned long long* fnd = (unsigned long long*)(cnt + 6);
+    R.maxLen = std::min<u32>((u32)std::max(d->maxL, 0), lenCap);
+    return 0;
+}
+// end of the chunk that starts at query r0: bounded in queries and in bytes, one query at least
+static u64 find_chunk_end(const FindRun& R, const uint64_t* off, u64 n, u64 r0) {
+    u64 r1 = r0 + 1; const u64 lastQ = std::min<u64>(n, r0 + R.qcap);
+    while (r1 < lastQ && off[r1 + 1] - off[r0] <= FIND_CHUNK_BYTES) r1++;
+    return r1;
+}
+// the body of one chunk, queries [r0, r1): upload, k_org_classify, k_find_pack, k_find_search.  The ids stay on the device (C.dids, with the sign bytes and
+// the counters [0..5] k_org_classify, [6] found); events T.ev[0..2] bracket pack and search.  Nothing is synchronised here.
+static int find_chunk(Device* d, FindTmp& T, const FindRun& R, const char* bases, const uint64_t* off, u64 r0, u64 r1, std::vector<u64>& ho, FindChunk& C, std::string& err) {
+    const int S = R.S; const bool byPos = R.byPos; const u64* store = R.store;
+    const u64 q = r1 - r0, nbytes = off[r1] - off[r0];
+    ho.resize(q + 1); for (u64 x = 0; x <= q; x++) ho[x] = off[r0 + x] - off[r0];
+    unsigned char* db = (unsigned char*)T.get(0, nbytes + 64); u64* dof = (u64*)T.get(1, (q + 1) * sizeof(u64)); u32* flag = (u32*)T.get(2, q * sizeof(u32));
+    u64* img = (u64*)T.get(3, q * S * sizeof(u64)); signed char* sign = (signed char*)T.get(4, q); long long* dids = (long long*)T.get(5, q * sizeof(long long));
+    u64* cnt = (u64*)T.get(6, 8 * sizeof(u64));
+    if (!db || !dof || !flag || !img || !sign || !dids || !cnt) { err = "read-id lookup: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+    if (nbytes) HIPCHK(hipMemcpyAsync(db, bases + off[r0], nbytes, hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipMemcpyAsync(dof, ho.data(), (q + 1) * sizeof(u64), hipMemcpyHostToDevice, d->stream));
+    const u64 init[8] = {0, 0, 0, 0, ~0ull, 0, 0, 0}; HIPCHK(hipMemcpyAsync(cnt, init, sizeof init, hipMemcpyHostToDevice, d->stream));      // [0..5] k_org_classify, [6] found
+    HIPCHK(hipEventRecord(T.ev[0], d->stream));
+    hipLaunchKernelGGL(k_org_classify, dim3(grid_for(q, 256)), dim3(256), 0, d->stream, db, dof, (u64)q, (u32)d->k, R.maxLen, flag, cnt);
+    hipLaunchKernelGGL(k_find_pack, dim3(grid_for(q, 256)), dim3(256), 0, d->stream, db, dof, (u64)q, flag, S, img, sign);
+    HIPCHK(hipEventRecord(T.ev[1], d->stream));
+    const dim3 grid(grid_for(q * (u64)(S / 2), 256)), block(256); unsigned long long* fnd = (unsigned long long*)(cnt + 6);
 #define S2_FIND(SS) do { if (byPos) hipLaunchKernelGGL((k_find_search<SS, true>), grid, block, 0, d->stream, store, d->posOf, d->findDir, d->findDirBits, img, sign, (u32)q, dids, fnd); \
                          else hipLaunchKernelGGL((k_find_search<SS, false>), grid, block, 0, d->stream, store, d->posOf, d->findDir, d->findDirBits, img, sign, (u32)q, dids, fnd); } while (0)
-        if (S == 4) S2_FIND(4); else if (S == 8) S2_FIND(8); else if (S == 16) S2_FIND(16); else S2_FIND(32);
+    if (S == 4) S2_FIND(4); else if (S == 8) S2_FIND(8); else if (S == 16) S2_FIND(16); else S2_FIND(32);
 #undef S2_FIND
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(T.ev[2], d->stream));
-        u64 hc[8];
-        HIPCHK(hipMemcpyAsync(ids + r0, dids, q * sizeof(long long), hipMemcpyDeviceToHost, d->stream));
-        HIPCHK(hipMemcpyAsync(hc, cnt, sizeof hc, hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(T.ev[2], d->stream));
+    C.q = q; C.db = db; C.dof = dof; C.sign = sign; C.dids = dids; C.cnt = cnt;
+    return 0;
+}
+int dev_find_ids(Device* d, const char* bases, const uint64_t* off, uint64_t n, int64_t* ids, FindStats* st, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    FindTmp T; FindRun R;
+    { const int rc = find_begin(d, T, R, st, err); if (rc) return rc; }
+    std::vector<u64> ho;
+    for (u64 r0 = 0; r0 < n;) {
+        const u64 r1 = find_chunk_end(R, off, n, r0); FindChunk C;
+        { const int rc = find_chunk(d, T, R, bases, off, r0, r1, ho, C, err); if (rc) return rc; }
+        const u64 q = C.q; u64 hc[8];
+        HIPCHK(hipMemcpyAsync(ids + r0, C.dids, q * sizeof(long long), hipMemcpyDeviceToHost, d->stream));
+        HIPCHK(hipMemcpyAsync(hc, C.cnt, sizeof hc, hipMemcpyDeviceToHost, d->stream));
         HIPCHK(hipStreamSynchronize(d->stream));
         float a = 0, b = 0; hipEventElapsedTime(&a, T.ev[0], T.ev[1]); hipEventElapsedTime(&b, T.ev[1], T.ev[2]);
         st->pack_ms += a; st->search_ms += b; st->launches++;
         st->found += hc[6]; st->not_good += q - hc[1] - hc[5];                       // hc[1]: good and no longer than the store's longest; hc[5]: good but longer
         r0 = r1;
     }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the mate-pair table (kernels_mates.inc)
+// MatePair::processMatePairs (matePair.cpp:161-239) on the device.  The table of a library (keys, counts, firsts: sorted by key, unique) and the pending
+// records of the call in progress live in allocations of their own (Device::mates): not in the phase block, not in the workspace arena, so the steps and
+// the table never see each other.  Everything else is a transient allocation of the call.
+constexpr u64 MATE_FLUSH_RECORDS = 1ull << 25;      // pending records at which a flush runs: one sort stays far below 2^32 records (k_rs_scatter's positions are u32)
+struct MateBufs {                                    // transient device buffers of one flush (freed on every return path)
+    std::vector<void*> p;
+    ~MateBufs() { for (void* q : p) if (q) hipFree(q); }
+    template <class T> T* get(u64 n) { void* q = nullptr; if (hipMalloc(&q, std::max<u64>(n, 1) * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); return nullptr; } p.push_back(q); return (T*)q; }
+    void release(void* q) { for (auto& x : p) if (x == q) { hipFree(x); x = nullptr; } }
+    void keep(void* q) { for (auto& x : p) if (x == q) x = nullptr; }              // ownership goes to the table
+};
+struct MateLap {                                     // HIP-event time of a stretch of the stream (synchronises at the end of it)
+    hipEvent_t a = nullptr, b = nullptr; hipStream_t st;
+    explicit MateLap(hipStream_t s) : st(s) { hipEventCreate(&a); hipEventCreate(&b); }
+    ~MateLap() { if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); }
+    void start() { hipEventRecord(a, st); }
+    hipError_t stop(double& acc) { hipError_t e = hipEventRecord(b, st); if (e == hipSuccess) e = hipStreamSynchronize(st); if (e == hipSuccess) { float ms = 0; hipEventElapsedTime(&ms, a, b); acc += ms; } return e; }
+};
+static Mates* mates_of(Device* d) { if (!d->mates) d->mates = new Mates(); return d->mates; }
+static void mates_drop_pending(Mates* m) { hipFree(m->pkey); hipFree(m->pord); m->pkey = m->pord = nullptr; m->pn = m->pcap = 0; }
+static void mates_release(Device* d) {
+    if (!d->mates) return;
+    for (auto& L : d->mates->lib) { hipFree(L.key); hipFree(L.cnt); hipFree(L.first); }
+    mates_drop_pending(d->mates); delete d->mates; d->mates = nullptr;
+}
+void dev_mates_clear(Device* d) { hipSetDevice(d->ordinal); mates_release(d); }
+void dev_mates_abort(Device* d) { if (d->mates) { hipSetDevice(d->ordinal); mates_drop_pending(d->mates); } }
+uint64_t dev_mates_count(Device* d, int library) { return d->mates ? d->mates->lib[library].n : 0; }
+// the 8-bit digits of a key (from:30 | to:30 | t_from:1 | t_to:1) that can be non-zero when no id exceeds N: `to` and the types end at bit 2 + b, `from` at 32 + b
+static int mate_passes(u64 N, int* shifts) {
+    int b = 0; while ((N >> b) != 0) b++;                                            // ceil(log2(N + 1))
+    int np = 0;
+    for (int p = 0; p < 8; p++) { const int lo = 8 * p; if (lo < 2 + b || (lo >= 32 && lo < 32 + b)) shifts[np++] = lo; }
+    return np;
+}
+// exclusive scan with a partial buffer of the caller's (scan_u32 uses the workspace arena, which belongs to the steps)
+static int mate_scan(Device* d, MateBufs& B, const u32* in, u64 n, u32* out, u64* total, std::string& err) {
+    const u64 nb = (n + SCAN_BLOCK - 1) / SCAN_BLOCK;
+    u64* partial = B.get<u64>(nb + 1); if (!partial) { err = "mate table: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+    hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, d->stream, in, (u64)n, partial);
+    hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(1024), 0, d->stream, partial, (u64)nb, partial + nb);
+    hipLaunchKernelGGL(k_scan_final, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, d->stream, in, (u64)n, partial, out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(total, partial + nb, sizeof(u64), hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    B.release(partial);
+    return 0;
+}
+// stable LSD sort of (key, index 0 .. n-1) by the passes of mate_passes; the sorted keys and indices come back in *ks / *vs (buffers of B)
+static int mate_sort(Device* d, MateBufs& B, u64* k0, u32 n, const int* shifts, int np, u64** ks, u32** vs, MateStats* st, std::string& err) {
+    const u32 nb = (n + RS_TILE - 1) / RS_TILE;
+    u64* k1 = B.get<u64>(n); u32* v0 = B.get<u32>(n); u32* v1 = B.get<u32>(n); u32* hist = B.get<u32>((u64)256 * nb + 2); u32* hscan = B.get<u32>((u64)256 * nb + 2);
+    if (!k1 || !v0 || !v1 || !hist || !hscan) { err = "mate table: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+    hipLaunchKernelGGL(k_mate_iota, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, v0, n);
+    u64 *ka = k0, *kb = k1; u32 *va = v0, *vb = v1;
+    for (int p = 0; p < np; p++) {
+        hipLaunchKernelGGL(k_rs_hist, dim3(nb), dim3(64), 0, d->stream, ka, (u64)n, shifts[p], hist, nb);
+        u64 tot = 0; const int rc = mate_scan(d, B, hist, (u64)256 * nb, hscan, &tot, err); if (rc) return rc;
+        hipLaunchKernelGGL(k_rs_scatter, dim3(nb), dim3(64), 0, d->stream, ka, va, (u64)n, shifts[p], hscan, nb, kb, vb);
+        std::swap(ka, kb); std::swap(va, vb); st->passes++;
+    }
+    HIPCHK(hipGetLastError());
+    B.release(hist); B.release(hscan); B.release(vb); if (kb != k0) B.release(kb);
+    *ks = ka; *vs = va;
+    return 0;
+}
+// heads of the sorted keys: hp[e] = position of the e-th distinct key, hp[E] = n
+static int mate_heads(Device* d, MateBufs& B, const u64* keys, u32 n, u32** hp_out, u32* E_out, std::string& err) {
+    u32* flag = B.get<u32>(n); u32* pos = B.get<u32>(n);
+    if (!flag || !pos) { err = "mate table: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+    hipLaunchKernelGGL(k_mate_heads, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, keys, n, flag);
+    u64 E = 0; { const int rc = mate_scan(d, B, flag, n, pos, &E, err); if (rc) return rc; }
+    u32* hp = B.get<u32>(E + 1); if (!hp) { err = "mate table: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+    hipLaunchKernelGGL(k_mate_headpos, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, flag, pos, n, hp, (u32)E);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(d->stream));
+    B.release(flag); B.release(pos);
+    *hp_out = hp; *E_out = (u32)E;
+    return 0;
+}
+// sort, reduce and merge the pending records into the library's table
+int dev_mates_flush(Device* d, int library, MateStats* st, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    Mates* M = d->mates; if (!M || !M->pn) { if (M) mates_drop_pending(M); return 0; }
+    MateLib& L = M->lib[library]; const u32 n = (u32)M->pn;
+    int shifts[8]; const int np = mate_passes(d->N, shifts);
+    MateBufs B; MateLap lap(d->stream);
+    u64 *ks = nullptr; u32 *vs = nullptr, *hp = nullptr; u32 E = 0;
+    lap.start();
+    { const int rc = mate_sort(d, B, M->pkey, n, shifts, np, &ks, &vs, st, err); if (rc) return rc; }
+    HIPCHK(lap.stop(st->sort_ms));
+    lap.start();
+    { const int rc = mate_heads(d, B, ks, n, &hp, &E, err); if (rc) return rc; }
+    u64* ek = B.get<u64>((u64)E + L.n); u64* ec = B.get<u64>((u64)E + L.n); u64* ef = B.get<u64>((u64)E + L.n);      // (room for the table behind the new entries: the merge's input)
+    if (!ek || !ec || !ef) { err = "mate table: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+    hipLaunchKernelGGL(k_mate_reduce, dim3(grid_for(E, 256)), dim3(256), 0, d->stream, ks, vs, M->pord, hp, E, ek, ec, ef);
+    HIPCHK(hipGetLastError());
+    HIPCHK(lap.stop(st->reduce_ms));
+    if (ks != M->pkey) B.release(ks); B.release(vs); B.release(hp);
+    mates_drop_pending(M);
+    st->flushes++;
+    if (!L.n) {                                                                      // a library's first entries: they are its table
+        B.keep(ek); B.keep(ec); B.keep(ef); L.key = ek; L.cnt = ec; L.first = ef; L.n = E;
+        return 0;
+    }
+    if ((u64)E + L.n >= (1ull << 32) - RS_TILE) { err = "mate table: more than 2^32 entries in one library"; return SAGE2OV_ERR_LIMIT; }
+    lap.start();
+    const u32 m = E + (u32)L.n;
+    HIPCHK(hipMemcpyAsync(ek + E, L.key, L.n * sizeof(u64), hipMemcpyDeviceToDevice, d->stream));
+    HIPCHK(hipMemcpyAsync(ec + E, L.cnt, L.n * sizeof(u64), hipMemcpyDeviceToDevice, d->stream));
+    HIPCHK(hipMemcpyAsync(ef + E, L.first, L.n * sizeof(u64), hipMemcpyDeviceToDevice, d->stream));
+    { const int rc = mate_sort(d, B, ek, m, shifts, np, &ks, &vs, st, err); if (rc) return rc; }
+    u32 E2 = 0; { const int rc = mate_heads(d, B, ks, m, &hp, &E2, err); if (rc) return rc; }
+    u64* nk = B.get<u64>(E2); u64* nc = B.get<u64>(E2); u64* nf = B.get<u64>(E2);
+    if (!nk || !nc || !nf) { err = "mate table: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+    hipLaunchKernelGGL(k_mate_merge, dim3(grid_for(E2, 256)), dim3(256), 0, d->stream, ks, vs, ec, ef, hp, E2, nk, nc, nf);
+    HIPCHK(hipGetLastError());
+    HIPCHK(lap.stop(st->merge_ms));
+    hipFree(L.key); hipFree(L.cnt); hipFree(L.first);
+    B.keep(nk); B.keep(nc); B.keep(nf); L.key = nk; L.cnt = nc; L.first = nf; L.n = E2;
+    return 0;
+}
+// One readsArray of processMatePairs: reads [0, n) of the call, n even (the caller drops a trailing odd read), pair0 = ordinal of the call's first pair in
+// its library.  The chunks hold an even number of queries, so a pair is never cut from its ids.  Records collect in the pending buffer, which is flushed at
+// MATE_FLUSH_RECORDS (SAGE2OV_TEST_MATE_FLUSH: a bound for tests); the caller ends its call with dev_mates_flush.  Returns 1 (and does nothing) when no
+// read store is resident.
+int dev_mates_add(Device* d, const char* bases, const uint64_t* off, uint64_t n, int library, uint64_t pair0, MateStats* st, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    if (d->N >= (1ull << 30)) { err = "mate table: read ids beyond 2^30 - 1"; return SAGE2OV_ERR_LIMIT; }
+    FindTmp T; FindRun R; FindStats fs;
+    { const int rc = find_begin(d, T, R, &fs, err); if (rc) return rc; }
+    st->find_ms += fs.dir_ms;
+    R.qcap = std::min<u64>((R.qcap + 1) & ~1ull, 1ull << 22);                      // an even number of queries per chunk (a forced odd value: the next even one)
+    const long long forced = d->opt.num("SAGE2OV_TEST_MATE_FLUSH", 0);
+    const u64 bound = forced > 0 ? (u64)forced : MATE_FLUSH_RECORDS;
+    Mates* M = mates_of(d); MateLap lap(d->stream);
+    std::vector<u64> ho;
+    for (u64 r0 = 0; r0 < n;) {
+        u64 r1 = find_chunk_end(R, off, n, r0); if ((r1 - r0) & 1) r1++;            // (n is even: r1 <= n)
+        FindChunk C;
+        { const int rc = find_chunk(d, T, R, bases, off, r0, r1, ho, C, err); if (rc) return rc; }
+        HIPCHK(hipStreamSynchronize(d->stream));
+        { float a = 0; hipEventElapsedTime(&a, T.ev[0], T.ev[2]); st->find_ms += a; }
+        st->chunks++;
+        const u32 np = (u32)(C.q / 2);
+        lap.start();
+        MateBufs B; u32* keep = B.get<u32>(np); u32* pos = B.get<u32>(np);
+        if (!keep || !pos) { err = "mate table: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+        unsigned long long* kinds = (unsigned long long*)(C.cnt + 6); HIPCHK(hipMemsetAsync(kinds, 0, 2 * sizeof(u64), d->stream));      // ([6], [7] of the chunk's counters: read above, free now)
+        hipLaunchKernelGGL(k_mate_keep, dim3(grid_for(np, 256)), dim3(256), 0, d->stream, C.dids, C.sign, C.db, C.dof, np, (u32)d->k, R.maxLen, keep, kinds);
+        u64 nrec = 0; { const int rc = mate_scan(d, B, keep, np, pos, &nrec, err); if (rc) return rc; }
+        u64 hk[2]; HIPCHK(hipMemcpyAsync(hk, kinds, sizeof hk, hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
+        st->seen += np; st->not_good += hk[0]; st->not_found += hk[1]; st->added += nrec / 2;
+        if (M->pn + nrec > M->pcap) {                                                // grow the pending buffer (its records are kept)
+            const u64 cap = std::max<u64>(M->pn + nrec, std::min<u64>(2 * M->pcap, bound + (1ull << 22)));
+            u64 *nk = nullptr, *no = nullptr;
+            if (hipMalloc(&nk, cap * sizeof(u64)) != hipSuccess || hipMalloc(&no, cap * sizeof(u64)) != hipSuccess) { (void)hipGetLastError(); hipFree(nk); err = "mate table: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+            if (M->pn) { hipMemcpyAsync(nk, M->pkey, M->pn * sizeof(u64), hipMemcpyDeviceToDevice, d->stream); hipMemcpyAsync(no, M->pord, M->pn * sizeof(u64), hipMemcpyDeviceToDevice, d->stream); }
+            hipError_t e = hipStreamSynchronize(d->stream);
+            hipFree(M->pkey); hipFree(M->pord); M->pkey = nk; M->pord = no; M->pcap = cap;
+            if (e != hipSuccess) { err = std::string("mate table: ") + hipGetErrorString(e); return SAGE2OV_ERR_DEVICE; }
+        }
+        if (nrec) hipLaunchKernelGGL(k_mate_records, dim3(grid_for(np, 256)), dim3(256), 0, d->stream, C.dids, keep, pos, np, 2ull * (pair0 + r0 / 2), M->pkey + M->pn, M->pord + M->pn);
+        HIPCHK(hipGetLastError());
+        HIPCHK(lap.stop(st->records_ms));
+        M->pn += nrec;
+        if (M->pn >= bound) { const int rc = dev_mates_flush(d, library, st, err); if (rc) return rc; }
+        r0 = r1;
+    }
+    return 0;
+}
+// the table of a library as it lies on the device: n = dev_mates_count entries each; offsets: N + 2 values (k_mate_offsets), or null
+int dev_mates_export(Device* d, int library, uint64_t* key, uint64_t* cnt, uint64_t* first, uint64_t* offsets, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    static const MateLib none; const MateLib& L = d->mates ? d->mates->lib[library] : none;
+    if (L.n) {
+        HIPCHK(hipMemcpyAsync(key, L.key, L.n * sizeof(u64), hipMemcpyDeviceToHost, d->stream));
+        HIPCHK(hipMemcpyAsync(cnt, L.cnt, L.n * sizeof(u64), hipMemcpyDeviceToHost, d->stream));
+        HIPCHK(hipMemcpyAsync(first, L.first, L.n * sizeof(u64), hipMemcpyDeviceToHost, d->stream));
+    }
+    if (offsets) {
+        MateBufs B; u64* dofs = B.get<u64>(d->N + 2); if (!dofs) { err = "mate table: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+        hipLaunchKernelGGL(k_mate_offsets, dim3(grid_for(d->N + 2, 256)), dim3(256), 0, d->stream, L.key, (u32)L.n, (u32)d->N, dofs);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(offsets, dofs, (d->N + 2) * sizeof(u64), hipMemcpyDeviceToHost, d->stream));
+        HIPCHK(hipStreamSynchronize(d->stream));
+    }
+    HIPCHK(hipStreamSynchronize(d->stream));
+    return 0;
+}
+// a table built on the host moves to the device (a context whose device had no store resident when the table was begun)
+int dev_mates_import(Device* d, int library, const uint64_t* key, const uint64_t* cnt, const uint64_t* first, uint64_t n, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    MateLib& L = mates_of(d)->lib[library];
+    hipFree(L.key); hipFree(L.cnt); hipFree(L.first); L = MateLib();
+    if (!n) return 0;
+    HIPCHK(hipMalloc(&L.key, n * sizeof(u64))); HIPCHK(hipMalloc(&L.cnt, n * sizeof(u64))); HIPCHK(hipMalloc(&L.first, n * sizeof(u64)));
+    HIPCHK(hipMemcpyAsync(L.key, key, n * sizeof(u64), hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipMemcpyAsync(L.cnt, cnt, n * sizeof(u64), hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipMemcpyAsync(L.first, first, n * sizeof(u64), hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    L.n = n;
     return 0;
 }
 

@@ -106,6 +106,17 @@ struct sage2ov_ctx {
     bool indexBuilt = false, probed = false, reciprocalDone = false, reduced = false, converted = false;
     sage2ov_index_stats istats{};
     sage2ov_find_stats fstats{};                       // of the last sage2ov_reads_find_ids
+    // ---- the mate-pair table (sage2ov_mates_*): per library either on the device (mateOnDevice) or here, sorted by key and unique
+    struct MateLib { std::vector<uint64_t> key, cnt, first; };
+    std::vector<MateLib> mates = std::vector<MateLib>(128); bool mateOnDevice[128] = {};
+    uint64_t matePairs[128] = {};                      // pairs given to each library so far, skipped ones included: the base of the record ordinals
+    uint32_t mateLibraries = 0;                        // highest library in use (numberOfLibrary)
+    sage2ov_mate_stats mstats{};                       // of the last add call
+    void mates_forget() {                              // the read set goes: its ids mean nothing any more (the device drops its part in free_reads)
+        for (auto& L : mates) L = MateLib();
+        for (int i = 0; i < 128; i++) { mateOnDevice[i] = false; matePairs[i] = 0; }
+        mateLibraries = 0; mstats = sage2ov_mate_stats{};
+    }
     sage2ov_overlap_stats ostats{};
     std::vector<FinalEdge> edges; bool edgesOnHost = false;
     SimplifiedGraph g4; bool g4Valid = false;
@@ -687,11 +698,11 @@ int sage2ov_reads_add_synth(sage2ov_ctx* c, const sage2ov_synth_params* p, const
 
 static int upload(sage2ov_ctx* c) {
     if (c->gpu() && !c->device()) return c->fail(SAGE2OV_ERR_DEVICE, c->devErr);
-    if (!c->device()) { c->organized = true; return SAGE2OV_OK; }      // step-1-only context (SAGE2OV_DEVICE_NONE)
+    if (!c->device()) { c->organized = true; c->mates_forget(); return SAGE2OV_OK; }      // step-1-only context (SAGE2OV_DEVICE_NONE)
     int minL = c->N ? 0xFFFF : 0; for (uint64_t i = 1; i <= c->N; i++) minL = std::min<int>(minL, c->len[i]);
     int rc = dev_upload_reads(c->device(), c->words.data(), c->N, c->S, minL, c->maxL, (int)c->cfg.min_overlap, c->err);
     if (rc) return rc;
-    c->organized = true; c->indexBuilt = c->probed = c->reciprocalDone = c->reduced = c->converted = false;
+    c->organized = true; c->mates_forget(); c->indexBuilt = c->probed = c->reciprocalDone = c->reduced = c->converted = false;
     return SAGE2OV_OK;
 }
 // a slot of S words holds the bases and, in the low 9 bits of its last word, the length: 123 / 251 / 507 bases for S = 4 / 8 / 16
@@ -721,7 +732,7 @@ int sage2ov_reads_organize(sage2ov_ctx* c) {                                    
         #pragma omp parallel for num_threads(nthr)
         for (uint64_t i = 1; i <= N; i++) c->len[i] = (uint16_t)(c->words[i * c->S + c->S - 1] & SLOT_LEN_MASK);
         std::vector<char>().swap(c->ascii); std::vector<uint64_t>().swap(c->asciiOff);
-        c->organized = true; c->indexBuilt = c->probed = c->reciprocalDone = c->reduced = c->converted = false;
+        c->organized = true; c->mates_forget(); c->indexBuilt = c->probed = c->reciprocalDone = c->reduced = c->converted = false;
         return SAGE2OV_OK;
     }
     const uint64_t n = c->poolLen.size(); HostLap lap(c, "step 1");
@@ -743,7 +754,7 @@ int sage2ov_reads_organize(sage2ov_ctx* c) {                                    
         for (uint64_t i = 1; i <= N; i++) c->len[i] = (uint16_t)(c->words[i * c->S + c->S - 1] & SLOT_LEN_MASK);
         RawU64().swap(c->pool); RawU64().swap(c->poolOff); RawU16().swap(c->poolLen);
         lap("lengths + release of the staging");
-        c->organized = true; c->indexBuilt = c->probed = c->reciprocalDone = c->reduced = c->converted = false;
+        c->organized = true; c->mates_forget(); c->indexBuilt = c->probed = c->reciprocalDone = c->reduced = c->converted = false;
         return SAGE2OV_OK;
     }
     #pragma omp parallel for num_threads(nthr)
@@ -992,6 +1003,214 @@ int sage2ov_reads_find_ids(sage2ov_ctx* c, const char* bases, const uint64_t* of
     return SAGE2OV_OK;
 }
 int sage2ov_reads_find_stats_get(const sage2ov_ctx* c, sage2ov_find_stats* o) { if (!c || !o) return SAGE2OV_ERR_ARG; *o = c->fstats; return SAGE2OV_OK; }
+// ------------------------------------------------------------------------------------------ the mate-pair table
+// MatePair::processMatePairs (matePair.cpp:161-239) as run with one thread; the semantics are stated in sage2ov.h.  A GPU context with a resident read store
+// builds the table on the device (dev_mates_add); a device-less context, or a GPU context with no store resident, here: find_ids_host, the
+// records (key = from:30 | to:30 | t_from:1 | t_to:1, ordinal) sorted, runs of equal keys reduced, the result merged into the library's sorted table.
+namespace {
+struct MateCall {                                      // one add call (one dataset of a list)
+    int lib = 0; bool onDevice = false, routeKnown = false; MateStats ds; uint64_t before = 0;
+    std::vector<std::pair<uint64_t, uint64_t>> rec;    // host route: (key, ordinal) of the call's records
+    std::vector<int64_t> ids;
+};
+uint64_t mates_entries(sage2ov_ctx* c, int lib) { return c->mateOnDevice[lib] ? dev_mates_count(c->device(), lib) : c->mates[lib].key.size(); }
+// the library's table goes where this call runs (only a context whose device lost or gained its read store between two calls ever moves one)
+int mates_place(sage2ov_ctx* c, int lib, bool onDevice) {
+    if (c->mateOnDevice[lib] == onDevice) return SAGE2OV_OK;
+    auto& L = c->mates[lib]; Device* d = c->device();
+    if (onDevice) {
+        if (!L.key.empty()) { const int rc = dev_mates_import(d, lib, L.key.data(), L.cnt.data(), L.first.data(), L.key.size(), c->err); if (rc) return rc; }
+        L = sage2ov_ctx::MateLib();
+    } else {
+        const uint64_t n = dev_mates_count(d, lib); L.key.resize(n); L.cnt.resize(n); L.first.resize(n);
+        int rc = dev_mates_export(d, lib, L.key.data(), L.cnt.data(), L.first.data(), nullptr, c->err); if (rc) return rc;
+        rc = dev_mates_import(d, lib, nullptr, nullptr, nullptr, 0, c->err); if (rc) return rc;
+    }
+    c->mateOnDevice[lib] = onDevice;
+    return SAGE2OV_OK;
+}
+int mates_begin(sage2ov_ctx* c, int lib, MateCall& M) {
+    M.lib = lib; M.before = mates_entries(c, lib);
+    c->mstats = sage2ov_mate_stats{}; c->mstats.library = (uint32_t)lib; c->mstats.libraries = c->mateLibraries;
+    c->mstats.entries_before = c->mstats.entries_after = M.before;
+    return SAGE2OV_OK;
+}
+// one readsArray: reads [0, n) with n even
+int mates_batch(sage2ov_ctx* c, MateCall& M, const char* bases, const uint64_t* off, uint64_t n) {
+    if (n == 0) return SAGE2OV_OK;
+    const int lib = M.lib; const uint64_t pair0 = c->matePairs[lib];
+    if (!M.routeKnown) {                                                               // the first batch decides the route of the call
+        int route = 1;
+        if (Device* d = c->device()) {
+            if (!c->mateOnDevice[lib]) { const int rc = mates_place(c, lib, true); if (rc) return rc; }
+            route = dev_mates_add(d, bases, off, n, lib, pair0, &M.ds, c->err);
+            if (route < 0) return route;
+            if (route == 1) { const int rc = mates_place(c, lib, false); if (rc) return rc; }
+        }
+        M.routeKnown = true; M.onDevice = route == 0;
+        if (M.onDevice) { c->matePairs[lib] += n / 2; return SAGE2OV_OK; }
+    } else if (M.onDevice) {
+        const int rc = dev_mates_add(c->device(), bases, off, n, lib, pair0, &M.ds, c->err);
+        if (rc) return rc < 0 ? rc : c->fail(SAGE2OV_ERR_DEVICE, "mate table: the read store left the device during a call");
+        c->matePairs[lib] += n / 2; return SAGE2OV_OK;
+    }
+    M.ids.resize(n); sage2ov_find_stats fs{};
+    find_ids_host(c, bases, off, n, M.ids.data(), fs);
+    const uint64_t k = c->cfg.min_overlap;
+    for (uint64_t j = 0; j < n / 2; j++) {
+        const int64_t a = M.ids[2 * j], b = M.ids[2 * j + 1];
+        M.ds.seen++;
+        if (!a || !b) {                                                                // not a good read (matePair.cpp:176), or a good read that is not in the store
+            bool bad = false;
+            for (uint64_t m = 2 * j; m < 2 * j + 2 && !bad; m++) {
+                if (M.ids[m]) continue;
+                const unsigned char* s = (const unsigned char*)bases + off[m]; const uint64_t Ls = off[m + 1] - off[m];
+                bad = Ls <= k; for (uint64_t i = 0; i < Ls && !bad; i++) bad = g_code[s[i]] > 3;
+            }
+            if (bad) M.ds.not_good++; else M.ds.not_found++;
+            continue;
+        }
+        const uint64_t id1 = (uint64_t)llabs(a), id2 = (uint64_t)llabs(b), t1 = a > 0, t2 = b > 0, o = 2 * (pair0 + j);      // :180-189
+        M.rec.emplace_back((id1 << 32) | (id2 << 2) | (t1 << 1) | t2, o);
+        M.rec.emplace_back((id2 << 32) | (id1 << 2) | (t2 << 1) | t1, o + 1);
+        M.ds.added++;
+    }
+    c->matePairs[lib] += n / 2;
+    return SAGE2OV_OK;
+}
+int mates_end(sage2ov_ctx* c, MateCall& M, int rc) {
+    const int lib = M.lib;
+    if (M.onDevice) { if (rc == SAGE2OV_OK) rc = dev_mates_flush(c->device(), lib, &M.ds, c->err); if (rc != SAGE2OV_OK) dev_mates_abort(c->device()); }
+    else if (rc == SAGE2OV_OK && !M.rec.empty()) {
+        __gnu_parallel::sort(M.rec.begin(), M.rec.end(), std::less<std::pair<uint64_t, uint64_t>>(), __gnu_parallel::default_parallel_tag(io_threads(c)));
+        auto& L = c->mates[lib]; sage2ov_ctx::MateLib out; size_t t = 0; const size_t nr = M.rec.size(), nt = L.key.size();
+        for (size_t i = 0; i < nr;) {                                                  // a run of equal keys = one entry; the table's entries below it first
+            size_t e = i + 1; while (e < nr && M.rec[e].first == M.rec[i].first) e++;
+            const uint64_t key = M.rec[i].first;
+            for (; t < nt && L.key[t] < key; t++) { out.key.push_back(L.key[t]); out.cnt.push_back(L.cnt[t]); out.first.push_back(L.first[t]); }
+            uint64_t cnt = e - i, first = M.rec[i].second;
+            if (t < nt && L.key[t] == key) { cnt += L.cnt[t]; first = std::min(first, L.first[t]); t++; }
+            out.key.push_back(key); out.cnt.push_back(cnt); out.first.push_back(first);
+            i = e;
+        }
+        for (; t < nt; t++) { out.key.push_back(L.key[t]); out.cnt.push_back(L.cnt[t]); out.first.push_back(L.first[t]); }
+        L = std::move(out);
+    }
+    if (M.ds.seen) c->mateLibraries = std::max<uint32_t>(c->mateLibraries, (uint32_t)lib);
+    sage2ov_mate_stats& s = c->mstats;
+    s.pairs_seen = M.ds.seen; s.pairs_added = M.ds.added; s.pairs_not_good = M.ds.not_good; s.pairs_not_found = M.ds.not_found; s.records = 2 * M.ds.added;
+    s.entries_after = mates_entries(c, lib); s.libraries = c->mateLibraries;
+    s.chunks = M.ds.chunks; s.sort_passes = M.ds.passes; s.flushes = M.ds.flushes; s.route = M.onDevice ? SAGE2OV_MATE_ROUTE_DEVICE : SAGE2OV_MATE_ROUTE_HOST;
+    s.find_ms = M.ds.find_ms; s.records_ms = M.ds.records_ms; s.sort_ms = M.ds.sort_ms; s.reduce_ms = M.ds.reduce_ms; s.merge_ms = M.ds.merge_ms;
+    return rc;
+}
+int mates_check(sage2ov_ctx* c, const char* who, int lib) {
+    if (!c->organized) return c->fail(SAGE2OV_ERR_ARG, std::string(who) + ": organise (or load) the reads first");
+    if (lib < 1 || lib > 127) return c->fail(SAGE2OV_ERR_ARG, std::string(who) + ": the library must be 1 .. 127");
+    if (c->gpu() && !c->device()) return c->fail(SAGE2OV_ERR_DEVICE, c->devErr);
+    return SAGE2OV_OK;
+}
+// mapMatePairs (matePair.cpp:125-159): the file(s) through the sequential reader, two files in turn by parity (inputReader.cpp:26-49), in batches of an even
+// number of reads so that the pairing is that of one continuous stream; the file is never staged whole
+int mates_add_files(sage2ov_ctx* c, const char* p1, const char* p2, int lib) {
+    SeqFile f1, f2; if (!f1.open(p1)) return c->fail(SAGE2OV_ERR_IO, std::string("cannot open ") + p1);
+    const bool two = p2 && *p2; if (two && !f2.open(p2)) return c->fail(SAGE2OV_ERR_IO, std::string("cannot open ") + p2);
+    const long long forced = c->opt.num("SAGE2OV_TEST_MATE_FILE_BATCH", 0);           // test-only: reads per batch (made even)
+    const size_t BATCH = forced > 0 ? (size_t)((forced + 1) & ~1ll) : (size_t)1 << 20;
+    MateCall M; int rc = mates_begin(c, lib, M);
+    std::string flat; std::vector<uint64_t> boff; uint64_t inFile = 0; bool more = true;
+    while (more && rc == SAGE2OV_OK) {
+        flat.clear(); boff.clear(); boff.push_back(0);
+        while (boff.size() <= BATCH) {
+            SeqFile& f = (two && (inFile & 1)) ? f2 : f1;
+            size_t len = 0;
+            if (!f.next(flat, len)) { more = false; break; }
+            boff.push_back(flat.size()); inFile++;
+        }
+        const uint64_t nb = (boff.size() - 1) & ~1ull;                                 // (only the last batch can be odd: its last read has no mate, :172)
+        rc = mates_batch(c, M, flat.data(), boff.data(), nb);
+    }
+    for (SeqFile* f : {&f1, &f2}) if (rc == SAGE2OV_OK && f->ioError) {
+        int en = 0; const char* m = f->fp ? gzerror(f->fp, &en) : nullptr;
+        rc = c->fail(SAGE2OV_ERR_IO, std::string("read error in ") + (f == &f1 ? p1 : p2) + ": " + (m && *m ? m : "corrupt or truncated input"));
+    }
+    return mates_end(c, M, rc);
+}
+}  // namespace
+int sage2ov_mates_add_ascii(sage2ov_ctx* c, const char* bases, const uint64_t* off, uint64_t n, int library) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    { const int rc = mates_check(c, "sage2ov_mates_add_ascii", library); if (rc) return rc; }
+    if (n > 0 && (!bases || !off)) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_mates_add_ascii: null argument");
+    for (uint64_t r = 0; r < n; r++) if (off[r + 1] < off[r]) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_mates_add_ascii: offsets must not decrease");
+    MateCall M; int rc = mates_begin(c, library, M);
+    if (rc == SAGE2OV_OK) rc = mates_batch(c, M, bases, off, n & ~1ull);               // a trailing odd read is dropped (matePair.cpp:172)
+    return mates_end(c, M, rc);
+}
+int sage2ov_mates_add_file(sage2ov_ctx* c, const char* p1, const char* p2, int library) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    { const int rc = mates_check(c, "sage2ov_mates_add_file", library); if (rc) return rc; }
+    if (!p1) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_mates_add_file: null argument");
+    return mates_add_files(c, p1, p2, library);
+}
+int sage2ov_mates_add_list(sage2ov_ctx* c, const char* lp) {                          // matePair.cpp:70-120
+    if (!c) return SAGE2OV_ERR_ARG;
+    { const int rc = mates_check(c, "sage2ov_mates_add_list", 1); if (rc) return rc; }
+    if (!lp) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_mates_add_list: null argument");
+    FILE* f = fopen(lp, "r"); if (!f) return c->fail(SAGE2OV_ERR_IO, std::string("cannot open ") + lp);
+    char buf[8192]; std::string val1; unsigned mate = 0; int rc = SAGE2OV_OK;
+    while (fgets(buf, sizeof buf, f)) {
+        std::string line = buf; while (!line.empty() && (line.back() == '\n' || line.back() == '\r')) line.pop_back();
+        if (line.empty() || line[0] == '#') continue;
+        size_t p = line.find('=');
+        if (p == std::string::npos) { rc = c->fail(SAGE2OV_ERR_IO, "list of input files in a wrong format"); break; }
+        std::string var = trim(line.substr(0, p)), val = trim(line.substr(p + 1));
+        const int lib = (int)(mate / 2) + 1;                                           // :102, :107
+        if (lib > 127 && (var == "f" || var == "f2")) { rc = c->fail(SAGE2OV_ERR_ARG, "sage2ov_mates_add_list: more than 127 datasets"); break; }
+        if (mate % 2 == 0 && var == "f1") val1 = val;
+        else if (mate % 2 == 0 && var == "f") { rc = mates_add_files(c, val.c_str(), nullptr, lib); mate++; }
+        else if (mate % 2 == 1 && var == "f2") rc = mates_add_files(c, val1.c_str(), val.c_str(), lib);
+        else { rc = c->fail(SAGE2OV_ERR_IO, "list of input files in a wrong format"); }
+        if (rc) break;
+        mate++;
+    }
+    fclose(f);
+    if (rc == SAGE2OV_OK && mate % 2 == 1) rc = c->fail(SAGE2OV_ERR_IO, "list of input files in a wrong format");      // an f1 without its f2
+    return rc;
+}
+int sage2ov_mates_count(sage2ov_ctx* c, int library, uint64_t* n) {
+    if (!c || !n) return SAGE2OV_ERR_ARG;
+    { const int rc = mates_check(c, "sage2ov_mates_count", library); if (rc) return rc; }
+    *n = mates_entries(c, library); return SAGE2OV_OK;
+}
+int sage2ov_mates_export(sage2ov_ctx* c, int library, sage2ov_mate* out, uint64_t cap, uint64_t* offsets) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    { const int rc = mates_check(c, "sage2ov_mates_export", library); if (rc) return rc; }
+    const uint64_t n = mates_entries(c, library);
+    if (cap < n) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_mates_export: the buffer holds fewer entries than the table (sage2ov_mates_count)");
+    if (n && !out) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_mates_export: null argument");
+    const sage2ov_ctx::MateLib* L = &c->mates[library]; sage2ov_ctx::MateLib tmp;
+    if (c->mateOnDevice[library]) {
+        tmp.key.resize(n); tmp.cnt.resize(n); tmp.first.resize(n); L = &tmp;
+        const int rc = dev_mates_export(c->device(), library, tmp.key.data(), tmp.cnt.data(), tmp.first.data(), offsets, c->err); if (rc) return rc;
+    } else if (offsets) {
+        uint64_t t = 0;
+        for (uint64_t a = 0; a <= c->N + 1; a++) { while (t < n && (L->key[t] >> 32) < a) t++; offsets[a] = a == c->N + 1 ? n : t; }
+    }
+    #pragma omp parallel for num_threads(io_threads(c))
+    for (uint64_t e = 0; e < n; e++) {
+        const uint64_t k = L->key[e]; sage2ov_mate m{};
+        m.from = (uint32_t)(k >> 32); m.to = (uint32_t)((k >> 2) & 0x3FFFFFFFu); m.type1 = (uint8_t)((k >> 1) & 1); m.type2 = (uint8_t)(k & 1);
+        m.count = L->cnt[e]; m.first = L->first[e]; m.freq = (uint8_t)(m.count & 255); m.library = (uint8_t)library;
+        out[e] = m;
+    }
+    return SAGE2OV_OK;
+}
+int sage2ov_mates_clear(sage2ov_ctx* c) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    if (Device* d = c->device()) dev_mates_clear(d);
+    c->mates_forget(); return SAGE2OV_OK;
+}
+int sage2ov_mates_stats_get(const sage2ov_ctx* c, sage2ov_mate_stats* o) { if (!c || !o) return SAGE2OV_ERR_ARG; *o = c->mstats; return SAGE2OV_OK; }
 int sage2ov_reads_set_totals(sage2ov_ctx* c, uint64_t good, uint64_t bp) { if (!c) return SAGE2OV_ERR_ARG; c->goodReads = good; c->totalBP = bp; return SAGE2OV_OK; }
 
 // ------------------------------------------------------------------------------------------ step 2

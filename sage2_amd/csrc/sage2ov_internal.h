@@ -134,6 +134,17 @@ int dev_meminfo(Device* d, uint64_t* out4, std::string& err);
 // read store is resident: the caller then searches the host copy
 struct FindStats { uint64_t found = 0, not_good = 0; uint32_t dirBits = 0, launches = 0; double pack_ms = 0, dir_ms = 0, search_ms = 0; bool byPos = false; };
 int dev_find_ids(Device* d, const char* bases, const uint64_t* off, uint64_t n, int64_t* ids, FindStats* st, std::string& err);
+// MatePair::processMatePairs on the device (sage2ov_mates_*): dev_mates_add takes one batch of an even number of reads (pair0: ordinal of its first pair in the
+// library) into the pending records and flushes them at a bound; dev_mates_flush ends the call.  dev_mates_add returns 1 (and does nothing) when no read store
+// is resident.  The table of a library is exported as parallel arrays (key = from:30 | to:30 | t_from:1 | t_to:1, count, first) in key order.
+struct MateStats { uint64_t seen = 0, added = 0, not_good = 0, not_found = 0; uint32_t chunks = 0, passes = 0, flushes = 0; double find_ms = 0, records_ms = 0, sort_ms = 0, reduce_ms = 0, merge_ms = 0; };
+int dev_mates_add(Device* d, const char* bases, const uint64_t* off, uint64_t n, int library, uint64_t pair0, MateStats* st, std::string& err);
+int dev_mates_flush(Device* d, int library, MateStats* st, std::string& err);
+void dev_mates_abort(Device* d);                 // drops the pending records of a call that failed
+uint64_t dev_mates_count(Device* d, int library);
+int dev_mates_export(Device* d, int library, uint64_t* key, uint64_t* cnt, uint64_t* first, uint64_t* offsets, std::string& err);
+int dev_mates_import(Device* d, int library, const uint64_t* key, const uint64_t* cnt, const uint64_t* first, uint64_t n, std::string& err);
+void dev_mates_clear(Device* d);
 int dev_debug_keys(Device* d, uint64_t* out, std::string& err);
 int dev_debug_all_hits(Device* d, std::vector<Hit>& hits, std::string& err);
 int dev_append_edges(Device* d, const EdgeCand* e, uint64_t n, std::string& err);
