@@ -10,9 +10,9 @@
 //   k_mate_records   key = from:30 | to:30 | t_from:1 | t_to:1 (bits 61..32, 31..2, 1, 0; a context holds at most 2^30 - 1 reads) and the record
 //                    ordinal 2 * p + side, appended to the pending buffer
 // and per flush of the pending buffer (at a bound, and at the end of every call):
-//   k_mate_iota, k_rs_hist / k_rs_scatter (kernels_organize.inc)   stable LSD radix sort of (key, index), only the passes whose digit can be non-zero
+//   k_mate_iota, k_rs_hist / k_rs_scatter (kernels_organize.inc; radix_sort_pairs)   stable LSD radix sort of (key, index), only the passes whose digit can be non-zero
 //   k_mate_heads     a record is a head when its key differs from its predecessor's
-//   (scan) + k_mate_headpos    position of head e in the sorted records; hp[E] = n
+//   (scan) + k_headpos (kernels_organize.inc; head_positions)    position of head e in the sorted records; hp[E] = n
 //   k_mate_reduce    entry e: count = hp[e + 1] - hp[e]; first = the ordinal of the head itself -- the sort is stable and the records were written in
 //                    ordinal order, so inside a run of equal keys the ordinals ascend.  No thread walks a run.
 //   k_mate_merge     the library's table (sorted, unique) and the new entries (sorted, unique), concatenated and sorted by the same passes: runs of
@@ -54,11 +54,6 @@ __global__ void k_mate_iota(u32* v, u32 n) { const u32 i = blockIdx.x * blockDim
 __global__ void k_mate_heads(const u64* __restrict__ keys, u32 n, u32* flag) {
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x; if (i >= n) return;
     flag[i] = (i == 0 || keys[i - 1] != keys[i]) ? 1u : 0u;
-}
-__global__ void k_mate_headpos(const u32* __restrict__ flag, const u32* __restrict__ pos, u32 n, u32* hp, u32 E) {
-    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && flag[i]) hp[pos[i]] = i;
-    if (i == 0) hp[E] = n;
 }
 __global__ void k_mate_reduce(const u64* __restrict__ keys, const u32* __restrict__ vals, const u64* __restrict__ ord, const u32* __restrict__ hp, u32 E,
                               u64* outKey, u64* outCnt, u64* outFirst) {

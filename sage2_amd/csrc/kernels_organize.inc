@@ -6,9 +6,11 @@
 // Input: the good reads as the host staged them (forward strand, 2-bit big-endian words, variable length).
 //   k_org_canon   read < revcomp ? read : revcomp (:195), written as an S-word slot with the length in the low 9 bits of
 //                 the last word: comparing slots word by word IS stringCompareInBytes (utils.cpp:224: bytes, then length)
-//   k_rs_*        stable LSD radix sort of (first word, read index), 8 passes of 8 bits, one wave per 2048-element tile
+//   k_rs_*        stable LSD radix sort of (first word, read index), 8 passes of 8 bits, one wave per 2048-element tile (driven by radix_sort_pairs,
+//                 sage2ov_device.hip, which the mate table uses too: kernels_mates.inc)
 //   k_org_ties    runs of equal first words ordered by the remaining words (insertion sort; duplicates cost one compare each)
 //   k_org_heads   first read of every run of equal slots = a unique read; exclusive scan = id - 1; run length = frequency (u16 wrap)
+//   k_headpos     position of head e in the sorted pairs, hp[E] = n (head_positions, sage2ov_device.hip; the mate table's heads go through it too)
 //   k_org_gather  the HBM read store in id order (slot 0 = zeros)
 // =============================================================================================
 constexpr int RS_TILE = 2048;
@@ -164,10 +166,10 @@ __global__ void k_org_heads(const u64* __restrict__ keys, const u32* __restrict_
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; if (i >= n) return;
     flag[i] = (i == 0 || keys[i - 1] != keys[i] || org_cmp(img, S, vals[i - 1], vals[i]) != 0) ? 1u : 0u;
 }
-__global__ void k_org_headpos(const u32* __restrict__ flag, const u32* __restrict__ uid, u64 n, u32* headPos, u64 N) {
+__global__ void k_headpos(const u32* __restrict__ flag, const u32* __restrict__ pos, u64 n, u32* hp, u64 E) {      // pos: exclusive scan of flag; E: its total
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && flag[i]) headPos[uid[i]] = (u32)i;
-    if (i == 0) headPos[N] = (u32)n;
+    if (i < n && flag[i]) hp[pos[i]] = (u32)i;
+    if (i == 0) hp[E] = (u32)n;
 }
 __global__ void k_org_gather(const u32* __restrict__ vals, const u32* __restrict__ headPos, u64 N, const u64* __restrict__ img, int S, u64* reads, unsigned short* freq) {
     // grid-stride: a launch of more than 2^32 threads is cut down to its size modulo 2^32 WITHOUT an error (found at 1.02 G reads x 8 words: the last 2^29

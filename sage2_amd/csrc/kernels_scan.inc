@@ -1,8 +1,8 @@
-// sage2_amd/csrc/kernels_scan.inc -- exclusive scan of u32.
+// sage2_amd/csrc/kernels_scan.inc -- exclusive scan of u32: the three kernels of scan_u32 (sage2ov_device.hip), the one driver every phase scans with.
 // Part of sage2ov_device.hip (included inside namespace s2, in this order); not a translation unit of its own.
 
 // =============================================================================================
-// exclusive scan of u32 (3 kernels, 2048 items per block)
+// exclusive scan of u32 (3 kernels, 2048 items per block; partial: one word per block and one for the total, the caller's buffer)
 // =============================================================================================
 constexpr int SCAN_ITEMS = 8, SCAN_THREADS = 256, SCAN_BLOCK = SCAN_ITEMS * SCAN_THREADS;
 template <int NWAVES = 4>

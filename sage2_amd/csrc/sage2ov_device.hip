@@ -197,7 +197,7 @@ static void mem_sample(Device* d) { size_t fr = 0, to = 0; if (hipMemGetInfo(&fr
 #include "kernels_mates.inc"
 
 // =============================================================================================
-// host-side launchers
+// host primitives: what the launchers below share (grids, counters, transient buffers, a stream timer, scan, radix sort, heads)
 // =============================================================================================
 // one thread per item.  A launch of 2^32 threads or more does NOT fail on this runtime: its size is taken modulo 2^32 and the tail of the work silently
 // never runs (round 3, 1.02 G reads).  grid_for is therefore only for item counts that the documented limits keep below 2^32 (asserted in debug
@@ -210,7 +210,72 @@ static int read_counters(Device* d, int first, int n, u64* out, std::string& err
     HIPCHK(hipStreamSynchronize(d->stream));
     return 0;
 }
+// Transient device buffers of one call, freed on every return path.  get: a buffer of its own (null: out of memory); slot: a numbered buffer, reused by the
+// next request that fits into it (the chunks of one call); release: freed early; keep: the caller takes it over.
+struct DevTmp {
+    static constexpr int SLOTS = 8;
+    std::vector<void*> own; struct { void* p = nullptr; size_t cap = 0; } slots[SLOTS];
+    ~DevTmp() { for (void* q : own) hipFree(q); for (auto& b : slots) hipFree(b.p); }
+    static void* alloc(size_t bytes) { void* q = nullptr; if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); return nullptr; } return q; }
+    template <class T> T* get(u64 n) { void* q = alloc(std::max<u64>(n, 1) * sizeof(T)); if (q) own.push_back(q); return (T*)q; }
+    template <class T> T* slot(int i, u64 n) { if (i < 0 || i >= SLOTS) return nullptr;
+                                               auto& b = slots[i]; const size_t bytes = n * sizeof(T);
+                                               if (!b.p || b.cap < bytes) { hipFree(b.p); b.p = alloc(bytes); b.cap = b.p ? bytes : 0; } return (T*)b.p; }
+    void release(void* q) { for (void*& x : own) if (x == q) { hipFree(q); x = nullptr; } }
+    void keep(void* q) { for (void*& x : own) if (x == q) x = nullptr; }
+};
+// HIP-event time of a stretch of the stream, added up in milliseconds: start, then stop (which synchronises) -- or end, and add once the caller has synchronised
+struct StreamLap {
+    hipEvent_t a = nullptr, b = nullptr; hipStream_t st;
+    explicit StreamLap(hipStream_t s) : st(s) {}
+    ~StreamLap() { if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); }
+    hipError_t create() { const hipError_t e = hipEventCreate(&a); return e != hipSuccess ? e : hipEventCreate(&b); }
+    hipError_t start() { return hipEventRecord(a, st); }
+    hipError_t end() { return hipEventRecord(b, st); }
+    void add(double& acc) const { float ms = 0; hipEventElapsedTime(&ms, a, b); acc += ms; }
+    hipError_t stop(double& acc) { hipError_t e = end(); if (e == hipSuccess) e = hipStreamSynchronize(st); if (e == hipSuccess) add(acc); return e; }
+};
+// Exclusive scan of n u32 (kernels_scan.inc); partial: scan_partial_words(n) words.  total null: nothing is read back, nothing is synchronised; else the sum
+// of the input comes back and the stream has finished.  n = 0: no block to launch, the total is 0.
+static inline u64 scan_partial_words(u64 n) { return n / SCAN_BLOCK + 2; }
+static int scan_u32(Device* d, const u32* in, u64 n, u32* out, u64* partial, u64* total, std::string& err) {
+    const u64 nb = (n + SCAN_BLOCK - 1) / SCAN_BLOCK;
+    if (nb) hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, d->stream, in, (u64)n, partial);
+    hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(1024), 0, d->stream, partial, (u64)nb, partial + nb);
+    if (nb) hipLaunchKernelGGL(k_scan_final, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, d->stream, in, (u64)n, partial, out);
+    HIPCHK(hipGetLastError());
+    if (total) { HIPCHK(hipMemcpyAsync(total, partial + nb, sizeof(u64), hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream)); }
+    return 0;
+}
+// the steps' form: the partial sums in the workspace arena (which the mate table never touches: it brings a buffer of its own)
+static int scan_u32(Device* d, const u32* in, u64 n, u32* out, u64* total, std::string& err) { WS(partial, u64, WS_PARTIAL, scan_partial_words(n)); return scan_u32(d, in, n, out, partial, total, err); }
+// Stable LSD radix sort of n > 0 (u64 key, u32 value) pairs by the 8-bit digits at shifts[0, np): k_rs_hist, scan, k_rs_scatter per digit (kernels_organize.inc).
+// The pairs are in k[0] / v[0]; every pass writes the other side, *side = the one that holds the result.  hist, hscan: rs_hist_words(n) words each, partial:
+// scan_partial_words of as many.  Nothing is synchronised.
+struct RsBufs { u64* k[2]; u32* v[2]; u32 *hist, *hscan; u64* partial; };
+constexpr int RS_ALL_DIGITS[] = {0, 8, 16, 24, 32, 40, 48, 56}; constexpr int RS_ALL_N = sizeof RS_ALL_DIGITS / sizeof RS_ALL_DIGITS[0];
+static inline u64 rs_hist_words(u64 n) { return 256 * ((n + RS_TILE - 1) / RS_TILE) + 2; }
+static int radix_sort_pairs(Device* d, const RsBufs& B, u64 n, const int* shifts, int np, int* side, std::string& err) {
+    const u32 nb = (u32)((n + RS_TILE - 1) / RS_TILE); int cur = 0;
+    for (int p = 0; p < np; p++, cur ^= 1) {
+        hipLaunchKernelGGL(k_rs_hist, dim3(nb), dim3(64), 0, d->stream, B.k[cur], (u64)n, shifts[p], B.hist, nb);
+        const int rc = scan_u32(d, B.hist, (u64)256 * nb, B.hscan, B.partial, nullptr, err); if (rc) return rc;
+        hipLaunchKernelGGL(k_rs_scatter, dim3(nb), dim3(64), 0, d->stream, B.k[cur], B.v[cur], (u64)n, shifts[p], B.hscan, nb, B.k[cur ^ 1], B.v[cur ^ 1]);
+    }
+    HIPCHK(hipGetLastError());
+    *side = cur; return 0;
+}
+// Heads to positions, second half: flag[i] = 1 where a run begins among n sorted items (the caller's predicate), pos = exclusive scan of the flags and E its total
+// (scan_u32 with a read-back: the caller sizes hp, E + 1 words, by it); then hp[e] = position of head e and hp[E] = n (k_headpos)
+static int head_positions(Device* d, const u32* flag, const u32* pos, u64 n, u32* hp, u64 E, std::string& err) {
+    hipLaunchKernelGGL(k_headpos, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, flag, pos, (u64)n, hp, (u64)E);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
 
+// =============================================================================================
+// host-side launchers
+// =============================================================================================
 void dev_set_options(Device* d, const Options& opt) { d->opt = opt; }
 Device* dev_create(int ordinal, const Options& opt, std::string& err) {
     int count = 0;
@@ -297,7 +362,6 @@ int dev_upload_reads(Device* d, const uint64_t* words, uint64_t N, int S, int mi
     return 0;
 }
 
-static int scan_u32(Device* d, const u32* in, u64 n, u32* out, u64* total, std::string& err);
 struct PtBufs { u32* E[2]; int W; const u32* src0 = nullptr; };      // two buffers of n tuples of W dwords each (kernels_partition.inc); src0: the first pass reads the tuples there (left untouched) and writes E[0]
 static int partition_by_window(Device* d, PtBufs& B, int keyw, u32 n, int shiftW, u64 nWin, bool digit0Counted, u32* cnt, u32* base, u32* off, int* cur_out, std::string& err);
 // Step 1 on the device: see k_org_canon.  On return the read store is resident exactly as after dev_upload_reads, and the
@@ -305,12 +369,10 @@ static int partition_by_window(Device* d, PtBufs& B, int keyw, u32 n, int shiftW
 int dev_organize_reads(Device* d, const uint64_t* pool, uint64_t pool_words, const uint64_t* off, const uint16_t* len, uint64_t n, int S, int minL, int maxL, int k,
                        uint64_t* N_out, RawU64& words_out, RawU16& freq_out, std::string& err, OrgAscii* ascii) {
     HIPCHK(hipSetDevice(d->ordinal));
-    struct EvPair { hipEvent_t a = nullptr, b = nullptr; ~EvPair() { if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); } } evp;   // (destroyed on every return path)
-    HIPCHK(hipEventCreate(&evp.a)); HIPCHK(hipEventCreate(&evp.b));
-    const hipEvent_t e0 = evp.a, e1 = evp.b;
+    StreamLap whole(d->stream); HIPCHK(whole.create());
     const bool timing = d->opt.get("SAGE2OV_TIMING") != nullptr; auto tp = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) { if (!timing) return; hipStreamSynchronize(d->stream); auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[step 1/device] %-30s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(t - tp).count()); tp = t; };
-    HIPCHK(hipEventRecord(e0, d->stream));
+    HIPCHK(whole.start());
     // ASCII input (sage2ov_reads_add_ascii): filter, 2-bit pack and canonical orientation on the device (utils.cpp:144-166, :96-119, readLoader.cpp:195)
     unsigned char* dbases = nullptr; u64* doffA = nullptr; u32* gflag = nullptr; u32* gpos = nullptr;
     if (ascii) {
@@ -334,7 +396,10 @@ int dev_organize_reads(Device* d, const uint64_t* pool, uint64_t pool_words, con
     u64 N = 0;
     u64* reads = nullptr; unsigned short* dfreq = nullptr;
     if (n) {
+        // (the whole work space before the first kernel is queued: the host no longer waits for every pass of the sort, and would otherwise allocate while it runs)
         WS(img, u64, WS_ORG_IMG, n * S); WS(k0, u64, WS_ORG_K0, n); WS(k1, u64, WS_ORG_K1, n); WS(v0, u32, WS_ORG_V0, n); WS(v1, u32, WS_ORG_V1, n);
+        WS(hist, u32, WS_ORG_HIST, rs_hist_words(n)); WS(hscan, u32, WS_ORG_HSCAN, rs_hist_words(n)); WS(flag, u32, WS_ORG_FLAG, n + 2); WS(uid, u32, WS_ORG_UID, n + 2);
+        WS(partial, u64, WS_PARTIAL, scan_partial_words(std::max<u64>(n, rs_hist_words(n))));      // (the sort's scans and the one over the heads)
         if (ascii) hipLaunchKernelGGL(k_org_pack, dim3(grid_for(ascii->n_in, 256)), dim3(256), 0, d->stream, dbases, doffA, (u64)ascii->n_in, gflag, gpos, S, img, k0, v0);
         else {
             WS(dpool, u64, WS_ORG_POOL, pool_words + 17); WS(doff, u64, WS_ORG_OFF, n); WS(dlen, unsigned short, WS_ORG_LEN, n);
@@ -345,16 +410,9 @@ int dev_organize_reads(Device* d, const uint64_t* pool, uint64_t pool_words, con
             lap("work space + upload");
             hipLaunchKernelGGL(k_org_canon, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, dpool, doff, dlen, (u64)n, S, img, k0, v0);
         }
-        const u32 nb = (u32)((n + RS_TILE - 1) / RS_TILE);
-        WS(hist, u32, WS_ORG_HIST, (u64)256 * nb + 2); WS(hscan, u32, WS_ORG_HSCAN, (u64)256 * nb + 2);
-        u64 *ka = k0, *kb = k1; u32 *va = v0, *vb = v1;
-        for (int pass = 0; pass < 8; pass++) {
-            hipLaunchKernelGGL(k_rs_hist, dim3(nb), dim3(64), 0, d->stream, ka, (u64)n, 8 * pass, hist, nb);
-            u64 tot = 0; int rc = scan_u32(d, hist, (u64)256 * nb, hscan, &tot, err); if (rc) return rc;
-            hipLaunchKernelGGL(k_rs_scatter, dim3(nb), dim3(64), 0, d->stream, ka, va, (u64)n, 8 * pass, hscan, nb, kb, vb);
-            std::swap(ka, kb); std::swap(va, vb);
-        }
-        WS(flag, u32, WS_ORG_FLAG, n + 2); WS(uid, u32, WS_ORG_UID, n + 2);
+        static_assert(RS_ALL_N % 2 == 0, "an even number of passes: every sort below leaves the pairs where it found them, in k0 / v0");
+        const RsBufs B = {{k0, k1}, {v0, v1}, hist, hscan, partial}; int side = 0; u64* const ka = k0; u32* const va = v0;
+        { const int rc = radix_sort_pairs(d, B, n, RS_ALL_DIGITS, RS_ALL_N, &side, err); if (rc) return rc; }
         u32 longrun = 0;
         HIPCHK(hipMemsetAsync(flag, 0, sizeof(u32), d->stream));
         hipLaunchKernelGGL(k_org_longrun, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, ka, (u64)n, flag);
@@ -364,19 +422,14 @@ int dev_organize_reads(Device* d, const uint64_t* pool, uint64_t pool_words, con
             // sorted by the first word, which the last eight passes simply reproduce)
             for (int c = S - 1; c >= 0; c--) {
                 hipLaunchKernelGGL(k_org_wordkeys, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, img, S, c, va, (u64)n, ka);
-                for (int pass = 0; pass < 8; pass++) {
-                    hipLaunchKernelGGL(k_rs_hist, dim3(nb), dim3(64), 0, d->stream, ka, (u64)n, 8 * pass, hist, nb);
-                    u64 tot = 0; int rc = scan_u32(d, hist, (u64)256 * nb, hscan, &tot, err); if (rc) return rc;
-                    hipLaunchKernelGGL(k_rs_scatter, dim3(nb), dim3(64), 0, d->stream, ka, va, (u64)n, 8 * pass, hscan, nb, kb, vb);
-                    std::swap(ka, kb); std::swap(va, vb);
-                }
+                { const int rc = radix_sort_pairs(d, B, n, RS_ALL_DIGITS, RS_ALL_N, &side, err); if (rc) return rc; }
             }
         } else hipLaunchKernelGGL(k_org_ties, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, ka, va, (u64)n, img, S);
         hipLaunchKernelGGL(k_org_heads, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, ka, va, (u64)n, img, S, flag);
-        { int rc = scan_u32(d, flag, n, uid, &N, err); if (rc) return rc; }
+        { int rc = scan_u32(d, flag, n, uid, partial, &N, err); if (rc) return rc; }
         if (N >= (1ull << 30)) { err = "more than 2^30-1 unique reads per context is not supported yet"; return SAGE2OV_ERR_LIMIT; }
         WS(headPos, u32, WS_ORG_HEAD, N + 2);
-        hipLaunchKernelGGL(k_org_headpos, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, flag, uid, (u64)n, headPos, (u64)N);
+        { int rc = head_positions(d, flag, uid, n, headPos, N, err); if (rc) return rc; }
         lap("canonical, sort, heads");
         HIPCHK(hipMalloc(&reads, (N + 1) * S * sizeof(u64))); HIPCHK(hipMalloc(&dfreq, (N + 1) * sizeof(unsigned short)));
         HIPCHK(hipMemsetAsync(reads, 0, S * sizeof(u64), d->stream)); HIPCHK(hipMemsetAsync(dfreq, 0, sizeof(unsigned short), d->stream));
@@ -386,7 +439,7 @@ int dev_organize_reads(Device* d, const uint64_t* pool, uint64_t pool_words, con
         HIPCHK(hipMemsetAsync(reads, 0, S * sizeof(u64), d->stream)); HIPCHK(hipMemsetAsync(dfreq, 0, sizeof(unsigned short), d->stream));
     }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(e1, d->stream));
+    HIPCHK(whole.end());
     lap("read store allocation + gather");
     words_out.resize((N + 1) * S); freq_out.resize(N + 1);
     touch_pages(words_out.data(), words_out.size() * sizeof(u64), 8);
@@ -395,7 +448,7 @@ int dev_organize_reads(Device* d, const uint64_t* pool, uint64_t pool_words, con
     HIPCHK(hipMemcpyAsync(freq_out.data(), dfreq, (N + 1) * sizeof(unsigned short), hipMemcpyDeviceToHost, d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
     lap("download of the store");
-    float ms = 0; hipEventElapsedTime(&ms, e0, e1); d->tm.organize_ms += ms;
+    whole.add(d->tm.organize_ms);
     hipFree(dfreq);
     // the organised store becomes the context's read store (same state as after dev_upload_reads)
     free_reads(d);
@@ -410,7 +463,32 @@ int dev_organize_reads(Device* d, const uint64_t* pool, uint64_t pool_words, con
     return 0;
 }
 
-static int build_locality_order(Device* d, u64 lo, u64 hi, const u32** order_out, std::string& err);
+// processing order of ids [lo,hi): grouped by the reads' global minimiser (see k_minimizer)
+static int build_locality_order(Device* d, u64 lo, u64 hi, const u32** order_out, std::string& err) {
+    const u64 n = hi - lo;
+    // reads sorted by (their global minimiser's hash, strand of the minimiser, start of the read relative to it): LSD radix passes
+    // (kernels_partition.inc), first the 9 bits of strand + offset, then the hash -- reads with one minimiser end up next to each
+    // other, each starting a few bases after the one before.  Measured at BASELINE configs[2]: probe kernel 149 -> 142 ms from the finer processing
+    // order alone, 120 ms with the read store in that order too.  *order_out: per position, meta << 32 | id.
+    // ALL 32 bits of the hash since the end of round 3 (four passes of 8 bits; 27 bits = three passes of 9 before): two minimisers that share a bucket interleave
+    // their reads and break each other's runs of shifted reads (window reuse, 5.2) -- hash bits -> probe pass at configs[2]: 18 -> 97.2 ms, 24 -> 78.8, 27 -> 62.5,
+    // 30 -> 57.2, 32 -> 56.5, for 0.3 ms more of index build.
+    constexpr int lg = 32;
+    const u32 ntiles = (u32)((n + PT_TILE - 1) / PT_TILE);
+    PtBufs B; B.W = 3;                                                        // {hash, id, meta}
+    { WS(a, u32, WS_MINH, 3 * (n + 4)); B.E[0] = a; } { WS(a, u32, WS_OCUR, 3 * (n + 4)); B.E[1] = a; }
+    WS(cnt, u32, WS_PT_CNT, (u64)PT_NB_MAX * std::max<u32>(ntiles, 1) + 2); WS(base, u32, WS_PT_BASE, (u64)PT_NB_MAX * std::max<u32>(ntiles, 1) + 2);
+    // one element format for all four passes, written by the minimiser kernel itself (round 2 had a pack and a re-key kernel in between): pass 1 sorts by
+    // the meta (dword 2), passes 2-4 by the hash (dword 0)
+    if (d->S == 4) hipLaunchKernelGGL((k_minimizer_t<4>), dim3(grid_for(n, 256)), dim3(256), 0, d->stream, d->reads, (u64)lo, (u64)hi, B.E[0]);
+    else if (d->S == 8) hipLaunchKernelGGL((k_minimizer_t<8>), dim3(grid_for(n, 256)), dim3(256), 0, d->stream, d->reads, (u64)lo, (u64)hi, B.E[0]);
+    else hipLaunchKernelGGL(k_minimizer, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, d->reads, (u64)lo, (u64)hi, d->S, B.E[0]);
+    int cur = 0; int rc = partition_by_window(d, B, 2, (u32)n, 0, 1ull << 9, false, cnt, base, nullptr, &cur, err); if (rc) return rc;
+    PtBufs C; C.W = 3; C.E[0] = B.E[cur]; C.E[1] = B.E[cur ^ 1];
+    int cur2 = 0; rc = partition_by_window(d, C, 0, (u32)n, 32 - lg, 1ull << lg, false, cnt, base, nullptr, &cur2, err); if (rc) return rc;
+    *order_out = C.E[cur2];
+    return 0;
+}
 // The locality-ordered copy of the read store + the two translation tables (see Device::readsLoc).  Part of the index build (timed with it).
 // Round 3: two kernels.  k_loc_index writes the translation tables from the order; k_loc_scatter then STREAMS the id-ordered store (coalesced reads) and
 // writes every slot to its position (whole 32 / 64 / 128-byte slots: no read-modify-write at the memory side).  The gather it replaces pulled every
@@ -469,9 +547,6 @@ static int refresh_status_by_pos(Device* d, std::string& err) {
     hipLaunchKernelGGL(k_status_by_pos, dim3(grid_for(d->N + 1, 256)), dim3(256), 0, d->stream, d->idOf, d->status, (u64)d->N, d->statusP);
     HIPCHK(hipGetLastError()); return 0;
 }
-// exclusive scan without the read-back of the total (no host synchronisation)
-static int scan_u32_async(Device* d, const u32* in, u64 n, u32* out, std::string& err);
-
 static int pt_digits(u64 nWin, int* bits, int* nd) {            // window id bits, number of <= 9-bit digits
     int wb = 0; while ((1ull << wb) < nWin) wb++;
     *bits = wb; *nd = wb == 0 ? 0 : (wb + 8) / 9; return 0;
@@ -489,7 +564,7 @@ static int partition_by_window(Device* d, PtBufs& B, int keyw, u32 n, int shiftW
         for (int j = 0; j < nd; j++) {
             const int shift = shiftW + j * bper; const int bj = std::min(bper, wb - j * bper); const u32 mask = (1u << bj) - 1u;
             if (!(j == 0 && digit0Counted)) hipLaunchKernelGGL(k_pt_hist, dim3(ntiles), dim3(PT_THREADS), 0, d->stream, in + keyw, n, shift, mask, cnt, ntiles, (u32)B.W);
-            int rc = scan_u32_async(d, cnt, (u64)(mask + 1) * ntiles, base, err); if (rc) return rc;
+            int rc = scan_u32(d, cnt, (u64)(mask + 1) * ntiles, base, nullptr, err); if (rc) return rc;      // (no read-back: nothing synchronises)
             const int o = (j == 0 && B.src0) ? 0 : (cur ^ 1);
             if (B.W == 4 && keyw == 0) hipLaunchKernelGGL((k_pt_scatter<4, 0>), dim3(ntiles), dim3(PT_SC_THREADS), 0, d->stream, in, n, shift, mask, base, ntiles, B.E[o]);
             else if (B.W == 3 && keyw == 0) hipLaunchKernelGGL((k_pt_scatter<3, 0>), dim3(ntiles), dim3(PT_SC_THREADS), 0, d->stream, in, n, shift, mask, base, ntiles, B.E[o]);
@@ -703,33 +778,6 @@ static int launch_probe(Device* d, ProbeArgs& A, std::string& err) {
         default: err = "bad S"; return SAGE2OV_ERR_INTERNAL;
     }
     HIPCHK(hipGetLastError());
-    return 0;
-}
-static int scan_u32(Device* d, const u32* in, u64 n, u32* out, u64* total, std::string& err);
-// processing order of ids [lo,hi): grouped by the reads' global minimiser (see k_minimizer)
-static int build_locality_order(Device* d, u64 lo, u64 hi, const u32** order_out, std::string& err) {
-    const u64 n = hi - lo;
-    // reads sorted by (their global minimiser's hash, strand of the minimiser, start of the read relative to it): LSD radix passes
-    // (kernels_partition.inc), first the 9 bits of strand + offset, then the hash -- reads with one minimiser end up next to each
-    // other, each starting a few bases after the one before.  Measured at BASELINE configs[2]: probe kernel 149 -> 142 ms from the finer processing
-    // order alone, 120 ms with the read store in that order too.  *order_out: per position, meta << 32 | id.
-    // ALL 32 bits of the hash since the end of round 3 (four passes of 8 bits; 27 bits = three passes of 9 before): two minimisers that share a bucket interleave
-    // their reads and break each other's runs of shifted reads (window reuse, 5.2) -- hash bits -> probe pass at configs[2]: 18 -> 97.2 ms, 24 -> 78.8, 27 -> 62.5,
-    // 30 -> 57.2, 32 -> 56.5, for 0.3 ms more of index build.
-    constexpr int lg = 32;
-    const u32 ntiles = (u32)((n + PT_TILE - 1) / PT_TILE);
-    PtBufs B; B.W = 3;                                                        // {hash, id, meta}
-    { WS(a, u32, WS_MINH, 3 * (n + 4)); B.E[0] = a; } { WS(a, u32, WS_OCUR, 3 * (n + 4)); B.E[1] = a; }
-    WS(cnt, u32, WS_PT_CNT, (u64)PT_NB_MAX * std::max<u32>(ntiles, 1) + 2); WS(base, u32, WS_PT_BASE, (u64)PT_NB_MAX * std::max<u32>(ntiles, 1) + 2);
-    // one element format for all four passes, written by the minimiser kernel itself (round 2 had a pack and a re-key kernel in between): pass 1 sorts by
-    // the meta (dword 2), passes 2-4 by the hash (dword 0)
-    if (d->S == 4) hipLaunchKernelGGL((k_minimizer_t<4>), dim3(grid_for(n, 256)), dim3(256), 0, d->stream, d->reads, (u64)lo, (u64)hi, B.E[0]);
-    else if (d->S == 8) hipLaunchKernelGGL((k_minimizer_t<8>), dim3(grid_for(n, 256)), dim3(256), 0, d->stream, d->reads, (u64)lo, (u64)hi, B.E[0]);
-    else hipLaunchKernelGGL(k_minimizer, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, d->reads, (u64)lo, (u64)hi, d->S, B.E[0]);
-    int cur = 0; int rc = partition_by_window(d, B, 2, (u32)n, 0, 1ull << 9, false, cnt, base, nullptr, &cur, err); if (rc) return rc;
-    PtBufs C; C.W = 3; C.E[0] = B.E[cur]; C.E[1] = B.E[cur ^ 1];
-    int cur2 = 0; rc = partition_by_window(d, C, 0, (u32)n, 32 - lg, 1ull << lg, false, cnt, base, nullptr, &cur2, err); if (rc) return rc;
-    *order_out = C.E[cur2];
     return 0;
 }
 static ProbeArgs base_args(Device* d) {
@@ -1518,32 +1566,29 @@ int dev_unresolved_ids(Device* d, std::vector<uint32_t>& ids, std::string& err) 
 // transient allocation of this call; the steps' results, their phase blocks and the workspace arena are not touched.  Returns 1 when no read store is resident
 // (the caller searches its host copy instead).
 constexpr u64 FIND_CHUNK_BYTES = 256ull << 20;      // ASCII per chunk, and the chunk's packed image
-struct FindTmp {                                                                     // transient buffers and events of one call (freed on every return path)
-    hipEvent_t ev[3] = {}; void* p[7] = {}; size_t cap[7] = {};
-    ~FindTmp() { for (auto e : ev) if (e) hipEventDestroy(e); for (auto q : p) if (q) hipFree(q); }
-    void* get(int i, size_t bytes) { if (cap[i] >= bytes && p[i]) return p[i]; if (p[i]) hipFree(p[i]); p[i] = nullptr; cap[i] = 0;
-                                     if (hipMalloc(&p[i], bytes) != hipSuccess) { (void)hipGetLastError(); p[i] = nullptr; return nullptr; } cap[i] = bytes; return p[i]; }
+struct FindRun {                                                                     // one call: which store, the chunk bound -- and the chunks' seven buffers (slots of tmp) and timers
+    const u64* store = nullptr; bool byPos = false; int S = 0; u64 qcap = 0; u32 maxLen = 0;
+    DevTmp tmp; StreamLap pack, search;
+    explicit FindRun(hipStream_t s) : pack(s), search(s) {}
 };
-struct FindRun { const u64* store = nullptr; bool byPos = false; int S = 0; u64 qcap = 0; u32 maxLen = 0; };
 struct FindChunk { u64 q = 0; unsigned char* db = nullptr; u64* dof = nullptr; signed char* sign = nullptr; long long* dids = nullptr; u64* cnt = nullptr; };
 // what every call does once: which store, the directory (once per read set), the chunk bound.  Returns 1 when no read store is resident.
-static int find_begin(Device* d, FindTmp& T, FindRun& R, FindStats* st, std::string& err) {
+static int find_begin(Device* d, FindRun& R, FindStats* st, std::string& err) {
     R.byPos = d->reads == nullptr;
     if (R.byPos && !(d->readsLoc && d->posOf)) return 1;
     R.store = R.byPos ? d->readsLoc : d->reads; R.S = d->S; const int S = d->S; const u64 N = d->N;
     if (S != 4 && S != 8 && S != 16 && S != 32) { err = "unsupported words-per-read"; return SAGE2OV_ERR_INTERNAL; }
-    for (auto& e : T.ev) HIPCHK(hipEventCreate(&e));
+    HIPCHK(R.pack.create()); HIPCHK(R.search.create());
     *st = FindStats(); st->byPos = R.byPos;
     if (!d->findDir) {                                                               // the directory: once per read set
         int B = 0; while ((1ull << B) < N) B++;                                      // ceil(log2 N)
         B = std::min(FIND_B_MAX, std::max(FIND_B_MIN, B - 1));
         u32* dir = nullptr; HIPCHK(hipMalloc(&dir, ((size_t)(1u << B) + 1) * sizeof(u32)));
-        HIPCHK(hipEventRecord(T.ev[0], d->stream));
+        HIPCHK(R.pack.start());                                                      // (the pack timer is free until the first chunk)
         if (R.byPos) hipLaunchKernelGGL(k_find_dir<true>, dim3(grid_for((1u << B) + 1, 256)), dim3(256), 0, d->stream, R.store, d->posOf, (u32)N, S, B, dir);
         else hipLaunchKernelGGL(k_find_dir<false>, dim3(grid_for((1u << B) + 1, 256)), dim3(256), 0, d->stream, R.store, d->posOf, (u32)N, S, B, dir);
-        hipError_t e = hipGetLastError(); if (e == hipSuccess) e = hipEventRecord(T.ev[1], d->stream); if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+        hipError_t e = hipGetLastError(); if (e == hipSuccess) e = R.pack.stop(st->dir_ms);
         if (e != hipSuccess) { hipFree(dir); err = std::string("read-id directory: ") + hipGetErrorString(e); return SAGE2OV_ERR_DEVICE; }
-        float ms = 0; hipEventElapsedTime(&ms, T.ev[0], T.ev[1]); st->dir_ms = ms;
         d->findDir = dir; d->findDirBits = B;
     }
     st->dirBits = (u32)d->findDirBits;
@@ -1560,46 +1605,46 @@ static u64 find_chunk_end(const FindRun& R, const uint64_t* off, u64 n, u64 r0) 
     return r1;
 }
 // the body of one chunk, queries [r0, r1): upload, k_org_classify, k_find_pack, k_find_search.  The ids stay on the device (C.dids, with the sign bytes and
-// the counters [0..5] k_org_classify, [6] found); events T.ev[0..2] bracket pack and search.  Nothing is synchronised here.
-static int find_chunk(Device* d, FindTmp& T, const FindRun& R, const char* bases, const uint64_t* off, u64 r0, u64 r1, std::vector<u64>& ho, FindChunk& C, std::string& err) {
+// the counters [0..5] k_org_classify, [6] found); R.pack and R.search bracket pack and search.  Nothing is synchronised here.
+static int find_chunk(Device* d, FindRun& R, const char* bases, const uint64_t* off, u64 r0, u64 r1, std::vector<u64>& ho, FindChunk& C, std::string& err) {
     const int S = R.S; const bool byPos = R.byPos; const u64* store = R.store;
     const u64 q = r1 - r0, nbytes = off[r1] - off[r0];
     ho.resize(q + 1); for (u64 x = 0; x <= q; x++) ho[x] = off[r0 + x] - off[r0];
-    unsigned char* db = (unsigned char*)T.get(0, nbytes + 64); u64* dof = (u64*)T.get(1, (q + 1) * sizeof(u64)); u32* flag = (u32*)T.get(2, q * sizeof(u32));
-    u64* img = (u64*)T.get(3, q * S * sizeof(u64)); signed char* sign = (signed char*)T.get(4, q); long long* dids = (long long*)T.get(5, q * sizeof(long long));
-    u64* cnt = (u64*)T.get(6, 8 * sizeof(u64));
+    DevTmp& T = R.tmp;
+    unsigned char* db = T.slot<unsigned char>(0, nbytes + 64); u64* dof = T.slot<u64>(1, q + 1); u32* flag = T.slot<u32>(2, q);
+    u64* img = T.slot<u64>(3, q * S); signed char* sign = T.slot<signed char>(4, q); long long* dids = T.slot<long long>(5, q);
+    u64* cnt = T.slot<u64>(6, 8);
     if (!db || !dof || !flag || !img || !sign || !dids || !cnt) { err = "read-id lookup: out of device memory"; return SAGE2OV_ERR_NOMEM; }
     if (nbytes) HIPCHK(hipMemcpyAsync(db, bases + off[r0], nbytes, hipMemcpyHostToDevice, d->stream));
     HIPCHK(hipMemcpyAsync(dof, ho.data(), (q + 1) * sizeof(u64), hipMemcpyHostToDevice, d->stream));
     const u64 init[8] = {0, 0, 0, 0, ~0ull, 0, 0, 0}; HIPCHK(hipMemcpyAsync(cnt, init, sizeof init, hipMemcpyHostToDevice, d->stream));      // [0..5] k_org_classify, [6] found
-    HIPCHK(hipEventRecord(T.ev[0], d->stream));
+    HIPCHK(R.pack.start());
     hipLaunchKernelGGL(k_org_classify, dim3(grid_for(q, 256)), dim3(256), 0, d->stream, db, dof, (u64)q, (u32)d->k, R.maxLen, flag, cnt);
     hipLaunchKernelGGL(k_find_pack, dim3(grid_for(q, 256)), dim3(256), 0, d->stream, db, dof, (u64)q, flag, S, img, sign);
-    HIPCHK(hipEventRecord(T.ev[1], d->stream));
+    HIPCHK(R.pack.end()); HIPCHK(R.search.start());
     const dim3 grid(grid_for(q * (u64)(S / 2), 256)), block(256); unsigned long long* fnd = (unsigned long long*)(cnt + 6);
 #define S2_FIND(SS) do { if (byPos) hipLaunchKernelGGL((k_find_search<SS, true>), grid, block, 0, d->stream, store, d->posOf, d->findDir, d->findDirBits, img, sign, (u32)q, dids, fnd); \
                          else hipLaunchKernelGGL((k_find_search<SS, false>), grid, block, 0, d->stream, store, d->posOf, d->findDir, d->findDirBits, img, sign, (u32)q, dids, fnd); } while (0)
     if (S == 4) S2_FIND(4); else if (S == 8) S2_FIND(8); else if (S == 16) S2_FIND(16); else S2_FIND(32);
 #undef S2_FIND
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(T.ev[2], d->stream));
+    HIPCHK(R.search.end());
     C.q = q; C.db = db; C.dof = dof; C.sign = sign; C.dids = dids; C.cnt = cnt;
     return 0;
 }
 int dev_find_ids(Device* d, const char* bases, const uint64_t* off, uint64_t n, int64_t* ids, FindStats* st, std::string& err) {
     HIPCHK(hipSetDevice(d->ordinal));
-    FindTmp T; FindRun R;
-    { const int rc = find_begin(d, T, R, st, err); if (rc) return rc; }
+    FindRun R(d->stream);
+    { const int rc = find_begin(d, R, st, err); if (rc) return rc; }
     std::vector<u64> ho;
     for (u64 r0 = 0; r0 < n;) {
         const u64 r1 = find_chunk_end(R, off, n, r0); FindChunk C;
-        { const int rc = find_chunk(d, T, R, bases, off, r0, r1, ho, C, err); if (rc) return rc; }
+        { const int rc = find_chunk(d, R, bases, off, r0, r1, ho, C, err); if (rc) return rc; }
         const u64 q = C.q; u64 hc[8];
         HIPCHK(hipMemcpyAsync(ids + r0, C.dids, q * sizeof(long long), hipMemcpyDeviceToHost, d->stream));
         HIPCHK(hipMemcpyAsync(hc, C.cnt, sizeof hc, hipMemcpyDeviceToHost, d->stream));
         HIPCHK(hipStreamSynchronize(d->stream));
-        float a = 0, b = 0; hipEventElapsedTime(&a, T.ev[0], T.ev[1]); hipEventElapsedTime(&b, T.ev[1], T.ev[2]);
-        st->pack_ms += a; st->search_ms += b; st->launches++;
+        R.pack.add(st->pack_ms); R.search.add(st->search_ms); st->launches++;
         st->found += hc[6]; st->not_good += q - hc[1] - hc[5];                       // hc[1]: good and no longer than the store's longest; hc[5]: good but longer
         r0 = r1;
     }
@@ -1611,20 +1656,6 @@ int dev_find_ids(Device* d, const char* bases, const uint64_t* off, uint64_t n, 
 // records of the call in progress live in allocations of their own (Device::mates): not in the phase block, not in the workspace arena, so the steps and
 // the table never see each other.  Everything else is a transient allocation of the call.
 constexpr u64 MATE_FLUSH_RECORDS = 1ull << 25;      // pending records at which a flush runs: one sort stays far below 2^32 records (k_rs_scatter's positions are u32)
-struct MateBufs {                                    // transient device buffers of one flush (freed on every return path)
-    std::vector<void*> p;
-    ~MateBufs() { for (void* q : p) if (q) hipFree(q); }
-    template <class T> T* get(u64 n) { void* q = nullptr; if (hipMalloc(&q, std::max<u64>(n, 1) * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); return nullptr; } p.push_back(q); return (T*)q; }
-    void release(void* q) { for (auto& x : p) if (x == q) { hipFree(x); x = nullptr; } }
-    void keep(void* q) { for (auto& x : p) if (x == q) x = nullptr; }              // ownership goes to the table
-};
-struct MateLap {                                     // HIP-event time of a stretch of the stream (synchronises at the end of it)
-    hipEvent_t a = nullptr, b = nullptr; hipStream_t st;
-    explicit MateLap(hipStream_t s) : st(s) { hipEventCreate(&a); hipEventCreate(&b); }
-    ~MateLap() { if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); }
-    void start() { hipEventRecord(a, st); }
-    hipError_t stop(double& acc) { hipError_t e = hipEventRecord(b, st); if (e == hipSuccess) e = hipStreamSynchronize(st); if (e == hipSuccess) { float ms = 0; hipEventElapsedTime(&ms, a, b); acc += ms; } return e; }
-};
 static Mates* mates_of(Device* d) { if (!d->mates) d->mates = new Mates(); return d->mates; }
 static void mates_drop_pending(Mates* m) { hipFree(m->pkey); hipFree(m->pord); m->pkey = m->pord = nullptr; m->pn = m->pcap = 0; }
 static void mates_release(Device* d) {
@@ -1642,48 +1673,29 @@ static int mate_passes(u64 N, int* shifts) {
     for (int p = 0; p < 8; p++) { const int lo = 8 * p; if (lo < 2 + b || (lo >= 32 && lo < 32 + b)) shifts[np++] = lo; }
     return np;
 }
-// exclusive scan with a partial buffer of the caller's (scan_u32 uses the workspace arena, which belongs to the steps)
-static int mate_scan(Device* d, MateBufs& B, const u32* in, u64 n, u32* out, u64* total, std::string& err) {
-    const u64 nb = (n + SCAN_BLOCK - 1) / SCAN_BLOCK;
-    u64* partial = B.get<u64>(nb + 1); if (!partial) { err = "mate table: out of device memory"; return SAGE2OV_ERR_NOMEM; }
-    hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, d->stream, in, (u64)n, partial);
-    hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(1024), 0, d->stream, partial, (u64)nb, partial + nb);
-    hipLaunchKernelGGL(k_scan_final, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, d->stream, in, (u64)n, partial, out);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(total, partial + nb, sizeof(u64), hipMemcpyDeviceToHost, d->stream));
-    HIPCHK(hipStreamSynchronize(d->stream));
-    B.release(partial);
-    return 0;
-}
+static int mate_nomem(std::string& err) { err = "mate table: out of device memory"; return SAGE2OV_ERR_NOMEM; }
 // stable LSD sort of (key, index 0 .. n-1) by the passes of mate_passes; the sorted keys and indices come back in *ks / *vs (buffers of B)
-static int mate_sort(Device* d, MateBufs& B, u64* k0, u32 n, const int* shifts, int np, u64** ks, u32** vs, MateStats* st, std::string& err) {
-    const u32 nb = (n + RS_TILE - 1) / RS_TILE;
-    u64* k1 = B.get<u64>(n); u32* v0 = B.get<u32>(n); u32* v1 = B.get<u32>(n); u32* hist = B.get<u32>((u64)256 * nb + 2); u32* hscan = B.get<u32>((u64)256 * nb + 2);
-    if (!k1 || !v0 || !v1 || !hist || !hscan) { err = "mate table: out of device memory"; return SAGE2OV_ERR_NOMEM; }
-    hipLaunchKernelGGL(k_mate_iota, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, v0, n);
-    u64 *ka = k0, *kb = k1; u32 *va = v0, *vb = v1;
-    for (int p = 0; p < np; p++) {
-        hipLaunchKernelGGL(k_rs_hist, dim3(nb), dim3(64), 0, d->stream, ka, (u64)n, shifts[p], hist, nb);
-        u64 tot = 0; const int rc = mate_scan(d, B, hist, (u64)256 * nb, hscan, &tot, err); if (rc) return rc;
-        hipLaunchKernelGGL(k_rs_scatter, dim3(nb), dim3(64), 0, d->stream, ka, va, (u64)n, shifts[p], hscan, nb, kb, vb);
-        std::swap(ka, kb); std::swap(va, vb); st->passes++;
-    }
-    HIPCHK(hipGetLastError());
-    B.release(hist); B.release(hscan); B.release(vb); if (kb != k0) B.release(kb);
-    *ks = ka; *vs = va;
+static int mate_sort(Device* d, DevTmp& B, u64* k0, u32 n, const int* shifts, int np, u64** ks, u32** vs, MateStats* st, std::string& err) {
+    const u64 nh = rs_hist_words(n);
+    const RsBufs R = {{k0, B.get<u64>(n)}, {B.get<u32>(n), B.get<u32>(n)}, B.get<u32>(nh), B.get<u32>(nh), B.get<u64>(scan_partial_words(nh))};
+    if (!R.k[1] || !R.v[0] || !R.v[1] || !R.hist || !R.hscan || !R.partial) return mate_nomem(err);
+    hipLaunchKernelGGL(k_mate_iota, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, R.v[0], n);
+    int side = 0; { const int rc = radix_sort_pairs(d, R, n, shifts, np, &side, err); if (rc) return rc; }
+    st->passes += np;
+    B.release(R.hist); B.release(R.hscan); B.release(R.partial); B.release(R.v[side ^ 1]); if (R.k[side ^ 1] != k0) B.release(R.k[side ^ 1]);
+    *ks = R.k[side]; *vs = R.v[side];
     return 0;
 }
 // heads of the sorted keys: hp[e] = position of the e-th distinct key, hp[E] = n
-static int mate_heads(Device* d, MateBufs& B, const u64* keys, u32 n, u32** hp_out, u32* E_out, std::string& err) {
-    u32* flag = B.get<u32>(n); u32* pos = B.get<u32>(n);
-    if (!flag || !pos) { err = "mate table: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+static int mate_heads(Device* d, DevTmp& B, const u64* keys, u32 n, u32** hp_out, u32* E_out, std::string& err) {
+    u32* flag = B.get<u32>(n); u32* pos = B.get<u32>(n); u64* partial = B.get<u64>(scan_partial_words(n));
+    if (!flag || !pos || !partial) return mate_nomem(err);
     hipLaunchKernelGGL(k_mate_heads, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, keys, n, flag);
-    u64 E = 0; { const int rc = mate_scan(d, B, flag, n, pos, &E, err); if (rc) return rc; }
-    u32* hp = B.get<u32>(E + 1); if (!hp) { err = "mate table: out of device memory"; return SAGE2OV_ERR_NOMEM; }
-    hipLaunchKernelGGL(k_mate_headpos, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, flag, pos, n, hp, (u32)E);
-    HIPCHK(hipGetLastError());
+    u64 E = 0; { const int rc = scan_u32(d, flag, n, pos, partial, &E, err); if (rc) return rc; }
+    u32* hp = B.get<u32>(E + 1); if (!hp) return mate_nomem(err);
+    { const int rc = head_positions(d, flag, pos, n, hp, E, err); if (rc) return rc; }
     HIPCHK(hipStreamSynchronize(d->stream));
-    B.release(flag); B.release(pos);
+    B.release(flag); B.release(pos); B.release(partial);
     *hp_out = hp; *E_out = (u32)E;
     return 0;
 }
@@ -1693,15 +1705,15 @@ int dev_mates_flush(Device* d, int library, MateStats* st, std::string& err) {
     Mates* M = d->mates; if (!M || !M->pn) { if (M) mates_drop_pending(M); return 0; }
     MateLib& L = M->lib[library]; const u32 n = (u32)M->pn;
     int shifts[8]; const int np = mate_passes(d->N, shifts);
-    MateBufs B; MateLap lap(d->stream);
+    DevTmp B; StreamLap lap(d->stream); HIPCHK(lap.create());
     u64 *ks = nullptr; u32 *vs = nullptr, *hp = nullptr; u32 E = 0;
-    lap.start();
+    HIPCHK(lap.start());
     { const int rc = mate_sort(d, B, M->pkey, n, shifts, np, &ks, &vs, st, err); if (rc) return rc; }
     HIPCHK(lap.stop(st->sort_ms));
-    lap.start();
+    HIPCHK(lap.start());
     { const int rc = mate_heads(d, B, ks, n, &hp, &E, err); if (rc) return rc; }
     u64* ek = B.get<u64>((u64)E + L.n); u64* ec = B.get<u64>((u64)E + L.n); u64* ef = B.get<u64>((u64)E + L.n);      // (room for the table behind the new entries: the merge's input)
-    if (!ek || !ec || !ef) { err = "mate table: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+    if (!ek || !ec || !ef) return mate_nomem(err);
     hipLaunchKernelGGL(k_mate_reduce, dim3(grid_for(E, 256)), dim3(256), 0, d->stream, ks, vs, M->pord, hp, E, ek, ec, ef);
     HIPCHK(hipGetLastError());
     HIPCHK(lap.stop(st->reduce_ms));
@@ -1713,7 +1725,7 @@ int dev_mates_flush(Device* d, int library, MateStats* st, std::string& err) {
         return 0;
     }
     if ((u64)E + L.n >= (1ull << 32) - RS_TILE) { err = "mate table: more than 2^32 entries in one library"; return SAGE2OV_ERR_LIMIT; }
-    lap.start();
+    HIPCHK(lap.start());
     const u32 m = E + (u32)L.n;
     HIPCHK(hipMemcpyAsync(ek + E, L.key, L.n * sizeof(u64), hipMemcpyDeviceToDevice, d->stream));
     HIPCHK(hipMemcpyAsync(ec + E, L.cnt, L.n * sizeof(u64), hipMemcpyDeviceToDevice, d->stream));
@@ -1721,7 +1733,7 @@ int dev_mates_flush(Device* d, int library, MateStats* st, std::string& err) {
     { const int rc = mate_sort(d, B, ek, m, shifts, np, &ks, &vs, st, err); if (rc) return rc; }
     u32 E2 = 0; { const int rc = mate_heads(d, B, ks, m, &hp, &E2, err); if (rc) return rc; }
     u64* nk = B.get<u64>(E2); u64* nc = B.get<u64>(E2); u64* nf = B.get<u64>(E2);
-    if (!nk || !nc || !nf) { err = "mate table: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+    if (!nk || !nc || !nf) return mate_nomem(err);
     hipLaunchKernelGGL(k_mate_merge, dim3(grid_for(E2, 256)), dim3(256), 0, d->stream, ks, vs, ec, ef, hp, E2, nk, nc, nf);
     HIPCHK(hipGetLastError());
     HIPCHK(lap.stop(st->merge_ms));
@@ -1736,28 +1748,28 @@ int dev_mates_flush(Device* d, int library, MateStats* st, std::string& err) {
 int dev_mates_add(Device* d, const char* bases, const uint64_t* off, uint64_t n, int library, uint64_t pair0, MateStats* st, std::string& err) {
     HIPCHK(hipSetDevice(d->ordinal));
     if (d->N >= (1ull << 30)) { err = "mate table: read ids beyond 2^30 - 1"; return SAGE2OV_ERR_LIMIT; }
-    FindTmp T; FindRun R; FindStats fs;
-    { const int rc = find_begin(d, T, R, &fs, err); if (rc) return rc; }
+    FindRun R(d->stream); FindStats fs;
+    { const int rc = find_begin(d, R, &fs, err); if (rc) return rc; }
     st->find_ms += fs.dir_ms;
     R.qcap = std::min<u64>((R.qcap + 1) & ~1ull, 1ull << 22);                      // an even number of queries per chunk (a forced odd value: the next even one)
     const long long forced = d->opt.num("SAGE2OV_TEST_MATE_FLUSH", 0);
     const u64 bound = forced > 0 ? (u64)forced : MATE_FLUSH_RECORDS;
-    Mates* M = mates_of(d); MateLap lap(d->stream);
+    Mates* M = mates_of(d); StreamLap lap(d->stream); HIPCHK(lap.create());
     std::vector<u64> ho;
     for (u64 r0 = 0; r0 < n;) {
         u64 r1 = find_chunk_end(R, off, n, r0); if ((r1 - r0) & 1) r1++;            // (n is even: r1 <= n)
         FindChunk C;
-        { const int rc = find_chunk(d, T, R, bases, off, r0, r1, ho, C, err); if (rc) return rc; }
+        { const int rc = find_chunk(d, R, bases, off, r0, r1, ho, C, err); if (rc) return rc; }
         HIPCHK(hipStreamSynchronize(d->stream));
-        { float a = 0; hipEventElapsedTime(&a, T.ev[0], T.ev[2]); st->find_ms += a; }
+        R.pack.add(st->find_ms); R.search.add(st->find_ms);
         st->chunks++;
         const u32 np = (u32)(C.q / 2);
-        lap.start();
-        MateBufs B; u32* keep = B.get<u32>(np); u32* pos = B.get<u32>(np);
-        if (!keep || !pos) { err = "mate table: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+        HIPCHK(lap.start());
+        DevTmp B; u32* keep = B.get<u32>(np); u32* pos = B.get<u32>(np); u64* partial = B.get<u64>(scan_partial_words(np));
+        if (!keep || !pos || !partial) return mate_nomem(err);
         unsigned long long* kinds = (unsigned long long*)(C.cnt + 6); HIPCHK(hipMemsetAsync(kinds, 0, 2 * sizeof(u64), d->stream));      // ([6], [7] of the chunk's counters: read above, free now)
         hipLaunchKernelGGL(k_mate_keep, dim3(grid_for(np, 256)), dim3(256), 0, d->stream, C.dids, C.sign, C.db, C.dof, np, (u32)d->k, R.maxLen, keep, kinds);
-        u64 nrec = 0; { const int rc = mate_scan(d, B, keep, np, pos, &nrec, err); if (rc) return rc; }
+        u64 nrec = 0; { const int rc = scan_u32(d, keep, np, pos, partial, &nrec, err); if (rc) return rc; }
         u64 hk[2]; HIPCHK(hipMemcpyAsync(hk, kinds, sizeof hk, hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
         st->seen += np; st->not_good += hk[0]; st->not_found += hk[1]; st->added += nrec / 2;
         if (M->pn + nrec > M->pcap) {                                                // grow the pending buffer (its records are kept)
@@ -1788,7 +1800,7 @@ int dev_mates_export(Device* d, int library, uint64_t* key, uint64_t* cnt, uint6
         HIPCHK(hipMemcpyAsync(first, L.first, L.n * sizeof(u64), hipMemcpyDeviceToHost, d->stream));
     }
     if (offsets) {
-        MateBufs B; u64* dofs = B.get<u64>(d->N + 2); if (!dofs) { err = "mate table: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+        DevTmp B; u64* dofs = B.get<u64>(d->N + 2); if (!dofs) return mate_nomem(err);
         hipLaunchKernelGGL(k_mate_offsets, dim3(grid_for(d->N + 2, 256)), dim3(256), 0, d->stream, L.key, (u32)L.n, (u32)d->N, dofs);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(offsets, dofs, (d->N + 2) * sizeof(u64), hipMemcpyDeviceToHost, d->stream));
@@ -1871,27 +1883,6 @@ int dev_append_edges(Device* d, const EdgeCand* e, uint64_t n, std::string& err)
     }
     HIPCHK(hipMemcpyAsync(d->cand + d->n_cand, e, n * sizeof(EdgeCand), hipMemcpyHostToDevice, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
     d->n_cand += n;
-    return 0;
-}
-
-static int scan_u32(Device* d, const u32* in, u64 n, u32* out, u64* total, std::string& err) {
-    const u64 nb = (n + SCAN_BLOCK - 1) / SCAN_BLOCK;
-    WS(partial, u64, WS_PARTIAL, nb + 1);
-    hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, d->stream, in, (u64)n, partial);
-    hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(1024), 0, d->stream, partial, (u64)nb, partial + nb);
-    hipLaunchKernelGGL(k_scan_final, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, d->stream, in, (u64)n, partial, out);
-    HIPCHK(hipMemcpyAsync(total, partial + nb, sizeof(u64), hipMemcpyDeviceToHost, d->stream));
-    HIPCHK(hipStreamSynchronize(d->stream));
-    return 0;
-}
-
-static int scan_u32_async(Device* d, const u32* in, u64 n, u32* out, std::string& err) {
-    const u64 nb = (n + SCAN_BLOCK - 1) / SCAN_BLOCK;
-    WS(partial, u64, WS_PARTIAL, nb + 1);
-    hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, d->stream, in, (u64)n, partial);
-    hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(1024), 0, d->stream, partial, (u64)nb, partial + nb);
-    hipLaunchKernelGGL(k_scan_final, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, d->stream, in, (u64)n, partial, out);
-    HIPCHK(hipGetLastError());
     return 0;
 }
 

@@ -1,5 +1,5 @@
 """GPU: the mate-pair table (sage2ov_mates_*) on the HIP path -- the chunk body of the read-id look-up with the ids left in HBM, k_mate_keep, k_mate_records,
-the k_rs_* passes, k_mate_heads, k_mate_headpos, k_mate_reduce, k_mate_merge and k_mate_offsets (kernels_mates.inc).  The cases and the expected value (a
+the k_rs_* passes, k_mate_heads, k_headpos, k_mate_reduce, k_mate_merge and k_mate_offsets (kernels_mates.inc).  The cases and the expected value (a
 restatement of matePair.cpp:161-239, one thread) are those of tests/test_mates_host.py, run here with device 0; on top of them: the chunk seam and the flush
 bound, every state of the store, device against host, and that the table and the steps do not disturb each other."""
 import numpy as np
@@ -43,6 +43,11 @@ def test_calls():
 @pytest.mark.parametrize("N", M.DIGIT_EDGE_COUNTS)
 def test_digit_edges(N):
     M.case_digit_edges(GPU, N)
+
+
+@pytest.mark.parametrize("P", M.TILE_SEAM_PAIRS)
+def test_tile_seams(P):
+    M.case_tile_seams(GPU, P)
 
 
 def test_libraries(tmp_path):

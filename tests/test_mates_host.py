@@ -261,6 +261,37 @@ def case_digit_edges(device, N):
     ctx.close()
 
 
+TILE_SEAM_PAIRS = [1023, 1024, 1025]
+
+
+def case_tile_seams(device, P):
+    """2 P = 2046 / 2048 / 2050 pending records, all with keys of their own, in one flush, then one more pair, whose merge sorts 2 P + 2 entries: the record
+    counts on both sides of the 2048 items that a block of the scan and a tile of the radix sort take (SCAN_BLOCK, RS_TILE), in the sort, the heads and the merge"""
+    k, n = 21, 300
+    ctx, _ = tiling_store(device, n, 100, k, 7400)
+    store = stored_reads(ctx)
+
+    def pair(x):                                                         # reads i and i + d (mod n), d <= 5 < n / 2: no two x share their two reads, in either order
+        i, d = x % n, 1 + x // n
+        a, b = store[1 + i], store[1 + (i + d) % n]
+        return [fx.revcomp(a) if x % 3 == 0 else a, fx.revcomp(b) if x % 4 == 1 else b]
+
+    passes = radix_passes(n)
+    on_device = device != HOST
+    R = Restated(); st = add(ctx, R, [r for x in range(P) for r in pair(x)], k)
+    assert (st.pairs_added, st.pairs_not_good, st.pairs_not_found, st.records, st.entries_after) == (P, 0, 0, 2 * P, 2 * P)      # every record an entry
+    assert st.route == (s2.MATE_ROUTE_DEVICE if on_device else s2.MATE_ROUTE_HOST)
+    assert (st.chunks, st.flushes, st.sort_passes) == ((1, 1, passes) if on_device else (0, 0, 0))                             # one sort of the records
+    ent = compare(ctx, R)
+    assert len(ent) == 2 * P and np.all(ent["count"] == 1)
+    st = add(ctx, R, pair(4 * n), k)                                     # d = 5: a new pair
+    assert (st.pairs_added, st.entries_before, st.entries_after) == (1, 2 * P, 2 * P + 2)
+    assert (st.chunks, st.flushes, st.sort_passes) == ((1, 1, 2 * passes) if on_device else (0, 0, 0))                         # its two records, then the merge
+    ent = compare(ctx, R)
+    assert len(ent) == 2 * P + 2 and np.all(ent["count"] == 1)
+    ctx.close()
+
+
 def case_libraries(device, tmp_path):
     k = 21
     ctx, reads = tiling_store(device, 300, 100, k, 6700)
@@ -452,6 +483,11 @@ def test_calls():
 @pytest.mark.parametrize("N", DIGIT_EDGE_COUNTS)
 def test_digit_edges(N):
     case_digit_edges(HOST, N)
+
+
+@pytest.mark.parametrize("P", TILE_SEAM_PAIRS)
+def test_tile_seams(P):
+    case_tile_seams(HOST, P)
 
 
 def test_radix_pass_count():
