@@ -305,7 +305,7 @@ __global__ __launch_bounds__(64 * WPB, (NW > 20 ? 1 : (NW > 10 ? 2 : (WPL >= 3 ?
         if (nh) {
             if (nh > hLeft) {                                               // next chunk; the rest of the old one is marked empty
                 for (u32 x = lane; x < hLeft; x += 64) A.hits[hBase + x].from = 0;
-                u64 nb_ = 0; if (lane == 0) nb_ = atomicAdd(&A.counters[4], (u64)HITS_CHUNK);
+                u64 nb_ = 0; if (lane == 0) nb_ = atomicAdd(&A.counters[CTR_HIT_CURSOR], (u64)HITS_CHUNK);
                 hBase = ((u64)__builtin_amdgcn_readfirstlane((int)(nb_ >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)(u32)nb_);
                 hLeft = hBase + HITS_CHUNK <= A.hits_cap ? HITS_CHUNK : 0u;
             }
@@ -1048,7 +1048,7 @@ __global__ __launch_bounds__(64 * WPB, (NW > 20 ? 1 : (NW > 10 ? 2 : (WPL >= 3 ?
                 if (nh) {
                     if (nh > hLeft) {                                               // next chunk; the rest of the old one is marked empty
                         for (u32 x = lane; x < hLeft; x += 64) A.hits[hBase + x].from = 0;
-                        u64 nb_ = 0; if (lane == 0) nb_ = atomicAdd(&A.counters[4], (u64)HITS_CHUNK);
+                        u64 nb_ = 0; if (lane == 0) nb_ = atomicAdd(&A.counters[CTR_HIT_CURSOR], (u64)HITS_CHUNK);
                         hBase = ((u64)__builtin_amdgcn_readfirstlane((int)(nb_ >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)(u32)nb_);
                         hLeft = hBase + HITS_CHUNK <= A.hits_cap ? HITS_CHUNK : 0u;     // over capacity: dropped, the host retries with a larger buffer
                     }
@@ -1501,7 +1501,7 @@ __global__ __launch_bounds__(64 * WPB, (NW > 20 ? 1 : (NW > 10 ? 2 : (WPL >= 3 ?
         }
         STAMP(8);
         if (slowpath) {
-            if (lane == 0) { u64* cn_ = COLD(A, counters); u64 p = atomicAdd(&cn_[6], 1ull); if (p < COLD(A, slow_cap)) COLD(A, slow)[p] = (u32)i; if (capOver) atomicAdd(&cn_[7], 1ull); }
+            if (lane == 0) { u64* cn_ = COLD(A, counters); u64 p = atomicAdd(&cn_[CTR_HANDED], 1ull); if (p < COLD(A, slow_cap)) COLD(A, slow)[p] = (u32)i; if (capOver) atomicAdd(&cn_[CTR_HANDED + 1], 1ull); }
         } else if (HITS) {
             // (not reached: the hit-list variant leaves the loop body above)
         } else {
@@ -1528,7 +1528,7 @@ __global__ __launch_bounds__(64 * WPB, (NW > 20 ? 1 : (NW > 10 ? 2 : (WPL >= 3 ?
     }
     if (HITS || (ALWAYS_TAIL && A.hitBase)) {
         for (u32 x = lane; x < hLeft; x += 64) A.hits[hBase + x].from = 0;
-        if (lane == 0 && hTotal) atomicAdd(&A.counters[5], hTotal);
+        if (lane == 0 && hTotal) atomicAdd(&A.counters[CTR_HIT_REAL], hTotal);
     }
 #ifdef SAGE2OV_STAMPS
     if (A.stamps && lane == 0) for (int x = 0; x < 32; x++) atomicAdd(&A.stamps[x], st_acc[x]);

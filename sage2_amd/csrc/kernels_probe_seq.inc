@@ -42,7 +42,7 @@ struct ProbeArgs {
     u64* hitBase;                                          // fast kernel, TAIL = 2, optional: the read's hits are written out in the initial pass; where they start (~0: not written)
     const u32* ids; u64 n_ids;                             // optional explicit list of positions (replaces [lo,hi))
     const u64* mi1; u64 TL; const u64* krec;               // minimiser index (may be null)
-    u32* slow; u64 slow_cap;                               // fast kernel: reads handed to the sequential kernel (count in counters[6])
+    u32* slow; u64 slow_cap;                               // fast kernel: reads handed to the sequential kernel (count in counters[CTR_HANDED])
     int uniL;                                              // the common read length when all reads have one (else 0): no length gathers
     u64* stamps;                                           // diagnostic build (-DSAGE2OV_STAMPS): wave cycles per phase
     // fast kernel: the grid in up to four PHASES {first block, blocks, rounds, first chunk}: a block of phase p walks chunks first chunk + (block - first block) + r * blocks,
@@ -178,7 +178,7 @@ __global__ __launch_bounds__(64 * WPB) void k_probe(ProbeArgs A) {
                 const u32 hidx = (u32)__popcll(hb & ((1ull << lane) - 1ull));
                 if (MODE == 1) {
                     if (nh) {
-                        u64 base = 0; if (lane == 0) base = atomicAdd(&A.counters[4], (u64)nh); base = __shfl(base, 0);
+                        u64 base = 0; if (lane == 0) base = atomicAdd(&A.counters[CTR_HIT_CURSOR], (u64)nh); base = __shfl(base, 0);
                         if (isHit && base + hidx < A.hits_cap) {
                             Hit hh; hh.from = iid; hh.to = A.idOf[hr2]; hh.len = hlen; hh.type = htype & 3u; hh.seq = seq + hidx;
                             A.hits[base + hidx] = hh;

@@ -82,7 +82,7 @@ __global__ void k_ra_degree_h(const u32* __restrict__ hitcount, u64 N, u32* deg)
 }
 // An entry goes into the list twice: the 64-bit key the marks' kernel sorts (len | to | type | index) and a 32-bit image (to:30 | type:2, ids stay below 2^30) at the same
 // place -- what the kernel reads of the NEIGHBOURS' lists, where only (to, type) matter: half the bytes per list.  (Rounds 2-3 wrote the image in a pass of its own,
-// k_ra_pack32, partitioned by the high bit of the type so that the walk of every list fetched only the half that continues in its direction; since round 4 the marks come
+// partitioned by the high bit of the type so that the walk of every list fetched only the half that continues in its direction; since round 4 the marks come
 // from 2-3 whole lists per read -- both halves: the other one names the list's potential markers -- and the pass, 3.1 ms at configs[1] + 0.1 % errors, is gone.)
 __device__ __forceinline__ void ra_put(u64* ent, u32* ent32, u64 at, u32 to, u32 type, u32 len) { ent[at] = ra_key(to, type, len); ent32[at] = (to << 2) | (type & 3u); }
 __global__ void k_ra_fill_c(const EdgeCand* __restrict__ cand, u64 n, const u64* __restrict__ reads, int S, int uniL, const u32* __restrict__ offs, u32* cursor, u64* ent, u32* ent32) {
@@ -483,7 +483,6 @@ __global__ void k_rr_unres_pick(const u32* __restrict__ order, u64 n, const u32*
 // the walk's starts: positions of the unresolved reads in ASCENDING ID order (the order in which the serial loop starts its searches, economyGraph.cpp:513)
 __global__ void k_rr_start_flag(u64 N, const uint8_t* __restrict__ status, u32* flag) { const u64 x = (u64)blockIdx.x * blockDim.x + threadIdx.x; if (x < N) flag[x] = status[x + 1] == 0 ? 1u : 0u; }
 __global__ void k_rr_start_pick(u64 N, const u32* __restrict__ flag, const u32* __restrict__ fpos, const u32* __restrict__ posOf, u32* out) { const u64 x = (u64)blockIdx.x * blockDim.x + threadIdx.x; if (x < N && flag[x]) out[fpos[x]] = posOf[x + 1]; }
-__global__ void k_rr_loc(const u32* __restrict__ order, u64 n, u32* loc) { const u64 p = (u64)blockIdx.x * blockDim.x + threadIdx.x; if (p < n) loc[order[p]] = (u32)p + 1u; }
 __global__ void k_rr_rank_by_id(const u32* __restrict__ rankByPos, const u32* __restrict__ loc, u64 n, u32* rankById) {
     const u64 id = (u64)blockIdx.x * blockDim.x + threadIdx.x; if (id < n) rankById[id] = rankByPos[loc[id]];
 }

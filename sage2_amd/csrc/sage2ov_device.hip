@@ -38,9 +38,33 @@ namespace s2 {
 typedef unsigned long long u64;
 typedef unsigned int u32;
 
-enum { WS_SLOTS, WS_CNT, WS_WHERE, WS_BIG, WS_CSR, WS_SLOW, WS_NEED, WS_DEG, WS_OFFS, WS_CURSOR, WS_KEYS, WS_KEEP, WS_POS, WS_OWNER, WS_FINAL,
-       WS_PARTIAL, WS_IDS, WS_NEAR, WS_HITS, WS_MINH, WS_OCNT, WS_OOFF, WS_OCUR, WS_ORDER, WS_MI1, WS_MICNT, WS_MICUR, WS_KREC, WS_SLOTMH, WS_RA_DEG, WS_RA_OFF, WS_RA_CUR, WS_RA_ENT, WS_RA_RM, WS_ORG_POOL, WS_ORG_OFF, WS_ORG_LEN, WS_ORG_IMG, WS_ORG_K0, WS_ORG_K1, WS_ORG_V0, WS_ORG_V1, WS_ORG_HIST, WS_ORG_HSCAN, WS_ORG_FLAG, WS_ORG_UID, WS_ORG_HEAD, WS_RR_IN, WS_RR_DEGP, WS_RR_OFFP, WS_RR_ENTP, WS_RR_OUTP, WS_RR_WIDX, WS_RR_RANK, WS_RR_CUR, WS_RA_HEAVY, WS_RA_HSIZE, WS_RA_HSCR, WS_RR_LEN, WS_RR_COFF, WS_RR_OUTC,
-       WS_PT_K0, WS_PT_K1, WS_PT_P0, WS_PT_P1, WS_PT_M0, WS_PT_M1, WS_PT_CNT, WS_PT_BASE, WS_PT_OFF, WS_PT_GOFF, WS_RR_LOC, WS_RR_RANKL, WS_LOC_READS, WS_LOC_IDOF, WS_LOC_POSOF, WS_LOC_STATUS, WS_ORG_GFLAG, WS_ORG_GPOS, WS_LOC_META, WS_SLOW2, WS_RA_ENT32, WS_RA_SPLIT, WS_PRE_BASE, WS_PRE_NONE, WS_COUNT };   // ids of the workspace arena (Device::ws)
+enum { WS_SLOTS, WS_WHERE, WS_BIG, WS_CSR, WS_SLOW, WS_NEED, WS_CURSOR, WS_KEYS, WS_KEEP, WS_POS, WS_OWNER, WS_FINAL,
+       WS_PARTIAL, WS_IDS, WS_NEAR, WS_HITS, WS_MINH, WS_OCUR, WS_MI1, WS_KREC, WS_RA_DEG, WS_RA_OFF, WS_RA_CUR, WS_RA_ENT, WS_RA_RM, WS_ORG_POOL, WS_ORG_OFF, WS_ORG_LEN, WS_ORG_IMG, WS_ORG_K0, WS_ORG_K1, WS_ORG_V0, WS_ORG_V1, WS_ORG_HIST, WS_ORG_HSCAN, WS_ORG_FLAG, WS_ORG_UID, WS_ORG_HEAD, WS_RR_IN, WS_RR_DEGP, WS_RR_OFFP, WS_RR_ENTP, WS_RR_OUTP, WS_RR_WIDX, WS_RR_RANK, WS_RR_CUR, WS_RA_HEAVY, WS_RA_HSIZE, WS_RA_HSCR, WS_RR_LEN, WS_RR_COFF, WS_RR_OUTC,
+       WS_PT_K0, WS_PT_K1, WS_PT_CNT, WS_PT_BASE, WS_PT_OFF, WS_PT_GOFF, WS_RR_RANKL, WS_LOC_READS, WS_LOC_IDOF, WS_LOC_POSOF, WS_LOC_STATUS, WS_ORG_GFLAG, WS_ORG_GPOS, WS_LOC_META, WS_SLOW2, WS_RA_ENT32, WS_RA_SPLIT, WS_PRE_BASE, WS_PRE_NONE, WS_COUNT };   // ids of the workspace arena (Device::ws)
+// Bases of the device counters (Device::d_counters, u64 words): who owns the words from each base on, how many, what each holds.  A kernel that is handed
+// d_counters + base indexes from that base; the probe kernels are handed d_counters itself (ProbeArgs::counters) and use the CTR_HIT_* / CTR_HANDED names.
+// Slots that two phases use in turn, never at once: CTR_LIST is CTR_HIT_REAL (a list is collected before or after the hit lists, not during them);
+// CTR_INDEX, CTR_RANKED and CTR_MARKS share base 8 (index build, then within one reduce the ranked lists, read back and zeroed before the marks);
+// the last two words of CTR_INDEX are the first two of CTR_ORG (step 1 is over when the index build starts);
+// dev_reciprocal zeroes the 8 words from CTR_RECIP, the probe's four with them (the probe pass is over by then).
+enum {
+    CTR_RECIP = 0,        // reciprocal pass, 4 words: [0] cursor of the candidate list, [1] verified overlaps, [2] contained reads, [3] their summed size
+    CTR_HIT_CURSOR = 4,   // probe kernels that write hits, 1 word: cursor in the Hit buffer (may pass the capacity: nothing is written beyond it)
+    CTR_HIT_REAL = 5,     // fast kernel's hit-list form, 1 word: real hits among the chunks it took
+    CTR_LIST = 5,         // cursor of a collected list, 1 word: k_red_unresolved, k_red_collect, k_red_collect_few (in turn with CTR_HIT_REAL)
+    CTR_HANDED = 6,       // fast kernel, 2 words: [0] reads handed on to the next pass (the slow list), [1] of them: more candidates than the form has slots
+    CTR_INDEX = 8,        // index build, 10 words: [0] csr entries, [1] keys, [2] long buckets, [3] impure long buckets, [4] pure ones, [5] group records, [6] groups,
+                          //   [7] group windows given up, [8] failures (windows overflowed | keys beyond the count field << 20 | heavy windows without scratch << 40), [9] scratch cursor
+    CTR_RANKED = 8,       // reduce phase, ranked lists, 4 words: [2] hits present in the final lists (k_rr_degree_h), [3] potential lists beyond RR_CAP (k_rr_sortp); [0], [1] unused
+    CTR_MARKS = 8,        // reduce phase, marks, 5 words: [0] lists beyond RA_CAP, [1] removed entries, [2] lists the short cut read, [3] reads it settled, [4] reads listed for the second launch
+    CTR_ORG = 16,         // step 1's ASCII front end (k_org_classify), 6 words: [0] longest good read, [1] good reads, [2] their bases, [3] reads not longer than
+                          //   the minimum overlap, [4] shortest good read, [5] reads beyond the length limit
+    CTR_FILTER = 22,      // reduce phase, pre-hits filter (k_hits_filter), 2 words: [0] kept hits, [1] unresolved reads without written hits
+    CTR_RUNSTARTS = 24,   // locality order (k_loc_index), 64 words: run starts, spread over 64 words (Device::d_runStarts)
+    CTR_WORDS = 24 + 64   // what dev_create allocates
+};
+static_assert(CTR_RECIP + 8 <= CTR_INDEX && CTR_HANDED + 2 <= CTR_INDEX && CTR_INDEX + 10 <= CTR_FILTER && CTR_MARKS + 5 <= CTR_ORG && CTR_ORG + 6 <= CTR_FILTER &&
+              CTR_FILTER + 2 <= CTR_RUNSTARTS && CTR_RUNSTARTS + 64 <= CTR_WORDS, "a counter group runs into the next one, or past the allocation");
 struct MateLib { u64* key = nullptr; u64* cnt = nullptr; u64* first = nullptr; u64 n = 0; };      // one library's mate table: sorted by key, unique (kernels_mates.inc)
 struct Mates { MateLib lib[128]; u64* pkey = nullptr; u64* pord = nullptr; u64 pn = 0, pcap = 0; };   // + the pending records of the call in progress (keys, record ordinals)
 struct Device {
@@ -65,7 +89,7 @@ struct Device {
     // per-read results
     u64* right = nullptr; u64* left = nullptr; u32* conn = nullptr; u32* cflag = nullptr; uint8_t* status = nullptr;
     // edge candidates
-    EdgeCand* cand = nullptr; u64 cand_cap = 0; u64* d_counters = nullptr;  // [0]=n_cand [1]=n_ov [2]=contained [3]=containedSize [4]=n_hits [5]=flag
+    EdgeCand* cand = nullptr; u64 cand_cap = 0; u64* d_counters = nullptr;  // CTR_WORDS words: see the CTR_ enum
     u64 n_cand = 0;
     // final edges (device resident)
     FinalEdge* final_edges = nullptr; u64 n_final = 0;
@@ -204,7 +228,7 @@ static void mem_sample(Device* d) { size_t fr = 0, to = 0; if (hipMemGetInfo(&fr
 // builds by the limit checks of the callers: reads < 2^30, tuples < 2^32); kernels whose item count can pass it are grid-stride and use grid_for_capped.
 static inline unsigned grid_for(u64 n, unsigned block) { return (unsigned)std::max<u64>(1, (n + block - 1) / block); }
 static inline unsigned grid_for_capped(u64 n, unsigned block) { return (unsigned)std::max<u64>(1, std::min<u64>((n + block - 1) / block, ((1ull << 32) / block) - 1)); }
-// out[0, n) = d_counters[first, first + n), once the stream has finished (the slots mean different things in different phases: see the callers)
+// out[0, n) = d_counters[first, first + n), once the stream has finished (first: a CTR_ base)
 static int read_counters(Device* d, int first, int n, u64* out, std::string& err) {
     HIPCHK(hipMemcpyAsync(out, d->d_counters + first, n * sizeof(u64), hipMemcpyDeviceToHost, d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
@@ -272,6 +296,33 @@ static int head_positions(Device* d, const u32* flag, const u32* pos, u64 n, u32
     HIPCHK(hipGetLastError());
     return 0;
 }
+// Host buffers on 2 MB pages where the kernel hands them out (transparent huge pages, madvise mode), pinned on request: what the exploration walk of the ranked
+// reduce reads is spread over gigabytes, far beyond what a TLB of 4 KB pages covers
+struct HugeBuf {
+    void* p = nullptr; size_t bytes = 0; bool registered = false;
+    void* get(size_t n) {
+        bytes = (std::max<size_t>(n, 1) + (2u << 20) - 1) & ~(size_t)((2u << 20) - 1);
+        p = mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
+        if (p == MAP_FAILED) { p = nullptr; return nullptr; }
+        madvise(p, bytes, MADV_HUGEPAGE);
+        return p;
+    }
+    ~HugeBuf() { if (p) { if (registered) hipHostUnregister(p); munmap(p, bytes); } }
+};
+// ranked reduce: the pinned buffers the potential lists are downloaded into (Device::rrStaging); slice s of a call reuses buffer s of the previous call when it is large enough
+struct RrStaging {
+    std::vector<std::unique_ptr<HugeBuf>> bufs; size_t next = 0;
+    u32* get(size_t n) {
+        const size_t want = (std::max<size_t>(n, 16) + 16) * sizeof(u32);
+        if (next < bufs.size() && bufs[next]->p && bufs[next]->bytes >= want) return (u32*)bufs[next++]->p;
+        std::unique_ptr<HugeBuf> b(new HugeBuf()); u32* p = (u32*)b->get(want + want / 8); if (!p) return nullptr;
+        memset(p, 0, b->bytes);                                  // (touch: the pages exist before they are pinned)
+        if (hipHostRegister(p, b->bytes, hipHostRegisterDefault) == hipSuccess) b->registered = true; else (void)hipGetLastError();
+        if (next < bufs.size()) bufs[next] = std::move(b); else bufs.push_back(std::move(b));
+        return (u32*)bufs[next++]->p;
+    }
+};
+static void rr_staging_release(Device* d) { if (d->rrStaging) { delete (RrStaging*)d->rrStaging; d->rrStaging = nullptr; } }
 
 // =============================================================================================
 // host-side launchers
@@ -297,14 +348,13 @@ Device* dev_create(int ordinal, const Options& opt, std::string& err) {
       const u32 fmask = (nf >= 0 && nf < 20) ? ((1u << nf) - 1u) : 0xFFFFFu;
       if (hipMemcpyToSymbol(HIP_SYMBOL(g_fp_mask), &fmask, sizeof fmask) != hipSuccess) { err = "fingerprint mask upload failed"; delete d; return nullptr; } }
     for (auto& ev : d->ev) hipEventCreate(&ev);
-    if (hipMalloc(&d->d_counters, (24 + 64) * sizeof(u64)) != hipSuccess) { err = "hipMalloc(counters) failed"; delete d; return nullptr; }
-    hipMemset(d->d_counters, 0, (24 + 64) * sizeof(u64));
-    d->d_runStarts = d->d_counters + 24;
+    if (hipMalloc(&d->d_counters, CTR_WORDS * sizeof(u64)) != hipSuccess) { err = "hipMalloc(counters) failed"; delete d; return nullptr; }
+    hipMemset(d->d_counters, 0, CTR_WORDS * sizeof(u64));
+    d->d_runStarts = d->d_counters + CTR_RUNSTARTS;
     if (hipHostMalloc((void**)&d->h_runStarts, 64 * sizeof(u64), hipHostMallocDefault) != hipSuccess || hipEventCreateWithFlags(&d->evRunStarts, hipEventDisableTiming) != hipSuccess) {
         err = "hipHostMalloc / hipEventCreate failed"; hipFree(d->d_counters); delete d; return nullptr; }
     return d;
 }
-static void rr_staging_release(Device* d);
 static void mates_release(Device* d);
 static void free_reads(Device* d) {
     rr_staging_release(d);                     // (pinned host buffers sized by the previous read set)
@@ -382,9 +432,9 @@ int dev_organize_reads(Device* d, const uint64_t* pool, uint64_t pool_words, con
         dbases = db; doffA = dof; gflag = gf; gpos = gp;
         HIPCHK(hipMemcpyAsync(dbases, ascii->bases, ascii->nbytes, hipMemcpyHostToDevice, d->stream));
         HIPCHK(hipMemcpyAsync(doffA, ascii->off, (nin + 1) * sizeof(u64), hipMemcpyHostToDevice, d->stream));
-        u64 init[6] = {0, 0, 0, 0, ~0ull, 0}; HIPCHK(hipMemcpyAsync(d->d_counters + 16, init, sizeof init, hipMemcpyHostToDevice, d->stream));
-        if (nin) hipLaunchKernelGGL(k_org_classify, dim3(grid_for(nin, 256)), dim3(256), 0, d->stream, dbases, doffA, (u64)nin, (u32)k, 1018u, gflag, d->d_counters + 16);
-        u64 cc[6]; { int rc = read_counters(d, 16, 6, cc, err); if (rc) return rc; }
+        u64 init[6] = {0, 0, 0, 0, ~0ull, 0}; HIPCHK(hipMemcpyAsync(d->d_counters + CTR_ORG, init, sizeof init, hipMemcpyHostToDevice, d->stream));
+        if (nin) hipLaunchKernelGGL(k_org_classify, dim3(grid_for(nin, 256)), dim3(256), 0, d->stream, dbases, doffA, (u64)nin, (u32)k, 1018u, gflag, d->d_counters + CTR_ORG);
+        u64 cc[6]; { int rc = read_counters(d, CTR_ORG, 6, cc, err); if (rc) return rc; }
         if (cc[5]) { err = "reads longer than 1018 bases are not supported"; return SAGE2OV_ERR_LIMIT; }
         ascii->good = cc[1]; ascii->total_bp = cc[2]; ascii->small = cc[3]; ascii->maxL = (int)cc[0]; ascii->minL = cc[1] ? (int)cc[4] : 0;
         n = cc[1]; maxL = ascii->maxL; minL = ascii->minL;
@@ -663,7 +713,7 @@ int dev_build_index(Device* d, uint64_t* slots_out, uint64_t* keys_out, uint64_t
     auto lap = [&](const char* what) { if (!timing) return; hipStreamSynchronize(d->stream); auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[index] %-34s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - tp).count()); tp = t; };
     u64 c[9]; u32 ixCntBits = (u32)IXW_CNT_BITS_DEFAULT;
     for (int attempt = 0;; attempt++) {
-        HIPCHK(hipMemsetAsync(d->d_counters + 8, 0, 10 * sizeof(u64), d->stream));
+        HIPCHK(hipMemsetAsync(d->d_counters + CTR_INDEX, 0, 10 * sizeof(u64), d->stream));
         // ---- tuples of the 4N entries, sorted by the window of their home slot
         int shift0, doHist; u32 mask0; pt_first_digit(nW, IX_WPLOG, &shift0, &mask0, &doHist);
         if (copyPending) { hipLaunchKernelGGL(k_ix_tuples_loc, dim3(ntiles), dim3(PT_THREADS), 0, d->stream, d->reads, d->posOf, (u32)N, d->h, d->seed, (u32)(d->T >> 1), wantMI ? 1 : 0, shift0, mask0, doHist,
@@ -683,15 +733,15 @@ int dev_build_index(Device* d, uint64_t* slots_out, uint64_t* keys_out, uint64_t
         }
         // ---- the windows of the uniform table, built in LDS; group tuples into the free buffer set
         IxWinArgs A; A.T = B.E[cur]; A.W = B.W; A.winOff = winOff; A.nW = (u32)nW; A.slots = d->slots; A.csr = d->csr;
-        A.counters = d->d_counters + 8; A.big = big; A.big_cap = big_cap; A.idOf = d->idOf; A.G = wantMI ? B.E[cur ^ 1] : nullptr; A.wh = nullptr; A.cntBits = ixCntBits;     // (group tuples, 12 bytes each, into the free 16-byte buffer)
+        A.counters = d->d_counters + CTR_INDEX; A.big = big; A.big_cap = big_cap; A.idOf = d->idOf; A.G = wantMI ? B.E[cur ^ 1] : nullptr; A.wh = nullptr; A.cntBits = ixCntBits;     // (group tuples, 12 bytes each, into the free 16-byte buffer)
         // (the scratch words of heavy windows need a buffer of their own)
         // one word per SURPLUS tuple of a heavy window (more than 3072 tuples where the mean is 2048: keys in thousands of reads); small inputs get the
         // worst case (every tuple in one window), big ones an eighth of it
         { const u64 whCap = n <= (64u << 20) ? nAlloc : nAlloc / 8; WS(whs, u64, WS_WHERE, whCap); A.wh = whs; A.wh_cap = whCap; }
         hipLaunchKernelGGL(k_ix_window, dim3((unsigned)std::min<u64>(nW, 256ull * 6)), dim3(IXW_T), 0, d->stream, A);      // persistent: two rounds of 3 workgroups per CU, each with ONE pair of statistics atomics
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(c, d->d_counters + 8, sizeof c, hipMemcpyDeviceToHost, d->stream));
-        u64 c9 = 0; HIPCHK(hipMemcpyAsync(&c9, d->d_counters + 8 + 9, sizeof c9, hipMemcpyDeviceToHost, d->stream));
+        HIPCHK(hipMemcpyAsync(c, d->d_counters + CTR_INDEX, sizeof c, hipMemcpyDeviceToHost, d->stream));
+        u64 c9 = 0; HIPCHK(hipMemcpyAsync(&c9, d->d_counters + CTR_INDEX + 9, sizeof c9, hipMemcpyDeviceToHost, d->stream));
         HIPCHK(hipStreamSynchronize(d->stream));
         lap("table windows"); mem_sample(d);
         if (c[8] && (c[8] & 0xFFFFFull) == 0 && (c[8] >> 40) == 0 && ixCntBits == (u32)IXW_CNT_BITS_DEFAULT) {      // only the per-key counter ran over: again, with 30 bits of count
@@ -702,8 +752,8 @@ int dev_build_index(Device* d, uint64_t* slots_out, uint64_t* keys_out, uint64_t
                     err = b_; return SAGE2OV_ERR_LIMIT; }
         if (c[2] > big_cap) { err = "too many long buckets"; return SAGE2OV_ERR_LIMIT; }
         if (c[2]) {
-            hipLaunchKernelGGL(k_index_purity, dim3(grid_for(c[2] * 64, 256)), dim3(256), 0, d->stream, d->readsLoc, d->S, d->h, big, c[2], d->csr, d->d_counters + 8);
-            HIPCHK(hipMemcpyAsync(c, d->d_counters + 8, 5 * sizeof(u64), hipMemcpyDeviceToHost, d->stream));
+            hipLaunchKernelGGL(k_index_purity, dim3(grid_for(c[2] * 64, 256)), dim3(256), 0, d->stream, d->readsLoc, d->S, d->h, big, c[2], d->csr, d->d_counters + CTR_INDEX);
+            HIPCHK(hipMemcpyAsync(c, d->d_counters + CTR_INDEX, 5 * sizeof(u64), hipMemcpyDeviceToHost, d->stream));
             HIPCHK(hipStreamSynchronize(d->stream));
         }
         if (c[3] == 0) { d->n_csr = c[0]; d->n_keys = c[1]; d->n_long = c[2];
@@ -715,12 +765,12 @@ int dev_build_index(Device* d, uint64_t* slots_out, uint64_t* keys_out, uint64_t
                 int gcur = 0; const int gshift = 31 - (tlBits - IX_GWLOG);                                  // keys are minimiser hashes >> 1
                 { int rc = partition_by_window(d, G, 0, nG, gshift, gW + 1, false, cnt, base, gOff, &gcur, err); if (rc) return rc; }
                 lap("partition by group window");
-                MiWinArgs MA; MA.G = G.E[gcur]; MA.gOff = gOff; MA.gW = (u32)gW; MA.tlBits = tlBits; MA.mi1 = mi1; MA.krec = krec; MA.counters = d->d_counters + 8; MA.wh = A.wh; MA.wh_cap = A.wh_cap;
-                HIPCHK(hipMemsetAsync(d->d_counters + 8 + 9, 0, sizeof(u64), d->stream));                  // (the scratch cursor starts over)
+                MiWinArgs MA; MA.G = G.E[gcur]; MA.gOff = gOff; MA.gW = (u32)gW; MA.tlBits = tlBits; MA.mi1 = mi1; MA.krec = krec; MA.counters = d->d_counters + CTR_INDEX; MA.wh = A.wh; MA.wh_cap = A.wh_cap;
+                HIPCHK(hipMemsetAsync(d->d_counters + CTR_INDEX + 9, 0, sizeof(u64), d->stream));                  // (the scratch cursor starts over)
                 hipLaunchKernelGGL(k_mi_window, dim3((unsigned)std::min<u64>(gW, 256ull * 8)), dim3(256), 0, d->stream, MA);
                 // the probe scan may run past the last group: empty records behind ALL records
                 u64 mc[3];
-                HIPCHK(hipMemcpyAsync(mc, d->d_counters + 8 + 5, sizeof mc, hipMemcpyDeviceToHost, d->stream));
+                HIPCHK(hipMemcpyAsync(mc, d->d_counters + CTR_INDEX + 5, sizeof mc, hipMemcpyDeviceToHost, d->stream));
                 HIPCHK(hipStreamSynchronize(d->stream));
                 HIPCHK(hipMemsetAsync(krec + mc[0], 0, MI_SCAN_PAD * sizeof(u64), d->stream));   // (mc[0] records, at krec[0 .. mc[0]))
                 lap("group windows"); mem_sample(d);
@@ -931,7 +981,7 @@ int dev_probe(Device* d, uint64_t lo, uint64_t hi, std::string& err) {
     HIPCHK(hipEventRecord(d->ev[0], d->stream));
     HIPCHK(hipMemsetAsync(d->right, 0, (N + 1) * sizeof(u64), d->stream)); HIPCHK(hipMemsetAsync(d->left, 0, (N + 1) * sizeof(u64), d->stream));
     HIPCHK(hipMemsetAsync(d->conn, 0, (N + 1) * sizeof(u32), d->stream)); HIPCHK(hipMemsetAsync(d->cflag, 0, (N + 1) * sizeof(u32), d->stream));
-    HIPCHK(hipMemsetAsync(d->d_counters + 6, 0, 2 * sizeof(u64), d->stream));          // [6] reads handed on, [7] of them: more candidates than the form has slots
+    HIPCHK(hipMemsetAsync(d->d_counters + CTR_HANDED, 0, 2 * sizeof(u64), d->stream));
     ProbeArgs A = base_args(d); A.lo = lo; A.hi = hi;
     const u64 nreads = hi > lo ? hi - lo : 0;
     d->pre.valid = false;
@@ -951,7 +1001,7 @@ int dev_probe(Device* d, uint64_t lo, uint64_t hi, std::string& err) {
         const bool prehits = d->probeShare == 1.0 && lo == 1 && hi == N + 1 && !d->opt.get("SAGE2OV_NO_PREHITS");
         struct FastPass { bool launched = false; u64 listed = 0, capped = 0; };
         // One timed pass of the fast kernel in form f over B's range or id list of n reads: its grid, the launch between two events, what it listed
-        // (d_counters[6..7]).  The main pass: its wide form falls back to the clean one, its TAIL = 2 form writes the hits out (prehits).
+        // (CTR_HANDED).  The main pass: its wide form falls back to the clean one, its TAIL = 2 form writes the hits out (prehits).
         auto pass = [&](Form f, ProbeArgs& B, u64 n, bool mainPass, FastPass& r) -> int {
             const unsigned nb = plan_fast_grid(d->opt, B, n, f == Form::Tail2);
             bool armed = false;
@@ -962,7 +1012,7 @@ int dev_probe(Device* d, uint64_t lo, uint64_t hi, std::string& err) {
                 else {
                     WS(hbase, u64, WS_PRE_BASE, N + 2); WS(hcnt, u32, WS_RA_CUR, N + 2);
                     HIPCHK(hipMemsetAsync(hbase, 0xFF, (N + 2) * sizeof(u64), d->stream)); HIPCHK(hipMemsetAsync(hcnt, 0, (N + 2) * sizeof(u32), d->stream));
-                    HIPCHK(hipMemsetAsync(d->d_counters + 4, 0, 2 * sizeof(u64), d->stream));
+                    HIPCHK(hipMemsetAsync(d->d_counters + CTR_HIT_CURSOR, 0, 2 * sizeof(u64), d->stream));      // (and CTR_HIT_REAL)
                     B.hits = hb; B.hits_cap = hcap; B.hitBase = hbase; B.hitcount = hcnt; armed = true;
                     d->pre.hits = hb; d->pre.cap = hcap; d->pre.base = hbase;
                 }
@@ -971,11 +1021,11 @@ int dev_probe(Device* d, uint64_t lo, uint64_t hi, std::string& err) {
             r.launched = launch_form(d, f, B, nb) || (mainPass && f == Form::Wide && launch_form(d, Form::Clean, B, nb));
             HIPCHK(hipGetLastError());
             HIPCHK(hipEventRecord(d->ev[3], d->stream));
-            u64 c[2]; { int rc = read_counters(d, 6, 2, c, err); if (rc) return rc; } r.listed = c[0]; r.capped = c[1];
+            u64 c[2]; { int rc = read_counters(d, CTR_HANDED, 2, c, err); if (rc) return rc; } r.listed = c[0]; r.capped = c[1];
             float ms = 0; hipEventElapsedTime(&ms, d->ev[2], d->ev[3]); kms += ms; d->tm.probe_fast_launches++;      // (counted even when nothing was launched)
             if (d->opt.get("SAGE2OV_TIMING")) fprintf(stderr, "[probe] fast kernel launch %.3f ms, listed so far %llu\n", ms, (unsigned long long)r.listed);
             if (armed && r.launched) {
-                u64 used = 0; { int rc = read_counters(d, 4, 1, &used, err); if (rc) return rc; }
+                u64 used = 0; { int rc = read_counters(d, CTR_HIT_CURSOR, 1, &used, err); if (rc) return rc; }
                 d->pre.used = used; d->pre.valid = used <= d->pre.cap;                  // (a chunk beyond the buffer: hits were dropped, the reduce phase makes its own lists)
             }
             return 0;
@@ -984,7 +1034,7 @@ int dev_probe(Device* d, uint64_t lo, uint64_t hi, std::string& err) {
         u32* list = slow; u64 nslow = 0;
         auto list_pass = [&](Form f, u32** out, FastPass& r) -> int {
             WS(slow2, u32, WS_SLOW2, nslow);
-            HIPCHK(hipMemsetAsync(d->d_counters + 6, 0, 2 * sizeof(u64), d->stream));
+            HIPCHK(hipMemsetAsync(d->d_counters + CTR_HANDED, 0, 2 * sizeof(u64), d->stream));
             ProbeArgs B = base_args(d); B.ids = slow; B.n_ids = nslow; B.slow = slow2; B.slow_cap = nslow;
 #ifdef SAGE2OV_STAMPS
             if (f == Form::Tail1) B.stamps = A.stamps;
@@ -1132,20 +1182,20 @@ int dev_reciprocal(Device* d, uint64_t emit_lo, uint64_t emit_hi, uint64_t* n_ov
     HIPCHK(hipSetDevice(d->ordinal));
     const u64 N = d->N;
     HIPCHK(hipEventRecord(d->ev[0], d->stream));
-    HIPCHK(hipMemsetAsync(d->d_counters, 0, 8 * sizeof(u64), d->stream));
+    HIPCHK(hipMemsetAsync(d->d_counters + CTR_RECIP, 0, 8 * sizeof(u64), d->stream));      // (its four words and the probe pass's four)
     // (records by position; the status goes out by position -- statusP, what the emit half and the hit-list kernels read -- and by id)
-    hipLaunchKernelGGL(k_recip_cond, dim3(grid_for(N, 256 * COND_PER_THREAD)), dim3(256), 0, d->stream, N, d->right, d->left, d->conn, d->cflag, d->idOf, d->status, d->statusP, d->d_counters);
+    hipLaunchKernelGGL(k_recip_cond, dim3(grid_for(N, 256 * COND_PER_THREAD)), dim3(256), 0, d->stream, N, d->right, d->left, d->conn, d->cflag, d->idOf, d->status, d->statusP, d->d_counters + CTR_RECIP);
     HIPCHK(hipEventRecord(d->ev[4], d->stream));
     if (d->diet && emit_hi > emit_lo) {                                     // the list is sized by a counting pass (capacity 0: nothing is written, the cursor counts)
-        hipLaunchKernelGGL(k_recip_emit, dim3(grid_for(emit_hi - emit_lo, 256 * EMIT_PER_THREAD)), dim3(256), 0, d->stream, N, d->readsLoc, d->S, d->uniL, d->right, d->left, d->statusP, d->idOf, (EdgeCand*)nullptr, (u64)0, d->d_counters, (u64)emit_lo, (u64)emit_hi);
-        u64 want = 0; { int rc = read_counters(d, 0, 1, &want, err); if (rc) return rc; }
+        hipLaunchKernelGGL(k_recip_emit, dim3(grid_for(emit_hi - emit_lo, 256 * EMIT_PER_THREAD)), dim3(256), 0, d->stream, N, d->readsLoc, d->S, d->uniL, d->right, d->left, d->statusP, d->idOf, (EdgeCand*)nullptr, (u64)0, d->d_counters + CTR_RECIP, (u64)emit_lo, (u64)emit_hi);
+        u64 want = 0; { int rc = read_counters(d, CTR_RECIP, 1, &want, err); if (rc) return rc; }
         if (want + 1024 > d->cand_cap || !d->cand) { int rc = cand_resize(d, want + 1024, 0, err); if (rc) return rc; }
-        HIPCHK(hipMemsetAsync(d->d_counters, 0, sizeof(u64), d->stream));
+        HIPCHK(hipMemsetAsync(d->d_counters + CTR_RECIP, 0, sizeof(u64), d->stream));
     }
     if (emit_hi > emit_lo)
-        hipLaunchKernelGGL(k_recip_emit, dim3(grid_for(emit_hi - emit_lo, 256 * EMIT_PER_THREAD)), dim3(256), 0, d->stream, N, d->readsLoc, d->S, d->uniL, d->right, d->left, d->statusP, d->idOf, d->cand, d->cand_cap, d->d_counters, (u64)emit_lo, (u64)emit_hi);
+        hipLaunchKernelGGL(k_recip_emit, dim3(grid_for(emit_hi - emit_lo, 256 * EMIT_PER_THREAD)), dim3(256), 0, d->stream, N, d->readsLoc, d->S, d->uniL, d->right, d->left, d->statusP, d->idOf, d->cand, d->cand_cap, d->d_counters + CTR_RECIP, (u64)emit_lo, (u64)emit_hi);
     u64 c[8];
-    HIPCHK(hipMemcpyAsync(c, d->d_counters, sizeof c, hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipMemcpyAsync(c, d->d_counters + CTR_RECIP, sizeof c, hipMemcpyDeviceToHost, d->stream));
     HIPCHK(hipEventRecord(d->ev[1], d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
     float ms = 0; hipEventElapsedTime(&ms, d->ev[0], d->ev[1]); d->tm.reciprocal_ms += ms;
@@ -1183,15 +1233,22 @@ static int collect_unresolved(Device* d, u32** ids, u64* n, std::string& err) {
     u64 cap = 1 << 20;
     for (int attempt = 0; attempt < 2; attempt++) {
         WS(buf, u32, WS_IDS, cap);
-        HIPCHK(hipMemsetAsync(d->d_counters + 5, 0, sizeof(u64), d->stream));
-        hipLaunchKernelGGL(k_red_unresolved, dim3(grid_for(d->N, 256 * UNRES_PER_THREAD)), dim3(256), 0, d->stream, (u64)d->N, d->status, buf, cap, d->d_counters + 5);
-        u64 cnt = 0; { int rc = read_counters(d, 5, 1, &cnt, err); if (rc) return rc; }
+        HIPCHK(hipMemsetAsync(d->d_counters + CTR_LIST, 0, sizeof(u64), d->stream));
+        hipLaunchKernelGGL(k_red_unresolved, dim3(grid_for(d->N, 256 * UNRES_PER_THREAD)), dim3(256), 0, d->stream, (u64)d->N, d->status, buf, cap, d->d_counters + CTR_LIST);
+        u64 cnt = 0; { int rc = read_counters(d, CTR_LIST, 1, &cnt, err); if (rc) return rc; }
         if (cnt <= cap) { *ids = buf; *n = cnt; return 0; }
         cap = cnt;
     }
     err = "unresolved id collection failed"; return SAGE2OV_ERR_INTERNAL;
 }
-int dev_unresolved_ids(Device* d, std::vector<uint32_t>& ids, std::string& err);
+int dev_unresolved_ids(Device* d, std::vector<uint32_t>& ids, std::string& err) {      // (the list stays in WS_IDS: dev_unresolved_hits probes it)
+    HIPCHK(hipSetDevice(d->ordinal));
+    ids.clear();
+    u32* buf = nullptr; u64 cnt = 0; { int rc = collect_unresolved(d, &buf, &cnt, err); if (rc) return rc; }
+    ids.resize(cnt); if (cnt) HIPCHK(hipMemcpy(ids.data(), buf, cnt * sizeof(u32), hipMemcpyDeviceToHost));
+    std::sort(ids.begin(), ids.end());
+    return 0;
+}
 int dev_unresolved_hits(Device* d, std::vector<Hit>& hits, uint64_t* n_unresolved, std::string& err, std::vector<uint32_t>* ids_out) {
     HIPCHK(hipSetDevice(d->ordinal));
     HIPCHK(hipEventRecord(d->ev[0], d->stream));
@@ -1202,12 +1259,12 @@ int dev_unresolved_hits(Device* d, std::vector<Hit>& hits, uint64_t* n_unresolve
     u64 cap = std::max<u64>(1 << 16, nun * 80);
     for (int attempt = 0; attempt < 4; attempt++) {
         WS(dh, Hit, WS_HITS, cap);
-        HIPCHK(hipMemsetAsync(d->d_counters + 4, 0, sizeof(u64), d->stream));
+        HIPCHK(hipMemsetAsync(d->d_counters + CTR_HIT_CURSOR, 0, sizeof(u64), d->stream));
         ProbeArgs A = base_args(d); A.hits = dh; A.hits_cap = cap;
         { WS(idbuf, u32, WS_IDS, nun); WS(pbuf, u32, WS_SLOW, nun + 1);      // the list dev_unresolved_ids left on the device, as positions: only these reads are probed
           hipLaunchKernelGGL(k_ids_to_pos, dim3(grid_for(nun, 256)), dim3(256), 0, d->stream, idbuf, (u64)nun, d->posOf, pbuf); A.ids = pbuf; A.n_ids = nun; }
         rc = launch_probe<1>(d, A, err); if (rc) return rc;
-        u64 nh = 0; rc = read_counters(d, 4, 1, &nh, err); if (rc) return rc;
+        u64 nh = 0; rc = read_counters(d, CTR_HIT_CURSOR, 1, &nh, err); if (rc) return rc;
         if (nh <= cap) {
             hits.resize(nh);
             if (nh) HIPCHK(hipMemcpy(hits.data(), dh, nh * sizeof(Hit), hipMemcpyDeviceToHost));
@@ -1220,14 +1277,14 @@ int dev_unresolved_hits(Device* d, std::vector<Hit>& hits, uint64_t* n_unresolve
     err = "hit buffer sizing failed"; return SAGE2OV_ERR_INTERNAL;
 }
 
-// The hit-list pass over A's range or id list (A.hits, A.hitcount set; d_counters[4..6] preset by the caller): the fast kernel's hit-list form, then the exact
-// sequential kernel, appending behind, for the reads it handed over into A.slow -- or for all of A when the layout has no such form.  c[0..2] = d_counters[4..6]
+// The hit-list pass over A's range or id list (A.hits, A.hitcount set; CTR_HIT_CURSOR, CTR_HIT_REAL and CTR_HANDED[0] preset by the caller): the fast kernel's hit-list form, then the exact
+// sequential kernel, appending behind, for the reads it handed over into A.slow -- or for all of A when the layout has no such form.  c[0..2] = those three
 // after the fast kernel (its cursor in the hit buffer, its count of real hits, the reads it handed over; the caller's preset when there was no fast kernel),
-// *used = d_counters[4] at the end.  A cursor beyond A.hits_cap: the sequential kernel does not run, *used = c[0].
+// *used = the cursor at the end.  A cursor beyond A.hits_cap: the sequential kernel does not run, *used = c[0].
 static int hit_list_pass(Device* d, ProbeArgs& A, unsigned blocks, u64 c[3], u64* used, std::string& err) {
     if (launch_form(d, Form::Hits, A, blocks)) {
         HIPCHK(hipGetLastError());
-        { int rc = read_counters(d, 4, 3, c, err); if (rc) return rc; }
+        { int rc = read_counters(d, CTR_HIT_CURSOR, 3, c, err); if (rc) return rc; }
         if (c[0] > A.hits_cap) { *used = c[0]; return 0; }                        // some chunk did not fit
         if (c[2]) {
             ProbeArgs B = base_args(d); B.hits = A.hits; B.hits_cap = A.hits_cap; B.hitcount = A.hitcount; B.ids = A.slow; B.n_ids = c[2];
@@ -1237,267 +1294,304 @@ static int hit_list_pass(Device* d, ProbeArgs& A, unsigned blocks, u64 c[3], u64
         A.slow = nullptr;
         int rc = launch_probe<1>(d, A, err); if (rc) return rc;
     }
-    return read_counters(d, 4, 1, used, err);
+    return read_counters(d, CTR_HIT_CURSOR, 1, used, err);
 }
-// Reduce phase on the device (see k_ra_mark).  *done = 0 when the preconditions do not hold (long buckets, too few
-// unresolved reads to be worth it, a list longer than RA_CAP, 32-bit offsets exhausted): the caller then runs the
-// serial replay on the host; nothing but the idempotent 0x80 flags has been changed in that case.
-// The serial part of the reduce phase when some bucket is long (economyGraph.cpp:513-564): the order in which the unresolved reads are
-// explored.  plist[offp[w] .. offp[w+1]) = potential list of the w-th unresolved read, sorted like the reference sorts a list when the
-// read is explored (:853-871); an entry is `to | twin << 31`.  An own hit is in the read's list iff the target was still unexplored
-// when the read was explored, a twin iff its source had been explored before; candidates of the reciprocal pass (hasCand) are always
-// there but their far ends are never explorable.  Returns rank[id] (1-based exploration order; 0: not an unresolved read).
-// Both inner loops look for RARE entries (a still unexplored target; an explored but unmarked neighbour) among ~100 per list, so they are
-// written as "find the next entry that satisfies the test": eight entries per step with AVX2 gathers of rank[] where the host has them
-// (the walk is instruction-bound: 2 ns per entry visit with a scalar loop, 1.9 G visits per 10 M reads).  After every event the search
-// restarts behind it with fresh values, so a batch never acts on state that an event of the same batch has changed.
-// Tables of the walk live on 2 MB pages where the kernel hands them out (transparent huge pages, madvise mode): the walk's accesses are
-// spread over ~2 GB (lists) + 170 MB (tables), far beyond what a TLB of 4 KB pages covers.
-struct HugeBuf {
-    void* p = nullptr; size_t bytes = 0; bool registered = false;
-    void* get(size_t n) {
-        bytes = (std::max<size_t>(n, 1) + (2u << 20) - 1) & ~(size_t)((2u << 20) - 1);
-        p = mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
-        if (p == MAP_FAILED) { p = nullptr; return nullptr; }
-        madvise(p, bytes, MADV_HUGEPAGE);
-        return p;
-    }
-    ~HugeBuf() { if (p) { if (registered) hipHostUnregister(p); munmap(p, bytes); } }
-};
-struct RrStaging {                                       // slice s of a call reuses buffer s of the previous call when it is large enough
-    std::vector<std::unique_ptr<HugeBuf>> bufs; size_t next = 0;
-    u32* get(size_t n) {
-        const size_t want = (std::max<size_t>(n, 16) + 16) * sizeof(u32);
-        if (next < bufs.size() && bufs[next]->p && bufs[next]->bytes >= want) return (u32*)bufs[next++]->p;
-        std::unique_ptr<HugeBuf> b(new HugeBuf()); u32* p = (u32*)b->get(want + want / 8); if (!p) return nullptr;
-        memset(p, 0, b->bytes);                                  // (touch: the pages exist before they are pinned)
-        if (hipHostRegister(p, b->bytes, hipHostRegisterDefault) == hipSuccess) b->registered = true; else (void)hipGetLastError();
-        if (next < bufs.size()) bufs[next] = std::move(b); else bufs.push_back(std::move(b));
-        return (u32*)bufs[next++]->p;
-    }
-};
-static void rr_staging_release(Device* d) { if (d->rrStaging) { delete (RrStaging*)d->rrStaging; d->rrStaging = nullptr; } }
-// (the exploration walk itself -- explore_order, host code with AVX2 gathers where the host has them -- lives in sage2ov_walk.cpp since round 4: it never was device code)
+// Reduce phase on the device (see k_ra_mark): dev_reduce_device is the sequence of the stages below.  *done = 0 when the preconditions do not hold (too few
+// unresolved reads to be worth it, a list longer than RA_CAP, 32-bit offsets exhausted): the caller then runs the serial replay on the host; nothing but the
+// idempotent 0x80 flags has been changed in that case.  A stage says so by returning REDUCE_REPLAY.
+// When some bucket is long (ranked: one-sided discovery, economyGraph.cpp:513-564) the order in which the unresolved reads are explored decides which edges
+// exist: the potential lists are built here, the order is found by the host's walk (explore_order, sage2ov_walk.cpp) and comes back as ranks.
 // Multi-rank contexts (shareRank / shareWorld): hit lists, adjacency and -- with long buckets -- the exploration order are computed for ALL unresolved
 // reads on every rank (they are read by everybody's marks), but the marks (:643-707), the removals and the re-emission of the surviving edges run for this
 // rank's share of the unresolved reads only (a contiguous part of the list): d->n_cand grows by this rank's survivors, *removed counts this rank's
 // removals; the caller all-gathers the survivor buckets (dev_export_survivors / dev_set_survivors) and sums the counters.
-int dev_reduce_device(Device* d, uint64_t min_unresolved, uint64_t* n_unresolved, uint64_t* n_hits, uint64_t* inserted, uint64_t* removed, int* done, std::string& err,
-                      uint32_t shareRank, uint32_t shareWorld) {
-    HIPCHK(hipSetDevice(d->ordinal));
-    *done = 0; *inserted = 0; *removed = 0; *n_hits = 0;
-    const u64 N = d->N;
-    HIPCHK(hipEventRecord(d->ev[0], d->stream));
-    u32* ids = nullptr; u64 nun = 0;
-    { int rc = collect_unresolved(d, &ids, &nun, err); if (rc) return rc; }
-    *n_unresolved = nun;
-    if (nun == 0) { *done = 1; return 0; }
-    if (nun < min_unresolved) return 0;
-    const bool ranked = d->n_long != 0;                                          // one-sided discovery: the exploration order decides which edges exist
-    const bool timing = d->opt.get("SAGE2OV_TIMING") != nullptr; auto tp = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) { if (!timing) return; hipStreamSynchronize(d->stream); auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[reduce/device] %-30s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(t - tp).count()); tp = t; };
-    // directional hits of the unresolved reads, device resident: the fast kernel in its hit-list form (locality order, minimiser
-    // groups), the sequential kernel for the few reads it hands over (> 128 candidates, ambiguous tags) and for the 16-word layout
-    Hit* dh = nullptr; u64 nh = 0, nslots = 0;
-    WS(hitcount, u32, WS_RA_CUR, N + 2);
-    u32* locDev = nullptr;                                                       // ranked form: read id -> 1-based position in the locality order
-    {
-        const u32* order = d->idOf + 1;                                            // ids in locality order (positions 1..N)
-        if (ranked) locDev = d->posOf;
-        if (ranked || shareWorld > 1) {                                            // (several ranks cut the SAME list into shares: it must not depend on the order of atomics)
-            // the unresolved reads listed in LOCALITY order (a stable compaction of `order`): their potential lists are then laid out in that
-            // order too, so the lists the host's walk visits one after the other sit next to each other in memory (cache lines, TLB)
-            WS(flg, u32, WS_RR_IN, N + 2); WS(fpos, u32, WS_RR_WIDX, N + 2);
-            hipLaunchKernelGGL(k_rr_unres_flag, dim3(grid_for(N, 256)), dim3(256), 0, d->stream, order, (u64)N, d->status, flg);
-            u64 cnt2 = 0; { int rc = scan_u32(d, flg, N, fpos, &cnt2, err); if (rc) return rc; }
-            if (cnt2 != nun) { err = "unresolved read count changed"; return SAGE2OV_ERR_INTERNAL; }
-            hipLaunchKernelGGL(k_rr_unres_pick, dim3(grid_for(N, 256)), dim3(256), 0, d->stream, order, (u64)N, flg, fpos, ids);
-        }
-        WS(slow, u32, WS_SLOW, N + 1);
-        const unsigned blocks = (unsigned)std::min<u64>((N + FAST_CHUNK - 1) / FAST_CHUNK, 256ull * 16);
-        u64 cap = std::max<u64>(1 << 16, nun * 80) + (u64)blocks * FAST_WPB * HITS_CHUNK; bool ok = false;
-        if (d->opt.get("SAGE2OV_TEST_SMALL_BUFFERS")) cap = 8192;                      // tests: start far too small, the sizing loop must recover
-        // The initial pass may have written every read's hits out already (dev_probe, noisy data): drop the ones with a resolved end, in place, and
-        // run the hit-list kernel only for the unresolved reads that pass did not cover (its sample, hand-overs).  Any shortage of room: the
-        // ordinary way below, from scratch.
-        if (d->pre.valid && !d->opt.get("SAGE2OV_TEST_SMALL_BUFFERS")) {
-            d->pre.valid = false;                                                     // (consumed: the filter works in place)
-            dh = d->pre.hits; const u64 pcap = d->pre.cap; u64 used = d->pre.used;
-            WS(noneList, u32, WS_PRE_NONE, N + 2);
-            HIPCHK(hipMemsetAsync(d->d_counters + 22, 0, 2 * sizeof(u64), d->stream));
-            hipLaunchKernelGGL(k_hits_filter, dim3((unsigned)std::min<u64>((N + 3) / 4, 256ull * 64)), dim3(256), 0, d->stream, dh, d->pre.base, d->status, d->statusP, d->idOf, d->posOf, (u64)N, hitcount, noneList, d->d_counters + 22);
-            u64 fc[2] = {0, 0}; { int rc = read_counters(d, 22, 2, fc, err); if (rc) return rc; }
-            HIPCHK(hipGetLastError());
-            nh = fc[0]; ok = true;
-            if (fc[1]) {                                                              // unresolved reads without written hits: the hit-list pass over their positions, appending
-                u64 c3[3] = {used, 0, 0}; HIPCHK(hipMemcpyAsync(d->d_counters + 4, c3, sizeof c3, hipMemcpyHostToDevice, d->stream));
-                ProbeArgs A = base_args(d); A.ids = noneList; A.n_ids = fc[1]; A.hits = dh; A.hits_cap = pcap; A.hitcount = hitcount; A.slow = slow; A.slow_cap = N + 1;
-                const unsigned nb = plan_fast_grid(d->opt, A, fc[1], true);
-                u64 used2 = 0; { int rc = hit_list_pass(d, A, nb, c3, &used2, err); if (rc) return rc; }
-                if (used2 > pcap) ok = false; else { nh += c3[1] + (used2 - std::max(c3[0], used)); used = used2; }
-            }
-            if (ok) nslots = used;
-        }
-        for (int attempt = 0; attempt < 4 && !ok; attempt++) {
-            WS(hb, Hit, WS_HITS, cap); dh = hb;
-            HIPCHK(hipMemsetAsync(d->d_counters + 4, 0, 3 * sizeof(u64), d->stream));
-            HIPCHK(hipMemsetAsync(hitcount, 0, (N + 2) * sizeof(u32), d->stream));
-            ProbeArgs A = base_args(d); A.lo = 1; A.hi = N + 1; A.hits = dh; A.hits_cap = cap; A.hitcount = hitcount;
-            A.slow = slow; A.slow_cap = N + 1;                                       // (all positions; the kernel skips what is not status 0)
-            u64 c3[3] = {0, 0, 0}, used = 0;
-            { int rc = hit_list_pass(d, A, blocks, c3, &used, err); if (rc) return rc; }
-            if (used > cap) { cap = used + used / 8 + 1024; continue; }                  // some chunk or the appended hits did not fit: everything again
-            nslots = used; nh = c3[1] + (used - c3[0]); ok = true;                           // real hits: fast kernel's count + what the sequential kernel appended
-        }
-        if (!ok) { err = "hit buffer sizing failed"; return SAGE2OV_ERR_INTERNAL; }
+constexpr int REDUCE_REPLAY = 1;
+struct ReduceRun {                                                                   // one call: the unresolved reads, their hit lists, the final lists -- what one stage leaves for the next
+    u32* ids = nullptr; u64 nun = 0;                                                 // the unresolved reads (WS_IDS), all ranks' shares
+    u64 wlo = 0, whi = 0; u32 shareWorld = 1;                                        // this rank's share: entries [wlo, whi) of ids (any contiguous cut is exact: a read's marks depend on the lists only)
+    bool ranked = false;                                                             // some bucket is long: the exploration order decides which edges exist
+    Hit* dh = nullptr; u64 nh = 0, nslots = 0; u32* hitcount = nullptr;              // hit lists: nh real hits in slots [0, nslots) of dh; hits per read position
+    u32 *deg = nullptr, *offs = nullptr, *cur = nullptr, *rankDev = nullptr; u64* ent = nullptr; u32* ent32 = nullptr; uint8_t* rm = nullptr; u64 present = 0;      // final lists
+    u32 *svn = nullptr, *svoff = nullptr; u64 removed = 0;                           // marks: survivors per read of the share, this rank's removals
+    bool timing = false; std::chrono::steady_clock::time_point tp;
+    void lap(Device* d, const char* what) { if (!timing) return; hipStreamSynchronize(d->stream); auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[reduce/device] %-30s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(t - tp).count()); tp = t; }
+    // (the grid of marks and emission: a wave per read, blocks walk the list round-robin; blocks per CU -> reduce phase at configs[1] + 0.1 % errors: 16 -> 69.5 ms, 64 -> 66.0, 256 -> 65.2, 1024 -> 65.2: the tail again)
+    unsigned share_grid() const { return (unsigned)std::max<u64>(1, std::min<u64>((whi - wlo + 3) / 4, 256ull * 256)); }
+};
+// Hit lists: directional hits of the unresolved reads, device resident: the fast kernel in its hit-list form (locality order, minimiser
+// groups), the sequential kernel for the few reads it hands over (> 128 candidates, ambiguous tags) and for the 16-word layout
+static int reduce_hit_lists(Device* d, ReduceRun& R, std::string& err) {
+    const u64 N = d->N, nun = R.nun;
+    WS(hitcount, u32, WS_RA_CUR, N + 2); R.hitcount = hitcount;                    // (what the probe pass counted when it wrote the hits out; else zeroed below)
+    const u32* order = d->idOf + 1;                                                // ids in locality order (positions 1..N)
+    if (R.ranked || R.shareWorld > 1) {                                            // (several ranks cut the SAME list into shares: it must not depend on the order of atomics)
+        // the unresolved reads listed in LOCALITY order (a stable compaction of `order`): their potential lists are then laid out in that
+        // order too, so the lists the host's walk visits one after the other sit next to each other in memory (cache lines, TLB)
+        WS(flg, u32, WS_RR_IN, N + 2); WS(fpos, u32, WS_RR_WIDX, N + 2);
+        hipLaunchKernelGGL(k_rr_unres_flag, dim3(grid_for(N, 256)), dim3(256), 0, d->stream, order, (u64)N, d->status, flg);
+        u64 cnt2 = 0; { int rc = scan_u32(d, flg, N, fpos, &cnt2, err); if (rc) return rc; }
+        if (cnt2 != nun) { err = "unresolved read count changed"; return SAGE2OV_ERR_INTERNAL; }
+        hipLaunchKernelGGL(k_rr_unres_pick, dim3(grid_for(N, 256)), dim3(256), 0, d->stream, order, (u64)N, flg, fpos, R.ids);
     }
-    *n_hits = nh;
-    lap("hit lists");
-    const u64 nc = d->n_cand;
-    WS(deg, u32, WS_RA_DEG, N + 2); WS(offs, u32, WS_RA_OFF, N + 2); WS(cur, u32, WS_CURSOR, N + 2);
+    WS(slow, u32, WS_SLOW, N + 1);
+    const unsigned blocks = (unsigned)std::min<u64>((N + FAST_CHUNK - 1) / FAST_CHUNK, 256ull * 16);
+    u64 cap = std::max<u64>(1 << 16, nun * 80) + (u64)blocks * FAST_WPB * HITS_CHUNK; bool ok = false;
+    if (d->opt.get("SAGE2OV_TEST_SMALL_BUFFERS")) cap = 8192;                      // tests: start far too small, the sizing loop must recover
+    // The initial pass may have written every read's hits out already (dev_probe, noisy data): drop the ones with a resolved end, in place, and
+    // run the hit-list kernel only for the unresolved reads that pass did not cover (its sample, hand-overs).  Any shortage of room: the
+    // ordinary way below, from scratch.
+    if (d->pre.valid && !d->opt.get("SAGE2OV_TEST_SMALL_BUFFERS")) {
+        d->pre.valid = false;                                                     // (consumed: the filter works in place)
+        R.dh = d->pre.hits; const u64 pcap = d->pre.cap; u64 used = d->pre.used;
+        WS(noneList, u32, WS_PRE_NONE, N + 2);
+        HIPCHK(hipMemsetAsync(d->d_counters + CTR_FILTER, 0, 2 * sizeof(u64), d->stream));
+        hipLaunchKernelGGL(k_hits_filter, dim3((unsigned)std::min<u64>((N + 3) / 4, 256ull * 64)), dim3(256), 0, d->stream, R.dh, d->pre.base, d->status, d->statusP, d->idOf, d->posOf, (u64)N, hitcount, noneList, d->d_counters + CTR_FILTER);
+        u64 fc[2] = {0, 0}; { int rc = read_counters(d, CTR_FILTER, 2, fc, err); if (rc) return rc; }
+        HIPCHK(hipGetLastError());
+        R.nh = fc[0]; ok = true;
+        if (fc[1]) {                                                              // unresolved reads without written hits: the hit-list pass over their positions, appending
+            u64 c3[3] = {used, 0, 0}; HIPCHK(hipMemcpyAsync(d->d_counters + CTR_HIT_CURSOR, c3, sizeof c3, hipMemcpyHostToDevice, d->stream));      // (cursor, CTR_HIT_REAL, CTR_HANDED[0])
+            ProbeArgs A = base_args(d); A.ids = noneList; A.n_ids = fc[1]; A.hits = R.dh; A.hits_cap = pcap; A.hitcount = hitcount; A.slow = slow; A.slow_cap = N + 1;
+            const unsigned nb = plan_fast_grid(d->opt, A, fc[1], true);
+            u64 used2 = 0; { int rc = hit_list_pass(d, A, nb, c3, &used2, err); if (rc) return rc; }
+            if (used2 > pcap) ok = false; else { R.nh += c3[1] + (used2 - std::max(c3[0], used)); used = used2; }
+        }
+        if (ok) R.nslots = used;
+    }
+    for (int attempt = 0; attempt < 4 && !ok; attempt++) {
+        WS(hb, Hit, WS_HITS, cap); R.dh = hb;
+        HIPCHK(hipMemsetAsync(d->d_counters + CTR_HIT_CURSOR, 0, 3 * sizeof(u64), d->stream));      // (cursor, CTR_HIT_REAL, CTR_HANDED[0])
+        HIPCHK(hipMemsetAsync(hitcount, 0, (N + 2) * sizeof(u32), d->stream));
+        ProbeArgs A = base_args(d); A.lo = 1; A.hi = N + 1; A.hits = R.dh; A.hits_cap = cap; A.hitcount = hitcount;
+        A.slow = slow; A.slow_cap = N + 1;                                       // (all positions; the kernel skips what is not status 0)
+        u64 c3[3] = {0, 0, 0}, used = 0;
+        { int rc = hit_list_pass(d, A, blocks, c3, &used, err); if (rc) return rc; }
+        if (used > cap) { cap = used + used / 8 + 1024; continue; }                  // some chunk or the appended hits did not fit: everything again
+        R.nslots = used; R.nh = c3[1] + (used - c3[0]); ok = true;                       // real hits: fast kernel's count + what the sequential kernel appended
+    }
+    if (!ok) { err = "hit buffer sizing failed"; return SAGE2OV_ERR_INTERNAL; }
+    return 0;
+}
+// Final lists, first half: their buffers, and the degrees that the candidates of the reciprocal pass contribute (the ranked order needs these alone)
+static int reduce_cand_degrees(Device* d, ReduceRun& R, std::string& err) {
+    const u64 N = d->N, nc = d->n_cand;
+    WS(deg, u32, WS_RA_DEG, N + 2); WS(offs, u32, WS_RA_OFF, N + 2); WS(cur, u32, WS_CURSOR, N + 2); R.deg = deg; R.offs = offs; R.cur = cur;
     HIPCHK(hipMemsetAsync(deg, 0, (N + 2) * sizeof(u32), d->stream)); HIPCHK(hipMemsetAsync(cur, 0, (N + 2) * sizeof(u32), d->stream));
     if (nc) hipLaunchKernelGGL(k_ra_degree_c, dim3(grid_for(nc, 256)), dim3(256), 0, d->stream, d->cand, (u64)nc, d->status, deg);
-    u32* rankDev = nullptr; u64 present = 0;
-    HIPCHK(hipMemsetAsync(d->d_counters + 8, 0, 4 * sizeof(u64), d->stream));
-    if (ranked) {
-        // potential lists (own hits + twins of incoming hits), sorted and merged on the device, slice by slice (a slice stays below 2^30
-        // entries); exploration order on the host; ranks back
-        WS(incount, u32, WS_RR_IN, N + 2); WS(widx, u32, WS_RR_WIDX, N + 2); WS(degp, u32, WS_RR_DEGP, nun + 2); WS(pcur, u32, WS_RR_CUR, N + 2);
-        HIPCHK(hipMemsetAsync(incount, 0, (N + 2) * sizeof(u32), d->stream)); HIPCHK(hipMemsetAsync(pcur, 0, (N + 2) * sizeof(u32), d->stream)); HIPCHK(hipMemsetAsync(widx, 0, (N + 2) * sizeof(u32), d->stream));
-        hipLaunchKernelGGL(k_rr_widx, dim3(grid_for(nun, 256)), dim3(256), 0, d->stream, ids, (u64)nun, widx);
-        if (nslots) hipLaunchKernelGGL(k_rr_incount, dim3(grid_for(nslots, 256)), dim3(256), 0, d->stream, dh, (u64)nslots, incount);
-        hipLaunchKernelGGL(k_rr_degp, dim3(grid_for(nun, 256)), dim3(256), 0, d->stream, ids, (u64)nun, hitcount, incount, degp);
-        std::vector<u32> hIds(nun), hLen(nun, 0), hDeg(N + 2), hDegp(nun), hLoc(N + 2); std::vector<uint8_t> hasCand(nun, 0); std::vector<const u32*> listPtr(nun, nullptr);
-        HIPCHK(hipMemcpyAsync(hLoc.data(), locDev, (N + 2) * sizeof(u32), hipMemcpyDeviceToHost, d->stream));
-        HIPCHK(hipMemcpyAsync(hDegp.data(), degp, nun * sizeof(u32), hipMemcpyDeviceToHost, d->stream));
-        HIPCHK(hipMemcpyAsync(hIds.data(), ids, nun * sizeof(u32), hipMemcpyDeviceToHost, d->stream));
-        HIPCHK(hipMemcpyAsync(hDeg.data(), deg, (N + 2) * sizeof(u32), hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));   // (deg so far: candidate entries only)
-        for (u64 w = 0; w < nun; w++) hasCand[w] = hDeg[hIds[w]] != 0;
-        if (timing) { u64 c512 = 0, c1k = 0, c4k = 0; u32 mx = 0; for (u32 v : hDegp) { c512 += v > 512; c1k += v > 1024; c4k += v > 4096; mx = std::max(mx, v); }
-            fprintf(stderr, "[reduce/device] potential lists: %llu reads, > 512: %llu, > 1024: %llu, > 4096: %llu, longest %u\n", (unsigned long long)nun, (unsigned long long)c512, (unsigned long long)c1k, (unsigned long long)c4k, mx); }
-        // gigabytes at 10 M reads: 2 MB pages for the host's walk, registered so that the download is a DMA; kept in the context from step to step (allocating, touching
-        // and registering 1.7 GB took 100 ms of every call)
-        if (!d->rrStaging) d->rrStaging = new RrStaging();
-        RrStaging& staging = *(RrStaging*)d->rrStaging; staging.next = 0;
-        std::vector<std::vector<u32>> heavyLists;                                 // lists beyond the device sort (reads that thousands of others see): sorted and merged on the host
-        u64 sliceEntries = 1ull << 30; if (const char* ev = d->opt.get("SAGE2OV_TEST_RANK_SLICE")) sliceEntries = std::max<u64>(1024, strtoull(ev, nullptr, 10));
-        WS(lenp, u32, WS_RR_LEN, nun + 2);
-        for (u64 w0 = 0; w0 < nun;) {
-            u64 w1 = w0, tot0 = 0; while (w1 < nun && (w1 == w0 || tot0 + hDegp[w1] <= sliceEntries)) tot0 += hDegp[w1++];
-            if (tot0 >= (1ull << 32) - 64) return 0;                              // one read with 2^32 potential neighbours: not this path
-            const u64 nw = w1 - w0;
-            WS(offp, u32, WS_RR_OFFP, nw + 2); WS(coff, u32, WS_RR_COFF, nw + 2);
-            u64 totp = 0; { int rc = scan_u32(d, degp + w0, nw, offp, &totp, err); if (rc) return rc; }
-            WS(entp, u64, WS_RR_ENTP, totp + 64); WS(outp, u32, WS_RR_OUTP, totp + 64);
-            HIPCHK(hipMemsetAsync(entp, 0, (totp + 64) * sizeof(u64), d->stream));
-            if (nslots) hipLaunchKernelGGL(k_rr_fillp, dim3(grid_for(nslots, 256)), dim3(256), 0, d->stream, dh, (u64)nslots, d->reads, d->S, d->uniL, widx, (u32)w0, (u32)w1, offp, hitcount, pcur, entp);
-            hipLaunchKernelGGL(k_rr_sortp, dim3((unsigned)std::min<u64>((nw + 3) / 4, 256ull * 16)), dim3(256), 0, d->stream, (u64)nw, offp, degp + w0, entp, outp, lenp + w0, d->d_counters + 8 + 3);
-            u64 totc = 0; { int rc = scan_u32(d, lenp + w0, nw, coff, &totc, err); if (rc) return rc; }
-            WS(outc, u32, WS_RR_OUTC, totc + 64);
-            hipLaunchKernelGGL(k_rr_compact, dim3((unsigned)std::min<u64>((nw + 3) / 4, 256ull * 16)), dim3(256), 0, d->stream, (u64)nw, offp, lenp + w0, coff, outp, locDev, outc);
-            lap("  potential lists: kernels");
-            u32* hbuf = staging.get(totc); if (!hbuf) { err = "host staging buffer allocation failed"; return SAGE2OV_ERR_NOMEM; }
-            lap("  potential lists: staging buffer (2 MB pages, touched, registered)");
-            HIPCHK(hipMemcpyAsync(hLen.data() + w0, lenp + w0, nw * sizeof(u32), hipMemcpyDeviceToHost, d->stream));
-            if (totc) HIPCHK(hipMemcpyAsync(hbuf, outc, totc * sizeof(u32), hipMemcpyDeviceToHost, d->stream));
-            HIPCHK(hipStreamSynchronize(d->stream));
-            u64 at = 0, rel = 0; std::vector<u64> seg;
-            for (u64 w = w0; w < w1; w++) {
-                const u32 n = hDegp[w];
-                if (n <= (u32)RR_CAP) { listPtr[w] = hbuf + at; at += hLen[w]; }
-                else {                                                            // (its device length is 0)
-                    seg.resize(n); HIPCHK(hipMemcpy(seg.data(), entp + rel, (size_t)n * sizeof(u64), hipMemcpyDeviceToHost));
-                    std::sort(seg.begin(), seg.end(), std::greater<u64>());
-                    heavyLists.emplace_back(); std::vector<u32>& hl = heavyLists.back(); hl.reserve(n);
-                    for (u32 x = 0; x < n; x++) {
-                        const u64 kx = seg[x]; if (kx == 0) break;
-                        const bool twin = kx & 1ull;
-                        if (!twin && x > 0 && (seg[x - 1] & 1ull) && (seg[x - 1] >> 1) == (kx >> 1)) continue;      // the own hit behind its twin: merged
-                        const bool sym = twin && x + 1 < n && seg[x + 1] != 0 && !(seg[x + 1] & 1ull) && (seg[x + 1] >> 1) == (kx >> 1);
-                        hl.push_back(hLoc[(u32)(kx >> 11) & 0x3FFFFFFFu] | ((sym ? 0u : (twin ? 2u : 1u)) << 30));
-                    }
-                    hLen[w] = (u32)hl.size();
-                }
-                rel += n;
+    HIPCHK(hipMemsetAsync(d->d_counters + CTR_RANKED, 0, 4 * sizeof(u64), d->stream));
+    return 0;
+}
+// Ranked order.  plist[offp[w] .. offp[w+1]) = potential list of the w-th unresolved read (own hits + twins of incoming hits), sorted like the reference sorts
+// a list when the read is explored (:853-871).  An own hit is in the read's list iff the target was still unexplored when the read was explored, a twin iff
+// its source had been explored before; candidates of the reciprocal pass (hasCand) are always there but their far ends are never explorable.
+struct RankLists {                                                                   // the potential lists as the host's walk reads them, and the device arrays the slices share
+    std::vector<u32> hLen, hDegp, hLoc; std::vector<uint8_t> hasCand; std::vector<const u32*> listPtr;
+    std::vector<std::vector<u32>> heavyLists;                                        // lists beyond the device sort (reads that thousands of others see): sorted and merged on the host
+    u32 *degp = nullptr, *lenp = nullptr, *widx = nullptr, *pcur = nullptr;
+};
+// degrees of the potential lists, on the device and on the host, with the tables the walk and the host merge need (position of an id, reads with candidates)
+static int rank_degrees(Device* d, ReduceRun& R, RankLists& L, std::string& err) {
+    const u64 N = d->N, nun = R.nun;
+    // (WS_RR_IN, WS_RR_WIDX: instead of the flags and positions of reduce_hit_lists' compaction, which are used up)
+    WS(incount, u32, WS_RR_IN, N + 2); WS(widx, u32, WS_RR_WIDX, N + 2); WS(degp, u32, WS_RR_DEGP, nun + 2); WS(pcur, u32, WS_RR_CUR, N + 2);
+    L.degp = degp; L.widx = widx; L.pcur = pcur;
+    HIPCHK(hipMemsetAsync(incount, 0, (N + 2) * sizeof(u32), d->stream)); HIPCHK(hipMemsetAsync(pcur, 0, (N + 2) * sizeof(u32), d->stream)); HIPCHK(hipMemsetAsync(widx, 0, (N + 2) * sizeof(u32), d->stream));
+    hipLaunchKernelGGL(k_rr_widx, dim3(grid_for(nun, 256)), dim3(256), 0, d->stream, R.ids, (u64)nun, widx);
+    if (R.nslots) hipLaunchKernelGGL(k_rr_incount, dim3(grid_for(R.nslots, 256)), dim3(256), 0, d->stream, R.dh, (u64)R.nslots, incount);
+    hipLaunchKernelGGL(k_rr_degp, dim3(grid_for(nun, 256)), dim3(256), 0, d->stream, R.ids, (u64)nun, R.hitcount, incount, degp);
+    std::vector<u32> hIds(nun), hDeg(N + 2);
+    L.hLen.assign(nun, 0); L.hDegp.resize(nun); L.hLoc.resize(N + 2); L.hasCand.assign(nun, 0); L.listPtr.assign(nun, nullptr);
+    HIPCHK(hipMemcpyAsync(L.hLoc.data(), d->posOf, (N + 2) * sizeof(u32), hipMemcpyDeviceToHost, d->stream));      // read id -> 1-based position in the locality order
+    HIPCHK(hipMemcpyAsync(L.hDegp.data(), degp, nun * sizeof(u32), hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipMemcpyAsync(hIds.data(), R.ids, nun * sizeof(u32), hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipMemcpyAsync(hDeg.data(), R.deg, (N + 2) * sizeof(u32), hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));   // (deg so far: candidate entries only)
+    for (u64 w = 0; w < nun; w++) L.hasCand[w] = hDeg[hIds[w]] != 0;
+    if (R.timing) { u64 c512 = 0, c1k = 0, c4k = 0; u32 mx = 0; for (u32 v : L.hDegp) { c512 += v > 512; c1k += v > 1024; c4k += v > 4096; mx = std::max(mx, v); }
+        fprintf(stderr, "[reduce/device] potential lists: %llu reads, > 512: %llu, > 1024: %llu, > 4096: %llu, longest %u\n", (unsigned long long)nun, (unsigned long long)c512, (unsigned long long)c1k, (unsigned long long)c4k, mx); }
+    return 0;
+}
+// one slice of potential lists, those of the unresolved reads [w0, w1): scan, fill, sort and compact on the device, download into a staging buffer; the lists
+// over RR_CAP (their device length is 0) are fetched unsorted and sorted and merged here
+static int rank_slice(Device* d, ReduceRun& R, RankLists& L, RrStaging& staging, u64 w0, u64 w1, std::string& err) {
+    const u64 nw = w1 - w0, nslots = R.nslots; u32* const degp = L.degp; u32* const lenp = L.lenp;
+    WS(offp, u32, WS_RR_OFFP, nw + 2); WS(coff, u32, WS_RR_COFF, nw + 2);
+    u64 totp = 0; { int rc = scan_u32(d, degp + w0, nw, offp, &totp, err); if (rc) return rc; }
+    WS(entp, u64, WS_RR_ENTP, totp + 64); WS(outp, u32, WS_RR_OUTP, totp + 64);
+    HIPCHK(hipMemsetAsync(entp, 0, (totp + 64) * sizeof(u64), d->stream));
+    if (nslots) hipLaunchKernelGGL(k_rr_fillp, dim3(grid_for(nslots, 256)), dim3(256), 0, d->stream, R.dh, (u64)nslots, d->reads, d->S, d->uniL, L.widx, (u32)w0, (u32)w1, offp, R.hitcount, L.pcur, entp);
+    hipLaunchKernelGGL(k_rr_sortp, dim3((unsigned)std::min<u64>((nw + 3) / 4, 256ull * 16)), dim3(256), 0, d->stream, (u64)nw, offp, degp + w0, entp, outp, lenp + w0, d->d_counters + CTR_RANKED + 3);
+    u64 totc = 0; { int rc = scan_u32(d, lenp + w0, nw, coff, &totc, err); if (rc) return rc; }
+    WS(outc, u32, WS_RR_OUTC, totc + 64);
+    hipLaunchKernelGGL(k_rr_compact, dim3((unsigned)std::min<u64>((nw + 3) / 4, 256ull * 16)), dim3(256), 0, d->stream, (u64)nw, offp, lenp + w0, coff, outp, d->posOf, outc);
+    R.lap(d, "  potential lists: kernels");
+    u32* hbuf = staging.get(totc); if (!hbuf) { err = "host staging buffer allocation failed"; return SAGE2OV_ERR_NOMEM; }
+    R.lap(d, "  potential lists: staging buffer (2 MB pages, touched, registered)");
+    HIPCHK(hipMemcpyAsync(L.hLen.data() + w0, lenp + w0, nw * sizeof(u32), hipMemcpyDeviceToHost, d->stream));
+    if (totc) HIPCHK(hipMemcpyAsync(hbuf, outc, totc * sizeof(u32), hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    u64 at = 0, rel = 0; std::vector<u64> seg;
+    for (u64 w = w0; w < w1; w++) {
+        const u32 n = L.hDegp[w];
+        if (n <= (u32)RR_CAP) { L.listPtr[w] = hbuf + at; at += L.hLen[w]; }
+        else {
+            seg.resize(n); HIPCHK(hipMemcpy(seg.data(), entp + rel, (size_t)n * sizeof(u64), hipMemcpyDeviceToHost));
+            std::sort(seg.begin(), seg.end(), std::greater<u64>());
+            L.heavyLists.emplace_back(); std::vector<u32>& hl = L.heavyLists.back(); hl.reserve(n);
+            for (u32 x = 0; x < n; x++) {
+                const u64 kx = seg[x]; if (kx == 0) break;
+                const bool twin = kx & 1ull;
+                if (!twin && x > 0 && (seg[x - 1] & 1ull) && (seg[x - 1] >> 1) == (kx >> 1)) continue;      // the own hit behind its twin: merged
+                const bool sym = twin && x + 1 < n && seg[x + 1] != 0 && !(seg[x + 1] & 1ull) && (seg[x + 1] >> 1) == (kx >> 1);
+                hl.push_back(L.hLoc[(u32)(kx >> 11) & 0x3FFFFFFFu] | ((sym ? 0u : (twin ? 2u : 1u)) << 30));
             }
-            w0 = w1;
+            L.hLen[w] = (u32)hl.size();
         }
-        { size_t hx = 0; for (u64 w = 0; w < nun; w++) if (hDegp[w] > (u32)RR_CAP) listPtr[w] = heavyLists[hx++].data(); }      // (after the last push_back: the vectors no longer move)
-        lap("potential lists (build + sort + download)");
-        std::vector<u32> rankByPos, posOf(nun), startOrder(nun);
-        {   // positions of the unresolved reads in list order and in ascending id order (the walk's starts): two gathers and a compaction, on the device
-            WS(sflg, u32, WS_RR_IN, N + 2); WS(sfpos, u32, WS_RR_WIDX, N + 2); WS(sout, u32, WS_RR_CUR, N + 2); WS(pout, u32, WS_RR_DEGP, nun + 2);
-            hipLaunchKernelGGL(k_ids_to_pos, dim3(grid_for(nun, 256)), dim3(256), 0, d->stream, ids, (u64)nun, d->posOf, pout);
-            hipLaunchKernelGGL(k_rr_start_flag, dim3(grid_for(N, 256)), dim3(256), 0, d->stream, (u64)N, d->status, sflg);
-            u64 cnt3 = 0; { int rc = scan_u32(d, sflg, N, sfpos, &cnt3, err); if (rc) return rc; }
-            if (cnt3 != nun) { err = "unresolved read count changed"; return SAGE2OV_ERR_INTERNAL; }
-            hipLaunchKernelGGL(k_rr_start_pick, dim3(grid_for(N, 256)), dim3(256), 0, d->stream, (u64)N, sflg, sfpos, d->posOf, sout);
-            HIPCHK(hipMemcpyAsync(posOf.data(), pout, nun * sizeof(u32), hipMemcpyDeviceToHost, d->stream));
-            HIPCHK(hipMemcpyAsync(startOrder.data(), sout, nun * sizeof(u32), hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
-        }
-        lap("walk set-up (device + download)");
-        explore_order(d->opt, posOf, listPtr, hLen, hasCand, N, startOrder, rankByPos);
-        if (rankByPos.size() != N + 2) { err = "exploration walk: table allocation failed"; return SAGE2OV_ERR_NOMEM; }
-        lap("exploration order (host)");
-        { WS(rk, u32, WS_RR_RANK, N + 2); rankDev = rk; }
-        { WS(rl, u32, WS_RR_RANKL, N + 2);
-          HIPCHK(hipMemcpyAsync(rl, rankByPos.data(), (N + 2) * sizeof(u32), hipMemcpyHostToDevice, d->stream));
-          hipLaunchKernelGGL(k_rr_rank_by_id, dim3(grid_for(N + 2, 256)), dim3(256), 0, d->stream, rl, locDev, (u64)(N + 2), rankDev);
-          HIPCHK(hipStreamSynchronize(d->stream)); }
-        if (nslots) hipLaunchKernelGGL(k_rr_degree_h, dim3(grid_for(nslots, 256)), dim3(256), 0, d->stream, dh, (u64)nslots, rankDev, deg, d->d_counters + 8);
-    } else hipLaunchKernelGGL(k_ra_degree_h, dim3(grid_for(N + 1, 256)), dim3(256), 0, d->stream, hitcount, (u64)N, deg);
-    lap("  ranks to the device, degrees of the final lists");
+        rel += n;
+    }
+    return 0;
+}
+// the walk's set-up: positions of the unresolved reads in list order (posOf) and in ascending id order (startOrder, the walk's starts): two gathers and a
+// compaction, on the device
+static int rank_walk_setup(Device* d, ReduceRun& R, std::vector<u32>& posOf, std::vector<u32>& startOrder, std::string& err) {
+    const u64 N = d->N, nun = R.nun;
+    // (all four instead of what the slices used, which the host has by now: WS_RR_IN incount, WS_RR_WIDX widx, WS_RR_CUR the fill cursors, WS_RR_DEGP degp)
+    WS(sflg, u32, WS_RR_IN, N + 2); WS(sfpos, u32, WS_RR_WIDX, N + 2); WS(sout, u32, WS_RR_CUR, N + 2); WS(pout, u32, WS_RR_DEGP, nun + 2);
+    hipLaunchKernelGGL(k_ids_to_pos, dim3(grid_for(nun, 256)), dim3(256), 0, d->stream, R.ids, (u64)nun, d->posOf, pout);
+    hipLaunchKernelGGL(k_rr_start_flag, dim3(grid_for(N, 256)), dim3(256), 0, d->stream, (u64)N, d->status, sflg);
+    u64 cnt3 = 0; { int rc = scan_u32(d, sflg, N, sfpos, &cnt3, err); if (rc) return rc; }
+    if (cnt3 != nun) { err = "unresolved read count changed"; return SAGE2OV_ERR_INTERNAL; }
+    hipLaunchKernelGGL(k_rr_start_pick, dim3(grid_for(N, 256)), dim3(256), 0, d->stream, (u64)N, sflg, sfpos, d->posOf, sout);
+    posOf.resize(nun); startOrder.resize(nun);
+    HIPCHK(hipMemcpyAsync(posOf.data(), pout, nun * sizeof(u32), hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipMemcpyAsync(startOrder.data(), sout, nun * sizeof(u32), hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
+    return 0;
+}
+// the ranks back on the device, by read id (R.rankDev): 1-based exploration order, 0: not an unresolved read
+static int rank_upload(Device* d, ReduceRun& R, const std::vector<u32>& rankByPos, std::string& err) {
+    const u64 N = d->N;
+    { WS(rk, u32, WS_RR_RANK, N + 2); R.rankDev = rk; }
+    WS(rl, u32, WS_RR_RANKL, N + 2);
+    HIPCHK(hipMemcpyAsync(rl, rankByPos.data(), (N + 2) * sizeof(u32), hipMemcpyHostToDevice, d->stream));
+    hipLaunchKernelGGL(k_rr_rank_by_id, dim3(grid_for(N + 2, 256)), dim3(256), 0, d->stream, rl, d->posOf, (u64)(N + 2), R.rankDev);
+    HIPCHK(hipStreamSynchronize(d->stream));
+    return 0;
+}
+// potential lists sorted and merged on the device, slice by slice (a slice stays below 2^30 entries); exploration order on the host; ranks back
+static int reduce_ranked_order(Device* d, ReduceRun& R, std::string& err) {
+    const u64 N = d->N, nun = R.nun; RankLists L;
+    { int rc = rank_degrees(d, R, L, err); if (rc) return rc; }
+    // gigabytes at 10 M reads: 2 MB pages for the host's walk, registered so that the download is a DMA; kept in the context from step to step (allocating, touching
+    // and registering 1.7 GB took 100 ms of every call)
+    if (!d->rrStaging) d->rrStaging = new RrStaging();
+    RrStaging& staging = *(RrStaging*)d->rrStaging; staging.next = 0;
+    u64 sliceEntries = 1ull << 30; if (const char* ev = d->opt.get("SAGE2OV_TEST_RANK_SLICE")) sliceEntries = std::max<u64>(1024, strtoull(ev, nullptr, 10));
+    { WS(lenp, u32, WS_RR_LEN, nun + 2); L.lenp = lenp; }
+    for (u64 w0 = 0; w0 < nun;) {
+        u64 w1 = w0, tot0 = 0; while (w1 < nun && (w1 == w0 || tot0 + L.hDegp[w1] <= sliceEntries)) tot0 += L.hDegp[w1++];
+        if (tot0 >= (1ull << 32) - 64) return REDUCE_REPLAY;                      // one read with 2^32 potential neighbours: not this path
+        { int rc = rank_slice(d, R, L, staging, w0, w1, err); if (rc) return rc; }
+        w0 = w1;
+    }
+    { size_t hx = 0; for (u64 w = 0; w < nun; w++) if (L.hDegp[w] > (u32)RR_CAP) L.listPtr[w] = L.heavyLists[hx++].data(); }      // (after the last push_back: the vectors no longer move)
+    R.lap(d, "potential lists (build + sort + download)");
+    std::vector<u32> rankByPos, posOf, startOrder;
+    { int rc = rank_walk_setup(d, R, posOf, startOrder, err); if (rc) return rc; }
+    R.lap(d, "walk set-up (device + download)");
+    explore_order(d->opt, posOf, L.listPtr, L.hLen, L.hasCand, N, startOrder, rankByPos);
+    if (rankByPos.size() != N + 2) { err = "exploration walk: table allocation failed"; return SAGE2OV_ERR_NOMEM; }
+    R.lap(d, "exploration order (host)");
+    return rank_upload(d, R, rankByPos, err);
+}
+// Final lists, second half: the degrees the hits contribute (ranked: those the exploration order keeps), offsets, and the entries of candidates and hits
+static int reduce_final_lists(Device* d, ReduceRun& R, std::string& err) {
+    const u64 N = d->N, nc = d->n_cand, nslots = R.nslots; u32* const deg = R.deg; u32* const offs = R.offs;
+    if (R.ranked) { if (nslots) hipLaunchKernelGGL(k_rr_degree_h, dim3(grid_for(nslots, 256)), dim3(256), 0, d->stream, R.dh, (u64)nslots, R.rankDev, deg, d->d_counters + CTR_RANKED); }
+    else hipLaunchKernelGGL(k_ra_degree_h, dim3(grid_for(N + 1, 256)), dim3(256), 0, d->stream, R.hitcount, (u64)N, deg);
+    R.lap(d, "  ranks to the device, degrees of the final lists");
     u64 tot = 0; { int rc = scan_u32(d, deg, N + 2, offs, &tot, err); if (rc) return rc; }
-    if (tot >= (1ull << 32) - 64) return 0;
-    WS(ent, u64, WS_RA_ENT, tot + 64); WS(rm, uint8_t, WS_RA_RM, tot + 64); WS(ent32, u32, WS_RA_ENT32, tot + 64);
-    if (nc) hipLaunchKernelGGL(k_ra_fill_c, dim3(grid_for(nc, 256)), dim3(256), 0, d->stream, d->cand, (u64)nc, d->reads, d->S, d->uniL, offs, cur, ent, ent32);
-    if (ranked) { if (nslots) hipLaunchKernelGGL(k_rr_fill_h, dim3(grid_for(nslots, 256)), dim3(256), 0, d->stream, dh, (u64)nslots, rankDev, d->reads, d->S, d->uniL, offs, cur, ent, ent32); }
-    else if (nslots) hipLaunchKernelGGL(k_ra_fill_h, dim3(grid_for(nslots, 256)), dim3(256), 0, d->stream, dh, (u64)nslots, offs, deg, hitcount, ent, ent32);
-    if (ranked) { u64 c3[3]; int rc = read_counters(d, 8, 3, c3, err); if (rc) return rc; present = c3[2]; }
-    HIPCHK(hipMemsetAsync(d->d_counters + 8, 0, 5 * sizeof(u64), d->stream));
-    // this rank's share of the unresolved reads: entries [wlo, whi) of the list (any contiguous cut is exact: a read's marks depend on the lists only)
-    const u64 wlo = shareWorld > 1 ? nun * shareRank / shareWorld : 0, whi = shareWorld > 1 ? nun * (shareRank + 1) / shareWorld : nun;
-    const u32* const idsAll = ids; ids = ids + wlo; const u64 nunAll = nun; nun = whi - wlo; (void)idsAll; (void)nunAll;
-    WS(svn, u32, WS_NEED, nun + 2); WS(svoff, u32, WS_OWNER, nun + 2);
-    // (the marks' grid: a wave per read, blocks walk the list round-robin; blocks per CU -> reduce phase at configs[1] + 0.1 % errors: 16 -> 69.5 ms, 64 -> 66.0, 256 -> 65.2, 1024 -> 65.2: the tail again)
-    const unsigned gb = (unsigned)std::max<u64>(1, std::min<u64>((nun + 3) / 4, 256ull * 256));
+    if (tot >= (1ull << 32) - 64) return REDUCE_REPLAY;
+    WS(ent, u64, WS_RA_ENT, tot + 64); WS(rm, uint8_t, WS_RA_RM, tot + 64); WS(ent32, u32, WS_RA_ENT32, tot + 64); R.ent = ent; R.rm = rm; R.ent32 = ent32;
+    if (nc) hipLaunchKernelGGL(k_ra_fill_c, dim3(grid_for(nc, 256)), dim3(256), 0, d->stream, d->cand, (u64)nc, d->reads, d->S, d->uniL, offs, R.cur, ent, ent32);
+    if (R.ranked) { if (nslots) hipLaunchKernelGGL(k_rr_fill_h, dim3(grid_for(nslots, 256)), dim3(256), 0, d->stream, R.dh, (u64)nslots, R.rankDev, d->reads, d->S, d->uniL, offs, R.cur, ent, ent32); }
+    else if (nslots) hipLaunchKernelGGL(k_ra_fill_h, dim3(grid_for(nslots, 256)), dim3(256), 0, d->stream, R.dh, (u64)nslots, offs, deg, R.hitcount, ent, ent32);
+    if (R.ranked) { u64 c3[3]; int rc = read_counters(d, CTR_RANKED, 3, c3, err); if (rc) return rc; R.present = c3[2]; }
+    return 0;
+}
+// the marks of lists beyond the LDS kernel (heavy[0, nhv), listed by k_ra_mark): same marking out of global scratch, one wavefront each; c = CTR_MARKS afterwards
+static int reduce_marks_heavy(Device* d, ReduceRun& R, const u32* ids, u32* heavy, u32 nhv, u64 c[4], std::string& err) {
+    WS(hsize, u32, WS_RA_HSIZE, nhv); WS(hscr, u64, WS_RA_HSCR, nhv);
+    hipLaunchKernelGGL(k_ra_heavy_sizes, dim3(grid_for(nhv, 256)), dim3(256), 0, d->stream, heavy, nhv, ids, R.deg, hsize);
+    std::vector<u32> hs(nhv); HIPCHK(hipMemcpyAsync(hs.data(), hsize, nhv * sizeof(u32), hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));   // (the stream is non-blocking: the null stream does not wait for it)
+    std::vector<u64> so(nhv); u64 words = 0;
+    for (u32 b = 0; b < nhv; b++) { u64 P = 64; while (P < hs[b]) P <<= 1; so[b] = words; words += P + 2 * P + 2 * P; }      // key[P] u64 + ht[4P] u32 + mk[4P] u32
+    HIPCHK(hipMemcpyAsync(hscr, so.data(), nhv * sizeof(u64), hipMemcpyHostToDevice, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
+    DevTmp tmp; u64* scratch = tmp.get<u64>(words); if (!scratch) { err = "k_ra_mark_big: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+    hipLaunchKernelGGL(k_ra_mark_big, dim3(nhv), dim3(64), 0, d->stream, ids, heavy, hscr, scratch, R.offs, R.deg, R.ent, R.rm, R.svn, d->d_counters + CTR_MARKS);
+    hipError_t e2 = hipStreamSynchronize(d->stream); tmp.release(scratch);
+    if (e2 != hipSuccess) { err = std::string("k_ra_mark_big: ") + hipGetErrorString(e2); return SAGE2OV_ERR_DEVICE; }
+    HIPCHK(hipMemcpy(c, d->d_counters + CTR_MARKS, 4 * sizeof(u64), hipMemcpyDeviceToHost));
+    return 0;
+}
+// Marks (:643-707) of this rank's share: the transitive entries of every list, survivors counted per read (R.svn); d->ev[5] opens marks_ms
+static int reduce_marks(Device* d, ReduceRun& R, std::string& err) {
+    HIPCHK(hipMemsetAsync(d->d_counters + CTR_MARKS, 0, 5 * sizeof(u64), d->stream));      // (the words of CTR_RANKED, read by now)
+    const u32* const ids = R.ids + R.wlo; const u64 nun = R.whi - R.wlo;
+    WS(svn, u32, WS_NEED, nun + 2); WS(svoff, u32, WS_OWNER, nun + 2); R.svn = svn; R.svoff = svoff;
+    const unsigned gb = R.share_grid();
     const u64 heavyCap = 1 << 16; WS(heavy, u32, WS_RA_HEAVY, heavyCap);
-    lap("  final lists filled");
+    R.lap(d, "  final lists filled");                                       // (closes reduce_final_lists: it stands behind the marks' buffers, in front of the event that opens marks_ms)
     HIPCHK(hipEventRecord(d->ev[5], d->stream));                          // (marks_ms: the sharded part of the phase -- marks, removals, re-emission)
     const u32 noShortcut = d->opt.get("SAGE2OV_RA_NO_SHORTCUT") ? 1u : 0u;      // (tests: the walk of every list, as until round 4)
     WS(mid, u32, WS_RA_SPLIT, nun + 2);                                          // the reads with more than 128 entries, listed by the first launch for the second
     if (nun) {
-    hipLaunchKernelGGL((k_ra_mark<128, 8, 0, false>), dim3(gb), dim3(256), 0, d->stream, ids, (u64)nun, offs, deg, ent, ent32, rm, svn, d->d_counters + 8, heavy, heavyCap, noShortcut, mid);     // lists of <= 128 entries
-    hipLaunchKernelGGL((k_ra_mark<RA_CAP, 10, 128, true>), dim3(gb), dim3(256), 0, d->stream, ids, (u64)nun, offs, deg, ent, ent32, rm, svn, d->d_counters + 8, heavy, heavyCap, noShortcut, mid);   // 129 .. RA_CAP (the reads the first launch listed); longer: k_ra_mark_big
+    hipLaunchKernelGGL((k_ra_mark<128, 8, 0, false>), dim3(gb), dim3(256), 0, d->stream, ids, (u64)nun, R.offs, R.deg, R.ent, R.ent32, R.rm, svn, d->d_counters + CTR_MARKS, heavy, heavyCap, noShortcut, mid);     // lists of <= 128 entries
+    hipLaunchKernelGGL((k_ra_mark<RA_CAP, 10, 128, true>), dim3(gb), dim3(256), 0, d->stream, ids, (u64)nun, R.offs, R.deg, R.ent, R.ent32, R.rm, svn, d->d_counters + CTR_MARKS, heavy, heavyCap, noShortcut, mid);   // 129 .. RA_CAP (the reads the first launch listed); longer: k_ra_mark_big
     }
     u64 c[4];
-    { int rc = read_counters(d, 8, 4, c, err); if (rc) return rc; }
+    { int rc = read_counters(d, CTR_MARKS, 4, c, err); if (rc) return rc; }
     HIPCHK(hipGetLastError());
-    if (timing) fprintf(stderr, "[reduce/device] marks of %llu of %llu reads by the short cut (k_ra_mark: ra_shortcut), %.2f lists read per read\n", (unsigned long long)c[3], (unsigned long long)nun, nun ? (double)c[2] / (double)nun : 0.0);
-    if (c[0] > heavyCap) { if (shareWorld > 1) { err = "reduce: too many oversized lists in this rank's share"; return SAGE2OV_ERR_LIMIT; } return 0; }   // (never seen) that many oversized lists: serial replay (a rank of many cannot decide that alone)
-    if (c[0]) {                                                           // lists beyond the LDS kernel: same marking out of global scratch, one wavefront each
-        const u32 nhv = (u32)c[0];
-        WS(hsize, u32, WS_RA_HSIZE, nhv); WS(hscr, u64, WS_RA_HSCR, nhv);
-        hipLaunchKernelGGL(k_ra_heavy_sizes, dim3(grid_for(nhv, 256)), dim3(256), 0, d->stream, heavy, nhv, ids, deg, hsize);
-        std::vector<u32> hs(nhv); HIPCHK(hipMemcpyAsync(hs.data(), hsize, nhv * sizeof(u32), hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));   // (the stream is non-blocking: the null stream does not wait for it)
-        std::vector<u64> so(nhv); u64 words = 0;
-        for (u32 b = 0; b < nhv; b++) { u64 P = 64; while (P < hs[b]) P <<= 1; so[b] = words; words += P + 2 * P + 2 * P; }      // key[P] u64 + ht[4P] u32 + mk[4P] u32
-        HIPCHK(hipMemcpyAsync(hscr, so.data(), nhv * sizeof(u64), hipMemcpyHostToDevice, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
-        u64* scratch = nullptr; HIPCHK(hipMalloc(&scratch, words * sizeof(u64)));
-        hipLaunchKernelGGL(k_ra_mark_big, dim3(nhv), dim3(64), 0, d->stream, ids, heavy, hscr, scratch, offs, deg, ent, rm, svn, d->d_counters + 8);
-        hipError_t e2 = hipStreamSynchronize(d->stream); hipFree(scratch);
-        if (e2 != hipSuccess) { err = std::string("k_ra_mark_big: ") + hipGetErrorString(e2); return SAGE2OV_ERR_DEVICE; }
-        HIPCHK(hipMemcpy(c, d->d_counters + 8, sizeof c, hipMemcpyDeviceToHost));
-    }
-    u64 nsv = 0; if (nun) { int rc = scan_u32(d, svn, nun, svoff, &nsv, err); if (rc) return rc; }
+    if (R.timing) fprintf(stderr, "[reduce/device] marks of %llu of %llu reads by the short cut (k_ra_mark: ra_shortcut), %.2f lists read per read\n", (unsigned long long)c[3], (unsigned long long)nun, nun ? (double)c[2] / (double)nun : 0.0);
+    if (c[0] > heavyCap) { if (R.shareWorld > 1) { err = "reduce: too many oversized lists in this rank's share"; return SAGE2OV_ERR_LIMIT; } return REDUCE_REPLAY; }   // (never seen) that many oversized lists: serial replay (a rank of many cannot decide that alone)
+    if (c[0]) { int rc = reduce_marks_heavy(d, R, ids, heavy, (u32)c[0], c, err); if (rc) return rc; }
+    R.removed = c[1];
+    return 0;
+}
+// Emit: the survivors of this rank's share behind the candidates of the reciprocal pass (d->n_cand grows by them)
+static int reduce_emit(Device* d, ReduceRun& R, std::string& err) {
+    const u32* const ids = R.ids + R.wlo; const u64 nun = R.whi - R.wlo;
+    u64 nsv = 0; if (nun) { int rc = scan_u32(d, R.svn, nun, R.svoff, &nsv, err); if (rc) return rc; }
     if (d->n_cand + nsv > d->cand_cap || d->opt.get("SAGE2OV_TEST_SMALL_BUFFERS")) {
         { int rc = cand_resize(d, d->n_cand + nsv + 1024, d->n_cand, err); if (rc) return rc; }
     }
-    lap("final lists + marks");
-    if (nun) hipLaunchKernelGGL(k_ra_emit, dim3(gb), dim3(256), 0, d->stream, ids, (u64)nun, offs, deg, ent, rm, svoff, d->cand, (u64)d->n_cand, (u64)d->cand_cap);
+    R.lap(d, "final lists + marks");                                           // (closes reduce_marks: printed here, once the candidate list has room)
+    if (nun) hipLaunchKernelGGL(k_ra_emit, dim3(R.share_grid()), dim3(256), 0, d->stream, ids, (u64)nun, R.offs, R.deg, R.ent, R.rm, R.svoff, d->cand, (u64)d->n_cand, (u64)d->cand_cap);
     HIPCHK(hipGetLastError());
     d->n_cand += nsv;
-    *inserted = ranked ? 2 * present : nh; *removed = c[1]; *done = 1;
+    return 0;
+}
+int dev_reduce_device(Device* d, uint64_t min_unresolved, uint64_t* n_unresolved, uint64_t* n_hits, uint64_t* inserted, uint64_t* removed, int* done, std::string& err,
+                      uint32_t shareRank, uint32_t shareWorld) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    *done = 0; *inserted = 0; *removed = 0; *n_hits = 0;
+    HIPCHK(hipEventRecord(d->ev[0], d->stream));
+    ReduceRun R;
+    { int rc = collect_unresolved(d, &R.ids, &R.nun, err); if (rc) return rc; }
+    const u64 nun = R.nun; *n_unresolved = nun;
+    if (nun == 0) { *done = 1; return 0; }
+    if (nun < min_unresolved) return 0;
+    R.ranked = d->n_long != 0; R.shareWorld = shareWorld;
+    R.wlo = shareWorld > 1 ? nun * shareRank / shareWorld : 0; R.whi = shareWorld > 1 ? nun * (shareRank + 1) / shareWorld : nun;
+    R.timing = d->opt.get("SAGE2OV_TIMING") != nullptr; R.tp = std::chrono::steady_clock::now();
+    int rc = reduce_hit_lists(d, R, err); if (rc) return rc;
+    *n_hits = R.nh;
+    R.lap(d, "hit lists");
+    rc = reduce_cand_degrees(d, R, err);
+    if (!rc && R.ranked) rc = reduce_ranked_order(d, R, err);
+    if (!rc) rc = reduce_final_lists(d, R, err);
+    if (!rc) rc = reduce_marks(d, R, err);
+    if (!rc) rc = reduce_emit(d, R, err);
+    if (rc) return rc == REDUCE_REPLAY ? 0 : rc;                          // (replay: *done stays 0)
+    *inserted = R.ranked ? 2 * R.present : R.nh; *removed = R.removed; *done = 1;
     HIPCHK(hipEventRecord(d->ev[1], d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
     float ms = 0; hipEventElapsedTime(&ms, d->ev[0], d->ev[1]); d->tm.hits_ms += ms;
     hipEventElapsedTime(&ms, d->ev[5], d->ev[1]); d->tm.marks_ms += ms;
@@ -1527,10 +1621,10 @@ int dev_collect_reduce_edges(Device* d, const std::vector<uint32_t>& unresolved,
         const unsigned blocks = (unsigned)std::min<u64>(grid_for(n, 256), 256ull * 8);
         // (every candidate that touches a read of the short list was emitted by a read of the list or by a partner of one: at most 2 per read and partner)
         cap = 2 * (u64)need.size() * 3 + 64; { WS(nb_, EdgeCand, WS_NEAR, cap); buf = nb_; }
-        HIPCHK(hipMemsetAsync(d->d_counters + 5, 0, sizeof(u64), d->stream));
-        hipLaunchKernelGGL(k_red_collect_few, dim3(blocks), dim3(256), 0, d->stream, d->cand, (u64)n, dNeed, (u32)need.size(), dIds, nUn, buf, cap, d->d_counters + 5);
+        HIPCHK(hipMemsetAsync(d->d_counters + CTR_LIST, 0, sizeof(u64), d->stream));
+        hipLaunchKernelGGL(k_red_collect_few, dim3(blocks), dim3(256), 0, d->stream, d->cand, (u64)n, dNeed, (u32)need.size(), dIds, nUn, buf, cap, d->d_counters + CTR_LIST);
         HIPCHK(hipGetLastError());
-        u64 cnt = 0; { int rc = read_counters(d, 5, 1, &cnt, err); if (rc) return rc; }
+        u64 cnt = 0; { int rc = read_counters(d, CTR_LIST, 1, &cnt, err); if (rc) return rc; }
         if (cnt <= cap) {                                                  // (else: the general form below -- the 0x80 flags are idempotent)
             out.resize(cnt); if (cnt) HIPCHK(hipMemcpy(out.data(), buf, cnt * sizeof(EdgeCand), hipMemcpyDeviceToHost));
             return 0;
@@ -1539,25 +1633,17 @@ int dev_collect_reduce_edges(Device* d, const std::vector<uint32_t>& unresolved,
     WS(need, uint8_t, WS_NEED, d->N + 1); HIPCHK(hipMemsetAsync(need, 0, d->N + 1, d->stream));
     hipLaunchKernelGGL(k_red_mark, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, d->cand, (u64)n, d->status, need);
     // first a dry count (cap 0 keeps the flagging idempotent), then the real collection
-    HIPCHK(hipMemsetAsync(d->d_counters + 5, 0, sizeof(u64), d->stream));
-    hipLaunchKernelGGL(k_red_collect, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, d->cand, (u64)n, d->status, need, (EdgeCand*)nullptr, (u64)0, d->d_counters + 5);
-    u64 cnt = 0; { int rc = read_counters(d, 5, 1, &cnt, err); if (rc) return rc; }
+    HIPCHK(hipMemsetAsync(d->d_counters + CTR_LIST, 0, sizeof(u64), d->stream));
+    hipLaunchKernelGGL(k_red_collect, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, d->cand, (u64)n, d->status, need, (EdgeCand*)nullptr, (u64)0, d->d_counters + CTR_LIST);
+    u64 cnt = 0; { int rc = read_counters(d, CTR_LIST, 1, &cnt, err); if (rc) return rc; }
     if (cnt) {
         cap = cnt; { WS(nb_, EdgeCand, WS_NEAR, cap); buf = nb_; }
-        HIPCHK(hipMemsetAsync(d->d_counters + 5, 0, sizeof(u64), d->stream));
-        hipLaunchKernelGGL(k_red_collect, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, d->cand, (u64)n, d->status, need, buf, cap, d->d_counters + 5);
+        HIPCHK(hipMemsetAsync(d->d_counters + CTR_LIST, 0, sizeof(u64), d->stream));
+        hipLaunchKernelGGL(k_red_collect, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, d->cand, (u64)n, d->status, need, buf, cap, d->d_counters + CTR_LIST);
         HIPCHK(hipStreamSynchronize(d->stream));
         out.resize(cnt); HIPCHK(hipMemcpy(out.data(), buf, cnt * sizeof(EdgeCand), hipMemcpyDeviceToHost));
         for (auto& e : out) e.type &= 0x7Fu;
     }
-    return 0;
-}
-int dev_unresolved_ids(Device* d, std::vector<uint32_t>& ids, std::string& err) {      // (the list stays in WS_IDS: dev_unresolved_hits probes it)
-    HIPCHK(hipSetDevice(d->ordinal));
-    ids.clear();
-    u32* buf = nullptr; u64 cnt = 0; { int rc = collect_unresolved(d, &buf, &cnt, err); if (rc) return rc; }
-    ids.resize(cnt); if (cnt) HIPCHK(hipMemcpy(ids.data(), buf, cnt * sizeof(u32), hipMemcpyDeviceToHost));
-    std::sort(ids.begin(), ids.end());
     return 0;
 }
 
@@ -1855,23 +1941,23 @@ int dev_debug_keys(Device* d, uint64_t* out, std::string& err) {
 // diagnostic: hit lists (economyGraph.cpp:591-633 semantics) of EVERY read, as if all were unresolved
 int dev_debug_all_hits(Device* d, std::vector<Hit>& hits, std::string& err) {
     HIPCHK(hipSetDevice(d->ordinal));
-    const u64 N = d->N; uint8_t* saved = nullptr;
-    HIPCHK(hipMalloc(&saved, N + 1)); HIPCHK(hipStreamSynchronize(d->stream));
+    const u64 N = d->N; DevTmp tmp;
+    uint8_t* saved = tmp.get<uint8_t>(N + 1); if (!saved) { err = "debug hits: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+    HIPCHK(hipStreamSynchronize(d->stream));
     HIPCHK(hipMemcpyAsync(saved, d->status, N + 1, hipMemcpyDeviceToDevice, d->stream));
     HIPCHK(hipMemsetAsync(d->status, 0, N + 1, d->stream));
-    u64 cap = std::max<u64>(1 << 16, N * 128); Hit* dh = nullptr;
-    HIPCHK(hipMalloc(&dh, cap * sizeof(Hit)));
-    HIPCHK(hipMemsetAsync(d->d_counters + 4, 0, sizeof(u64), d->stream));
+    u64 cap = std::max<u64>(1 << 16, N * 128);
+    Hit* dh = tmp.get<Hit>(cap); if (!dh) { err = "debug hits: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+    HIPCHK(hipMemsetAsync(d->d_counters + CTR_HIT_CURSOR, 0, sizeof(u64), d->stream));
     ProbeArgs A = base_args(d); A.lo = 1; A.hi = N + 1; A.hits = dh; A.hits_cap = cap;
     int rc = refresh_status_by_pos(d, err); if (!rc) rc = launch_probe<1>(d, A, err);
     u64 nh = 0;
-    if (!rc) { int rcr = read_counters(d, 4, 1, &nh, err); if (rcr) return rcr; }
+    if (!rc) { int rcr = read_counters(d, CTR_HIT_CURSOR, 1, &nh, err); if (rcr) return rcr; }
     if (!rc && nh > cap) { err = "debug hit buffer too small"; rc = SAGE2OV_ERR_LIMIT; }
     if (!rc) { hits.resize(nh); if (nh) HIPCHK(hipMemcpy(hits.data(), dh, nh * sizeof(Hit), hipMemcpyDeviceToHost)); }
     HIPCHK(hipMemcpyAsync(d->status, saved, N + 1, hipMemcpyDeviceToDevice, d->stream));
     { int rc2 = refresh_status_by_pos(d, err); if (!rc) rc = rc2; }      // (statusP is what the reciprocal pass left again)
     HIPCHK(hipStreamSynchronize(d->stream));
-    hipFree(saved); hipFree(dh);
     return rc;
 }
 
