@@ -37,7 +37,7 @@ struct ProbeArgs {
     const u64* slots; u64 T; const u32* csr; u64 seed;
     u64 lo, hi;                    // range of POSITIONS [lo, hi)
     u64* right; u64* left; u32* conn; u32* cflag;         // MODE 0 outputs
-    const uint8_t* status; Hit* hits; u64 hits_cap; u64* counters;   // MODE 1
+    Hit* hits; u64 hits_cap; u64* counters;                // MODE 1
     u32* hitcount;                                         // MODE 1, optional: number of hits of every read (written for status-0 reads)
     u64* hitBase;                                          // fast kernel, TAIL = 2, optional: the read's hits are written out in the initial pass; where they start (~0: not written)
     const u32* ids; u64 n_ids;                             // optional explicit list of positions (replaces [lo,hi))
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(64 * WPB) void k_probe(ProbeArgs A) {
     for (u64 it = first + wave0; it < last; it += nwaves) {
         const u64 i = A.ids ? (u64)A.ids[it] : it;
         const u32 iid = A.idOf[i];                                  // i is a position in the locality-ordered store
-        if (MODE == 1) { if (A.status[iid] != 0) continue; }        // (this kernel reads exploredReads through the ids: no by-position copy needed)
+        if (MODE == 1) { if (A.statusP[i] != 0) continue; }         // (exploredReads by position: the copy by id exists on demand only, ensure_status_by_id)
         // ---- stage the read and its reverse complement in LDS
         wave_sync();
         if (lane < S) W.x[0][lane] = A.reads[i * S + lane];
@@ -131,7 +131,7 @@ __global__ __launch_bounds__(64 * WPB) void k_probe(ProbeArgs A) {
                     const u64 r2 = entry >> 2; const int t = entry & 3;
                     const bool rightSide = (t == 0 || t == 2);
                     bool gate = (r2 != i) && (rightSide ? (jj <= L1 - k) : (jj >= k - h));
-                    if (MODE == 1 && gate) gate = (A.status[A.idOf[r2]] == 0);
+                    if (MODE == 1 && gate) gate = (A.statusP[r2] == 0);
                     if (gate) {
                         const u64* yp = A.reads + r2 * S;
 #pragma unroll

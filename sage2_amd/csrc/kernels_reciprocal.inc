@@ -11,10 +11,13 @@ constexpr int COND_PER_THREAD = 8;                // reads per thread: the three
 // Round 3: the per-read records (right / left / conn / cflag) are indexed by POSITION in the locality order and name their neighbours by position, as the
 // probe kernels produce them: a read's two neighbours are its neighbours in the genome, hence (mostly) a few lines away -- round 2 gathered their records
 // by id, two random 128-byte lines per read, 2.3 ms at BASELINE configs[2] (now 1.1).  cond() is a statement about a read and its neighbours: the same in
-// either numbering.  The status goes out twice: by position (statusP: what the hit-list kernels read) and by id (what the reduce and convert phases index).
+// either numbering.  The status goes out by position (statusP: what the emit half, the hit-list kernels and the unresolved list read).  The copy by id that
+// the reduce phase's by-id readers index is a random one-byte store per read: BY_ID = true writes it here (SAGE2OV_STATUS_EAGER=1, the A/B route); by default
+// it is gathered from statusP when a reader first asks for it (k_status_by_id, ensure_status_by_id) -- on clean data nobody does.
+template <bool BY_ID>
 __global__ __launch_bounds__(256) void k_recip_cond(u64 N, const u64* __restrict__ right, const u64* __restrict__ left, const u32* __restrict__ conn,
                              const u32* __restrict__ cflag, const u32* __restrict__ idOf, uint8_t* status, uint8_t* statusP, u64* counters) {
-    u64 ovs = 0; u32 ncond = 0, n6 = 0;
+    u64 ovs = 0; u32 ncond = 0, n6 = 0, n0 = 0;
 #pragma unroll
     for (int it = 0; it < COND_PER_THREAD; it++) {
         const u64 p = (u64)blockIdx.x * (256 * COND_PER_THREAD) + (u64)it * 256 + threadIdx.x + 1;
@@ -29,19 +32,19 @@ __global__ __launch_bounds__(256) void k_recip_cond(u64 N, const u64* __restrict
                 cond = lrec && rrec;
             }
             const uint8_t st = cond ? 4 : (is6 ? 6 : (over ? 5 : 0));
-            statusP[p] = st; status[idOf[p]] = st;
-            ovs += c; ncond += cond; n6 += is6;
+            statusP[p] = st; if (BY_ID) status[idOf[p]] = st;
+            ovs += c; ncond += cond; n6 += is6; n0 += st == 0;
         }
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) { statusP[0] = 0xFF; status[0] = 0; }     // (position 0: never unresolved; id 0 does not exist)
-    // block reductions of the log counters: one atomic per counter per block
-    __shared__ u64 red[3][4];
-    u64 v0 = ovs, v1 = ncond, v2 = n6;
-    for (int d = 32; d; d >>= 1) { v0 += __shfl_xor(v0, d); v1 += __shfl_xor(v1, d); v2 += __shfl_xor(v2, d); }
+    if (blockIdx.x == 0 && threadIdx.x == 0) { statusP[0] = 0xFF; if (BY_ID) status[0] = 0; }     // (position 0: never unresolved; id 0 does not exist)
+    // block reductions of the log counters and of the number of unresolved reads (what collect_unresolved sizes its list by): one atomic per counter per block
+    __shared__ u64 red[4][4];
+    u64 v0 = ovs, v1 = ncond, v2 = n6, v3 = n0;
+    for (int d = 32; d; d >>= 1) { v0 += __shfl_xor(v0, d); v1 += __shfl_xor(v1, d); v2 += __shfl_xor(v2, d); v3 += __shfl_xor(v3, d); }
     const u32 w = threadIdx.x >> 6;
-    if (lane_id() == 0) { red[0][w] = v0; red[1][w] = v1; red[2][w] = v2; }
+    if (lane_id() == 0) { red[0][w] = v0; red[1][w] = v1; red[2][w] = v2; red[3][w] = v3; }
     __syncthreads();
-    if (threadIdx.x < 3) {
+    if (threadIdx.x < 4) {
         u64 t = 0; for (u32 x = 0; x < 4; x++) t += red[threadIdx.x][x];
         if (t) atomicAdd(&counters[1 + threadIdx.x], t);
     }
@@ -137,19 +140,24 @@ __global__ void k_records_to_ids(u64 N, const u32* __restrict__ idOf, const u64*
     const u32 i = idOf[p]; const u64 r = right[p], l = left[p];
     rightI[i] = (r & ~ID_MASK) | idOf[r & ID_MASK]; leftI[i] = (l & ~ID_MASK) | idOf[l & ID_MASK]; connI[i] = conn[p];
 }
+// the by-id copy of the status, on demand (ensure_status_by_id): coalesced byte stores, random byte loads
+__global__ __launch_bounds__(256) void k_status_by_id(u64 N, const u32* __restrict__ posOf, const uint8_t* __restrict__ statusP, uint8_t* status) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; if (i > N) return; status[i] = i ? statusP[posOf[i]] : (uint8_t)0;
+}
+// the unresolved reads: the positions with status 0, listed by id, in any order
 constexpr int UNRES_PER_THREAD = 16;
-__global__ __launch_bounds__(256) void k_red_unresolved(u64 N, const uint8_t* __restrict__ status, u32* out, u64 cap, u64* counter) {
+__global__ __launch_bounds__(256) void k_red_unresolved(u64 N, const uint8_t* __restrict__ statusP, const u32* __restrict__ idOf, u32* out, u64 cap, u64* counter) {
     __shared__ u32 sh[4]; __shared__ u64 shBase;
     const u64 tile0 = (u64)blockIdx.x * (256 * UNRES_PER_THREAD) + 1;
     u32 flags = 0, mine = 0;
 #pragma unroll
-    for (int it = 0; it < UNRES_PER_THREAD; it++) { const u64 i = tile0 + (u64)it * 256 + threadIdx.x; if (i <= N && status[i] == 0) { flags |= 1u << it; mine++; } }
+    for (int it = 0; it < UNRES_PER_THREAD; it++) { const u64 i = tile0 + (u64)it * 256 + threadIdx.x; if (i <= N && statusP[i] == 0) { flags |= 1u << it; mine++; } }
     u32 total; const u32 excl = block_excl_scan(mine, sh, total);
     if (total == 0) return;
     if (threadIdx.x == 0) shBase = atomicAdd(counter, (u64)total);                 // one atomic per 4096 reads (most reads are unresolved on noisy data)
     __syncthreads();
     u64 p = shBase + excl;
 #pragma unroll
-    for (int it = 0; it < UNRES_PER_THREAD; it++) if (flags & (1u << it)) { if (p < cap) out[p] = (u32)(tile0 + (u64)it * 256 + threadIdx.x); p++; }
+    for (int it = 0; it < UNRES_PER_THREAD; it++) if (flags & (1u << it)) { if (p < cap) out[p] = idOf[tile0 + (u64)it * 256 + threadIdx.x]; p++; }
 }
 

@@ -38,32 +38,33 @@ namespace s2 {
 typedef unsigned long long u64;
 typedef unsigned int u32;
 
-enum { WS_SLOTS, WS_WHERE, WS_BIG, WS_CSR, WS_SLOW, WS_NEED, WS_CURSOR, WS_KEYS, WS_KEEP, WS_POS, WS_OWNER, WS_FINAL,
+enum { WS_SLOTS, WS_WHERE, WS_BIG, WS_CSR, WS_SLOW, WS_NEED, WS_CURSOR, WS_KEYS, WS_KEEP, WS_OWNER, WS_FINAL,
        WS_PARTIAL, WS_IDS, WS_NEAR, WS_HITS, WS_MINH, WS_OCUR, WS_MI1, WS_KREC, WS_RA_DEG, WS_RA_OFF, WS_RA_CUR, WS_RA_ENT, WS_RA_RM, WS_ORG_POOL, WS_ORG_OFF, WS_ORG_LEN, WS_ORG_IMG, WS_ORG_K0, WS_ORG_K1, WS_ORG_V0, WS_ORG_V1, WS_ORG_HIST, WS_ORG_HSCAN, WS_ORG_FLAG, WS_ORG_UID, WS_ORG_HEAD, WS_RR_IN, WS_RR_DEGP, WS_RR_OFFP, WS_RR_ENTP, WS_RR_OUTP, WS_RR_WIDX, WS_RR_RANK, WS_RR_CUR, WS_RA_HEAVY, WS_RA_HSIZE, WS_RA_HSCR, WS_RR_LEN, WS_RR_COFF, WS_RR_OUTC,
        WS_PT_K0, WS_PT_K1, WS_PT_CNT, WS_PT_BASE, WS_PT_OFF, WS_PT_GOFF, WS_RR_RANKL, WS_LOC_READS, WS_LOC_IDOF, WS_LOC_POSOF, WS_LOC_STATUS, WS_ORG_GFLAG, WS_ORG_GPOS, WS_LOC_META, WS_SLOW2, WS_RA_ENT32, WS_RA_SPLIT, WS_PRE_BASE, WS_PRE_NONE, WS_COUNT };   // ids of the workspace arena (Device::ws)
 // Bases of the device counters (Device::d_counters, u64 words): who owns the words from each base on, how many, what each holds.  A kernel that is handed
 // d_counters + base indexes from that base; the probe kernels are handed d_counters itself (ProbeArgs::counters) and use the CTR_HIT_* / CTR_HANDED names.
 // Slots that two phases use in turn, never at once: CTR_LIST is CTR_HIT_REAL (a list is collected before or after the hit lists, not during them);
-// CTR_INDEX, CTR_RANKED and CTR_MARKS share base 8 (index build, then within one reduce the ranked lists, read back and zeroed before the marks);
+// CTR_INDEX, CTR_RANKED and CTR_MARKS share base 9 (index build, then within one reduce the ranked lists, read back and zeroed before the marks);
 // the last two words of CTR_INDEX are the first two of CTR_ORG (step 1 is over when the index build starts);
-// dev_reciprocal zeroes the 8 words from CTR_RECIP, the probe's four with them (the probe pass is over by then).
+// dev_reciprocal zeroes the 9 words from CTR_RECIP, the probe's four with them (the probe pass is over by then).
 enum {
-    CTR_RECIP = 0,        // reciprocal pass, 4 words: [0] cursor of the candidate list, [1] verified overlaps, [2] contained reads, [3] their summed size
-    CTR_HIT_CURSOR = 4,   // probe kernels that write hits, 1 word: cursor in the Hit buffer (may pass the capacity: nothing is written beyond it)
-    CTR_HIT_REAL = 5,     // fast kernel's hit-list form, 1 word: real hits among the chunks it took
-    CTR_LIST = 5,         // cursor of a collected list, 1 word: k_red_unresolved, k_red_collect, k_red_collect_few (in turn with CTR_HIT_REAL)
-    CTR_HANDED = 6,       // fast kernel, 2 words: [0] reads handed on to the next pass (the slow list), [1] of them: more candidates than the form has slots
-    CTR_INDEX = 8,        // index build, 10 words: [0] csr entries, [1] keys, [2] long buckets, [3] impure long buckets, [4] pure ones, [5] group records, [6] groups,
+    CTR_RECIP = 0,        // reciprocal pass, 5 words: [0] cursor of the candidate list, [1] verified overlaps, [2] contained reads, [3] their summed size,
+                          //   [4] unresolved reads (status 0): what collect_unresolved sizes its list by
+    CTR_HIT_CURSOR = 5,   // probe kernels that write hits, 1 word: cursor in the Hit buffer (may pass the capacity: nothing is written beyond it)
+    CTR_HIT_REAL = 6,     // fast kernel's hit-list form, 1 word: real hits among the chunks it took
+    CTR_LIST = 6,         // cursor of a collected list, 1 word: k_red_unresolved, k_red_collect, k_red_collect_few (in turn with CTR_HIT_REAL)
+    CTR_HANDED = 7,       // fast kernel, 2 words: [0] reads handed on to the next pass (the slow list), [1] of them: more candidates than the form has slots
+    CTR_INDEX = 9,        // index build, 10 words: [0] csr entries, [1] keys, [2] long buckets, [3] impure long buckets, [4] pure ones, [5] group records, [6] groups,
                           //   [7] group windows given up, [8] failures (windows overflowed | keys beyond the count field << 20 | heavy windows without scratch << 40), [9] scratch cursor
-    CTR_RANKED = 8,       // reduce phase, ranked lists, 4 words: [2] hits present in the final lists (k_rr_degree_h), [3] potential lists beyond RR_CAP (k_rr_sortp); [0], [1] unused
-    CTR_MARKS = 8,        // reduce phase, marks, 5 words: [0] lists beyond RA_CAP, [1] removed entries, [2] lists the short cut read, [3] reads it settled, [4] reads listed for the second launch
-    CTR_ORG = 16,         // step 1's ASCII front end (k_org_classify), 6 words: [0] longest good read, [1] good reads, [2] their bases, [3] reads not longer than
+    CTR_RANKED = 9,       // reduce phase, ranked lists, 4 words: [2] hits present in the final lists (k_rr_degree_h), [3] potential lists beyond RR_CAP (k_rr_sortp); [0], [1] unused
+    CTR_MARKS = 9,        // reduce phase, marks, 5 words: [0] lists beyond RA_CAP, [1] removed entries, [2] lists the short cut read, [3] reads it settled, [4] reads listed for the second launch
+    CTR_ORG = 17,         // step 1's ASCII front end (k_org_classify), 6 words: [0] longest good read, [1] good reads, [2] their bases, [3] reads not longer than
                           //   the minimum overlap, [4] shortest good read, [5] reads beyond the length limit
-    CTR_FILTER = 22,      // reduce phase, pre-hits filter (k_hits_filter), 2 words: [0] kept hits, [1] unresolved reads without written hits
-    CTR_RUNSTARTS = 24,   // locality order (k_loc_index), 64 words: run starts, spread over 64 words (Device::d_runStarts)
-    CTR_WORDS = 24 + 64   // what dev_create allocates
+    CTR_FILTER = 23,      // reduce phase, pre-hits filter (k_hits_filter), 2 words: [0] kept hits, [1] unresolved reads without written hits
+    CTR_RUNSTARTS = 25,   // locality order (k_loc_index), 64 words: run starts, spread over 64 words (Device::d_runStarts)
+    CTR_WORDS = 25 + 64   // what dev_create allocates
 };
-static_assert(CTR_RECIP + 8 <= CTR_INDEX && CTR_HANDED + 2 <= CTR_INDEX && CTR_INDEX + 10 <= CTR_FILTER && CTR_MARKS + 5 <= CTR_ORG && CTR_ORG + 6 <= CTR_FILTER &&
+static_assert(CTR_RECIP + 5 <= CTR_HIT_CURSOR && CTR_HIT_CURSOR + 1 <= CTR_HIT_REAL && CTR_HIT_REAL + 1 <= CTR_HANDED && CTR_RECIP + 9 <= CTR_INDEX && CTR_HANDED + 2 <= CTR_INDEX && CTR_INDEX + 10 <= CTR_FILTER && CTR_MARKS + 5 <= CTR_ORG && CTR_ORG + 6 <= CTR_FILTER &&
               CTR_FILTER + 2 <= CTR_RUNSTARTS && CTR_RUNSTARTS + 64 <= CTR_WORDS, "a counter group runs into the next one, or past the allocation");
 struct MateLib { u64* key = nullptr; u64* cnt = nullptr; u64* first = nullptr; u64 n = 0; };      // one library's mate table: sorted by key, unique (kernels_mates.inc)
 struct Mates { MateLib lib[128]; u64* pkey = nullptr; u64* pord = nullptr; u64 pn = 0, pcap = 0; };   // + the pending records of the call in progress (keys, record ordinals)
@@ -88,6 +89,11 @@ struct Device {
     int uniL = 0;                                                                // the common read length when all reads have one (else 0): no length gathers
     // per-read results
     u64* right = nullptr; u64* left = nullptr; u32* conn = nullptr; u32* cflag = nullptr; uint8_t* status = nullptr;
+    // The status of the reciprocal pass: statusP (by position) is what k_recip_cond writes and is authoritative from then on; status (by id) follows it when a
+    // by-id reader asks (ensure_status_by_id), or at once on the eager route.  statusByIdValid: the two agree.  statusGen: stamps the statuses (bumped by
+    // dev_reciprocal and by everything else that writes one); nUnres: the status-0 reads k_recip_cond counted; unresGen: the statusGen whose unresolved reads
+    // WS_IDS lists (nUnres of them, any order), 0 when it lists nothing of the kind.
+    bool statusByIdValid = true; u64 statusGen = 1, nUnres = 0, unresGen = 0;
     // edge candidates
     EdgeCand* cand = nullptr; u64 cand_cap = 0; u64* d_counters = nullptr;  // CTR_WORDS words: see the CTR_ enum
     u64 n_cand = 0;
@@ -148,7 +154,7 @@ static void* ws_get(Device* d, int id, size_t bytes) {
 // workspace ids that live in the phase block in diet mode (see Device::Phase)
 static bool ws_phased(int id) {
     switch (id) { case WS_PT_K0: case WS_PT_K1: case WS_WHERE: case WS_MINH: case WS_OCUR: case WS_PT_CNT: case WS_PT_BASE: case WS_PARTIAL: case WS_PT_OFF:
-                  case WS_KEYS: case WS_KEEP: case WS_POS: case WS_FINAL: case WS_SLOW: case WS_SLOW2: return true; default: return false; }
+                  case WS_KEYS: case WS_KEEP: case WS_FINAL: case WS_SLOW: case WS_SLOW2: return true; default: return false; }
 }
 static void* ph_carve(Device* d, size_t bytes) {
     Device::Phase& P = d->ph;
@@ -262,10 +268,15 @@ struct StreamLap {
 // Exclusive scan of n u32 (kernels_scan.inc); partial: scan_partial_words(n) words.  total null: nothing is read back, nothing is synchronised; else the sum
 // of the input comes back and the stream has finished.  n = 0: no block to launch, the total is 0.
 static inline u64 scan_partial_words(u64 n) { return n / SCAN_BLOCK + 2; }
-static int scan_u32(Device* d, const u32* in, u64 n, u32* out, u64* partial, u64* total, std::string& err) {
+// the first two kernels of the scan: partial[b] = sum of the items in front of block b (SCAN_BLOCK items each), partial[nb] = the sum of all; returns nb
+static u64 scan_block_sums(Device* d, const u32* in, u64 n, u64* partial) {
     const u64 nb = (n + SCAN_BLOCK - 1) / SCAN_BLOCK;
     if (nb) hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, d->stream, in, (u64)n, partial);
     hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(1024), 0, d->stream, partial, (u64)nb, partial + nb);
+    return nb;
+}
+static int scan_u32(Device* d, const u32* in, u64 n, u32* out, u64* partial, u64* total, std::string& err) {
+    const u64 nb = scan_block_sums(d, in, n, partial);
     if (nb) hipLaunchKernelGGL(k_scan_final, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, d->stream, in, (u64)n, partial, out);
     HIPCHK(hipGetLastError());
     if (total) { HIPCHK(hipMemcpyAsync(total, partial + nb, sizeof(u64), hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream)); }
@@ -366,6 +377,7 @@ static void free_reads(Device* d) {
     for (auto& b : d->ws) { if (b.p && !b.epoch) hipFree(b.p); b.p = nullptr; b.cap = 0; b.epoch = 0; }
     s4cache_release(d);
     d->runStartFrac = 0.0; d->runStartsValid = false;          // (measured on the read set that just went: a new one decides for itself)
+    d->statusByIdValid = true; d->statusGen++; d->nUnres = 0; d->unresGen = 0;      // (no status of either kind is left)
     d->readsLoc = nullptr; d->idOf = d->posOf = nullptr; d->statusP = nullptr; d->metaP = nullptr; d->mi1 = d->krec = nullptr; d->cand_cap = 0; d->n_cand = 0;
     d->reads = d->slots = nullptr; d->csr = nullptr; d->right = d->left = nullptr; d->conn = d->cflag = nullptr; d->status = nullptr; d->cand = nullptr; d->final_edges = nullptr;
 }
@@ -596,6 +608,13 @@ static int build_locality_store(Device* d, bool deferCopy, std::string& err) {
 static int refresh_status_by_pos(Device* d, std::string& err) {
     hipLaunchKernelGGL(k_status_by_pos, dim3(grid_for(d->N + 1, 256)), dim3(256), 0, d->stream, d->idOf, d->status, (u64)d->N, d->statusP);
     HIPCHK(hipGetLastError()); return 0;
+}
+// In front of every reader of d->status: the by-id copy of what k_recip_cond left by position, gathered once (the clean-data step never gets here)
+static int ensure_status_by_id(Device* d, std::string& err) {
+    if (d->statusByIdValid) return 0;
+    if (!d->status || !d->statusP || !d->posOf) { err = "status by id: no reciprocal pass to take it from"; return SAGE2OV_ERR_INTERNAL; }
+    hipLaunchKernelGGL(k_status_by_id, dim3(grid_for(d->N + 1, 256)), dim3(256), 0, d->stream, (u64)d->N, d->posOf, d->statusP, d->status);
+    HIPCHK(hipGetLastError()); d->statusByIdValid = true; return 0;
 }
 static int pt_digits(u64 nWin, int* bits, int* nd) {            // window id bits, number of <= 9-bit digits
     int wb = 0; while ((1ull << wb) < nWin) wb++;
@@ -833,7 +852,7 @@ static int launch_probe(Device* d, ProbeArgs& A, std::string& err) {
 static ProbeArgs base_args(Device* d) {
     ProbeArgs A; memset(&A, 0, sizeof A);
     A.reads = d->readsLoc; A.idOf = d->idOf; A.statusP = d->statusP; A.meta = d->metaP; A.N = d->N; A.S = d->S; A.k = d->k; A.h = d->h; A.slots = d->slots; A.T = d->T; A.csr = d->csr; A.seed = d->seed;
-    A.right = d->right; A.left = d->left; A.conn = d->conn; A.cflag = d->cflag; A.status = d->status; A.counters = d->d_counters;
+    A.right = d->right; A.left = d->left; A.conn = d->conn; A.cflag = d->cflag; A.counters = d->d_counters;
     A.mi1 = d->mi1; A.TL = d->TL; A.krec = d->krec; A.uniL = d->uniL;
     A.chunkShift = (u32)FAST_CHUNK_LOG;      // (plan_fast_grid may double the positions per block visit)
     A.noRun = d->opt.get("SAGE2OV_NO_RUN_MODE") ? 1u : 0u; A.noParTail = d->opt.get("SAGE2OV_NO_PAR_TAIL") ? 1u : 0u;
@@ -1182,9 +1201,12 @@ int dev_reciprocal(Device* d, uint64_t emit_lo, uint64_t emit_hi, uint64_t* n_ov
     HIPCHK(hipSetDevice(d->ordinal));
     const u64 N = d->N;
     HIPCHK(hipEventRecord(d->ev[0], d->stream));
-    HIPCHK(hipMemsetAsync(d->d_counters + CTR_RECIP, 0, 8 * sizeof(u64), d->stream));      // (its four words and the probe pass's four)
-    // (records by position; the status goes out by position -- statusP, what the emit half and the hit-list kernels read -- and by id)
-    hipLaunchKernelGGL(k_recip_cond, dim3(grid_for(N, 256 * COND_PER_THREAD)), dim3(256), 0, d->stream, N, d->right, d->left, d->conn, d->cflag, d->idOf, d->status, d->statusP, d->d_counters + CTR_RECIP);
+    HIPCHK(hipMemsetAsync(d->d_counters + CTR_RECIP, 0, 9 * sizeof(u64), d->stream));      // (its five words and the probe pass's four)
+    // (records by position; the status goes out by position -- statusP, what the emit half and the hit-list kernels read; by id on demand, or here on the A/B route)
+    const bool eager = d->opt.get("SAGE2OV_STATUS_EAGER") != nullptr;
+    if (eager) hipLaunchKernelGGL(k_recip_cond<true>, dim3(grid_for(N, 256 * COND_PER_THREAD)), dim3(256), 0, d->stream, N, d->right, d->left, d->conn, d->cflag, d->idOf, d->status, d->statusP, d->d_counters + CTR_RECIP);
+    else hipLaunchKernelGGL(k_recip_cond<false>, dim3(grid_for(N, 256 * COND_PER_THREAD)), dim3(256), 0, d->stream, N, d->right, d->left, d->conn, d->cflag, d->idOf, d->status, d->statusP, d->d_counters + CTR_RECIP);
+    d->statusByIdValid = eager; d->statusGen++; d->unresGen = 0;
     HIPCHK(hipEventRecord(d->ev[4], d->stream));
     if (d->diet && emit_hi > emit_lo) {                                     // the list is sized by a counting pass (capacity 0: nothing is written, the cursor counts)
         hipLaunchKernelGGL(k_recip_emit, dim3(grid_for(emit_hi - emit_lo, 256 * EMIT_PER_THREAD)), dim3(256), 0, d->stream, N, d->readsLoc, d->S, d->uniL, d->right, d->left, d->statusP, d->idOf, (EdgeCand*)nullptr, (u64)0, d->d_counters + CTR_RECIP, (u64)emit_lo, (u64)emit_hi);
@@ -1201,7 +1223,7 @@ int dev_reciprocal(Device* d, uint64_t emit_lo, uint64_t emit_hi, uint64_t* n_ov
     float ms = 0; hipEventElapsedTime(&ms, d->ev[0], d->ev[1]); d->tm.reciprocal_ms += ms;
     hipEventElapsedTime(&ms, d->ev[0], d->ev[4]); d->tm.recip_cond_ms += ms;
     if (c[0] > d->cand_cap) { err = "edge candidate buffer overflow"; return SAGE2OV_ERR_INTERNAL; }
-    d->n_cand = c[0]; *n_ov = c[1]; *contained = c[2]; *contained_size = c[3];
+    d->n_cand = c[0]; *n_ov = c[1]; *contained = c[2]; *contained_size = c[3]; d->nUnres = c[4];
     return 0;
 }
 
@@ -1218,34 +1240,39 @@ int dev_download_initial(Device* d, uint64_t* right, uint64_t* left, uint8_t* st
         if (left) HIPCHK(hipMemcpy(left, li, (N + 1) * sizeof(u64), hipMemcpyDeviceToHost));
         if (conn) HIPCHK(hipMemcpy(conn, ci, (N + 1) * sizeof(u32), hipMemcpyDeviceToHost));
     }
-    if (status) HIPCHK(hipMemcpy(status, d->status, N + 1, hipMemcpyDeviceToHost));
+    if (status) { int rc = ensure_status_by_id(d, err); if (rc) return rc; HIPCHK(hipStreamSynchronize(d->stream)); HIPCHK(hipMemcpy(status, d->status, N + 1, hipMemcpyDeviceToHost)); }
     return 0;
 }
 int dev_download_status(Device* d, std::vector<uint8_t>& status, std::string& err) {
     HIPCHK(hipSetDevice(d->ordinal));
     status.resize(d->N + 1);
+    { int rc = ensure_status_by_id(d, err); if (rc) return rc; } HIPCHK(hipStreamSynchronize(d->stream));
     HIPCHK(hipMemcpy(status.data(), d->status, d->N + 1, hipMemcpyDeviceToHost));
     return 0;
 }
 
-// the unresolved reads (status 0), any order, left in WS_IDS: *ids, *n (a second try with the exact count when the first guess of room was short)
+// the unresolved reads (status 0), any order, left in WS_IDS: *ids, *n.  k_recip_cond counted them, so the list has its size before it is written and a step
+// without any launches nothing; the list is stamped with the statuses it was taken from, and the next caller of the same reciprocal pass gets it as it is.
 static int collect_unresolved(Device* d, u32** ids, u64* n, std::string& err) {
-    u64 cap = 1 << 20;
-    for (int attempt = 0; attempt < 2; attempt++) {
-        WS(buf, u32, WS_IDS, cap);
+    const u64 cnt = d->nUnres;
+    WS(buf, u32, WS_IDS, std::max<u64>(cnt, 1));
+    *ids = buf; *n = cnt;
+    if (d->unresGen == d->statusGen) return 0;
+    d->unresGen = 0;
+    if (cnt) {
         HIPCHK(hipMemsetAsync(d->d_counters + CTR_LIST, 0, sizeof(u64), d->stream));
-        hipLaunchKernelGGL(k_red_unresolved, dim3(grid_for(d->N, 256 * UNRES_PER_THREAD)), dim3(256), 0, d->stream, (u64)d->N, d->status, buf, cap, d->d_counters + CTR_LIST);
-        u64 cnt = 0; { int rc = read_counters(d, CTR_LIST, 1, &cnt, err); if (rc) return rc; }
-        if (cnt <= cap) { *ids = buf; *n = cnt; return 0; }
-        cap = cnt;
+        hipLaunchKernelGGL(k_red_unresolved, dim3(grid_for(d->N, 256 * UNRES_PER_THREAD)), dim3(256), 0, d->stream, (u64)d->N, d->statusP, d->idOf, buf, cnt, d->d_counters + CTR_LIST);
+        u64 got = 0; { int rc = read_counters(d, CTR_LIST, 1, &got, err); if (rc) return rc; }
+        if (got != cnt) { err = "unresolved read count changed"; return SAGE2OV_ERR_INTERNAL; }
     }
-    err = "unresolved id collection failed"; return SAGE2OV_ERR_INTERNAL;
+    d->unresGen = d->statusGen;
+    return 0;
 }
 int dev_unresolved_ids(Device* d, std::vector<uint32_t>& ids, std::string& err) {      // (the list stays in WS_IDS: dev_unresolved_hits probes it)
     HIPCHK(hipSetDevice(d->ordinal));
     ids.clear();
     u32* buf = nullptr; u64 cnt = 0; { int rc = collect_unresolved(d, &buf, &cnt, err); if (rc) return rc; }
-    ids.resize(cnt); if (cnt) HIPCHK(hipMemcpy(ids.data(), buf, cnt * sizeof(u32), hipMemcpyDeviceToHost));
+    ids.resize(cnt); if (cnt) { HIPCHK(hipMemcpyAsync(ids.data(), buf, cnt * sizeof(u32), hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream)); }
     std::sort(ids.begin(), ids.end());
     return 0;
 }
@@ -1328,6 +1355,7 @@ static int reduce_hit_lists(Device* d, ReduceRun& R, std::string& err) {
         // the unresolved reads listed in LOCALITY order (a stable compaction of `order`): their potential lists are then laid out in that
         // order too, so the lists the host's walk visits one after the other sit next to each other in memory (cache lines, TLB)
         WS(flg, u32, WS_RR_IN, N + 2); WS(fpos, u32, WS_RR_WIDX, N + 2);
+        { int rc = ensure_status_by_id(d, err); if (rc) return rc; }
         hipLaunchKernelGGL(k_rr_unres_flag, dim3(grid_for(N, 256)), dim3(256), 0, d->stream, order, (u64)N, d->status, flg);
         u64 cnt2 = 0; { int rc = scan_u32(d, flg, N, fpos, &cnt2, err); if (rc) return rc; }
         if (cnt2 != nun) { err = "unresolved read count changed"; return SAGE2OV_ERR_INTERNAL; }
@@ -1345,6 +1373,7 @@ static int reduce_hit_lists(Device* d, ReduceRun& R, std::string& err) {
         R.dh = d->pre.hits; const u64 pcap = d->pre.cap; u64 used = d->pre.used;
         WS(noneList, u32, WS_PRE_NONE, N + 2);
         HIPCHK(hipMemsetAsync(d->d_counters + CTR_FILTER, 0, 2 * sizeof(u64), d->stream));
+        { int rc = ensure_status_by_id(d, err); if (rc) return rc; }
         hipLaunchKernelGGL(k_hits_filter, dim3((unsigned)std::min<u64>((N + 3) / 4, 256ull * 64)), dim3(256), 0, d->stream, R.dh, d->pre.base, d->status, d->statusP, d->idOf, d->posOf, (u64)N, hitcount, noneList, d->d_counters + CTR_FILTER);
         u64 fc[2] = {0, 0}; { int rc = read_counters(d, CTR_FILTER, 2, fc, err); if (rc) return rc; }
         HIPCHK(hipGetLastError());
@@ -1377,6 +1406,7 @@ static int reduce_cand_degrees(Device* d, ReduceRun& R, std::string& err) {
     const u64 N = d->N, nc = d->n_cand;
     WS(deg, u32, WS_RA_DEG, N + 2); WS(offs, u32, WS_RA_OFF, N + 2); WS(cur, u32, WS_CURSOR, N + 2); R.deg = deg; R.offs = offs; R.cur = cur;
     HIPCHK(hipMemsetAsync(deg, 0, (N + 2) * sizeof(u32), d->stream)); HIPCHK(hipMemsetAsync(cur, 0, (N + 2) * sizeof(u32), d->stream));
+    { int rc = ensure_status_by_id(d, err); if (rc) return rc; }
     if (nc) hipLaunchKernelGGL(k_ra_degree_c, dim3(grid_for(nc, 256)), dim3(256), 0, d->stream, d->cand, (u64)nc, d->status, deg);
     HIPCHK(hipMemsetAsync(d->d_counters + CTR_RANKED, 0, 4 * sizeof(u64), d->stream));
     return 0;
@@ -1457,6 +1487,7 @@ static int rank_walk_setup(Device* d, ReduceRun& R, std::vector<u32>& posOf, std
     // (all four instead of what the slices used, which the host has by now: WS_RR_IN incount, WS_RR_WIDX widx, WS_RR_CUR the fill cursors, WS_RR_DEGP degp)
     WS(sflg, u32, WS_RR_IN, N + 2); WS(sfpos, u32, WS_RR_WIDX, N + 2); WS(sout, u32, WS_RR_CUR, N + 2); WS(pout, u32, WS_RR_DEGP, nun + 2);
     hipLaunchKernelGGL(k_ids_to_pos, dim3(grid_for(nun, 256)), dim3(256), 0, d->stream, R.ids, (u64)nun, d->posOf, pout);
+    { int rc = ensure_status_by_id(d, err); if (rc) return rc; }
     hipLaunchKernelGGL(k_rr_start_flag, dim3(grid_for(N, 256)), dim3(256), 0, d->stream, (u64)N, d->status, sflg);
     u64 cnt3 = 0; { int rc = scan_u32(d, sflg, N, sfpos, &cnt3, err); if (rc) return rc; }
     if (cnt3 != nun) { err = "unresolved read count changed"; return SAGE2OV_ERR_INTERNAL; }
@@ -1609,6 +1640,7 @@ int dev_collect_reduce_edges(Device* d, const std::vector<uint32_t>& unresolved,
     const u32 nUn = (u32)std::min<size_t>(unresolved.size(), 1u << 30);
     if (nUn && nUn <= FEW_MAX / 3 && !d->opt.get("SAGE2OV_TEST_GENERAL_COLLECT")) {
         // a handful of unresolved reads (see k_red_collect_few): the short list = these reads + their two extension partners, found from their records
+        d->unresGen = 0;                                                   // (WS_IDS is taken: it lists the short list from here on)
         WS(dIds, u32, WS_IDS, 4 * (u64)FEW_MAX); WS(dRec, u64, WS_NEED, 2 * (u64)nUn + 2);
         u32* dNeed = dIds + FEW_MAX;
         HIPCHK(hipMemcpyAsync(dIds, unresolved.data(), nUn * sizeof(u32), hipMemcpyHostToDevice, d->stream));
@@ -1630,6 +1662,7 @@ int dev_collect_reduce_edges(Device* d, const std::vector<uint32_t>& unresolved,
             return 0;
         }
     }
+    { int rc = ensure_status_by_id(d, err); if (rc) return rc; }
     WS(need, uint8_t, WS_NEED, d->N + 1); HIPCHK(hipMemsetAsync(need, 0, d->N + 1, d->stream));
     hipLaunchKernelGGL(k_red_mark, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, d->cand, (u64)n, d->status, need);
     // first a dry count (cap 0 keeps the flagging idempotent), then the real collection
@@ -1944,6 +1977,8 @@ int dev_debug_all_hits(Device* d, std::vector<Hit>& hits, std::string& err) {
     const u64 N = d->N; DevTmp tmp;
     uint8_t* saved = tmp.get<uint8_t>(N + 1); if (!saved) { err = "debug hits: out of device memory"; return SAGE2OV_ERR_NOMEM; }
     HIPCHK(hipStreamSynchronize(d->stream));
+    { int rc = ensure_status_by_id(d, err); if (rc) return rc; }           // (the by-id array is the one written here, statusP refreshed from it: both agree, before and after)
+    d->statusGen++; d->unresGen = 0;
     HIPCHK(hipMemcpyAsync(saved, d->status, N + 1, hipMemcpyDeviceToDevice, d->stream));
     HIPCHK(hipMemsetAsync(d->status, 0, N + 1, d->stream));
     u64 cap = std::max<u64>(1 << 16, N * 128);
@@ -2000,13 +2035,16 @@ int dev_convert(Device* d, uint64_t* n_final, std::string& err) {
         { WS(a, u32, WS_PT_K0, 4 * (n + 4)); B.E[0] = a; } { WS(a, u32, WS_PT_K1, 4 * (n + 4)); B.E[1] = a; }
         const u32 ntiles = (u32)((n + PT_TILE - 1) / PT_TILE);
         WS(cnt, u32, WS_PT_CNT, (u64)PT_NB_MAX * std::max<u32>(ntiles, 1) + 2); WS(base, u32, WS_PT_BASE, (u64)PT_NB_MAX * std::max<u32>(ntiles, 1) + 2);
-        WS(keys, u64, WS_KEYS, n); WS(keep, u32, WS_KEEP, n); WS(pos, u32, WS_POS, n);
+        WS(keys, u64, WS_KEYS, n); WS(keep, u32, WS_KEEP, n);
         int cur = 0; int rc = partition_by_window(d, B, 0, (u32)n, 0, N + 2, false, cnt, base, nullptr, &cur, err); if (rc) return rc;
         const EdgeCand* sorted = (const EdgeCand*)B.E[cur];
         hipLaunchKernelGGL(k_conv_group, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, sorted, (u64)n, keys, keep);
-        u64 nf = 0; rc = scan_u32(d, keep, n, pos, &nf, err); if (rc) return rc;
+        // the kept entries in front of every block of SCAN_BLOCK candidates; k_conv_emit ranks the entries within its block itself
+        WS(partial, u64, WS_PARTIAL, scan_partial_words(n));      // (asked for after the sort's scans: they use the same buffer)
+        const u64 nb = scan_block_sums(d, keep, n, partial);
+        u64 nf = 0; HIPCHK(hipMemcpyAsync(&nf, partial + nb, sizeof(u64), hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
         { WS(fe, FinalEdge, WS_FINAL, std::max<u64>(1, nf)); d->final_edges = fe; }
-        hipLaunchKernelGGL(k_conv_emit, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, (u64)n, keys, keep, pos, sorted, d->reads, d->S, d->uniL, d->final_edges);
+        hipLaunchKernelGGL(k_conv_emit, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, d->stream, (u64)n, keys, keep, partial, sorted, d->reads, d->S, d->uniL, d->final_edges);
         HIPCHK(hipGetLastError());
         d->n_final = nf;
         HIPCHK(hipStreamSynchronize(d->stream));
@@ -2015,7 +2053,7 @@ int dev_convert(Device* d, uint64_t* n_final, std::string& err) {
     HIPCHK(hipStreamSynchronize(d->stream));
     float ms = 0; hipEventElapsedTime(&ms, d->ev[0], d->ev[1]); d->tm.convert_ms += ms;
     mem_sample(d);
-    if (d->diet) for (int id : {WS_PT_K0, WS_PT_K1, WS_PT_CNT, WS_PT_BASE, WS_KEYS, WS_KEEP, WS_POS, WS_PARTIAL}) ws_free(d, id);
+    if (d->diet) for (int id : {WS_PT_K0, WS_PT_K1, WS_PT_CNT, WS_PT_BASE, WS_KEYS, WS_KEEP, WS_PARTIAL}) ws_free(d, id);
     *n_final = d->n_final;
     return 0;
 }
