@@ -246,6 +246,81 @@ int sage2ov_graph_simplify(sage2ov_ctx* ctx);
 int sage2ov_simplify_stats_get(const sage2ov_ctx* ctx, sage2ov_simplify_stats* out);
 int sage2ov_graph4_save(sage2ov_ctx* ctx, const char* path);
 
+/* loadOverlapGraphFromFile's role for a graph with composite edges (overlapGraph.cpp:371-443): any P.graph4 / P.graph5 / P.graph6.  The file is parsed on the
+ * host and uploaded into step 4's half-edge and read-list pools, record pairs in file order (pair p = half-edges 2p, 2p+1: the record and its twin).  The
+ * header is handled as sage2ov_graph_load handles it.  `flow` is parsed and NOT kept: none of the calls below reads it (step 5 assigns it and changes no
+ * edge, copycountEstimator.cpp:401-402, :710-711), and sage2ov_graph4_save writes 0 as it always does.  Needs organised reads and a GPU context.
+ * Refused with SAGE2OV_ERR_ARG: a twin that does not mirror its record (end nodes, list length, or a twin list that is not the forward list's read ids in
+ * reverse order); node or read ids above N or 0; a truncated record.  SAGE2OV_ERR_LIMIT: a distPrevious / distNext above the 11-bit field of a list entry.
+ * Afterwards sage2ov_graph4_save and the sage2ov_mates_* calls below work on the loaded graph; sage2ov_graph_simplify is refused (SAGE2OV_ERR_ARG) until
+ * sage2ov_overlap_convert has run again.
+ * A DELIBERATE DIFFERENCE: saveOverlapGraphInFile writes the record pair of a loop edge (from == to) twice -- both halves hang on the one node and pass
+ * `i <= u->ID` (overlapGraph.cpp:354-364) -- as (A, B) and then (B, A).  The reference's loader makes two edges of the two pairs (and its next save four).
+ * Here a loop's record pair that is directly followed by its mirror image is taken for what the writer made of ONE edge: it becomes one pair, so that the
+ * loaded graph is the graph that was saved and load-then-save reproduces the file.  A loop pair without its mirror image is loaded as it stands. */
+int sage2ov_graph_load_composite(sage2ov_ctx* ctx, const char* path);
+
+/* ---- MatePair::meanSdEstimation (matePair.cpp:244-313) over mapReadsToEdges (:387-484), mapReadLocations (:490-569), computeMeanSD (:318-381), as the
+ * reference runs them with ONE thread (its loops insert into shared lists without a lock).  On the device; all quantities are integers.
+ * The graph is the one step 4 left in HBM (sage2ov_graph_simplify) or a loaded one (sage2ov_graph_load_composite).
+ *   A pair p is two half-edges.  E(p) is the half mapReadsToEdges visits first: the one leaving the smaller node id; for a loop the one that comes first in
+ *   the node's newest-first list = the half with the higher index = the second record of the pair as sage2ov_graph4_save writes it the first time.
+ *   READ-TO-EDGE TABLE: one entry per distinct (read, pair) with the read on the pair's lists (end nodes are not on lists): `forward` = the read's locations
+ *   on E's list, `reverse` = on the twin's list, both in list order.  A location is the running sum of distPrevious from the start of the list up to and
+ *   including the read's entry (uint32_t arithmetic), negated when orientation == 0 (:521-524), read as int32_t (:575-609).
+ *   FLAG of a mate entry (from a, to b): 1 (:206), 0 when a and b have an entry for the same pair (:461-481).
+ *   DISTANCES of library L: per mate entry with from < to (once per entry, whatever its count) and per pair both reads have an entry for, when both reads
+ *   have exactly one forward location there (:352): d = | |loc(a)| - |loc(b)| |.
+ *   ESTIMATION (sage2ov_insert_estimate): mu = sd = 5000; up to 10 rounds; a round considers the d < 4 * mu: count, sum = SUM d, sq = SUM (mu - d)^2,
+ *   rmu = sum / count (integer division), rsd = (int)sqrtl((long double)sq / (count - 1)); it is final when |mu - rmu| <= rmu / 100 and |sd - rsd| <= rsd / 100;
+ *   then mu, sd = rmu, rsd.  mean = rmu + average read length, sd = rsd, lower = max(0, mean - 3 sd), upper = mean + 3 sd.
+ * DELIBERATE DIFFERENCES: (1) a round with count < 2 makes the reference divide by zero; here the library gets valid = 0, rounds = the rounds completed before
+ * it, zero mean / sd / bounds, and is left out of the minimum and maximum upper bound.  (2) sq is accumulated exactly (128 bits); the reference's long double
+ * sum is exact only below 2^64, equality with it is claimed below that.  (3) 4 * mu is taken in 64 bits (the reference's int product wraps from mu = 2^29 on).
+ * The pair of a loop edge: see sage2ov_graph_load_composite. */
+typedef struct sage2ov_read_edge {     /* one entry of the read-to-edge table (ReadToEdgeMap, matePair.h) -- 32 bytes */
+    uint32_t read, pair;               /* pair: ordinal of the record pair in the order sage2ov_graph4_save writes (a loop, written twice: the first time) */
+    uint32_t from, to;                 /* of E */
+    uint32_t n_forward, n_reverse;
+    uint32_t location;                 /* the entry's locations start here in the location array: n_forward forward ones, then n_reverse reverse ones */
+    uint8_t  type, pad[3];             /* typeOfEdge of E */
+} sage2ov_read_edge;
+#define SAGE2OV_INSERT_ROUNDS 10
+typedef struct sage2ov_insert {
+    uint32_t valid, rounds, final_round, library;       /* rounds: rounds completed (<= 10); final_round: 1 when the last one met the 1 % rule */
+    uint64_t considered[SAGE2OV_INSERT_ROUNDS];         /* "Mate-pairs considered" per round; with valid = 0, considered[rounds] is the count (0 or 1) that ended it */
+    int64_t  mu[SAGE2OV_INSERT_ROUNDS], sd[SAGE2OV_INSERT_ROUNDS];   /* rmu, rsd per completed round */
+    int64_t  mean, deviation, lower, upper;             /* Mean[L], standardDeviation[L], lowerBoundOfInsert[L], upperBoundOfInsert[L] */
+} sage2ov_insert;
+typedef struct sage2ov_readmap_stats {                  /* of the last sage2ov_mates_map_reads / sage2ov_mates_estimate */
+    uint64_t entries, locations, records;               /* table entries; locations = records = list entries of the alive half-edges */
+    uint64_t mate_entries;                              /* mate entries whose flag was computed, all libraries */
+    uint64_t distances[128];                            /* per library */
+    uint32_t sort_passes, route;                        /* 8-bit radix passes run; SAGE2OV_MATE_ROUTE_DEVICE */
+    uint32_t rounds, reserved;                          /* round launches of the last estimate, all libraries */
+    double scan_ms, records_ms, sort_ms, reduce_ms, join_ms, round_ms;   /* HIP events */
+} sage2ov_readmap_stats;
+/* mapReadsToEdges + mapReadLocations: builds the table from the resident graph and sets the flag of every mate entry present.  SAGE2OV_ERR_ARG without a
+ * step-4 graph, SAGE2OV_ERR_DEVICE on a device-less context.  The table is dropped whenever the graph or the read set changes (reads_*, overlap_convert,
+ * edges_import, graph_simplify, graph_load_composite); after sage2ov_mates_add_* / _clear the flags and distances are recomputed by the next call that needs them. */
+int sage2ov_mates_map_reads(sage2ov_ctx* ctx);
+/* the table in ascending (read, pair): offsets (N + 2 values, may be NULL) as in sage2ov_mates_export; locations: n_locations int32_t.  A buffer that is too
+ * small: SAGE2OV_ERR_ARG, nothing written.  Maps first when the table is stale. */
+int sage2ov_mates_read_edges_count(sage2ov_ctx* ctx, uint64_t* n_entries, uint64_t* n_locations);
+int sage2ov_mates_read_edges_export(sage2ov_ctx* ctx, sage2ov_read_edge* out, uint64_t cap, int32_t* locations, uint64_t cap_locations, uint64_t* offsets);
+/* MatePairInfo::flag of the library's entries, parallel to sage2ov_mates_export's order (sage2ov_mates_count values) */
+int sage2ov_mates_flags_export(sage2ov_ctx* ctx, int library, uint8_t* flags);
+/* the library's distances in mate-entry order, then ascending pair; d may be NULL to size.  *n = their number; cap < *n with d given: SAGE2OV_ERR_ARG */
+int sage2ov_mates_distances_export(sage2ov_ctx* ctx, int library, uint32_t* d, uint64_t cap, uint64_t* n);
+/* meanSdEstimation: maps when the table is stale, then distances and rounds for every library 1 .. the highest in use.  The distances stay in HBM; a round is
+ * one launch that returns count, sum and sq, and the arithmetic is sage2ov_insert_estimate's. */
+int sage2ov_mates_estimate(sage2ov_ctx* ctx);
+int sage2ov_mates_insert_get(const sage2ov_ctx* ctx, int library, sage2ov_insert* out);                       /* after sage2ov_mates_estimate */
+int sage2ov_mates_bounds_get(const sage2ov_ctx* ctx, uint64_t* minimum_upper, uint64_t* maximum_upper);      /* minimumUpperBoundOfInsert, maximumUpperBoundOfInsert (:292-308) */
+int sage2ov_readmap_stats_get(const sage2ov_ctx* ctx, sage2ov_readmap_stats* out);
+/* the round arithmetic alone, on the host: needs no context and no GPU.  out->library is left 0. */
+int sage2ov_insert_estimate(const uint32_t* d, uint64_t n, uint64_t average_read_length, sage2ov_insert* out);
+
 /* diagnostic: table census {occupied, inline, claimed-but-unfilled, zero-tag, entries in short CSR buckets} */
 int sage2ov_debug_table(sage2ov_ctx* ctx, uint64_t* out5);
 /* diagnostic: device memory {free now, total, LOWEST free seen at the library's sampling points since the context was created (end of step 1, the index

@@ -56,6 +56,24 @@ MATE_DTYPE = np.dtype([("from", np.uint32), ("to", np.uint32), ("count", np.uint
                        ("type2", np.uint8), ("library", np.uint8), ("pad", np.uint8, (4,))])
 
 
+# sage2ov_read_edge (32 bytes): one entry of the read-to-edge table
+READ_EDGE_DTYPE = np.dtype([("read", np.uint32), ("pair", np.uint32), ("from", np.uint32), ("to", np.uint32), ("n_forward", np.uint32), ("n_reverse", np.uint32),
+                            ("location", np.uint32), ("type", np.uint8), ("pad", np.uint8, (3,))])
+INSERT_ROUNDS = 10
+
+
+class Insert(C.Structure):
+    _fields_ = [("valid", C.c_uint32), ("rounds", C.c_uint32), ("final_round", C.c_uint32), ("library", C.c_uint32),
+                ("considered", C.c_uint64 * INSERT_ROUNDS), ("mu", C.c_int64 * INSERT_ROUNDS), ("sd", C.c_int64 * INSERT_ROUNDS),
+                ("mean", C.c_int64), ("deviation", C.c_int64), ("lower", C.c_int64), ("upper", C.c_int64)]
+
+
+class ReadMapStats(C.Structure):
+    _fields_ = [("entries", C.c_uint64), ("locations", C.c_uint64), ("records", C.c_uint64), ("mate_entries", C.c_uint64), ("distances", C.c_uint64 * 128),
+                ("sort_passes", C.c_uint32), ("route", C.c_uint32), ("rounds", C.c_uint32), ("reserved", C.c_uint32),
+                ("scan_ms", C.c_double), ("records_ms", C.c_double), ("sort_ms", C.c_double), ("reduce_ms", C.c_double), ("join_ms", C.c_double), ("round_ms", C.c_double)]
+
+
 class OverlapStats(C.Structure):
     _fields_ = [("verified_overlaps", C.c_uint64), ("contained_extension", C.c_uint64), ("contained_size", C.c_uint64),
                 ("left_to_explore", C.c_uint64), ("edges_inserted", C.c_uint64), ("transitive_removed", C.c_uint64),
@@ -142,6 +160,16 @@ def synth_write_fasta(p: SynthParams, path: str):
     rc = lib().sage2ov_synth_write_fasta(C.byref(p), path.encode())
     if rc:
         raise Sage2ovError(rc, "synth_write_fasta")
+
+
+def insert_estimate(d, average_read_length) -> Insert:
+    """the rounds of MatePair::meanSdEstimation over the distances d (uint32), on the host: no context, no GPU"""
+    d = np.ascontiguousarray(d, dtype=np.uint32)
+    out = Insert()
+    rc = lib().sage2ov_insert_estimate(C.c_void_p(d.ctypes.data), C.c_uint64(len(d)), C.c_uint64(average_read_length), C.byref(out))
+    if rc:
+        raise Sage2ovError(rc, "insert_estimate")
+    return out
 
 
 class Context:
@@ -276,6 +304,55 @@ class Context:
         self._chk(lib().sage2ov_mates_stats_get(self._h, C.byref(s)))
         return s
 
+    # ---- MatePair::meanSdEstimation (matePair.cpp:244-569): reads on edges, flags, distances, insert sizes
+    def mates_map_reads(self):
+        """mapReadsToEdges + mapReadLocations over the resident step-4 graph; sets the flag of every mate entry present"""
+        self._chk(lib().sage2ov_mates_map_reads(self._h))
+
+    def read_edges(self):
+        """(entries, locations, offsets): the read-to-edge table (READ_EDGE_DTYPE) in ascending (read, pair); the entries of read a are
+        entries[offsets[a]:offsets[a + 1]]; entry e has locations[e.location : +n_forward] forward and the next n_reverse reverse"""
+        ne, nl = C.c_uint64(0), C.c_uint64(0)
+        self._chk(lib().sage2ov_mates_read_edges_count(self._h, C.byref(ne), C.byref(nl)))
+        out = np.zeros(ne.value, dtype=READ_EDGE_DTYPE)
+        loc = np.zeros(nl.value, dtype=np.int32)
+        offsets = np.zeros(self.reads_stats().unique_reads + 2, dtype=np.uint64)
+        self._chk(lib().sage2ov_mates_read_edges_export(self._h, C.c_void_p(out.ctypes.data), C.c_uint64(ne.value), C.c_void_p(loc.ctypes.data), C.c_uint64(nl.value),
+                                                       C.c_void_p(offsets.ctypes.data)))
+        return out, loc, offsets
+
+    def mates_flags(self, library) -> np.ndarray:
+        """MatePairInfo::flag of the library's entries, parallel to mates(library)"""
+        out = np.zeros(self.mates_count(library), dtype=np.uint8)
+        self._chk(lib().sage2ov_mates_flags_export(self._h, C.c_int(library), C.c_void_p(out.ctypes.data)))
+        return out
+
+    def mates_distances(self, library) -> np.ndarray:
+        n = C.c_uint64(0)
+        self._chk(lib().sage2ov_mates_distances_export(self._h, C.c_int(library), None, C.c_uint64(0), C.byref(n)))
+        out = np.zeros(n.value, dtype=np.uint32)
+        self._chk(lib().sage2ov_mates_distances_export(self._h, C.c_int(library), C.c_void_p(out.ctypes.data), C.c_uint64(n.value), C.byref(n)))
+        return out
+
+    def mates_estimate(self):
+        self._chk(lib().sage2ov_mates_estimate(self._h))
+
+    def mates_insert(self, library) -> Insert:
+        out = Insert()
+        self._chk(lib().sage2ov_mates_insert_get(self._h, C.c_int(library), C.byref(out)))
+        return out
+
+    def mates_bounds(self):
+        """(minimumUpperBoundOfInsert, maximumUpperBoundOfInsert)"""
+        lo, hi = C.c_uint64(0), C.c_uint64(0)
+        self._chk(lib().sage2ov_mates_bounds_get(self._h, C.byref(lo), C.byref(hi)))
+        return int(lo.value), int(hi.value)
+
+    def readmap_stats(self) -> ReadMapStats:
+        s = ReadMapStats()
+        self._chk(lib().sage2ov_readmap_stats_get(self._h, C.byref(s)))
+        return s
+
     # ---- step 2
     def index_build(self):
         self._chk(lib().sage2ov_index_build(self._h))
@@ -341,6 +418,10 @@ class Context:
 
     def graph_load(self, path):
         self._chk(lib().sage2ov_graph_load(self._h, path.encode()))
+
+    def graph_load_composite(self, path):
+        """loadOverlapGraphFromFile for a graph with composite edges (P.graph4 / graph5 / graph6)"""
+        self._chk(lib().sage2ov_graph_load_composite(self._h, os.fsencode(path)))
 
     def graph_save(self, path):
         self._chk(lib().sage2ov_graph_save(self._h, path.encode()))

@@ -87,10 +87,52 @@ public:
         return out;
     }
     sage2ov_mate_stats stats() const { sage2ov_mate_stats s{}; ctx().check(sage2ov_mates_stats_get(ctx().get(), &s)); return s; }
+    // ---- matePair.cpp:244-609: reads on edges, locations, insert sizes.  The graph is the one the context holds after step 4 (OverlapGraph::simplify) or
+    // after OverlapGraph::loadCompositeGraphFromFile.  The members below carry the reference's names; index = library, 0 unused.
+    std::vector<unsigned> Mean, standardDeviation; std::vector<int> upperBoundOfInsert, lowerBoundOfInsert;
+    uint64_t minimumUpperBoundOfInsert = 0, maximumUpperBoundOfInsert = 0;
+    void mapReadsToEdges() { ctx().check(sage2ov_mates_map_reads(ctx().get())); table_ = false; }      // (mapReadLocations' work is done with it)
+    void mapReadLocations() { fetch(); }
+    void meanSdEstimation() {
+        ctx().check(sage2ov_mates_estimate(ctx().get())); table_ = false;
+        const int nl = numberOfLibrary();
+        Mean.assign(nl + 1, 0); standardDeviation.assign(nl + 1, 0); upperBoundOfInsert.assign(nl + 1, 0); lowerBoundOfInsert.assign(nl + 1, 0);
+        for (int l = 1; l <= nl; l++) {
+            const sage2ov_insert i = insert(l);
+            Mean[l] = (unsigned)i.mean; standardDeviation[l] = (unsigned)i.deviation; upperBoundOfInsert[l] = (int)i.upper; lowerBoundOfInsert[l] = (int)i.lower;
+        }
+        ctx().check(sage2ov_mates_bounds_get(ctx().get(), &minimumUpperBoundOfInsert, &maximumUpperBoundOfInsert));
+    }
+    sage2ov_insert insert(int library) const { sage2ov_insert i{}; ctx().check(sage2ov_mates_insert_get(ctx().get(), library, &i)); return i; }
+    // readToEdgeList[readId]: the read's entries in ascending pair; locations(e): forward ones, then reverse ones
+    std::vector<sage2ov_read_edge> readToEdgeList(uint64_t readId) {
+        fetch(); if (readId + 1 >= edgeOffsets_.size()) return {};
+        return std::vector<sage2ov_read_edge>(edges_.begin() + edgeOffsets_[readId], edges_.begin() + edgeOffsets_[readId + 1]);
+    }
+    std::vector<int32_t> locations(const sage2ov_read_edge& e, bool forward) {
+        fetch(); const size_t a = e.location + (forward ? 0 : e.n_forward);
+        return std::vector<int32_t>(locations_.begin() + a, locations_.begin() + a + (forward ? e.n_forward : e.n_reverse));
+    }
+    // findDistanceOnEdge (:575-609) for the edge a table entry stands for (pair = sage2ov_read_edge::pair): {count, locations...} of `read` on E, {0} when it
+    // is not there -- the reference's array with its length in front
+    std::vector<int32_t> findDistanceOnEdge(uint32_t pair, uint64_t read) {
+        for (const sage2ov_read_edge& e : readToEdgeList(read)) if (e.pair == pair) {
+            std::vector<int32_t> out = locations(e, true); out.insert(out.begin(), (int32_t)e.n_forward); return out;
+        }
+        return {0};
+    }
     ReadLoader* loaderObj;
 private:
     Context& ctx() const { return loaderObj->context(); }
+    void fetch() {
+        if (table_) return;
+        uint64_t ne = 0, nl = 0; ctx().check(sage2ov_mates_read_edges_count(ctx().get(), &ne, &nl));
+        sage2ov_read_stats rs{}; ctx().check(sage2ov_reads_stats(ctx().get(), &rs));
+        edges_.assign(ne, sage2ov_read_edge{}); locations_.assign(nl, 0); edgeOffsets_.assign(rs.unique_reads + 2, 0);
+        ctx().check(sage2ov_mates_read_edges_export(ctx().get(), edges_.data(), ne, locations_.data(), nl, edgeOffsets_.data())); table_ = true;
+    }
     std::vector<sage2ov_mate> entries_; std::vector<uint64_t> offsets_; int cachedLibrary_ = 0;
+    std::vector<sage2ov_read_edge> edges_; std::vector<int32_t> locations_; std::vector<uint64_t> edgeOffsets_; bool table_ = false;
 };
 
 // HashTable (hashTable.h:20-43)
@@ -125,6 +167,7 @@ public:
     void loadOverlapGraphFromFile(const std::string& path) { ctx_->check(sage2ov_graph_load(ctx_->get(), path.c_str())); }
     // step 4: the loop of main.cpp:150-172 over contractCompositePaths / removeDeadEnds / removeBubbles (simplification.cpp), on the device
     sage2ov_simplify_stats simplify() { ctx_->check(sage2ov_graph_simplify(ctx_->get())); sage2ov_simplify_stats s{}; ctx_->check(sage2ov_simplify_stats_get(ctx_->get(), &s)); return s; }
+    void loadCompositeGraphFromFile(const std::string& path) { ctx_->check(sage2ov_graph_load_composite(ctx_->get(), path.c_str())); }   // overlapGraph.cpp:371 for P.graph4 / 5 / 6
     void saveSimplifiedGraphInFile(const std::string& path) { ctx_->check(sage2ov_graph4_save(ctx_->get(), path.c_str())); }   // what step 5 loads (main.cpp:196)
     EconomyGraph* economyObj;
 private:

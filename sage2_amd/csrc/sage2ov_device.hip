@@ -78,6 +78,7 @@ struct Device {
     u64* d_runStarts = nullptr; u64* h_runStarts = nullptr; hipEvent_t evRunStarts = nullptr; bool runStartsValid = false; double runStartFrac = 0.0;      // share of the reads without a predecessor in the locality order (counted by k_loc_index into d_runStarts)
     u64* reads = nullptr;        // (N+1)*S words, slot i = read id i
     Mates* mates = nullptr;      // the mate-pair table (dev_mates_add): allocations of its own, dropped with the read set
+    void* readmap = nullptr;     // the read-to-edge table, the mate flags and the distances (dev_readmap_build; ReadMap): allocations of its own, dropped with the graph and the read set
     u32* findDir = nullptr; int findDirBits = 0;      // read-id lookup (dev_find_ids): first id per value of the top bits of word 0, built by the first call, dropped with the read set
     // the same reads in LOCALITY order (slot p = the read at position p of the order by global minimiser): what the index entries point at and
     // what the probe kernels gather from -- a read's overlap partners are neighbours in the genome, hence (mostly) neighbours here
@@ -225,6 +226,7 @@ static void mem_sample(Device* d) { size_t fr = 0, to = 0; if (hipMemGetInfo(&fr
 #include "kernels_simplify.inc"
 #include "kernels_find.inc"
 #include "kernels_mates.inc"
+#include "kernels_readmap.inc"
 
 // =============================================================================================
 // host primitives: what the launchers below share (grids, counters, transient buffers, a stream timer, scan, radix sort, heads)
@@ -368,6 +370,7 @@ Device* dev_create(int ordinal, const Options& opt, std::string& err) {
 }
 static void mates_release(Device* d);
 static void free_reads(Device* d) {
+    dev_readmap_release(d);                                             // (read ids again)
     rr_staging_release(d);                     // (pinned host buffers sized by the previous read set)
     hipFree(d->reads);
     hipFree(d->findDir); d->findDir = nullptr; d->findDirBits = 0;      // (the lookup directory describes the read set that goes)
@@ -2081,7 +2084,7 @@ struct S4Mem {                                   // released on every exit path 
 }
 #define S4GET(var, type, n) type* var = mem.get<type>((n), err); if (!var) return SAGE2OV_ERR_NOMEM;
 struct S4Keep { S4Mem mem; S4Graph g; u32 nh = 0; u64 listUsed = 0; };
-void dev_simplify_release(Device* d) { if (d->s4keep) { hipSetDevice(d->ordinal); delete (S4Keep*)d->s4keep; d->s4keep = nullptr; } }
+void dev_simplify_release(Device* d) { dev_readmap_release(d); if (d->s4keep) { hipSetDevice(d->ordinal); delete (S4Keep*)d->s4keep; d->s4keep = nullptr; } }
 
 int dev_simplify(Device* d, SimplifiedGraph& out, std::string& err) {
     HIPCHK(hipSetDevice(d->ordinal));
@@ -2302,6 +2305,194 @@ int dev_simplify_download(Device* d, SimplifiedGraph& out, std::string& err) {
     }
     if (k.listUsed) HIPCHK(hipMemcpy(out.lists.data(), g.lists, k.listUsed * sizeof(u64), hipMemcpyDeviceToHost));
     out.downloaded = true;
+    return 0;
+}
+
+// a graph that was parsed from a file (sage2ov_graph_load_composite) takes the place of step 4's result: the half-edge arrays and the list pool, nothing else
+int dev_simplify_upload(Device* d, const SimplifiedGraph& in, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    dev_simplify_release(d);
+    const u64 nh64 = in.n_half_edges, nl = in.lists.size();
+    if (nh64 >= (1ull << 32) - RS_TILE || nl >= (1ull << 32) - RS_TILE) { err = "graph load: too many edges or list entries"; return SAGE2OV_ERR_LIMIT; }
+    std::unique_ptr<S4Keep> keep(new S4Keep());
+    S4Mem& mem = keep->mem; S4Graph& g = keep->g; mem.d = d; g = S4Graph();
+    const u32 nh = (u32)nh64;
+    { S4GET(a, u32, nh) g.from = a; } { S4GET(a, u32, nh) g.to = a; } { S4GET(a, u32, nh) g.len = a; } { S4GET(a, u32, nh) g.cnt = a; } { S4GET(a, u32, nh) g.off = a; }
+    { S4GET(a, uint8_t, nh) g.type = a; } { S4GET(a, uint8_t, nh) g.alive = a; } { S4GET(a, u64, nl) g.lists = a; }
+    if (nh) {
+        HIPCHK(hipMemcpy(g.from, in.from.data(), nh * sizeof(u32), hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(g.to, in.to.data(), nh * sizeof(u32), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(g.len, in.len.data(), nh * sizeof(u32), hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(g.cnt, in.cnt.data(), nh * sizeof(u32), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(g.off, in.off.data(), nh * sizeof(u32), hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(g.type, in.type.data(), nh, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(g.alive, in.alive.data(), nh, hipMemcpyHostToDevice));
+    }
+    if (nl) HIPCHK(hipMemcpy(g.lists, in.lists.data(), nl * sizeof(u64), hipMemcpyHostToDevice));
+    keep->nh = nh; keep->listUsed = nl;
+    d->s4keep = keep.release();
+    return 0;
+}
+
+// =============================================================================================
+// the read-to-edge table, the mate flags, the distances and the rounds (kernels_readmap.inc; MatePair::meanSdEstimation, matePair.cpp:244-569)
+// =============================================================================================
+struct ReadMapLib { unsigned char* flag = nullptr; u32 *dist = nullptr, *dEntry = nullptr, *dPair = nullptr; u64 nflag = 0, nd = 0; bool joined = false; };
+static void readmap_drop_join(ReadMapLib& L) { hipFree(L.flag); hipFree(L.dist); hipFree(L.dEntry); hipFree(L.dPair); L = ReadMapLib(); }
+struct ReadMap {
+    u32 *eRead = nullptr, *ePair = nullptr, *eNf = nullptr, *eNr = nullptr, *eLoc = nullptr, *readOff = nullptr; int* locs = nullptr; u64 E = 0, R = 0; ReadMapLib lib[128];
+    ~ReadMap() { for (auto& L : lib) readmap_drop_join(L); hipFree(eRead); hipFree(ePair); hipFree(eNf); hipFree(eNr); hipFree(eLoc); hipFree(readOff); hipFree(locs); }
+};
+void dev_readmap_drop_joins(Device* d) { if (!d->readmap) return; hipSetDevice(d->ordinal); for (auto& L : ((ReadMap*)d->readmap)->lib) readmap_drop_join(L); }
+void dev_readmap_release(Device* d) { if (d->readmap) { hipSetDevice(d->ordinal); delete (ReadMap*)d->readmap; d->readmap = nullptr; } }
+static int readmap_nomem(std::string& err) { err = "read-to-edge table: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+template <class T> static T* readmap_alloc(u64 n) { return (T*)DevTmp::alloc(std::max<u64>(n, 1) * sizeof(T)); }
+// the 8-bit digits of a record key (read:30 | pair:31 | side:1) that can be non-zero: side and pair end at bit 1 + bits(pairs), the read at 32 + bits(N)
+static int readmap_passes(u64 N, u64 pairs, int* shifts) {
+    int b = 0; while ((N >> b) != 0) b++;
+    int bp = 0; while ((pairs >> bp) != 0) bp++;
+    int np = 0;
+    for (int p = 0; p < 8; p++) { const int lo = 8 * p; if (lo < 1 + bp || (lo >= 32 && lo < 32 + b)) shifts[np++] = lo; }
+    return np;
+}
+int dev_readmap_build(Device* d, ReadMapStats* st, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    if (!d->s4keep) { err = "read-to-edge table: no step-4 graph on the device"; return SAGE2OV_ERR_ARG; }
+    if (d->N >= (1ull << 30)) { err = "read-to-edge table: read ids beyond 2^30 - 1"; return SAGE2OV_ERR_LIMIT; }
+    dev_readmap_release(d);
+    const S4Keep& K = *(S4Keep*)d->s4keep; const S4Graph& g = K.g; const u32 nh = K.nh; const u64 nl = K.listUsed;
+    if (nl >= (1ull << 32) - RS_TILE) { err = "read-to-edge table: more than 2^32 list entries"; return SAGE2OV_ERR_LIMIT; }
+    std::unique_ptr<ReadMap> M(new ReadMap());
+    DevTmp B; StreamLap lap(d->stream); HIPCHK(lap.create());
+    M->readOff = readmap_alloc<u32>(d->N + 2); if (!M->readOff) return readmap_nomem(err);
+    // ---- locations: one scan of distPrevious over the whole pool
+    HIPCHK(lap.start());
+    u32* dprev = B.get<u32>(nl); u32* scan = B.get<u32>(nl); u64* partial = B.get<u64>(scan_partial_words(std::max<u64>(nl, nh)));
+    u32* cnt = B.get<u32>(nh); u32* recOff = B.get<u32>(nh);
+    if (!dprev || !scan || !partial || !cnt || !recOff) return readmap_nomem(err);
+    if (nl) hipLaunchKernelGGL(k_rm_dprev, dim3(grid_for_capped(nl, 256)), dim3(256), 0, d->stream, g.lists, nl, dprev);
+    { const int rc = scan_u32(d, dprev, nl, scan, partial, nullptr, err); if (rc) return rc; }
+    HIPCHK(lap.stop(st->scan_ms));
+    // ---- records
+    HIPCHK(lap.start());
+    if (nh) hipLaunchKernelGGL(k_rm_count, dim3(grid_for(nh, 256)), dim3(256), 0, d->stream, g, nh, cnt);
+    u64 R = 0; { const int rc = scan_u32(d, cnt, nh, recOff, partial, &R, err); if (rc) return rc; }
+    if (R >= (1ull << 32) - RS_TILE) { err = "read-to-edge table: more than 2^32 records"; return SAGE2OV_ERR_LIMIT; }
+    st->records = st->locations = R;
+    if (!R) {                                                                        // a graph of simple edges maps nothing
+        HIPCHK(hipMemsetAsync(M->readOff, 0, (d->N + 2) * sizeof(u32), d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
+        d->readmap = M.release(); return 0;
+    }
+    u64* key = B.get<u64>(R); u32* loc = B.get<u32>(R);
+    if (!key || !loc) return readmap_nomem(err);
+    hipLaunchKernelGGL(k_rm_records, dim3(grid_for(R, 256)), dim3(256), 0, d->stream, g, nh, recOff, (u32)R, scan, nl, key, loc);
+    HIPCHK(hipGetLastError());
+    HIPCHK(lap.stop(st->records_ms));
+    B.release(dprev); B.release(scan); B.release(cnt); B.release(recOff); B.release(partial);
+    // ---- sort by (read, pair, side)
+    HIPCHK(lap.start());
+    int shifts[8]; const int np = readmap_passes(d->N, nh / 2, shifts);
+    u64* ks = nullptr; u32* vs = nullptr; MateStats ms;
+    { const int rc = mate_sort(d, B, key, (u32)R, shifts, np, &ks, &vs, &ms, err); if (rc) return rc; }
+    st->passes = ms.passes;
+    HIPCHK(lap.stop(st->sort_ms));
+    // ---- reduce: heads over (read, pair), entries, locations in sorted order, per-read offsets
+    HIPCHK(lap.start());
+    u32* flag = B.get<u32>(R); u32* pos = B.get<u32>(R); u64* partial2 = B.get<u64>(scan_partial_words(R));
+    if (!flag || !pos || !partial2) return readmap_nomem(err);
+    hipLaunchKernelGGL(k_rm_heads, dim3(grid_for(R, 256)), dim3(256), 0, d->stream, ks, (u32)R, flag);
+    u64 E = 0; { const int rc = scan_u32(d, flag, R, pos, partial2, &E, err); if (rc) return rc; }
+    u32* hp = B.get<u32>(E + 1); if (!hp) return readmap_nomem(err);
+    { const int rc = head_positions(d, flag, pos, R, hp, E, err); if (rc) return rc; }
+    M->eRead = readmap_alloc<u32>(E); M->ePair = readmap_alloc<u32>(E); M->eNf = readmap_alloc<u32>(E); M->eNr = readmap_alloc<u32>(E); M->eLoc = readmap_alloc<u32>(E); M->locs = readmap_alloc<int>(R);
+    if (!M->eRead || !M->ePair || !M->eNf || !M->eNr || !M->eLoc || !M->locs) return readmap_nomem(err);
+    hipLaunchKernelGGL(k_rm_entries, dim3(grid_for(E, 256)), dim3(256), 0, d->stream, ks, hp, (u32)E, M->eRead, M->ePair, M->eNf, M->eNr, M->eLoc);
+    hipLaunchKernelGGL(k_rm_gather, dim3(grid_for(R, 256)), dim3(256), 0, d->stream, vs, loc, (u32)R, M->locs);
+    hipLaunchKernelGGL(k_rm_offsets, dim3(grid_for(d->N + 2, 256)), dim3(256), 0, d->stream, M->eRead, (u32)E, (u32)d->N, M->readOff);
+    HIPCHK(hipGetLastError());
+    HIPCHK(lap.stop(st->reduce_ms));
+    M->E = E; M->R = R; st->entries = E;
+    d->readmap = M.release();
+    return 0;
+}
+// flags of the library's mate entries, and its distances (left in HBM for the rounds)
+int dev_readmap_join(Device* d, int library, ReadMapStats* st, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    if (!d->readmap) { err = "read-to-edge table: not built"; return SAGE2OV_ERR_INTERNAL; }
+    ReadMap* M = (ReadMap*)d->readmap; ReadMapLib& J = M->lib[library];
+    if (J.joined) return 0;
+    readmap_drop_join(J);
+    static const MateLib none; const MateLib& L = d->mates ? d->mates->lib[library] : none;
+    if (!L.n) { J.joined = true; return 0; }
+    if (L.n >= (1ull << 32) / RM_GROUP) { err = "read-to-edge table: too many mate entries in one library"; return SAGE2OV_ERR_LIMIT; }
+    const u32 n = (u32)L.n;
+    DevTmp B; StreamLap lap(d->stream); HIPCHK(lap.create());
+    HIPCHK(lap.start());
+    u32* dcount = B.get<u32>(n); u32* dpos = B.get<u32>(n); u64* partial = B.get<u64>(scan_partial_words(n));
+    J.flag = readmap_alloc<unsigned char>(n);
+    if (!dcount || !dpos || !partial || !J.flag) { readmap_drop_join(J); return readmap_nomem(err); }
+    const RmTable T = {M->readOff, M->ePair, M->eNf, M->eLoc, M->locs, (u32)d->N};
+    const dim3 grid(grid_for((u64)n * RM_GROUP, 256)), block(256);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rm_join<false>), grid, block, 0, d->stream, L.key, n, T, J.flag, dcount, (const u32*)nullptr, (u32*)nullptr, (u32*)nullptr, (u32*)nullptr);
+    u64 nd = 0; { const int rc = scan_u32(d, dcount, n, dpos, partial, &nd, err); if (rc) { readmap_drop_join(J); return rc; } }
+    if (nd) {
+        J.dist = readmap_alloc<u32>(nd); J.dEntry = readmap_alloc<u32>(nd); J.dPair = readmap_alloc<u32>(nd);
+        if (!J.dist || !J.dEntry || !J.dPair) { readmap_drop_join(J); return readmap_nomem(err); }
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rm_join<true>), grid, block, 0, d->stream, L.key, n, T, (unsigned char*)nullptr, (u32*)nullptr, (const u32*)dpos, J.dist, J.dEntry, J.dPair);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(lap.stop(st->join_ms));
+    J.nflag = n; J.nd = nd; J.joined = true;
+    return 0;
+}
+// one round of computeMeanSD over the library's distances: out = {count, sum, sq low, sq high} of the d < thr
+int dev_readmap_round(Device* d, int library, long long mu, uint64_t thr, uint64_t out[4], ReadMapStats* st, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (!d->readmap) { err = "read-to-edge table: not built"; return SAGE2OV_ERR_INTERNAL; }
+    const ReadMapLib& J = ((ReadMap*)d->readmap)->lib[library];
+    if (!J.nd) return 0;
+    const unsigned blocks = (unsigned)std::min<u64>(grid_for(J.nd, 256), 1024);
+    DevTmp B; u64* partial = B.get<u64>(4ull * blocks); if (!partial) return readmap_nomem(err);
+    StreamLap lap(d->stream); HIPCHK(lap.create()); HIPCHK(lap.start());
+    hipLaunchKernelGGL(k_rm_round, dim3(blocks), dim3(256), 0, d->stream, J.dist, J.nd, (u64)thr, mu, partial);
+    HIPCHK(hipGetLastError());
+    std::vector<u64> h(4ull * blocks);
+    HIPCHK(hipMemcpyAsync(h.data(), partial, h.size() * sizeof(u64), hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(lap.stop(st->round_ms));
+    unsigned __int128 sq = 0;
+    for (unsigned b = 0; b < blocks; b++) { out[0] += h[4 * b]; out[1] += h[4 * b + 1]; sq += ((unsigned __int128)h[4 * b + 3] << 64) | h[4 * b + 2]; }
+    out[2] = (u64)sq; out[3] = (u64)(sq >> 64);
+    st->rounds++;
+    return 0;
+}
+void dev_readmap_counts(Device* d, uint64_t* entries, uint64_t* locations) { const ReadMap* M = (const ReadMap*)d->readmap; *entries = M ? M->E : 0; *locations = M ? M->R : 0; }
+// the table as it lies on the device: entries arrays of E values, locations of R, offsets of N + 2
+int dev_readmap_export(Device* d, uint32_t* read, uint32_t* pair, uint32_t* nf, uint32_t* nr, uint32_t* loc, int32_t* locs, uint32_t* offsets, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    const ReadMap* M = (const ReadMap*)d->readmap; if (!M) { err = "read-to-edge table: not built"; return SAGE2OV_ERR_INTERNAL; }
+    if (M->E) {
+        HIPCHK(hipMemcpy(read, M->eRead, M->E * sizeof(u32), hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(pair, M->ePair, M->E * sizeof(u32), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(nf, M->eNf, M->E * sizeof(u32), hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(nr, M->eNr, M->E * sizeof(u32), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(loc, M->eLoc, M->E * sizeof(u32), hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(locs, M->locs, M->R * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    HIPCHK(hipMemcpy(offsets, M->readOff, (d->N + 2) * sizeof(u32), hipMemcpyDeviceToHost));
+    return 0;
+}
+uint64_t dev_readmap_flag_count(Device* d, int library) { const ReadMap* M = (const ReadMap*)d->readmap; return M ? M->lib[library].nflag : 0; }
+uint64_t dev_readmap_distance_count(Device* d, int library) { const ReadMap* M = (const ReadMap*)d->readmap; return M ? M->lib[library].nd : 0; }
+int dev_readmap_flags(Device* d, int library, uint8_t* out, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    const ReadMap* M = (const ReadMap*)d->readmap; if (!M) { err = "read-to-edge table: not built"; return SAGE2OV_ERR_INTERNAL; }
+    const ReadMapLib& J = M->lib[library];
+    if (J.nflag) HIPCHK(hipMemcpy(out, J.flag, J.nflag, hipMemcpyDeviceToHost));
+    return 0;
+}
+int dev_readmap_distances(Device* d, int library, uint32_t* dist, uint32_t* entry, uint32_t* pair, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    const ReadMap* M = (const ReadMap*)d->readmap; if (!M) { err = "read-to-edge table: not built"; return SAGE2OV_ERR_INTERNAL; }
+    const ReadMapLib& J = M->lib[library];
+    if (J.nd) {
+        HIPCHK(hipMemcpy(dist, J.dist, J.nd * sizeof(u32), hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(entry, J.dEntry, J.nd * sizeof(u32), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(pair, J.dPair, J.nd * sizeof(u32), hipMemcpyDeviceToHost));
+    }
     return 0;
 }
 

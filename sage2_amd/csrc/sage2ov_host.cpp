@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <parallel/algorithm>
@@ -112,7 +113,15 @@ struct sage2ov_ctx {
     uint64_t matePairs[128] = {};                      // pairs given to each library so far, skipped ones included: the base of the record ordinals
     uint32_t mateLibraries = 0;                        // highest library in use (numberOfLibrary)
     sage2ov_mate_stats mstats{};                       // of the last add call
-    void mates_forget() {                              // the read set goes: its ids mean nothing any more (the device drops its part in free_reads)
+    // ---- the read-to-edge table, flags, distances and insert sizes (sage2ov_mates_map_reads / _estimate): the data live on the device
+    bool rmValid = false, estimated = false;           // the table describes the resident graph; inserts / bounds are of the present table and mates
+    sage2ov_readmap_stats rmstats{};
+    std::vector<sage2ov_insert> inserts = std::vector<sage2ov_insert>(128); uint64_t minUpper = 0, maxUpper = 0;
+    std::vector<uint32_t> pairOrdinal;                 // internal pair -> ordinal of its record pair in sage2ov_graph4_save's order (filled by the exports)
+    uint64_t readsGen = 0, g4Gen = 0;                  // stamps of the read set and of the read set the step-4 graph was made from: the table is built only when they agree
+    void readmap_forget() { rmValid = estimated = false; pairOrdinal.clear(); rmstats = sage2ov_readmap_stats{}; }      // the graph or the read set goes
+    void mates_forget(bool readSetGoes = true) {       // the read set goes: its ids mean nothing any more (the device drops its part in free_reads) -- or sage2ov_mates_clear
+        if (readSetGoes) { readmap_forget(); readsGen++; } else estimated = false;
         for (auto& L : mates) L = MateLib();
         for (int i = 0; i < 128; i++) { mateOnDevice[i] = false; matePairs[i] = 0; }
         mateLibraries = 0; mstats = sage2ov_mate_stats{};
@@ -1080,6 +1089,7 @@ int mates_batch(sage2ov_ctx* c, MateCall& M, const char* bases, const uint64_t* 
 }
 int mates_end(sage2ov_ctx* c, MateCall& M, int rc) {
     const int lib = M.lib;
+    c->estimated = false; if (Device* d = c->device()) dev_readmap_drop_joins(d);      // flags and distances are recomputed by the next call that needs them
     if (M.onDevice) { if (rc == SAGE2OV_OK) rc = dev_mates_flush(c->device(), lib, &M.ds, c->err); if (rc != SAGE2OV_OK) dev_mates_abort(c->device()); }
     else if (rc == SAGE2OV_OK && !M.rec.empty()) {
         __gnu_parallel::sort(M.rec.begin(), M.rec.end(), std::less<std::pair<uint64_t, uint64_t>>(), __gnu_parallel::default_parallel_tag(io_threads(c)));
@@ -1207,8 +1217,8 @@ int sage2ov_mates_export(sage2ov_ctx* c, int library, sage2ov_mate* out, uint64_
 }
 int sage2ov_mates_clear(sage2ov_ctx* c) {
     if (!c) return SAGE2OV_ERR_ARG;
-    if (Device* d = c->device()) dev_mates_clear(d);
-    c->mates_forget(); return SAGE2OV_OK;
+    if (Device* d = c->device()) { dev_mates_clear(d); dev_readmap_drop_joins(d); }    // (the read-to-edge table describes the graph, not the mates: it stays)
+    c->mates_forget(false); return SAGE2OV_OK;
 }
 int sage2ov_mates_stats_get(const sage2ov_ctx* c, sage2ov_mate_stats* o) { if (!c || !o) return SAGE2OV_ERR_ARG; *o = c->mstats; return SAGE2OV_OK; }
 int sage2ov_reads_set_totals(sage2ov_ctx* c, uint64_t good, uint64_t bp) { if (!c) return SAGE2OV_ERR_ARG; c->goodReads = good; c->totalBP = bp; return SAGE2OV_OK; }
@@ -1465,7 +1475,9 @@ int sage2ov_overlap_convert(sage2ov_ctx* c) {
     if (!c) return SAGE2OV_ERR_ARG; if (!c->reduced) return c->fail(SAGE2OV_ERR_ARG, "run the reduce phase first");
     if (!c->survivorsExchanged) return c->fail(SAGE2OV_ERR_ARG, "multi-rank context: exchange the survivor buckets of the reduce phase first (sage2ov_shard_survivors_*)");
     uint64_t nf = 0; int rc = dev_convert(c->device(), &nf, c->err); if (rc) return rc;
-    c->ostats.edges = nf; c->edgesOnHost = false; c->converted = true; return SAGE2OV_OK;
+    c->ostats.edges = nf; c->edgesOnHost = false; c->converted = true;
+    c->readmap_forget(); dev_readmap_release(c->device());                             // (the graph the table described is being replaced)
+    return SAGE2OV_OK;
 }
 int sage2ov_overlap_stats_get(const sage2ov_ctx* c, sage2ov_overlap_stats* o) { if (!c || !o) return SAGE2OV_ERR_ARG; *o = c->ostats; return SAGE2OV_OK; }
 int sage2ov_overlap_export_initial(sage2ov_ctx* c, uint64_t* r, uint64_t* l, uint8_t* st, uint32_t* cn) {
@@ -1497,7 +1509,7 @@ int sage2ov_edges_import(sage2ov_ctx* c, const sage2ov_edge* e, uint64_t n) {
         c->edges[x] = FinalEdge{(uint32_t)e[x].from, (uint32_t)e[x].to, e[x].length, e[x].length_twin, e[x].type};
     }
     int rc = dev_upload_edges(c->device(), c->edges, c->err); if (rc) return rc;
-    c->ostats.edges = n; c->edgesOnHost = true; c->converted = true; c->g4Valid = false;
+    c->ostats.edges = n; c->edgesOnHost = true; c->converted = true; c->g4Valid = false; c->readmap_forget(); if (Device* dd = c->device()) dev_readmap_release(dd);
     return SAGE2OV_OK;
 }
 // loadOverlapGraphFromFile (overlapGraph.cpp:371-442) for the graph step 3 writes: simple edges only (list size 0)
@@ -1604,13 +1616,25 @@ int sage2ov_graph_save(sage2ov_ctx* c, const char* path) {                      
 }
 
 // ---- step 4
+namespace {
+// the half-edges sage2ov_graph4_save writes a record pair for, in its order: per node, the alive half-edges with from <= to by ascending index (the writer
+// walks each list from its tail, overlapGraph.cpp:356-358).  Both halves of a loop are among them: its pair is written twice
+void g4_save_order(const SimplifiedGraph& g, std::vector<uint32_t>& order) {
+    const uint64_t N = g.N, nh = g.n_half_edges;
+    std::vector<uint32_t> offs(N + 2, 0);
+    for (uint64_t h = 0; h < nh; h++) if (g.alive[h] && g.from[h] <= g.to[h]) offs[g.from[h] + 1]++;
+    for (uint64_t i = 0; i <= N; i++) offs[i + 1] += offs[i];
+    order.resize(offs[N + 1]);
+    std::vector<uint32_t> cur(offs.begin(), offs.end() - 1); for (uint64_t h = 0; h < nh; h++) if (g.alive[h] && g.from[h] <= g.to[h]) order[cur[g.from[h]]++] = (uint32_t)h;
+}
+}  // namespace
 int sage2ov_graph_simplify(sage2ov_ctx* c) {                                          // main.cpp:139-172
     if (!c) return SAGE2OV_ERR_ARG;
     if (!c->device()) return c->fail(SAGE2OV_ERR_DEVICE, "no GPU context: step 4 runs on the device only");
     if (!c->converted) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_simplify: call sage2ov_overlap_convert first");
-    c->g4Valid = false; c->g4 = SimplifiedGraph();
+    c->g4Valid = false; c->g4 = SimplifiedGraph(); c->readmap_forget();
     int rc = dev_simplify(c->device(), c->g4, c->err); if (rc) return rc;
-    c->g4Valid = true; return SAGE2OV_OK;
+    c->g4Valid = true; c->g4Gen = c->readsGen; return SAGE2OV_OK;
 }
 int sage2ov_simplify_stats_get(const sage2ov_ctx* c, sage2ov_simplify_stats* o) {
     if (!c || !o || !c->g4Valid) return SAGE2OV_ERR_ARG;
@@ -1624,13 +1648,8 @@ int sage2ov_graph4_save(sage2ov_ctx* c, const char* path) {                     
     HostLap lap(c, "graph4");
     { int rc = dev_simplify_download(c->device(), c->g4, c->err); if (rc) return rc; }
     lap("download of the simplified graph");
-    const SimplifiedGraph& g = c->g4; const uint64_t N = g.N, nh = g.n_half_edges;
-    // a node's list, oldest first = its alive half-edges by ascending index (the writer walks each list from its tail, :356-358)
-    std::vector<uint32_t> offs(N + 2, 0), order;
-    for (uint64_t h = 0; h < nh; h++) if (g.alive[h] && g.from[h] <= g.to[h]) offs[g.from[h] + 1]++;
-    for (uint64_t i = 0; i <= N; i++) offs[i + 1] += offs[i];
-    order.resize(offs[N + 1]);
-    { std::vector<uint32_t> cur(offs.begin(), offs.end() - 1); for (uint64_t h = 0; h < nh; h++) if (g.alive[h] && g.from[h] <= g.to[h]) order[cur[g.from[h]]++] = (uint32_t)h; }
+    const SimplifiedGraph& g = c->g4;
+    std::vector<uint32_t> order; g4_save_order(g, order);
     FILE* f = fopen(path, "w"); if (!f) return c->fail(SAGE2OV_ERR_IO, std::string("cannot open ") + path);
     std::vector<char> io(1 << 22); setvbuf(f, io.data(), _IOFBF, io.size());
     fprintf(f, "0\n%llu\n%llu\n", (unsigned long long)c->goodReads, (unsigned long long)(c->goodReads ? c->totalBP / c->goodReads : 0));
@@ -1661,6 +1680,256 @@ int sage2ov_graph4_save(sage2ov_ctx* c, const char* path) {                     
     });
     fclose(f); return rc;
 }
+
+// ---- a graph with composite edges from a file (loadOverlapGraphFromFile, overlapGraph.cpp:371-443); the semantics are stated in sage2ov.h
+int sage2ov_graph_load_composite(sage2ov_ctx* c, const char* path) {
+    if (!c || !path) return SAGE2OV_ERR_ARG;
+    if (!c->device()) return c->fail(SAGE2OV_ERR_DEVICE, c->gpu() && !c->devErr.empty() ? c->devErr : "no GPU context: the loaded graph lives on the device");
+    if (!c->organized) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_load_composite: organise (or load) the reads first");
+    FILE* f = fopen(path, "rb"); if (!f) return c->fail(SAGE2OV_ERR_IO, std::string("cannot open ") + path);
+    std::string txt; { char buf[1 << 16]; size_t n; while ((n = fread(buf, 1, sizeof buf, f)) > 0) txt.append(buf, n); } fclose(f);
+    const char* p = txt.c_str(); const char* end = p + txt.size();
+    auto skip = [&]() { while (p < end && (*p == ' ' || *p == '\t' || *p == '\n' || *p == '\r')) p++; };
+    auto num = [&](unsigned long long& v) -> bool {
+        skip(); if (p >= end || *p < '0' || *p > '9') return false;
+        v = 0; while (p < end && *p >= '0' && *p <= '9') v = v * 10 + (unsigned long long)(*p++ - '0');
+        return p >= end || *p == ' ' || *p == '\t' || *p == '\n' || *p == '\r';
+    };
+    auto real = [&]() -> bool {                                                        // the flow column (a float: "0", "2", "1.5", "1e+06"): parsed, not kept
+        skip(); if (p >= end) return false;
+        char* e = nullptr; (void)strtod(p, &e); if (e == p) return false; p = e; return true;
+    };
+    unsigned long long gs, nr, avg;
+    if (!num(gs) || !num(nr) || !num(avg)) return c->fail(SAGE2OV_ERR_IO, "sage2ov_graph_load_composite: bad header");
+    const uint64_t N = c->N;
+    SimplifiedGraph g; g.N = N;
+    // one record into the pools; 0 ok, 1 clean end of file (only where a record may start), else an error code
+    auto record = [&](bool mayEnd) -> int {
+        unsigned long long v[7];
+        skip(); if (p >= end) return mayEnd ? 1 : c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_load_composite: a record without its twin (truncated file)");
+        for (int x = 0; x < 7; x++) if (x == 5 ? !real() : !num(v[x])) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_load_composite: truncated or malformed record");
+        if (v[0] < 1 || v[0] > N || v[1] < 1 || v[1] > N) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_load_composite: a node id is 0 or above the number of reads");
+        if (v[2] > 3 || v[4] > 0xFFFFFFFFull || v[6] >= (1ull << 32)) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_load_composite: edge type, length or list size out of range");
+        if (g.lists.size() + v[6] >= (1ull << 32)) return c->fail(SAGE2OV_ERR_LIMIT, "sage2ov_graph_load_composite: more than 2^32 list entries");
+        g.from.push_back((uint32_t)v[0]); g.to.push_back((uint32_t)v[1]); g.type.push_back((uint8_t)v[2]); g.len.push_back((uint32_t)v[4]);
+        g.cnt.push_back((uint32_t)v[6]); g.off.push_back((uint32_t)g.lists.size()); g.alive.push_back(1);
+        for (unsigned long long j = 0; j < v[6]; j++) {
+            unsigned long long e[5];
+            for (int x = 0; x < 5; x++) if (!num(e[x])) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_load_composite: truncated or malformed read list");
+            if (e[0] < 1 || e[0] > N) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_load_composite: a read id on a list is 0 or above the number of reads");
+            if (e[1] > 1 || e[2] > 1) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_load_composite: orientation and flag are 0 or 1");
+            if (e[3] > 0x7FF || e[4] > 0x7FF) return c->fail(SAGE2OV_ERR_LIMIT, "sage2ov_graph_load_composite: distPrevious / distNext above 2047 (the 11-bit field of a list entry)");
+            g.lists.push_back(e[0] | (e[1] << 40) | (e[2] << 41) | (e[3] << 42) | (e[4] << 53));
+        }
+        return 0;
+    };
+    auto same = [&](size_t a, size_t b) {                                              // two half-edges with equal fields and equal lists
+        return g.from[a] == g.from[b] && g.to[a] == g.to[b] && g.type[a] == g.type[b] && g.len[a] == g.len[b] && g.cnt[a] == g.cnt[b] &&
+               std::equal(g.lists.begin() + g.off[a], g.lists.begin() + g.off[a] + g.cnt[a], g.lists.begin() + g.off[b]);
+    };
+    auto pop = [&]() { g.lists.resize(g.off.back()); g.from.pop_back(); g.to.pop_back(); g.type.pop_back(); g.len.pop_back(); g.cnt.pop_back(); g.off.pop_back(); g.alive.pop_back(); };
+    uint64_t reads = 0;
+    for (;;) {
+        int rc = record(true); if (rc == 1) break; if (rc) return rc;
+        rc = record(false); if (rc) return rc;
+        const size_t a = g.from.size() - 2, b = a + 1;
+        if (g.from[a] != g.to[b] || g.to[a] != g.from[b]) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_load_composite: a record is not followed by its twin");
+        if (g.cnt[a] != g.cnt[b]) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_load_composite: the twin's list has another length");
+        for (uint32_t x = 0; x < g.cnt[a]; x++)
+            if (((g.lists[(uint64_t)g.off[a] + x] ^ g.lists[(uint64_t)g.off[b] + g.cnt[a] - 1 - x]) & ((1ull << 40) - 1)) != 0)
+                return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_load_composite: the twin's list is not the forward list's read ids in reverse order");
+        // a loop's pair directly after its mirror image: the second writing of one edge (see sage2ov.h)
+        if (a >= 2 && g.from[a] == g.to[a] && g.from[a - 2] == g.to[a - 2] && g.alive[a - 2] == 1 && same(a, a - 1) && same(b, a - 2)) { pop(); pop(); g.alive[a - 2] = g.alive[a - 1] = 2; continue; }
+        reads += g.cnt[a];
+    }
+    for (auto& x : g.alive) x = 1;                                                     // (2 marked a loop pair that has taken its mirror image: a third copy is a pair of its own)
+    g.n_half_edges = g.from.size(); g.pairs_alive = g.n_half_edges / 2; g.reads_on_edges = reads; g.downloaded = true;
+    c->g4Valid = false; c->readmap_forget();
+    { const int rc = dev_simplify_upload(c->device(), g, c->err); if (rc) return rc; }
+    c->g4 = std::move(g); c->g4Valid = true; c->g4Gen = c->readsGen; c->converted = false;                     // (no edge list of step 3 stands behind this graph: graph_simplify is refused)
+    c->goodReads = nr; c->totalBP = avg * nr;
+    return SAGE2OV_OK;
+}
+
+// ---- MatePair::meanSdEstimation (matePair.cpp:244-569); the semantics are stated in sage2ov.h
+namespace {
+typedef unsigned __int128 u128;
+// the rounds of meanSdEstimation (:265-291) over round(mu, count, sum, sq) = computeMeanSD's sums (:318-381) of the d < 4 * mu
+extern "C++" { template <class F>
+int estimate_rounds(F&& round, uint64_t averageReadLength, sage2ov_insert* o) {
+    *o = sage2ov_insert{};
+    int64_t mu = 5000, sd = 5000, rmu = 0, rsd = 0;
+    for (int i = 0; i < SAGE2OV_INSERT_ROUNDS; i++) {
+        uint64_t count = 0, sum = 0; u128 sq = 0;
+        { const int rc = round(mu, count, sum, sq); if (rc) return rc; }
+        o->considered[i] = count;
+        if (count < 2) { o->valid = 0; o->final_round = 0; return SAGE2OV_OK; }        // (the reference divides by zero here)
+        rmu = (int64_t)(sum / count);
+        rsd = (int64_t)sqrtl((long double)sq / (long double)(count - 1));
+        const bool fin = llabs(mu - rmu) <= rmu / 100 && llabs(sd - rsd) <= rsd / 100;
+        mu = rmu; sd = rsd; o->mu[i] = rmu; o->sd[i] = rsd; o->rounds = (uint32_t)(i + 1);
+        if (fin) { o->final_round = 1; break; }
+    }
+    o->valid = 1; o->mean = rmu + (int64_t)averageReadLength; o->deviation = rsd;
+    o->lower = std::max<int64_t>(0, o->mean - 3 * o->deviation); o->upper = o->mean + 3 * o->deviation;
+    return SAGE2OV_OK;
+} }
+uint64_t average_read_length(const sage2ov_ctx* c) { return c->goodReads ? c->totalBP / c->goodReads : 0; }
+int readmap_check(sage2ov_ctx* c, const char* who) {
+    if (!c->device()) return c->fail(SAGE2OV_ERR_DEVICE, c->gpu() && !c->devErr.empty() ? c->devErr : std::string(who) + ": no GPU context: the read-to-edge table is built on the device only");
+    if (!c->g4Valid || c->g4Gen != c->readsGen) return c->fail(SAGE2OV_ERR_ARG, std::string(who) + ": call sage2ov_graph_simplify or sage2ov_graph_load_composite first (on the present read set)");
+    return SAGE2OV_OK;
+}
+void readmap_stats_take(sage2ov_ctx* c, const ReadMapStats& s) {
+    sage2ov_readmap_stats& o = c->rmstats;
+    o.entries = s.entries; o.locations = s.locations; o.records = s.records; o.sort_passes = s.passes; o.route = SAGE2OV_MATE_ROUTE_DEVICE;
+    o.scan_ms = s.scan_ms; o.records_ms = s.records_ms; o.sort_ms = s.sort_ms; o.reduce_ms = s.reduce_ms;
+}
+int readmap_build(sage2ov_ctx* c) {
+    c->rmValid = c->estimated = false; c->rmstats = sage2ov_readmap_stats{};
+    ReadMapStats s; const int rc = dev_readmap_build(c->device(), &s, c->err); if (rc) return rc;
+    readmap_stats_take(c, s); c->rmValid = true; return SAGE2OV_OK;
+}
+// flags and distances of one library (kept on the device until the mate table changes)
+int readmap_join(sage2ov_ctx* c, int lib) {
+    if (!c->mateOnDevice[lib] && !c->mates[lib].key.empty()) { const int rc = mates_place(c, lib, true); if (rc) return rc; }
+    ReadMapStats s; const int rc = dev_readmap_join(c->device(), lib, &s, c->err); if (rc) return rc;
+    c->rmstats.join_ms += s.join_ms; c->rmstats.distances[lib] = dev_readmap_distance_count(c->device(), lib);
+    return SAGE2OV_OK;
+}
+int readmap_ensure(sage2ov_ctx* c, const char* who) {
+    { const int rc = readmap_check(c, who); if (rc) return rc; }
+    return c->rmValid ? SAGE2OV_OK : readmap_build(c);
+}
+// internal pair -> ordinal of its record pair in sage2ov_graph4_save's order (a loop, written twice: the first time)
+int pair_ordinals(sage2ov_ctx* c) {
+    if (!c->pairOrdinal.empty()) return SAGE2OV_OK;
+    { const int rc = dev_simplify_download(c->device(), c->g4, c->err); if (rc) return rc; }
+    std::vector<uint32_t> order; g4_save_order(c->g4, order);
+    c->pairOrdinal.assign(c->g4.n_half_edges / 2 + 1, ~0u);
+    for (size_t x = 0; x < order.size(); x++) { uint32_t& o = c->pairOrdinal[order[x] >> 1]; if (o == ~0u) o = (uint32_t)x; }
+    return SAGE2OV_OK;
+}
+}  // namespace
+int sage2ov_insert_estimate(const uint32_t* d, uint64_t n, uint64_t averageReadLength, sage2ov_insert* out) {
+    if (!out || (n && !d)) return SAGE2OV_ERR_ARG;
+    return estimate_rounds([&](int64_t mu, uint64_t& count, uint64_t& sum, u128& sq) {
+        const uint64_t thr = 4 * (uint64_t)mu;
+        for (uint64_t i = 0; i < n; i++) if (d[i] < thr) { const int64_t df = mu - (int64_t)d[i]; sq += (u128)((__int128)df * df); count++; sum += d[i]; }
+        return 0;
+    }, averageReadLength, out);
+}
+int sage2ov_mates_map_reads(sage2ov_ctx* c) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    { const int rc = readmap_check(c, "sage2ov_mates_map_reads"); if (rc) return rc; }
+    { const int rc = readmap_build(c); if (rc) return rc; }
+    dev_readmap_drop_joins(c->device());
+    for (int lib = 1; lib < 128; lib++) {
+        if (!mates_entries(c, lib)) continue;
+        const int rc = readmap_join(c, lib); if (rc) return rc;
+        c->rmstats.mate_entries += dev_readmap_flag_count(c->device(), lib);
+    }
+    return SAGE2OV_OK;
+}
+int sage2ov_mates_read_edges_count(sage2ov_ctx* c, uint64_t* ne, uint64_t* nl) {
+    if (!c || !ne || !nl) return SAGE2OV_ERR_ARG;
+    { const int rc = readmap_ensure(c, "sage2ov_mates_read_edges_count"); if (rc) return rc; }
+    dev_readmap_counts(c->device(), ne, nl); return SAGE2OV_OK;
+}
+int sage2ov_mates_read_edges_export(sage2ov_ctx* c, sage2ov_read_edge* out, uint64_t cap, int32_t* locations, uint64_t capLoc, uint64_t* offsets) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    { const int rc = readmap_ensure(c, "sage2ov_mates_read_edges_export"); if (rc) return rc; }
+    uint64_t E = 0, R = 0; dev_readmap_counts(c->device(), &E, &R);
+    if (cap < E || capLoc < R) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_mates_read_edges_export: a buffer holds fewer values than the table (sage2ov_mates_read_edges_count)");
+    if ((E && !out) || (R && !locations)) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_mates_read_edges_export: null argument");
+    { const int rc = pair_ordinals(c); if (rc) return rc; }
+    std::vector<uint32_t> rd(E), pr(E), nf(E), nr(E), lo(E), off(c->N + 2); std::vector<int32_t> ls(R);
+    { const int rc = dev_readmap_export(c->device(), rd.data(), pr.data(), nf.data(), nr.data(), lo.data(), ls.data(), off.data(), c->err); if (rc) return rc; }
+    const SimplifiedGraph& g = c->g4; const std::vector<uint32_t>& ord = c->pairOrdinal;
+    // per read: its entries by the ordinal of the pair (the device orders them by the pair's index in the pool); the read's locations keep their stretch
+    #pragma omp parallel for num_threads(io_threads(c)) schedule(dynamic, 4096)
+    for (uint64_t a = 0; a <= c->N; a++) {
+        const uint32_t e0 = off[a], e1 = off[a + 1]; if (e0 == e1) continue;
+        uint32_t idx[8]; std::vector<uint32_t> big; uint32_t* ix = idx;
+        if (e1 - e0 > 8) { big.resize(e1 - e0); ix = big.data(); }
+        for (uint32_t x = 0; x < e1 - e0; x++) ix[x] = e0 + x;
+        std::sort(ix, ix + (e1 - e0), [&](uint32_t x, uint32_t y) { return ord[pr[x]] < ord[pr[y]]; });
+        uint32_t at = lo[e0];
+        for (uint32_t x = 0; x < e1 - e0; x++) {
+            const uint32_t e = ix[x], p = pr[e], h0 = 2 * p, h1 = 2 * p + 1;
+            const uint32_t hE = g.from[h0] < g.to[h0] ? h0 : (g.from[h0] > g.to[h0] ? h1 : h1);
+            sage2ov_read_edge r{}; r.read = rd[e]; r.pair = ord[p]; r.from = g.from[hE]; r.to = g.to[hE]; r.type = g.type[hE]; r.n_forward = nf[e]; r.n_reverse = nr[e]; r.location = at;
+            out[e0 + x] = r;
+            memcpy(locations + at, ls.data() + lo[e], (size_t)(nf[e] + nr[e]) * sizeof(int32_t)); at += nf[e] + nr[e];
+        }
+    }
+    if (offsets) for (uint64_t a = 0; a <= c->N + 1; a++) offsets[a] = off[a];
+    return SAGE2OV_OK;
+}
+int sage2ov_mates_flags_export(sage2ov_ctx* c, int library, uint8_t* flags) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    { const int rc = mates_check(c, "sage2ov_mates_flags_export", library); if (rc) return rc; }
+    { const int rc = readmap_ensure(c, "sage2ov_mates_flags_export"); if (rc) return rc; }
+    { const int rc = readmap_join(c, library); if (rc) return rc; }
+    if (dev_readmap_flag_count(c->device(), library) && !flags) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_mates_flags_export: null argument");
+    return dev_readmap_flags(c->device(), library, flags, c->err);
+}
+int sage2ov_mates_distances_export(sage2ov_ctx* c, int library, uint32_t* d, uint64_t cap, uint64_t* n) {
+    if (!c || !n) return SAGE2OV_ERR_ARG;
+    { const int rc = mates_check(c, "sage2ov_mates_distances_export", library); if (rc) return rc; }
+    { const int rc = readmap_ensure(c, "sage2ov_mates_distances_export"); if (rc) return rc; }
+    { const int rc = readmap_join(c, library); if (rc) return rc; }
+    const uint64_t nd = dev_readmap_distance_count(c->device(), library); *n = nd;
+    if (!d) return SAGE2OV_OK;
+    if (cap < nd) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_mates_distances_export: the buffer holds fewer values than there are distances");
+    { const int rc = pair_ordinals(c); if (rc) return rc; }
+    std::vector<uint32_t> dist(nd), ent(nd), pr(nd);
+    { const int rc = dev_readmap_distances(c->device(), library, dist.data(), ent.data(), pr.data(), c->err); if (rc) return rc; }
+    const std::vector<uint32_t>& ord = c->pairOrdinal;
+    for (uint64_t i = 0; i < nd;) {                                                    // a mate entry with several distances (rare): by the pair's ordinal
+        uint64_t e = i + 1; while (e < nd && ent[e] == ent[i]) e++;
+        if (e - i > 1) {
+            std::vector<std::pair<uint32_t, uint32_t>> run; for (uint64_t x = i; x < e; x++) run.emplace_back(ord[pr[x]], dist[x]);
+            std::sort(run.begin(), run.end()); for (uint64_t x = i; x < e; x++) dist[x] = run[x - i].second;
+        }
+        i = e;
+    }
+    if (nd) memcpy(d, dist.data(), nd * sizeof(uint32_t));
+    return SAGE2OV_OK;
+}
+int sage2ov_mates_estimate(sage2ov_ctx* c) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    { const int rc = readmap_ensure(c, "sage2ov_mates_estimate"); if (rc) return rc; }
+    c->estimated = false; c->rmstats.rounds = 0; c->rmstats.round_ms = 0;
+    const uint64_t arl = average_read_length(c); Device* d = c->device();
+    c->minUpper = 1000000; c->maxUpper = 0;                                            // matePair.cpp:292-293
+    for (auto& I : c->inserts) I = sage2ov_insert{};
+    for (int lib = 1; lib <= (int)c->mateLibraries; lib++) {
+        { const int rc = readmap_join(c, lib); if (rc) return rc; }
+        ReadMapStats s; sage2ov_insert& I = c->inserts[lib];
+        const int rc = estimate_rounds([&](int64_t mu, uint64_t& count, uint64_t& sum, u128& sq) {
+            uint64_t o[4]; const int r = dev_readmap_round(d, lib, mu, 4 * (uint64_t)mu, o, &s, c->err);
+            count = o[0]; sum = o[1]; sq = ((u128)o[3] << 64) | o[2]; return r;
+        }, arl, &I);
+        if (rc) return rc;
+        I.library = (uint32_t)lib; c->rmstats.rounds += s.rounds; c->rmstats.round_ms += s.round_ms;
+        if (!I.valid) continue;                                                        // (left out of the bounds: see sage2ov.h)
+        if (c->minUpper >= (uint64_t)I.upper) c->minUpper = (uint64_t)I.upper;
+        if (c->maxUpper <= (uint64_t)I.upper) c->maxUpper = (uint64_t)I.upper;
+    }
+    c->maxUpper *= 3 * ((arl + 99) / 100);                                             // 3 * ceil(averageReadLength / 100.0), :308
+    c->estimated = true;
+    return SAGE2OV_OK;
+}
+int sage2ov_mates_insert_get(const sage2ov_ctx* c, int library, sage2ov_insert* out) {
+    if (!c || !out || library < 1 || library > 127 || !c->estimated) return SAGE2OV_ERR_ARG;
+    *out = c->inserts[library]; return SAGE2OV_OK;
+}
+int sage2ov_mates_bounds_get(const sage2ov_ctx* c, uint64_t* mn, uint64_t* mx) {
+    if (!c || !mn || !mx || !c->estimated) return SAGE2OV_ERR_ARG;
+    *mn = c->minUpper; *mx = c->maxUpper; return SAGE2OV_OK;
+}
+int sage2ov_readmap_stats_get(const sage2ov_ctx* c, sage2ov_readmap_stats* o) { if (!c || !o) return SAGE2OV_ERR_ARG; *o = c->rmstats; return SAGE2OV_OK; }
 
 int sage2ov_run_steps23(sage2ov_ctx* c) {
     if (!c) return SAGE2OV_ERR_ARG;

@@ -160,6 +160,22 @@ struct SimplifiedGraph {
 int dev_simplify(Device* d, SimplifiedGraph& out, std::string& err);             // result stays in HBM
 int dev_simplify_download(Device* d, SimplifiedGraph& out, std::string& err);    // fills the arrays (once)
 void dev_simplify_release(Device* d);
+int dev_simplify_upload(Device* d, const SimplifiedGraph& in, std::string& err);  // a parsed graph (from .. lists filled) takes the place of step 4's result in HBM
+// MatePair::mapReadsToEdges / mapReadLocations / computeMeanSD on the device (sage2ov_mates_map_reads, _estimate): dev_readmap_build makes the
+// read-to-edge table from the resident step-4 graph; dev_readmap_join the flags and distances of one library's mate table (kept until dev_readmap_drop_joins);
+// dev_readmap_round one round's {count, sum, sq low, sq high}.  The table goes with the graph (dev_simplify_release) and the read set.
+struct ReadMapStats { uint64_t entries = 0, locations = 0, records = 0; uint32_t passes = 0, rounds = 0; double scan_ms = 0, records_ms = 0, sort_ms = 0, reduce_ms = 0, join_ms = 0, round_ms = 0; };
+int dev_readmap_build(Device* d, ReadMapStats* st, std::string& err);
+int dev_readmap_join(Device* d, int library, ReadMapStats* st, std::string& err);
+int dev_readmap_round(Device* d, int library, long long mu, uint64_t thr, uint64_t out[4], ReadMapStats* st, std::string& err);
+void dev_readmap_counts(Device* d, uint64_t* entries, uint64_t* locations);
+int dev_readmap_export(Device* d, uint32_t* read, uint32_t* pair, uint32_t* nf, uint32_t* nr, uint32_t* loc, int32_t* locs, uint32_t* offsets, std::string& err);
+uint64_t dev_readmap_flag_count(Device* d, int library);
+uint64_t dev_readmap_distance_count(Device* d, int library);
+int dev_readmap_flags(Device* d, int library, uint8_t* out, std::string& err);
+int dev_readmap_distances(Device* d, int library, uint32_t* dist, uint32_t* entry, uint32_t* pair, std::string& err);
+void dev_readmap_drop_joins(Device* d);
+void dev_readmap_release(Device* d);
 void dev_timings(Device* d, DevTimings* t);
 void dev_reset_timings(Device* d);
 int dev_sync(Device* d, std::string& err);
