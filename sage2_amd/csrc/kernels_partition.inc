@@ -117,6 +117,89 @@ __global__ __launch_bounds__(PT_SC_THREADS) void k_pt_scatter(const u32* __restr
     }
 }
 
+// The same scatter as TWO workgroups of eight waves per CU: the same 8192-tuple tile, the same (wave, round, lane) input order and the same stable ranking, so
+// cnt / base and the output are those of k_pt_scatter byte for byte.  What makes two fit is that the sorted tile is staged in LDS in two HALVES: after the
+// (digit, wave) scan every tuple knows its position in the sorted tile; phase 0 stages and stores positions [0, 4096), phase 1 the rest -- a (tile, digit) run
+// across the boundary is written in two pieces to the same contiguous place.  One workgroup's loads and stores then run under the other's ranking.
+// Registers (four waves per SIMD: 128): the tile's loads go through ONE address with immediate offsets under the lanes' validity, and the sixteen tile
+// positions of a thread are kept as 16-bit pairs (0xFFFF: no tuple).
+constexpr int PT2_THREADS = 512, PT2_WAVES = PT2_THREADS / 64, PT2_ROUNDS = PT_TILE / PT2_THREADS, PT2_HALF = PT_TILE / 2, PT2_LOG_HALF = 12;
+static_assert(PT_NB_MAX <= PT2_THREADS && PT2_ROUNDS % 2 == 0 && (1 << PT2_LOG_HALF) == PT2_HALF && PT2_HALF % PT2_THREADS == 0 && PT_TILE < 65535, "partition tile, two workgroups");
+template <int W, int KEYW>
+__global__ __launch_bounds__(PT2_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4)))
+void k_pt_scatter2(const u32* __restrict__ in, u32 n, int shift, u32 mask, const u32* __restrict__ base, u32 ntiles, u32* out) {
+    __shared__ pt_cnt_t cntw[PT2_WAVES][PT_NB_MAX];
+    __shared__ u32 gdst[PT_NB_MAX];
+    __shared__ __attribute__((aligned(16))) u32 sE[PT2_HALF * W];    // one half of the tile sorted by digit
+    __shared__ u32 shw[PT2_WAVES];
+    const u32 tid = threadIdx.x, lane = tid & 63u, w = (u32)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    for (u32 x = tid; x < PT2_WAVES * PT_NB_MAX; x += PT2_THREADS) (&cntw[0][0])[x] = 0;
+    __syncthreads();
+    const u32 tile0 = blockIdx.x * PT_TILE, nt = min((u32)PT_TILE, n - tile0);
+    const u32 l0 = w * (PT_TILE / PT2_WAVES) + lane;                 // my first tuple inside the tile; round r: l0 + 64 r
+    const u32* tb = in + (u64)tile0 * W;                             // (uniform: the loads are this base + a 32-bit lane offset + an immediate)
+    PtElem<W> e[PT2_ROUNDS]; u32 pos2[PT2_ROUNDS / 2];
+    if (nt == PT_TILE) {
+#pragma unroll
+        for (int r = 0; r < PT2_ROUNDS; r++) e[r] = PtElem<W>::ld(tb + (l0 + r * 64) * W);
+    } else {
+#pragma unroll
+        for (int r = 0; r < PT2_ROUNDS; r++) { const u32 l = l0 + r * 64; e[r] = PtElem<W>::ld(tb + (l < nt ? l : 0u) * W); }
+    }
+    const u64 below = (1ull << lane) - 1ull;
+#pragma unroll
+    for (int r = 0; r < PT2_ROUNDS; r++) {
+        const bool v = l0 + r * 64 < nt;
+        const u32 d = pt_digit(e[r].d[KEYW], shift, mask);
+        u64 peers = __ballot(v);
+        for (int b = 0; (mask >> b) != 0u; b++) { const u64 mb = __ballot((d >> b) & 1u); peers &= ((d >> b) & 1u) ? mb : ~mb; }
+        const u32 old = cntw[w][d];
+        wave_sync();
+        if (v && (peers >> lane) == 1ull) cntw[w][d] = (pt_cnt_t)(old + (u32)__popcll(peers));
+        wave_sync();
+        const u32 loc = old + (u32)__popcll(peers & below);          // < PT_TILE / PT2_WAVES
+        pos2[r / 2] = (r & 1) ? (pos2[r / 2] | (loc << 16)) : loc;
+        asm volatile("" : "+v"(pos2[r / 2]));                        // packed HERE: left to the scheduler, old and peers (three registers) stay live per round instead
+    }
+    __syncthreads();
+    // exclusive scan over (digit, wave): thread t owns digit t
+    {
+        u32 mine[PT2_WAVES]; u32 sum = 0;
+#pragma unroll
+        for (int ww = 0; ww < PT2_WAVES; ww++) { mine[ww] = tid <= mask ? cntw[ww][tid] : 0u; sum += mine[ww]; }
+        u32 total; u32 run = block_excl_scan<PT2_WAVES>(sum, shw, total);
+        if (tid <= mask) gdst[tid] = base[(u64)tid * ntiles + blockIdx.x] - run;
+#pragma unroll
+        for (int ww = 0; ww < PT2_WAVES; ww++) { if (tid <= mask) cntw[ww][tid] = (pt_cnt_t)run; run += mine[ww]; }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < PT2_ROUNDS; r++) {                           // position inside the sorted tile
+        const u32 loc = (r & 1) ? (pos2[r / 2] >> 16) : (pos2[r / 2] & 0xFFFFu);
+        const u32 pos = l0 + r * 64 < nt ? cntw[w][pt_digit(e[r].d[KEYW], shift, mask)] + loc : 0xFFFFu;
+        pos2[r / 2] = (r & 1) ? ((pos2[r / 2] & 0xFFFFu) | (pos << 16)) : ((pos2[r / 2] & 0xFFFF0000u) | pos);
+    }
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        if (h) __syncthreads();                                      // the first half has been read
+#pragma unroll
+        for (int r = 0; r < PT2_ROUNDS; r++) {
+            const u32 pos = (r & 1) ? (pos2[r / 2] >> 16) : (pos2[r / 2] & 0xFFFFu);
+            if ((pos >> PT2_LOG_HALF) == (u32)h) e[r].st(sE + (pos & (PT2_HALF - 1)) * W);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < PT2_HALF / PT2_THREADS; q++) {
+            const u32 hp = q * PT2_THREADS + tid, pos = h * PT2_HALF + hp;
+            if (pos < nt) {
+                const PtElem<W> x = PtElem<W>::ld(sE + hp * W);
+                const u32 dst = gdst[pt_digit(x.d[KEYW], shift, mask)] + pos;
+                x.st(out + (u64)dst * W);
+            }
+        }
+    }
+}
+
 // K is sorted by (K >> shiftW): off[w] = first position whose window id is >= w, off[nW] = n.  (n == 0: the host zeroes off.)
 __global__ void k_pt_bounds(const u32* __restrict__ K, u32 n, int shiftW, u32 nW, u32* off, u32 stride) {
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x; if (i >= n) return;

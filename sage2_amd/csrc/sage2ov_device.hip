@@ -270,16 +270,25 @@ struct StreamLap {
 // Exclusive scan of n u32 (kernels_scan.inc); partial: scan_partial_words(n) words.  total null: nothing is read back, nothing is synchronised; else the sum
 // of the input comes back and the stream has finished.  n = 0: no block to launch, the total is 0.
 static inline u64 scan_partial_words(u64 n) { return n / SCAN_BLOCK + 2; }
-// the first two kernels of the scan: partial[b] = sum of the items in front of block b (SCAN_BLOCK items each), partial[nb] = the sum of all; returns nb
+// for the callers that rank inside a block themselves (k_conv_emit): partial[b] = sum of the items in front of block b (SCAN_BLOCK items each), partial[nb] = the
+// sum of all; returns nb
 static u64 scan_block_sums(Device* d, const u32* in, u64 n, u64* partial) {
     const u64 nb = (n + SCAN_BLOCK - 1) / SCAN_BLOCK;
-    if (nb) hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, d->stream, in, (u64)n, partial);
+    if (nb) hipLaunchKernelGGL((k_scan_reduce<SCAN_ITEMS, SCAN_THREADS>), dim3((unsigned)nb), dim3(SCAN_THREADS), 0, d->stream, in, (u64)n, partial);
     hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(1024), 0, d->stream, partial, (u64)nb, partial + nb);
     return nb;
 }
+// two launches while every block can add up the sums of the blocks in front of it by itself, three (one block scans the sums in between) beyond
 static int scan_u32(Device* d, const u32* in, u64 n, u32* out, u64* partial, u64* total, std::string& err) {
-    const u64 nb = scan_block_sums(d, in, n, partial);
-    if (nb) hipLaunchKernelGGL(k_scan_final, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, d->stream, in, (u64)n, partial, out);
+    const u64 nb = (n + SCAN2_BLOCK - 1) / SCAN2_BLOCK;
+    if (nb) hipLaunchKernelGGL((k_scan_reduce<SCAN2_ITEMS, SCAN2_THREADS>), dim3((unsigned)nb), dim3(SCAN2_THREADS), 0, d->stream, in, (u64)n, partial);
+    // (SAGE2OV_TEST_SCAN_DIRECT_BLOCKS=<b>: the bound, lowered -- tests: both forms and the step between them on a few thousand items)
+    const u64 directMax = (u64)std::min<long long>(SCAN_DIRECT_MAX_BLOCKS, std::max<long long>(0, d->opt.num("SAGE2OV_TEST_SCAN_DIRECT_BLOCKS", SCAN_DIRECT_MAX_BLOCKS)));
+    if (nb && nb <= directMax) hipLaunchKernelGGL((k_scan_final<SCAN2_ITEMS, SCAN2_THREADS, true>), dim3((unsigned)nb), dim3(SCAN2_THREADS), 0, d->stream, in, (u64)n, partial, out, partial + nb);
+    else {
+        hipLaunchKernelGGL(k_scan_partials, dim3(1), dim3(1024), 0, d->stream, partial, (u64)nb, partial + nb);
+        if (nb) hipLaunchKernelGGL((k_scan_final<SCAN2_ITEMS, SCAN2_THREADS, false>), dim3((unsigned)nb), dim3(SCAN2_THREADS), 0, d->stream, in, (u64)n, partial, out, partial + nb);
+    }
     HIPCHK(hipGetLastError());
     if (total) { HIPCHK(hipMemcpyAsync(total, partial + nb, sizeof(u64), hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream)); }
     return 0;
@@ -623,6 +632,17 @@ static int pt_digits(u64 nWin, int* bits, int* nd) {            // window id bit
     int wb = 0; while ((1ull << wb) < nWin) wb++;
     *bits = wb; *nd = wb == 0 ? 0 : (wb + 8) / 9; return 0;
 }
+// One scatter pass: two workgroups of eight waves per CU on half-staged tiles (k_pt_scatter2), same output as the one workgroup of sixteen (k_pt_scatter), which
+// keeps two cases.  (1) Thin runs: where the digits of the window id or the hash (dword 0: spread evenly) leave a (tile, digit) pair less than two 128-byte lines, the
+// pass is at the limit of its partial-line writes and a second workgroup on the CU gives it nothing to overlap -- measured, the table's first pass at BASELINE configs[2]
+// (170 M 12-byte tuples, 9 bits: 192 bytes) 1.39 ms with one workgroup, 1.55 with two; every other pass 5 - 19 % faster with two.  The order's
+// meta digit (dword 2) has 9 bits too but takes some 270 of its values: runs of 360 bytes.  (2) SAGE2OV_PT_ONE_BLOCK: every pass, for A/B runs and the tests.
+template <int W, int KEYW>
+static void pt_launch_scatter(Device* d, u32 ntiles, const u32* in, u32 n, int shift, u32 mask, const u32* base, u32* out) {
+    const bool thinRuns = KEYW == 0 && (u64)PT_TILE * W * sizeof(u32) / ((u64)mask + 1) < 256;
+    if (thinRuns || d->opt.flag("SAGE2OV_PT_ONE_BLOCK")) hipLaunchKernelGGL((k_pt_scatter<W, KEYW>), dim3(ntiles), dim3(PT_SC_THREADS), 0, d->stream, in, n, shift, mask, base, ntiles, out);
+    else hipLaunchKernelGGL((k_pt_scatter2<W, KEYW>), dim3(ntiles), dim3(PT2_THREADS), 0, d->stream, in, n, shift, mask, base, ntiles, out);
+}
 // The tuples are sorted by the window id (dword keyw >> shiftW); `digit 0 counted` tells that cnt already holds the first digit's per-tile histogram (taken
 // by the kernel that wrote the tuples).  On return B.E[*cur_out] is the sorted array and off[0..nWin] (if given) holds the window boundaries.
 static int partition_by_window(Device* d, PtBufs& B, int keyw, u32 n, int shiftW, u64 nWin, bool digit0Counted, u32* cnt, u32* base, u32* off, int* cur_out, std::string& err) {
@@ -638,9 +658,9 @@ static int partition_by_window(Device* d, PtBufs& B, int keyw, u32 n, int shiftW
             if (!(j == 0 && digit0Counted)) hipLaunchKernelGGL(k_pt_hist, dim3(ntiles), dim3(PT_THREADS), 0, d->stream, in + keyw, n, shift, mask, cnt, ntiles, (u32)B.W);
             int rc = scan_u32(d, cnt, (u64)(mask + 1) * ntiles, base, nullptr, err); if (rc) return rc;      // (no read-back: nothing synchronises)
             const int o = (j == 0 && B.src0) ? 0 : (cur ^ 1);
-            if (B.W == 4 && keyw == 0) hipLaunchKernelGGL((k_pt_scatter<4, 0>), dim3(ntiles), dim3(PT_SC_THREADS), 0, d->stream, in, n, shift, mask, base, ntiles, B.E[o]);
-            else if (B.W == 3 && keyw == 0) hipLaunchKernelGGL((k_pt_scatter<3, 0>), dim3(ntiles), dim3(PT_SC_THREADS), 0, d->stream, in, n, shift, mask, base, ntiles, B.E[o]);
-            else if (B.W == 3 && keyw == 2) hipLaunchKernelGGL((k_pt_scatter<3, 2>), dim3(ntiles), dim3(PT_SC_THREADS), 0, d->stream, in, n, shift, mask, base, ntiles, B.E[o]);
+            if (B.W == 4 && keyw == 0) pt_launch_scatter<4, 0>(d, ntiles, in, n, shift, mask, base, B.E[o]);
+            else if (B.W == 3 && keyw == 0) pt_launch_scatter<3, 0>(d, ntiles, in, n, shift, mask, base, B.E[o]);
+            else if (B.W == 3 && keyw == 2) pt_launch_scatter<3, 2>(d, ntiles, in, n, shift, mask, base, B.E[o]);
             else { err = "partition: unsupported tuple format"; return SAGE2OV_ERR_INTERNAL; }
             cur = o; in = B.E[o];
         }

@@ -87,7 +87,7 @@ if any(c == "WRITE_SIZE" for (_, c) in acc):
     import re
     steps = max(cnt.get(("s2::k_ix_window", "WRITE_SIZE"), 0), 1)
     def is_index(k):
-        return any(x in k for x in ("k_minimizer", "k_pt_hist", "k_pt_scatter<3", "k_loc_index", "k_loc_scatter", "k_ix_tuples", "k_pt_bounds", "k_ix_window", "k_index_purity"))
+        return any(x in k for x in ("k_minimizer", "k_pt_hist", "k_pt_scatter<3", "k_pt_scatter2<3", "k_loc_index", "k_loc_scatter", "k_ix_tuples", "k_pt_bounds", "k_ix_window", "k_index_purity"))
     per = {}
     for (k, c), v in acc.items():
         if not is_index(k): continue
