@@ -248,8 +248,8 @@ int sage2ov_graph4_save(sage2ov_ctx* ctx, const char* path);
 
 /* loadOverlapGraphFromFile's role for a graph with composite edges (overlapGraph.cpp:371-443): any P.graph4 / P.graph5 / P.graph6.  The file is parsed on the
  * host and uploaded into step 4's half-edge and read-list pools, record pairs in file order (pair p = half-edges 2p, 2p+1: the record and its twin).  The
- * header is handled as sage2ov_graph_load handles it.  `flow` is parsed and NOT kept: none of the calls below reads it (step 5 assigns it and changes no
- * edge, copycountEstimator.cpp:401-402, :710-711), and sage2ov_graph4_save writes 0 as it always does.  Needs organised reads and a GPU context.
+ * header is handled as sage2ov_graph_load handles it.  `flow` is parsed and kept, one float per half-edge, the record's and the twin's each their own (overlapGraph.cpp:393, :409, :433): sage2ov_mates_supports
+ * reads it (step 5 assigns it and changes no edge, copycountEstimator.cpp:401-402, :710-711); sage2ov_graph4_save writes 0 as it always does.  Needs organised reads and a GPU context.
  * Refused with SAGE2OV_ERR_ARG: a twin that does not mirror its record (end nodes, list length, or a twin list that is not the forward list's read ids in
  * reverse order); node or read ids above N or 0; a truncated record.  SAGE2OV_ERR_LIMIT: a distPrevious / distNext above the 11-bit field of a list entry.
  * Afterwards sage2ov_graph4_save and the sage2ov_mates_* calls below work on the loaded graph; sage2ov_graph_simplify is refused (SAGE2OV_ERR_ARG) until
@@ -320,6 +320,55 @@ int sage2ov_mates_bounds_get(const sage2ov_ctx* ctx, uint64_t* minimum_upper, ui
 int sage2ov_readmap_stats_get(const sage2ov_ctx* ctx, sage2ov_readmap_stats* out);
 /* the round arithmetic alone, on the host: needs no context and no GPU.  out->library is left 0. */
 int sage2ov_insert_estimate(const uint32_t* d, uint64_t n, uint64_t average_read_length, sage2ov_insert* out);
+
+/* ---- the flows of the resident step-4 graph: one float per half-edge.  sage2ov_graph_load_composite fills them from the file; after sage2ov_graph_simplify they are 0
+ * (what the reference holds before its step 5).  Both calls use two values per record pair (record, twin) in the order sage2ov_graph4_save writes the pairs; a
+ * loop, written twice, counts at its first writing.  This is the in-process route for a caller that ran its own step 5.  export: cap below twice the pair count:
+ * SAGE2OV_ERR_ARG, nothing written.  import: n must be twice the pair count, else SAGE2OV_ERR_ARG; the supports below are recomputed by the next call that needs
+ * them.  SAGE2OV_ERR_ARG without a step-4 graph, SAGE2OV_ERR_DEVICE on a device-less context. */
+int sage2ov_graph_flow_export(sage2ov_ctx* ctx, float* flow, uint64_t cap);
+int sage2ov_graph_flow_import(sage2ov_ctx* ctx, const float* flow, uint64_t n);
+
+/* ---- the sweep of ContigExtender::findMatepairSupports (matePair/mergeContigs.cpp:959-1030): getSupportOfEdges (:1032-1097) over isUniqueInEdge (:1102-1110) for every
+ * incoming x outgoing pair of composite edges of every node, on the device; all quantities are integers.  The merge that follows it in the
+ * reference (mergeByMatepairSupports / mergeEdgesAndUpdate: serial, order-dependent, changes the graph) is NOT part of this library.
+ * The graph is the resident step-4 graph; mates, read-to-edge table, locations and insert bounds are those of the calls above.
+ *   CANDIDATE HALVES of node i: the alive half-edges leaving i with flow >= 1 (the half's own float), a non-empty read list and from != to (:979).  Such a half is an
+ *   IN-HALF when its type is 0 or 1 (the reference's edge1 is its twin, which enters i, :981-983) and an OUT-HALF when its type is 2 or 3 (:984-986).
+ *   CANDIDATES: every (in-half a, out-half b) of one node (:987-989).
+ *   support(a, b) = getSupportOfEdges(a, b, minOverlap): walk a's list from the node outward with run = the running sum of distPrevious; stop at the first entry with
+ *   run > maximumUpperBoundOfInsert (:1043; sage2ov_mates_bounds_get's second value).  For every entry walked (per list entry: a read that stands twice within the
+ *   bound counts twice) whose read m1 is UNIQUE ON a, and every mate entry (m1 -> m2, type1, type2) of every library L, whatever its flag or count, once per entry,
+ *   with m2 UNIQUE ON b: let d1 be the locations of m1 on half a -- the `forward` ones of its read-to-edge entry if a is E of its pair, else the `reverse` ones
+ *   (findDistanceOnEdge, matePair.cpp:575-609) -- and d2 likewise for m2 on b.  The entry counts 1 when some x in d1, y in d2 have s1 * x < 0, s2 * y < 0 (s = +1 for
+ *   type 1, -1 for type 0) and |x| + |y| + 2 * averageReadLength < upper[L] + minOverlap (strict, :1073-1076).  A library with valid = 0 never counts.
+ *   UNIQUE ON h (:1102-1110): the read has exactly one read-to-edge entry, that entry is for h's pair, and the read is not itself a node with an alive edge.
+ * THE TABLE has one entry per candidate with support >= 1.  findMatepairSupports takes those with support > 1 (:992): min_support = 2 gives its list.
+ * Equal to the reference while list totals stay below 2^32 and |x| + |y| below 2^31 (its int32_t distance_all).  The pair of a loop edge (sage2ov_graph_load_composite)
+ * does not matter here: loops are never candidates and a read on a loop is never unique on a candidate.
+ * After sage2ov_graph_simplify every flow is 0: the table is empty, which is no error. */
+typedef struct sage2ov_support {       /* 24 bytes */
+    uint32_t node;                     /* the node both halves leave */
+    uint32_t pair_in, pair_out;        /* ordinals of the record pairs in sage2ov_graph4_save's order, as in sage2ov_read_edge */
+    uint32_t to_in, to_out;            /* the other end of the in-half and of the out-half */
+    uint32_t support;
+} sage2ov_support;
+typedef struct sage2ov_support_stats { /* of the last sage2ov_mates_supports */
+    uint64_t in_halves, out_halves, candidates;      /* candidates = SUM over the nodes of ins x outs, zero supports included */
+    uint64_t entries_within;                         /* list entries of in-halves whose running sum is within the bound */
+    uint64_t records;                                /* mate entries that counted (the sum of all supports) */
+    uint64_t keys, keys2;                            /* candidates with support >= 1 and >= 2 */
+    uint32_t sort_passes, reserved;                  /* 8-bit radix passes run */
+    double roles_ms, scan_ms, records_ms, sort_ms, reduce_ms;   /* HIP events */
+} sage2ov_support_stats;
+/* builds the table.  Estimates first when the estimate is stale (as sage2ov_mates_estimate maps first).  SAGE2OV_ERR_ARG without a step-4 graph, SAGE2OV_ERR_DEVICE on
+ * a device-less context, SAGE2OV_ERR_LIMIT from 2^32 - 2048 records on.  The table goes with the graph and the read set, and when the mate table, the flows or the
+ * estimate change; sage2ov_mates_supports_count / _export build it when it is stale.  Not sharded: a context with world > 1 behaves as a single one. */
+int sage2ov_mates_supports(sage2ov_ctx* ctx);
+int sage2ov_mates_supports_count(sage2ov_ctx* ctx, uint32_t min_support, uint64_t* n);
+/* the entries with support >= min_support in ascending (node, pair_in, pair_out); cap below their number: SAGE2OV_ERR_ARG, nothing written */
+int sage2ov_mates_supports_export(sage2ov_ctx* ctx, uint32_t min_support, sage2ov_support* out, uint64_t cap);
+int sage2ov_support_stats_get(const sage2ov_ctx* ctx, sage2ov_support_stats* out);
 
 /* diagnostic: table census {occupied, inline, claimed-but-unfilled, zero-tag, entries in short CSR buckets} */
 int sage2ov_debug_table(sage2ov_ctx* ctx, uint64_t* out5);

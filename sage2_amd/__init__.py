@@ -74,6 +74,16 @@ class ReadMapStats(C.Structure):
                 ("scan_ms", C.c_double), ("records_ms", C.c_double), ("sort_ms", C.c_double), ("reduce_ms", C.c_double), ("join_ms", C.c_double), ("round_ms", C.c_double)]
 
 
+# sage2ov_support (24 bytes): one (in-half, out-half) pair of a node with its mate-pair support
+SUPPORT_DTYPE = np.dtype([("node", np.uint32), ("pair_in", np.uint32), ("pair_out", np.uint32), ("to_in", np.uint32), ("to_out", np.uint32), ("support", np.uint32)])
+
+
+class SupportStats(C.Structure):
+    _fields_ = [("in_halves", C.c_uint64), ("out_halves", C.c_uint64), ("candidates", C.c_uint64), ("entries_within", C.c_uint64), ("records", C.c_uint64),
+                ("keys", C.c_uint64), ("keys2", C.c_uint64), ("sort_passes", C.c_uint32), ("reserved", C.c_uint32),
+                ("roles_ms", C.c_double), ("scan_ms", C.c_double), ("records_ms", C.c_double), ("sort_ms", C.c_double), ("reduce_ms", C.c_double)]
+
+
 class OverlapStats(C.Structure):
     _fields_ = [("verified_overlaps", C.c_uint64), ("contained_extension", C.c_uint64), ("contained_size", C.c_uint64),
                 ("left_to_explore", C.c_uint64), ("edges_inserted", C.c_uint64), ("transitive_removed", C.c_uint64),
@@ -351,6 +361,36 @@ class Context:
     def readmap_stats(self) -> ReadMapStats:
         s = ReadMapStats()
         self._chk(lib().sage2ov_readmap_stats_get(self._h, C.byref(s)))
+        return s
+
+    # ---- the sweep of ContigExtender::findMatepairSupports (mergeContigs.cpp:959-1110): flows, supports of (in, out) edge pairs at a node
+    def graph_flows(self) -> np.ndarray:
+        """the flows of the resident step-4 graph: two float32 per record pair (record, twin) in graph4_save's order"""
+        s = SimplifyStats()
+        n = 2 * s.edges if lib().sage2ov_simplify_stats_get(self._h, C.byref(s)) == 0 else 0          # (no graph: the export says what is missing)
+        out = np.zeros(n, dtype=np.float32)
+        self._chk(lib().sage2ov_graph_flow_export(self._h, C.c_void_p(out.ctypes.data), C.c_uint64(n)))
+        return out
+
+    def graph_set_flows(self, flows):
+        flows = np.ascontiguousarray(flows, dtype=np.float32)
+        self._chk(lib().sage2ov_graph_flow_import(self._h, C.c_void_p(flows.ctypes.data), C.c_uint64(len(flows))))
+
+    def mates_supports(self, min_support=2) -> np.ndarray:
+        """the candidates with support >= min_support (SUPPORT_DTYPE) in ascending (node, pair_in, pair_out); 2 gives findMatepairSupports' list"""
+        n = C.c_uint64(0)
+        self._chk(lib().sage2ov_mates_supports_count(self._h, C.c_uint32(min_support), C.byref(n)))
+        out = np.zeros(n.value, dtype=SUPPORT_DTYPE)
+        self._chk(lib().sage2ov_mates_supports_export(self._h, C.c_uint32(min_support), C.c_void_p(out.ctypes.data), C.c_uint64(n.value)))
+        return out
+
+    def mates_supports_build(self):
+        """builds the table now (mates_supports builds it when it is stale)"""
+        self._chk(lib().sage2ov_mates_supports(self._h))
+
+    def support_stats(self) -> SupportStats:
+        s = SupportStats()
+        self._chk(lib().sage2ov_support_stats_get(self._h, C.byref(s)))
         return s
 
     # ---- step 2

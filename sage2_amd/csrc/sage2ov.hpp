@@ -121,6 +121,13 @@ public:
         }
         return {0};
     }
+    // the sweep of ContigExtender::findMatepairSupports (mergeContigs.cpp:959-1022): every (in, out) pair of a node with support >= minSupport; 2 gives the list the
+    // reference merges from (:992).  The merges themselves stay with the caller
+    std::vector<sage2ov_support> matepairSupports(uint32_t minSupport = 2) {
+        uint64_t n = 0; ctx().check(sage2ov_mates_supports_count(ctx().get(), minSupport, &n));
+        std::vector<sage2ov_support> out(n); ctx().check(sage2ov_mates_supports_export(ctx().get(), minSupport, out.data(), n));
+        return out;
+    }
     ReadLoader* loaderObj;
 private:
     Context& ctx() const { return loaderObj->context(); }

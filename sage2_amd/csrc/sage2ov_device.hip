@@ -109,6 +109,7 @@ struct Device {
     bool diet = false;
     // hits written out by the initial pass (k_probe_fast<..., TAIL = 2> on noisy data, one context probing everything): the reduce phase filters them
     struct PreHits { bool valid = false; Hit* hits = nullptr; u64 cap = 0, used = 0; u64* base = nullptr; } pre;
+    void* support = nullptr;     // the mate-pair supports of edge pairs (dev_support_build; Support): allocations of its own, dropped with the read-to-edge table and the mate flags
     void* s4keep = nullptr;      // step 4: the simplified graph stays in HBM until the next call (S4Keep)
     // step 4: blocks a call released, kept for the next call (it asks for the same ~50 sizes; fresh HBM costs ~50 ms per GB to map, 0.7 s per call at BASELINE
     // configs[2]).  Emptied when the read set changes, when the workspace arena runs out of memory, and never filled in memory-diet mode.
@@ -227,6 +228,7 @@ static void mem_sample(Device* d) { size_t fr = 0, to = 0; if (hipMemGetInfo(&fr
 #include "kernels_find.inc"
 #include "kernels_mates.inc"
 #include "kernels_readmap.inc"
+#include "kernels_support.inc"
 
 // =============================================================================================
 // host primitives: what the launchers below share (grids, counters, transient buffers, a stream timer, scan, radix sort, heads)
@@ -2103,7 +2105,7 @@ struct S4Mem {                                   // released on every exit path 
 };
 }
 #define S4GET(var, type, n) type* var = mem.get<type>((n), err); if (!var) return SAGE2OV_ERR_NOMEM;
-struct S4Keep { S4Mem mem; S4Graph g; u32 nh = 0; u64 listUsed = 0; };
+struct S4Keep { S4Mem mem; S4Graph g; u32 nh = 0; u64 listUsed = 0; float* flow = nullptr; };      // flow: one float per half-edge (null: every flow is 0, the state after step 4)
 void dev_simplify_release(Device* d) { dev_readmap_release(d); if (d->s4keep) { hipSetDevice(d->ordinal); delete (S4Keep*)d->s4keep; d->s4keep = nullptr; } }
 
 int dev_simplify(Device* d, SimplifiedGraph& out, std::string& err) {
@@ -2348,6 +2350,18 @@ int dev_simplify_upload(Device* d, const SimplifiedGraph& in, std::string& err) 
     if (nl) HIPCHK(hipMemcpy(g.lists, in.lists.data(), nl * sizeof(u64), hipMemcpyHostToDevice));
     keep->nh = nh; keep->listUsed = nl;
     d->s4keep = keep.release();
+    return in.flow.empty() ? 0 : dev_flow_set(d, in.flow.data(), in.flow.size(), err);
+}
+// the flows of the resident graph, one per half-edge (null: all 0 again).  The supports go: they were made from the flows
+int dev_flow_set(Device* d, const float* flow, uint64_t n, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    if (!d->s4keep) { err = "flows: no step-4 graph on the device"; return SAGE2OV_ERR_ARG; }
+    S4Keep& K = *(S4Keep*)d->s4keep; S4Mem& mem = K.mem;
+    dev_support_release(d);
+    if (!flow) { if (K.flow) { mem.drop(K.flow); K.flow = nullptr; } return 0; }
+    if (n != K.nh) { err = "flows: one value per half-edge"; return SAGE2OV_ERR_INTERNAL; }
+    if (!K.flow) { S4GET(a, float, K.nh) K.flow = a; }
+    if (n) HIPCHK(hipMemcpy(K.flow, flow, n * sizeof(float), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -2360,8 +2374,8 @@ struct ReadMap {
     u32 *eRead = nullptr, *ePair = nullptr, *eNf = nullptr, *eNr = nullptr, *eLoc = nullptr, *readOff = nullptr; int* locs = nullptr; u64 E = 0, R = 0; ReadMapLib lib[128];
     ~ReadMap() { for (auto& L : lib) readmap_drop_join(L); hipFree(eRead); hipFree(ePair); hipFree(eNf); hipFree(eNr); hipFree(eLoc); hipFree(readOff); hipFree(locs); }
 };
-void dev_readmap_drop_joins(Device* d) { if (!d->readmap) return; hipSetDevice(d->ordinal); for (auto& L : ((ReadMap*)d->readmap)->lib) readmap_drop_join(L); }
-void dev_readmap_release(Device* d) { if (d->readmap) { hipSetDevice(d->ordinal); delete (ReadMap*)d->readmap; d->readmap = nullptr; } }
+void dev_readmap_drop_joins(Device* d) { dev_support_release(d); if (!d->readmap) return; hipSetDevice(d->ordinal); for (auto& L : ((ReadMap*)d->readmap)->lib) readmap_drop_join(L); }
+void dev_readmap_release(Device* d) { dev_support_release(d); if (d->readmap) { hipSetDevice(d->ordinal); delete (ReadMap*)d->readmap; d->readmap = nullptr; } }
 static int readmap_nomem(std::string& err) { err = "read-to-edge table: out of device memory"; return SAGE2OV_ERR_NOMEM; }
 template <class T> static T* readmap_alloc(u64 n) { return (T*)DevTmp::alloc(std::max<u64>(n, 1) * sizeof(T)); }
 // the 8-bit digits of a record key (read:30 | pair:31 | side:1) that can be non-zero: side and pair end at bit 1 + bits(pairs), the read at 32 + bits(N)
@@ -2513,6 +2527,104 @@ int dev_readmap_distances(Device* d, int library, uint32_t* dist, uint32_t* entr
         HIPCHK(hipMemcpy(dist, J.dist, J.nd * sizeof(u32), hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(entry, J.dEntry, J.nd * sizeof(u32), hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(pair, J.dPair, J.nd * sizeof(u32), hipMemcpyDeviceToHost));
     }
+    return 0;
+}
+
+// =============================================================================================
+// the mate-pair supports of (in-half, out-half) pairs at a node (kernels_support.inc; the sweep of ContigExtender::findMatepairSupports, mergeContigs.cpp:959-1110)
+// =============================================================================================
+struct Support { u64* key = nullptr; u32* sup = nullptr; u64 E = 0; ~Support() { hipFree(key); hipFree(sup); } };
+void dev_support_release(Device* d) { if (d->support) { hipSetDevice(d->ordinal); delete (Support*)d->support; d->support = nullptr; } }
+uint64_t dev_support_count(Device* d) { const Support* S = (const Support*)d->support; return S ? S->E : 0; }
+static int support_nomem(std::string& err) { err = "mate-pair supports: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+int dev_support_build(Device* d, const SupportParams& P, SupportStats* st, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    if (!d->s4keep) { err = "mate-pair supports: no step-4 graph on the device"; return SAGE2OV_ERR_ARG; }
+    if (!d->readmap) { err = "mate-pair supports: the read-to-edge table is not built"; return SAGE2OV_ERR_INTERNAL; }
+    dev_support_release(d);
+    const S4Keep& K = *(S4Keep*)d->s4keep; const S4Graph& g = K.g; const u32 nh = K.nh; const u64 nl = K.listUsed; const ReadMap* M = (const ReadMap*)d->readmap;
+    std::unique_ptr<Support> S(new Support());
+    *st = SupportStats();
+    if (!K.flow || !nh || !nl) { d->support = S.release(); return 0; }                 // every flow is 0 (the graph as step 4 leaves it), or no list: no candidate
+    const u32 N = (u32)d->N; hipStream_t sm = d->stream;
+    DevTmp B; StreamLap lap(sm); HIPCHK(lap.create());
+    // ---- unique reads, the role of every half-edge, candidates per node
+    HIPCHK(lap.start());
+    uint8_t* nodeFlag = B.get<uint8_t>((u64)N + 2); u32* uniq = B.get<u32>((u64)N + 2); uint8_t* role = B.get<uint8_t>(nh); u32* inCnt = B.get<u32>(nh); u32* inOff = B.get<u32>(nh);
+    u32* nIn = B.get<u32>((u64)N + 2); u32* nOut = B.get<u32>((u64)N + 2); u32* prod = B.get<u32>((u64)N + 2); u32* prodScan = B.get<u32>((u64)N + 2);
+    unsigned long long* ctr = B.get<unsigned long long>(4); u64* partial = B.get<u64>(scan_partial_words(std::max<u64>(std::max<u64>(nl, nh), (u64)N + 2)));
+    MsLib* libs = B.get<MsLib>(128);
+    if (!nodeFlag || !uniq || !role || !inCnt || !inOff || !nIn || !nOut || !prod || !prodScan || !ctr || !partial || !libs) return support_nomem(err);
+    HIPCHK(hipMemsetAsync(nodeFlag, 0, (u64)N + 2, sm)); HIPCHK(hipMemsetAsync(nIn, 0, ((u64)N + 2) * sizeof(u32), sm)); HIPCHK(hipMemsetAsync(nOut, 0, ((u64)N + 2) * sizeof(u32), sm));
+    HIPCHK(hipMemsetAsync(ctr, 0, 4 * sizeof(unsigned long long), sm));
+    const MsTable T = {M->readOff, M->ePair, M->eNf, M->eNr, M->eLoc, M->locs, N};
+    const dim3 b256(256);
+    hipLaunchKernelGGL(k_ms_nodes, dim3(grid_for(nh, 256)), b256, 0, sm, g, nh, nodeFlag);
+    hipLaunchKernelGGL(k_ms_unique, dim3(grid_for((u64)N + 1, 256)), b256, 0, sm, T, nodeFlag, uniq);
+    hipLaunchKernelGGL(k_ms_roles, dim3(grid_for(nh, 256)), b256, 0, sm, g, nh, K.flow, role, inCnt, nIn, nOut, ctr);
+    hipLaunchKernelGGL(k_ms_cand, dim3(grid_for((u64)N + 1, 256)), b256, 0, sm, nIn, nOut, N, prod);
+    { u64 cand = 0; const int rc = scan_u32(d, prod, (u64)N + 1, prodScan, partial, &cand, err); if (rc) return rc; st->candidates = cand; }
+    u64 W = 0; { const int rc = scan_u32(d, inCnt, nh, inOff, partial, &W, err); if (rc) return rc; }
+    HIPCHK(lap.stop(st->roles_ms));
+    unsigned long long hc[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpy(hc, ctr, sizeof hc, hipMemcpyDeviceToHost));
+    st->in_halves = hc[0]; st->out_halves = hc[1];
+    B.release(nodeFlag); B.release(nIn); B.release(nOut); B.release(prod); B.release(prodScan); B.release(inCnt);
+    if (!W || !st->out_halves) { d->support = S.release(); return 0; }
+    // ---- the running sums of the whole pool (as dev_readmap_build makes them; not kept there)
+    HIPCHK(lap.start());
+    u32* dprev = B.get<u32>(nl); u32* scan = B.get<u32>(nl);
+    if (!dprev || !scan) return support_nomem(err);
+    hipLaunchKernelGGL(k_rm_dprev, dim3(grid_for_capped(nl, 256)), b256, 0, sm, g.lists, nl, dprev);
+    { const int rc = scan_u32(d, dprev, nl, scan, partial, nullptr, err); if (rc) return rc; }
+    HIPCHK(lap.stop(st->scan_ms));
+    B.release(dprev);
+    // ---- records: count, scan, write
+    HIPCHK(lap.start());
+    MsLib hl[128]; for (auto& x : hl) x = MsLib{nullptr, 0, 0};
+    const u32 nlib = std::min<u32>(P.libraries, 127);
+    for (u32 L = 1; L <= nlib; L++) if (d->mates && d->mates->lib[L].n && P.thr[L] > 0) hl[L] = MsLib{d->mates->lib[L].key, d->mates->lib[L].n, (long long)P.thr[L]};
+    HIPCHK(hipMemcpyAsync(libs, hl, sizeof hl, hipMemcpyHostToDevice, sm));
+    u32* cnt = B.get<u32>(W); u32* pos = B.get<u32>(W);
+    if (!cnt || !pos) return support_nomem(err);
+    const dim3 gW(grid_for(W, 256));
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ms_records<false>), gW, b256, 0, sm, g, nh, inOff, (u32)W, scan, nl, (u64)P.bound, role, uniq, T, libs, nlib, cnt, (const u32*)nullptr, (u64*)nullptr, ctr + 3);
+    u64 R = 0; { const int rc = scan_u32(d, cnt, W, pos, partial, &R, err); if (rc) return rc; }      // (synchronises: hl may go out of scope after it)
+    HIPCHK(hipMemcpy(hc, ctr, sizeof hc, hipMemcpyDeviceToHost));
+    st->entries_within = hc[3]; st->records = R;
+    if (R >= (1ull << 32) - RS_TILE) { err = "mate-pair supports: more than 2^32 records"; return SAGE2OV_ERR_LIMIT; }
+    if (!R) { HIPCHK(lap.stop(st->records_ms)); d->support = S.release(); return 0; }
+    u64* key = B.get<u64>(R); if (!key) return support_nomem(err);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ms_records<true>), gW, b256, 0, sm, g, nh, inOff, (u32)W, scan, nl, (u64)P.bound, role, uniq, T, libs, nlib, (u32*)nullptr, (const u32*)pos, key, ctr + 3);
+    HIPCHK(hipGetLastError());
+    HIPCHK(lap.stop(st->records_ms));
+    B.release(cnt); B.release(pos); B.release(scan); B.release(uniq); B.release(role); B.release(inOff); B.release(partial);
+    // ---- sort by (in-half, out-half): the digits below the number of half-edges, in both words
+    HIPCHK(lap.start());
+    int shifts[8], np = 0; { int b = 0; while (((u64)nh >> b) != 0) b++; for (int p = 0; p < 8; p++) { const int lo = 8 * p; if ((lo & 31) < b) shifts[np++] = lo; } }
+    u64* ks = nullptr; u32* vs = nullptr; MateStats ms;
+    { const int rc = mate_sort(d, B, key, (u32)R, shifts, np, &ks, &vs, &ms, err); if (rc) return rc; }
+    st->passes = ms.passes;
+    HIPCHK(lap.stop(st->sort_ms));
+    B.release(vs);
+    // ---- reduce: one entry per distinct key, its support the length of the run
+    HIPCHK(lap.start());
+    u32* hp = nullptr; u32 E = 0;
+    { const int rc = mate_heads(d, B, ks, (u32)R, &hp, &E, err); if (rc) return rc; }
+    S->key = (u64*)DevTmp::alloc((u64)E * sizeof(u64)); S->sup = (u32*)DevTmp::alloc((u64)E * sizeof(u32));
+    if (!S->key || !S->sup) return support_nomem(err);
+    hipLaunchKernelGGL(k_ms_reduce, dim3(grid_for(E, 256)), b256, 0, sm, ks, hp, E, S->key, S->sup, ctr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(lap.stop(st->reduce_ms));
+    HIPCHK(hipMemcpy(hc, ctr, sizeof hc, hipMemcpyDeviceToHost));
+    S->E = E; st->keys = E; st->keys2 = hc[2];
+    d->support = S.release();
+    return 0;
+}
+int dev_support_export(Device* d, uint64_t* key, uint32_t* support, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    const Support* S = (const Support*)d->support; if (!S) { err = "mate-pair supports: not built"; return SAGE2OV_ERR_INTERNAL; }
+    if (S->E) { HIPCHK(hipMemcpy(key, S->key, S->E * sizeof(u64), hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(support, S->sup, S->E * sizeof(u32), hipMemcpyDeviceToHost)); }
     return 0;
 }
 

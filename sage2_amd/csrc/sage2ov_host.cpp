@@ -119,7 +119,11 @@ struct sage2ov_ctx {
     std::vector<sage2ov_insert> inserts = std::vector<sage2ov_insert>(128); uint64_t minUpper = 0, maxUpper = 0;
     std::vector<uint32_t> pairOrdinal;                 // internal pair -> ordinal of its record pair in sage2ov_graph4_save's order (filled by the exports)
     uint64_t readsGen = 0, g4Gen = 0;                  // stamps of the read set and of the read set the step-4 graph was made from: the table is built only when they agree
-    void readmap_forget() { rmValid = estimated = false; pairOrdinal.clear(); rmstats = sage2ov_readmap_stats{}; }      // the graph or the read set goes
+    // ---- the mate-pair supports (sage2ov_mates_supports): built on the device, kept here in export order once a call has asked for them
+    bool supValid = false;                             // the table is of the present graph, flows, mates and estimate (it also needs `estimated`)
+    sage2ov_support_stats sstats{}; std::vector<sage2ov_support> supports; bool supOnHost = false;
+    void supports_forget() { supValid = supOnHost = false; supports.clear(); sstats = sage2ov_support_stats{}; }
+    void readmap_forget() { rmValid = estimated = false; pairOrdinal.clear(); rmstats = sage2ov_readmap_stats{}; supports_forget(); }      // the graph or the read set goes
     void mates_forget(bool readSetGoes = true) {       // the read set goes: its ids mean nothing any more (the device drops its part in free_reads) -- or sage2ov_mates_clear
         if (readSetGoes) { readmap_forget(); readsGen++; } else estimated = false;
         for (auto& L : mates) L = MateLib();
@@ -1695,9 +1699,10 @@ int sage2ov_graph_load_composite(sage2ov_ctx* c, const char* path) {
         v = 0; while (p < end && *p >= '0' && *p <= '9') v = v * 10 + (unsigned long long)(*p++ - '0');
         return p >= end || *p == ' ' || *p == '\t' || *p == '\n' || *p == '\r';
     };
-    auto real = [&]() -> bool {                                                        // the flow column (a float: "0", "2", "1.5", "1e+06"): parsed, not kept
+    float flowRead = 0;
+    auto real = [&]() -> bool {                                                        // the flow column (a float: "0", "2", "1.5", "1e+06"), kept as the reference keeps it: a float
         skip(); if (p >= end) return false;
-        char* e = nullptr; (void)strtod(p, &e); if (e == p) return false; p = e; return true;
+        char* e = nullptr; const double v = strtod(p, &e); if (e == p) return false; p = e; flowRead = (float)v; return true;
     };
     unsigned long long gs, nr, avg;
     if (!num(gs) || !num(nr) || !num(avg)) return c->fail(SAGE2OV_ERR_IO, "sage2ov_graph_load_composite: bad header");
@@ -1712,7 +1717,7 @@ int sage2ov_graph_load_composite(sage2ov_ctx* c, const char* path) {
         if (v[2] > 3 || v[4] > 0xFFFFFFFFull || v[6] >= (1ull << 32)) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_load_composite: edge type, length or list size out of range");
         if (g.lists.size() + v[6] >= (1ull << 32)) return c->fail(SAGE2OV_ERR_LIMIT, "sage2ov_graph_load_composite: more than 2^32 list entries");
         g.from.push_back((uint32_t)v[0]); g.to.push_back((uint32_t)v[1]); g.type.push_back((uint8_t)v[2]); g.len.push_back((uint32_t)v[4]);
-        g.cnt.push_back((uint32_t)v[6]); g.off.push_back((uint32_t)g.lists.size()); g.alive.push_back(1);
+        g.cnt.push_back((uint32_t)v[6]); g.off.push_back((uint32_t)g.lists.size()); g.alive.push_back(1); g.flow.push_back(flowRead);
         for (unsigned long long j = 0; j < v[6]; j++) {
             unsigned long long e[5];
             for (int x = 0; x < 5; x++) if (!num(e[x])) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_load_composite: truncated or malformed read list");
@@ -1727,7 +1732,7 @@ int sage2ov_graph_load_composite(sage2ov_ctx* c, const char* path) {
         return g.from[a] == g.from[b] && g.to[a] == g.to[b] && g.type[a] == g.type[b] && g.len[a] == g.len[b] && g.cnt[a] == g.cnt[b] &&
                std::equal(g.lists.begin() + g.off[a], g.lists.begin() + g.off[a] + g.cnt[a], g.lists.begin() + g.off[b]);
     };
-    auto pop = [&]() { g.lists.resize(g.off.back()); g.from.pop_back(); g.to.pop_back(); g.type.pop_back(); g.len.pop_back(); g.cnt.pop_back(); g.off.pop_back(); g.alive.pop_back(); };
+    auto pop = [&]() { g.lists.resize(g.off.back()); g.from.pop_back(); g.to.pop_back(); g.type.pop_back(); g.len.pop_back(); g.cnt.pop_back(); g.off.pop_back(); g.alive.pop_back(); g.flow.pop_back(); };
     uint64_t reads = 0;
     for (;;) {
         int rc = record(true); if (rc == 1) break; if (rc) return rc;
@@ -1786,7 +1791,7 @@ void readmap_stats_take(sage2ov_ctx* c, const ReadMapStats& s) {
     o.scan_ms = s.scan_ms; o.records_ms = s.records_ms; o.sort_ms = s.sort_ms; o.reduce_ms = s.reduce_ms;
 }
 int readmap_build(sage2ov_ctx* c) {
-    c->rmValid = c->estimated = false; c->rmstats = sage2ov_readmap_stats{};
+    c->rmValid = c->estimated = false; c->rmstats = sage2ov_readmap_stats{}; c->supports_forget();
     ReadMapStats s; const int rc = dev_readmap_build(c->device(), &s, c->err); if (rc) return rc;
     readmap_stats_take(c, s); c->rmValid = true; return SAGE2OV_OK;
 }
@@ -1900,7 +1905,7 @@ int sage2ov_mates_distances_export(sage2ov_ctx* c, int library, uint32_t* d, uin
 int sage2ov_mates_estimate(sage2ov_ctx* c) {
     if (!c) return SAGE2OV_ERR_ARG;
     { const int rc = readmap_ensure(c, "sage2ov_mates_estimate"); if (rc) return rc; }
-    c->estimated = false; c->rmstats.rounds = 0; c->rmstats.round_ms = 0;
+    c->estimated = false; c->rmstats.rounds = 0; c->rmstats.round_ms = 0; c->supports_forget();
     const uint64_t arl = average_read_length(c); Device* d = c->device();
     c->minUpper = 1000000; c->maxUpper = 0;                                            // matePair.cpp:292-293
     for (auto& I : c->inserts) I = sage2ov_insert{};
@@ -1930,6 +1935,97 @@ int sage2ov_mates_bounds_get(const sage2ov_ctx* c, uint64_t* mn, uint64_t* mx) {
     *mn = c->minUpper; *mx = c->maxUpper; return SAGE2OV_OK;
 }
 int sage2ov_readmap_stats_get(const sage2ov_ctx* c, sage2ov_readmap_stats* o) { if (!c || !o) return SAGE2OV_ERR_ARG; *o = c->rmstats; return SAGE2OV_OK; }
+
+// ---- the flows of the resident graph and the sweep of ContigExtender::findMatepairSupports (mergeContigs.cpp:959-1110); the semantics are stated in sage2ov.h
+namespace {
+static_assert(sizeof(sage2ov_support) == 24, "sage2ov_support is six uint32_t");
+// the half-edges that open a record pair in sage2ov_graph4_save's order, a loop at its first writing only
+int flow_order(sage2ov_ctx* c, std::vector<uint32_t>& first) {
+    { const int rc = dev_simplify_download(c->device(), c->g4, c->err); if (rc) return rc; }
+    std::vector<uint32_t> order; g4_save_order(c->g4, order);
+    std::vector<uint8_t> seen(c->g4.n_half_edges / 2 + 1, 0); first.clear();
+    for (uint32_t h : order) if (!seen[h >> 1]) { seen[h >> 1] = 1; first.push_back(h); }
+    return SAGE2OV_OK;
+}
+int supports_ensure(sage2ov_ctx* c, const char* who) {
+    { const int rc = readmap_check(c, who); if (rc) return rc; }
+    if (c->supValid && c->estimated && c->rmValid) return SAGE2OV_OK;
+    return sage2ov_mates_supports(c);
+}
+// the table in export order, on the host (once per table)
+int supports_fetch(sage2ov_ctx* c) {
+    if (c->supOnHost) return SAGE2OV_OK;
+    Device* d = c->device(); const uint64_t E = dev_support_count(d);
+    std::vector<uint64_t> key(E); std::vector<uint32_t> sup(E);
+    { const int rc = dev_support_export(d, key.data(), sup.data(), c->err); if (rc) return rc; }
+    { const int rc = pair_ordinals(c); if (rc) return rc; }
+    const SimplifiedGraph& g = c->g4; const std::vector<uint32_t>& ord = c->pairOrdinal;
+    c->supports.resize(E);
+    for (uint64_t e = 0; e < E; e++) {
+        const uint32_t a = (uint32_t)(key[e] >> 32), b = (uint32_t)key[e];
+        sage2ov_support o{}; o.node = g.from[a]; o.pair_in = ord[a >> 1]; o.pair_out = ord[b >> 1]; o.to_in = g.to[a]; o.to_out = g.to[b]; o.support = sup[e];
+        c->supports[e] = o;
+    }
+    std::sort(c->supports.begin(), c->supports.end(), [](const sage2ov_support& x, const sage2ov_support& y) {
+        return x.node != y.node ? x.node < y.node : (x.pair_in != y.pair_in ? x.pair_in < y.pair_in : x.pair_out < y.pair_out); });
+    c->supOnHost = true;
+    return SAGE2OV_OK;
+}
+}  // namespace
+int sage2ov_graph_flow_export(sage2ov_ctx* c, float* flow, uint64_t cap) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    { const int rc = readmap_check(c, "sage2ov_graph_flow_export"); if (rc) return rc; }
+    std::vector<uint32_t> first; { const int rc = flow_order(c, first); if (rc) return rc; }
+    if (cap < 2 * first.size()) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_flow_export: the buffer holds fewer than two values per record pair");
+    if (!first.empty() && !flow) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_flow_export: null argument");
+    const std::vector<float>& f = c->g4.flow;
+    for (size_t x = 0; x < first.size(); x++) { flow[2 * x] = f.empty() ? 0.f : f[first[x]]; flow[2 * x + 1] = f.empty() ? 0.f : f[first[x] ^ 1u]; }
+    return SAGE2OV_OK;
+}
+int sage2ov_graph_flow_import(sage2ov_ctx* c, const float* flow, uint64_t n) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    { const int rc = readmap_check(c, "sage2ov_graph_flow_import"); if (rc) return rc; }
+    std::vector<uint32_t> first; { const int rc = flow_order(c, first); if (rc) return rc; }
+    if (n != 2 * first.size()) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_flow_import: two values per record pair, in sage2ov_graph4_save's order");
+    if (n && !flow) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_flow_import: null argument");
+    std::vector<float> f(c->g4.n_half_edges, 0.f);
+    for (size_t x = 0; x < first.size(); x++) { f[first[x]] = flow[2 * x]; f[first[x] ^ 1u] = flow[2 * x + 1]; }
+    c->supports_forget();
+    { const int rc = dev_flow_set(c->device(), f.data(), f.size(), c->err); if (rc) return rc; }
+    c->g4.flow = std::move(f);
+    return SAGE2OV_OK;
+}
+int sage2ov_mates_supports(sage2ov_ctx* c) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    { const int rc = readmap_check(c, "sage2ov_mates_supports"); if (rc) return rc; }
+    if (!c->estimated || !c->rmValid) { const int rc = sage2ov_mates_estimate(c); if (rc) return rc; }
+    c->supports_forget();
+    const int64_t arl = (int64_t)average_read_length(c), k = (int64_t)c->cfg.min_overlap;
+    SupportParams P; P.bound = c->maxUpper; P.libraries = c->mateLibraries;
+    for (int lib = 1; lib <= (int)c->mateLibraries && lib < 128; lib++) P.thr[lib] = c->inserts[lib].valid ? c->inserts[lib].upper + k - 2 * arl : 0;
+    SupportStats s; const int rc = dev_support_build(c->device(), P, &s, c->err); if (rc) return rc;
+    sage2ov_support_stats& o = c->sstats;
+    o.in_halves = s.in_halves; o.out_halves = s.out_halves; o.candidates = s.candidates; o.entries_within = s.entries_within; o.records = s.records; o.keys = s.keys; o.keys2 = s.keys2;
+    o.sort_passes = s.passes; o.roles_ms = s.roles_ms; o.scan_ms = s.scan_ms; o.records_ms = s.records_ms; o.sort_ms = s.sort_ms; o.reduce_ms = s.reduce_ms;
+    c->supValid = true;
+    return SAGE2OV_OK;
+}
+int sage2ov_mates_supports_count(sage2ov_ctx* c, uint32_t min_support, uint64_t* n) {
+    if (!c || !n) return SAGE2OV_ERR_ARG;
+    { const int rc = supports_ensure(c, "sage2ov_mates_supports_count"); if (rc) return rc; }
+    { const int rc = supports_fetch(c); if (rc) return rc; }
+    uint64_t m = 0; for (const sage2ov_support& e : c->supports) m += e.support >= min_support;
+    *n = m; return SAGE2OV_OK;
+}
+int sage2ov_mates_supports_export(sage2ov_ctx* c, uint32_t min_support, sage2ov_support* out, uint64_t cap) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    uint64_t m = 0; { const int rc = sage2ov_mates_supports_count(c, min_support, &m); if (rc) return rc; }
+    if (cap < m) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_mates_supports_export: the buffer holds fewer entries than the table (sage2ov_mates_supports_count)");
+    if (m && !out) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_mates_supports_export: null argument");
+    uint64_t at = 0; for (const sage2ov_support& e : c->supports) if (e.support >= min_support) out[at++] = e;
+    return SAGE2OV_OK;
+}
+int sage2ov_support_stats_get(const sage2ov_ctx* c, sage2ov_support_stats* o) { if (!c || !o) return SAGE2OV_ERR_ARG; *o = c->sstats; return SAGE2OV_OK; }
 
 int sage2ov_run_steps23(sage2ov_ctx* c) {
     if (!c) return SAGE2OV_ERR_ARG;

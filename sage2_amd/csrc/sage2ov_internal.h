@@ -154,6 +154,7 @@ int dev_download_edges(Device* d, std::vector<FinalEdge>& out, std::string& err)
 int dev_upload_edges(Device* d, const std::vector<FinalEdge>& in, std::string& err);
 // step 4 (graph simplification) on the device: the surviving half-edges (pair p = 2p, 2p+1; index = age) and their read lists
 struct SimplifiedGraph {
+    std::vector<float> flow;          // one per half-edge as loadOverlapGraphFromFile parses it (overlapGraph.cpp:393, :409, :433); empty: every flow is 0
     uint64_t N = 0, n_half_edges = 0, contracted = 0, removed = 0, iterations = 0, pairs_alive = 0, reads_on_edges = 0; double device_ms = 0; bool downloaded = false;
     std::vector<uint32_t> from, to, len, cnt, off; std::vector<uint8_t> type, alive; std::vector<uint64_t> lists;
 };
@@ -176,6 +177,16 @@ int dev_readmap_flags(Device* d, int library, uint8_t* out, std::string& err);
 int dev_readmap_distances(Device* d, int library, uint32_t* dist, uint32_t* entry, uint32_t* pair, std::string& err);
 void dev_readmap_drop_joins(Device* d);
 void dev_readmap_release(Device* d);
+int dev_flow_set(Device* d, const float* flow, uint64_t n, std::string& err);      // one float per half-edge of the resident graph; null: every flow is 0
+// the sweep of ContigExtender::findMatepairSupports on the device (sage2ov_mates_supports): needs the read-to-edge table, the mate tables and the
+// insert bounds.  The table (key = in-half:32 | out-half:32, support) stays in HBM until the read-to-edge table, the mate flags or the flows go.
+struct SupportParams { uint64_t bound = 0; int64_t thr[128] = {}; uint32_t libraries = 0; };      // bound: maximumUpperBoundOfInsert; thr[L]: upper[L] + minOverlap - 2 * averageReadLength, 0 when L is not valid
+struct SupportStats { uint64_t in_halves = 0, out_halves = 0, candidates = 0, entries_within = 0, records = 0, keys = 0, keys2 = 0; uint32_t passes = 0;
+                      double roles_ms = 0, scan_ms = 0, records_ms = 0, sort_ms = 0, reduce_ms = 0; };
+int dev_support_build(Device* d, const SupportParams& P, SupportStats* st, std::string& err);
+uint64_t dev_support_count(Device* d);
+int dev_support_export(Device* d, uint64_t* key, uint32_t* support, std::string& err);
+void dev_support_release(Device* d);
 void dev_timings(Device* d, DevTimings* t);
 void dev_reset_timings(Device* d);
 int dev_sync(Device* d, std::string& err);
