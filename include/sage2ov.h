@@ -370,6 +370,61 @@ int sage2ov_mates_supports_count(sage2ov_ctx* ctx, uint32_t min_support, uint64_
 int sage2ov_mates_supports_export(sage2ov_ctx* ctx, uint32_t min_support, sage2ov_support* out, uint64_t cap);
 int sage2ov_support_stats_get(const sage2ov_ctx* ctx, sage2ov_support_stats* out);
 
+/* ---- OverlapGraph::printGraph (overlapGraph.cpp:507-593) and saveContigsToFile (:607-784): the contigs of the resident step-4 graph, selected, ordered, laid out and
+ * spelled on the device; all quantities are integers.  L(i) is the length of read i; a node's DEGREE is the number of alive half-edges leaving it
+ * (getDegree, :595-602).
+ *   SELECTION (:529-585): a half-edge h is a row when it is alive, from[h] >= to[h] and len[h] >= threshold.  Of a loop (from == to) only the half met first in the
+ *   node's newest-first list is a row (:535-547): the half with the higher index of its pair.
+ *   threshold = 0 asks for contigLengthThreshold = (int)ceilf(100 * (averageReadLength / 100.0)) (:32) from the context's read totals.
+ *   ORDER: lengthOfEdge descending.  The reference's std::sort (:496-501, :588) leaves the order of equal lengths open; HERE ties keep the enumeration order of
+ *   :529-531, `from` ascending, then half-edge index descending (a deliberate difference: the order is defined).
+ *   STRING (:635-697): len[h] + L(from) characters, all 'N' at first.  The `from` read, reverse-complemented for types 0 and 1; then per list entry its read (forward
+ *   when orientation is 1, else reverse-complemented): its last distPrevious bases when distPrevious <= L, else (a GAP) distPrevious - L times 'N' and the whole read --
+ *   1 to gap_count, distPrevious - L to n_count --; then the last nextDistance bases of the `to` read, forward for types 1 and 3, else reverse-complemented, where
+ *   nextDistance is the last entry's distNext, or len[h] without a list.  Kept quirks: nextDistance > L(to) copies nothing (the reference's unsigned loop start wraps,
+ *   :696) and those positions stay 'N'; when distPrevious's sum + nextDistance != len[h] the edge counts as `inconsistent`, characters beyond the string are dropped
+ *   and positions not reached stay 'N' (the reference writes out of bounds there).
+ *   TRIM (:699-724): both degrees 1: the whole string; only from's: start 0, contig_length = L(from) + (len - L(to) / 2); only to's: start = L(from) - L(from) / 2,
+ *   contig_length = start + len; neither: start likewise, contig_length = start + (len - L(to) / 2).  Where len < L(to) / 2 the reference's unsigned subtraction wraps:
+ *   HERE contig_length = 0, the row is left out of the file and counts as `wrapped` (a deliberate difference).
+ *   FILE (:726-742): a record for every row with contig_length >= threshold: the header of :730, then string[start, start + contig_length) in lines of 60 -- cut at
+ *   the string's end as substr cuts it (start + contig_length passes it by one when L(from) is odd).  The ordinal is the row's position in the table, from 1; gapCount
+ *   and nCount in the header are the reference's running totals over all rows so far, written or not (:668-669 never resets them); flow= as an ostream writes a float.
+ *   STATISTICS (:745-783) from genome_size: N_X adds contig_length row by row; N50 / N90 are the contig_length and ordinal of the first row with N_X >= genome_size / 2
+ *   resp. genome_size * 9 / 10 (genome_size = 0: the first row, as in the reference); covered = base_pair_covered, the sum of len over the rows; longest =
+ *   contig_length of row 1.
+ * A loop that a graph file holds twice is one edge here (sage2ov_graph_load_composite) and one row; the reference's loader makes two edges of it, and two rows. */
+typedef struct sage2ov_contig {        /* 48 bytes */
+    uint32_t from, to;
+    uint32_t pair;                     /* ordinal of the record pair in sage2ov_graph4_save's order, as in sage2ov_read_edge */
+    uint32_t edge_length, string_length, contig_length, start;
+    uint32_t gap_count, n_count;       /* of this row (the file's header carries running totals) */
+    float    flow;
+    uint8_t  type;
+    uint8_t  pad[7];
+} sage2ov_contig;
+typedef struct sage2ov_contig_stats {  /* of the last sage2ov_contigs_build; spell_ms grows with every string spelled since */
+    uint64_t contigs, written, bases, longest;      /* rows; rows with contig_length >= threshold; their summed contig_length; contig_length of row 1 */
+    uint64_t n50, n50_ordinal, n90, n90_ordinal;
+    uint64_t covered, gaps, n_bases, inconsistent, wrapped;
+    double   select_ms, sort_ms, layout_ms, spell_ms;          /* HIP events; spell_ms: the spelling kernel alone */
+} sage2ov_contig_stats;
+/* builds the table and where every string begins, in HBM; spells nothing.  SAGE2OV_ERR_ARG without a step-4 graph, SAGE2OV_ERR_DEVICE on a device-less context,
+ * SAGE2OV_ERR_LIMIT for a string of 2^32 characters or 2^36 in all.  The table goes with the graph and the read set and when the flows change; the calls below build it
+ * when it is stale, with the threshold and genome size of the last build (0, 0 before any).  Not sharded: a context with world > 1 behaves as a single one. */
+int sage2ov_contigs_build(sage2ov_ctx* ctx, uint32_t threshold, uint64_t genome_size);
+int sage2ov_contigs_count(sage2ov_ctx* ctx, uint64_t* n, uint64_t* total_string_bases);
+/* the rows in table order; cap below their number: SAGE2OV_ERR_ARG, nothing written */
+int sage2ov_contigs_export(sage2ov_ctx* ctx, sage2ov_contig* out, uint64_t cap);
+/* the whole strings of rows [first, first + count), one after the other, and count + 1 offsets into `out`.  cap below their summed length, or a range outside the table:
+ * SAGE2OV_ERR_ARG, nothing written.  The device buffer has the size of the range (every row rounded up to 16 bytes): the caller bounds the memory by the range. */
+int sage2ov_contigs_sequences(sage2ov_ctx* ctx, uint64_t first, uint64_t count, char* out, uint64_t cap, uint64_t* offsets);
+/* P_contig.fasta (is_scaffold 0) or P_scaffold.fasta's text (1: ">scaffold_"), spelled in ranges of at most SAGE2OV_CONTIG_RANGE_BYTES (a longer string is a range
+ * of its own); a range is formatted while the next one is spelled */
+#define SAGE2OV_CONTIG_RANGE_BYTES (64u << 20)
+int sage2ov_contigs_save(sage2ov_ctx* ctx, const char* path, int is_scaffold);
+int sage2ov_contig_stats_get(const sage2ov_ctx* ctx, sage2ov_contig_stats* out);
+
 /* diagnostic: table census {occupied, inline, claimed-but-unfilled, zero-tag, entries in short CSR buckets} */
 int sage2ov_debug_table(sage2ov_ctx* ctx, uint64_t* out5);
 /* diagnostic: device memory {free now, total, LOWEST free seen at the library's sampling points since the context was created (end of step 1, the index

@@ -84,6 +84,22 @@ class SupportStats(C.Structure):
                 ("roles_ms", C.c_double), ("scan_ms", C.c_double), ("records_ms", C.c_double), ("sort_ms", C.c_double), ("reduce_ms", C.c_double)]
 
 
+# sage2ov_contig (48 bytes): one row of the contig table
+CONTIG_DTYPE = np.dtype([("from", np.uint32), ("to", np.uint32), ("pair", np.uint32), ("edge_length", np.uint32), ("string_length", np.uint32), ("contig_length", np.uint32),
+                         ("start", np.uint32), ("gap_count", np.uint32), ("n_count", np.uint32), ("flow", np.float32), ("type", np.uint8), ("pad", np.uint8, (7,))])
+
+
+class Contig(C.Structure):
+    _fields_ = [("from_", C.c_uint32), ("to", C.c_uint32), ("pair", C.c_uint32), ("edge_length", C.c_uint32), ("string_length", C.c_uint32), ("contig_length", C.c_uint32),
+                ("start", C.c_uint32), ("gap_count", C.c_uint32), ("n_count", C.c_uint32), ("flow", C.c_float), ("type", C.c_uint8), ("pad", C.c_uint8 * 7)]
+
+
+class ContigStats(C.Structure):
+    _fields_ = [("contigs", C.c_uint64), ("written", C.c_uint64), ("bases", C.c_uint64), ("longest", C.c_uint64), ("n50", C.c_uint64), ("n50_ordinal", C.c_uint64),
+                ("n90", C.c_uint64), ("n90_ordinal", C.c_uint64), ("covered", C.c_uint64), ("gaps", C.c_uint64), ("n_bases", C.c_uint64), ("inconsistent", C.c_uint64),
+                ("wrapped", C.c_uint64), ("select_ms", C.c_double), ("sort_ms", C.c_double), ("layout_ms", C.c_double), ("spell_ms", C.c_double)]
+
+
 class OverlapStats(C.Structure):
     _fields_ = [("verified_overlaps", C.c_uint64), ("contained_extension", C.c_uint64), ("contained_size", C.c_uint64),
                 ("left_to_explore", C.c_uint64), ("edges_inserted", C.c_uint64), ("transitive_removed", C.c_uint64),
@@ -391,6 +407,44 @@ class Context:
     def support_stats(self) -> SupportStats:
         s = SupportStats()
         self._chk(lib().sage2ov_support_stats_get(self._h, C.byref(s)))
+        return s
+
+    # ---- OverlapGraph::printGraph / saveContigsToFile (overlapGraph.cpp:507-784): the contigs of the resident step-4 graph
+    def contigs_build(self, threshold=0, genome_size=0):
+        """builds the table (the calls below build it when it is stale, with the last threshold and genome size); threshold 0: the reference's contigLengthThreshold"""
+        self._chk(lib().sage2ov_contigs_build(self._h, C.c_uint32(threshold), C.c_uint64(genome_size)))
+
+    def contigs_count(self):
+        """(rows, summed string length)"""
+        n, t = C.c_uint64(0), C.c_uint64(0)
+        self._chk(lib().sage2ov_contigs_count(self._h, C.byref(n), C.byref(t)))
+        return n.value, t.value
+
+    def contigs(self) -> np.ndarray:
+        """the rows (CONTIG_DTYPE) in table order: edge length descending, then `from` ascending, then newest first"""
+        n = self.contigs_count()[0]
+        out = np.zeros(n, dtype=CONTIG_DTYPE)
+        self._chk(lib().sage2ov_contigs_export(self._h, C.c_void_p(out.ctypes.data), C.c_uint64(n)))
+        return out
+
+    def contig_sequences(self, first=0, count=None, string_lengths=None):
+        """(uint8 array of the whole strings of rows [first, first + count) one after the other, count + 1 uint64 offsets); the device buffer is sized by the range.
+        string_lengths: the table's column, when the caller has it already"""
+        if string_lengths is None:
+            string_lengths = self.contigs()["string_length"]
+        count = len(string_lengths) - first if count is None else count
+        need = int(np.asarray(string_lengths[first:first + count], dtype=np.uint64).sum())
+        out = np.zeros(need, dtype=np.uint8); off = np.zeros(count + 1, dtype=np.uint64)
+        self._chk(lib().sage2ov_contigs_sequences(self._h, C.c_uint64(first), C.c_uint64(count), C.c_void_p(out.ctypes.data), C.c_uint64(need), C.c_void_p(off.ctypes.data)))
+        return out, off
+
+    def contigs_save(self, path, scaffold=False):
+        """P_contig.fasta as saveContigsToFile writes it (scaffold: P_scaffold.fasta's record names)"""
+        self._chk(lib().sage2ov_contigs_save(self._h, path.encode(), C.c_int(1 if scaffold else 0)))
+
+    def contig_stats(self) -> ContigStats:
+        s = ContigStats()
+        self._chk(lib().sage2ov_contig_stats_get(self._h, C.byref(s)))
         return s
 
     # ---- step 2

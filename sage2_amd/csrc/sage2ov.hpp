@@ -176,6 +176,24 @@ public:
     sage2ov_simplify_stats simplify() { ctx_->check(sage2ov_graph_simplify(ctx_->get())); sage2ov_simplify_stats s{}; ctx_->check(sage2ov_simplify_stats_get(ctx_->get(), &s)); return s; }
     void loadCompositeGraphFromFile(const std::string& path) { ctx_->check(sage2ov_graph_load_composite(ctx_->get(), path.c_str())); }   // overlapGraph.cpp:371 for P.graph4 / 5 / 6
     void saveSimplifiedGraphInFile(const std::string& path) { ctx_->check(sage2ov_graph4_save(ctx_->get(), path.c_str())); }   // what step 5 loads (main.cpp:196)
+    // printGraph (overlapGraph.cpp:507-593) without the .gdl: writes fileName + ".fasta" over the graph the context holds; the statistics the reference logs come back.
+    // contigLengthThreshold 0: the reference's own (:32)
+    sage2ov_contig_stats printGraph(const std::string& fileName, bool isScaff = false, uint64_t genomeSize = 0, uint32_t contigLengthThreshold = 0) {
+        ctx_->check(sage2ov_contigs_build(ctx_->get(), contigLengthThreshold, genomeSize));
+        ctx_->check(sage2ov_contigs_save(ctx_->get(), (fileName + ".fasta").c_str(), isScaff ? 1 : 0));
+        sage2ov_contig_stats s{}; ctx_->check(sage2ov_contig_stats_get(ctx_->get(), &s)); return s;
+    }
+    std::vector<sage2ov_contig> contigs() {
+        uint64_t n = 0; ctx_->check(sage2ov_contigs_count(ctx_->get(), &n, nullptr));
+        std::vector<sage2ov_contig> out(n); ctx_->check(sage2ov_contigs_export(ctx_->get(), out.data(), n)); return out;
+    }
+    // the whole strings of rows [first, first + count) of contigs(), one after the other; offsets: count + 1 values
+    std::string contigSequences(uint64_t first, uint64_t count, std::vector<uint64_t>& offsets) {
+        const std::vector<sage2ov_contig> rows = contigs(); uint64_t need = 0;
+        for (uint64_t i = first; i < first + count && i < rows.size(); i++) need += rows[i].string_length;
+        std::string out(need, 'N'); offsets.assign(count + 1, 0);
+        ctx_->check(sage2ov_contigs_sequences(ctx_->get(), first, count, &out[0], need, offsets.data())); return out;
+    }
     EconomyGraph* economyObj;
 private:
     Context* ctx_;

@@ -1,6 +1,7 @@
 // sage2_amd/csrc/sage2ov_cli.cpp -- `sage2ov`: drop-in producer of <outdir>/<prefix>.reads and <prefix>.graph3.
 // Mimics the SAGE2 command line for steps 1-3 (main.cpp:384-521): -f | -l, -k, -o, -p, -i, -m, -M, -s, -d, -h.
 // Continue with the unchanged reference:  SAGE2 -f reads.fa -k K -o out -p P -i P -m 4      (main.cpp:141-148)
+// --contigs [--genomeSize G] also writes <prefix>_contig.fasta, printGraph's file (main.cpp:246), for the graph after step 4 or a P.graph4 / 5 / 6 (-m 5 | 6 | 7).
 #include <getopt.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -28,14 +29,16 @@ static void printListOfArgs() {
             "\t-i|--inputPrefix <string>\t[prefix]\n\t-m|--minStep <int>\t[1]\n\t-M|--maxStep <int>\t[3] (4 = simplified graph P.graph4; steps 5-7: run SAGE2 -m 5 on the files written here)\n"
             "\t-s|--saveAll\n\t-d|--debug\n\t-g|--gpu <int>\tHIP device ordinal [0]\n"
             "\t-G|--gpus <int>\tsteps 2-3 on this many GPUs of the node (devices gpu .. gpu+G-1): reads and index replicated, probe pass\n"
-            "\t\t\trange-partitioned, records / flags / edge and survivor buckets exchanged with RCCL over xGMI [1]\n\t-h|--help\n\n";
+            "\t\t\trange-partitioned, records / flags / edge and survivor buckets exchanged with RCCL over xGMI [1]\n"
+            "\t--contigs\t\talso write <prefix>_contig.fasta (printGraph): after step 4, or with -m 5|6|7 from <inputPrefix>.reads and <inputPrefix>.graph4|5|6\n"
+            "\t--genomeSize <int>\tgenome size for the N50 / N90 of --contigs [0]\n\t-h|--help\n\n";
 }
 static string trimBack(string s, const string& pat) { size_t e = s.find_last_not_of(pat); return e == string::npos ? "" : s.substr(0, e + 1); }
 static double now() { return chrono::duration<double>(chrono::steady_clock::now().time_since_epoch()).count(); }
 
 int main(int argc, char* argv[]) {
     const double tMain = now(); const bool timing = getenv("SAGE2OV_TIMING") != nullptr;
-    int minStep = 1, maxStep = 3, gpu = 0, gpus = 1, failRank = -1; bool shareGpu = false, forceMulti = false; unsigned minOverlap = 0; bool saveAll = false, debugging = false, fFlag = false, lFlag = false;
+    int minStep = 1, maxStep = 3, gpu = 0, gpus = 1, failRank = -1; bool shareGpu = false, forceMulti = false; unsigned minOverlap = 0; bool contigs = false; unsigned long long genomeSize = 0; bool saveAll = false, debugging = false, fFlag = false, lFlag = false;
     string fileInput, listInput, outputDir, prefixName = "untitled", inputPrefix;
     static struct option opts[] = {{"help", no_argument, 0, 'h'}, {"fileInput", required_argument, 0, 'f'}, {"minOverlap", required_argument, 0, 'k'},
         {"listInput", required_argument, 0, 'l'}, {"outputDir", required_argument, 0, 'o'}, {"prefix", required_argument, 0, 'p'},
@@ -43,6 +46,7 @@ int main(int argc, char* argv[]) {
         {"saveAll", no_argument, 0, 's'}, {"debug", no_argument, 0, 'd'}, {"gpu", required_argument, 0, 'g'}, {"gpus", required_argument, 0, 'G'},
         {"share-gpu", no_argument, 0, 1001},      // rehearsal: all ranks on device `gpu`, exchanges by device copies instead of RCCL (a box with fewer GPUs than ranks)
         {"fail-rank", required_argument, 0, 1003},  // tests: this rank of a multi-GPU run fails before its first step (the run must end non-zero, not hang)
+        {"contigs", no_argument, 0, 1004}, {"genomeSize", required_argument, 0, 1005},
         {"force-multi", no_argument, 0, 1002},    // the multi-GPU code path (RCCL communicator, the four exchanges) even with one GPU
         {0, 0, 0, 0}};
     int c, oi = 0;
@@ -64,6 +68,8 @@ int main(int argc, char* argv[]) {
             case 1001: shareGpu = true; break;
             case 1002: forceMulti = true; break;
             case 1003: failRank = atoi(optarg); break;
+            case 1004: contigs = true; break;
+            case 1005: genomeSize = strtoull(optarg, nullptr, 10); break;
             case '?': cout << "\n"; exit(0);
             default: cout << "[ERROR] Wrong command line arguments!\n\n"; exit(0);
         }
@@ -75,7 +81,7 @@ int main(int argc, char* argv[]) {
     if (maxStep < minStep) { cout << "[ERROR] maxStep should not be smaller than minStep!\n\n"; allSet = false; }
     if (inputPrefix == "") inputPrefix = prefixName;
     if (!allSet) { cout << "\n"; printUsage(); cout << "(For more information run sage2ov -h)\n\n"; exit(0); }
-    if (minStep > 4) { cout << "[ERROR] sage2ov implements steps 1-4; continue with: SAGE2 -m " << minStep << " -i " << inputPrefix << " ...\n"; exit(0); }
+    if (minStep > 4 && !contigs) { cout << "[ERROR] sage2ov implements steps 1-4; continue with: SAGE2 -m " << minStep << " -i " << inputPrefix << " ...\n"; exit(0); }
     (void)debugging;
     if (outputDir != "") { string cmd = "mkdir -p " + outputDir; if (system(cmd.c_str())) {} }     // utils.cpp:45
     ofstream logStream((outputDir + prefixName + ".log").c_str());
@@ -105,6 +111,12 @@ int main(int argc, char* argv[]) {
             loaderObj.loadReadsFromFile(outputDir + inputPrefix + ".reads");                 // main.cpp:70-74 / :101-104
             logStream << "\tNumber of unique reads: " << loaderObj.numberOfUniqueReads << " (loaded)\n";
         }
+        auto writeContigs = [&](OverlapGraph& graphObj) {                                     // main.cpp:246: printGraph(outputDir + prefix + "_contig", 0)
+            double tw = now();
+            auto cs = graphObj.printGraph(outputDir + prefixName + "_contig", false, genomeSize);
+            logStream << "\t" << prefixName << "_contig.fasta written in " << now() - tw << " sec.\n\t  Number of Contigs: " << cs.contigs << " (" << cs.written << " in the file)\n\t     Longest Contig: " << cs.longest
+                      << "\n\t     Genome Covered: " << cs.covered << " BP\n\t                N50: " << cs.n50 << " BP (" << cs.n50_ordinal << ")\n\t                N90: " << cs.n90 << " BP (" << cs.n90_ordinal << ")\n";
+        };
         auto step4 = [&](OverlapGraph& graphObj) {                                            // main.cpp:134-181
             double t4 = now();
             auto ss = graphObj.simplify();
@@ -112,8 +124,13 @@ int main(int argc, char* argv[]) {
                       << "\n\tLoop iterations: " << ss.loop_iterations << "\n\tEdges left: " << ss.edges << " carrying " << ss.reads_on_edges << " reads\n\tStep 4 in " << now() - t4
                       << " sec (device " << ss.device_ms / 1000.0 << ").\n";
             { double tw = now(); graphObj.saveSimplifiedGraphInFile(outputDir + prefixName + ".graph4"); logStream << "\t" << prefixName << ".graph4 written in " << now() - tw << " sec.\n"; }   // the file step 5 loads (main.cpp:196)
+            if (contigs) writeContigs(graphObj);
         };
-        if (minStep == 4) {                                                                   // main.cpp:141-148
+        if (minStep > 4) {                                                                    // --contigs on the graph an earlier run or the reference left: P.graph4 / 5 / 6
+            OverlapGraph graphObj(&loaderObj);
+            graphObj.loadCompositeGraphFromFile(outputDir + inputPrefix + ".graph" + to_string(minStep - 1));
+            writeContigs(graphObj);
+        } else if (minStep == 4) {                                                            // main.cpp:141-148
             OverlapGraph graphObj(&loaderObj);
             graphObj.loadOverlapGraphFromFile(outputDir + inputPrefix + ".graph3");
             step4(graphObj);
@@ -177,7 +194,7 @@ int main(int argc, char* argv[]) {
             }
         }
         if (timing) fprintf(stderr, "[cli] until the last file is written %8.1f ms\n", 1e3 * (now() - tMain));
-        if (maxStep > 4) {
+        if (maxStep > 4 && minStep <= 4) {
             cout << "sage2ov: steps 1-4 done; continue with the reference: SAGE2 " << (listInput != "" ? "-l " + listInput : "-f " + fileInput) << " -k " << minOverlap
                  << " -o " << (outputDir == "" ? "." : outputDir) << " -p " << prefixName << " -i " << prefixName << " -m 5 -M " << maxStep << "\n";
         }

@@ -110,6 +110,7 @@ struct Device {
     // hits written out by the initial pass (k_probe_fast<..., TAIL = 2> on noisy data, one context probing everything): the reduce phase filters them
     struct PreHits { bool valid = false; Hit* hits = nullptr; u64 cap = 0, used = 0; u64* base = nullptr; } pre;
     void* support = nullptr;     // the mate-pair supports of edge pairs (dev_support_build; Support): allocations of its own, dropped with the read-to-edge table and the mate flags
+    void* contigs = nullptr;     // the contig table and the spelling buffers (dev_contigs_build; Contigs): allocations of its own, dropped with the graph and the read set
     void* s4keep = nullptr;      // step 4: the simplified graph stays in HBM until the next call (S4Keep)
     // step 4: blocks a call released, kept for the next call (it asks for the same ~50 sizes; fresh HBM costs ~50 ms per GB to map, 0.7 s per call at BASELINE
     // configs[2]).  Emptied when the read set changes, when the workspace arena runs out of memory, and never filled in memory-diet mode.
@@ -229,6 +230,7 @@ static void mem_sample(Device* d) { size_t fr = 0, to = 0; if (hipMemGetInfo(&fr
 #include "kernels_mates.inc"
 #include "kernels_readmap.inc"
 #include "kernels_support.inc"
+#include "kernels_contig.inc"
 
 // =============================================================================================
 // host primitives: what the launchers below share (grids, counters, transient buffers, a stream timer, scan, radix sort, heads)
@@ -382,6 +384,7 @@ Device* dev_create(int ordinal, const Options& opt, std::string& err) {
 static void mates_release(Device* d);
 static void free_reads(Device* d) {
     dev_readmap_release(d);                                             // (read ids again)
+    dev_contigs_release(d);                                             // (and the reads the strings are spelled from)
     rr_staging_release(d);                     // (pinned host buffers sized by the previous read set)
     hipFree(d->reads);
     hipFree(d->findDir); d->findDir = nullptr; d->findDirBits = 0;      // (the lookup directory describes the read set that goes)
@@ -2106,7 +2109,7 @@ struct S4Mem {                                   // released on every exit path 
 }
 #define S4GET(var, type, n) type* var = mem.get<type>((n), err); if (!var) return SAGE2OV_ERR_NOMEM;
 struct S4Keep { S4Mem mem; S4Graph g; u32 nh = 0; u64 listUsed = 0; float* flow = nullptr; };      // flow: one float per half-edge (null: every flow is 0, the state after step 4)
-void dev_simplify_release(Device* d) { dev_readmap_release(d); if (d->s4keep) { hipSetDevice(d->ordinal); delete (S4Keep*)d->s4keep; d->s4keep = nullptr; } }
+void dev_simplify_release(Device* d) { dev_readmap_release(d); dev_contigs_release(d); if (d->s4keep) { hipSetDevice(d->ordinal); delete (S4Keep*)d->s4keep; d->s4keep = nullptr; } }
 
 int dev_simplify(Device* d, SimplifiedGraph& out, std::string& err) {
     HIPCHK(hipSetDevice(d->ordinal));
@@ -2625,6 +2628,123 @@ int dev_support_export(Device* d, uint64_t* key, uint32_t* support, std::string&
     HIPCHK(hipSetDevice(d->ordinal));
     const Support* S = (const Support*)d->support; if (!S) { err = "mate-pair supports: not built"; return SAGE2OV_ERR_INTERNAL; }
     if (S->E) { HIPCHK(hipMemcpy(key, S->key, S->E * sizeof(u64), hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(support, S->sup, S->E * sizeof(u32), hipMemcpyDeviceToHost)); }
+    return 0;
+}
+
+// =============================================================================================
+// the contig table and the contig strings (kernels_contig.inc; OverlapGraph::printGraph / saveContigsToFile, overlapGraph.cpp:507-784)
+// =============================================================================================
+struct Contigs {
+    CtRow* rows = nullptr; u32* chunkOff = nullptr; u32* dScan = nullptr; u64 R = 0, chunks = 0;
+    struct Buf { uint4* dev = nullptr; char* host = nullptr; u64 cap = 0; hipEvent_t a = nullptr, b = nullptr, done = nullptr; } buf[2];      // a range is spelled into one while the caller formats the other
+    ~Contigs() { hipFree(rows); hipFree(chunkOff); hipFree(dScan);
+                 for (auto& B : buf) { hipFree(B.dev); if (B.host) hipHostFree(B.host); if (B.a) hipEventDestroy(B.a); if (B.b) hipEventDestroy(B.b); if (B.done) hipEventDestroy(B.done); } }
+};
+void dev_contigs_release(Device* d) { if (d->contigs) { hipSetDevice(d->ordinal); hipStreamSynchronize(d->stream); delete (Contigs*)d->contigs; d->contigs = nullptr; } }
+static int contigs_nomem(std::string& err) { err = "contigs: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+// whichever read store is resident: the id-ordered one, or (memory-diet mode) the locality-ordered one through posOf
+static bool contig_reads(Device* d, CtReads& R) {
+    const bool byPos = d->reads == nullptr;
+    if (byPos && !(d->readsLoc && d->posOf)) return false;
+    R = CtReads{byPos ? d->readsLoc : d->reads, d->posOf, byPos ? 1 : 0, d->S, (u32)d->uniL, (u32)d->N, slot_len_mask(d->S)};
+    return true;
+}
+int dev_contigs_build(Device* d, uint32_t threshold, std::vector<ContigRow>& out, ContigBuildStats* st, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    if (!d->s4keep) { err = "contigs: no step-4 graph on the device"; return SAGE2OV_ERR_ARG; }
+    dev_contigs_release(d);
+    CtReads Rd; if (!contig_reads(d, Rd)) { err = "contigs: no read store on the device"; return SAGE2OV_ERR_ARG; }
+    const S4Keep& K = *(S4Keep*)d->s4keep; const S4Graph& g = K.g; const u32 nh = K.nh; const u64 nl = K.listUsed; const u32 N = (u32)d->N; hipStream_t sm = d->stream;
+    std::unique_ptr<Contigs> C(new Contigs());
+    *st = ContigBuildStats(); out.clear();
+    DevTmp B; StreamLap lap(sm); HIPCHK(lap.create());
+    const dim3 b256(256);
+    // ---- select and compact
+    HIPCHK(lap.start());
+    u32* sel = B.get<u32>(nh); u32* pos = B.get<u32>(nh); unsigned long long* ctr = B.get<unsigned long long>(2);
+    u64* partial = B.get<u64>(scan_partial_words(std::max<u64>(nl + 1, nh)));
+    if (!sel || !pos || !ctr || !partial) return contigs_nomem(err);
+    HIPCHK(hipMemsetAsync(ctr, 0, 2 * sizeof(unsigned long long), sm));
+    if (nh) hipLaunchKernelGGL(k_ct_select, dim3(grid_for(nh, 256)), b256, 0, sm, g, nh, (u32)threshold, sel, ctr);
+    u64 R = 0; { const int rc = scan_u32(d, sel, nh, pos, partial, &R, err); if (rc) return rc; }
+    HIPCHK(lap.stop(st->select_ms));
+    if (!R) { d->contigs = C.release(); return 0; }
+    unsigned long long hc[2] = {0, 0}; HIPCHK(hipMemcpy(hc, ctr, sizeof hc, hipMemcpyDeviceToHost));
+    const u32 longest = (u32)hc[0];
+    // ---- order: (len descending, from ascending, index descending) by stable passes over the digits of (longest - len, from) that can be non-zero
+    HIPCHK(lap.start());
+    u64* key = B.get<u64>(R); u32* hs = B.get<u32>(R); u32* rowH = B.get<u32>(R);
+    if (!key || !hs || !rowH) return contigs_nomem(err);
+    hipLaunchKernelGGL(k_ct_keys, dim3(grid_for(nh, 256)), b256, 0, sm, g, nh, sel, pos, (u32)R, longest, key, hs);
+    int shifts[8], np = 0; { int bn = 0, bl = 0; while (((u64)N >> bn) != 0) bn++; while (((u64)longest >> bl) != 0) bl++;
+                             for (int p = 0; p < 8; p++) { const int lo = 8 * p; if (lo < 32 ? lo < bn : lo - 32 < bl) shifts[np++] = lo; } }
+    u64* ks = nullptr; u32* vs = nullptr; MateStats ms;
+    { const int rc = mate_sort(d, B, key, (u32)R, shifts, np, &ks, &vs, &ms, err); if (rc) return rc; }
+    hipLaunchKernelGGL(k_ct_gather, dim3(grid_for(R, 256)), b256, 0, sm, vs, hs, (u32)R, rowH);
+    HIPCHK(hipGetLastError());
+    HIPCHK(lap.stop(st->sort_ms));
+    st->passes = ms.passes;
+    B.release(sel); B.release(pos); B.release(vs); B.release(hs); if (ks != key) B.release(ks); B.release(key);
+    // ---- layout: the running distPrevious (kept for the spelling), the gap and N counts, the rows, where their chunks begin
+    HIPCHK(lap.start());
+    u32* tmp = B.get<u32>(nl + 1); u32* gap = B.get<u32>(nl + 1); u32* ns = B.get<u32>(nl + 1); u32* gScan = B.get<u32>(nl + 1); u32* nScan = B.get<u32>(nl + 1); u32* deg = B.get<u32>((u64)N + 2);
+    u32* chunks = B.get<u32>(R + 1);
+    C->dScan = (u32*)DevTmp::alloc((nl + 1) * sizeof(u32)); C->rows = (CtRow*)DevTmp::alloc(R * sizeof(CtRow)); C->chunkOff = (u32*)DevTmp::alloc((R + 1) * sizeof(u32));
+    if (!tmp || !gap || !ns || !gScan || !nScan || !deg || !chunks || !C->dScan || !C->rows || !C->chunkOff) return contigs_nomem(err);
+    HIPCHK(hipMemsetAsync(deg, 0, ((u64)N + 2) * sizeof(u32), sm));
+    HIPCHK(hipMemsetAsync(tmp + nl, 0, sizeof(u32), sm)); HIPCHK(hipMemsetAsync(gap + nl, 0, sizeof(u32), sm)); HIPCHK(hipMemsetAsync(ns + nl, 0, sizeof(u32), sm));
+    hipLaunchKernelGGL(k_ct_degree, dim3(grid_for(nh, 256)), b256, 0, sm, g, nh, deg);
+    if (nl) {
+        hipLaunchKernelGGL(k_rm_dprev, dim3(grid_for_capped(nl, 256)), b256, 0, sm, g.lists, nl, tmp);
+        hipLaunchKernelGGL(k_ct_gaps, dim3(grid_for_capped(nl, 256)), b256, 0, sm, g.lists, nl, Rd, gap, ns);
+    }
+    { const int rc = scan_u32(d, tmp, nl + 1, C->dScan, partial, nullptr, err); if (rc) return rc; }
+    { const int rc = scan_u32(d, gap, nl + 1, gScan, partial, nullptr, err); if (rc) return rc; }
+    { const int rc = scan_u32(d, ns, nl + 1, nScan, partial, nullptr, err); if (rc) return rc; }
+    hipLaunchKernelGGL(k_ct_layout, dim3(grid_for(R + 1, 256)), b256, 0, sm, g, rowH, (u32)R, Rd, deg, C->dScan, gScan, nScan, nl, C->rows, chunks);
+    u64 total = 0; { const int rc = scan_u32(d, chunks, R + 1, C->chunkOff, partial, &total, err); if (rc) return rc; }
+    HIPCHK(lap.stop(st->layout_ms));
+    static_assert(sizeof(CtRow) == sizeof(ContigRow), "the row as the host takes it");
+    out.resize(R); HIPCHK(hipMemcpy(out.data(), C->rows, R * sizeof(CtRow), hipMemcpyDeviceToHost));
+    u64 sum = 0;
+    for (const ContigRow& r : out) { if (r.flags & CT_LIMIT) { err = "contigs: a contig string of 2^32 characters or more"; return SAGE2OV_ERR_LIMIT; } sum += ((u64)r.string_length + 15) >> 4; }
+    if (sum != total || total >= (1ull << 32) - RS_TILE) { err = "contigs: 2^36 characters or more in all"; return SAGE2OV_ERR_LIMIT; }
+    C->R = R; C->chunks = total;
+    d->contigs = C.release();
+    return 0;
+}
+// rows [first, first + count), whose chunks are [chunk0, chunk0 + nChunks) of the table, into buffer `which` (0 or 1) and on to its pinned host image; nothing is waited for
+int dev_contigs_spell_begin(Device* d, int which, uint64_t first, uint64_t count, uint64_t chunk0, uint64_t nChunks, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    Contigs* C = (Contigs*)d->contigs; if (!C || !d->s4keep) { err = "contigs: not built"; return SAGE2OV_ERR_INTERNAL; }
+    if (which < 0 || which > 1 || first + count > C->R || chunk0 + nChunks > C->chunks) { err = "contigs: range outside the table"; return SAGE2OV_ERR_INTERNAL; }
+    CtReads Rd; if (!contig_reads(d, Rd)) { err = "contigs: no read store on the device"; return SAGE2OV_ERR_ARG; }
+    Contigs::Buf& B = C->buf[which];
+    if (!B.a) { HIPCHK(hipEventCreate(&B.a)); HIPCHK(hipEventCreate(&B.b)); HIPCHK(hipEventCreate(&B.done)); }
+    if (B.cap < nChunks) {
+        HIPCHK(hipStreamSynchronize(d->stream));
+        hipFree(B.dev); if (B.host) hipHostFree(B.host); B.dev = nullptr; B.host = nullptr; B.cap = 0;
+        B.dev = (uint4*)DevTmp::alloc(nChunks * 16); if (!B.dev) return contigs_nomem(err);
+        if (hipHostMalloc((void**)&B.host, nChunks * 16, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); B.host = nullptr; err = "contigs: out of pinned host memory"; return SAGE2OV_ERR_NOMEM; }
+        B.cap = nChunks;
+    }
+    const S4Keep& K = *(S4Keep*)d->s4keep;
+    HIPCHK(hipEventRecord(B.a, d->stream));
+    if (nChunks) hipLaunchKernelGGL(k_ct_spell, dim3(grid_for(nChunks, 256)), dim3(256), 0, d->stream, K.g, Rd, C->rows, C->chunkOff, (u32)first, (u32)count, C->dScan, K.listUsed, B.dev, (u32)nChunks);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(B.b, d->stream));
+    if (nChunks) HIPCHK(hipMemcpyAsync(B.host, B.dev, nChunks * 16, hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipEventRecord(B.done, d->stream));
+    return 0;
+}
+// the host image of buffer `which`, once its copy has arrived: a row begins 16 * (its first chunk - chunk0) bytes in; ms += the kernel's time
+int dev_contigs_spell_wait(Device* d, int which, const char** image, double* ms, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    Contigs* C = (Contigs*)d->contigs; if (!C || which < 0 || which > 1 || !C->buf[which].done) { err = "contigs: nothing was spelled"; return SAGE2OV_ERR_INTERNAL; }
+    Contigs::Buf& B = C->buf[which];
+    HIPCHK(hipEventSynchronize(B.done));
+    float t = 0; if (hipEventElapsedTime(&t, B.a, B.b) == hipSuccess) *ms += t; else (void)hipGetLastError();
+    *image = B.host;
     return 0;
 }
 

@@ -123,7 +123,11 @@ struct sage2ov_ctx {
     bool supValid = false;                             // the table is of the present graph, flows, mates and estimate (it also needs `estimated`)
     sage2ov_support_stats sstats{}; std::vector<sage2ov_support> supports; bool supOnHost = false;
     void supports_forget() { supValid = supOnHost = false; supports.clear(); sstats = sage2ov_support_stats{}; }
-    void readmap_forget() { rmValid = estimated = false; pairOrdinal.clear(); rmstats = sage2ov_readmap_stats{}; supports_forget(); }      // the graph or the read set goes
+    // ---- the contigs (sage2ov_contigs_*): rows and layout are built on the device and kept here in table order; threshold and genome size as the last build was asked
+    bool ctgValid = false; uint32_t ctgThreshold = 0, ctgThresholdUsed = 0; uint64_t ctgGenome = 0; sage2ov_contig_stats cstats{};
+    std::vector<ContigRow> ctgRows; std::vector<uint64_t> ctgChunk;      // ctgChunk[r]: 16-byte chunks of the device buffer in front of row r (every row begins at a chunk); R + 1 values
+    void contigs_forget() { ctgValid = false; ctgRows.clear(); ctgChunk.clear(); cstats = sage2ov_contig_stats{}; }
+    void readmap_forget() { rmValid = estimated = false; pairOrdinal.clear(); rmstats = sage2ov_readmap_stats{}; supports_forget(); contigs_forget(); }      // the graph or the read set goes
     void mates_forget(bool readSetGoes = true) {       // the read set goes: its ids mean nothing any more (the device drops its part in free_reads) -- or sage2ov_mates_clear
         if (readSetGoes) { readmap_forget(); readsGen++; } else estimated = false;
         for (auto& L : mates) L = MateLib();
@@ -1990,7 +1994,7 @@ int sage2ov_graph_flow_import(sage2ov_ctx* c, const float* flow, uint64_t n) {
     if (n && !flow) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_flow_import: null argument");
     std::vector<float> f(c->g4.n_half_edges, 0.f);
     for (size_t x = 0; x < first.size(); x++) { f[first[x]] = flow[2 * x]; f[first[x] ^ 1u] = flow[2 * x + 1]; }
-    c->supports_forget();
+    c->supports_forget(); c->contigs_forget();
     { const int rc = dev_flow_set(c->device(), f.data(), f.size(), c->err); if (rc) return rc; }
     c->g4.flow = std::move(f);
     return SAGE2OV_OK;
@@ -2026,6 +2030,133 @@ int sage2ov_mates_supports_export(sage2ov_ctx* c, uint32_t min_support, sage2ov_
     return SAGE2OV_OK;
 }
 int sage2ov_support_stats_get(const sage2ov_ctx* c, sage2ov_support_stats* o) { if (!c || !o) return SAGE2OV_ERR_ARG; *o = c->sstats; return SAGE2OV_OK; }
+
+// ---- OverlapGraph::printGraph / saveContigsToFile (overlapGraph.cpp:507-784); the semantics are stated in sage2ov.h
+namespace {
+static_assert(sizeof(sage2ov_contig) == 48, "sage2ov_contig is 48 bytes");
+constexpr uint32_t CONTIG_WRAPPED = 2;                                                // ContigRow::flags
+int contigs_ensure(sage2ov_ctx* c, const char* who) {
+    { const int rc = readmap_check(c, who); if (rc) return rc; }
+    return c->ctgValid ? SAGE2OV_OK : sage2ov_contigs_build(c, c->ctgThreshold, c->ctgGenome);
+}
+bool contig_written(const sage2ov_ctx* c, const ContigRow& r) { return !(r.flags & CONTIG_WRAPPED) && r.contig_length >= c->ctgThresholdUsed; }
+// the bound of one range of sage2ov_contigs_save in 16-byte chunks (SAGE2OV_TEST_CONTIG_RANGE=<bytes>: lowered, so that the tests' few kilobases make many ranges)
+uint64_t contig_range_chunks(const sage2ov_ctx* c) {
+    const long long v = c->opt.num("SAGE2OV_TEST_CONTIG_RANGE", (long long)SAGE2OV_CONTIG_RANGE_BYTES);
+    return std::max<uint64_t>(1, (uint64_t)std::max<long long>(16, std::min<long long>(v, (long long)SAGE2OV_CONTIG_RANGE_BYTES)) / 16);
+}
+// one FASTA record (overlapGraph.cpp:730-741): ordinal from 1, the running counters as they stand after this row
+void contig_record(const sage2ov_ctx* c, uint64_t ordinal, const ContigRow& r, const char* str, bool scaffold, uint64_t gaps, uint64_t ns, std::string& o) {
+    const SimplifiedGraph& g = c->g4; char buf[256];
+    const float flow = g.flow.empty() ? 0.f : g.flow[r.h];
+    const int n = snprintf(buf, sizeof buf, ">%s_%llu flow=%g Edge length=%u String length: %u e(%u, %u) gapCount=%llu nCount=%llu\n", scaffold ? "scaffold" : "contig", (unsigned long long)ordinal,
+                           (double)flow, r.contig_length, r.string_length, g.from[r.h], g.to[r.h], (unsigned long long)gaps, (unsigned long long)ns);
+    o.append(buf, (size_t)n);
+    for (uint64_t at = r.start, left = r.contig_length; left > 0;) {                   // substr(startIndex, 60) cuts at the string's end
+        const uint64_t want = std::min<uint64_t>(60, left), have = at < r.string_length ? std::min<uint64_t>(want, r.string_length - at) : 0;
+        o.append(str + at, (size_t)have); o.push_back('\n'); at += want; left -= want;
+    }
+}
+}  // namespace
+int sage2ov_contigs_build(sage2ov_ctx* c, uint32_t threshold, uint64_t genome_size) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    { const int rc = readmap_check(c, "sage2ov_contigs_build"); if (rc) return rc; }
+    c->contigs_forget(); c->ctgThreshold = threshold; c->ctgGenome = genome_size;
+    const uint32_t thr = threshold ? threshold : (uint32_t)(int)ceilf((float)(100 * ((double)average_read_length(c) / 100.0)));      // overlapGraph.cpp:32
+    c->ctgThresholdUsed = thr;
+    ContigBuildStats bs; { const int rc = dev_contigs_build(c->device(), thr, c->ctgRows, &bs, c->err); if (rc) { c->ctgRows.clear(); return rc; } }
+    { const int rc = pair_ordinals(c); if (rc) return rc; }                            // (the graph on the host: ends, lengths, types and flows of the rows)
+    const SimplifiedGraph& g = c->g4; const std::vector<ContigRow>& rows = c->ctgRows;
+    c->ctgChunk.assign(rows.size() + 1, 0);
+    sage2ov_contig_stats& s = c->cstats; s = sage2ov_contig_stats{};
+    s.select_ms = bs.select_ms; s.sort_ms = bs.sort_ms; s.layout_ms = bs.layout_ms;
+    uint64_t nx = 0;
+    for (size_t i = 0; i < rows.size(); i++) {
+        const ContigRow& r = rows[i];
+        c->ctgChunk[i + 1] = c->ctgChunk[i] + (((uint64_t)r.string_length + 15) >> 4);
+        s.covered += g.len[r.h]; s.gaps += r.gap_count; s.n_bases += r.n_count; s.inconsistent += r.flags & 1u; s.wrapped += (r.flags & CONTIG_WRAPPED) ? 1 : 0;
+        if (contig_written(c, r)) { s.written++; s.bases += r.contig_length; }
+        if (i == 0) s.longest = r.contig_length;
+        nx += r.contig_length;                                                         // overlapGraph.cpp:745-755
+        if (!s.n50_ordinal && nx >= genome_size / 2) { s.n50 = r.contig_length; s.n50_ordinal = i + 1; }
+        if (!s.n90_ordinal && nx >= genome_size * 9 / 10) { s.n90 = r.contig_length; s.n90_ordinal = i + 1; }
+    }
+    s.contigs = rows.size();
+    c->ctgValid = true;
+    return SAGE2OV_OK;
+}
+int sage2ov_contigs_count(sage2ov_ctx* c, uint64_t* n, uint64_t* total) {
+    if (!c || !n) return SAGE2OV_ERR_ARG;
+    { const int rc = contigs_ensure(c, "sage2ov_contigs_count"); if (rc) return rc; }
+    *n = c->ctgRows.size();
+    if (total) { uint64_t t = 0; for (const ContigRow& r : c->ctgRows) t += r.string_length; *total = t; }
+    return SAGE2OV_OK;
+}
+int sage2ov_contigs_export(sage2ov_ctx* c, sage2ov_contig* out, uint64_t cap) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    { const int rc = contigs_ensure(c, "sage2ov_contigs_export"); if (rc) return rc; }
+    if (cap < c->ctgRows.size()) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_contigs_export: the buffer holds fewer rows than the table (sage2ov_contigs_count)");
+    if (!c->ctgRows.empty() && !out) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_contigs_export: null argument");
+    const SimplifiedGraph& g = c->g4;
+    for (size_t i = 0; i < c->ctgRows.size(); i++) {
+        const ContigRow& r = c->ctgRows[i]; sage2ov_contig o{};
+        o.from = g.from[r.h]; o.to = g.to[r.h]; o.pair = c->pairOrdinal[r.h >> 1]; o.edge_length = g.len[r.h]; o.string_length = r.string_length; o.contig_length = r.contig_length;
+        o.start = r.start; o.gap_count = r.gap_count; o.n_count = r.n_count; o.flow = g.flow.empty() ? 0.f : g.flow[r.h]; o.type = g.type[r.h];
+        out[i] = o;
+    }
+    return SAGE2OV_OK;
+}
+int sage2ov_contigs_sequences(sage2ov_ctx* c, uint64_t first, uint64_t count, char* out, uint64_t cap, uint64_t* offsets) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    { const int rc = contigs_ensure(c, "sage2ov_contigs_sequences"); if (rc) return rc; }
+    const std::vector<ContigRow>& rows = c->ctgRows;
+    if (first > rows.size() || count > rows.size() - first) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_contigs_sequences: the range lies outside the table (sage2ov_contigs_count)");
+    uint64_t need = 0; for (uint64_t i = first; i < first + count; i++) need += rows[i].string_length;
+    if (cap < need) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_contigs_sequences: the buffer is shorter than the strings of the range");
+    if (!offsets || (need && !out)) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_contigs_sequences: null argument");
+    const uint64_t chunk0 = c->ctgChunk[first], nChunks = c->ctgChunk[first + count] - chunk0;
+    const char* img = nullptr;
+    if (count) {
+        { const int rc = dev_contigs_spell_begin(c->device(), 0, first, count, chunk0, nChunks, c->err); if (rc) return rc; }
+        { const int rc = dev_contigs_spell_wait(c->device(), 0, &img, &c->cstats.spell_ms, c->err); if (rc) return rc; }
+    }
+    uint64_t at = 0;
+    for (uint64_t i = first; i < first + count; i++) {                                 // compact on the way out: in the device buffer every row begins at a 16-byte chunk
+        offsets[i - first] = at; memcpy(out + at, img + 16 * (c->ctgChunk[i] - chunk0), rows[i].string_length); at += rows[i].string_length;
+    }
+    offsets[count] = at;
+    return SAGE2OV_OK;
+}
+int sage2ov_contigs_save(sage2ov_ctx* c, const char* path, int is_scaffold) {
+    if (!c || !path) return SAGE2OV_ERR_ARG;
+    { const int rc = contigs_ensure(c, "sage2ov_contigs_save"); if (rc) return rc; }
+    const std::vector<ContigRow>& rows = c->ctgRows; const std::vector<uint64_t>& ch = c->ctgChunk; const uint64_t R = rows.size(), bound = contig_range_chunks(c);
+    FILE* f = fopen(path, "w"); if (!f) return c->fail(SAGE2OV_ERR_IO, std::string("cannot open ") + path);
+    std::vector<char> io(1 << 22); setvbuf(f, io.data(), _IOFBF, io.size());
+    // a range: rows [a, b) with at most `bound` chunks, at least one row
+    auto range_end = [&](uint64_t a) { uint64_t b = a + 1; while (b < R && ch[b + 1] - ch[a] <= bound) b++; return std::min(b, R); };
+    auto begin = [&](int which, uint64_t a, uint64_t b) { return dev_contigs_spell_begin(c->device(), which, a, b - a, ch[a], ch[b] - ch[a], c->err); };
+    int rc = SAGE2OV_OK, which = 0; uint64_t a = 0, b = R ? range_end(0) : 0, gaps = 0, ns = 0; std::string text;
+    if (R) rc = begin(0, a, b);
+    while (!rc && a < R) {
+        const uint64_t a2 = b, b2 = a2 < R ? range_end(a2) : a2;
+        if (a2 < R) rc = begin(which ^ 1, a2, b2);                                      // the next range is spelled while this one is formatted
+        const char* img = nullptr;
+        if (!rc) rc = dev_contigs_spell_wait(c->device(), which, &img, &c->cstats.spell_ms, c->err);
+        if (rc) break;
+        text.clear();
+        for (uint64_t i = a; i < b; i++) {
+            gaps += rows[i].gap_count; ns += rows[i].n_count;                           // running totals over all rows, written or not (:668-669)
+            if (contig_written(c, rows[i])) contig_record(c, i + 1, rows[i], img + 16 * (ch[i] - ch[a]), is_scaffold != 0, gaps, ns, text);
+        }
+        if (fwrite(text.data(), 1, text.size(), f) != text.size()) { rc = c->fail(SAGE2OV_ERR_IO, std::string("cannot write ") + path); break; }
+        a = a2; b = b2; which ^= 1;
+    }
+    if (rc) { std::string e; dev_sync(c->device(), e); }                               // (a range may still be in flight)
+    if (fclose(f) != 0 && !rc) rc = c->fail(SAGE2OV_ERR_IO, std::string("cannot write ") + path);
+    return rc;
+}
+int sage2ov_contig_stats_get(const sage2ov_ctx* c, sage2ov_contig_stats* o) { if (!c || !o) return SAGE2OV_ERR_ARG; *o = c->cstats; return SAGE2OV_OK; }
 
 int sage2ov_run_steps23(sage2ov_ctx* c) {
     if (!c) return SAGE2OV_ERR_ARG;

@@ -187,6 +187,16 @@ int dev_support_build(Device* d, const SupportParams& P, SupportStats* st, std::
 uint64_t dev_support_count(Device* d);
 int dev_support_export(Device* d, uint64_t* key, uint32_t* support, std::string& err);
 void dev_support_release(Device* d);
+// OverlapGraph::printGraph / saveContigsToFile on the device (sage2ov_contigs_*).  dev_contigs_build selects, orders and lays out the rows: they stay
+// in HBM with the running distPrevious of the list pool and come back in table order.  dev_contigs_spell_begin spells the strings of a range of rows into one of two
+// buffers -- 16-byte chunks, every row from a chunk boundary -- and copies them to a pinned host image; dev_contigs_spell_wait hands that image out.  The table goes
+// with the graph (dev_simplify_release) and the read set.
+struct ContigRow { uint32_t h, string_length, contig_length, start, gap_count, n_count, flags, pad; };      // h: the half-edge; flags: 1 inconsistent, 2 wrapped, 4 beyond the limit
+struct ContigBuildStats { uint32_t passes = 0; double select_ms = 0, sort_ms = 0, layout_ms = 0; };
+int dev_contigs_build(Device* d, uint32_t threshold, std::vector<ContigRow>& rows, ContigBuildStats* st, std::string& err);
+int dev_contigs_spell_begin(Device* d, int which, uint64_t first, uint64_t count, uint64_t chunk0, uint64_t nChunks, std::string& err);
+int dev_contigs_spell_wait(Device* d, int which, const char** image, double* ms, std::string& err);
+void dev_contigs_release(Device* d);
 void dev_timings(Device* d, DevTimings* t);
 void dev_reset_timings(Device* d);
 int dev_sync(Device* d, std::string& err);
