@@ -370,6 +370,63 @@ int sage2ov_mates_supports_count(sage2ov_ctx* ctx, uint32_t min_support, uint64_
 int sage2ov_mates_supports_export(sage2ov_ctx* ctx, uint32_t min_support, sage2ov_support* out, uint64_t cap);
 int sage2ov_support_stats_get(const sage2ov_ctx* ctx, sage2ov_support_stats* out);
 
+/* ---- the sweep that opens every round of ScaffoldMaker::mergeFinal (matePair/scaffolding.cpp:786-935) and mergeFinalSmall (:981-1130): for every composite edge and every
+ * edge its mates reach, connected through a node or not, the number of mate pairs that link the two and the mean gap those pairs imply, on the device;
+ * all quantities are integers.  The merges that follow it in the reference (mergeAccordingToSupport / mergeAccordingToSupport2 / mergeDisconnectedEdges: serial, they change
+ * the graph) and its ordering of the rows (quicksortListOfLongEdges, :252-275: ties are open there) are NOT part of this library.
+ * The graph is the resident step-4 graph; mates, read-to-edge table, locations and insert estimates are those of the calls above; minOverlap is the context's k.
+ *   LINK(a, b) is defined for an ordered pair of alive half-edges with pair(a) != pair(b) and a non-empty list on a.  Loops take part like any other pair (unlike
+ *   sage2ov_mates_supports).  Walk a's list from its start with run = the running sum of distPrevious; stop at the first entry with run > maximumUpperBoundOfInsert
+ *   (:833-835).  For every entry walked (per list entry: a read that stands twice within the bound counts twice) whose read m1 is UNIQUE ON a (:837), and every mate
+ *   entry (m1 -> m2, type1, type2) of every valid library L, once per entry whatever its count or flag, with m2 UNIQUE ON b (:839-843): let d1 be the locations of m1 on
+ *   half a -- the `forward` ones of its read-to-edge entry if a is E of its pair, else the `reverse` ones (findDistanceOnEdge, matePair.cpp:575-609) -- and d2 those of
+ *   m2 on half b, both in list order.  Scan x over d1 outside and y over d2 inside: dist = |x| + |y| when s1 * x < 0 and s2 * y < 0 (s = +1 for type 1, -1 for type 0),
+ *   otherwise dist = 10 000 000 (:854-865).  The FIRST (x, y) with dist + 2 * averageReadLength < upper[L] + minOverlap (strict, :866) ends the scan: the entry counts 1
+ *   towards support and adds Mean[L] - (dist + 2 * averageReadLength) to gapSum, in 32-bit wrapping arithmetic (the reference's int32_t gapSum takes a uint64_t
+ *   expression, :878).  It is the first hit in list order that fixes the gap, not the nearest.  gap = gapSum / support as an int32_t division, truncating towards zero (:892).
+ *   UNIQUE ON h (:239-247): as for sage2ov_mates_supports.
+ * THE TABLE has one row per ordered (a, b) with support >= 1.  No feasibility filter is needed: support >= 1 implies that b's pair is in getListOfFeasibleEdges of a's
+ * pair (:148-234), and given that the reference evaluates each ordered pair at most once, from a's side.  Its row (edge_1, edge_2) = (twin of a, b) (:889-890).
+ * DELIBERATE DIFFERENCES: (1) the reference skips (a, b) when `edge1 > edge2` compares the ADDRESSES of the two Edge objects (:828), so of (a, b) and (b, a) it keeps
+ * whichever malloc placed lower; the table here holds both directions and leaves that choice to the caller.  (2) A library with valid = 0 never counts, as for
+ * sage2ov_mates_supports.  (3) A loop that a graph file holds twice is one pair here (sage2ov_graph_load_composite); the reference's loader makes two edges of it.
+ * Equal to the reference while list totals stay below 2^32 and |x| + |y| below 2^31 (its int32_t distance_all).
+ * FILTERS are applied at export, on the host.  They read lengthOfEdge and flow of E(pair(a)) and E(pair(b)): the halves getListOfCompositeEdges (:104-143) and
+ * readToEdgeList[..]->edge hand to the reference.  SAGE2OV_LINKS_ALL: none.  SAGE2OV_LINKS_FINAL (:801): len1 > 200 && len2 > 200, or both flows > 0 and both lengths >
+ * contigLengthThreshold = (int)ceilf(100 * (averageReadLength / 100.0)) (:20).  SAGE2OV_LINKS_SMALL (:996): len1 < 500 && len2 < 500.  The flows are those of the host
+ * copy at export (as sage2ov_contigs_* take them): sage2ov_graph_flow_import does not make the table stale. */
+#define SAGE2OV_LINKS_ALL 0
+#define SAGE2OV_LINKS_FINAL 1
+#define SAGE2OV_LINKS_SMALL 2
+typedef struct sage2ov_link {          /* 44 bytes */
+    uint32_t pair_a, pair_b;           /* ordinals of the record pairs in sage2ov_graph4_save's order, as in sage2ov_read_edge */
+    uint32_t from_a, to_a, from_b, to_b;   /* the end nodes of the halves a and b themselves */
+    uint32_t len_a, len_b;             /* lengthOfEdge of E(pair(a)) and E(pair(b)): the values the filters read */
+    uint32_t support;
+    int32_t  gap;
+    uint8_t  second_a, second_b;       /* 0: the half is the record sage2ov_graph4_save writes first of its pair (the first time, for a loop); 1: it is that record's twin */
+    uint8_t  type_a, type_b;           /* typeOfEdge of the halves a and b */
+} sage2ov_link;
+typedef struct sage2ov_link_stats {    /* of the last sage2ov_links */
+    uint64_t halves;                   /* alive half-edges with a list: the halves walked */
+    uint64_t entries_within;           /* their list entries whose running sum is within the bound */
+    uint64_t unique_entries;           /* of those, the entries whose read is unique on the half */
+    uint64_t mate_entries;             /* mate entries of valid libraries probed from them */
+    uint64_t records;                  /* (entry, mate entry, half of the mate's pair) that counted: the sum of all supports */
+    uint64_t keys;                     /* rows */
+    uint32_t sort_passes, reserved;    /* 8-bit radix passes run */
+    double halves_ms, scan_ms, records_ms, sort_ms, reduce_ms;   /* HIP events */
+} sage2ov_link_stats;
+/* builds the table.  Estimates (and maps) first when those are stale.  SAGE2OV_ERR_ARG without a step-4 graph, SAGE2OV_ERR_DEVICE on a device-less context,
+ * SAGE2OV_ERR_LIMIT from 2^32 - 2048 records on.  The table goes with the graph and the read set, and when the mate table or the estimate change;
+ * sage2ov_links_count / _export build it when it is stale.  Not sharded: a context with world > 1 behaves as a single one. */
+int sage2ov_links(sage2ov_ctx* ctx);
+/* mode: SAGE2OV_LINKS_*, anything else: SAGE2OV_ERR_ARG */
+int sage2ov_links_count(sage2ov_ctx* ctx, uint32_t mode, uint32_t min_support, uint64_t* n);
+/* the rows that pass the filter with support >= min_support in ascending (pair_a, second_a, pair_b, second_b); cap below their number: SAGE2OV_ERR_ARG, nothing written */
+int sage2ov_links_export(sage2ov_ctx* ctx, uint32_t mode, uint32_t min_support, sage2ov_link* out, uint64_t cap);
+int sage2ov_link_stats_get(const sage2ov_ctx* ctx, sage2ov_link_stats* out);
+
 /* ---- OverlapGraph::printGraph (overlapGraph.cpp:507-593) and saveContigsToFile (:607-784): the contigs of the resident step-4 graph, selected, ordered, laid out and
  * spelled on the device; all quantities are integers.  L(i) is the length of read i; a node's DEGREE is the number of alive half-edges leaving it
  * (getDegree, :595-602).

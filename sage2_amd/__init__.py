@@ -100,6 +100,19 @@ class ContigStats(C.Structure):
                 ("wrapped", C.c_uint64), ("select_ms", C.c_double), ("sort_ms", C.c_double), ("layout_ms", C.c_double), ("spell_ms", C.c_double)]
 
 
+# sage2ov_link (44 bytes): one ordered pair of half-edges that mate pairs link, with its support and mean gap
+LINK_DTYPE = np.dtype([("pair_a", np.uint32), ("pair_b", np.uint32), ("from_a", np.uint32), ("to_a", np.uint32), ("from_b", np.uint32), ("to_b", np.uint32),
+                       ("len_a", np.uint32), ("len_b", np.uint32), ("support", np.uint32), ("gap", np.int32),
+                       ("second_a", np.uint8), ("second_b", np.uint8), ("type_a", np.uint8), ("type_b", np.uint8)])
+LINKS_ALL, LINKS_FINAL, LINKS_SMALL = 0, 1, 2
+
+
+class LinkStats(C.Structure):
+    _fields_ = [("halves", C.c_uint64), ("entries_within", C.c_uint64), ("unique_entries", C.c_uint64), ("mate_entries", C.c_uint64), ("records", C.c_uint64),
+                ("keys", C.c_uint64), ("sort_passes", C.c_uint32), ("reserved", C.c_uint32),
+                ("halves_ms", C.c_double), ("scan_ms", C.c_double), ("records_ms", C.c_double), ("sort_ms", C.c_double), ("reduce_ms", C.c_double)]
+
+
 class OverlapStats(C.Structure):
     _fields_ = [("verified_overlaps", C.c_uint64), ("contained_extension", C.c_uint64), ("contained_size", C.c_uint64),
                 ("left_to_explore", C.c_uint64), ("edges_inserted", C.c_uint64), ("transitive_removed", C.c_uint64),
@@ -407,6 +420,25 @@ class Context:
     def support_stats(self) -> SupportStats:
         s = SupportStats()
         self._chk(lib().sage2ov_support_stats_get(self._h, C.byref(s)))
+        return s
+
+    # ---- the sweep that opens ScaffoldMaker::mergeFinal / mergeFinalSmall (scaffolding.cpp:786-935, :981-1130): support and gap of half-edge pairs linked by mates
+    def links(self, mode=0, min_support=1) -> np.ndarray:
+        """the rows (LINK_DTYPE) that pass the filter (LINKS_ALL / LINKS_FINAL / LINKS_SMALL) with support >= min_support, in ascending
+        (pair_a, second_a, pair_b, second_b)"""
+        n = C.c_uint64(0)
+        self._chk(lib().sage2ov_links_count(self._h, C.c_uint32(mode), C.c_uint32(min_support), C.byref(n)))
+        out = np.zeros(n.value, dtype=LINK_DTYPE)
+        self._chk(lib().sage2ov_links_export(self._h, C.c_uint32(mode), C.c_uint32(min_support), C.c_void_p(out.ctypes.data), C.c_uint64(n.value)))
+        return out
+
+    def links_build(self):
+        """builds the table now (links builds it when it is stale)"""
+        self._chk(lib().sage2ov_links(self._h))
+
+    def link_stats(self) -> LinkStats:
+        s = LinkStats()
+        self._chk(lib().sage2ov_link_stats_get(self._h, C.byref(s)))
         return s
 
     # ---- OverlapGraph::printGraph / saveContigsToFile (overlapGraph.cpp:507-784): the contigs of the resident step-4 graph

@@ -128,6 +128,13 @@ public:
         std::vector<sage2ov_support> out(n); ctx().check(sage2ov_mates_supports_export(ctx().get(), minSupport, out.data(), n));
         return out;
     }
+    // the sweep that opens ScaffoldMaker::mergeFinal (mode SAGE2OV_LINKS_FINAL) / mergeFinalSmall (SAGE2OV_LINKS_SMALL), scaffolding.cpp:786-935, :981-1130: support and
+    // gap of every ordered pair of half-edges linked by mates, both directions.  The merges stay with the caller
+    std::vector<sage2ov_link> scaffoldLinks(uint32_t mode = SAGE2OV_LINKS_ALL, uint32_t minSupport = 1) {
+        uint64_t n = 0; ctx().check(sage2ov_links_count(ctx().get(), mode, minSupport, &n));
+        std::vector<sage2ov_link> out(n); ctx().check(sage2ov_links_export(ctx().get(), mode, minSupport, out.data(), n));
+        return out;
+    }
     ReadLoader* loaderObj;
 private:
     Context& ctx() const { return loaderObj->context(); }

@@ -111,6 +111,7 @@ struct Device {
     struct PreHits { bool valid = false; Hit* hits = nullptr; u64 cap = 0, used = 0; u64* base = nullptr; } pre;
     void* support = nullptr;     // the mate-pair supports of edge pairs (dev_support_build; Support): allocations of its own, dropped with the read-to-edge table and the mate flags
     void* contigs = nullptr;     // the contig table and the spelling buffers (dev_contigs_build; Contigs): allocations of its own, dropped with the graph and the read set
+    void* links = nullptr;       // the scaffold links of half-edge pairs (dev_links_build; Links): allocations of its own, dropped with the read-to-edge table and the mate flags
     void* s4keep = nullptr;      // step 4: the simplified graph stays in HBM until the next call (S4Keep)
     // step 4: blocks a call released, kept for the next call (it asks for the same ~50 sizes; fresh HBM costs ~50 ms per GB to map, 0.7 s per call at BASELINE
     // configs[2]).  Emptied when the read set changes, when the workspace arena runs out of memory, and never filled in memory-diet mode.
@@ -230,6 +231,7 @@ static void mem_sample(Device* d) { size_t fr = 0, to = 0; if (hipMemGetInfo(&fr
 #include "kernels_mates.inc"
 #include "kernels_readmap.inc"
 #include "kernels_support.inc"
+#include "kernels_links.inc"
 #include "kernels_contig.inc"
 
 // =============================================================================================
@@ -2377,8 +2379,8 @@ struct ReadMap {
     u32 *eRead = nullptr, *ePair = nullptr, *eNf = nullptr, *eNr = nullptr, *eLoc = nullptr, *readOff = nullptr; int* locs = nullptr; u64 E = 0, R = 0; ReadMapLib lib[128];
     ~ReadMap() { for (auto& L : lib) readmap_drop_join(L); hipFree(eRead); hipFree(ePair); hipFree(eNf); hipFree(eNr); hipFree(eLoc); hipFree(readOff); hipFree(locs); }
 };
-void dev_readmap_drop_joins(Device* d) { dev_support_release(d); if (!d->readmap) return; hipSetDevice(d->ordinal); for (auto& L : ((ReadMap*)d->readmap)->lib) readmap_drop_join(L); }
-void dev_readmap_release(Device* d) { dev_support_release(d); if (d->readmap) { hipSetDevice(d->ordinal); delete (ReadMap*)d->readmap; d->readmap = nullptr; } }
+void dev_readmap_drop_joins(Device* d) { dev_support_release(d); dev_links_release(d); if (!d->readmap) return; hipSetDevice(d->ordinal); for (auto& L : ((ReadMap*)d->readmap)->lib) readmap_drop_join(L); }
+void dev_readmap_release(Device* d) { dev_support_release(d); dev_links_release(d); if (d->readmap) { hipSetDevice(d->ordinal); delete (ReadMap*)d->readmap; d->readmap = nullptr; } }
 static int readmap_nomem(std::string& err) { err = "read-to-edge table: out of device memory"; return SAGE2OV_ERR_NOMEM; }
 template <class T> static T* readmap_alloc(u64 n) { return (T*)DevTmp::alloc(std::max<u64>(n, 1) * sizeof(T)); }
 // the 8-bit digits of a record key (read:30 | pair:31 | side:1) that can be non-zero: side and pair end at bit 1 + bits(pairs), the read at 32 + bits(N)
@@ -2628,6 +2630,106 @@ int dev_support_export(Device* d, uint64_t* key, uint32_t* support, std::string&
     HIPCHK(hipSetDevice(d->ordinal));
     const Support* S = (const Support*)d->support; if (!S) { err = "mate-pair supports: not built"; return SAGE2OV_ERR_INTERNAL; }
     if (S->E) { HIPCHK(hipMemcpy(key, S->key, S->E * sizeof(u64), hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(support, S->sup, S->E * sizeof(u32), hipMemcpyDeviceToHost)); }
+    return 0;
+}
+
+// =============================================================================================
+// the scaffold links of ordered half-edge pairs (kernels_links.inc; the sweep that opens ScaffoldMaker::mergeFinal / mergeFinalSmall, scaffolding.cpp:786-935, :981-1130)
+// =============================================================================================
+struct Links { u64* key = nullptr; u32* sup = nullptr; int* gap = nullptr; u64 E = 0; ~Links() { hipFree(key); hipFree(sup); hipFree(gap); } };
+void dev_links_release(Device* d) { if (d->links) { hipSetDevice(d->ordinal); delete (Links*)d->links; d->links = nullptr; } }
+uint64_t dev_links_count(Device* d) { const Links* S = (const Links*)d->links; return S ? S->E : 0; }
+static int links_nomem(std::string& err) { err = "scaffold links: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+int dev_links_build(Device* d, const LinkParams& P, LinkStats* st, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    if (!d->s4keep) { err = "scaffold links: no step-4 graph on the device"; return SAGE2OV_ERR_ARG; }
+    if (!d->readmap) { err = "scaffold links: the read-to-edge table is not built"; return SAGE2OV_ERR_INTERNAL; }
+    dev_links_release(d);
+    const S4Keep& K = *(S4Keep*)d->s4keep; const S4Graph& g = K.g; const u32 nh = K.nh; const u64 nl = K.listUsed; const ReadMap* M = (const ReadMap*)d->readmap;
+    std::unique_ptr<Links> S(new Links());
+    *st = LinkStats();
+    if (!nh || !nl) { d->links = S.release(); return 0; }
+    const u32 N = (u32)d->N; hipStream_t sm = d->stream;
+    DevTmp B; StreamLap lap(sm); HIPCHK(lap.create());
+    // ---- unique reads, the list length of every alive half-edge
+    HIPCHK(lap.start());
+    uint8_t* nodeFlag = B.get<uint8_t>((u64)N + 2); u32* uniq = B.get<u32>((u64)N + 2); u32* hCnt = B.get<u32>(nh); u32* hOff = B.get<u32>(nh);
+    unsigned long long* ctr = B.get<unsigned long long>(4); u64* partial = B.get<u64>(scan_partial_words(std::max<u64>(nl, nh) + 1));
+    SlLib* libs = B.get<SlLib>(128);
+    if (!nodeFlag || !uniq || !hCnt || !hOff || !ctr || !partial || !libs) return links_nomem(err);
+    HIPCHK(hipMemsetAsync(nodeFlag, 0, (u64)N + 2, sm)); HIPCHK(hipMemsetAsync(ctr, 0, 4 * sizeof(unsigned long long), sm));
+    const MsTable T = {M->readOff, M->ePair, M->eNf, M->eNr, M->eLoc, M->locs, N};
+    const dim3 b256(256);
+    hipLaunchKernelGGL(k_ms_nodes, dim3(grid_for(nh, 256)), b256, 0, sm, g, nh, nodeFlag);
+    hipLaunchKernelGGL(k_ms_unique, dim3(grid_for((u64)N + 1, 256)), b256, 0, sm, T, nodeFlag, uniq);
+    hipLaunchKernelGGL(k_sl_halves, dim3(grid_for(nh, 256)), b256, 0, sm, g, nh, hCnt, ctr);
+    u64 W = 0; { const int rc = scan_u32(d, hCnt, nh, hOff, partial, &W, err); if (rc) return rc; }
+    HIPCHK(lap.stop(st->halves_ms));
+    B.release(nodeFlag); B.release(hCnt);
+    if (!W) { d->links = S.release(); return 0; }
+    if (W >= (1ull << 32) - RS_TILE) { err = "scaffold links: more than 2^32 list entries"; return SAGE2OV_ERR_LIMIT; }
+    // ---- the running sums of the whole pool (as dev_readmap_build makes them; not kept there)
+    HIPCHK(lap.start());
+    u32* dprev = B.get<u32>(nl); u32* scan = B.get<u32>(nl);
+    if (!dprev || !scan) return links_nomem(err);
+    hipLaunchKernelGGL(k_rm_dprev, dim3(grid_for_capped(nl, 256)), b256, 0, sm, g.lists, nl, dprev);
+    { const int rc = scan_u32(d, dprev, nl, scan, partial, nullptr, err); if (rc) return rc; }
+    HIPCHK(lap.stop(st->scan_ms));
+    B.release(dprev);
+    // ---- records: count, scan, write
+    HIPCHK(lap.start());
+    SlLib hl[128]; for (auto& x : hl) x = SlLib{nullptr, 0, 0, 0, 0};
+    const u32 nlib = std::min<u32>(P.libraries, 127);
+    for (u32 L = 1; L <= nlib; L++) if (d->mates && d->mates->lib[L].n && P.thr[L] > 0) hl[L] = SlLib{d->mates->lib[L].key, d->mates->lib[L].n, (long long)P.thr[L], P.gbase[L], 0};
+    HIPCHK(hipMemcpyAsync(libs, hl, sizeof hl, hipMemcpyHostToDevice, sm));
+    u32* cnt = B.get<u32>(W); u32* pos = B.get<u32>(W);
+    if (!cnt || !pos) return links_nomem(err);
+    const dim3 gW(grid_for(W, 256));
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sl_records<false>), gW, b256, 0, sm, g, nh, hOff, (u32)W, scan, nl, (u64)P.bound, uniq, T, libs, nlib, cnt, (const u32*)nullptr, (u64*)nullptr, (u32*)nullptr, ctr);
+    u64 R = 0; { const int rc = scan_u32(d, cnt, W, pos, partial, &R, err); if (rc) return rc; }      // (synchronises: hl may go out of scope after it)
+    unsigned long long hc[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpy(hc, ctr, sizeof hc, hipMemcpyDeviceToHost));
+    st->halves = hc[0]; st->entries_within = hc[1]; st->unique_entries = hc[2]; st->mate_entries = hc[3]; st->records = R;
+    if (R >= (1ull << 32) - RS_TILE) { err = "scaffold links: more than 2^32 records"; return SAGE2OV_ERR_LIMIT; }
+    if (!R) { HIPCHK(lap.stop(st->records_ms)); d->links = S.release(); return 0; }
+    u64* key = B.get<u64>(R); u32* val = B.get<u32>(R); if (!key || !val) return links_nomem(err);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_sl_records<true>), gW, b256, 0, sm, g, nh, hOff, (u32)W, scan, nl, (u64)P.bound, uniq, T, libs, nlib, (u32*)nullptr, (const u32*)pos, key, val, ctr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(lap.stop(st->records_ms));
+    B.release(cnt); B.release(pos); B.release(scan); B.release(uniq); B.release(hOff);
+    // ---- sort by (a, b): the digits below the number of half-edges, in both words; then the values in sorted order and their running sum
+    HIPCHK(lap.start());
+    int shifts[8], np = 0; { int b = 0; while (((u64)nh >> b) != 0) b++; for (int p = 0; p < 8; p++) { const int lo = 8 * p; if ((lo & 31) < b) shifts[np++] = lo; } }
+    u64* ks = nullptr; u32* vs = nullptr; MateStats ms;
+    { const int rc = mate_sort(d, B, key, (u32)R, shifts, np, &ks, &vs, &ms, err); if (rc) return rc; }
+    st->passes = ms.passes;
+    HIPCHK(lap.stop(st->sort_ms));
+    HIPCHK(lap.start());
+    B.release(partial);                                                            // (sized for the pool; the records may be more)
+    u32* sv = B.get<u32>(R + 1); u32* sc = B.get<u32>(R + 1); u64* partialR = B.get<u64>(scan_partial_words(R + 1)); if (!sv || !sc || !partialR) return links_nomem(err);
+    hipLaunchKernelGGL(k_sl_gather, dim3(grid_for(R + 1, 256)), b256, 0, sm, vs, val, (u32)R, sv);
+    { const int rc = scan_u32(d, sv, R + 1, sc, partialR, nullptr, err); if (rc) return rc; }
+    HIPCHK(hipStreamSynchronize(sm));
+    B.release(vs); B.release(val); B.release(sv); B.release(partialR);
+    // ---- reduce: one row per distinct key
+    u32* hp = nullptr; u32 E = 0;
+    { const int rc = mate_heads(d, B, ks, (u32)R, &hp, &E, err); if (rc) return rc; }
+    S->key = (u64*)DevTmp::alloc((u64)E * sizeof(u64)); S->sup = (u32*)DevTmp::alloc((u64)E * sizeof(u32)); S->gap = (int*)DevTmp::alloc((u64)E * sizeof(int));
+    if (!S->key || !S->sup || !S->gap) return links_nomem(err);
+    hipLaunchKernelGGL(k_sl_reduce, dim3(grid_for(E, 256)), b256, 0, sm, ks, hp, sc, E, S->key, S->sup, S->gap);
+    HIPCHK(hipGetLastError());
+    HIPCHK(lap.stop(st->reduce_ms));
+    S->E = E; st->keys = E;
+    d->links = S.release();
+    return 0;
+}
+int dev_links_export(Device* d, uint64_t* key, uint32_t* support, int32_t* gap, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    const Links* S = (const Links*)d->links; if (!S) { err = "scaffold links: not built"; return SAGE2OV_ERR_INTERNAL; }
+    if (S->E) {
+        HIPCHK(hipMemcpy(key, S->key, S->E * sizeof(u64), hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(support, S->sup, S->E * sizeof(u32), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(gap, S->gap, S->E * sizeof(int), hipMemcpyDeviceToHost));
+    }
     return 0;
 }
 

@@ -123,11 +123,15 @@ struct sage2ov_ctx {
     bool supValid = false;                             // the table is of the present graph, flows, mates and estimate (it also needs `estimated`)
     sage2ov_support_stats sstats{}; std::vector<sage2ov_support> supports; bool supOnHost = false;
     void supports_forget() { supValid = supOnHost = false; supports.clear(); sstats = sage2ov_support_stats{}; }
+    // ---- the scaffold links (sage2ov_links): built on the device, kept here in export order, unfiltered, once a call has asked for them; the flows are read at export
+    bool linkValid = false, linkOnHost = false;        // the table is of the present graph, mates and estimate (it also needs `estimated`)
+    sage2ov_link_stats lstats{}; std::vector<sage2ov_link> links; std::vector<uint32_t> linkHalves;      // linkHalves: E(pair(a)), E(pair(b)) of every row, internal half-edges
+    void links_forget() { linkValid = linkOnHost = false; links.clear(); linkHalves.clear(); lstats = sage2ov_link_stats{}; }
     // ---- the contigs (sage2ov_contigs_*): rows and layout are built on the device and kept here in table order; threshold and genome size as the last build was asked
     bool ctgValid = false; uint32_t ctgThreshold = 0, ctgThresholdUsed = 0; uint64_t ctgGenome = 0; sage2ov_contig_stats cstats{};
     std::vector<ContigRow> ctgRows; std::vector<uint64_t> ctgChunk;      // ctgChunk[r]: 16-byte chunks of the device buffer in front of row r (every row begins at a chunk); R + 1 values
     void contigs_forget() { ctgValid = false; ctgRows.clear(); ctgChunk.clear(); cstats = sage2ov_contig_stats{}; }
-    void readmap_forget() { rmValid = estimated = false; pairOrdinal.clear(); rmstats = sage2ov_readmap_stats{}; supports_forget(); contigs_forget(); }      // the graph or the read set goes
+    void readmap_forget() { rmValid = estimated = false; pairOrdinal.clear(); rmstats = sage2ov_readmap_stats{}; supports_forget(); links_forget(); contigs_forget(); }      // the graph or the read set goes
     void mates_forget(bool readSetGoes = true) {       // the read set goes: its ids mean nothing any more (the device drops its part in free_reads) -- or sage2ov_mates_clear
         if (readSetGoes) { readmap_forget(); readsGen++; } else estimated = false;
         for (auto& L : mates) L = MateLib();
@@ -1795,7 +1799,7 @@ void readmap_stats_take(sage2ov_ctx* c, const ReadMapStats& s) {
     o.scan_ms = s.scan_ms; o.records_ms = s.records_ms; o.sort_ms = s.sort_ms; o.reduce_ms = s.reduce_ms;
 }
 int readmap_build(sage2ov_ctx* c) {
-    c->rmValid = c->estimated = false; c->rmstats = sage2ov_readmap_stats{}; c->supports_forget();
+    c->rmValid = c->estimated = false; c->rmstats = sage2ov_readmap_stats{}; c->supports_forget(); c->links_forget();
     ReadMapStats s; const int rc = dev_readmap_build(c->device(), &s, c->err); if (rc) return rc;
     readmap_stats_take(c, s); c->rmValid = true; return SAGE2OV_OK;
 }
@@ -1909,7 +1913,7 @@ int sage2ov_mates_distances_export(sage2ov_ctx* c, int library, uint32_t* d, uin
 int sage2ov_mates_estimate(sage2ov_ctx* c) {
     if (!c) return SAGE2OV_ERR_ARG;
     { const int rc = readmap_ensure(c, "sage2ov_mates_estimate"); if (rc) return rc; }
-    c->estimated = false; c->rmstats.rounds = 0; c->rmstats.round_ms = 0; c->supports_forget();
+    c->estimated = false; c->rmstats.rounds = 0; c->rmstats.round_ms = 0; c->supports_forget(); c->links_forget();
     const uint64_t arl = average_read_length(c); Device* d = c->device();
     c->minUpper = 1000000; c->maxUpper = 0;                                            // matePair.cpp:292-293
     for (auto& I : c->inserts) I = sage2ov_insert{};
@@ -2030,6 +2034,93 @@ int sage2ov_mates_supports_export(sage2ov_ctx* c, uint32_t min_support, sage2ov_
     return SAGE2OV_OK;
 }
 int sage2ov_support_stats_get(const sage2ov_ctx* c, sage2ov_support_stats* o) { if (!c || !o) return SAGE2OV_ERR_ARG; *o = c->sstats; return SAGE2OV_OK; }
+
+// ---- the sweep that opens ScaffoldMaker::mergeFinal / mergeFinalSmall (scaffolding.cpp:786-935, :981-1130); the semantics are stated in sage2ov.h
+namespace {
+static_assert(sizeof(sage2ov_link) == 44, "sage2ov_link is ten 32-bit words and four bytes");
+int links_ensure(sage2ov_ctx* c, const char* who) {
+    { const int rc = readmap_check(c, who); if (rc) return rc; }
+    if (c->linkValid && c->estimated && c->rmValid) return SAGE2OV_OK;
+    return sage2ov_links(c);
+}
+// the table in export order, on the host (once per table)
+int links_fetch(sage2ov_ctx* c) {
+    if (c->linkOnHost) return SAGE2OV_OK;
+    Device* d = c->device(); const uint64_t E = dev_links_count(d);
+    std::vector<uint64_t> key(E); std::vector<uint32_t> sup(E); std::vector<int32_t> gap(E);
+    { const int rc = dev_links_export(d, key.data(), sup.data(), gap.data(), c->err); if (rc) return rc; }
+    { const int rc = pair_ordinals(c); if (rc) return rc; }
+    const SimplifiedGraph& g = c->g4; const std::vector<uint32_t>& ord = c->pairOrdinal;
+    std::vector<uint32_t> order, first(g.n_half_edges / 2 + 1, ~0u); g4_save_order(g, order);      // first[pair]: the half that opens the pair's record in the save (a loop: the first time)
+    for (uint32_t h : order) if (first[h >> 1] == ~0u) first[h >> 1] = h;
+    auto E_of = [&](uint32_t h) -> uint32_t { const uint32_t t = h ^ 1u; return g.from[h] < g.to[h] ? h : (g.from[h] > g.to[h] ? t : (h | 1u)); };      // a loop: the half with the higher index
+    std::vector<uint64_t> at(E); for (uint64_t e = 0; e < E; e++) at[e] = e;
+    std::vector<sage2ov_link> rows(E); std::vector<uint32_t> halves(2 * E);
+    for (uint64_t e = 0; e < E; e++) {
+        const uint32_t a = (uint32_t)(key[e] >> 32), b = (uint32_t)key[e], ea = E_of(a), eb = E_of(b);
+        sage2ov_link o{}; o.pair_a = ord[a >> 1]; o.pair_b = ord[b >> 1]; o.from_a = g.from[a]; o.to_a = g.to[a]; o.from_b = g.from[b]; o.to_b = g.to[b];
+        o.len_a = g.len[ea]; o.len_b = g.len[eb]; o.support = sup[e]; o.gap = gap[e];
+        o.second_a = first[a >> 1] == a ? 0 : 1; o.second_b = first[b >> 1] == b ? 0 : 1; o.type_a = g.type[a]; o.type_b = g.type[b];
+        rows[e] = o; halves[2 * e] = ea; halves[2 * e + 1] = eb;
+    }
+    std::sort(at.begin(), at.end(), [&](uint64_t x, uint64_t y) {
+        const sage2ov_link &p = rows[x], &q = rows[y];
+        if (p.pair_a != q.pair_a) return p.pair_a < q.pair_a;
+        if (p.second_a != q.second_a) return p.second_a < q.second_a;
+        if (p.pair_b != q.pair_b) return p.pair_b < q.pair_b;
+        return p.second_b < q.second_b; });
+    c->links.resize(E); c->linkHalves.resize(2 * E);
+    for (uint64_t e = 0; e < E; e++) { c->links[e] = rows[at[e]]; c->linkHalves[2 * e] = halves[2 * at[e]]; c->linkHalves[2 * e + 1] = halves[2 * at[e] + 1]; }
+    c->linkOnHost = true;
+    return SAGE2OV_OK;
+}
+// scaffolding.cpp:801 and :996 on row e, with the flows of the host copy as they are now
+bool link_passes(const sage2ov_ctx* c, uint64_t e, uint32_t mode, int threshold) {
+    if (mode == SAGE2OV_LINKS_ALL) return true;
+    const sage2ov_link& r = c->links[e]; const int64_t len1 = r.len_a, len2 = r.len_b;
+    if (mode == SAGE2OV_LINKS_SMALL) return len1 < 500 && len2 < 500;
+    const std::vector<float>& f = c->g4.flow;
+    const float f1 = f.empty() ? 0.f : f[c->linkHalves[2 * e]], f2 = f.empty() ? 0.f : f[c->linkHalves[2 * e + 1]];
+    return (len1 > 200 && len2 > 200) || ((f1 > 0 && len1 > threshold) && (f2 > 0 && len2 > threshold));
+}
+}  // namespace
+int sage2ov_links(sage2ov_ctx* c) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    { const int rc = readmap_check(c, "sage2ov_links"); if (rc) return rc; }
+    if (!c->estimated || !c->rmValid) { const int rc = sage2ov_mates_estimate(c); if (rc) return rc; }
+    c->links_forget();
+    const int64_t arl = (int64_t)average_read_length(c), k = (int64_t)c->cfg.min_overlap;
+    LinkParams P; P.bound = c->maxUpper; P.libraries = c->mateLibraries;
+    for (int lib = 1; lib <= (int)c->mateLibraries && lib < 128; lib++) {
+        P.thr[lib] = c->inserts[lib].valid ? c->inserts[lib].upper + k - 2 * arl : 0;
+        P.gbase[lib] = (uint32_t)(uint64_t)(c->inserts[lib].mean - 2 * arl);
+    }
+    LinkStats s; const int rc = dev_links_build(c->device(), P, &s, c->err); if (rc) return rc;
+    sage2ov_link_stats& o = c->lstats;
+    o.halves = s.halves; o.entries_within = s.entries_within; o.unique_entries = s.unique_entries; o.mate_entries = s.mate_entries; o.records = s.records; o.keys = s.keys;
+    o.sort_passes = s.passes; o.halves_ms = s.halves_ms; o.scan_ms = s.scan_ms; o.records_ms = s.records_ms; o.sort_ms = s.sort_ms; o.reduce_ms = s.reduce_ms;
+    c->linkValid = true;
+    return SAGE2OV_OK;
+}
+int sage2ov_links_count(sage2ov_ctx* c, uint32_t mode, uint32_t min_support, uint64_t* n) {
+    if (!c || !n) return SAGE2OV_ERR_ARG;
+    if (mode > SAGE2OV_LINKS_SMALL) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_links_count: mode is one of SAGE2OV_LINKS_ALL, _FINAL, _SMALL");
+    { const int rc = links_ensure(c, "sage2ov_links_count"); if (rc) return rc; }
+    { const int rc = links_fetch(c); if (rc) return rc; }
+    const int thr = (int)ceilf((float)(100 * ((double)average_read_length(c) / 100.0)));      // scaffolding.cpp:20
+    uint64_t m = 0; for (uint64_t e = 0; e < c->links.size(); e++) m += c->links[e].support >= min_support && link_passes(c, e, mode, thr);
+    *n = m; return SAGE2OV_OK;
+}
+int sage2ov_links_export(sage2ov_ctx* c, uint32_t mode, uint32_t min_support, sage2ov_link* out, uint64_t cap) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    uint64_t m = 0; { const int rc = sage2ov_links_count(c, mode, min_support, &m); if (rc) return rc; }
+    if (cap < m) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_links_export: the buffer holds fewer rows than the table (sage2ov_links_count)");
+    if (m && !out) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_links_export: null argument");
+    const int thr = (int)ceilf((float)(100 * ((double)average_read_length(c) / 100.0)));
+    uint64_t at = 0; for (uint64_t e = 0; e < c->links.size(); e++) if (c->links[e].support >= min_support && link_passes(c, e, mode, thr)) out[at++] = c->links[e];
+    return SAGE2OV_OK;
+}
+int sage2ov_link_stats_get(const sage2ov_ctx* c, sage2ov_link_stats* o) { if (!c || !o) return SAGE2OV_ERR_ARG; *o = c->lstats; return SAGE2OV_OK; }
 
 // ---- OverlapGraph::printGraph / saveContigsToFile (overlapGraph.cpp:507-784); the semantics are stated in sage2ov.h
 namespace {

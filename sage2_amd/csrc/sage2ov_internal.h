@@ -187,6 +187,16 @@ int dev_support_build(Device* d, const SupportParams& P, SupportStats* st, std::
 uint64_t dev_support_count(Device* d);
 int dev_support_export(Device* d, uint64_t* key, uint32_t* support, std::string& err);
 void dev_support_release(Device* d);
+// the sweep that opens ScaffoldMaker::mergeFinal / mergeFinalSmall on the device (sage2ov_links): needs the read-to-edge table, the mate tables and
+// the insert estimates.  The table (key = half a:32 | half b:32, support, gap) stays in HBM until the read-to-edge table or the mate flags go; flows are not read.
+struct LinkParams { uint64_t bound = 0; int64_t thr[128] = {}; uint32_t gbase[128] = {}; uint32_t libraries = 0; };      // bound: maximumUpperBoundOfInsert; thr[L]: upper[L] + minOverlap -
+                                                                                                                         // 2 * averageReadLength, 0 when L is not valid; gbase[L]: Mean[L] - 2 * averageReadLength mod 2^32
+struct LinkStats { uint64_t halves = 0, entries_within = 0, unique_entries = 0, mate_entries = 0, records = 0, keys = 0; uint32_t passes = 0;
+                   double halves_ms = 0, scan_ms = 0, records_ms = 0, sort_ms = 0, reduce_ms = 0; };
+int dev_links_build(Device* d, const LinkParams& P, LinkStats* st, std::string& err);
+uint64_t dev_links_count(Device* d);
+int dev_links_export(Device* d, uint64_t* key, uint32_t* support, int32_t* gap, std::string& err);
+void dev_links_release(Device* d);
 // OverlapGraph::printGraph / saveContigsToFile on the device (sage2ov_contigs_*).  dev_contigs_build selects, orders and lays out the rows: they stay
 // in HBM with the running distPrevious of the list pool and come back in table order.  dev_contigs_spell_begin spells the strings of a range of rows into one of two
 // buffers -- 16-byte chunks, every row from a chunk boundary -- and copies them to a pinned host image; dev_contigs_spell_wait hands that image out.  The table goes
