@@ -544,6 +544,10 @@ typedef struct sage2ov_timings {
 } sage2ov_timings;
 int sage2ov_timings_get(const sage2ov_ctx* ctx, sage2ov_timings* out);
 int sage2ov_timings_reset(sage2ov_ctx* ctx);
+/* Run mode of the last probe pass (the launches of one sage2ov_overlap_probe_shard / sage2ov_overlap_initial), counted on the device and copied on this call only:
+ * out[0] reads answered off the slot ring, out[1] steps that answered them (a step answers up to 16 consecutive reads), out[2] of those reads: records computed
+ * with a lane per read, out[3] such steps.  Zero where the resident reads have no run mode (several lengths, k > 64, noisy data's forms). */
+int sage2ov_probe_run_stats_get(sage2ov_ctx* ctx, uint64_t out[4]);
 void* sage2ov_stream(sage2ov_ctx* ctx);   /* hipStream_t the context launches on */
 
 /* ---- deterministic synthetic reads (repo-owned, not part of the reference) ---- */

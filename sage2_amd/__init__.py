@@ -569,6 +569,12 @@ class Context:
         self._chk(lib().sage2ov_timings_get(self._h, C.byref(t)))
         return t
 
+    def probe_run_stats(self):
+        """run mode of the last probe pass: (reads answered off the ring, steps, of those reads: records with a lane per read, such steps)"""
+        out = (C.c_uint64 * 4)()
+        self._chk(lib().sage2ov_probe_run_stats_get(self._h, out))
+        return tuple(int(v) for v in out)
+
     def debug_all_hits(self):
         n = C.c_uint64()
         self._chk(lib().sage2ov_debug_all_hits(self._h, None, C.c_uint64(0), C.byref(n)))

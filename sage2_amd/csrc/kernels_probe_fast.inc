@@ -71,6 +71,8 @@ constexpr int RUN_NPRE = 3;                        // passes of a step's new-slo
 constexpr u32 RUN_MMAX = 16;                       // most reads per step (the plan: 2 words each in LDS)
 constexpr int RUN_PF = 16;                         // windows behind a step's whose table pairs are fetched ahead
 constexpr int RUN_PW = 256;                        // window numbers are told apart mod this: the <= 128 windows of a read + the RUN_DMAX of a step fit
+constexpr u32 RUN_LANES_MIN = 3;                   // reads of a planned step from which its records are computed with a lane per read (fewer: a loop over the reads; DESIGN.md 5.2)
+constexpr int RSX_CNT = 2 * RUN_MMAX, RSX_LMIN = RSX_CNT + 4, RSX_WORDS = RSX_LMIN + 2;      // rsx[] behind the plan: the wave's four run counters (CTR_RUNSTATS), the threshold above as the launch set it
 static_assert(RUN_DMAX <= 64 && RUN_NMAX <= 64 && RUN_MMAX >= 1 && RUN_MMAX <= 64 && 128 + RUN_DMAX <= RUN_PW, "run mode limits");
 // SPEC: the form speculates (extended strings e[], the two furthest-reaching reads m[]); the form that sends every read through the state machine (TAIL = 2) does not,
 // and its LDS decides its occupancy: without them and with candidate rows of NW + 1 dwords it keeps 8.0 KB per wave at NW = 10 -- five waves per SIMD instead of four.
@@ -86,7 +88,7 @@ struct FastLds {                   // every string has one zero dword in front (
     // overhang of every verified hit (<= 128 bases) in this read's orientation
     // run mode: the slot ring (entry, absolute window of every slot), per absolute window (mod RUN_PW) {first slot of the ring | count << 8}, the frame, a row for the read that
     // extends it, and the state {on, minimiser offset and strand of the current read, its frame position, frame end, ring start, slots, frame start}
-    u32 pent[RUN ? CAPS : 1]; unsigned short sJ[RUN ? CAPS : 1]; unsigned short pcw[RUN ? RUN_PW : 1]; u32 rst[8]; int rsx[RUN ? 2 * RUN_MMAX : 1];      // (rsx: the plan of a step for several reads: cumulative shifts, offset words)
+    u32 pent[RUN ? CAPS : 1]; unsigned short sJ[RUN ? CAPS : 1]; unsigned short pcw[RUN ? RUN_PW : 1]; u32 rst[8]; int rsx[RUN ? RSX_WORDS : 1];      // (rsx: the plan of a step for several reads: cumulative shifts, offset words; behind it the wave's run counters and the lane-form threshold)
     u32 G[RUN ? 1 + RUN_FD + 2 : 1], RCG[RUN ? 1 + RUN_FD + 2 : 1], mrow[RUN ? 1 + NW + 3 : 1];
     uint8_t tslotIdx[TAILED ? FAST_CAP : 4];          // slot number of the x-th verified hit (visiting order)
     // per candidate slot: one dword in front, the candidate's NW dwords, then its overhang in place.  Rows of NW + 1 dwords (odd: a lane per row is conflict-free; NW + 3
@@ -241,7 +243,7 @@ __global__ __launch_bounds__(64 * WPB, (NW > 20 ? 1 : (NW > 10 ? 2 : (WPL >= 3 ?
     u64 st_prev = __builtin_amdgcn_s_memtime();
 #endif
     if (lane == 0) { L.xf[0][0] = 0; L.xf[1][0] = 0; L.m[0][0] = 0; L.m[1][0] = 0; L.e[0][0] = 0; L.e[1][0] = 0; L.e[2][0] = 0; L.e[3][0] = 0; L.xp[0] = 0; L.rst[0] = 0;
-                     if constexpr (RUN) { L.G[0] = 0; L.RCG[0] = 0; L.mrow[0] = 0; L.G[RUN_FD + 1] = 0; L.G[RUN_FD + 2] = 0; L.RCG[RUN_FD + 1] = 0; L.RCG[RUN_FD + 2] = 0; } }
+                     if constexpr (RUN) { for (int x_ = 0; x_ < 4; x_++) L.rsx[RSX_CNT + x_] = 0; L.rsx[RSX_LMIN] = (int)A.runLanesMin; L.G[0] = 0; L.RCG[0] = 0; L.mrow[0] = 0; L.G[RUN_FD + 1] = 0; L.G[RUN_FD + 2] = 0; L.RCG[RUN_FD + 1] = 0; L.RCG[RUN_FD + 2] = 0; } }
     // (run mode needs gates that do not depend on the window -- k <= 64, so that every window of a read is a key of k bases --, one read length, and a frame that holds a run)
     // (evaluated where it is needed, out of the kernel-argument segment: as a value computed in front of the loop it is one more scalar register pair that lives across the
     //  whole loop -- the form spills ~65 scalars into the lanes of ONE spare vector register, and a 65th lane is a second register)
@@ -532,9 +534,55 @@ __global__ __launch_bounds__(64 * WPB, (NW > 20 ? 1 : (NW > 10 ? 2 : (WPL >= 3 ?
                 //      (the tie rules of the general path: first / last window, then bucket order), connections = the others' count
                 // (the slots are read out of LDS once for all the reads of a step; both sides' selection keys go through ONE wave reduction: right key = slot number in ring order,
                 //  left key = (last window first) << 8 | slot number, 16 bits each)
-                auto records = [&](u32 pos0, u32 mReads, bool planned) {      // (planned: the reads start at the cumulative shifts of the step's plan; else: one read at the current position)
+                // A LANE PER READ (the 128-slot form, planned steps of lanesMin reads and more): the ring is in window order and a window's slots are contiguous, so the slots of
+                // read r are ONE range [sa, sb) of ring-relative slot numbers -- from the first slot of its first window to the end of its last, both out of pcw[], which has a word
+                // for every window of the ring, empty ones included.  Once per step the wave reads the ring in that order and ballots which slots are right-type (128 wave-uniform
+                // bits; the others are left-type), and every slot that is an entry of one of the step's reads ORs its bit into that read's 128-bit word in candJ[] (free here: 16
+                // reads x 4 dwords; own entries may sit in any window -- a look-up by tag --, not only the first and the last).  Lane r then has valid = range & ~own and reads its
+                // records off it: connections = its population, right = its lowest right-type bit, left = the lowest left-type bit inside the window of the highest one ("last
+                // window with a left-type slot, then bucket order").  Three coalesced stores per step.  Returns whether this form answered.
+                auto records = [&](u32 pos0, u32 mReads, bool planned) -> bool {      // (planned: the reads start at the cumulative shifts of the step's plan; else: one read at the current position)
                     u32 lane = lane0r_; asm volatile("" : "+v"(lane));      // (opaque per call: what is derived from the lane number is computed here, not in front of the loop the call sits in)
                     const int J0r = (int)L.rst[3]; const u32 base = L.rst[5], tot = L.rst[6];
+                    if constexpr (QN == 2) {
+                        const u32 lm_ = (u32)L.rsx[RSX_LMIN];
+                        if (planned && lm_ != 0u && mReads >= lm_) {
+                            u32 e3[2]; u64 rt[2];
+                            L.candJ[lane] = 0;
+#pragma unroll
+                            for (int q = 0; q < 2; q++) { const u32 sx = lane + 64u * q; e3[q] = L.pent[(base + sx) & RM]; rt[q] = __ballot(sx < tot && (e3[q] & 1u) == 0u); }
+                            wave_sync();
+#pragma unroll
+                            for (int q = 0; q < 2; q++) { const u32 r_ = (e3[q] >> 2) - pos0; if (lane + 64u * q < tot && r_ < mReads) atomicOr(&L.candJ[4u * r_ + 2u * q + (lane >> 5)], 1u << (lane & 31u)); }
+                            wave_sync();
+                            const bool act = lane < mReads; const u32 r = act ? lane : 0u;
+                            const int Jk = J0r + L.rsx[r], Jl = Jk + nwinR - 1;
+                            const u32 pcA = L.pcw[Jk & (RUN_PW - 1)], pcB = L.pcw[Jl & (RUN_PW - 1)];
+                            u32 sa = ((pcA & 255u) - base) & RM, sb = ((pcB & 255u) - base) & RM;
+                            // (a full ring: the first slot of an empty window behind all CAP slots reads as 0.  Told apart by the window of the ring's first slot.)
+                            const bool ambA = tot == (u32)CAP && sa == 0u && (pcA >> 8) == 0u, ambB = tot == (u32)CAP && sb == 0u && (pcB >> 8) == 0u;
+                            if (__any(ambA || ambB)) { const int Jf = (int)L.sJ[base & RM]; if (ambA && Jf < Jk) sa = (u32)CAP; if (ambB && Jf < Jl) sb = (u32)CAP; }
+                            sb += pcB >> 8;
+                            auto below = [](u32 x) -> u64 { return x >= 64u ? ~0ull : ((1ull << x) - 1ull); };      // the bits under x
+                            const u64 o0 = (u64)L.candJ[4u * r] | ((u64)L.candJ[4u * r + 1u] << 32), o1 = (u64)L.candJ[4u * r + 2u] | ((u64)L.candJ[4u * r + 3u] << 32);
+                            const u64 v0 = act ? (below(sb) & ~below(sa) & ~o0) : 0ull, v1 = act ? (below(sb > 64u ? sb - 64u : 0u) & ~below(sa > 64u ? sa - 64u : 0u) & ~o1) : 0ull;
+                            const u32 nconn = (u32)__popcll(v0) + (u32)__popcll(v1);
+                            const u64 r0 = v0 & rt[0], r1 = v1 & rt[1], l0 = v0 & ~rt[0], l1 = v1 & ~rt[1];
+                            const bool hasR = (r0 | r1) != 0ull, hasL = (l0 | l1) != 0ull;
+                            const u32 keyR = r0 ? (u32)__builtin_ctzll(r0) : (r1 ? 64u + (u32)__builtin_ctzll(r1) : 0u);
+                            const u32 hiL = l1 ? 127u - (u32)__builtin_clzll(l1) : (l0 ? 63u - (u32)__builtin_clzll(l0) : 0u);
+                            const u32 pcH = L.pcw[(u32)L.sJ[(base + hiL) & RM] & (u32)(RUN_PW - 1)]; const u32 ha = ((pcH & 255u) - base) & RM;      // (that window holds a slot: no full-ring case)
+                            const u64 m0 = l0 & ~below(ha), m1 = l1 & ~below(ha > 64u ? ha - 64u : 0u);
+                            const u32 keyL = m0 ? (u32)__builtin_ctzll(m0) : (m1 ? 64u + (u32)__builtin_ctzll(m1) : 0u);
+                            u64 rv = 0, lv = 0;
+                            { const u32 ph = (base + keyR) & RM, e = L.pent[ph]; const int j3 = (int)L.sJ[ph] - Jk;
+                              if (hasR) rv = (u64)(e >> 2) | ((u64)((e & 3u) == 2u ? 1 : 0) << 40) | ((u64)((u32)j3 & 0x3FFFFFu) << 42); }
+                            { const u32 ph = (base + keyL) & RM, e = L.pent[ph]; const int j3 = (int)L.sJ[ph] - Jk;
+                              if (hasL) lv = (u64)(e >> 2) | ((u64)((e & 3u) == 3u ? 1 : 0) << 40) | ((u64)((u32)(Lr - j3 - h) & 0x3FFFFFu) << 42); }
+                            if (act) { A.right[pos0 + lane] = rv; A.left[pos0 + lane] = lv; A.conn[pos0 + lane] = nconn; }
+                            return true;
+                        }
+                    }
                     u32 e3[QN], sx[QN]; int sj[QN];
 #pragma unroll
                     for (int q = 0; q < QN; q++) {
@@ -564,6 +612,7 @@ __global__ __launch_bounds__(64 * WPB, (NW > 20 ? 1 : (NW > 10 ? 2 : (WPL >= 3 ?
                             A.right[pos] = rv; A.left[pos] = lv; A.conn[pos] = nconn;
                         }
                     }
+                    return false;
                 };
                 // ---- the ring of the current stretch, mirrored: windows in reverse order (window J -> RUN_F - (J + h)), slots of a window in their order, types 0 <-> 3 and
                 //      1 <-> 2; the two arrays of the frame change roles.  Not if a window holds one read twice (the mirrored bucket orders its two types the other way round).
@@ -603,12 +652,25 @@ __global__ __launch_bounds__(64 * WPB, (NW > 20 ? 1 : (NW > 10 ? 2 : (WPL >= 3 ?
                 // extension, the compare passes shared), then each reads its own records off the ring.  Up to RUN_MMAX reads, RUN_DMAX windows.  The plan -- cumulative shifts
                 // rsx[0..RUN_MMAX), offset words behind them -- lives in LDS too.
                 u32 m = 1;
+                // (0: the plan, the own-entry checks and the records loop over the reads of a step, SAGE2OV_RUN_LANES=0; else they take a lane per read: see RUN_LANES_MIN)
+                static_assert(RUN_MMAX <= 16, "a lane per read of a step: one DPP row in the plan, 16 x 4 dwords of own-slot masks in candJ[]");
+                // (the wide form, QN = 4, keeps the loops: it sits at its register budget and sees the few reads the 128-slot form lists)
+                const u32 lanesMin = QN == 2 ? (u32)__builtin_amdgcn_readfirstlane(L.rsx[RSX_LMIN]) : 0u;
                 if (lane == 0) { L.rsx[0] = d1; L.rsx[RUN_MMAX] = offR; }
                 if (ok && !flipReq && A.ids == nullptr) {
                     const bool a1 = idCur == (u32)i + 1u, a2 = a1 && idNext == (u32)i + 2u, a3 = a2 && vIt < vEnd && (u32)(A.lo + vIt) == (u32)i + 3u;
                     const u32 avail = min(RUN_MMAX - 1u, a3 ? 2u + (vEnd - vIt) : (a2 ? 2u : (a1 ? 1u : 0u)));      // (the reads behind this one that are consecutive items of the visit)
                     const u32 mk_ = avail ? (u32)A.meta[(u64)i + 1u + (lane < avail ? lane : 0u)] : 0xFFFFu;
                     const int rStrand = (int)(L.rst[2] & 1u);
+                    if (lanesMin != 0u) {
+                        // (a lane per candidate read: the running sum of the shifts telescopes to d1 + (its offset - this read's), the predecessor's offset comes from the
+                        //  lane below -- avail < 16: one DPP row -- and the plan ends in front of the first lane that fails a test; offsets ascend strictly up to there,
+                        //  so the sum is monotone and "first lane beyond RUN_DMAX" is where the loop below stops)
+                        const int o_ = (int)(mk_ & 255u), oPrev = (int)dpp_mov<0x111, 0xF>((u32)offR, (u32)o_), DPk = d1 + (o_ - offR);
+                        const bool bad = lane >= avail || mk_ == 0xFFFFu || (mk_ & 0x200u) != 0u || (int)((mk_ >> 8) & 1u) != rStrand || o_ - oPrev < 1 || DPk > RUN_DMAX;
+                        m = 1u + (u32)__builtin_ctzll(__ballot(bad));          // (avail < RUN_MMAX <= 64: some lane is bad)
+                        if (lane + 1u < m) { L.rsx[lane + 1u] = DPk; L.rsx[RUN_MMAX + 1u + lane] = o_; }
+                    } else {
                     int oP = offR, DP = d1;
                     for (u32 k2 = 0; k2 < avail; k2++) {
                         const u32 mw = (u32)__builtin_amdgcn_readlane((int)mk_, (int)k2);      // (k2 is wave-uniform: a scalar-indexed readlane)
@@ -617,11 +679,21 @@ __global__ __launch_bounds__(64 * WPB, (NW > 20 ? 1 : (NW > 10 ? 2 : (WPL >= 3 ?
                         oP = o_; DP += dk; m = k2 + 2u;
                         if (lane == 0) { L.rsx[k2 + 1] = DP; L.rsx[RUN_MMAX + 1u + k2] = oP; }
                     }
+                    }
                 }
                 wave_sync();
                 // every read of the step must be in the list where it should start: (position * 4 + type 0) among the slots of its window; the read of the other strand: its
                 // reverse-complement prefix entry (type 2) at the start of the stretch it covers (when that lies in front of the ring, d2 > 0, its entry is looked for after the mirror)
-                if (ok && !flipReq) { u32 mm = 0; for (; mm < m; mm++) if (!in_window(L.rsx[mm], ((u32)i + mm) << 2)) break; m = mm; ok = m >= 1u; }
+                if (ok && !flipReq && lanesMin != 0u) {
+                    // (a lane per read of the plan: it walks the slots of its start window -- as many rounds as the largest of these windows has slots, typically 1 to 3 --
+                    //  and the step keeps the reads in front of the first one that did not find itself.  The ring as it stands holds every start window: rsx <= RUN_DMAX < nwin.)
+                    const bool act = lane < m;
+                    const u32 pc = L.pcw[((int)L.rst[3] + L.rsx[act ? lane : 0u]) & (RUN_PW - 1)]; const u32 wf = pc & 255u, wc = pc >> 8, key = ((u32)i + lane) << 2;
+                    bool pend = act && wc != 0u && wc <= 64u, found = false;
+                    for (u32 s = 0; __any(pend); s++) { const u32 e_ = L.pent[(wf + s) & RM]; found = found || (pend && e_ == key); pend = pend && !found && s + 1u < wc; }
+                    m = (u32)__builtin_ctzll(__ballot(!found)); ok = m >= 1u;          // (m <= RUN_MMAX <= 64 before: the lanes behind it found nothing)
+                }
+                else if (ok && !flipReq) { u32 mm = 0; for (; mm < m; mm++) if (!in_window(L.rsx[mm], ((u32)i + mm) << 2)) break; m = mm; ok = m >= 1u; }
                 else if (ok && d2 == 0) { ok = in_window(d1, ((u32)i << 2) | 2u);
 #ifdef SAGE2OV_STAMPS
                     if (!ok && lane == 0) st_acc[30] += 1;
@@ -649,9 +721,9 @@ __global__ __launch_bounds__(64 * WPB, (NW > 20 ? 1 : (NW > 10 ? 2 : (WPL >= 3 ?
                     if (ok && flipReq) { if (lane == 0) L.rst[3] += (u32)dd; wave_sync(); }   // (a one-read step moves the current position; the step for several reads keeps it until the records are out)
                 }
                 STAMP(22);
-                u32 nDone = 0;
+                u32 nDone = 0; bool byLanes = false;
                 if (ok && !flipReq) {
-                    records((u32)i, m, true);
+                    byLanes = records((u32)i, m, true);
                     wave_sync();
                     if (lane == 0) { const int J0n = (int)L.rst[3] + L.rsx[m - 1u]; const u32 base = L.rst[5]; const u32 drop2 = ((L.pcw[J0n & (RUN_PW - 1)] & 255u) - base) & RM;      // (the windows of the reads before the last one leave)
                                      L.rst[3] = (u32)J0n; L.rst[5] = (base + drop2) & RM; L.rst[6] -= drop2; L.rst[1] = (u32)L.rsx[RUN_MMAX - 1u + m]; }
@@ -665,8 +737,12 @@ __global__ __launch_bounds__(64 * WPB, (NW > 20 ? 1 : (NW > 10 ? 2 : (WPL >= 3 ?
 #ifdef SAGE2OV_STAMPS
                     if (lane == 0) { st_acc[24] += nDone; st_acc[28] += 1; }
 #endif
-                    // (the reads answered with this one are taken off the wave's items)
-                    for (u32 k2 = 1; k2 < nDone; k2++) { idCur = idNext; idNext = advance(lane); }
+                    // (the wave's run counters, CTR_RUNSTATS: reads answered off the ring, steps; of them with a lane per read.  Four LDS words, one ds_add per step.)
+                    if (lane < (byLanes ? 4u : 2u)) atomicAdd(&L.rsx[RSX_CNT + lane], (int)((lane & 1u) ? 1u : nDone));
+                    // (the reads answered with this one are taken off the wave's items.  They are consecutive items of the visit -- a1, a2, a3 of the plan --: idCur and idNext
+                    //  hold the first two, the others are skipped where they stand and the last two calls fetch what follows; the plan's `avail` keeps vIt <= vEnd)
+                    if (nDone > 3u) vIt += nDone - 3u;
+                    for (u32 k2 = 1; k2 < min(nDone, 3u); k2++) { idCur = idNext; idNext = advance(lane); }
                     if (nDone > 1u) { metaNext = A.meta ? (u32)A.meta[idCur] : 0xFFFFu; if constexpr (RUN) metaNext = (u32)__builtin_amdgcn_readfirstlane((int)metaNext); }
                     wave_sync();
                     continue;
@@ -1525,6 +1601,11 @@ __global__ __launch_bounds__(64 * WPB, (NW > 20 ? 1 : (NW > 10 ? 2 : (WPL >= 3 ?
             if (lane == 0) { A.right[i] = rv | (u64)pr; A.left[i] = lv | (u64)pl; A.conn[i] = nhits; }
         }
         STAMP(9);
+    }
+    if constexpr (RUN) {                                           // the wave's run counters go to the device's once, when it has run out of items
+        wave_sync();
+        const u32 rc_ = lane < 4u ? (u32)L.rsx[RSX_CNT + lane] : 0u;
+        if (rc_ != 0u) atomicAdd(&COLD(A, counters)[CTR_RUNSTATS + lane], (u64)rc_);
     }
     if (HITS || (ALWAYS_TAIL && A.hitBase)) {
         for (u32 x = lane; x < hLeft; x += 64) A.hits[hBase + x].from = 0;

@@ -51,6 +51,8 @@ struct ProbeArgs {
     u32 chunkShift;      // log2 of the positions a block takes per visit: FAST_CHUNK_LOG or FAST_CHUNK_LOG + 1 (plan_fast_grid)
     u32 noRun;           // 1: the sequential-groups form does not enter run mode (tests: both ways must give the same records; SAGE2OV_NO_RUN_MODE)
     u32 noParTail;       // 1: the state machine of the fast kernel steps through the hits one by one, never in its parallel form (tests: both ways, the same records; SAGE2OV_NO_PAR_TAIL)
+    u32 runLanesMin;     // run mode: planned steps of this many reads and more compute their records with a lane per read; 0: plan, own-entry checks and records loop over the reads
+                         // (RUN_LANES_MIN; tests: SAGE2OV_RUN_LANES=0, SAGE2OV_RUN_LANES_MIN=<n>: the same records every way)
 };
 #ifdef SAGE2OV_STAMPS
 #define STAMP(k) do { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); const u64 t_ = __builtin_amdgcn_s_memtime(); st_acc[k] += t_ - st_prev; st_prev = t_; } while (0)

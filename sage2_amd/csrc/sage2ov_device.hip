@@ -62,10 +62,12 @@ enum {
                           //   the minimum overlap, [4] shortest good read, [5] reads beyond the length limit
     CTR_FILTER = 23,      // reduce phase, pre-hits filter (k_hits_filter), 2 words: [0] kept hits, [1] unresolved reads without written hits
     CTR_RUNSTARTS = 25,   // locality order (k_loc_index), 64 words: run starts, spread over 64 words (Device::d_runStarts)
-    CTR_WORDS = 25 + 64   // what dev_create allocates
+    CTR_RUNSTATS = 25 + 64,   // fast kernel, run mode, 4 words: [0] reads answered off the ring, [1] steps, [2] of those reads: records computed with a lane per read, [3] such steps
+                          //   (zeroed by dev_probe, summed over its launches; read back on request only: dev_probe_run_stats)
+    CTR_WORDS = 25 + 64 + 4   // what dev_create allocates
 };
 static_assert(CTR_RECIP + 5 <= CTR_HIT_CURSOR && CTR_HIT_CURSOR + 1 <= CTR_HIT_REAL && CTR_HIT_REAL + 1 <= CTR_HANDED && CTR_RECIP + 9 <= CTR_INDEX && CTR_HANDED + 2 <= CTR_INDEX && CTR_INDEX + 10 <= CTR_FILTER && CTR_MARKS + 5 <= CTR_ORG && CTR_ORG + 6 <= CTR_FILTER &&
-              CTR_FILTER + 2 <= CTR_RUNSTARTS && CTR_RUNSTARTS + 64 <= CTR_WORDS, "a counter group runs into the next one, or past the allocation");
+              CTR_FILTER + 2 <= CTR_RUNSTARTS && CTR_RUNSTARTS + 64 <= CTR_RUNSTATS && CTR_RUNSTATS + 4 <= CTR_WORDS, "a counter group runs into the next one, or past the allocation");
 struct MateLib { u64* key = nullptr; u64* cnt = nullptr; u64* first = nullptr; u64 n = 0; };      // one library's mate table: sorted by key, unique (kernels_mates.inc)
 struct Mates { MateLib lib[128]; u64* pkey = nullptr; u64* pord = nullptr; u64 pn = 0, pcap = 0; };   // + the pending records of the call in progress (keys, record ordinals)
 struct Device {
@@ -886,6 +888,8 @@ static ProbeArgs base_args(Device* d) {
     A.mi1 = d->mi1; A.TL = d->TL; A.krec = d->krec; A.uniL = d->uniL;
     A.chunkShift = (u32)FAST_CHUNK_LOG;      // (plan_fast_grid may double the positions per block visit)
     A.noRun = d->opt.get("SAGE2OV_NO_RUN_MODE") ? 1u : 0u; A.noParTail = d->opt.get("SAGE2OV_NO_PAR_TAIL") ? 1u : 0u;
+    // (run mode with a lane per read: RUN_LANES_MIN; the switches are for the tests -- every setting gives the same records)
+    A.runLanesMin = d->opt.num("SAGE2OV_RUN_LANES", 1) == 0 ? 0u : (u32)std::max<long long>(1, std::min<long long>(RUN_MMAX + 1, d->opt.num("SAGE2OV_RUN_LANES_MIN", RUN_LANES_MIN)));
     return A;
 }
 
@@ -978,6 +982,13 @@ static unsigned plan_fast_grid(const Options& O, ProbeArgs& A, u64 n, bool write
     return (unsigned)(block0 + nb);
 }
 
+// the run counters of the last dev_probe (CTR_RUNSTATS)
+int dev_probe_run_stats(Device* d, uint64_t out[4], std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    u64 c[4]; { int rc = read_counters(d, CTR_RUNSTATS, 4, c, err); if (rc) return rc; }
+    for (int x = 0; x < 4; x++) out[x] = c[x];
+    return 0;
+}
 void dev_set_probe_share(Device* d, double share) { d->probeShare = share; }
 bool dev_has_minimiser_groups(Device* d) { return d->mi1 != nullptr && d->TL != 0; }
 
@@ -1031,6 +1042,7 @@ int dev_probe(Device* d, uint64_t lo, uint64_t hi, std::string& err) {
     HIPCHK(hipMemsetAsync(d->right, 0, (N + 1) * sizeof(u64), d->stream)); HIPCHK(hipMemsetAsync(d->left, 0, (N + 1) * sizeof(u64), d->stream));
     HIPCHK(hipMemsetAsync(d->conn, 0, (N + 1) * sizeof(u32), d->stream)); HIPCHK(hipMemsetAsync(d->cflag, 0, (N + 1) * sizeof(u32), d->stream));
     HIPCHK(hipMemsetAsync(d->d_counters + CTR_HANDED, 0, 2 * sizeof(u64), d->stream));
+    HIPCHK(hipMemsetAsync(d->d_counters + CTR_RUNSTATS, 0, 4 * sizeof(u64), d->stream));
     ProbeArgs A = base_args(d); A.lo = lo; A.hi = hi;
     const u64 nreads = hi > lo ? hi - lo : 0;
     d->pre.valid = false;

@@ -2260,6 +2260,11 @@ int sage2ov_run_steps23(sage2ov_ctx* c) {
     c->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return SAGE2OV_OK;
 }
+int sage2ov_probe_run_stats_get(sage2ov_ctx* c, uint64_t out[4]) {
+    if (!c || !out) return SAGE2OV_ERR_ARG;
+    if (!c->device()) return c->fail(SAGE2OV_ERR_DEVICE, "no GPU context: the probe pass runs on the device only");
+    return dev_probe_run_stats(c->device(), out, c->err);
+}
 int sage2ov_timings_reset(sage2ov_ctx* c) { if (!c) return SAGE2OV_ERR_ARG; if (c->device()) dev_reset_timings(c->device()); c->reduce_ms = 0; c->total_ms = 0; return SAGE2OV_OK; }
 int sage2ov_timings_get(const sage2ov_ctx* c, sage2ov_timings* o) {
     if (!c || !o) return SAGE2OV_ERR_ARG;

@@ -76,6 +76,8 @@ int dev_build_index(Device* d, uint64_t* slots, uint64_t* keys, uint64_t* csr, u
 int dev_lookup(Device* d, uint64_t hi, uint64_t lo, uint64_t* entries, uint32_t cap, uint32_t* count, std::string& err);
 // probe+verify+extension kernel over ids [lo, hi)
 int dev_probe(Device* d, uint64_t lo, uint64_t hi, std::string& err);
+// run mode of the last dev_probe: {reads answered off the ring, steps, of those reads: records with a lane per read, such steps}
+int dev_probe_run_stats(Device* d, uint64_t out[4], std::string& err);
 // multi-GPU record exchange: 24 bytes per read {right u64, left u64, conn u32, cflag u32}
 int dev_export_records(Device* d, void* dev_dst, uint64_t lo, uint64_t hi, std::string& err);
 int dev_import_records(Device* d, const void* dev_src, uint64_t first, uint64_t n, std::string& err);
