@@ -168,9 +168,10 @@ def same_fasta_up_to_ties(ref_text, rows):
                     own.setdefault((r["contig_length"], r["string_length"], r["frm"], r["to"]), []).append((r["gaps"], r["ns"]))
                 g, n = g0, n0
                 for t in theirs:
-                    cands = own[(t["contig_length"], t["string_length"], t["frm"], t["to"])]; dg, dn = cands.pop(0)
-                    g += dg; n += dn
-                    assert (t["gaps"], t["ns"]) == (g, n) or any((t["gaps"], t["ns"]) == (g - dg + a, n - dn + b) for a, b in cands)      # (parallel edges: either one)
+                    cands = own[(t["contig_length"], t["string_length"], t["frm"], t["to"])]
+                    pick = next((c for c in cands if (t["gaps"], t["ns"]) == (g + c[0], n + c[1])), None)      # (parallel edges: the one the reference took here,
+                    assert pick is not None, (t, g, n, cands)                                                  # and the running totals go on from that one)
+                    cands.remove(pick); g += pick[0]; n += pick[1]
             else:
                 assert all(g0 <= t["gaps"] <= g1 and n0 <= t["ns"] <= n1 for t in theirs)
         g0, n0 = g1, n1; i = j
