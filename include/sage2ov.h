@@ -548,6 +548,14 @@ int sage2ov_timings_reset(sage2ov_ctx* ctx);
  * out[0] reads answered off the slot ring, out[1] steps that answered them (a step answers up to 16 consecutive reads), out[2] of those reads: records computed
  * with a lane per read, out[3] such steps.  Zero where the resident reads have no run mode (several lengths, k > 64, noisy data's forms). */
 int sage2ov_probe_run_stats_get(sage2ov_ctx* ctx, uint64_t out[4]);
+/* Which way the reduce phase went in the last sage2ov_overlap_reduce / sage2ov_run_steps23 (a multi-rank context: this rank's share of the marks).  Every word
+ * is a counter the phase keeps anyway, copied on its read-backs:
+ * out[0] form: 0 nothing unresolved, 1 symmetric form on the device, 2 ranked form on the device, 3 serial replay on the host; out[1] unresolved reads;
+ * out[2] lists of more than 128 entries (handed to the second size class of the marks' kernel); out[3] lists beyond its 512 entries (marked out of global scratch);
+ * out[4] neighbour lists the marks' short cut read; out[5] reads whose marks it settled; out[6] removed entries; out[7] potential lists of more than 1024 entries
+ * (ranked form: sorted on the host); out[8] slices the potential lists were built in.  out[2..5], [7], [8] are zero in form 3. */
+#define SAGE2OV_REDUCE_STATS 9
+int sage2ov_reduce_stats_get(sage2ov_ctx* ctx, uint64_t out[SAGE2OV_REDUCE_STATS]);
 void* sage2ov_stream(sage2ov_ctx* ctx);   /* hipStream_t the context launches on */
 
 /* ---- deterministic synthetic reads (repo-owned, not part of the reference) ---- */

@@ -115,6 +115,7 @@ struct Oracle {
     // ---- step 3 state
     std::vector<Ext> rightE, leftE; std::vector<uint8_t> status; std::vector<uint32_t> conn;
     std::vector<std::vector<EdgeE>> adj;
+    std::vector<uint32_t> markLen, markCnt;   // per read, at its mark_transitive call: entries of its list, entries it marks (test export only)
     uint64_t nOv = 0, contained = 0, containedSize = 0, edgesInserted = 0, transRemoved = 0, hashMissSearch = 0;
     // final canonical edge list (overlapGraph.cpp:84-111)
     struct OutEdge { uint64_t from, to; uint32_t len, lenTwin; uint8_t type; };
@@ -389,6 +390,7 @@ struct Oracle {
     }
     // economyGraph.cpp:643-679 markTransitiveEdge
     void mark_transitive(uint64_t from, std::vector<uint8_t>& mk) {
+        markLen[from] = (uint32_t)adj[from].size();
         for (auto& e : adj[from]) mk[e.to] = 1;
         for (auto& e : adj[from]) {
             if (mk[e.to] != 1) continue;
@@ -399,7 +401,7 @@ struct Oracle {
                 else if ((t1 == 1 || t1 == 3) && (t2 == 2 || t2 == 3)) mk[f.to] = 2;
             }
         }
-        for (auto& e : adj[from]) if (mk[e.to] == 2) e.mark = 1;
+        for (auto& e : adj[from]) if (mk[e.to] == 2) { e.mark = 1; markCnt[from]++; }
         for (auto& e : adj[from]) mk[e.to] = 0;
         mk[from] = 0; status[from] = 2;
     }
@@ -414,6 +416,7 @@ struct Oracle {
         auto t0 = std::chrono::steady_clock::now();
         std::vector<uint8_t> mk(N + 1, 0); std::vector<uint64_t> queue; queue.reserve(1024);
         edgesInserted = transRemoved = 0;
+        markLen.assign(N + 1, 0); markCnt.assign(N + 1, 0);
         for (uint64_t i = 1; i <= N; i++) {
             if (status[i] != 0) continue;
             queue.clear(); size_t start = 0; queue.push_back(i);
@@ -528,6 +531,11 @@ void orc_export_initial(void* p, uint64_t* right, uint64_t* left, uint8_t* statu
         left[i] = o->leftE[i].id | ((uint64_t)o->leftE[i].type << 40) | ((uint64_t)o->leftE[i].len << 42);
         status[i] = o->status[i]; conn[i] = o->conn[i];
     }
+}
+// list length and number of marked entries of every read at its mark_transitive call (arrays sized N+1; 0 for reads never marked)
+void orc_export_mark_lengths(void* p, uint32_t* length, uint32_t* marked) {
+    auto* o = (Oracle*)p;
+    for (uint64_t i = 0; i <= o->N; i++) { length[i] = i < o->markLen.size() ? o->markLen[i] : 0; marked[i] = i < o->markCnt.size() ? o->markCnt[i] : 0; }
 }
 // canonical edges: 5 u64 per edge (from, to, type, len, lenTwin)
 void orc_export_edges(void* p, uint64_t* e) {

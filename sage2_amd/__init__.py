@@ -575,6 +575,14 @@ class Context:
         self._chk(lib().sage2ov_probe_run_stats_get(self._h, out))
         return tuple(int(v) for v in out)
 
+    REDUCE_STATS = ("form", "unresolved", "lists_over_128", "lists_over_512", "shortcut_lists", "shortcut_reads", "removed", "potential_over_1024", "slices")
+
+    def reduce_stats(self):
+        """which way the last reduce phase went, as a dict over REDUCE_STATS (form: 0 nothing unresolved, 1 symmetric device, 2 ranked device, 3 serial replay on the host)"""
+        out = (C.c_uint64 * len(self.REDUCE_STATS))()
+        self._chk(lib().sage2ov_reduce_stats_get(self._h, out))
+        return dict(zip(self.REDUCE_STATS, (int(v) for v in out)))
+
     def debug_all_hits(self):
         n = C.c_uint64()
         self._chk(lib().sage2ov_debug_all_hits(self._h, None, C.c_uint64(0), C.byref(n)))

@@ -202,7 +202,7 @@ __device__ __forceinline__ bool ra_shortcut(RaLds<CAP, HTLOG>& L, u32 n, u32 lan
     if (bad) { for (u32 x = lane; x < n; x += 64) L.mk[L.slot[x]] = 1; wave_sync(); return false; }
     return true;
 }
-// counters: [0] lists longer than RA_CAP (-> host replay), [1] removed entries.  svn[w] = survivors with to > r of the w-th read.
+// counters: [0] lists longer than RA_CAP (-> k_ra_mark_big), [1] removed entries.  svn[w] = survivors with to > r of the w-th read.
 // The reads whose list has more than NLO and at most CAP entries (NLO = 0: empty lists too); the last size class hands longer lists over.
 constexpr int RA_B = 6;                           // neighbour lists fetched and looked up together
 constexpr int RA_BLOCKS = 8;                      // occupancy bound of k_ra_mark's __launch_bounds__ for lists of at most 128 entries (longer lists: 4)

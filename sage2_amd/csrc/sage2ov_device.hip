@@ -118,6 +118,7 @@ struct Device {
     // step 4: blocks a call released, kept for the next call (it asks for the same ~50 sizes; fresh HBM costs ~50 ms per GB to map, 0.7 s per call at BASELINE
     // configs[2]).  Emptied when the read set changes, when the workspace arena runs out of memory, and never filled in memory-diet mode.
     std::vector<std::pair<void*, size_t>> s4cache;
+    u64 reduceStats[SAGE2OV_REDUCE_STATS] = {0};   // which way the last dev_reduce_device went (dev_reduce_stats; the layout of sage2ov_reduce_stats_get)
     void* rrStaging = nullptr;   // ranked reduce: the pinned 2 MB-page host buffers the potential lists are downloaded into, kept from step to step (RrStaging)
     // workspace arena: buffers of the timed path are allocated once and only ever grow (no hipMalloc/hipFree per step)
     struct Buf { void* p = nullptr; size_t cap = 0; u32 epoch = 0; };
@@ -989,6 +990,8 @@ int dev_probe_run_stats(Device* d, uint64_t out[4], std::string& err) {
     for (int x = 0; x < 4; x++) out[x] = c[x];
     return 0;
 }
+// which way the last dev_reduce_device went: the words of sage2ov_reduce_stats_get (form 0 when it left the phase to the caller's replay)
+void dev_reduce_stats(Device* d, uint64_t out[SAGE2OV_REDUCE_STATS]) { for (int x = 0; x < SAGE2OV_REDUCE_STATS; x++) out[x] = d->reduceStats[x]; }
 void dev_set_probe_share(Device* d, double share) { d->probeShare = share; }
 bool dev_has_minimiser_groups(Device* d) { return d->mi1 != nullptr && d->TL != 0; }
 
@@ -1366,7 +1369,7 @@ static int hit_list_pass(Device* d, ProbeArgs& A, unsigned blocks, u64 c[3], u64
     return read_counters(d, CTR_HIT_CURSOR, 1, used, err);
 }
 // Reduce phase on the device (see k_ra_mark): dev_reduce_device is the sequence of the stages below.  *done = 0 when the preconditions do not hold (too few
-// unresolved reads to be worth it, a list longer than RA_CAP, 32-bit offsets exhausted): the caller then runs the serial replay on the host; nothing but the
+// unresolved reads to be worth it, more than 2^16 lists longer than RA_CAP, 32-bit offsets exhausted; a list longer than RA_CAP alone goes to k_ra_mark_big): the caller then runs the serial replay on the host; nothing but the
 // idempotent 0x80 flags has been changed in that case.  A stage says so by returning REDUCE_REPLAY.
 // When some bucket is long (ranked: one-sided discovery, economyGraph.cpp:513-564) the order in which the unresolved reads are explored decides which edges
 // exist: the potential lists are built here, the order is found by the host's walk (explore_order, sage2ov_walk.cpp) and comes back as ranks.
@@ -1382,10 +1385,12 @@ struct ReduceRun {                                                              
     Hit* dh = nullptr; u64 nh = 0, nslots = 0; u32* hitcount = nullptr;              // hit lists: nh real hits in slots [0, nslots) of dh; hits per read position
     u32 *deg = nullptr, *offs = nullptr, *cur = nullptr, *rankDev = nullptr; u64* ent = nullptr; u32* ent32 = nullptr; uint8_t* rm = nullptr; u64 present = 0;      // final lists
     u32 *svn = nullptr, *svoff = nullptr; u64 removed = 0;                           // marks: survivors per read of the share, this rank's removals
+    u64 nMid = 0, nHeavy = 0, scLists = 0, scReads = 0, potBeyond = 0, slices = 0;   // which way it went (Device::reduceStats): CTR_MARKS [4] [0] [2] [3], CTR_RANKED[3], slices of potential lists
+    u64 gridCap = 256ull * 256;                                                      // SAGE2OV_TEST_MARK_BLOCKS=<b>: at most b blocks for marks and emission (tests: a wave walks many reads of a small input)
     bool timing = false; std::chrono::steady_clock::time_point tp;
     void lap(Device* d, const char* what) { if (!timing) return; hipStreamSynchronize(d->stream); auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[reduce/device] %-30s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(t - tp).count()); tp = t; }
     // (the grid of marks and emission: a wave per read, blocks walk the list round-robin; blocks per CU -> reduce phase at configs[1] + 0.1 % errors: 16 -> 69.5 ms, 64 -> 66.0, 256 -> 65.2, 1024 -> 65.2: the tail again)
-    unsigned share_grid() const { return (unsigned)std::max<u64>(1, std::min<u64>((whi - wlo + 3) / 4, 256ull * 256)); }
+    unsigned share_grid() const { return (unsigned)std::max<u64>(1, std::min<u64>((whi - wlo + 3) / 4, gridCap)); }
 };
 // Hit lists: directional hits of the unresolved reads, device resident: the fast kernel in its hit-list form (locality order, minimiser
 // groups), the sequential kernel for the few reads it hands over (> 128 candidates, ambiguous tags) and for the 16-word layout
@@ -1563,7 +1568,7 @@ static int reduce_ranked_order(Device* d, ReduceRun& R, std::string& err) {
         u64 w1 = w0, tot0 = 0; while (w1 < nun && (w1 == w0 || tot0 + L.hDegp[w1] <= sliceEntries)) tot0 += L.hDegp[w1++];
         if (tot0 >= (1ull << 32) - 64) return REDUCE_REPLAY;                      // one read with 2^32 potential neighbours: not this path
         { int rc = rank_slice(d, R, L, staging, w0, w1, err); if (rc) return rc; }
-        w0 = w1;
+        w0 = w1; R.slices++;
     }
     { size_t hx = 0; for (u64 w = 0; w < nun; w++) if (L.hDegp[w] > (u32)RR_CAP) L.listPtr[w] = L.heavyLists[hx++].data(); }      // (after the last push_back: the vectors no longer move)
     R.lap(d, "potential lists (build + sort + download)");
@@ -1587,7 +1592,7 @@ static int reduce_final_lists(Device* d, ReduceRun& R, std::string& err) {
     if (nc) hipLaunchKernelGGL(k_ra_fill_c, dim3(grid_for(nc, 256)), dim3(256), 0, d->stream, d->cand, (u64)nc, d->reads, d->S, d->uniL, offs, R.cur, ent, ent32);
     if (R.ranked) { if (nslots) hipLaunchKernelGGL(k_rr_fill_h, dim3(grid_for(nslots, 256)), dim3(256), 0, d->stream, R.dh, (u64)nslots, R.rankDev, d->reads, d->S, d->uniL, offs, R.cur, ent, ent32); }
     else if (nslots) hipLaunchKernelGGL(k_ra_fill_h, dim3(grid_for(nslots, 256)), dim3(256), 0, d->stream, R.dh, (u64)nslots, offs, deg, R.hitcount, ent, ent32);
-    if (R.ranked) { u64 c3[3]; int rc = read_counters(d, CTR_RANKED, 3, c3, err); if (rc) return rc; R.present = c3[2]; }
+    if (R.ranked) { u64 c4[4]; int rc = read_counters(d, CTR_RANKED, 4, c4, err); if (rc) return rc; R.present = c4[2]; R.potBeyond = c4[3]; }
     return 0;
 }
 // the marks of lists beyond the LDS kernel (heavy[0, nhv), listed by k_ra_mark): same marking out of global scratch, one wavefront each; c = CTR_MARKS afterwards
@@ -1620,9 +1625,10 @@ static int reduce_marks(Device* d, ReduceRun& R, std::string& err) {
     hipLaunchKernelGGL((k_ra_mark<128, 8, 0, false>), dim3(gb), dim3(256), 0, d->stream, ids, (u64)nun, R.offs, R.deg, R.ent, R.ent32, R.rm, svn, d->d_counters + CTR_MARKS, heavy, heavyCap, noShortcut, mid);     // lists of <= 128 entries
     hipLaunchKernelGGL((k_ra_mark<RA_CAP, 10, 128, true>), dim3(gb), dim3(256), 0, d->stream, ids, (u64)nun, R.offs, R.deg, R.ent, R.ent32, R.rm, svn, d->d_counters + CTR_MARKS, heavy, heavyCap, noShortcut, mid);   // 129 .. RA_CAP (the reads the first launch listed); longer: k_ra_mark_big
     }
-    u64 c[4];
-    { int rc = read_counters(d, CTR_MARKS, 4, c, err); if (rc) return rc; }
+    u64 c[5];
+    { int rc = read_counters(d, CTR_MARKS, 5, c, err); if (rc) return rc; }
     HIPCHK(hipGetLastError());
+    R.nHeavy = c[0]; R.scLists = c[2]; R.scReads = c[3]; R.nMid = c[4];      // (before reduce_marks_heavy reads c again)
     if (R.timing) fprintf(stderr, "[reduce/device] marks of %llu of %llu reads by the short cut (k_ra_mark: ra_shortcut), %.2f lists read per read\n", (unsigned long long)c[3], (unsigned long long)nun, nun ? (double)c[2] / (double)nun : 0.0);
     if (c[0] > heavyCap) { if (R.shareWorld > 1) { err = "reduce: too many oversized lists in this rank's share"; return SAGE2OV_ERR_LIMIT; } return REDUCE_REPLAY; }   // (never seen) that many oversized lists: serial replay (a rank of many cannot decide that alone)
     if (c[0]) { int rc = reduce_marks_heavy(d, R, ids, heavy, (u32)c[0], c, err); if (rc) return rc; }
@@ -1646,10 +1652,13 @@ int dev_reduce_device(Device* d, uint64_t min_unresolved, uint64_t* n_unresolved
                       uint32_t shareRank, uint32_t shareWorld) {
     HIPCHK(hipSetDevice(d->ordinal));
     *done = 0; *inserted = 0; *removed = 0; *n_hits = 0;
+    for (u64& v : d->reduceStats) v = 0;
     HIPCHK(hipEventRecord(d->ev[0], d->stream));
     ReduceRun R;
+    if (const char* eb = d->opt.get("SAGE2OV_TEST_MARK_BLOCKS")) R.gridCap = (u64)std::max(1, atoi(eb));
     { int rc = collect_unresolved(d, &R.ids, &R.nun, err); if (rc) return rc; }
     const u64 nun = R.nun; *n_unresolved = nun;
+    d->reduceStats[1] = nun;
     if (nun == 0) { *done = 1; return 0; }
     if (nun < min_unresolved) return 0;
     R.ranked = d->n_long != 0; R.shareWorld = shareWorld;
@@ -1665,6 +1674,7 @@ int dev_reduce_device(Device* d, uint64_t min_unresolved, uint64_t* n_unresolved
     if (!rc) rc = reduce_emit(d, R, err);
     if (rc) return rc == REDUCE_REPLAY ? 0 : rc;                          // (replay: *done stays 0)
     *inserted = R.ranked ? 2 * R.present : R.nh; *removed = R.removed; *done = 1;
+    { const u64 st[SAGE2OV_REDUCE_STATS] = {R.ranked ? 2ull : 1ull, nun, R.nMid, R.nHeavy, R.scLists, R.scReads, R.removed, R.potBeyond, R.slices}; for (int x = 0; x < SAGE2OV_REDUCE_STATS; x++) d->reduceStats[x] = st[x]; }
     HIPCHK(hipEventRecord(d->ev[1], d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
     float ms = 0; hipEventElapsedTime(&ms, d->ev[0], d->ev[1]); d->tm.hits_ms += ms;
     hipEventElapsedTime(&ms, d->ev[5], d->ev[1]); d->tm.marks_ms += ms;

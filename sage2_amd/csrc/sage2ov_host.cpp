@@ -144,6 +144,7 @@ struct sage2ov_ctx {
     double reduce_ms = 0, total_ms = 0;
     // multi-rank contexts: the survivors this rank's share of the reduce phase re-emitted = candidates [survBase, survBase + survCount) of the device list
     uint64_t survBase = 0, survCount = 0, removedPartial = 0; bool survivorsExchanged = true;
+    uint64_t rstats[SAGE2OV_REDUCE_STATS] = {0};   // which way the last reduce phase went (sage2ov_reduce_stats_get)
 
     int fail(int code, const std::string& m) { err = m; return code; }
 };
@@ -1403,7 +1404,9 @@ int sage2ov_overlap_reduce(sage2ov_ctx* c) {
         if (!c->opt.get("SAGE2OV_HOST_REDUCE")) {
             int rc0 = dev_reduce_device(c->device(), minUn, &nun0, &nh0, &ins, &rem, &done, c->err, c->cfg.rank, multi ? c->cfg.world : 1); if (rc0) return rc0;
         }
+        for (uint64_t& v : c->rstats) v = 0;
         if (done) {
+            dev_reduce_stats(c->device(), c->rstats);
             c->survCount = dev_cand_count(c->device()) - c->survBase; c->removedPartial = rem;
             c->ostats.unresolved_hits = nh0; c->ostats.edges_inserted = ins; c->ostats.transitive_removed = rem;
             c->reduce_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -1417,6 +1420,7 @@ int sage2ov_overlap_reduce(sage2ov_ctx* c) {
     int rc = dev_unresolved_hits(c->device(), hits, &nun, c->err, &ids); if (rc) return rc;
     lap("hit lists (device + download)");
     c->ostats.unresolved_hits = hits.size(); c->ostats.edges_inserted = 0; c->ostats.transitive_removed = 0;
+    c->rstats[0] = nun ? 3 : 0; c->rstats[1] = nun;
     if (nun) {
         std::vector<EdgeCand> near; rc = dev_collect_reduce_edges(c->device(), ids, near, c->err); if (rc) return rc;
         lap("ids + nearby candidates");
@@ -1440,7 +1444,7 @@ int sage2ov_overlap_reduce(sage2ov_ctx* c) {
         lap("replay set-up");
         R.timing = timing; R.run(ids);
         lap("replay (total)");
-        c->ostats.edges_inserted = R.inserted; c->ostats.transitive_removed = R.removed;
+        c->ostats.edges_inserted = R.inserted; c->ostats.transitive_removed = R.removed; c->rstats[6] = R.removed;
         // surviving list entries of unresolved reads with to > from replace what the device dropped
         std::vector<EdgeCand> survivors;
         for (uint32_t i : ids) for (auto& e : R.adj[R.dense[i] - 1]) if (e.to > i) survivors.push_back(EdgeCand{i, e.to, e.len, e.type});
@@ -2264,6 +2268,11 @@ int sage2ov_probe_run_stats_get(sage2ov_ctx* c, uint64_t out[4]) {
     if (!c || !out) return SAGE2OV_ERR_ARG;
     if (!c->device()) return c->fail(SAGE2OV_ERR_DEVICE, "no GPU context: the probe pass runs on the device only");
     return dev_probe_run_stats(c->device(), out, c->err);
+}
+int sage2ov_reduce_stats_get(sage2ov_ctx* c, uint64_t out[SAGE2OV_REDUCE_STATS]) {
+    if (!c || !out) return SAGE2OV_ERR_ARG; if (!c->reduced) return c->fail(SAGE2OV_ERR_ARG, "run the reduce phase first");
+    for (int x = 0; x < SAGE2OV_REDUCE_STATS; x++) out[x] = c->rstats[x];
+    return SAGE2OV_OK;
 }
 int sage2ov_timings_reset(sage2ov_ctx* c) { if (!c) return SAGE2OV_ERR_ARG; if (c->device()) dev_reset_timings(c->device()); c->reduce_ms = 0; c->total_ms = 0; return SAGE2OV_OK; }
 int sage2ov_timings_get(const sage2ov_ctx* c, sage2ov_timings* o) {

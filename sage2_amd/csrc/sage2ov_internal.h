@@ -2,6 +2,7 @@
 // and the device side (sage2ov_device.hip, hipcc).  Plain C++ structs, no HIP types leak out.
 #pragma once
 #include <cstdint>
+#include "sage2ov.h"
 #include <sys/mman.h>
 #include <algorithm>
 #include <cstdlib>
@@ -125,6 +126,8 @@ inline void touch_pages(void* p, size_t bytes, int nt) {
 struct OrgAscii { const char* bases; uint64_t nbytes; const uint64_t* off; uint64_t n_in; uint64_t good = 0, total_bp = 0, small = 0; int maxL = 0, minL = 0, S = 0; };
 int dev_organize_reads(Device* d, const uint64_t* pool, uint64_t pool_words, const uint64_t* off, const uint16_t* len, uint64_t n, int S, int minL, int maxL, int k,
                        uint64_t* N_out, RawU64& words_out, RawU16& freq_out, std::string& err, OrgAscii* ascii = nullptr);
+// which way the last dev_reduce_device went (the words of sage2ov_reduce_stats_get)
+void dev_reduce_stats(Device* d, uint64_t out[SAGE2OV_REDUCE_STATS]);
 int dev_reduce_device(Device* d, uint64_t min_unresolved, uint64_t* n_unresolved, uint64_t* n_hits, uint64_t* inserted, uint64_t* removed, int* done, std::string& err,
                       uint32_t shareRank = 0, uint32_t shareWorld = 1);
 int dev_export_cand_range(Device* d, void* dev_dst, uint64_t first, uint64_t n, std::string& err);

@@ -77,6 +77,13 @@ class Oracle:
         lib().orc_export_initial(self.h, C.c_void_p(right.ctypes.data), C.c_void_p(left.ctypes.data), C.c_void_p(status.ctypes.data), C.c_void_p(conn.ctypes.data))
         return right, left, status, conn
 
+    def export_mark_lengths(self):
+        """per read, at the moment its list was final (mark_transitive): entries of the list, entries marked; 0 for reads never marked"""
+        n = self.counter("N")
+        length = np.zeros(n + 1, dtype=np.uint32); marked = np.zeros(n + 1, dtype=np.uint32)
+        lib().orc_export_mark_lengths(self.h, C.c_void_p(length.ctypes.data), C.c_void_p(marked.ctypes.data))
+        return length, marked
+
     def export_edges(self):
         n = self.counter("edges")
         e = np.zeros((n, 5), dtype=np.uint64)

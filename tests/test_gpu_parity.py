@@ -668,7 +668,7 @@ def test_long_bucket_reduce_ranked_device_path_equals_serial_replay(monkeypatch)
     host, lists / marks / removals on the device) against the serial replay of the whole phase on the host -- same edges, same counters"""
     pd = dict(seed=31, genome_len=900000, n_reads=300000, read_len=150, err_ppm=1500, n_repeat_families=5, repeat_copies=250, repeat_len=350)
     bases, off = fx.make_reads(pd)
-    res = {}
+    res, rs = {}, {}
     for mode in ("default", "host"):
         if mode == "host":
             monkeypatch.setenv("SAGE2OV_HOST_REDUCE", "1")
@@ -676,8 +676,10 @@ def test_long_bucket_reduce_ranked_device_path_equals_serial_replay(monkeypatch)
             monkeypatch.delenv("SAGE2OV_HOST_REDUCE", raising=False)
         ctx = s2.Context(40); ctx.reads_add_ascii(bases, off); ctx.reads_organize(); ctx.run_steps23()
         st = ctx.overlap_stats(); res[mode] = (ctx.edges().tobytes(), st.edges_inserted, st.transitive_removed, st.left_to_explore, ctx.index_stats().long_buckets)
-        ctx.close()
+        rs[mode] = ctx.reduce_stats(); ctx.close()
     assert res["default"][4] > 0 and res["default"][3] > 100000
+    assert rs["default"]["form"] == 2 and rs["host"]["form"] == 3              # the ranked form on the device, the serial replay on the host
+    assert rs["default"]["unresolved"] == rs["host"]["unresolved"] and rs["default"]["removed"] == rs["host"]["removed"] == res["default"][2]
     assert res["default"][1:] == res["host"][1:]
     assert res["default"][0] == res["host"][0]
     # ... and both against the pinned restatement of the reference (not only against each other)
@@ -690,11 +692,16 @@ def test_long_bucket_reduce_ranked_device_path_equals_serial_replay(monkeypatch)
 
 def test_long_bucket_reduce_with_oversized_lists_equals_serial_replay(monkeypatch):
     """a genome one quarter repeats: a few hundred unresolved reads next to the repeats are seen by thousands of others, so their potential
-    and final lists exceed what the LDS kernels hold (host-sorted potential lists, `k_ra_mark_big` out of global scratch) -- same edges
-    and counters as the serial replay"""
+    lists exceed what the device sorts (RR_CAP: host-sorted potential lists).  Their FINAL lists do not exceed the LDS kernel (Context.reduce_stats():
+    96 potential lists beyond 1024 entries, 22 final lists beyond 128, none beyond RA_CAP = 512 -- the longest has 284; nor with 1200 or 2500 copies per
+    family), so a planted fan is added to the reads (tests/redgen.py: 1024 reads behind two hubs that see none of them): two final lists of 1025 entries
+    for `k_ra_mark_big` out of global scratch -- same edges and counters as the serial replay"""
+    import redgen as rd
     pd = dict(seed=3, genome_len=1500000, n_reads=500000, read_len=150, err_ppm=1000, n_repeat_families=12, repeat_copies=300, repeat_len=400)
     bases, off = fx.make_reads(pd)
-    res = {}
+    fb, fo = rd.Case(691, k=40, L=150).blind(1024, stem=True).arrays()
+    bases = np.concatenate([bases, fb]); off = np.concatenate([off, off[-1] + fo[1:]])
+    res, rs = {}, {}
     for mode in ("default", "host"):
         if mode == "host":
             monkeypatch.setenv("SAGE2OV_HOST_REDUCE", "1")
@@ -702,8 +709,13 @@ def test_long_bucket_reduce_with_oversized_lists_equals_serial_replay(monkeypatc
             monkeypatch.delenv("SAGE2OV_HOST_REDUCE", raising=False)
         ctx = s2.Context(40); ctx.reads_add_ascii(bases, off); ctx.reads_organize(); ctx.run_steps23()
         st = ctx.overlap_stats(); res[mode] = (ctx.edges().tobytes(), st.edges_inserted, st.transitive_removed, st.left_to_explore, ctx.index_stats().long_buckets)
-        ctx.close()
+        rs[mode] = ctx.reduce_stats(); ctx.close()
     assert res["default"][4] > 500 and res["default"][3] > 100000
+    print("oversized lists:", rs["default"])
+    assert rs["default"]["form"] == 2 and rs["host"]["form"] == 3
+    assert rs["default"]["lists_over_512"] == 2 and rs["default"]["potential_over_1024"] > 2     # what the docstring claims: k_ra_mark_big and the host-sorted potential lists ran
+    assert rs["default"]["lists_over_128"] >= rs["default"]["lists_over_512"]
+    assert rs["default"]["unresolved"] == rs["host"]["unresolved"] and rs["default"]["removed"] == rs["host"]["removed"] == res["default"][2]
     assert res["default"][1:] == res["host"][1:]
     assert res["default"][0] == res["host"][0]
     monkeypatch.delenv("SAGE2OV_HOST_REDUCE", raising=False)
@@ -722,7 +734,7 @@ def test_long_bucket_reduce_more_shapes_equal_serial_replay(pd, k, monkeypatch):
     """the ranked device reduce against the serial replay on other shapes of data: mixed read lengths (containment marks next to
     long buckets), repeats shorter than a read, the long layout"""
     bases, off = fx.make_reads(pd)
-    res = {}
+    res, rs = {}, {}
     for mode in ("default", "host"):
         if mode == "host":
             monkeypatch.setenv("SAGE2OV_HOST_REDUCE", "1")
@@ -731,9 +743,11 @@ def test_long_bucket_reduce_more_shapes_equal_serial_replay(pd, k, monkeypatch):
             monkeypatch.setenv("SAGE2OV_DEVICE_REDUCE_MIN", "1")
         ctx = s2.Context(k); ctx.reads_add_ascii(bases, off); ctx.reads_organize(); ctx.run_steps23()
         st = ctx.overlap_stats(); res[mode] = (ctx.edges().tobytes(), st.edges_inserted, st.transitive_removed, st.left_to_explore, ctx.index_stats().long_buckets)
-        ctx.close()
+        rs[mode] = ctx.reduce_stats(); ctx.close()
         monkeypatch.delenv("SAGE2OV_DEVICE_REDUCE_MIN", raising=False)
     assert res["default"][4] > 0 and res["default"][3] > 1000
+    assert rs["default"]["form"] == 2 and rs["host"]["form"] == 3
+    assert rs["default"]["unresolved"] == rs["host"]["unresolved"] and rs["default"]["removed"] == rs["host"]["removed"] == res["default"][2]
     assert res["default"][1:] == res["host"][1:]
     assert res["default"][0] == res["host"][0]
     monkeypatch.setenv("SAGE2OV_DEVICE_REDUCE_MIN", "1")
@@ -748,7 +762,7 @@ def test_long_bucket_reduce_in_many_slices(monkeypatch):
     here with slices of 200 k entries, i.e. dozens of them, against the serial replay"""
     pd = dict(seed=3, genome_len=1500000, n_reads=500000, read_len=150, err_ppm=1000, n_repeat_families=12, repeat_copies=300, repeat_len=400)
     bases, off = fx.make_reads(pd)
-    res = {}
+    res, rs = {}, {}
     for mode in ("sliced", "host"):
         if mode == "host":
             monkeypatch.setenv("SAGE2OV_HOST_REDUCE", "1")
@@ -756,8 +770,9 @@ def test_long_bucket_reduce_in_many_slices(monkeypatch):
             monkeypatch.delenv("SAGE2OV_HOST_REDUCE", raising=False); monkeypatch.setenv("SAGE2OV_TEST_RANK_SLICE", "200000")
         ctx = s2.Context(40); ctx.reads_add_ascii(bases, off); ctx.reads_organize(); ctx.run_steps23()
         st = ctx.overlap_stats(); res[mode] = (ctx.edges().tobytes(), st.edges_inserted, st.transitive_removed, st.left_to_explore)
-        ctx.close(); monkeypatch.delenv("SAGE2OV_TEST_RANK_SLICE", raising=False)
+        rs[mode] = ctx.reduce_stats(); ctx.close(); monkeypatch.delenv("SAGE2OV_TEST_RANK_SLICE", raising=False)
     assert res["sliced"][1:] == res["host"][1:] and res["sliced"][0] == res["host"][0]
+    assert rs["sliced"]["form"] == 2 and rs["sliced"]["slices"] >= 12 and rs["host"]["form"] == 3      # dozens of slices, as the docstring says
 
 
 def test_device_filter_and_pack_of_ascii_input(monkeypatch):
