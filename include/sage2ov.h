@@ -329,6 +329,79 @@ int sage2ov_insert_estimate(const uint32_t* d, uint64_t n, uint64_t average_read
 int sage2ov_graph_flow_export(sage2ov_ctx* ctx, float* flow, uint64_t cap);
 int sage2ov_graph_flow_import(sage2ov_ctx* ctx, const float* flow, uint64_t n);
 
+/* ---- step 5 around its solver (CopyCountEstimator, overlapGraph/copycountEstimator.cpp): the genome-size estimate (:29-100), the flow network as
+ * input.cs2 (computeMinCostFlow, :105-355) and a solver's output.cs2 back onto the flows (:362-403), over the resident step-4 graph.  The solver itself (CS2, :359)
+ * is not part of the library: the caller runs any min-cost-flow solver on the file or the arc records.  computeMinCostFlow_new (:422-) is never called by main.cpp.
+ *
+ * State restated: the reference's after `-m 5` loads the files this library writes -- loadOverlapGraphFromFile (overlapGraph.cpp:371-443) of what
+ * sage2ov_graph4_save would write.  insertIntoList puts the newest edge first, so a node's edge list is the reverse of file order over the records that start at the
+ * node; a loop's record pair is in the file twice and is two edges, four records at its node.  checkIfAllReadsPresent (overlapGraph.cpp:445-493, main.cpp:199)
+ * runs first and replaces numberOfReads: n = the sum of Read::frequency over the reads that are a node with an edge or stand on a read list (reads_present).
+ *   k of a record     sum of frequency (uint16_t) over its read list (:73-79, :137-143, :250-254); forward and twin lists hold the same reads; 0 for a simple edge.
+ *                     delta = lengthOfEdge - 1.
+ *   genome size       previous = 0; up to 10 rounds (:36-49).  A round (:59-100) sums delta and k over the records with from < to (:69: each non-loop pair once, a
+ *                     loop never) that qualify: lengthOfEdge > 500 in the round with previous == 0 (:90), else a >= 3 && delta >= 1000 with
+ *                     a = (float)delta * ((float)n / (float)previous) - (float)k * log((float)2), every operation in float (:83-84).
+ *                     current = (uint64_t)((float)n / (float)kSum * (float)deltaSum) (:98); the rounds end when current == previous (:39).
+ *                     NAMED DIFFERENCE FROM ISO C++ (not from the reference): a float that does not fit uint64_t -- NaN when nothing qualifies, an infinity, 2^64 or
+ *                     more -- gives 2^63 = 9223372036854775808, as the reference's x86-64 build does for the NaN, and `degenerate` is 1.
+ *   classes           of a record with from >= to (:130, :229): simple (no list); once: a_1 >= 3 && delta >= 1000 (:146, :294); many: every other one.
+ *                     a_j = (float)delta * ((float)n / (float)G) - (float)k * log((float)((float)(j + 1) / (float)j)), j = 1..20 (:145, :256), G the genome size.
+ *                     many: flow_lb = the first j + 1, j = 1..19, with a_j < -3 && a_{j+1} > 3 when delta > 1000 (:305-315), else 1 when the list has more than 35
+ *                     entries (:318), else 0.
+ *   arcs              header, `n 1 0`, `n 2 0`, `a 2 1 1 <100 * network nodes> 0` (:190-193); network nodes = 4 * nodes + 2 (:160).  Six arcs per node that has an
+ *                     edge, nodes ascending, node_index = 3 + 4 * rank (:195-224).  Then for every node i ascending the records of its list, in list order, with
+ *                     i >= ID (:225-229): two arcs (simple: 0 100 cost 10000; once: 1 1 cost 1) or six (many: bounds :333-338); end points by typeOfEdge :258-285.
+ *   costs of a many   three float accumulators folded over the list entries in list order (:325-332), divided by 2, 2 and 995 (:340-342), printed as cost * 10 with
+ *                     std::fixed.  With <cmath> and `using namespace std`, log((float)x) is the float overload and log(N - first_UB), log(N - third_UB) -- integer
+ *                     arguments -- the double one: the terms of cost_1 and cost_3 are double, added to the float accumulator in double and rounded back; cost_2 is
+ *                     float throughout.  (n - xi) is uint64_t and goes to float or double as its partner demands.  The goldens confirm the overloads.
+ *   apply             a line `from to flow` (:365-366), in the solver's order.  Lines on node 1 or 2 are skipped (a `2 1` or `1 2` line is the T-to-S flow, the last such line when there are several, :372-373), as are
+ *                     lines whose ends are the same graph node (:378).  Else the flow is added to the first record of from_node's list whose ID is to_node
+ *                     (:380-387): with parallel edges the record written last in the file, whatever arc carried the flow.  Then both halves of every pair get
+ *                     (f + f_twin) / 2, and flow_different counts the pairs whose halves differed (:391-403).  The additions are small integers, exact in any
+ *                     order: integer atomics and one averaging pass equal the reference.
+ *   P.graph5          saveOverlapGraphInFile (overlapGraph.cpp:338-369): sage2ov_graph4_save's text with the genome size in line 1, reads_present in line 2 and
+ *                     the flows as `ostream << float` prints them.  A loop's pair is written twice (the reference, holding it as two edges, writes four).
+ * Every call: SAGE2OV_ERR_ARG without a step-4 graph, SAGE2OV_ERR_DEVICE on a device-less context.  Estimate and network go when the graph or the read set
+ * changes; build estimates first when the estimate is stale, count / export / save build first when the network is stale. */
+#define SAGE2OV_GENOME_ROUNDS 10
+typedef struct sage2ov_genome_estimate {
+    uint64_t genome_size;                              /* the estimate of the last round */
+    uint64_t estimate[SAGE2OV_GENOME_ROUNDS];          /* of every round run */
+    uint64_t delta_sum[SAGE2OV_GENOME_ROUNDS], k_sum[SAGE2OV_GENOME_ROUNDS];
+    uint32_t rounds;                                   /* rounds run, 1..10 */
+    uint32_t degenerate;                               /* the last round's float did not fit uint64_t */
+    uint32_t agreed;                                   /* the last round repeated the one before ("Final estimation"); 0 after ten rounds without */
+    uint32_t reserved;
+} sage2ov_genome_estimate;
+typedef struct sage2ov_flow_arc { uint32_t from, to; int32_t lower, upper; float cost; } sage2ov_flow_arc;      /* cost: as printed (already * 10).  Arc 0 is `2 1`:
+                                                                                                                 * its upper bound saturates at 2^31 - 1 here, the file has the exact number */
+typedef struct sage2ov_copycount_stats {
+    uint64_t genome_size, estimate[SAGE2OV_GENOME_ROUNDS];
+    uint32_t rounds, degenerate, agreed, reserved;
+    uint64_t reads_present;                            /* n: numberOfReads after checkIfAllReadsPresent */
+    uint64_t nodes, edges, simple, once, many;         /* as computeMinCostFlow logs them (:154-158); a loop counts four times */
+    uint64_t network_nodes, network_arcs;              /* the `p min` line */
+    uint64_t t_to_s_flow, flow_different;              /* of the last solution applied */
+    uint64_t solution_lines, lines_applied;            /* lines given, lines that found their record */
+    double prepare_ms, rounds_ms, order_ms, classes_ms, arcs_ms, apply_ms;      /* HIP-event times of the stages */
+} sage2ov_copycount_stats;
+/* the rounds alone, on the host: needs no context and no GPU.  length[i], k[i]: lengthOfEdge and k of the i-th non-loop pair (its record with from < to); reads: n */
+int sage2ov_genome_size_rounds(const uint32_t* length, const uint64_t* k, uint64_t pairs, uint64_t reads, sage2ov_genome_estimate* out);
+int sage2ov_genome_size_estimate(sage2ov_ctx* ctx, uint64_t* genome_size);
+int sage2ov_flow_network_build(sage2ov_ctx* ctx);                                       /* SAGE2OV_ERR_LIMIT from 2^32 - 2048 arcs on */
+int sage2ov_flow_network_count(sage2ov_ctx* ctx, uint64_t* network_nodes, uint64_t* arcs);
+int sage2ov_flow_network_export(sage2ov_ctx* ctx, sage2ov_flow_arc* out, uint64_t cap);  /* the arcs in input.cs2's order; cap below their number: SAGE2OV_ERR_ARG, nothing written */
+int sage2ov_flow_network_save(sage2ov_ctx* ctx, const char* path);                      /* input.cs2, byte for byte */
+/* n lines (from[i], to[i], flow[i]).  A node number that is 0 or above the network's nodes, or a null array: SAGE2OV_ERR_ARG, nothing changes (any other error: the
+ * supports and contigs are stale and the flows may be partly updated, as after a failed sage2ov_graph_flow_import).  The flows add onto those present; the
+ * supports and contigs are recomputed by the next call that needs them, as after sage2ov_graph_flow_import.  Needs the network (built when stale). */
+int sage2ov_flow_solution_apply(sage2ov_ctx* ctx, const uint64_t* from, const uint64_t* to, const uint64_t* flow, uint64_t n);
+int sage2ov_flow_solution_load(sage2ov_ctx* ctx, const char* path);                     /* output.cs2: whitespace-separated triples; anything else: SAGE2OV_ERR_IO */
+int sage2ov_graph5_save(sage2ov_ctx* ctx, const char* path);
+int sage2ov_copycount_stats_get(const sage2ov_ctx* ctx, sage2ov_copycount_stats* out);
+
 /* ---- the sweep of ContigExtender::findMatepairSupports (matePair/mergeContigs.cpp:959-1030): getSupportOfEdges (:1032-1097) over isUniqueInEdge (:1102-1110) for every
  * incoming x outgoing pair of composite edges of every node, on the device; all quantities are integers.  The merge that follows it in the
  * reference (mergeByMatepairSupports / mergeEdgesAndUpdate: serial, order-dependent, changes the graph) is NOT part of this library.

@@ -113,6 +113,24 @@ class LinkStats(C.Structure):
                 ("halves_ms", C.c_double), ("scan_ms", C.c_double), ("records_ms", C.c_double), ("sort_ms", C.c_double), ("reduce_ms", C.c_double)]
 
 
+# sage2ov_flow_arc (20 bytes): one arc of the flow network, cost as input.cs2 prints it
+FLOW_ARC_DTYPE = np.dtype([("from", np.uint32), ("to", np.uint32), ("lower", np.int32), ("upper", np.int32), ("cost", np.float32)])
+GENOME_ROUNDS = 10
+
+
+class GenomeEstimate(C.Structure):
+    _fields_ = [("genome_size", C.c_uint64), ("estimate", C.c_uint64 * GENOME_ROUNDS), ("delta_sum", C.c_uint64 * GENOME_ROUNDS), ("k_sum", C.c_uint64 * GENOME_ROUNDS),
+                ("rounds", C.c_uint32), ("degenerate", C.c_uint32), ("agreed", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class CopyCountStats(C.Structure):
+    _fields_ = [("genome_size", C.c_uint64), ("estimate", C.c_uint64 * GENOME_ROUNDS), ("rounds", C.c_uint32), ("degenerate", C.c_uint32), ("agreed", C.c_uint32),
+                ("reserved", C.c_uint32), ("reads_present", C.c_uint64), ("nodes", C.c_uint64), ("edges", C.c_uint64), ("simple", C.c_uint64), ("once", C.c_uint64),
+                ("many", C.c_uint64), ("network_nodes", C.c_uint64), ("network_arcs", C.c_uint64), ("t_to_s_flow", C.c_uint64), ("flow_different", C.c_uint64),
+                ("solution_lines", C.c_uint64), ("lines_applied", C.c_uint64), ("prepare_ms", C.c_double), ("rounds_ms", C.c_double), ("order_ms", C.c_double),
+                ("classes_ms", C.c_double), ("arcs_ms", C.c_double), ("apply_ms", C.c_double)]
+
+
 class OverlapStats(C.Structure):
     _fields_ = [("verified_overlaps", C.c_uint64), ("contained_extension", C.c_uint64), ("contained_size", C.c_uint64),
                 ("left_to_explore", C.c_uint64), ("edges_inserted", C.c_uint64), ("transitive_removed", C.c_uint64),
@@ -208,6 +226,17 @@ def insert_estimate(d, average_read_length) -> Insert:
     rc = lib().sage2ov_insert_estimate(C.c_void_p(d.ctypes.data), C.c_uint64(len(d)), C.c_uint64(average_read_length), C.byref(out))
     if rc:
         raise Sage2ovError(rc, "insert_estimate")
+    return out
+
+
+def genome_size_rounds(length, k, reads) -> GenomeEstimate:
+    """the rounds of CopyCountEstimator::genomeSizeEstimation over lengthOfEdge and k of the non-loop pairs, on the host: no context, no GPU"""
+    length = np.ascontiguousarray(length, dtype=np.uint32)
+    k = np.ascontiguousarray(k, dtype=np.uint64)
+    out = GenomeEstimate()
+    rc = lib().sage2ov_genome_size_rounds(C.c_void_p(length.ctypes.data), C.c_void_p(k.ctypes.data), C.c_uint64(len(length)), C.c_uint64(reads), C.byref(out))
+    if rc:
+        raise Sage2ovError(rc, "genome_size_rounds")
     return out
 
 
@@ -404,6 +433,44 @@ class Context:
     def graph_set_flows(self, flows):
         flows = np.ascontiguousarray(flows, dtype=np.float32)
         self._chk(lib().sage2ov_graph_flow_import(self._h, C.c_void_p(flows.ctypes.data), C.c_uint64(len(flows))))
+
+    # ---- step 5 around its solver (CopyCountEstimator: genome size, flow network, a solver's flows, P.graph5)
+    def genome_size(self) -> int:
+        n = C.c_uint64(0)
+        self._chk(lib().sage2ov_genome_size_estimate(self._h, C.byref(n)))
+        return int(n.value)
+
+    def flow_network_build(self):
+        self._chk(lib().sage2ov_flow_network_build(self._h))
+
+    def flow_network(self) -> np.ndarray:
+        """the arcs of the flow network (FLOW_ARC_DTYPE) in input.cs2's order, the 2 -> 1 arc first"""
+        nodes, arcs = C.c_uint64(0), C.c_uint64(0)
+        self._chk(lib().sage2ov_flow_network_count(self._h, C.byref(nodes), C.byref(arcs)))
+        out = np.zeros(arcs.value, dtype=FLOW_ARC_DTYPE)
+        self._chk(lib().sage2ov_flow_network_export(self._h, C.c_void_p(out.ctypes.data), C.c_uint64(arcs.value)))
+        return out
+
+    def flow_network_save(self, path):
+        self._chk(lib().sage2ov_flow_network_save(self._h, os.fsencode(path)))
+
+    def flow_apply(self, from_, to, flow):
+        """the lines (from, to, flow) of a solver's output, in any order, onto the flows of the resident graph"""
+        a = np.ascontiguousarray(from_, dtype=np.uint64); b = np.ascontiguousarray(to, dtype=np.uint64); f = np.ascontiguousarray(flow, dtype=np.uint64)
+        if not (len(a) == len(b) == len(f)):
+            raise ValueError("from, to and flow have one value per line")
+        self._chk(lib().sage2ov_flow_solution_apply(self._h, C.c_void_p(a.ctypes.data), C.c_void_p(b.ctypes.data), C.c_void_p(f.ctypes.data), C.c_uint64(len(a))))
+
+    def flow_load(self, path):
+        self._chk(lib().sage2ov_flow_solution_load(self._h, os.fsencode(path)))
+
+    def graph5_save(self, path):
+        self._chk(lib().sage2ov_graph5_save(self._h, os.fsencode(path)))
+
+    def copycount_stats(self) -> CopyCountStats:
+        s = CopyCountStats()
+        self._chk(lib().sage2ov_copycount_stats_get(self._h, C.byref(s)))
+        return s
 
     def mates_supports(self, min_support=2) -> np.ndarray:
         """the candidates with support >= min_support (SUPPORT_DTYPE) in ascending (node, pair_in, pair_out); 2 gives findMatepairSupports' list"""

@@ -1,6 +1,8 @@
 // sage2_amd/csrc/sage2ov_cli.cpp -- `sage2ov`: drop-in producer of <outdir>/<prefix>.reads and <prefix>.graph3.
 // Mimics the SAGE2 command line for steps 1-3 (main.cpp:384-521): -f | -l, -k, -o, -p, -i, -m, -M, -s, -d, -h.
 // Continue with the unchanged reference:  SAGE2 -f reads.fa -k K -o out -p P -i P -m 4      (main.cpp:141-148)
+// --flowNetwork writes <outdir>/input.cs2 (step 5's flow network, with the genome-size estimate) and --flowSolution FILE applies a solver's output.cs2 and writes
+// <prefix>.graph5: after step 4, or with -m 5 from <inputPrefix>.reads and <inputPrefix>.graph4.  No solver is started here.
 // --contigs [--genomeSize G] also writes <prefix>_contig.fasta, printGraph's file (main.cpp:246), for the graph after step 4 or a P.graph4 / 5 / 6 (-m 5 | 6 | 7).
 #include <getopt.h>
 #include <sys/stat.h>
@@ -31,14 +33,16 @@ static void printListOfArgs() {
             "\t-G|--gpus <int>\tsteps 2-3 on this many GPUs of the node (devices gpu .. gpu+G-1): reads and index replicated, probe pass\n"
             "\t\t\trange-partitioned, records / flags / edge and survivor buckets exchanged with RCCL over xGMI [1]\n"
             "\t--contigs\t\talso write <prefix>_contig.fasta (printGraph): after step 4, or with -m 5|6|7 from <inputPrefix>.reads and <inputPrefix>.graph4|5|6\n"
-            "\t--genomeSize <int>\tgenome size for the N50 / N90 of --contigs [0]\n\t-h|--help\n\n";
+            "\t--genomeSize <int>\tgenome size for the N50 / N90 of --contigs [0; with --flowNetwork or --flowSolution: the estimate]\n"
+            "\t--flowNetwork\t\tstep 5 up to its solver: estimate the genome size and write <outputDir>input.cs2 (after step 4, or with -m 5 from <inputPrefix>.graph4)\n"
+            "\t--flowSolution <string>\tstep 5 after its solver: apply this output.cs2 to the flows and write <prefix>.graph5\n\t-h|--help\n\n";
 }
 static string trimBack(string s, const string& pat) { size_t e = s.find_last_not_of(pat); return e == string::npos ? "" : s.substr(0, e + 1); }
 static double now() { return chrono::duration<double>(chrono::steady_clock::now().time_since_epoch()).count(); }
 
 int main(int argc, char* argv[]) {
     const double tMain = now(); const bool timing = getenv("SAGE2OV_TIMING") != nullptr;
-    int minStep = 1, maxStep = 3, gpu = 0, gpus = 1, failRank = -1; bool shareGpu = false, forceMulti = false; unsigned minOverlap = 0; bool contigs = false; unsigned long long genomeSize = 0; bool saveAll = false, debugging = false, fFlag = false, lFlag = false;
+    int minStep = 1, maxStep = 3, gpu = 0, gpus = 1, failRank = -1; bool shareGpu = false, forceMulti = false; unsigned minOverlap = 0; bool contigs = false, flowNetwork = false, genomeSizeGiven = false, maxGiven = false; string flowSolution; unsigned long long genomeSize = 0; bool saveAll = false, debugging = false, fFlag = false, lFlag = false;
     string fileInput, listInput, outputDir, prefixName = "untitled", inputPrefix;
     static struct option opts[] = {{"help", no_argument, 0, 'h'}, {"fileInput", required_argument, 0, 'f'}, {"minOverlap", required_argument, 0, 'k'},
         {"listInput", required_argument, 0, 'l'}, {"outputDir", required_argument, 0, 'o'}, {"prefix", required_argument, 0, 'p'},
@@ -46,7 +50,7 @@ int main(int argc, char* argv[]) {
         {"saveAll", no_argument, 0, 's'}, {"debug", no_argument, 0, 'd'}, {"gpu", required_argument, 0, 'g'}, {"gpus", required_argument, 0, 'G'},
         {"share-gpu", no_argument, 0, 1001},      // rehearsal: all ranks on device `gpu`, exchanges by device copies instead of RCCL (a box with fewer GPUs than ranks)
         {"fail-rank", required_argument, 0, 1003},  // tests: this rank of a multi-GPU run fails before its first step (the run must end non-zero, not hang)
-        {"contigs", no_argument, 0, 1004}, {"genomeSize", required_argument, 0, 1005},
+        {"contigs", no_argument, 0, 1004}, {"genomeSize", required_argument, 0, 1005}, {"flowNetwork", no_argument, 0, 1006}, {"flowSolution", required_argument, 0, 1007},
         {"force-multi", no_argument, 0, 1002},    // the multi-GPU code path (RCCL communicator, the four exchanges) even with one GPU
         {0, 0, 0, 0}};
     int c, oi = 0;
@@ -60,7 +64,7 @@ int main(int argc, char* argv[]) {
             case 'p': prefixName = optarg; break;
             case 'i': inputPrefix = optarg; break;
             case 'm': minStep = atoi(optarg); if (minStep < 1) minStep = 1; break;
-            case 'M': maxStep = atoi(optarg); if (maxStep > 7) maxStep = 7; break;
+            case 'M': maxStep = atoi(optarg); if (maxStep > 7) maxStep = 7; maxGiven = true; break;
             case 's': saveAll = true; break;
             case 'd': debugging = true; break;
             case 'g': gpu = atoi(optarg); break;
@@ -69,19 +73,25 @@ int main(int argc, char* argv[]) {
             case 1002: forceMulti = true; break;
             case 1003: failRank = atoi(optarg); break;
             case 1004: contigs = true; break;
-            case 1005: genomeSize = strtoull(optarg, nullptr, 10); break;
+            case 1005: genomeSize = strtoull(optarg, nullptr, 10); genomeSizeGiven = true; break;
+            case 1006: flowNetwork = true; break;
+            case 1007: flowSolution = optarg; break;
             case '?': cout << "\n"; exit(0);
             default: cout << "[ERROR] Wrong command line arguments!\n\n"; exit(0);
         }
     }
     if (fFlag && lFlag) { cout << "[ERROR] Options -f|--fileInput and -l|--listInput are mutually exclusive!\n\n"; exit(0); }
+    const bool step5 = flowNetwork || flowSolution != "";
+    if (step5 && !maxGiven && maxStep < minStep) maxStep = minStep;                          // (`-m 5 --flowSolution FILE` needs no -M)
     bool allSet = true;                                                                     // main.cpp:498-521
     if (fileInput == "" && listInput == "" && minStep <= 1) { cout << "[ERROR] One of the options -f|--fileInput or -l|--listInput is required.\n"; allSet = false; }
     if (minOverlap == 0) { cout << "[ERROR] Option -k|--minOverlap is required.\n"; allSet = false; }
     if (maxStep < minStep) { cout << "[ERROR] maxStep should not be smaller than minStep!\n\n"; allSet = false; }
     if (inputPrefix == "") inputPrefix = prefixName;
     if (!allSet) { cout << "\n"; printUsage(); cout << "(For more information run sage2ov -h)\n\n"; exit(0); }
-    if (minStep > 4 && !contigs) { cout << "[ERROR] sage2ov implements steps 1-4; continue with: SAGE2 -m " << minStep << " -i " << inputPrefix << " ...\n"; exit(0); }
+    if (step5 && maxStep < 4) { cout << "[ERROR] --flowNetwork and --flowSolution need the graph after step 4: run with -M 4 (or -m 5 on the files of such a run).\n"; exit(0); }
+    if (minStep > 5 && step5) { cout << "[ERROR] --flowNetwork and --flowSolution work on the graph after step 4 (-m 5 at the most).\n"; exit(0); }
+    if (minStep > 4 && !contigs && !step5) { cout << "[ERROR] sage2ov implements steps 1-4; continue with: SAGE2 -m " << minStep << " -i " << inputPrefix << " ...\n"; exit(0); }
     (void)debugging;
     if (outputDir != "") { string cmd = "mkdir -p " + outputDir; if (system(cmd.c_str())) {} }     // utils.cpp:45
     ofstream logStream((outputDir + prefixName + ".log").c_str());
@@ -117,6 +127,34 @@ int main(int argc, char* argv[]) {
             logStream << "\t" << prefixName << "_contig.fasta written in " << now() - tw << " sec.\n\t  Number of Contigs: " << cs.contigs << " (" << cs.written << " in the file)\n\t     Longest Contig: " << cs.longest
                       << "\n\t     Genome Covered: " << cs.covered << " BP\n\t                N50: " << cs.n50 << " BP (" << cs.n50_ordinal << ")\n\t                N90: " << cs.n90 << " BP (" << cs.n90_ordinal << ")\n";
         };
+        auto copyCounts = [&]() {                                                             // main.cpp:199-203, without the solver
+            if (!step5) return;
+            double t5 = now();
+            uint64_t est = 0; ctx.check(sage2ov_genome_size_estimate(ctx.get(), &est));
+            sage2ov_copycount_stats cs{}; ctx.check(sage2ov_copycount_stats_get(ctx.get(), &cs));
+            logStream << "STEP 5: copy counts\n";
+            for (uint32_t i = 0; i < cs.rounds; i++) {                                        // copycountEstimator.cpp:41, :47
+                const bool fin = cs.agreed && i + 1 == cs.rounds;
+                string line = "\tGenome Size: " + to_string(cs.estimate[i]) + (fin ? " (Final estimation)" : " (Estimation " + to_string(i + 1) + ")") + "\n";
+                logStream << line; if (flowNetwork) cout << line;
+            }
+            if (flowNetwork) {
+                ctx.check(sage2ov_flow_network_save(ctx.get(), (outputDir + "input.cs2").c_str()));
+                ctx.check(sage2ov_copycount_stats_get(ctx.get(), &cs));
+                logStream << "\t          Number of nodes: " << cs.nodes << "\n\t          Number of edges: " << cs.edges << "\n\t             Simple edges: " << cs.simple
+                          << "\n\t  Edges used exactly once: " << cs.once << "\n\tEdges used more than once: " << cs.many << "\n\tinput.cs2 written: " << cs.network_nodes << " nodes, "
+                          << cs.network_arcs << " arcs\n";
+            }
+            if (flowSolution != "") {
+                ctx.check(sage2ov_flow_solution_load(ctx.get(), flowSolution.c_str()));
+                ctx.check(sage2ov_copycount_stats_get(ctx.get(), &cs));
+                logStream << "\t         Flow from T to S: " << cs.t_to_s_flow << "\n\t  Flow different in edges: " << cs.flow_different << "\n";
+                ctx.check(sage2ov_graph5_save(ctx.get(), (outputDir + prefixName + ".graph5").c_str()));
+                logStream << "\t" << prefixName << ".graph5 written\n";
+            }
+            if (!genomeSizeGiven) genomeSize = est;
+            logStream << "\tStep 5 (without its solver) in " << now() - t5 << " sec.\n";
+        };
         auto step4 = [&](OverlapGraph& graphObj) {                                            // main.cpp:134-181
             double t4 = now();
             auto ss = graphObj.simplify();
@@ -124,12 +162,14 @@ int main(int argc, char* argv[]) {
                       << "\n\tLoop iterations: " << ss.loop_iterations << "\n\tEdges left: " << ss.edges << " carrying " << ss.reads_on_edges << " reads\n\tStep 4 in " << now() - t4
                       << " sec (device " << ss.device_ms / 1000.0 << ").\n";
             { double tw = now(); graphObj.saveSimplifiedGraphInFile(outputDir + prefixName + ".graph4"); logStream << "\t" << prefixName << ".graph4 written in " << now() - tw << " sec.\n"; }   // the file step 5 loads (main.cpp:196)
+            copyCounts();
             if (contigs) writeContigs(graphObj);
         };
         if (minStep > 4) {                                                                    // --contigs on the graph an earlier run or the reference left: P.graph4 / 5 / 6
             OverlapGraph graphObj(&loaderObj);
             graphObj.loadCompositeGraphFromFile(outputDir + inputPrefix + ".graph" + to_string(minStep - 1));
-            writeContigs(graphObj);
+            copyCounts();
+            if (contigs) writeContigs(graphObj);
         } else if (minStep == 4) {                                                            // main.cpp:141-148
             OverlapGraph graphObj(&loaderObj);
             graphObj.loadOverlapGraphFromFile(outputDir + inputPrefix + ".graph3");

@@ -114,6 +114,7 @@ struct Device {
     void* support = nullptr;     // the mate-pair supports of edge pairs (dev_support_build; Support): allocations of its own, dropped with the read-to-edge table and the mate flags
     void* contigs = nullptr;     // the contig table and the spelling buffers (dev_contigs_build; Contigs): allocations of its own, dropped with the graph and the read set
     void* links = nullptr;       // the scaffold links of half-edge pairs (dev_links_build; Links): allocations of its own, dropped with the read-to-edge table and the mate flags
+    void* copycount = nullptr;   // step 5 around its solver (dev_copycount_prepare, dev_flownet_build; CopyCount): allocations of its own, dropped with the graph and the read set
     void* s4keep = nullptr;      // step 4: the simplified graph stays in HBM until the next call (S4Keep)
     // step 4: blocks a call released, kept for the next call (it asks for the same ~50 sizes; fresh HBM costs ~50 ms per GB to map, 0.7 s per call at BASELINE
     // configs[2]).  Emptied when the read set changes, when the workspace arena runs out of memory, and never filled in memory-diet mode.
@@ -236,6 +237,7 @@ static void mem_sample(Device* d) { size_t fr = 0, to = 0; if (hipMemGetInfo(&fr
 #include "kernels_support.inc"
 #include "kernels_links.inc"
 #include "kernels_contig.inc"
+#include "kernels_copycount.inc"
 
 // =============================================================================================
 // host primitives: what the launchers below share (grids, counters, transient buffers, a stream timer, scan, radix sort, heads)
@@ -390,6 +392,7 @@ static void mates_release(Device* d);
 static void free_reads(Device* d) {
     dev_readmap_release(d);                                             // (read ids again)
     dev_contigs_release(d);                                             // (and the reads the strings are spelled from)
+    dev_copycount_release(d);                                           // (the frequencies and the present reads are of this read set)
     rr_staging_release(d);                     // (pinned host buffers sized by the previous read set)
     hipFree(d->reads);
     hipFree(d->findDir); d->findDir = nullptr; d->findDirBits = 0;      // (the lookup directory describes the read set that goes)
@@ -2133,7 +2136,7 @@ struct S4Mem {                                   // released on every exit path 
 }
 #define S4GET(var, type, n) type* var = mem.get<type>((n), err); if (!var) return SAGE2OV_ERR_NOMEM;
 struct S4Keep { S4Mem mem; S4Graph g; u32 nh = 0; u64 listUsed = 0; float* flow = nullptr; };      // flow: one float per half-edge (null: every flow is 0, the state after step 4)
-void dev_simplify_release(Device* d) { dev_readmap_release(d); dev_contigs_release(d); if (d->s4keep) { hipSetDevice(d->ordinal); delete (S4Keep*)d->s4keep; d->s4keep = nullptr; } }
+void dev_simplify_release(Device* d) { dev_readmap_release(d); dev_contigs_release(d); dev_copycount_release(d); if (d->s4keep) { hipSetDevice(d->ordinal); delete (S4Keep*)d->s4keep; d->s4keep = nullptr; } }
 
 int dev_simplify(Device* d, SimplifiedGraph& out, std::string& err) {
     HIPCHK(hipSetDevice(d->ordinal));
@@ -2869,6 +2872,196 @@ int dev_contigs_spell_wait(Device* d, int which, const char** image, double* ms,
     HIPCHK(hipEventSynchronize(B.done));
     float t = 0; if (hipEventElapsedTime(&t, B.a, B.b) == hipSuccess) *ms += t; else (void)hipGetLastError();
     *image = B.host;
+    return 0;
+}
+
+// =============================================================================================
+// step 5 around its solver (kernels_copycount.inc; CopyCountEstimator, copycountEstimator.cpp:29-417)
+// =============================================================================================
+struct CopyCount {
+    unsigned short* freq = nullptr; unsigned long long* kPair = nullptr; u64 present = 0;      // of dev_copycount_prepare
+    u32 *adj = nullptr, *hp = nullptr, *nodeOf = nullptr; CcArc* arcs = nullptr; u64 F = 0, E = 0, nArcs = 0; bool net = false;      // of dev_flownet_build
+    void drop_net() { hipFree(adj); hipFree(hp); hipFree(nodeOf); hipFree(arcs); adj = hp = nodeOf = nullptr; arcs = nullptr; F = E = nArcs = 0; net = false; }
+    ~CopyCount() { drop_net(); hipFree(freq); hipFree(kPair); }
+};
+static_assert(sizeof(CcArc) == sizeof(FlowArc) && sizeof(CcArc) == 20, "an arc record is five 32-bit words");
+void dev_copycount_release(Device* d) { if (d->copycount) { hipSetDevice(d->ordinal); delete (CopyCount*)d->copycount; d->copycount = nullptr; } }
+static int copycount_nomem(std::string& err) { err = "copy counts: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+// the 8-bit digits of a node id that can be non-zero
+static int copycount_passes(u64 N, int* shifts) { int b = 0; while ((N >> b) != 0) b++; int np = 0; for (int p = 0; p < 4; p++) if (8 * p < b) shifts[np++] = 8 * p; return np; }
+
+int dev_copycount_prepare(Device* d, const uint16_t* freq, CopyCountStats* st, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    if (!d->s4keep) { err = "copy counts: no step-4 graph on the device"; return SAGE2OV_ERR_ARG; }
+    if (d->N >= (1ull << 32) - 2) { err = "copy counts: read ids beyond 2^32 - 3"; return SAGE2OV_ERR_LIMIT; }
+    dev_copycount_release(d);
+    const S4Keep& K = *(S4Keep*)d->s4keep; const S4Graph& g = K.g; const u32 nh = K.nh; const u64 nl = K.listUsed; const u32 N = (u32)d->N; hipStream_t sm = d->stream;
+    std::unique_ptr<CopyCount> S(new CopyCount());
+    DevTmp B; StreamLap lap(sm); HIPCHK(lap.create());
+    HIPCHK(lap.start());
+    const u64 np = (u64)nh / 2 + 1;
+    S->freq = (unsigned short*)DevTmp::alloc(((u64)N + 2) * sizeof(unsigned short)); S->kPair = (unsigned long long*)DevTmp::alloc(np * sizeof(unsigned long long));
+    uint8_t* present = B.get<uint8_t>((u64)N + 2); u32* hCnt = B.get<u32>(nh); u32* hOff = B.get<u32>(nh); unsigned long long* ctr = B.get<unsigned long long>(2);
+    u64* partial = B.get<u64>(scan_partial_words((u64)nh + 1));
+    if (!S->freq || !S->kPair || !present || !hCnt || !hOff || !ctr || !partial) return copycount_nomem(err);
+    HIPCHK(hipMemcpyAsync(S->freq, freq, ((u64)N + 1) * sizeof(unsigned short), hipMemcpyHostToDevice, sm));
+    HIPCHK(hipMemsetAsync(S->kPair, 0, np * sizeof(unsigned long long), sm)); HIPCHK(hipMemsetAsync(present, 0, (u64)N + 2, sm)); HIPCHK(hipMemsetAsync(ctr, 0, 2 * sizeof(unsigned long long), sm));
+    const dim3 b256(256);
+    u64 W = 0;
+    if (nh) {
+        hipLaunchKernelGGL(k_cc_nodes, dim3(grid_for(nh, 256)), b256, 0, sm, g, nh, present, N);
+        hipLaunchKernelGGL(k_sl_halves, dim3(grid_for(nh, 256)), b256, 0, sm, g, nh, hCnt, ctr + 1);
+        { const int rc = scan_u32(d, hCnt, nh, hOff, partial, &W, err); if (rc) return rc; }
+        if (W >= (1ull << 32) - RS_TILE) { err = "copy counts: more than 2^32 list entries"; return SAGE2OV_ERR_LIMIT; }
+        if (W) hipLaunchKernelGGL(k_cc_entries, dim3(grid_for(W, 256)), b256, 0, sm, g, nh, hOff, (u32)W, nl, S->freq, N, present, S->kPair);
+    }
+    hipLaunchKernelGGL(k_cc_present, dim3((unsigned)std::min<u64>(grid_for((u64)N + 1, 256), 4096)), b256, 0, sm, present, S->freq, N, ctr);
+    HIPCHK(hipGetLastError());
+    unsigned long long hc[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(hc, ctr, sizeof hc, hipMemcpyDeviceToHost, sm));
+    HIPCHK(lap.stop(st->k_ms));
+    S->present = hc[0]; st->present = hc[0];
+    d->copycount = S.release();
+    return 0;
+}
+int dev_copycount_round(Device* d, int first, float ratio, float l2, uint64_t out[2], CopyCountStats* st, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    CopyCount* S = (CopyCount*)d->copycount;
+    if (!d->s4keep || !S) { err = "copy counts: not prepared"; return SAGE2OV_ERR_INTERNAL; }
+    const S4Keep& K = *(S4Keep*)d->s4keep; const u32 nh = K.nh; hipStream_t sm = d->stream;
+    DevTmp B; StreamLap lap(sm); HIPCHK(lap.create());
+    unsigned long long* ctr = B.get<unsigned long long>(2); if (!ctr) return copycount_nomem(err);
+    HIPCHK(lap.start());
+    HIPCHK(hipMemsetAsync(ctr, 0, 2 * sizeof(unsigned long long), sm));
+    if (nh) hipLaunchKernelGGL(k_cc_round, dim3(grid_for(nh, 256)), dim3(256), 0, sm, K.g, nh, S->kPair, first, ratio, l2, ctr);
+    HIPCHK(hipGetLastError());
+    unsigned long long hc[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(hc, ctr, sizeof hc, hipMemcpyDeviceToHost, sm));
+    HIPCHK(lap.stop(st->round_ms));
+    out[0] = hc[0]; out[1] = hc[1];
+    return 0;
+}
+int dev_flownet_build(Device* d, const CopyCountConst& P, CopyCountStats* st, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    CopyCount* S = (CopyCount*)d->copycount;
+    if (!d->s4keep || !S) { err = "flow network: the copy counts are not prepared"; return SAGE2OV_ERR_INTERNAL; }
+    S->drop_net();
+    const S4Keep& K = *(S4Keep*)d->s4keep; const S4Graph& g = K.g; const u32 nh = K.nh; const u64 nl = K.listUsed; const u32 N = (u32)d->N; hipStream_t sm = d->stream;
+    CcConst C; C.ratio = P.ratio; for (int j = 0; j < 21; j++) C.lj[j] = P.lj[j];
+    C.l1 = P.l1; C.l3 = P.l3; C.l5 = P.l5; C.l1000 = P.l1000; C.fN1 = P.fN1; C.fN3 = P.fN3; C.fN5 = P.fN5; C.dN3 = P.dN3; C.dN1000 = P.dN1000; C.n = P.n;
+    DevTmp B; StreamLap lap(sm); HIPCHK(lap.create());
+    const dim3 b256(256);
+    // ---- the save order: the halves the writer visits, per node by ascending index
+    HIPCHK(lap.start());
+    u64 nOrd = 0;
+    u32* sel = B.get<u32>(nh); u32* pos = B.get<u32>(nh); u64* partial = B.get<u64>(scan_partial_words((u64)nh + 1));
+    if (!sel || !pos || !partial) return copycount_nomem(err);
+    if (nh) {
+        hipLaunchKernelGGL(k_cc_select, dim3(grid_for(nh, 256)), b256, 0, sm, g, nh, sel);
+        const int rc = scan_u32(d, sel, nh, pos, partial, &nOrd, err); if (rc) return rc;
+    }
+    const u64 F = 2 * nOrd;
+    if (F >= (1ull << 32) - RS_TILE) { err = "flow network: more than 2^32 records"; return SAGE2OV_ERR_LIMIT; }
+    S->arcs = nullptr;
+    if (!F) {                                                                          // no edge: the header arc alone
+        S->arcs = (CcArc*)DevTmp::alloc(sizeof(CcArc)); if (!S->arcs) return copycount_nomem(err);
+        hipLaunchKernelGGL(k_cc_node_arcs, dim3(1), b256, 0, sm, 0u, S->arcs);
+        HIPCHK(hipGetLastError()); HIPCHK(lap.stop(st->order_ms));
+        S->nArcs = 1; S->net = true; st->nodes = st->edges = st->simple = st->once = st->many = 0; st->arcs = 1;
+        return 0;
+    }
+    int shifts[4]; const int np = copycount_passes(N, shifts);
+    u64* key1 = B.get<u64>(nOrd); u32* half = B.get<u32>(nOrd); if (!key1 || !half) return copycount_nomem(err);
+    hipLaunchKernelGGL(k_cc_compact, dim3(grid_for(nh, 256)), b256, 0, sm, g, nh, sel, pos, key1, half);
+    u64* ks1 = nullptr; u32* idx1 = nullptr; MateStats ms;
+    { const int rc = mate_sort(d, B, key1, (u32)nOrd, shifts, np, &ks1, &idx1, &ms, err); if (rc) return rc; }
+    // ---- the records in descending file position, sorted by their start node: the loaded lists
+    u64* key2 = B.get<u64>(F); u32* rec = B.get<u32>(F); if (!key2 || !rec) return copycount_nomem(err);
+    hipLaunchKernelGGL(k_cc_filekeys, dim3(grid_for(F, 256)), b256, 0, sm, g, half, idx1, (u32)F, key2, rec);
+    u64* ks2 = nullptr; u32* idx2 = nullptr;
+    { const int rc = mate_sort(d, B, key2, (u32)F, shifts, np, &ks2, &idx2, &ms, err); if (rc) return rc; }
+    st->passes = ms.passes;
+    S->adj = (u32*)DevTmp::alloc(F * sizeof(u32)); if (!S->adj) return copycount_nomem(err);
+    hipLaunchKernelGGL(k_cc_gather, dim3(grid_for(F, 256)), b256, 0, sm, idx2, rec, (u32)F, S->adj);
+    u32* hp = nullptr; u32 E = 0;
+    { const int rc = mate_heads(d, B, ks2, (u32)F, &hp, &E, err); if (rc) return rc; }
+    S->hp = (u32*)DevTmp::alloc(((u64)E + 1) * sizeof(u32)); S->nodeOf = (u32*)DevTmp::alloc(std::max<u64>(E, 1) * sizeof(u32));
+    u32* rankOf = B.get<u32>((u64)N + 2);
+    if (!S->hp || !S->nodeOf || !rankOf) return copycount_nomem(err);
+    HIPCHK(hipMemcpyAsync(S->hp, hp, ((u64)E + 1) * sizeof(u32), hipMemcpyDeviceToDevice, sm));
+    hipLaunchKernelGGL(k_cc_ranks, dim3(grid_for(E, 256)), b256, 0, sm, ks2, hp, E, S->nodeOf);
+    HIPCHK(hipMemsetAsync(rankOf, 0, ((u64)N + 2) * sizeof(u32), sm));
+    hipLaunchKernelGGL(k_cc_rank_of, dim3(grid_for(E, 256)), b256, 0, sm, S->nodeOf, E, rankOf, N);
+    HIPCHK(hipGetLastError());
+    HIPCHK(lap.stop(st->order_ms));
+    S->F = F; S->E = E;
+    // ---- classes, arc counts, positions
+    HIPCHK(lap.start());
+    uint8_t* cls = B.get<uint8_t>(F); uint8_t* lb = B.get<uint8_t>(F); u32* arcs = B.get<u32>(F); u32* apos = B.get<u32>(F); unsigned long long* ctr = B.get<unsigned long long>(4);
+    u64* partialF = B.get<u64>(scan_partial_words(F + 1));
+    if (!cls || !lb || !arcs || !apos || !ctr || !partialF) return copycount_nomem(err);
+    HIPCHK(hipMemsetAsync(ctr, 0, 4 * sizeof(unsigned long long), sm));
+    hipLaunchKernelGGL(k_cc_classes, dim3(grid_for(F, 256)), b256, 0, sm, g, S->adj, (u32)F, S->kPair, C, cls, lb, arcs, ctr);
+    u64 A = 0; { const int rc = scan_u32(d, arcs, F, apos, partialF, &A, err); if (rc) return rc; }
+    unsigned long long hc[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpy(hc, ctr, sizeof hc, hipMemcpyDeviceToHost));
+    HIPCHK(lap.stop(st->classes_ms));
+    st->nodes = E; st->edges = hc[0]; st->simple = hc[1]; st->once = hc[2]; st->many = hc[3];
+    const u64 base = 1 + 6ull * E, total = base + A;
+    if (total >= (1ull << 32) - RS_TILE) { err = "flow network: 2^32 - 2048 arcs or more"; S->drop_net(); return SAGE2OV_ERR_LIMIT; }
+    // ---- the arc records
+    HIPCHK(lap.start());
+    S->arcs = (CcArc*)DevTmp::alloc(total * sizeof(CcArc)); if (!S->arcs) { S->drop_net(); return copycount_nomem(err); }
+    hipLaunchKernelGGL(k_cc_node_arcs, dim3(grid_for(std::max<u64>(E, 1), 256)), b256, 0, sm, E, S->arcs);
+    hipLaunchKernelGGL(k_cc_edge_arcs, dim3((unsigned)std::min<u64>(grid_for(F, 4), CC_ARC_BLOCKS)), b256, 0, sm, g, S->adj, (u32)F, cls, lb, apos, base, rankOf, S->freq, N, nl, C, S->arcs);
+    HIPCHK(hipGetLastError());
+    HIPCHK(lap.stop(st->arcs_ms));
+    S->nArcs = total; S->net = true; st->arcs = total;
+    return 0;
+}
+uint64_t dev_flownet_arcs(Device* d) { const CopyCount* S = (const CopyCount*)d->copycount; return S && S->net ? S->nArcs : 0; }
+int dev_flownet_export(Device* d, FlowArc* out, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    const CopyCount* S = (const CopyCount*)d->copycount; if (!S || !S->net) { err = "flow network: not built"; return SAGE2OV_ERR_INTERNAL; }
+    HIPCHK(hipMemcpy(out, S->arcs, S->nArcs * sizeof(CcArc), hipMemcpyDeviceToHost));
+    return 0;
+}
+// the lines of a solution onto the flows of the resident graph (the caller has checked every node number against the network); the supports go, as in dev_flow_set
+int dev_flow_apply(Device* d, const uint64_t* from, const uint64_t* to, const uint64_t* flow, uint64_t n, CopyCountStats* st, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    const CopyCount* S = (const CopyCount*)d->copycount;
+    if (!d->s4keep || !S || !S->net) { err = "flow solution: no flow network"; return SAGE2OV_ERR_INTERNAL; }
+    S4Keep& K = *(S4Keep*)d->s4keep; S4Mem& mem = K.mem; const u32 nh = K.nh; hipStream_t sm = d->stream;
+    DevTmp B; StreamLap lap(sm); HIPCHK(lap.create());
+    u64* dfr = B.get<u64>(n); u64* dto = B.get<u64>(n); u64* dfl = B.get<u64>(n); unsigned long long* acc = B.get<unsigned long long>(nh); unsigned long long* ctr = B.get<unsigned long long>(2);
+    if (!dfr || !dto || !dfl || !acc || !ctr) return copycount_nomem(err);
+    const bool fresh = !K.flow;
+    if (fresh) { S4GET(a, float, nh) K.flow = a; }
+    dev_support_release(d);
+    HIPCHK(lap.start());
+    if (fresh && nh) HIPCHK(hipMemsetAsync(K.flow, 0, (u64)nh * sizeof(float), sm));
+    if (nh) HIPCHK(hipMemsetAsync(acc, 0, (u64)nh * sizeof(unsigned long long), sm));
+    HIPCHK(hipMemsetAsync(ctr, 0, 2 * sizeof(unsigned long long), sm));
+    if (n) {
+        HIPCHK(hipMemcpyAsync(dfr, from, n * sizeof(u64), hipMemcpyHostToDevice, sm)); HIPCHK(hipMemcpyAsync(dto, to, n * sizeof(u64), hipMemcpyHostToDevice, sm));
+        HIPCHK(hipMemcpyAsync(dfl, flow, n * sizeof(u64), hipMemcpyHostToDevice, sm));
+        if (S->F) hipLaunchKernelGGL(k_cc_apply, dim3(grid_for(n, 256)), dim3(256), 0, sm, K.g, S->adj, S->hp, S->nodeOf, (u32)S->E, dfr, dto, dfl, (u64)n, acc, ctr);
+    }
+    if (nh) hipLaunchKernelGGL(k_cc_average, dim3(grid_for((u64)nh / 2 + 1, 256)), dim3(256), 0, sm, K.g, nh, acc, K.flow, ctr);
+    HIPCHK(hipGetLastError());
+    unsigned long long hc[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(hc, ctr, sizeof hc, hipMemcpyDeviceToHost, sm));
+    HIPCHK(lap.stop(st->apply_ms));
+    st->applied = hc[0]; st->different = hc[1];
+    return 0;
+}
+int dev_flow_get(Device* d, float* flow, uint64_t n, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    if (!d->s4keep) { err = "flows: no step-4 graph on the device"; return SAGE2OV_ERR_ARG; }
+    const S4Keep& K = *(S4Keep*)d->s4keep;
+    if (n != K.nh) { err = "flows: one value per half-edge"; return SAGE2OV_ERR_INTERNAL; }
+    if (!K.flow) { std::fill(flow, flow + n, 0.f); return 0; }
+    if (n) HIPCHK(hipMemcpy(flow, K.flow, n * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -131,7 +131,10 @@ struct sage2ov_ctx {
     bool ctgValid = false; uint32_t ctgThreshold = 0, ctgThresholdUsed = 0; uint64_t ctgGenome = 0; sage2ov_contig_stats cstats{};
     std::vector<ContigRow> ctgRows; std::vector<uint64_t> ctgChunk;      // ctgChunk[r]: 16-byte chunks of the device buffer in front of row r (every row begins at a chunk); R + 1 values
     void contigs_forget() { ctgValid = false; ctgRows.clear(); ctgChunk.clear(); cstats = sage2ov_contig_stats{}; }
-    void readmap_forget() { rmValid = estimated = false; pairOrdinal.clear(); rmstats = sage2ov_readmap_stats{}; supports_forget(); links_forget(); contigs_forget(); }      // the graph or the read set goes
+    // ---- step 5 around its solver (sage2ov_genome_size_estimate, sage2ov_flow_*): the estimate and the network are of the present graph and read set; the data live on the device
+    bool gsValid = false, netValid = false; sage2ov_copycount_stats ccstats{};
+    void copycount_forget() { gsValid = netValid = false; ccstats = sage2ov_copycount_stats{}; }
+    void readmap_forget() { rmValid = estimated = false; pairOrdinal.clear(); rmstats = sage2ov_readmap_stats{}; supports_forget(); links_forget(); contigs_forget(); copycount_forget(); }      // the graph or the read set goes
     void mates_forget(bool readSetGoes = true) {       // the read set goes: its ids mean nothing any more (the device drops its part in free_reads) -- or sage2ov_mates_clear
         if (readSetGoes) { readmap_forget(); readsGen++; } else estimated = false;
         for (auto& L : mates) L = MateLib();
@@ -1658,17 +1661,18 @@ int sage2ov_simplify_stats_get(const sage2ov_ctx* c, sage2ov_simplify_stats* o) 
     o->nodes_contracted = g.contracted; o->removed = g.removed; o->loop_iterations = g.iterations; o->edges = e; o->reads_on_edges = r; o->device_ms = g.device_ms;
     return SAGE2OV_OK;
 }
-int sage2ov_graph4_save(sage2ov_ctx* c, const char* path) {                           // overlapGraph.cpp:338-369, :12-20
-    if (!c || !path) return SAGE2OV_ERR_ARG;
-    if (!c->g4Valid) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph4_save: call sage2ov_graph_simplify first");
-    HostLap lap(c, "graph4");
+// saveOverlapGraphInFile of the resident graph: P.graph4 (line 1 and the flow column 0, line 2 the good reads) or, withFlows, P.graph5 (line 1 the genome size,
+// line 2 `reads`, the flows as `ostream << float` prints them)
+static int save_composite(sage2ov_ctx* c, const char* path, bool withFlows, unsigned long long genomeSize, unsigned long long reads) {
+    HostLap lap(c, withFlows ? "graph5" : "graph4");
     { int rc = dev_simplify_download(c->device(), c->g4, c->err); if (rc) return rc; }
     lap("download of the simplified graph");
     const SimplifiedGraph& g = c->g4;
     std::vector<uint32_t> order; g4_save_order(g, order);
     FILE* f = fopen(path, "w"); if (!f) return c->fail(SAGE2OV_ERR_IO, std::string("cannot open ") + path);
     std::vector<char> io(1 << 22); setvbuf(f, io.data(), _IOFBF, io.size());
-    fprintf(f, "0\n%llu\n%llu\n", (unsigned long long)c->goodReads, (unsigned long long)(c->goodReads ? c->totalBP / c->goodReads : 0));
+    fprintf(f, "%llu\n%llu\n%llu\n", genomeSize, reads, (unsigned long long)(c->goodReads ? c->totalBP / c->goodReads : 0));
+    const float* flows = withFlows && !g.flow.empty() ? g.flow.data() : nullptr;
     // items: a header line, a block of up to 4096 list entries, or the blank line that ends a record -- a contracted chromosome is ONE
     // edge with millions of entries, so the unit of parallel formatting cannot be the edge
     struct Item { uint32_t h, first, count; };                                          // count == 0: header; first == ~0u: blank line
@@ -1685,7 +1689,9 @@ int sage2ov_graph4_save(sage2ov_ctx* c, const char* path) {                     
         if (it.first == ~0u) { o.push_back('\n'); return; }
         if (it.count == 0) {
             p = put_u(buf, g.from[h]); *p++ = '\t'; p = put_u(p, g.to[h]); *p++ = '\t'; p = put_u(p, g.type[h]); memcpy(p, "\t1\t", 3); p += 3;
-            p = put_u(p, g.len[h]); memcpy(p, "\t0\t", 3); p += 3; p = put_u(p, g.cnt[h]); *p++ = '\n'; o.append(buf, (size_t)(p - buf));
+            p = put_u(p, g.len[h]); *p++ = '\t';
+            if (flows) p += snprintf(p, 32, "%g", (double)flows[h]); else *p++ = '0';
+            *p++ = '\t'; p = put_u(p, g.cnt[h]); *p++ = '\n'; o.append(buf, (size_t)(p - buf));
             return;
         }
         for (uint32_t y = it.first; y < it.first + it.count; y++) {
@@ -1695,6 +1701,11 @@ int sage2ov_graph4_save(sage2ov_ctx* c, const char* path) {                     
         }
     });
     fclose(f); return rc;
+}
+int sage2ov_graph4_save(sage2ov_ctx* c, const char* path) {                           // overlapGraph.cpp:338-369, :12-20
+    if (!c || !path) return SAGE2OV_ERR_ARG;
+    if (!c->g4Valid) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph4_save: call sage2ov_graph_simplify first");
+    return save_composite(c, path, false, 0, (unsigned long long)c->goodReads);
 }
 
 // ---- a graph with composite edges from a file (loadOverlapGraphFromFile, overlapGraph.cpp:371-443); the semantics are stated in sage2ov.h
@@ -2007,6 +2018,180 @@ int sage2ov_graph_flow_import(sage2ov_ctx* c, const float* flow, uint64_t n) {
     c->g4.flow = std::move(f);
     return SAGE2OV_OK;
 }
+// ---- step 5 around its solver (copycountEstimator.cpp:29-417); the semantics are stated in sage2ov.h
+namespace {
+static_assert(sizeof(sage2ov_flow_arc) == 20 && sizeof(sage2ov_flow_arc) == sizeof(FlowArc), "sage2ov_flow_arc is five 32-bit words");
+// (uint64_t)x as the reference's build leaves it, with the named rule for a float that does not fit
+inline uint64_t float_to_u64(float x, uint32_t* degenerate) {
+    if (!(x >= 0.0f) || !(x < 18446744073709551616.0f)) { *degenerate = 1; return 1ull << 63; }
+    *degenerate = 0; return (uint64_t)x;
+}
+// :83, :145: every operation in float
+inline float a_statistic(uint64_t delta, uint64_t k, float ratio, float lg) {
+    const float t1 = (float)delta * ratio;
+    const float t2 = (float)k * lg;
+    return t1 - t2;
+}
+// genomeSizeEstimation (:29-54) over sums(first, ratio, l2, out) = findGenomeSize's deltaSum and kSum (:59-97)
+extern "C++" { template <class F>
+int genome_rounds(F&& sums, uint64_t n, sage2ov_genome_estimate* o) {
+    *o = sage2ov_genome_estimate{};
+    const float l2 = std::log((float)2);
+    uint64_t previous = 0, current = 0;
+    for (int i = 0; i < SAGE2OV_GENOME_ROUNDS; i++) {
+        uint64_t ds[2] = {0, 0};
+        const float ratio = previous ? (float)n / (float)previous : 0.0f;
+        { const int rc = sums(previous == 0, ratio, l2, ds); if (rc) return rc; }
+        const float q = (float)n / (float)ds[1];
+        const float x = q * (float)ds[0];                                              // :98
+        current = float_to_u64(x, &o->degenerate);
+        o->estimate[i] = current; o->delta_sum[i] = ds[0]; o->k_sum[i] = ds[1]; o->rounds = (uint32_t)(i + 1);
+        if (current == previous) { o->agreed = 1; break; }
+        previous = current;
+    }
+    o->genome_size = current;
+    return SAGE2OV_OK;
+} }
+int copycount_check(sage2ov_ctx* c, const char* who) { return readmap_check(c, who); }
+void copycount_times(sage2ov_ctx* c, const CopyCountStats& s) {
+    sage2ov_copycount_stats& o = c->ccstats;
+    o.prepare_ms += s.k_ms; o.rounds_ms += s.round_ms; o.order_ms += s.order_ms; o.classes_ms += s.classes_ms; o.arcs_ms += s.arcs_ms; o.apply_ms += s.apply_ms;
+}
+int genome_estimate(sage2ov_ctx* c) {
+    c->copycount_forget();
+    CopyCountStats s;
+    { const int rc = dev_copycount_prepare(c->device(), c->freq.data(), &s, c->err); if (rc) return rc; }
+    sage2ov_genome_estimate e;
+    const int rc = genome_rounds([&](bool first, float ratio, float l2, uint64_t* out) { return dev_copycount_round(c->device(), first ? 1 : 0, ratio, l2, out, &s, c->err); }, s.present, &e);
+    if (rc) return rc;
+    sage2ov_copycount_stats& o = c->ccstats;
+    o.genome_size = e.genome_size; for (int i = 0; i < SAGE2OV_GENOME_ROUNDS; i++) o.estimate[i] = e.estimate[i];
+    o.rounds = e.rounds; o.degenerate = e.degenerate; o.agreed = e.agreed; o.reads_present = s.present;
+    copycount_times(c, s);
+    c->gsValid = true;
+    return SAGE2OV_OK;
+}
+int network_ensure(sage2ov_ctx* c, const char* who) {
+    { const int rc = copycount_check(c, who); if (rc) return rc; }
+    return c->netValid ? SAGE2OV_OK : sage2ov_flow_network_build(c);
+}
+}  // namespace
+int sage2ov_genome_size_rounds(const uint32_t* length, const uint64_t* k, uint64_t pairs, uint64_t reads, sage2ov_genome_estimate* out) {
+    if (!out || (pairs && (!length || !k))) return SAGE2OV_ERR_ARG;
+    return genome_rounds([&](bool first, float ratio, float l2, uint64_t* o) {
+        uint64_t ds = 0, ks = 0;
+        for (uint64_t i = 0; i < pairs; i++) {
+            const uint64_t delta = (uint32_t)(length[i] - 1u);
+            const bool ok = first ? length[i] > 500 : (a_statistic(delta, k[i], ratio, l2) >= 3.0f && delta >= 1000);
+            if (ok) { ds += delta; ks += k[i]; }
+        }
+        o[0] = ds; o[1] = ks; return 0;
+    }, reads, out);
+}
+int sage2ov_genome_size_estimate(sage2ov_ctx* c, uint64_t* genome_size) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    { const int rc = copycount_check(c, "sage2ov_genome_size_estimate"); if (rc) return rc; }
+    if (!c->gsValid) { const int rc = genome_estimate(c); if (rc) return rc; }
+    if (genome_size) *genome_size = c->ccstats.genome_size;
+    return SAGE2OV_OK;
+}
+int sage2ov_flow_network_build(sage2ov_ctx* c) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    { const int rc = copycount_check(c, "sage2ov_flow_network_build"); if (rc) return rc; }
+    if (!c->gsValid) { const int rc = genome_estimate(c); if (rc) return rc; }
+    c->netValid = false;
+    const uint64_t n = c->ccstats.reads_present, N = c->ccstats.genome_size;
+    CopyCountConst P;                                                                  // every log as the reference spells it (:145, :329-331)
+    P.ratio = (float)n / (float)N;
+    P.lj[0] = 0; for (int j = 1; j <= 20; j++) P.lj[j] = std::log((float)((float)(j + 1) / (float)j));
+    const int first_UB = 3, second_UB = 5, third_UB = 1000;
+    P.l1 = std::log((float)(1)); P.l3 = std::log((float)(first_UB)); P.l5 = std::log((float)(second_UB)); P.l1000 = std::log((float)(third_UB));
+    P.fN1 = std::log((float)(N - 1)); P.fN3 = std::log((float)(N - first_UB)); P.fN5 = std::log((float)(N - second_UB));
+    P.dN3 = std::log(N - first_UB); P.dN1000 = std::log(N - third_UB);
+    P.n = n;
+    CopyCountStats s;
+    { const int rc = dev_flownet_build(c->device(), P, &s, c->err); if (rc) return rc; }
+    sage2ov_copycount_stats& o = c->ccstats;
+    o.nodes = s.nodes; o.edges = s.edges; o.simple = s.simple; o.once = s.once; o.many = s.many; o.network_nodes = 4 * s.nodes + 2; o.network_arcs = s.arcs;
+    copycount_times(c, s);
+    c->netValid = true;
+    return SAGE2OV_OK;
+}
+int sage2ov_flow_network_count(sage2ov_ctx* c, uint64_t* nodes, uint64_t* arcs) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    { const int rc = network_ensure(c, "sage2ov_flow_network_count"); if (rc) return rc; }
+    if (nodes) *nodes = c->ccstats.network_nodes;
+    if (arcs) *arcs = c->ccstats.network_arcs;
+    return SAGE2OV_OK;
+}
+int sage2ov_flow_network_export(sage2ov_ctx* c, sage2ov_flow_arc* out, uint64_t cap) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    { const int rc = network_ensure(c, "sage2ov_flow_network_export"); if (rc) return rc; }
+    if (cap < c->ccstats.network_arcs) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_flow_network_export: the buffer holds fewer arcs than the network has");
+    if (!out) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_flow_network_export: null argument");
+    return dev_flownet_export(c->device(), (FlowArc*)out, c->err);
+}
+int sage2ov_flow_network_save(sage2ov_ctx* c, const char* path) {                      // :185-356
+    if (!c || !path) return SAGE2OV_ERR_ARG;
+    { const int rc = network_ensure(c, "sage2ov_flow_network_save"); if (rc) return rc; }
+    std::vector<FlowArc> arcs(c->ccstats.network_arcs);
+    { const int rc = dev_flownet_export(c->device(), arcs.data(), c->err); if (rc) return rc; }
+    FILE* f = fopen(path, "w"); if (!f) return c->fail(SAGE2OV_ERR_IO, std::string("cannot open ") + path);
+    std::vector<char> io(1 << 22); setvbuf(f, io.data(), _IOFBF, io.size());
+    const unsigned long long nn = c->ccstats.network_nodes;
+    fprintf(f, "p min %llu %llu\nn 1 0\nn 2 0\na 2 1 1 %llu 0\n", nn, (unsigned long long)arcs.size(), nn * 100ull);
+    const int rc = write_formatted(c, f, arcs.size() - 1, 40, [&](uint64_t x, std::string& o) {
+        const FlowArc& a = arcs[x + 1]; char buf[128]; char* p = buf;
+        *p++ = 'a'; *p++ = ' '; p = put_u(p, a.from); *p++ = ' '; p = put_u(p, a.to); *p++ = ' ';
+        p += snprintf(p, 64, "%d %d %f\n", a.lower, a.upper, (double)a.cost);          // (`ostream << std::fixed << float`: six decimals of the float's value)
+        o.append(buf, (size_t)(p - buf));
+    });
+    fclose(f); return rc;
+}
+int sage2ov_flow_solution_apply(sage2ov_ctx* c, const uint64_t* from, const uint64_t* to, const uint64_t* flow, uint64_t n) {      // :365-403
+    if (!c) return SAGE2OV_ERR_ARG;
+    { const int rc = network_ensure(c, "sage2ov_flow_solution_apply"); if (rc) return rc; }
+    if (n && (!from || !to || !flow)) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_flow_solution_apply: null argument");
+    if (n >= (1ull << 32) - 2048) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_flow_solution_apply: more lines than a network can have arcs");
+    const uint64_t nn = c->ccstats.network_nodes; uint64_t tts = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        if (from[i] < 1 || from[i] > nn || to[i] < 1 || to[i] > nn) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_flow_solution_apply: a node number outside the network");
+        if ((from[i] == 1 && to[i] == 2) || (from[i] == 2 && to[i] == 1)) tts = flow[i];
+    }
+    CopyCountStats s;
+    c->supports_forget(); c->contigs_forget();
+    { const int rc = dev_flow_apply(c->device(), from, to, flow, n, &s, c->err); if (rc) return rc; }
+    std::vector<float> f(c->g4.n_half_edges, 0.f);
+    { const int rc = dev_flow_get(c->device(), f.data(), f.size(), c->err); if (rc) return rc; }
+    c->g4.flow = std::move(f);
+    sage2ov_copycount_stats& o = c->ccstats;
+    o.t_to_s_flow = tts; o.flow_different = s.different; o.solution_lines = n; o.lines_applied = s.applied;
+    copycount_times(c, s);
+    return SAGE2OV_OK;
+}
+int sage2ov_flow_solution_load(sage2ov_ctx* c, const char* path) {
+    if (!c || !path) return SAGE2OV_ERR_ARG;
+    { const int rc = network_ensure(c, "sage2ov_flow_solution_load"); if (rc) return rc; }
+    FILE* f = fopen(path, "rb"); if (!f) return c->fail(SAGE2OV_ERR_IO, std::string("cannot open ") + path);
+    std::string txt; { char buf[1 << 16]; size_t n; while ((n = fread(buf, 1, sizeof buf, f)) > 0) txt.append(buf, n); } fclose(f);
+    std::vector<uint64_t> v[3]; const char* p = txt.c_str(); const char* end = p + txt.size(); int col = 0;
+    for (;;) {
+        while (p < end && (*p == ' ' || *p == '\t' || *p == '\n' || *p == '\r')) p++;
+        if (p >= end) break;
+        if (*p < '0' || *p > '9') return c->fail(SAGE2OV_ERR_IO, "sage2ov_flow_solution_load: not a number");
+        uint64_t x = 0; while (p < end && *p >= '0' && *p <= '9') x = x * 10 + (uint64_t)(*p++ - '0');
+        v[col].push_back(x); col = (col + 1) % 3;
+    }
+    if (col != 0) return c->fail(SAGE2OV_ERR_IO, "sage2ov_flow_solution_load: a line is not `from to flow`");
+    return sage2ov_flow_solution_apply(c, v[0].data(), v[1].data(), v[2].data(), v[0].size());
+}
+int sage2ov_graph5_save(sage2ov_ctx* c, const char* path) {                            // overlapGraph.cpp:338-369
+    if (!c || !path) return SAGE2OV_ERR_ARG;
+    { const int rc = copycount_check(c, "sage2ov_graph5_save"); if (rc) return rc; }
+    if (!c->gsValid) { const int rc = genome_estimate(c); if (rc) return rc; }
+    return save_composite(c, path, true, (unsigned long long)c->ccstats.genome_size, (unsigned long long)c->ccstats.reads_present);
+}
+int sage2ov_copycount_stats_get(const sage2ov_ctx* c, sage2ov_copycount_stats* o) { if (!c || !o) return SAGE2OV_ERR_ARG; *o = c->ccstats; return SAGE2OV_OK; }
 int sage2ov_mates_supports(sage2ov_ctx* c) {
     if (!c) return SAGE2OV_ERR_ARG;
     { const int rc = readmap_check(c, "sage2ov_mates_supports"); if (rc) return rc; }

@@ -212,6 +212,21 @@ int dev_contigs_build(Device* d, uint32_t threshold, std::vector<ContigRow>& row
 int dev_contigs_spell_begin(Device* d, int which, uint64_t first, uint64_t count, uint64_t chunk0, uint64_t nChunks, std::string& err);
 int dev_contigs_spell_wait(Device* d, int which, const char** image, double* ms, std::string& err);
 void dev_contigs_release(Device* d);
+// step 5 around its solver on the device (sage2ov_genome_size_estimate, sage2ov_flow_*; kernels_copycount.inc).  dev_copycount_prepare uploads the
+// frequencies (freq[0 .. N]) and makes k of every pair and the number of present reads; dev_copycount_round returns one round's {deltaSum, kSum} (previous 0: the
+// first round); dev_flownet_build the arc records and what dev_flow_apply needs, in allocations of their own that go with the graph and the read set.
+struct CopyCountStats { uint64_t present = 0, nodes = 0, edges = 0, simple = 0, once = 0, many = 0, arcs = 0, applied = 0, different = 0; uint32_t passes = 0;
+                        double k_ms = 0, round_ms = 0, order_ms = 0, classes_ms = 0, arcs_ms = 0, apply_ms = 0; };
+struct CopyCountConst { float ratio, lj[21], l1, l3, l5, l1000, fN1, fN3, fN5; double dN3, dN1000; uint64_t n; };
+struct FlowArc { uint32_t from, to; int32_t lower, upper; float cost; };
+int dev_copycount_prepare(Device* d, const uint16_t* freq, CopyCountStats* st, std::string& err);
+int dev_copycount_round(Device* d, int first, float ratio, float l2, uint64_t out[2], CopyCountStats* st, std::string& err);
+int dev_flownet_build(Device* d, const CopyCountConst& C, CopyCountStats* st, std::string& err);
+uint64_t dev_flownet_arcs(Device* d);
+int dev_flownet_export(Device* d, FlowArc* out, std::string& err);
+int dev_flow_apply(Device* d, const uint64_t* from, const uint64_t* to, const uint64_t* flow, uint64_t n, CopyCountStats* st, std::string& err);
+int dev_flow_get(Device* d, float* flow, uint64_t n, std::string& err);
+void dev_copycount_release(Device* d);
 void dev_timings(Device* d, DevTimings* t);
 void dev_reset_timings(Device* d);
 int dev_sync(Device* d, std::string& err);
