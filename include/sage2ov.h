@@ -404,7 +404,7 @@ int sage2ov_copycount_stats_get(const sage2ov_ctx* ctx, sage2ov_copycount_stats*
 
 /* ---- the sweep of ContigExtender::findMatepairSupports (matePair/mergeContigs.cpp:959-1030): getSupportOfEdges (:1032-1097) over isUniqueInEdge (:1102-1110) for every
  * incoming x outgoing pair of composite edges of every node, on the device; all quantities are integers.  The merge that follows it in the
- * reference (mergeByMatepairSupports / mergeEdgesAndUpdate: serial, order-dependent, changes the graph) is NOT part of this library.
+ * reference (mergeByMatepairSupports / mergeEdgesAndUpdate: order-dependent, changes the graph) is sage2ov_extend_round, below.
  * The graph is the resident step-4 graph; mates, read-to-edge table, locations and insert bounds are those of the calls above.
  *   CANDIDATE HALVES of node i: the alive half-edges leaving i with flow >= 1 (the half's own float), a non-empty read list and from != to (:979).  Such a half is an
  *   IN-HALF when its type is 0 or 1 (the reference's edge1 is its twin, which enters i, :981-983) and an OUT-HALF when its type is 2 or 3 (:984-986).
@@ -554,6 +554,87 @@ int sage2ov_contigs_sequences(sage2ov_ctx* ctx, uint64_t first, uint64_t count, 
 #define SAGE2OV_CONTIG_RANGE_BYTES (64u << 20)
 int sage2ov_contigs_save(sage2ov_ctx* ctx, const char* path, int is_scaffold);
 int sage2ov_contig_stats_get(const sage2ov_ctx* ctx, sage2ov_contig_stats* out);
+
+/* ---- the first loop of ContigExtender::extendContigs (matePair/mergeContigs.cpp:47-60): findMatepairSupports as a whole (:959-1030) -- the sweep above, the selection
+ * of mergeByMatepairSupports (:1112-1255) and mergeEdgesAndUpdate (:1260-1469) applied on the device to the resident step-4 graph -- run until a round
+ * merges nothing.  findPathSupports, findPathSupportsNew and mergeShortOverlaps (:62-) are not part of this library.
+ *   MERGE (e1, e2), e1 entering a node and e2 leaving it (mergeEdgesAndUpdate, overlapGraph.cpp:165-186, :259-266, :299-336): refused (no error, nothing changes) when
+ *   e1 == e2, e1 == e2's twin, either is dead, or combinedEdgeType is -1 -- the valid rows are (e1 type, e2 type) -> (0,0) 0, (1,2) 0, (0,1) 1, (1,3) 1, (2,0) 2, (3,2) 2,
+ *   (2,1) 3, (3,3) 3.  isReducible is 1 on every edge the loader, step 4 and a merge make (insertEdge sets it, nothing here clears it): no field is carried.
+ *   flow = 0 when both operands' flows are 0, else 1.0 for type_of_merge 1, else min(e1.flow, e2.flow) (type 2), read from e1's and e2's own floats.  The new edge
+ *   e1.from -> e2.to has type combinedEdgeType, length e1.len + e2.len (twin: e1.twin.len + e2.twin.len), `flow` on both halves, and the list getListOfReads(e1, e2):
+ *   e1's entries, one entry for the shared node {read = e1.to, orientation = 1 iff e1's type is 1 or 3, flag 0, distPrevious = distNext of e1's last entry (e1.len
+ *   when e1 has no list), distNext = distPrevious of e2's first entry (e2.len without a list)}, e2's entries; the twin's list is getListOfReads(e2.twin, e1.twin).
+ *   Then for e1 and for e2: own flow <= `flow`: both halves are deleted; else both halves lose `flow`, each its own float.
+ *   The new halves are the newest of their nodes (insertIntoList): they go to the end of the half-edge pool, forward half first, dead halves stay dead in place, and
+ *   sage2ov_graph4_save's order (node ascending, then pool order) is the reference's file order: a new pair comes after every older pair written at min(from, to).
+ *   A ROUND (findMatepairSupports(minOverlap = the context's k, high_threshold)): LIST = the supports table's entries with support > 1 as {edge1 = the twin of the
+ *   in-half, edge2 = the out-half, support}, built node ascending, in-half newest first (descending pool index), out-half likewise.  SEARCH maps the key
+ *   (edge1.from ^ edge1.to, edge2.from ^ edge2.to) -- an XOR: distinct pairs can share a key -- to the support of the first entry with the largest support (:1005-1012).
+ *   Every entry is filed under its four end nodes (deleteList).  The list is ordered by support descending.  For each entry in order (:1125-1248): skip when its key
+ *   is not in SEARCH; skip when node = edge1.to is BLOCKED (nodeSearch); stop at the first support < high_threshold.  Over the node's alive halves v, newest first,
+ *   with flow >= 1, a list and from != to, as the graph is now: ins = the twins v' != edge1 that match edge2, outs = the v != edge2 that edge1 matches (match(x, y):
+ *   combinedEdgeType(x, y) != -1, matchEdgeType :392).  inSupp = SEARCH[key(in), key(edge2)], else SEARCH[key(edge2), key(in)] (the mirrored pair of twins has
+ *   the same XOR values, swapped), else 0; outSupp likewise for (edge1, out).  Any of them > low_threshold: no merge.  Otherwise the `to` of every alive non-loop half
+ *   of the node is BLOCKED and MERGE(edge1, edge2, 1) runs; when it is not refused, every entry filed under the node leaves SEARCH.
+ *   Within a round no selection reads what an earlier merge of the round changed (both ends of a merged edge and all other neighbours of its node are blocked), so the
+ *   selection is a serial pass on the host over the table and the half-edge fields (from, to, type, flow, list length, alive -- never a read list), and the merges
+ *   of a round are edge-disjoint and go to the device as one batch.  (Should a selection name an edge an earlier merge of the round made or used, the batch so far is
+ *   applied first.)
+ *   THE INSERT BOUNDS are those of the last sage2ov_mates_estimate: a merge drops the read-to-edge table, supports, links, contigs and step 5's network -- the next call
+ *   that needs one rebuilds it from the merged graph -- but mean, deviation, bounds and maximumUpperBoundOfInsert stay until the caller estimates again (or the mates,
+ *   the read set or the graph are replaced).  Without an estimate, a round estimates once before its sweep.
+ * DELIBERATE DIFFERENCES: (1) std::sort leaves the order of equal supports open; HERE ties keep the order the list is built in (node ascending, in-half newest first,
+ * out-half newest first).  Equality with findMatepairSupports is claimed when no round holds two entries of equal support >= high_threshold; with ties, with the
+ * reference's mergeByMatepairSupports handed the list in this order.  (2) :1233 reads edge1->ID after mergeEdgesAndUpdate may have freed edge1; HERE the erase key is
+ * always the node.  Equality is claimed for rounds in which no merge deletes its in-edge while another entry at the same node is still listed.  (3) An entry whose key
+ * is listed through an XOR collision but whose edges are dead is skipped (the reference reads freed memory).  (4) The mate flags describe the merged graph after
+ * the table is rebuilt; the reference keeps those of meanSdEstimation.  Nothing here reads them after the estimate. */
+typedef struct sage2ov_merge {         /* one merge of the last round, 40 bytes */
+    uint32_t node, from, to;           /* the shared node; the new edge's ends (edge1.from, edge2.to) */
+    uint32_t support;
+    uint32_t pair_in, pair_out;        /* ordinals of edge1's and edge2's record pairs in sage2ov_graph4_save's order BEFORE the round (0xFFFFFFFF: made within it) */
+    uint32_t pair_new;                 /* ordinal of the new pair AFTER the round (0xFFFFFFFF: a later merge of the round used it up) */
+    float    flow;                     /* of the new edge */
+    uint8_t  type, in_deleted, out_deleted, pad[5];
+} sage2ov_merge;
+typedef struct sage2ov_extend_counts {
+    uint64_t entries;                  /* list entries (support > 1) */
+    uint64_t at_threshold;             /* of those, support >= high_threshold */
+    uint64_t refused;                  /* entries reached whose inSupp or outSupp exceeded low_threshold */
+    uint64_t blocked;                  /* entries skipped because their node was blocked */
+    uint64_t merges;
+    uint64_t entries_copied;           /* entries written to new lists (both lists of every merge) */
+    uint64_t pairs_deleted;            /* operand pairs deleted */
+    uint64_t batches;                  /* device batches (1 per round with a merge unless a selection named an edge of the round) */
+    double   sweep_ms, select_ms, lists_ms, commit_ms;      /* HIP events; select_ms: host wall time */
+} sage2ov_extend_counts;               /* 96 bytes */
+typedef struct sage2ov_extend_stats { uint64_t rounds, reserved; sage2ov_extend_counts last, total; } sage2ov_extend_stats;      /* 208 bytes; total: since the graph was made or loaded */
+/* the primitive: MERGE for a batch.  Operand i is e1 = the record (first_reversed[i] == 0) or the twin (1) of record pair pair_first[i] in sage2ov_graph4_save's order
+ * (the ordinals of sage2ov_read_edge and sage2ov_support; a loop is written twice and either ordinal names it, the record being the half written first there), e2 likewise from pair_second / second_reversed; type_of_merge 1 or 2.  merged[i] (may be NULL) = 1, or 0 for a refused merge.
+ * New pairs are created in batch order.  SAGE2OV_ERR_ARG, nothing changed: an ordinal out of range, a pair named twice in the batch, e1.to != e2.from, a null array,
+ * another type_of_merge, no step-4 graph.  SAGE2OV_ERR_LIMIT, nothing changed: a simple operand (no list) whose length or twin length is above 2047, the 11-bit field
+ * of a list entry; half-edges or list entries beyond the pools' 32-bit limits.  SAGE2OV_ERR_DEVICE on a device-less context.  Before the first merge on a graph the
+ * genome size is estimated if it is not (sage2ov_graph6_save writes that header).  Not sharded: a context with world > 1 behaves as a single one. */
+int sage2ov_graph_merge_pairs(sage2ov_ctx* ctx, const uint32_t* pair_first, const uint8_t* first_reversed, const uint32_t* pair_second, const uint8_t* second_reversed,
+                              uint64_t n, int type_of_merge, uint8_t* merged);
+/* :43-54, float for float: coverage = (float)((reads * average_read_length) / genome_size) (integer division), high = (int)ceilf((0.20 * coverage) * (100.0 /
+ * average_read_length)); with genome_size > 10^9 the factor is 0.10 in iterations 4-6 and 0.05 from 7 on.  Host only.  genome_size or average_read_length 0,
+ * iteration 0: SAGE2OV_ERR_ARG (the reference divides by zero). */
+int sage2ov_extend_threshold(uint64_t reads, uint64_t average_read_length, uint64_t genome_size, uint32_t iteration, int* high_threshold);
+/* one round; *merged (may be NULL) = its merges */
+int sage2ov_extend_round(sage2ov_ctx* ctx, int high_threshold, int low_threshold, uint64_t* merged);
+/* the loop of :47-60 with low_threshold 1 (main.cpp:357): rounds until one merges nothing; *rounds counts that one too.  genome_size 0: the value sage2ov_graph5_save
+ * would write (estimated when it is not); reads and average read length are that file's other two header values.  A genome size or average read length of 0:
+ * SAGE2OV_ERR_ARG.  After 10 000 rounds: SAGE2OV_ERR_INTERNAL. */
+int sage2ov_extend_by_supports(sage2ov_ctx* ctx, uint64_t genome_size, uint64_t* rounds, uint64_t* merged);
+/* the merges of the last round in selection order; cap below their number: SAGE2OV_ERR_ARG, nothing written */
+int sage2ov_extend_merges_count(const sage2ov_ctx* ctx, uint64_t* n);
+int sage2ov_extend_merges_export(const sage2ov_ctx* ctx, sage2ov_merge* out, uint64_t cap);
+int sage2ov_extend_stats_get(const sage2ov_ctx* ctx, sage2ov_extend_stats* out);
+/* P.graph6: saveOverlapGraphInFile of the graph as it now is.  sage2ov_graph5_save's text, except that after a merge line 1 and line 2 stay what sage2ov_graph5_save
+ * would have written before the first merge (the reference's genomeSize and numberOfReads do not change in step 6); on a graph without a merge it is an alias. */
+int sage2ov_graph6_save(sage2ov_ctx* ctx, const char* path);
 
 /* diagnostic: table census {occupied, inline, claimed-but-unfilled, zero-tag, entries in short CSR buckets} */
 int sage2ov_debug_table(sage2ov_ctx* ctx, uint64_t* out5);

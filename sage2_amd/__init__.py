@@ -84,6 +84,21 @@ class SupportStats(C.Structure):
                 ("roles_ms", C.c_double), ("scan_ms", C.c_double), ("records_ms", C.c_double), ("sort_ms", C.c_double), ("reduce_ms", C.c_double)]
 
 
+# sage2ov_merge (40 bytes): one merge of the last round of extend_round
+MERGE_DTYPE = np.dtype([("node", np.uint32), ("from", np.uint32), ("to", np.uint32), ("support", np.uint32), ("pair_in", np.uint32), ("pair_out", np.uint32),
+                        ("pair_new", np.uint32), ("flow", np.float32), ("type", np.uint8), ("in_deleted", np.uint8), ("out_deleted", np.uint8), ("pad", np.uint8, (5,))])
+
+
+class ExtendCounts(C.Structure):
+    _fields_ = [("entries", C.c_uint64), ("at_threshold", C.c_uint64), ("refused", C.c_uint64), ("blocked", C.c_uint64), ("merges", C.c_uint64),
+                ("entries_copied", C.c_uint64), ("pairs_deleted", C.c_uint64), ("batches", C.c_uint64),
+                ("sweep_ms", C.c_double), ("select_ms", C.c_double), ("lists_ms", C.c_double), ("commit_ms", C.c_double)]
+
+
+class ExtendStats(C.Structure):
+    _fields_ = [("rounds", C.c_uint64), ("reserved", C.c_uint64), ("last", ExtendCounts), ("total", ExtendCounts)]
+
+
 # sage2ov_contig (48 bytes): one row of the contig table
 CONTIG_DTYPE = np.dtype([("from", np.uint32), ("to", np.uint32), ("pair", np.uint32), ("edge_length", np.uint32), ("string_length", np.uint32), ("contig_length", np.uint32),
                          ("start", np.uint32), ("gap_count", np.uint32), ("n_count", np.uint32), ("flow", np.float32), ("type", np.uint8), ("pad", np.uint8, (7,))])
@@ -238,6 +253,15 @@ def genome_size_rounds(length, k, reads) -> GenomeEstimate:
     if rc:
         raise Sage2ovError(rc, "genome_size_rounds")
     return out
+
+
+def extend_threshold(reads, average_read_length, genome_size, iteration=1) -> int:
+    """highTh of ContigExtender::extendContigs (mergeContigs.cpp:43-54) in the given iteration of its first loop, on the host: no context, no GPU"""
+    out = C.c_int(0)
+    rc = lib().sage2ov_extend_threshold(C.c_uint64(reads), C.c_uint64(average_read_length), C.c_uint64(genome_size), C.c_uint32(iteration), C.byref(out))
+    if rc:
+        raise Sage2ovError(rc, "extend_threshold")
+    return int(out.value)
 
 
 class Context:
@@ -488,6 +512,50 @@ class Context:
         s = SupportStats()
         self._chk(lib().sage2ov_support_stats_get(self._h, C.byref(s)))
         return s
+
+    # ---- the first loop of ContigExtender::extendContigs (mergeContigs.cpp:47-60): merge rounds by mate-pair support on the resident graph
+    def merge_pairs(self, first, second, type_of_merge=1) -> np.ndarray:
+        """mergeEdgesAndUpdate for a batch of edge-disjoint merges.  first, second: per merge (pair ordinal in graph4_save's order, reversed) -- reversed 0 means the
+        pair's record, 1 its twin; first enters the shared node, second leaves it.  Returns the merged mask (0: a merge the reference refuses)."""
+        a = np.asarray(first, dtype=np.int64).reshape(-1, 2); b = np.asarray(second, dtype=np.int64).reshape(-1, 2)
+        if len(a) != len(b):
+            raise ValueError("one first and one second operand per merge")
+        if len(a) and (a.min() < 0 or b.min() < 0 or max(a[:, 0].max(), b[:, 0].max()) >= 1 << 32):
+            raise ValueError("pair ordinals are uint32")
+        pa = np.ascontiguousarray(a[:, 0], dtype=np.uint32); ra = np.ascontiguousarray(a[:, 1] != 0, dtype=np.uint8)
+        pb = np.ascontiguousarray(b[:, 0], dtype=np.uint32); rb = np.ascontiguousarray(b[:, 1] != 0, dtype=np.uint8)
+        out = np.zeros(len(a), dtype=np.uint8)
+        self._chk(lib().sage2ov_graph_merge_pairs(self._h, C.c_void_p(pa.ctypes.data), C.c_void_p(ra.ctypes.data), C.c_void_p(pb.ctypes.data), C.c_void_p(rb.ctypes.data),
+                                                  C.c_uint64(len(a)), C.c_int(type_of_merge), C.c_void_p(out.ctypes.data)))
+        return out
+
+    def extend_round(self, high, low=1) -> int:
+        """one findMatepairSupports(k, high): sweep, selection, merges; returns the number of merges"""
+        n = C.c_uint64(0)
+        self._chk(lib().sage2ov_extend_round(self._h, C.c_int(high), C.c_int(low), C.byref(n)))
+        return int(n.value)
+
+    def extend_by_supports(self, genome_size=0):
+        """rounds until one merges nothing -> (rounds, merges)"""
+        r, m = C.c_uint64(0), C.c_uint64(0)
+        self._chk(lib().sage2ov_extend_by_supports(self._h, C.c_uint64(genome_size), C.byref(r), C.byref(m)))
+        return int(r.value), int(m.value)
+
+    def extend_merges(self) -> np.ndarray:
+        """the merges of the last round (MERGE_DTYPE) in selection order"""
+        n = C.c_uint64(0)
+        self._chk(lib().sage2ov_extend_merges_count(self._h, C.byref(n)))
+        out = np.zeros(n.value, dtype=MERGE_DTYPE)
+        self._chk(lib().sage2ov_extend_merges_export(self._h, C.c_void_p(out.ctypes.data), C.c_uint64(n.value)))
+        return out
+
+    def extend_stats(self) -> ExtendStats:
+        s = ExtendStats()
+        self._chk(lib().sage2ov_extend_stats_get(self._h, C.byref(s)))
+        return s
+
+    def graph6_save(self, path):
+        self._chk(lib().sage2ov_graph6_save(self._h, os.fsencode(path)))
 
     # ---- the sweep that opens ScaffoldMaker::mergeFinal / mergeFinalSmall (scaffolding.cpp:786-935, :981-1130): support and gap of half-edge pairs linked by mates
     def links(self, mode=0, min_support=1) -> np.ndarray:

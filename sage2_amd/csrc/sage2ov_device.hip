@@ -231,6 +231,7 @@ static void mem_sample(Device* d) { size_t fr = 0, to = 0; if (hipMemGetInfo(&fr
 #include "kernels_reduce.inc"
 #include "kernels_convert.inc"
 #include "kernels_simplify.inc"
+#include "kernels_merge.inc"
 #include "kernels_find.inc"
 #include "kernels_mates.inc"
 #include "kernels_readmap.inc"
@@ -2135,7 +2136,8 @@ struct S4Mem {                                   // released on every exit path 
 };
 }
 #define S4GET(var, type, n) type* var = mem.get<type>((n), err); if (!var) return SAGE2OV_ERR_NOMEM;
-struct S4Keep { S4Mem mem; S4Graph g; u32 nh = 0; u64 listUsed = 0; float* flow = nullptr; };      // flow: one float per half-edge (null: every flow is 0, the state after step 4)
+struct S4Keep { S4Mem mem; S4Graph g; u32 nh = 0; u64 listUsed = 0; float* flow = nullptr;       // flow: one float per half-edge (null: every flow is 0, the state after step 4)
+                u64 capH = 0, listCap = 0, flowCap = 0; };                                       // what the half-edge arrays, the list pool and flow[] hold (dev_merge_pairs grows them)
 void dev_simplify_release(Device* d) { dev_readmap_release(d); dev_contigs_release(d); dev_copycount_release(d); if (d->s4keep) { hipSetDevice(d->ordinal); delete (S4Keep*)d->s4keep; d->s4keep = nullptr; } }
 
 int dev_simplify(Device* d, SimplifiedGraph& out, std::string& err) {
@@ -2339,22 +2341,25 @@ int dev_simplify(Device* d, SimplifiedGraph& out, std::string& err) {
                     (void*)isNew, (void*)newCnt, (void*)rank, (void*)cntScan, (void*)othA, (void*)othB}) mem.drop(p);
     g.adj = nullptr;
     lap("statistics + release of the work buffers");
-    keep->nh = nh; keep->listUsed = listUsed;
+    keep->nh = nh; keep->listUsed = listUsed; keep->capH = capH; keep->listCap = listCap;
     d->s4keep = keep.release();
     return 0;
 }
-int dev_simplify_download(Device* d, SimplifiedGraph& out, std::string& err) {
+int dev_simplify_download(Device* d, SimplifiedGraph& out, std::string& err, bool withLists) {
     HIPCHK(hipSetDevice(d->ordinal));
     if (!d->s4keep) { err = "step 4: no simplified graph on the device"; return SAGE2OV_ERR_ARG; }
-    if (out.downloaded) return 0;
+    if (out.downloaded || (out.fields && !withLists)) return 0;
     const S4Keep& k = *(S4Keep*)d->s4keep; const S4Graph& g = k.g; const u32 nh = k.nh;
-    out.from.resize(nh); out.to.resize(nh); out.len.resize(nh); out.cnt.resize(nh); out.off.resize(nh); out.type.resize(nh); out.alive.resize(nh); out.lists.resize(k.listUsed);
-    if (nh) {
+    if (!out.fields) { out.from.resize(nh); out.to.resize(nh); out.len.resize(nh); out.cnt.resize(nh); out.off.resize(nh); out.type.resize(nh); out.alive.resize(nh); }
+    if (nh && !out.fields) {
         HIPCHK(hipMemcpy(out.from.data(), g.from, nh * sizeof(u32), hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out.to.data(), g.to, nh * sizeof(u32), hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(out.len.data(), g.len, nh * sizeof(u32), hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out.cnt.data(), g.cnt, nh * sizeof(u32), hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(out.off.data(), g.off, nh * sizeof(u32), hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out.type.data(), g.type, nh, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(out.alive.data(), g.alive, nh, hipMemcpyDeviceToHost));
     }
+    out.fields = true;
+    if (!withLists) return 0;
+    out.lists.resize(k.listUsed);
     if (k.listUsed) HIPCHK(hipMemcpy(out.lists.data(), g.lists, k.listUsed * sizeof(u64), hipMemcpyDeviceToHost));
     out.downloaded = true;
     return 0;
@@ -2378,7 +2383,7 @@ int dev_simplify_upload(Device* d, const SimplifiedGraph& in, std::string& err) 
         HIPCHK(hipMemcpy(g.alive, in.alive.data(), nh, hipMemcpyHostToDevice));
     }
     if (nl) HIPCHK(hipMemcpy(g.lists, in.lists.data(), nl * sizeof(u64), hipMemcpyHostToDevice));
-    keep->nh = nh; keep->listUsed = nl;
+    keep->nh = nh; keep->listUsed = nl; keep->capH = std::max<u64>(nh, 1); keep->listCap = std::max<u64>(nl, 1);
     d->s4keep = keep.release();
     return in.flow.empty() ? 0 : dev_flow_set(d, in.flow.data(), in.flow.size(), err);
 }
@@ -2388,10 +2393,82 @@ int dev_flow_set(Device* d, const float* flow, uint64_t n, std::string& err) {
     if (!d->s4keep) { err = "flows: no step-4 graph on the device"; return SAGE2OV_ERR_ARG; }
     S4Keep& K = *(S4Keep*)d->s4keep; S4Mem& mem = K.mem;
     dev_support_release(d);
-    if (!flow) { if (K.flow) { mem.drop(K.flow); K.flow = nullptr; } return 0; }
+    if (!flow) { if (K.flow) { mem.drop(K.flow); K.flow = nullptr; K.flowCap = 0; } return 0; }
     if (n != K.nh) { err = "flows: one value per half-edge"; return SAGE2OV_ERR_INTERNAL; }
-    if (!K.flow) { S4GET(a, float, K.nh) K.flow = a; }
+    if (!K.flow) { S4GET(a, float, K.nh) K.flow = a; K.flowCap = std::max<u64>(K.nh, 1); }
     if (n) HIPCHK(hipMemcpy(K.flow, flow, n * sizeof(float), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// ---- mergeEdgesAndUpdate for a batch (kernels_merge.inc).  a[i], b[i]: the half-edges e1 and e2 of merge i, below K.nh, to[a] == from[b], no pair
+// named twice -- the caller has checked all of it, and the 11-bit limit of a simple operand's length.  out[i]: bit 0 merged, bit 1 e1's pair deleted, bit 2 e2's,
+// bits 4-5 the new type.  Everything made from the graph goes (as in dev_simplify_release), the graph itself stays.
+int dev_merge_pairs(Device* d, const u32* a, const u32* b, uint64_t n, int typeOfMerge, uint8_t* out, MergeStats* st, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    if (!d->s4keep) { err = "merge: no step-4 graph on the device"; return SAGE2OV_ERR_ARG; }
+    S4Keep& K = *(S4Keep*)d->s4keep; S4Mem& mem = K.mem; S4Graph& g = K.g; hipStream_t sm = d->stream;
+    *st = MergeStats();
+    if (!n) return 0;
+    if (n >= (1ull << 31) || (u64)K.nh + 2 * n >= (1ull << 32) - RS_TILE) { err = "merge: more than 2^32 half-edges"; return SAGE2OV_ERR_LIMIT; }
+    DevTmp B; StreamLap lap(sm); HIPCHK(lap.create());
+    const u32 m = (u32)n;
+    u32* da = B.get<u32>(n); u32* db = B.get<u32>(n); MgPlan* plan = B.get<MgPlan>(n); u32* lens = B.get<u32>(2 * n); u32* lo = B.get<u32>(2 * n); u32* isNew = B.get<u32>(n); u32* rank = B.get<u32>(n);
+    u64* partial = B.get<u64>(scan_partial_words(2 * n));
+    if (!da || !db || !plan || !lens || !lo || !isNew || !rank || !partial) { err = "merge: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+    HIPCHK(lap.start());
+    HIPCHK(hipMemcpyAsync(da, a, n * sizeof(u32), hipMemcpyHostToDevice, sm)); HIPCHK(hipMemcpyAsync(db, b, n * sizeof(u32), hipMemcpyHostToDevice, sm));
+    hipLaunchKernelGGL(k_mg_plan, dim3(grid_for(n, 256)), dim3(256), 0, sm, g, (const float*)K.flow, da, db, m, typeOfMerge, plan, lens, isNew);
+    u64 total = 0, created = 0;
+    { const int rc = scan_u32(d, lens, 2 * n, lo, partial, &total, err); if (rc) return rc; }
+    { const int rc = scan_u32(d, isNew, n, rank, partial, &created, err); if (rc) return rc; }
+    HIPCHK(lap.stop(st->plan_ms));
+    if (K.listUsed + total >= (1ull << 32) - RS_TILE) { err = "merge: read lists exceed 2^32 entries"; return SAGE2OV_ERR_LIMIT; }
+    // the pools grow as step 4's list pool does: a new block, the old content copied
+    if (created) {
+        const u64 needH = (u64)K.nh + 2 * created;
+        if (needH > K.capH) {
+            const u64 want = std::min<u64>(std::max<u64>(needH, K.capH + K.capH / 2), (1ull << 32) - RS_TILE);
+            auto grow = [&](auto*& arr) -> int {
+                using T = std::remove_reference_t<decltype(*arr)>;
+                T* nw = mem.get<T>(want, err); if (!nw) return SAGE2OV_ERR_NOMEM;
+                if (K.nh && hipMemcpyAsync(nw, arr, (size_t)K.nh * sizeof(T), hipMemcpyDeviceToDevice, sm) != hipSuccess) { err = "merge: device copy failed"; return SAGE2OV_ERR_DEVICE; }
+                if (hipStreamSynchronize(sm) != hipSuccess) { err = "merge: device copy failed"; return SAGE2OV_ERR_DEVICE; }
+                mem.drop(arr); arr = nw; return 0;
+            };
+            int rc;
+            if ((rc = grow(g.from)) || (rc = grow(g.to)) || (rc = grow(g.len)) || (rc = grow(g.cnt)) || (rc = grow(g.off)) || (rc = grow(g.type)) || (rc = grow(g.alive))) return rc;
+            K.capH = want;
+        }
+        if (K.flow && needH > K.flowCap) {
+            float* nw = mem.get<float>(K.capH, err); if (!nw) return SAGE2OV_ERR_NOMEM;
+            if (K.nh) HIPCHK(hipMemcpyAsync(nw, K.flow, (size_t)K.nh * sizeof(float), hipMemcpyDeviceToDevice, sm));
+            HIPCHK(hipStreamSynchronize(sm)); mem.drop(K.flow); K.flow = nw; K.flowCap = K.capH;
+        }
+        if (K.listUsed + total > K.listCap) {
+            const u64 want = std::max<u64>(K.listUsed + total, K.listCap + K.listCap / 2);
+            u64* nl = mem.get<u64>(want, err); if (!nl) return SAGE2OV_ERR_NOMEM;
+            if (K.listUsed) HIPCHK(hipMemcpyAsync(nl, g.lists, K.listUsed * sizeof(u64), hipMemcpyDeviceToDevice, sm));
+            HIPCHK(hipStreamSynchronize(sm)); mem.drop(g.lists); g.lists = nl; K.listCap = want;
+        }
+        dev_readmap_release(d); dev_contigs_release(d); dev_copycount_release(d);
+        HIPCHK(lap.start());
+        if (total) hipLaunchKernelGGL(k_mg_lists, dim3(grid_for(total, 256)), dim3(256), 0, sm, g, plan, lo, 2 * m, (u64)total, (u32)K.listUsed);
+        HIPCHK(hipGetLastError());
+        HIPCHK(lap.stop(st->lists_ms));
+        HIPCHK(lap.start());
+        hipLaunchKernelGGL(k_mg_commit, dim3(grid_for(n, 256)), dim3(256), 0, sm, g, K.flow, plan, lo, rank, m, K.nh, (u32)K.listUsed);
+        HIPCHK(hipGetLastError());
+        HIPCHK(lap.stop(st->commit_ms));
+    }
+    std::vector<MgPlan> hp(n);
+    HIPCHK(hipMemcpy(hp.data(), plan, n * sizeof(MgPlan), hipMemcpyDeviceToHost));
+    for (u64 i = 0; i < n; i++) {
+        const MgPlan& p = hp[i];
+        out[i] = (uint8_t)(p.merged | (p.del1 << 1) | (p.del2 << 2) | (p.type << 4));
+        st->pairs_deleted += (u64)p.del1 + p.del2;
+    }
+    K.nh += (u32)(2 * created); K.listUsed += total;
+    st->merged = created; st->entries_copied = total; st->half_edges = K.nh; st->list_entries = K.listUsed;
     return 0;
 }
 
@@ -3036,7 +3113,7 @@ int dev_flow_apply(Device* d, const uint64_t* from, const uint64_t* to, const ui
     u64* dfr = B.get<u64>(n); u64* dto = B.get<u64>(n); u64* dfl = B.get<u64>(n); unsigned long long* acc = B.get<unsigned long long>(nh); unsigned long long* ctr = B.get<unsigned long long>(2);
     if (!dfr || !dto || !dfl || !acc || !ctr) return copycount_nomem(err);
     const bool fresh = !K.flow;
-    if (fresh) { S4GET(a, float, nh) K.flow = a; }
+    if (fresh) { S4GET(a, float, nh) K.flow = a; K.flowCap = std::max<u64>(nh, 1); }
     dev_support_release(d);
     HIPCHK(lap.start());
     if (fresh && nh) HIPCHK(hipMemsetAsync(K.flow, 0, (u64)nh * sizeof(float), sm));

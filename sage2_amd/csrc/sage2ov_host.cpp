@@ -18,6 +18,7 @@
 #include <mutex>
 #include <condition_variable>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 #include <omp.h>
 #include <sched.h>
@@ -134,9 +135,14 @@ struct sage2ov_ctx {
     // ---- step 5 around its solver (sage2ov_genome_size_estimate, sage2ov_flow_*): the estimate and the network are of the present graph and read set; the data live on the device
     bool gsValid = false, netValid = false; sage2ov_copycount_stats ccstats{};
     void copycount_forget() { gsValid = netValid = false; ccstats = sage2ov_copycount_stats{}; }
-    void readmap_forget() { rmValid = estimated = false; pairOrdinal.clear(); rmstats = sage2ov_readmap_stats{}; supports_forget(); links_forget(); contigs_forget(); copycount_forget(); }      // the graph or the read set goes
+    // ---- the merge rounds (sage2ov_graph_merge_pairs, sage2ov_extend_*): the estimate outlives a merge (estimateHeld: a rebuilt table leaves it alone); the header
+    // values of P.graph6 are those from before the first merge
+    bool estimateHeld = false, hdrHeld = false; uint64_t hdrGenome = 0, hdrReads = 0;
+    sage2ov_extend_stats xstats{}; std::vector<sage2ov_merge> xmerges;
+    void extend_forget() { estimateHeld = hdrHeld = false; hdrGenome = hdrReads = 0; xstats = sage2ov_extend_stats{}; xmerges.clear(); }
+    void readmap_forget() { rmValid = estimated = false; extend_forget(); pairOrdinal.clear(); rmstats = sage2ov_readmap_stats{}; supports_forget(); links_forget(); contigs_forget(); copycount_forget(); }      // the graph or the read set goes
     void mates_forget(bool readSetGoes = true) {       // the read set goes: its ids mean nothing any more (the device drops its part in free_reads) -- or sage2ov_mates_clear
-        if (readSetGoes) { readmap_forget(); readsGen++; } else estimated = false;
+        if (readSetGoes) { readmap_forget(); readsGen++; } else estimated = estimateHeld = false;
         for (auto& L : mates) L = MateLib();
         for (int i = 0; i < 128; i++) { mateOnDevice[i] = false; matePairs[i] = 0; }
         mateLibraries = 0; mstats = sage2ov_mate_stats{};
@@ -1771,7 +1777,7 @@ int sage2ov_graph_load_composite(sage2ov_ctx* c, const char* path) {
         reads += g.cnt[a];
     }
     for (auto& x : g.alive) x = 1;                                                     // (2 marked a loop pair that has taken its mirror image: a third copy is a pair of its own)
-    g.n_half_edges = g.from.size(); g.pairs_alive = g.n_half_edges / 2; g.reads_on_edges = reads; g.downloaded = true;
+    g.n_half_edges = g.from.size(); g.pairs_alive = g.n_half_edges / 2; g.reads_on_edges = reads; g.downloaded = g.fields = true;
     c->g4Valid = false; c->readmap_forget();
     { const int rc = dev_simplify_upload(c->device(), g, c->err); if (rc) return rc; }
     c->g4 = std::move(g); c->g4Valid = true; c->g4Gen = c->readsGen; c->converted = false;                     // (no edge list of step 3 stands behind this graph: graph_simplify is refused)
@@ -1814,7 +1820,8 @@ void readmap_stats_take(sage2ov_ctx* c, const ReadMapStats& s) {
     o.scan_ms = s.scan_ms; o.records_ms = s.records_ms; o.sort_ms = s.sort_ms; o.reduce_ms = s.reduce_ms;
 }
 int readmap_build(sage2ov_ctx* c) {
-    c->rmValid = c->estimated = false; c->rmstats = sage2ov_readmap_stats{}; c->supports_forget(); c->links_forget();
+    c->rmValid = false; if (!c->estimateHeld) c->estimated = false;
+    c->rmstats = sage2ov_readmap_stats{}; c->supports_forget(); c->links_forget();
     ReadMapStats s; const int rc = dev_readmap_build(c->device(), &s, c->err); if (rc) return rc;
     readmap_stats_take(c, s); c->rmValid = true; return SAGE2OV_OK;
 }
@@ -1829,10 +1836,20 @@ int readmap_ensure(sage2ov_ctx* c, const char* who) {
     { const int rc = readmap_check(c, who); if (rc) return rc; }
     return c->rmValid ? SAGE2OV_OK : readmap_build(c);
 }
+// the estimate for a sweep: made when there is none; after a merge (estimateHeld) it stands and only the table is rebuilt from the merged graph, with the mates
+// placed as an estimate would place them
+int estimate_ensure(sage2ov_ctx* c) {
+    if (!c->estimated) return sage2ov_mates_estimate(c);
+    if (c->rmValid) return SAGE2OV_OK;
+    { const int rc = readmap_build(c); if (rc) return rc; }
+    dev_readmap_drop_joins(c->device());
+    for (int lib = 1; lib <= (int)c->mateLibraries && lib < 128; lib++) { const int rc = readmap_join(c, lib); if (rc) return rc; }
+    return SAGE2OV_OK;
+}
 // internal pair -> ordinal of its record pair in sage2ov_graph4_save's order (a loop, written twice: the first time)
 int pair_ordinals(sage2ov_ctx* c) {
     if (!c->pairOrdinal.empty()) return SAGE2OV_OK;
-    { const int rc = dev_simplify_download(c->device(), c->g4, c->err); if (rc) return rc; }
+    { const int rc = dev_simplify_download(c->device(), c->g4, c->err, false); if (rc) return rc; }
     std::vector<uint32_t> order; g4_save_order(c->g4, order);
     c->pairOrdinal.assign(c->g4.n_half_edges / 2 + 1, ~0u);
     for (size_t x = 0; x < order.size(); x++) { uint32_t& o = c->pairOrdinal[order[x] >> 1]; if (o == ~0u) o = (uint32_t)x; }
@@ -1928,7 +1945,7 @@ int sage2ov_mates_distances_export(sage2ov_ctx* c, int library, uint32_t* d, uin
 int sage2ov_mates_estimate(sage2ov_ctx* c) {
     if (!c) return SAGE2OV_ERR_ARG;
     { const int rc = readmap_ensure(c, "sage2ov_mates_estimate"); if (rc) return rc; }
-    c->estimated = false; c->rmstats.rounds = 0; c->rmstats.round_ms = 0; c->supports_forget(); c->links_forget();
+    c->estimated = c->estimateHeld = false; c->rmstats.rounds = 0; c->rmstats.round_ms = 0; c->supports_forget(); c->links_forget();
     const uint64_t arl = average_read_length(c); Device* d = c->device();
     c->minUpper = 1000000; c->maxUpper = 0;                                            // matePair.cpp:292-293
     for (auto& I : c->inserts) I = sage2ov_insert{};
@@ -1964,7 +1981,7 @@ namespace {
 static_assert(sizeof(sage2ov_support) == 24, "sage2ov_support is six uint32_t");
 // the half-edges that open a record pair in sage2ov_graph4_save's order, a loop at its first writing only
 int flow_order(sage2ov_ctx* c, std::vector<uint32_t>& first) {
-    { const int rc = dev_simplify_download(c->device(), c->g4, c->err); if (rc) return rc; }
+    { const int rc = dev_simplify_download(c->device(), c->g4, c->err, false); if (rc) return rc; }
     std::vector<uint32_t> order; g4_save_order(c->g4, order);
     std::vector<uint8_t> seen(c->g4.n_half_edges / 2 + 1, 0); first.clear();
     for (uint32_t h : order) if (!seen[h >> 1]) { seen[h >> 1] = 1; first.push_back(h); }
@@ -2195,7 +2212,7 @@ int sage2ov_copycount_stats_get(const sage2ov_ctx* c, sage2ov_copycount_stats* o
 int sage2ov_mates_supports(sage2ov_ctx* c) {
     if (!c) return SAGE2OV_ERR_ARG;
     { const int rc = readmap_check(c, "sage2ov_mates_supports"); if (rc) return rc; }
-    if (!c->estimated || !c->rmValid) { const int rc = sage2ov_mates_estimate(c); if (rc) return rc; }
+    { const int rc = estimate_ensure(c); if (rc) return rc; }
     c->supports_forget();
     const int64_t arl = (int64_t)average_read_length(c), k = (int64_t)c->cfg.min_overlap;
     SupportParams P; P.bound = c->maxUpper; P.libraries = c->mateLibraries;
@@ -2223,6 +2240,217 @@ int sage2ov_mates_supports_export(sage2ov_ctx* c, uint32_t min_support, sage2ov_
     return SAGE2OV_OK;
 }
 int sage2ov_support_stats_get(const sage2ov_ctx* c, sage2ov_support_stats* o) { if (!c || !o) return SAGE2OV_ERR_ARG; *o = c->sstats; return SAGE2OV_OK; }
+
+// ---- the first loop of ContigExtender::extendContigs (mergeContigs.cpp:47-60, :959-1030, :1112-1469); the semantics are stated in sage2ov.h
+namespace {
+static_assert(sizeof(sage2ov_merge) == 40 && sizeof(sage2ov_extend_counts) == 96 && sizeof(sage2ov_extend_stats) == 208, "the records of the merge rounds");
+inline int combined_type(unsigned t1, unsigned t2) {                                   // overlapGraph.cpp:259-266
+    if ((t1 == 0 && t2 == 0) || (t1 == 1 && t2 == 2)) return 0;
+    if ((t1 == 0 && t2 == 1) || (t1 == 1 && t2 == 3)) return 1;
+    if ((t1 == 2 && t2 == 0) || (t1 == 3 && t2 == 2)) return 2;
+    if ((t1 == 2 && t2 == 1) || (t1 == 3 && t2 == 3)) return 3;
+    return -1;
+}
+// lines 1 and 2 of P.graph6: what sage2ov_graph5_save would write before the first merge
+int header_hold(sage2ov_ctx* c) {
+    if (c->hdrHeld) return SAGE2OV_OK;
+    if (!c->gsValid) { const int rc = genome_estimate(c); if (rc) return rc; }
+    c->hdrGenome = c->ccstats.genome_size; c->hdrReads = c->ccstats.reads_present; c->hdrHeld = true;
+    return SAGE2OV_OK;
+}
+// a batch of internal half-edges through the device; afterwards everything made from the graph is stale, the estimate stands and the host copy of the fields is gone
+int merge_apply(sage2ov_ctx* c, const std::vector<uint32_t>& a, const std::vector<uint32_t>& b, int type, std::vector<uint8_t>& out, MergeStats& s) {
+    { const int rc = header_hold(c); if (rc) return rc; }
+    out.assign(a.size(), 0);
+    { const int rc = dev_merge_pairs(c->device(), a.data(), b.data(), a.size(), type, out.data(), &s, c->err); if (rc) return rc; }
+    if (!s.merged) return SAGE2OV_OK;
+    const bool est = c->estimated;
+    c->rmValid = false; c->pairOrdinal.clear(); c->rmstats = sage2ov_readmap_stats{}; c->supports_forget(); c->links_forget(); c->contigs_forget(); c->copycount_forget();
+    c->estimateHeld = est;
+    SimplifiedGraph& g = c->g4;
+    g.downloaded = g.fields = false; g.lists.clear(); g.lists.shrink_to_fit();
+    g.n_half_edges = s.half_edges; g.pairs_alive += s.merged; g.pairs_alive -= std::min<uint64_t>(g.pairs_alive, s.pairs_deleted);
+    if (!g.flow.empty()) { g.flow.assign(g.n_half_edges, 0.f); const int rc = dev_flow_get(c->device(), g.flow.data(), g.flow.size(), c->err); if (rc) return rc; }
+    return SAGE2OV_OK;
+}
+void counts_add(sage2ov_extend_counts& t, const sage2ov_extend_counts& r) {
+    t.entries += r.entries; t.at_threshold += r.at_threshold; t.refused += r.refused; t.blocked += r.blocked; t.merges += r.merges; t.entries_copied += r.entries_copied;
+    t.pairs_deleted += r.pairs_deleted; t.batches += r.batches; t.sweep_ms += r.sweep_ms; t.select_ms += r.select_ms; t.lists_ms += r.lists_ms; t.commit_ms += r.commit_ms;
+}
+}  // namespace
+int sage2ov_graph_merge_pairs(sage2ov_ctx* c, const uint32_t* pf, const uint8_t* fr, const uint32_t* ps, const uint8_t* sr, uint64_t n, int type, uint8_t* merged) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    if (type != 1 && type != 2) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_merge_pairs: type_of_merge is 1 or 2");
+    if (n && (!pf || !fr || !ps || !sr)) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_merge_pairs: null argument");
+    { const int rc = readmap_check(c, "sage2ov_graph_merge_pairs"); if (rc) return rc; }
+    if (n >= (1ull << 31)) return c->fail(SAGE2OV_ERR_LIMIT, "sage2ov_graph_merge_pairs: more merges than there can be pairs");
+    { const int rc = dev_simplify_download(c->device(), c->g4, c->err, false); if (rc) return rc; }
+    const SimplifiedGraph& g = c->g4;
+    std::vector<uint32_t> first; g4_save_order(g, first);                              // ordinal -> the half that opens the record pair (a loop has two ordinals, one per half)
+    std::vector<uint32_t> a(n), b(n); std::vector<uint8_t> used(g.n_half_edges / 2 + 1, 0);
+    for (uint64_t i = 0; i < n; i++) {
+        if (pf[i] >= first.size() || ps[i] >= first.size()) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_merge_pairs: a pair ordinal beyond the record pairs of the graph");
+        a[i] = first[pf[i]] ^ (fr[i] ? 1u : 0u); b[i] = first[ps[i]] ^ (sr[i] ? 1u : 0u);
+        if (used[a[i] >> 1] || used[b[i] >> 1]) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_merge_pairs: a record pair is named by two merges of the batch");
+        used[a[i] >> 1] = used[b[i] >> 1] = 1;
+        if (g.to[a[i]] != g.from[b[i]]) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_merge_pairs: the first edge does not end where the second begins");
+    }
+    for (uint64_t i = 0; i < n; i++)
+        for (uint32_t h : {a[i], b[i]})
+            if (g.cnt[h] == 0 && (g.len[h] > 0x7FF || g.len[h ^ 1u] > 0x7FF))
+                return c->fail(SAGE2OV_ERR_LIMIT, "sage2ov_graph_merge_pairs: a simple edge longer than 2047 (the 11-bit field of a list entry)");
+    std::vector<uint8_t> out; MergeStats s;
+    { const int rc = merge_apply(c, a, b, type, out, s); if (rc) return rc; }
+    if (merged) for (uint64_t i = 0; i < n; i++) merged[i] = out[i] & 1u;
+    return SAGE2OV_OK;
+}
+int sage2ov_extend_threshold(uint64_t reads, uint64_t arl, uint64_t genomeSize, uint32_t iteration, int* high) {     // mergeContigs.cpp:43-54
+    if (!high || !arl || !genomeSize || !iteration) return SAGE2OV_ERR_ARG;
+    const float coverage = (reads * arl) / genomeSize;
+    double factor = 0.20;
+    if (genomeSize > 1000000000) { if (iteration >= 4 && iteration <= 6) factor = 0.10; else if (iteration > 6) factor = 0.05; }
+    *high = (int)ceilf((factor * coverage) * (100.0 / arl));
+    return SAGE2OV_OK;
+}
+int sage2ov_extend_round(sage2ov_ctx* c, int highTh, int lowTh, uint64_t* merged) {                                   // :959-1030, :1112-1255
+    if (!c) return SAGE2OV_ERR_ARG;
+    { const int rc = readmap_check(c, "sage2ov_extend_round"); if (rc) return rc; }
+    sage2ov_extend_counts R{};
+    const bool swept = !(c->supValid && c->estimated && c->rmValid);
+    { const int rc = supports_ensure(c, "sage2ov_extend_round"); if (rc) return rc; }
+    if (swept) R.sweep_ms = c->sstats.roles_ms + c->sstats.scan_ms + c->sstats.records_ms + c->sstats.sort_ms + c->sstats.reduce_ms;
+    Device* d = c->device();
+    const uint64_t E = dev_support_count(d);
+    std::vector<uint64_t> key(E); std::vector<uint32_t> sup(E);
+    { const int rc = dev_support_export(d, key.data(), sup.data(), c->err); if (rc) return rc; }
+    { const int rc = pair_ordinals(c); if (rc) return rc; }                           // (the half-edge fields come with it; no read list)
+    const auto t0 = std::chrono::steady_clock::now();
+    const std::vector<uint32_t> ordBefore = c->pairOrdinal;
+    std::vector<uint32_t> from = c->g4.from, to = c->g4.to, cnt = c->g4.cnt; std::vector<uint8_t> type = c->g4.type, alive = c->g4.alive;
+    std::vector<float> flow = c->g4.flow; flow.resize(from.size(), 0.f);
+    uint32_t nh = (uint32_t)from.size(), devNh = nh;
+    // the node lists as the round finds them (alive halves by ascending index; walked backwards: newest first) and the halves the round adds
+    std::vector<uint32_t> offs(c->g4.N + 2, 0), adj;
+    for (uint32_t h = 0; h < nh; h++) if (alive[h]) offs[from[h] + 1]++;
+    for (uint64_t i = 0; i <= c->g4.N; i++) offs[i + 1] += offs[i];
+    adj.resize(offs[c->g4.N + 1]);
+    { std::vector<uint32_t> cur(offs.begin(), offs.end() - 1); for (uint32_t h = 0; h < nh; h++) if (alive[h]) adj[cur[from[h]]++] = h; }
+    std::unordered_map<uint32_t, std::vector<uint32_t>> added;
+    auto walk = [&](uint32_t node, auto&& fn) {
+        auto it = added.find(node);
+        if (it != added.end()) for (size_t x = it->second.size(); x-- > 0;) if (alive[it->second[x]]) fn(it->second[x]);
+        for (uint32_t x = offs[node + 1]; x-- > offs[node];) if (alive[adj[x]]) fn(adj[x]);
+    };
+    // the list in building order (node ascending, in-half newest first, out-half newest first), SEARCH and the entries filed under their end nodes
+    struct Ent { uint32_t e1, e2, sup, node; };
+    std::vector<Ent> list;
+    for (uint64_t e = 0; e < E; e++) if (sup[e] > 1) { const uint32_t ia = (uint32_t)(key[e] >> 32), ob = (uint32_t)key[e]; list.push_back(Ent{ia ^ 1u, ob, sup[e], from[ia]}); }
+    std::sort(list.begin(), list.end(), [](const Ent& x, const Ent& y) { return x.node != y.node ? x.node < y.node : (x.e1 != y.e1 ? x.e1 > y.e1 : x.e2 > y.e2); });
+    auto xk = [&](uint32_t h) -> uint64_t { return (uint64_t)(from[h] ^ to[h]); };
+    auto k2 = [&](uint32_t h1, uint32_t h2) -> uint64_t { return (xk(h1) << 32) | xk(h2); };
+    std::unordered_map<uint64_t, uint32_t> search; std::unordered_multimap<uint32_t, uint64_t> filed;
+    for (const Ent& en : list) {
+        const uint64_t kk = k2(en.e1, en.e2);
+        auto it = search.find(kk);
+        if (it == search.end()) search[kk] = en.sup; else if (en.sup > it->second) it->second = en.sup;
+        for (uint32_t nd : {to[en.e1], from[en.e1], to[en.e2], from[en.e2]}) filed.insert({nd, kk});
+    }
+    std::stable_sort(list.begin(), list.end(), [](const Ent& x, const Ent& y) { return x.sup > y.sup; });
+    R.entries = list.size(); for (const Ent& en : list) R.at_threshold += (int64_t)en.sup >= (int64_t)highTh;
+    auto lookup = [&](uint64_t kk) -> int64_t { auto it = search.find(kk); return it == search.end() ? -1 : (int64_t)it->second; };
+    std::unordered_set<uint32_t> blocked, usedPair;
+    std::vector<uint32_t> bA, bB; std::vector<sage2ov_merge> merges; std::vector<uint32_t> newHalf;
+    double selectOut = 0;                                                              // time spent in the device batches, not selection
+    auto flush = [&]() -> int {
+        if (bA.empty()) return SAGE2OV_OK;
+        const auto f0 = std::chrono::steady_clock::now();
+        std::vector<uint8_t> out; MergeStats s;
+        { const int rc = merge_apply(c, bA, bB, 1, out, s); if (rc) return rc; }
+        for (uint8_t o : out) if (!(o & 1u)) return c->fail(SAGE2OV_ERR_INTERNAL, "sage2ov_extend_round: the device refused a merge the selection made");
+        if (s.half_edges != nh) return c->fail(SAGE2OV_ERR_INTERNAL, "sage2ov_extend_round: the device and the selection disagree on the half-edges");
+        R.entries_copied += s.entries_copied; R.pairs_deleted += s.pairs_deleted; R.batches++; R.lists_ms += s.lists_ms; R.commit_ms += s.plan_ms + s.commit_ms;
+        bA.clear(); bB.clear(); usedPair.clear(); devNh = nh;
+        selectOut += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - f0).count();
+        return SAGE2OV_OK;
+    };
+    for (const Ent& en : list) {
+        const uint32_t e1 = en.e1, e2 = en.e2;
+        if (!alive[e1] || !alive[e2]) continue;                                        // (difference 3)
+        if (lookup(k2(e1, e2)) < 0) continue;
+        const uint32_t node = to[e1];
+        if (blocked.count(node)) { R.blocked++; continue; }
+        if ((int64_t)en.sup < (int64_t)highTh) break;
+        bool unique = true;
+        walk(node, [&](uint32_t v) {
+            if (!(flow[v] >= 1.f) || cnt[v] == 0 || to[v] == from[v]) return;
+            if ((v ^ 1u) != e1 && combined_type(type[v ^ 1u], type[e2]) >= 0) {
+                int64_t s = lookup(k2(v ^ 1u, e2)); if (s < 0) s = lookup(k2(e2 ^ 1u, v)); if (s > lowTh) unique = false;
+            }
+            if (v != e2 && combined_type(type[e1], type[v]) >= 0) {
+                int64_t s = lookup(k2(e1, v)); if (s < 0) s = lookup(k2(v ^ 1u, e1 ^ 1u)); if (s > lowTh) unique = false;
+            }
+        });
+        if (!unique) { R.refused++; continue; }
+        walk(node, [&](uint32_t v) { if (to[v] != from[v]) blocked.insert(to[v]); });
+        const int t = combined_type(type[e1], type[e2]);
+        if (e1 == e2 || e1 == (e2 ^ 1u) || t < 0) continue;                            // mergeEdgesAndUpdate returns NULL
+        if (e1 >= devNh || e2 >= devNh || usedPair.count(e1 >> 1) || usedPair.count(e2 >> 1)) { const int rc = flush(); if (rc) return rc; }
+        if ((uint64_t)nh + 2 >= (1ull << 32) - 4096) return c->fail(SAGE2OV_ERR_LIMIT, "sage2ov_extend_round: more than 2^32 half-edges");
+        const float f1 = flow[e1], f2 = flow[e2], f = (f1 == 0.f && f2 == 0.f) ? 0.f : 1.f;
+        sage2ov_merge m{}; m.node = node; m.from = from[e1]; m.to = to[e2]; m.support = en.sup; m.flow = f; m.type = (uint8_t)t;
+        m.pair_in = (e1 >> 1) < ordBefore.size() ? ordBefore[e1 >> 1] : ~0u; m.pair_out = (e2 >> 1) < ordBefore.size() ? ordBefore[e2 >> 1] : ~0u; m.pair_new = ~0u;
+        m.in_deleted = f1 <= f; m.out_deleted = f2 <= f;
+        from.push_back(from[e1]); to.push_back(to[e2]); type.push_back((uint8_t)t); cnt.push_back(cnt[e1] + cnt[e2] + 1); alive.push_back(1); flow.push_back(f);
+        from.push_back(to[e2]); to.push_back(from[e1]); type.push_back((uint8_t)flip_type_host(t)); cnt.push_back(cnt[e1] + cnt[e2] + 1); alive.push_back(1); flow.push_back(f);
+        if (m.in_deleted) alive[e1] = alive[e1 ^ 1u] = 0; else { flow[e1] -= f; flow[e1 ^ 1u] -= f; }
+        if (m.out_deleted) alive[e2] = alive[e2 ^ 1u] = 0; else { flow[e2] -= f; flow[e2 ^ 1u] -= f; }
+        added[from[nh]].push_back(nh); added[from[nh + 1]].push_back(nh + 1);
+        bA.push_back(e1); bB.push_back(e2); usedPair.insert(e1 >> 1); usedPair.insert(e2 >> 1); usedPair.insert(nh >> 1);
+        merges.push_back(m); newHalf.push_back(nh); nh += 2;
+        auto its = filed.equal_range(node);                                           // (difference 2: the key is the node)
+        for (auto it = its.first; it != its.second; ++it) search.erase(it->second);
+    }
+    { const int rc = flush(); if (rc) return rc; }
+    R.merges = merges.size();
+    R.select_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - selectOut;
+    if (!merges.empty()) {
+        { const int rc = pair_ordinals(c); if (rc) return rc; }
+        for (size_t i = 0; i < merges.size(); i++) merges[i].pair_new = (newHalf[i] >> 1) < c->pairOrdinal.size() ? c->pairOrdinal[newHalf[i] >> 1] : ~0u;
+    }
+    c->xmerges = std::move(merges);
+    c->xstats.rounds++; c->xstats.last = R; counts_add(c->xstats.total, R);
+    if (merged) *merged = R.merges;
+    return SAGE2OV_OK;
+}
+int sage2ov_extend_by_supports(sage2ov_ctx* c, uint64_t genomeSize, uint64_t* rounds, uint64_t* merged) {             // :47-60
+    if (!c) return SAGE2OV_ERR_ARG;
+    { const int rc = readmap_check(c, "sage2ov_extend_by_supports"); if (rc) return rc; }
+    { const int rc = header_hold(c); if (rc) return rc; }
+    const uint64_t gs = genomeSize ? genomeSize : c->hdrGenome, reads = c->hdrReads, arl = average_read_length(c);
+    if (!gs || !arl) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_extend_by_supports: a genome size or an average read length of 0");
+    uint64_t r = 0, total = 0;
+    for (uint32_t it = 1; it <= 10000; it++) {
+        int high = 0; sage2ov_extend_threshold(reads, arl, gs, it, &high);
+        uint64_t m = 0; { const int rc = sage2ov_extend_round(c, high, 1, &m); if (rc) return rc; }
+        r++; total += m;
+        if (rounds) *rounds = r; if (merged) *merged = total;
+        if (!m) return SAGE2OV_OK;
+    }
+    return c->fail(SAGE2OV_ERR_INTERNAL, "sage2ov_extend_by_supports: 10 000 rounds without a fixed point");
+}
+int sage2ov_extend_merges_count(const sage2ov_ctx* c, uint64_t* n) { if (!c || !n) return SAGE2OV_ERR_ARG; *n = c->xmerges.size(); return SAGE2OV_OK; }
+int sage2ov_extend_merges_export(const sage2ov_ctx* c, sage2ov_merge* out, uint64_t cap) {
+    if (!c || cap < c->xmerges.size() || (!out && !c->xmerges.empty())) return SAGE2OV_ERR_ARG;
+    if (!c->xmerges.empty()) memcpy(out, c->xmerges.data(), c->xmerges.size() * sizeof(sage2ov_merge));
+    return SAGE2OV_OK;
+}
+int sage2ov_extend_stats_get(const sage2ov_ctx* c, sage2ov_extend_stats* o) { if (!c || !o) return SAGE2OV_ERR_ARG; *o = c->xstats; return SAGE2OV_OK; }
+int sage2ov_graph6_save(sage2ov_ctx* c, const char* path) {                            // overlapGraph.cpp:338-369
+    if (!c || !path) return SAGE2OV_ERR_ARG;
+    if (!c->hdrHeld) return sage2ov_graph5_save(c, path);
+    { const int rc = copycount_check(c, "sage2ov_graph6_save"); if (rc) return rc; }
+    return save_composite(c, path, true, (unsigned long long)c->hdrGenome, (unsigned long long)c->hdrReads);
+}
 
 // ---- the sweep that opens ScaffoldMaker::mergeFinal / mergeFinalSmall (scaffolding.cpp:786-935, :981-1130); the semantics are stated in sage2ov.h
 namespace {
@@ -2276,7 +2504,7 @@ bool link_passes(const sage2ov_ctx* c, uint64_t e, uint32_t mode, int threshold)
 int sage2ov_links(sage2ov_ctx* c) {
     if (!c) return SAGE2OV_ERR_ARG;
     { const int rc = readmap_check(c, "sage2ov_links"); if (rc) return rc; }
-    if (!c->estimated || !c->rmValid) { const int rc = sage2ov_mates_estimate(c); if (rc) return rc; }
+    { const int rc = estimate_ensure(c); if (rc) return rc; }
     c->links_forget();
     const int64_t arl = (int64_t)average_read_length(c), k = (int64_t)c->cfg.min_overlap;
     LinkParams P; P.bound = c->maxUpper; P.libraries = c->mateLibraries;

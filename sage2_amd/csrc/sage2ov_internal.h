@@ -161,10 +161,14 @@ int dev_upload_edges(Device* d, const std::vector<FinalEdge>& in, std::string& e
 struct SimplifiedGraph {
     std::vector<float> flow;          // one per half-edge as loadOverlapGraphFromFile parses it (overlapGraph.cpp:393, :409, :433); empty: every flow is 0
     uint64_t N = 0, n_half_edges = 0, contracted = 0, removed = 0, iterations = 0, pairs_alive = 0, reads_on_edges = 0; double device_ms = 0; bool downloaded = false;
+    bool fields = false;              // from .. alive are filled (downloaded: the lists too)
     std::vector<uint32_t> from, to, len, cnt, off; std::vector<uint8_t> type, alive; std::vector<uint64_t> lists;
 };
 int dev_simplify(Device* d, SimplifiedGraph& out, std::string& err);             // result stays in HBM
-int dev_simplify_download(Device* d, SimplifiedGraph& out, std::string& err);    // fills the arrays (once)
+int dev_simplify_download(Device* d, SimplifiedGraph& out, std::string& err, bool withLists = true);    // fills the arrays (once); withLists false: the half-edge fields only
+// ContigExtender::mergeEdgesAndUpdate for a batch of edge-disjoint merges over the resident graph (sage2ov_graph_merge_pairs; kernels_merge.inc)
+struct MergeStats { uint64_t merged = 0, entries_copied = 0, pairs_deleted = 0, half_edges = 0, list_entries = 0; double plan_ms = 0, lists_ms = 0, commit_ms = 0; };
+int dev_merge_pairs(Device* d, const uint32_t* a, const uint32_t* b, uint64_t n, int typeOfMerge, uint8_t* out, MergeStats* st, std::string& err);
 void dev_simplify_release(Device* d);
 int dev_simplify_upload(Device* d, const SimplifiedGraph& in, std::string& err);  // a parsed graph (from .. lists filled) takes the place of step 4's result in HBM
 // MatePair::mapReadsToEdges / mapReadLocations / computeMeanSD on the device (sage2ov_mates_map_reads, _estimate): dev_readmap_build makes the
