@@ -446,7 +446,7 @@ int sage2ov_support_stats_get(const sage2ov_ctx* ctx, sage2ov_support_stats* out
 /* ---- the sweep that opens every round of ScaffoldMaker::mergeFinal (matePair/scaffolding.cpp:786-935) and mergeFinalSmall (:981-1130): for every composite edge and every
  * edge its mates reach, connected through a node or not, the number of mate pairs that link the two and the mean gap those pairs imply, on the device;
  * all quantities are integers.  The merges that follow it in the reference (mergeAccordingToSupport / mergeAccordingToSupport2 / mergeDisconnectedEdges: serial, they change
- * the graph) and its ordering of the rows (quicksortListOfLongEdges, :252-275: ties are open there) are NOT part of this library.
+ * the graph) and its ordering of the rows (quicksortListOfLongEdges, :252-275: ties are open there) are sage2ov_scaffold_round, below.
  * The graph is the resident step-4 graph; mates, read-to-edge table, locations and insert estimates are those of the calls above; minOverlap is the context's k.
  *   LINK(a, b) is defined for an ordered pair of alive half-edges with pair(a) != pair(b) and a non-empty list on a.  Loops take part like any other pair (unlike
  *   sage2ov_mates_supports).  Walk a's list from its start with run = the running sum of distPrevious; stop at the first entry with run > maximumUpperBoundOfInsert
@@ -633,8 +633,95 @@ int sage2ov_extend_merges_count(const sage2ov_ctx* ctx, uint64_t* n);
 int sage2ov_extend_merges_export(const sage2ov_ctx* ctx, sage2ov_merge* out, uint64_t cap);
 int sage2ov_extend_stats_get(const sage2ov_ctx* ctx, sage2ov_extend_stats* out);
 /* P.graph6: saveOverlapGraphInFile of the graph as it now is.  sage2ov_graph5_save's text, except that after a merge line 1 and line 2 stay what sage2ov_graph5_save
- * would have written before the first merge (the reference's genomeSize and numberOfReads do not change in step 6); on a graph without a merge it is an alias. */
+ * would have written before the first merge (the reference's genomeSize and numberOfReads do not change in step 6); on a graph without a merge it is an alias.
+ * It serves after sage2ov_graph_join_pairs and the scaffold rounds too: the resident graph with the same two header lines (the reference has no file for that state). */
 int sage2ov_graph6_save(sage2ov_ctx* ctx, const char* path);
+
+/* ---- step 7, ScaffoldMaker::makeScaffolds (matePair/scaffolding.cpp:31-98): the rounds of mergeFinal (:774-967) and mergeFinalSmall (:969-) -- the sweep of
+ * sage2ov_links above, the selection of mergeAccordingToSupport (:488-626) / mergeAccordingToSupport2 (:631-769) and mergeDisconnectedEdges (:281-482) applied on the
+ * device to the resident step-4 graph.  All citations without a file are matePair/scaffolding.cpp.
+ *   OVERLAP(s1, s2, L1, L2) (stringOverlapSize, overlapGraph.cpp:884-907): the smallest i in [0, L1 - 10) with L2 - i >= 0 for which the number of j in [0, L2 - i) with
+ *   s1[i + j] != s2[j] is at most (L2 - i) / 10 + 1 (the early break of :895 does not change that); -1 when there is none.  A position i + j >= L1 is a mismatch: the
+ *   reference reads past its string there, so equality with it is claimed for L2 <= L1 only.
+ *   JOIN(e1, e2, gap), e1 and e2 alive halves of different pairs, both with a list, sharing a node or not (mergeDisconnectedEdges; nothing is refused, the type is
+ *   never -1): type = 0 / 1 / 2 / 3 for (e1's type in {0, 1}, e2's in {0, 2}) / ({0, 1}, {1, 3}) / ({2, 3}, {0, 2}) / ({2, 3}, {1, 3}) (:290-297).  The new edge e1.from ->
+ *   e2.to has flow 1.0 on both halves and two lists made each on its own, LIST(e1, e2, gap) for the forward half and LIST(e2.twin, e1.twin, gap) for the twin, each with
+ *   its own length (getListOfReadsInDisconnectedEdges, overlapGraph.cpp:789-882).  LIST(x, y, gap): node1 = x.to spelled forward iff x's type is 1 or 3, node2 = y.from
+ *   spelled forward iff y's type is 2 or 3 (else the reverse complement), L1 and L2 their read lengths, P = distNext of x's last entry, Q = distPrevious of y's first.
+ *     node1 == node2: x's entries, {node1, orientation = spelled forward, flag 0, distPrevious P, distNext Q}, y's entries; length x.len + y.len.  (The reference
+ *     leaves the flag of the entries it inserts uninitialised; HERE it is 0.)
+ *     otherwise: x's entries, {node1, .., P, D1}, {node2, .., D2, Q}, y's entries; length x.len + y.len + D1, with o = OVERLAP(spelling of node1, spelling of node2, L1, L2):
+ *       o > 0: D1 = D2 = o.   o == 0 and o == -1 alike (:837 tests len > 0): gap < 0: D1 = L1, D2 = L2 (concatenated); gap >= 0: D1 = gap + L1, D2 = gap + L2 (N's).
+ *     The entry's distances are 11-bit fields (overlapGraph.h:20-21): D1, D2 above 2047 wrap in the entry, in the reference and here alike; the length takes D1 whole.
+ *   Then for e1 and for e2: own flow <= 1.0 (0 included): both halves are deleted; else both halves lose 1.0, each its own float (:301-386).
+ *   The new halves go to the end of the half-edge pool, forward half first, in batch order.
+ *   A ROUND (high, flag 1 or 2, small): ROWS = for every LINK(a, b) of the table above that passes SAGE2OV_LINKS_FINAL (small: SAGE2OV_LINKS_SMALL) and has a < b as
+ *   half-edge pool indices: {edge_1 = a's twin, edge_2 = b, support, gap}, in the table's export order.  SEARCH maps (edge_1.from ^ edge_1.to, edge_2.from ^ edge_2.to) to
+ *   the support of the first row with the largest support of that key (:904-911); every row is filed under its four end nodes (:913-916).  The rows are ordered by
+ *   support descending, then edge_1.len + edge_2.len descending (:252-275).  For each row in order: SKIPPED when its key is not in SEARCH (:504-506); BELOW when its
+ *   support < high (no break, :508); else with FEASIBLE(p) = the pairs that share a row of the unfiltered table (either direction, any halves) with pair p at the
+ *   start of the round, less the SPENT pairs, and nothing at all when p is spent: count2 = the q in FEASIBLE(pair(edge_1)) with SEARCH[x(edge_1), x(q)], else SEARCH[x(q),
+ *   x(edge_1)], else 0, >= high -- leaving out q == pair(edge_2) when edge_2 is E of its pair (the reference compares the pointer the read-to-edge table holds, :565);
+ *   count1 likewise over FEASIBLE(pair(edge_2)) with SEARCH[x(q), x(edge_2)], else SEARCH[x(edge_2), x(q)], leaving out pair(edge_1) when edge_1 is E; CYCLE when one q
+ *   counts on both sides (:580-600).  count1, count2 <= 1 (flag 2: <= 2) and no cycle: JOIN(edge_1, edge_2, gap), both pairs become SPENT, and every row filed under
+ *   edge_1.to leaves SEARCH (:607-614); otherwise the row is a CYCLE or BLOCKED.
+ *   THE LOOPS (:31-98) with coverage = (float)((reads * averageReadLength) / genomeSize) (an integer quotient), T(f) = (int)ceilf((f * coverage) * (100.0 /
+ *   averageReadLength)): loop 1: rounds of flag 1 at T(0.10), from iteration 6 on at T(0.05), until a round merges nothing at high == T(0.05); loop 2: the same with
+ *   flag 2; loop 3: flag 1 at high 2 until a round merges nothing; loop 4: flag 1 at high 1; loop 5: flag 2, small, at high 1.
+ * WHAT THE CONTRACT SETTLES: (a) the reference evaluates (a, b) only when a's Edge object lies at or below b's in memory (:828, :1023); LINK(a, b) and LINK(b, a) propose the
+ * same join (b.twin . a is the twin of a.twin . b) with possibly different support and gap.  HERE the row of {a, b} is LINK(a, b) with a < b as pool indices and no row
+ * comes from the other direction, even when only that one has support; on a freshly loaded graph this is what malloc order gives the reference.  (b) Ties of the sort
+ * (open in the reference's quicksort) keep the table's export order.  (c) The reference takes getListOfFeasibleEdges (:148-234) from the read-to-edge table as the
+ * merges of the round have changed it.  After a join the reads of both operands lie on the new edge alone (operand deleted) or on two edges (operand kept): unique
+ * on no operand.  HERE an operand pair of an earlier join of the round is SPENT; a new edge is feasible but has no SEARCH entry of its own and is left out (an XOR
+ * collision could give it one in the reference).  Feasible pairs without any row of the unfiltered table cannot reach SEARCH except through such a collision and
+ * are left out too.  (d) A row that names a half an earlier join of the round deleted is skipped (the reference reads the freed Edge, :502); the erase key is the node
+ * edge_1.to as read before the join (:607 reads it after, from an Edge the join may have freed: a join that deletes edge_1 while other rows filed under that node are
+ * still in SEARCH is outside the reference too); the round is marked outside_reference from such a row or join on.  (e) A kept operand (flow above 1) may be named
+ * again by a later row: the batch so far is applied first (`batches`).
+ * The selection is a serial pass on the host over the exported table and the half-edge fields; the joins of a round go to the device as a batch and no read list
+ * is downloaded.  A join drops the read-to-edge table, supports, links, contigs and step 5's network; the insert estimate stands, as for sage2ov_extend_round. */
+typedef struct sage2ov_join {          /* one join of the last scaffold round, 48 bytes */
+    uint32_t from, to;                 /* the new edge's ends (edge_1.from, edge_2.to) */
+    uint32_t support; int32_t gap;
+    uint32_t pair_first, pair_second;  /* ordinals of edge_1's and edge_2's record pairs in sage2ov_graph4_save's order BEFORE the round (the rows are older than the edges a round makes) */
+    uint32_t pair_new;                 /* ordinal of the new pair AFTER the round */
+    int32_t  overlap_forward, overlap_twin;      /* OVERLAP of the forward and of the twin list; -2: equal end nodes, no search */
+    uint8_t  type, first_deleted, second_deleted;
+    uint8_t  how_forward, how_twin;    /* SAGE2OV_JOIN_* */
+    uint8_t  pad[7];
+} sage2ov_join;
+#define SAGE2OV_JOIN_EQUAL 0           /* node1 == node2: one entry */
+#define SAGE2OV_JOIN_OVERLAP 1         /* OVERLAP > 0 */
+#define SAGE2OV_JOIN_CONCAT 2          /* no overlap, gap < 0 */
+#define SAGE2OV_JOIN_GAPPED 3          /* no overlap, gap >= 0 */
+typedef struct sage2ov_scaffold_counts {
+    uint64_t rows, below_threshold, skipped, blocked, cycles, merged, batches;
+    uint64_t overlaps, concatenated, gapped;       /* lists (two per join) by SAGE2OV_JOIN_*; the rest have equal end nodes */
+    uint64_t outside_reference;        /* last: 1 when (d) applied -- a row named a deleted half, or a join deleted edge_1 while other rows filed under its node were in
+                                          SEARCH --, else 0; total: the number of such rounds */
+    uint64_t entries_copied, pairs_deleted;
+    double   sweep_ms, select_ms, overlap_ms, lists_ms, commit_ms;      /* HIP events; select_ms: host wall time */
+} sage2ov_scaffold_counts;             /* 144 bytes */
+typedef struct sage2ov_scaffold_stats { uint64_t rounds, reserved; sage2ov_scaffold_counts last, total; } sage2ov_scaffold_stats;      /* 304 bytes; total: since the graph was made or loaded */
+/* the primitive: JOIN for a batch.  Operands as for sage2ov_graph_merge_pairs ((pair ordinal, reversed) in sage2ov_graph4_save's order); gap[i] as a row carries it.
+ * overlap (may be NULL): 2 n values, OVERLAP of the forward list and of the twin list of join i (-2: equal end nodes); how (may be NULL): 2 n values SAGE2OV_JOIN_*.
+ * New pairs are created in batch order.  SAGE2OV_ERR_ARG, nothing changed: an ordinal out of range, a pair named twice in the batch (e1 and e2 of one pair included),
+ * an operand without a list, a null array, no step-4 graph, no read store.  SAGE2OV_ERR_LIMIT, nothing changed: a length beyond 32 bits, half-edges or list entries
+ * beyond the pools' limits.  SAGE2OV_ERR_DEVICE on a device-less context.  The P.graph6 header is held as for sage2ov_graph_merge_pairs.  Not sharded. */
+int sage2ov_graph_join_pairs(sage2ov_ctx* ctx, const uint32_t* pair_first, const uint8_t* first_reversed, const uint32_t* pair_second, const uint8_t* second_reversed,
+                             const int32_t* gap, uint64_t n, int32_t* overlap, uint8_t* how);
+/* high of THE LOOPS: loop 1..5, iteration from 1.  Host only.  genome_size or average_read_length 0, iteration 0, another loop: SAGE2OV_ERR_ARG. */
+int sage2ov_scaffold_threshold(uint64_t reads, uint64_t average_read_length, uint64_t genome_size, uint32_t loop, uint32_t iteration, int* high);
+/* one round; flag 1 or 2 (else SAGE2OV_ERR_ARG); small != 0: mergeFinalSmall's filter; *merged (may be NULL) = its joins */
+int sage2ov_scaffold_round(sage2ov_ctx* ctx, int high, int flag, int small, uint64_t* merged);
+/* the five loops; *rounds counts every round, the empty ones that end a loop too.  genome_size 0, reads and average read length: as for sage2ov_extend_by_supports.
+ * After 10 000 rounds: SAGE2OV_ERR_INTERNAL. */
+int sage2ov_scaffold(sage2ov_ctx* ctx, uint64_t genome_size, uint64_t* rounds, uint64_t* merged);
+/* the joins of the last round in selection order; cap below their number: SAGE2OV_ERR_ARG, nothing written */
+int sage2ov_scaffold_merges_count(const sage2ov_ctx* ctx, uint64_t* n);
+int sage2ov_scaffold_merges_export(const sage2ov_ctx* ctx, sage2ov_join* out, uint64_t cap);
+int sage2ov_scaffold_stats_get(const sage2ov_ctx* ctx, sage2ov_scaffold_stats* out);
 
 /* diagnostic: table census {occupied, inline, claimed-but-unfilled, zero-tag, entries in short CSR buckets} */
 int sage2ov_debug_table(sage2ov_ctx* ctx, uint64_t* out5);

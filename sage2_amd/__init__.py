@@ -99,6 +99,24 @@ class ExtendStats(C.Structure):
     _fields_ = [("rounds", C.c_uint64), ("reserved", C.c_uint64), ("last", ExtendCounts), ("total", ExtendCounts)]
 
 
+# sage2ov_join (48 bytes): one join of the last round of scaffold_round
+JOIN_DTYPE = np.dtype([("from", np.uint32), ("to", np.uint32), ("support", np.uint32), ("gap", np.int32), ("pair_first", np.uint32), ("pair_second", np.uint32),
+                       ("pair_new", np.uint32), ("overlap_forward", np.int32), ("overlap_twin", np.int32), ("type", np.uint8), ("first_deleted", np.uint8),
+                       ("second_deleted", np.uint8), ("how_forward", np.uint8), ("how_twin", np.uint8), ("pad", np.uint8, (7,))])
+JOIN_EQUAL, JOIN_OVERLAP, JOIN_CONCAT, JOIN_GAPPED = 0, 1, 2, 3
+
+
+class ScaffoldCounts(C.Structure):
+    _fields_ = [("rows", C.c_uint64), ("below_threshold", C.c_uint64), ("skipped", C.c_uint64), ("blocked", C.c_uint64), ("cycles", C.c_uint64), ("merged", C.c_uint64),
+                ("batches", C.c_uint64), ("overlaps", C.c_uint64), ("concatenated", C.c_uint64), ("gapped", C.c_uint64), ("outside_reference", C.c_uint64),
+                ("entries_copied", C.c_uint64), ("pairs_deleted", C.c_uint64),
+                ("sweep_ms", C.c_double), ("select_ms", C.c_double), ("overlap_ms", C.c_double), ("lists_ms", C.c_double), ("commit_ms", C.c_double)]
+
+
+class ScaffoldStats(C.Structure):
+    _fields_ = [("rounds", C.c_uint64), ("reserved", C.c_uint64), ("last", ScaffoldCounts), ("total", ScaffoldCounts)]
+
+
 # sage2ov_contig (48 bytes): one row of the contig table
 CONTIG_DTYPE = np.dtype([("from", np.uint32), ("to", np.uint32), ("pair", np.uint32), ("edge_length", np.uint32), ("string_length", np.uint32), ("contig_length", np.uint32),
                          ("start", np.uint32), ("gap_count", np.uint32), ("n_count", np.uint32), ("flow", np.float32), ("type", np.uint8), ("pad", np.uint8, (7,))])
@@ -261,6 +279,15 @@ def extend_threshold(reads, average_read_length, genome_size, iteration=1) -> in
     rc = lib().sage2ov_extend_threshold(C.c_uint64(reads), C.c_uint64(average_read_length), C.c_uint64(genome_size), C.c_uint32(iteration), C.byref(out))
     if rc:
         raise Sage2ovError(rc, "extend_threshold")
+    return int(out.value)
+
+
+def scaffold_threshold(reads, average_read_length, genome_size, loop, iteration=1) -> int:
+    """highTh of ScaffoldMaker::makeScaffolds (scaffolding.cpp:38-94) in the given iteration of loop 1..5, on the host: no context, no GPU"""
+    out = C.c_int(0)
+    rc = lib().sage2ov_scaffold_threshold(C.c_uint64(reads), C.c_uint64(average_read_length), C.c_uint64(genome_size), C.c_uint32(loop), C.c_uint32(iteration), C.byref(out))
+    if rc:
+        raise Sage2ovError(rc, "scaffold_threshold")
     return int(out.value)
 
 
@@ -556,6 +583,47 @@ class Context:
 
     def graph6_save(self, path):
         self._chk(lib().sage2ov_graph6_save(self._h, os.fsencode(path)))
+
+    # ---- step 7, ScaffoldMaker::makeScaffolds (scaffolding.cpp:31-98): joins of edges that share no node, by the links below
+    def join_pairs(self, first, second, gap):
+        """mergeDisconnectedEdges for a batch of edge-disjoint joins.  first, second: per join (pair ordinal in graph4_save's order, reversed), as for merge_pairs;
+        gap: one int per join.  Returns (overlap, how): per join the (forward list, twin list) values of stringOverlapSize (-2: equal end nodes) and of JOIN_*."""
+        a = np.asarray(first, dtype=np.int64).reshape(-1, 2); b = np.asarray(second, dtype=np.int64).reshape(-1, 2); g = np.ascontiguousarray(gap, dtype=np.int32).reshape(-1)
+        if not len(a) == len(b) == len(g):
+            raise ValueError("one first operand, one second operand and one gap per join")
+        if len(a) and (a.min() < 0 or b.min() < 0 or max(a[:, 0].max(), b[:, 0].max()) >= 1 << 32):
+            raise ValueError("pair ordinals are uint32")
+        pa = np.ascontiguousarray(a[:, 0], dtype=np.uint32); ra = np.ascontiguousarray(a[:, 1] != 0, dtype=np.uint8)
+        pb = np.ascontiguousarray(b[:, 0], dtype=np.uint32); rb = np.ascontiguousarray(b[:, 1] != 0, dtype=np.uint8)
+        ov = np.zeros((len(a), 2), dtype=np.int32); how = np.zeros((len(a), 2), dtype=np.uint8)
+        self._chk(lib().sage2ov_graph_join_pairs(self._h, C.c_void_p(pa.ctypes.data), C.c_void_p(ra.ctypes.data), C.c_void_p(pb.ctypes.data), C.c_void_p(rb.ctypes.data),
+                                                 C.c_void_p(g.ctypes.data), C.c_uint64(len(a)), C.c_void_p(ov.ctypes.data), C.c_void_p(how.ctypes.data)))
+        return ov, how
+
+    def scaffold_round(self, high, flag=1, small=False) -> int:
+        """one mergeFinal(k, high, flag) (small: mergeFinalSmall): sweep, selection, joins; returns the number of joins"""
+        n = C.c_uint64(0)
+        self._chk(lib().sage2ov_scaffold_round(self._h, C.c_int(high), C.c_int(flag), C.c_int(1 if small else 0), C.byref(n)))
+        return int(n.value)
+
+    def scaffold(self, genome_size=0):
+        """the five loops of makeScaffolds -> (rounds, joins)"""
+        r, m = C.c_uint64(0), C.c_uint64(0)
+        self._chk(lib().sage2ov_scaffold(self._h, C.c_uint64(genome_size), C.byref(r), C.byref(m)))
+        return int(r.value), int(m.value)
+
+    def scaffold_merges(self) -> np.ndarray:
+        """the joins of the last round (JOIN_DTYPE) in selection order"""
+        n = C.c_uint64(0)
+        self._chk(lib().sage2ov_scaffold_merges_count(self._h, C.byref(n)))
+        out = np.zeros(n.value, dtype=JOIN_DTYPE)
+        self._chk(lib().sage2ov_scaffold_merges_export(self._h, C.c_void_p(out.ctypes.data), C.c_uint64(n.value)))
+        return out
+
+    def scaffold_stats(self) -> ScaffoldStats:
+        s = ScaffoldStats()
+        self._chk(lib().sage2ov_scaffold_stats_get(self._h, C.byref(s)))
+        return s
 
     # ---- the sweep that opens ScaffoldMaker::mergeFinal / mergeFinalSmall (scaffolding.cpp:786-935, :981-1130): support and gap of half-edge pairs linked by mates
     def links(self, mode=0, min_support=1) -> np.ndarray:

@@ -135,6 +135,14 @@ public:
         std::vector<sage2ov_link> out(n); ctx().check(sage2ov_links_export(ctx().get(), mode, minSupport, out.data(), n));
         return out;
     }
+    // ScaffoldMaker::makeScaffolds (scaffolding.cpp:31-98) on the resident graph: the five loops, or one mergeFinal / mergeFinalSmall round; the joins of the last round
+    std::pair<uint64_t, uint64_t> makeScaffolds(uint64_t genomeSize = 0) { uint64_t r = 0, m = 0; ctx().check(sage2ov_scaffold(ctx().get(), genomeSize, &r, &m)); table_ = false; return {r, m}; }
+    uint64_t mergeFinal(int highTh, int flag, bool small = false) { uint64_t m = 0; ctx().check(sage2ov_scaffold_round(ctx().get(), highTh, flag, small ? 1 : 0, &m)); table_ = false; return m; }
+    std::vector<sage2ov_join> scaffoldJoins() {
+        uint64_t n = 0; ctx().check(sage2ov_scaffold_merges_count(ctx().get(), &n));
+        std::vector<sage2ov_join> out(n); ctx().check(sage2ov_scaffold_merges_export(ctx().get(), out.data(), n));
+        return out;
+    }
     ReadLoader* loaderObj;
 private:
     Context& ctx() const { return loaderObj->context(); }

@@ -37,14 +37,16 @@ static void printListOfArgs() {
             "\t--flowNetwork\t\tstep 5 up to its solver: estimate the genome size and write <outputDir>input.cs2 (after step 4, or with -m 5 from <inputPrefix>.graph4)\n"
             "\t--flowSolution <string>\tstep 5 after its solver: apply this output.cs2 to the flows and write <prefix>.graph5\n"
             "\t--extend\t\twith -m 6: load <inputPrefix>.graph5, map the mate pairs of -f|-l, estimate the insert sizes, merge contigs by mate-pair\n"
-            "\t\t\tsupport until a round merges nothing (the first loop of extendContigs) and write <prefix>.graph6 [--genomeSize: the estimate on the loaded graph]\n\t-h|--help\n\n";
+            "\t\t\tsupport until a round merges nothing (the first loop of extendContigs) and write <prefix>.graph6 [--genomeSize: the estimate on the loaded graph]\n"
+            "\t--scaffold\t\twith -m 7: load <inputPrefix>.graph6, map the mate pairs of -f|-l, estimate the insert sizes, join contigs that share no node by\n"
+            "\t\t\tmate-pair links (the five loops of makeScaffolds) and write <prefix>_scaffold.fasta; with -m 6 --extend: go on from the merged graph, no new estimate\n\t-h|--help\n\n";
 }
 static string trimBack(string s, const string& pat) { size_t e = s.find_last_not_of(pat); return e == string::npos ? "" : s.substr(0, e + 1); }
 static double now() { return chrono::duration<double>(chrono::steady_clock::now().time_since_epoch()).count(); }
 
 int main(int argc, char* argv[]) {
     const double tMain = now(); const bool timing = getenv("SAGE2OV_TIMING") != nullptr;
-    int minStep = 1, maxStep = 3, gpu = 0, gpus = 1, failRank = -1; bool shareGpu = false, forceMulti = false; unsigned minOverlap = 0; bool contigs = false, extend = false, flowNetwork = false, genomeSizeGiven = false, maxGiven = false; string flowSolution; unsigned long long genomeSize = 0; bool saveAll = false, debugging = false, fFlag = false, lFlag = false;
+    int minStep = 1, maxStep = 3, gpu = 0, gpus = 1, failRank = -1; bool shareGpu = false, forceMulti = false; unsigned minOverlap = 0; bool contigs = false, extend = false, scaffold = false, flowNetwork = false, genomeSizeGiven = false, maxGiven = false; string flowSolution; unsigned long long genomeSize = 0; bool saveAll = false, debugging = false, fFlag = false, lFlag = false;
     string fileInput, listInput, outputDir, prefixName = "untitled", inputPrefix;
     static struct option opts[] = {{"help", no_argument, 0, 'h'}, {"fileInput", required_argument, 0, 'f'}, {"minOverlap", required_argument, 0, 'k'},
         {"listInput", required_argument, 0, 'l'}, {"outputDir", required_argument, 0, 'o'}, {"prefix", required_argument, 0, 'p'},
@@ -52,7 +54,7 @@ int main(int argc, char* argv[]) {
         {"saveAll", no_argument, 0, 's'}, {"debug", no_argument, 0, 'd'}, {"gpu", required_argument, 0, 'g'}, {"gpus", required_argument, 0, 'G'},
         {"share-gpu", no_argument, 0, 1001},      // rehearsal: all ranks on device `gpu`, exchanges by device copies instead of RCCL (a box with fewer GPUs than ranks)
         {"fail-rank", required_argument, 0, 1003},  // tests: this rank of a multi-GPU run fails before its first step (the run must end non-zero, not hang)
-        {"contigs", no_argument, 0, 1004}, {"genomeSize", required_argument, 0, 1005}, {"flowNetwork", no_argument, 0, 1006}, {"flowSolution", required_argument, 0, 1007}, {"extend", no_argument, 0, 1008},
+        {"contigs", no_argument, 0, 1004}, {"genomeSize", required_argument, 0, 1005}, {"flowNetwork", no_argument, 0, 1006}, {"flowSolution", required_argument, 0, 1007}, {"extend", no_argument, 0, 1008}, {"scaffold", no_argument, 0, 1009},
         {"force-multi", no_argument, 0, 1002},    // the multi-GPU code path (RCCL communicator, the four exchanges) even with one GPU
         {0, 0, 0, 0}};
     int c, oi = 0;
@@ -79,6 +81,7 @@ int main(int argc, char* argv[]) {
             case 1006: flowNetwork = true; break;
             case 1007: flowSolution = optarg; break;
             case 1008: extend = true; break;
+            case 1009: scaffold = true; break;
             case '?': cout << "\n"; exit(0);
             default: cout << "[ERROR] Wrong command line arguments!\n\n"; exit(0);
         }
@@ -89,14 +92,15 @@ int main(int argc, char* argv[]) {
     bool allSet = true;                                                                     // main.cpp:498-521
     if (fileInput == "" && listInput == "" && minStep <= 1) { cout << "[ERROR] One of the options -f|--fileInput or -l|--listInput is required.\n"; allSet = false; }
     if (minOverlap == 0) { cout << "[ERROR] Option -k|--minOverlap is required.\n"; allSet = false; }
-    if (extend && !maxGiven && maxStep < minStep) maxStep = minStep;                        // (`-m 6 --extend` needs no -M)
+    if ((extend || scaffold) && !maxGiven && maxStep < minStep) maxStep = minStep;           // (`-m 6 --extend` and `-m 7 --scaffold` need no -M)
     if (maxStep < minStep) { cout << "[ERROR] maxStep should not be smaller than minStep!\n\n"; allSet = false; }
     if (inputPrefix == "") inputPrefix = prefixName;
     if (!allSet) { cout << "\n"; printUsage(); cout << "(For more information run sage2ov -h)\n\n"; exit(0); }
     if (step5 && maxStep < 4) { cout << "[ERROR] --flowNetwork and --flowSolution need the graph after step 4: run with -M 4 (or -m 5 on the files of such a run).\n"; exit(0); }
     if (minStep > 5 && step5) { cout << "[ERROR] --flowNetwork and --flowSolution work on the graph after step 4 (-m 5 at the most).\n"; exit(0); }
     if (extend && (minStep != 6 || (fileInput == "" && listInput == ""))) { cout << "[ERROR] --extend works on <inputPrefix>.graph5 (-m 6) and needs the mate pairs (-f or -l).\n"; exit(0); }
-    if (minStep > 4 && !contigs && !step5 && !extend) { cout << "[ERROR] sage2ov implements steps 1-4; continue with: SAGE2 -m " << minStep << " -i " << inputPrefix << " ...\n"; exit(0); }
+    if (scaffold && (!(minStep == 7 || (minStep == 6 && extend)) || (fileInput == "" && listInput == ""))) { cout << "[ERROR] --scaffold works on <inputPrefix>.graph6 (-m 7), or after --extend (-m 6), and needs the mate pairs (-f or -l).\n"; exit(0); }
+    if (minStep > 4 && !contigs && !step5 && !extend && !scaffold) { cout << "[ERROR] sage2ov implements steps 1-4; continue with: SAGE2 -m " << minStep << " -i " << inputPrefix << " ...\n"; exit(0); }
     (void)debugging;
     if (outputDir != "") { string cmd = "mkdir -p " + outputDir; if (system(cmd.c_str())) {} }     // utils.cpp:45
     ofstream logStream((outputDir + prefixName + ".log").c_str());
@@ -192,6 +196,27 @@ int main(int argc, char* argv[]) {
                 logStream << "\t" << prefixName << ".graph6 written\n\tFirst loop of step 6 in " << now() - t6 << " sec.\n";
             }
             if (contigs) writeContigs(graphObj);
+            if (scaffold) {                                                                   // main.cpp:263-290, makeScaffolds (scaffolding.cpp:31-98)
+                double t7 = now();
+                logStream << "STEP 7: merge contigs to get scaffolds\n";
+                if (!extend) {                                                                // (after --extend the mates and the estimate of step 6 stand, main.cpp:270)
+                    if (listInput != "") ctx.check(sage2ov_mates_add_list(ctx.get(), listInput.c_str()));
+                    else ctx.check(sage2ov_mates_add_file(ctx.get(), fileInput.c_str(), nullptr, 1));
+                    ctx.check(sage2ov_mates_estimate(ctx.get()));
+                }
+                logStream << "\nIn function makeScaffolds().\n";
+                uint64_t rounds = 0, merged = 0;
+                const int rc = sage2ov_scaffold(ctx.get(), genomeSizeGiven ? genomeSize : 0, &rounds, &merged);
+                sage2ov_scaffold_stats ss{}; ctx.check(sage2ov_scaffold_stats_get(ctx.get(), &ss));
+                logStream << "\tRounds of mergeFinal: " << rounds << " (" << ss.total.rows << " rows, " << ss.total.below_threshold << " below the threshold, " << ss.total.skipped << " skipped, "
+                          << ss.total.blocked << " blocked, " << ss.total.cycles << " cycles; lists joined by overlap " << ss.total.overlaps << ", concatenated " << ss.total.concatenated
+                          << ", with a gap " << ss.total.gapped << ")\n";
+                ctx.check(rc);
+                logStream << "\nTotal number of merged scaffolds: " << merged << "\n";
+                double tw = now();
+                auto cs = graphObj.printGraph(outputDir + prefixName + "_scaffold", true, genomeSize);
+                logStream << "\t" << prefixName << "_scaffold.fasta written in " << now() - tw << " sec.\n\t  Number of Scaffolds: " << cs.contigs << " (" << cs.written << " in the file)\n\tStep 7 in " << now() - t7 << " sec.\n";
+            }
         } else if (minStep == 4) {                                                            // main.cpp:141-148
             OverlapGraph graphObj(&loaderObj);
             graphObj.loadOverlapGraphFromFile(outputDir + inputPrefix + ".graph3");

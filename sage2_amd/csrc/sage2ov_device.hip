@@ -238,6 +238,7 @@ static void mem_sample(Device* d) { size_t fr = 0, to = 0; if (hipMemGetInfo(&fr
 #include "kernels_support.inc"
 #include "kernels_links.inc"
 #include "kernels_contig.inc"
+#include "kernels_scaffold.inc"
 #include "kernels_copycount.inc"
 
 // =============================================================================================
@@ -2400,6 +2401,36 @@ int dev_flow_set(Device* d, const float* flow, uint64_t n, std::string& err) {
     return 0;
 }
 
+// room for `created` new pairs and `total` new list entries.  The pools grow as step 4's list pool does: a new block, the old content copied
+static int s4_pools_grow(Device* d, S4Keep& K, u64 created, u64 total, std::string& err) {
+    S4Mem& mem = K.mem; S4Graph& g = K.g; hipStream_t sm = d->stream;
+    const u64 needH = (u64)K.nh + 2 * created;
+    if (needH > K.capH) {
+        const u64 want = std::min<u64>(std::max<u64>(needH, K.capH + K.capH / 2), (1ull << 32) - RS_TILE);
+        auto grow = [&](auto*& arr) -> int {
+            using T = std::remove_reference_t<decltype(*arr)>;
+            T* nw = mem.get<T>(want, err); if (!nw) return SAGE2OV_ERR_NOMEM;
+            if (K.nh && hipMemcpyAsync(nw, arr, (size_t)K.nh * sizeof(T), hipMemcpyDeviceToDevice, sm) != hipSuccess) { err = "graph pools: device copy failed"; return SAGE2OV_ERR_DEVICE; }
+            if (hipStreamSynchronize(sm) != hipSuccess) { err = "graph pools: device copy failed"; return SAGE2OV_ERR_DEVICE; }
+            mem.drop(arr); arr = nw; return 0;
+        };
+        int rc;
+        if ((rc = grow(g.from)) || (rc = grow(g.to)) || (rc = grow(g.len)) || (rc = grow(g.cnt)) || (rc = grow(g.off)) || (rc = grow(g.type)) || (rc = grow(g.alive))) return rc;
+        K.capH = want;
+    }
+    if (K.flow && needH > K.flowCap) {
+        float* nw = mem.get<float>(K.capH, err); if (!nw) return SAGE2OV_ERR_NOMEM;
+        if (K.nh) HIPCHK(hipMemcpyAsync(nw, K.flow, (size_t)K.nh * sizeof(float), hipMemcpyDeviceToDevice, sm));
+        HIPCHK(hipStreamSynchronize(sm)); mem.drop(K.flow); K.flow = nw; K.flowCap = K.capH;
+    }
+    if (K.listUsed + total > K.listCap) {
+        const u64 want = std::max<u64>(K.listUsed + total, K.listCap + K.listCap / 2);
+        u64* nl = mem.get<u64>(want, err); if (!nl) return SAGE2OV_ERR_NOMEM;
+        if (K.listUsed) HIPCHK(hipMemcpyAsync(nl, g.lists, K.listUsed * sizeof(u64), hipMemcpyDeviceToDevice, sm));
+        HIPCHK(hipStreamSynchronize(sm)); mem.drop(g.lists); g.lists = nl; K.listCap = want;
+    }
+    return 0;
+}
 // ---- mergeEdgesAndUpdate for a batch (kernels_merge.inc).  a[i], b[i]: the half-edges e1 and e2 of merge i, below K.nh, to[a] == from[b], no pair
 // named twice -- the caller has checked all of it, and the 11-bit limit of a simple operand's length.  out[i]: bit 0 merged, bit 1 e1's pair deleted, bit 2 e2's,
 // bits 4-5 the new type.  Everything made from the graph goes (as in dev_simplify_release), the graph itself stays.
@@ -2423,33 +2454,8 @@ int dev_merge_pairs(Device* d, const u32* a, const u32* b, uint64_t n, int typeO
     { const int rc = scan_u32(d, isNew, n, rank, partial, &created, err); if (rc) return rc; }
     HIPCHK(lap.stop(st->plan_ms));
     if (K.listUsed + total >= (1ull << 32) - RS_TILE) { err = "merge: read lists exceed 2^32 entries"; return SAGE2OV_ERR_LIMIT; }
-    // the pools grow as step 4's list pool does: a new block, the old content copied
     if (created) {
-        const u64 needH = (u64)K.nh + 2 * created;
-        if (needH > K.capH) {
-            const u64 want = std::min<u64>(std::max<u64>(needH, K.capH + K.capH / 2), (1ull << 32) - RS_TILE);
-            auto grow = [&](auto*& arr) -> int {
-                using T = std::remove_reference_t<decltype(*arr)>;
-                T* nw = mem.get<T>(want, err); if (!nw) return SAGE2OV_ERR_NOMEM;
-                if (K.nh && hipMemcpyAsync(nw, arr, (size_t)K.nh * sizeof(T), hipMemcpyDeviceToDevice, sm) != hipSuccess) { err = "merge: device copy failed"; return SAGE2OV_ERR_DEVICE; }
-                if (hipStreamSynchronize(sm) != hipSuccess) { err = "merge: device copy failed"; return SAGE2OV_ERR_DEVICE; }
-                mem.drop(arr); arr = nw; return 0;
-            };
-            int rc;
-            if ((rc = grow(g.from)) || (rc = grow(g.to)) || (rc = grow(g.len)) || (rc = grow(g.cnt)) || (rc = grow(g.off)) || (rc = grow(g.type)) || (rc = grow(g.alive))) return rc;
-            K.capH = want;
-        }
-        if (K.flow && needH > K.flowCap) {
-            float* nw = mem.get<float>(K.capH, err); if (!nw) return SAGE2OV_ERR_NOMEM;
-            if (K.nh) HIPCHK(hipMemcpyAsync(nw, K.flow, (size_t)K.nh * sizeof(float), hipMemcpyDeviceToDevice, sm));
-            HIPCHK(hipStreamSynchronize(sm)); mem.drop(K.flow); K.flow = nw; K.flowCap = K.capH;
-        }
-        if (K.listUsed + total > K.listCap) {
-            const u64 want = std::max<u64>(K.listUsed + total, K.listCap + K.listCap / 2);
-            u64* nl = mem.get<u64>(want, err); if (!nl) return SAGE2OV_ERR_NOMEM;
-            if (K.listUsed) HIPCHK(hipMemcpyAsync(nl, g.lists, K.listUsed * sizeof(u64), hipMemcpyDeviceToDevice, sm));
-            HIPCHK(hipStreamSynchronize(sm)); mem.drop(g.lists); g.lists = nl; K.listCap = want;
-        }
+        { const int rc = s4_pools_grow(d, K, created, total, err); if (rc) return rc; }
         dev_readmap_release(d); dev_contigs_release(d); dev_copycount_release(d);
         HIPCHK(lap.start());
         if (total) hipLaunchKernelGGL(k_mg_lists, dim3(grid_for(total, 256)), dim3(256), 0, sm, g, plan, lo, 2 * m, (u64)total, (u32)K.listUsed);
@@ -2469,6 +2475,65 @@ int dev_merge_pairs(Device* d, const u32* a, const u32* b, uint64_t n, int typeO
     }
     K.nh += (u32)(2 * created); K.listUsed += total;
     st->merged = created; st->entries_copied = total; st->half_edges = K.nh; st->list_entries = K.listUsed;
+    return 0;
+}
+
+// ---- mergeDisconnectedEdges for a batch (kernels_scaffold.inc).  a[i], b[i], gap[i]: the half-edges e1 and e2 and the gap of join i, below K.nh,
+// alive, both with a list, no pair named twice, lengths within 32 bits -- the caller has checked all of it.  Nothing is refused: join i makes pair K.nh / 2 + i.
+// out[i]: bit 0 e1's pair deleted, bit 1 e2's, bits 2-3 the new type, bits 4-5 and 6-7 how the forward and the twin list were joined (SC_EQUAL .. SC_GAPPED).
+// Flows that were all 0 (no array) become an array: the new edges have flow 1.0.  Everything made from the graph goes, the graph itself stays.
+static bool contig_reads(Device* d, CtReads& R);
+int dev_join_pairs(Device* d, const u32* a, const u32* b, const int32_t* gap, uint64_t n, uint8_t* out, int32_t* overlap, JoinStats* st, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    if (!d->s4keep) { err = "join: no step-4 graph on the device"; return SAGE2OV_ERR_ARG; }
+    CtReads Rd; if (!contig_reads(d, Rd)) { err = "join: no read store on the device"; return SAGE2OV_ERR_ARG; }
+    S4Keep& K = *(S4Keep*)d->s4keep; S4Mem& mem = K.mem; S4Graph& g = K.g; hipStream_t sm = d->stream;
+    *st = JoinStats();
+    if (!n) return 0;
+    if (n >= (1ull << 30) || (u64)K.nh + 2 * n >= (1ull << 32) - RS_TILE) { err = "join: more than 2^32 half-edges"; return SAGE2OV_ERR_LIMIT; }
+    DevTmp B; StreamLap lap(sm); HIPCHK(lap.create());
+    const u32 m = (u32)n;
+    u32* da = B.get<u32>(n); u32* db = B.get<u32>(n); int* dgap = B.get<int>(n); int* ov = B.get<int>(2 * n); ScPlan* plan = B.get<ScPlan>(n); u32* lens = B.get<u32>(2 * n); u32* lo = B.get<u32>(2 * n);
+    u64* partial = B.get<u64>(scan_partial_words(2 * n));
+    if (!da || !db || !dgap || !ov || !plan || !lens || !lo || !partial) { err = "join: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+    HIPCHK(lap.start());
+    HIPCHK(hipMemcpyAsync(da, a, n * sizeof(u32), hipMemcpyHostToDevice, sm)); HIPCHK(hipMemcpyAsync(db, b, n * sizeof(u32), hipMemcpyHostToDevice, sm));
+    HIPCHK(hipMemcpyAsync(dgap, gap, n * sizeof(int), hipMemcpyHostToDevice, sm));
+    hipLaunchKernelGGL(k_sc_overlap, dim3(2 * m), dim3(64), 0, sm, g, Rd, da, db, 2 * m, ov);
+    HIPCHK(hipGetLastError());
+    HIPCHK(lap.stop(st->overlap_ms));
+    HIPCHK(lap.start());
+    hipLaunchKernelGGL(k_sc_plan, dim3(grid_for(n, 256)), dim3(256), 0, sm, g, Rd, (const float*)K.flow, da, db, dgap, ov, m, plan, lens);
+    HIPCHK(hipGetLastError());
+    u64 total = 0;
+    { const int rc = scan_u32(d, lens, 2 * n, lo, partial, &total, err); if (rc) return rc; }
+    HIPCHK(lap.stop(st->plan_ms));
+    if (K.listUsed + total >= (1ull << 32) - RS_TILE) { err = "join: read lists exceed 2^32 entries"; return SAGE2OV_ERR_LIMIT; }
+    if (!K.flow) {                                                                     // (every flow was 0: the plan read them as 0; the new edges have 1.0)
+        float* f = mem.get<float>(std::max<u64>(K.capH, 1), err); if (!f) return SAGE2OV_ERR_NOMEM;
+        HIPCHK(hipMemsetAsync(f, 0, std::max<u64>(K.capH, 1) * sizeof(float), sm)); K.flow = f; K.flowCap = std::max<u64>(K.capH, 1);
+    }
+    { const int rc = s4_pools_grow(d, K, n, total, err); if (rc) return rc; }
+    dev_readmap_release(d); dev_contigs_release(d); dev_copycount_release(d);
+    HIPCHK(lap.start());
+    hipLaunchKernelGGL(k_sc_lists, dim3(grid_for(total, 256)), dim3(256), 0, sm, g, plan, lo, 2 * m, (u64)total, (u32)K.listUsed);
+    HIPCHK(hipGetLastError());
+    HIPCHK(lap.stop(st->lists_ms));
+    HIPCHK(lap.start());
+    hipLaunchKernelGGL(k_sc_commit, dim3(grid_for(n, 256)), dim3(256), 0, sm, g, K.flow, plan, lo, m, K.nh, (u32)K.listUsed);
+    HIPCHK(hipGetLastError());
+    HIPCHK(lap.stop(st->commit_ms));
+    std::vector<ScPlan> hp(n);
+    HIPCHK(hipMemcpy(hp.data(), plan, n * sizeof(ScPlan), hipMemcpyDeviceToHost));
+    if (overlap) HIPCHK(hipMemcpy(overlap, ov, 2 * n * sizeof(int), hipMemcpyDeviceToHost));
+    for (u64 i = 0; i < n; i++) {
+        const ScPlan& p = hp[i];
+        out[i] = (uint8_t)(p.del1 | (p.del2 << 1) | (p.type << 2) | (p.how[0] << 4) | (p.how[1] << 6));
+        st->pairs_deleted += (u64)p.del1 + p.del2;
+        for (int dI = 0; dI < 2; dI++) { st->overlaps += p.how[dI] == SC_OVERLAP; st->concatenated += p.how[dI] == SC_CONCAT; st->gapped += p.how[dI] == SC_GAPPED; }
+    }
+    K.nh += (u32)(2 * n); K.listUsed += total;
+    st->joined = n; st->entries_copied = total; st->half_edges = K.nh; st->list_entries = K.listUsed;
     return 0;
 }
 

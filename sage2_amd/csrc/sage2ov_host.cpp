@@ -139,7 +139,8 @@ struct sage2ov_ctx {
     // values of P.graph6 are those from before the first merge
     bool estimateHeld = false, hdrHeld = false; uint64_t hdrGenome = 0, hdrReads = 0;
     sage2ov_extend_stats xstats{}; std::vector<sage2ov_merge> xmerges;
-    void extend_forget() { estimateHeld = hdrHeld = false; hdrGenome = hdrReads = 0; xstats = sage2ov_extend_stats{}; xmerges.clear(); }
+    sage2ov_scaffold_stats scstats{}; std::vector<sage2ov_join> scjoins;      // the scaffold rounds (sage2ov_scaffold_*)
+    void extend_forget() { estimateHeld = hdrHeld = false; hdrGenome = hdrReads = 0; xstats = sage2ov_extend_stats{}; xmerges.clear(); scstats = sage2ov_scaffold_stats{}; scjoins.clear(); }
     void readmap_forget() { rmValid = estimated = false; extend_forget(); pairOrdinal.clear(); rmstats = sage2ov_readmap_stats{}; supports_forget(); links_forget(); contigs_forget(); copycount_forget(); }      // the graph or the read set goes
     void mates_forget(bool readSetGoes = true) {       // the read set goes: its ids mean nothing any more (the device drops its part in free_reads) -- or sage2ov_mates_clear
         if (readSetGoes) { readmap_forget(); readsGen++; } else estimated = estimateHeld = false;
@@ -2538,6 +2539,209 @@ int sage2ov_links_export(sage2ov_ctx* c, uint32_t mode, uint32_t min_support, sa
     return SAGE2OV_OK;
 }
 int sage2ov_link_stats_get(const sage2ov_ctx* c, sage2ov_link_stats* o) { if (!c || !o) return SAGE2OV_ERR_ARG; *o = c->lstats; return SAGE2OV_OK; }
+
+// ---- step 7: ScaffoldMaker::makeScaffolds (scaffolding.cpp:31-98, :281-482, :488-769); the semantics are stated in sage2ov.h
+namespace {
+static_assert(sizeof(sage2ov_join) == 48 && sizeof(sage2ov_scaffold_counts) == 144 && sizeof(sage2ov_scaffold_stats) == 304, "the records of the scaffold rounds");
+// a batch of internal half-edges through the device; afterwards everything made from the graph is stale, the estimate stands and the host copy of the fields is gone
+int join_apply(sage2ov_ctx* c, const std::vector<uint32_t>& a, const std::vector<uint32_t>& b, const std::vector<int32_t>& gap, std::vector<uint8_t>& out, std::vector<int32_t>& ov, JoinStats& s) {
+    { const int rc = header_hold(c); if (rc) return rc; }
+    out.assign(a.size(), 0); ov.assign(2 * a.size(), 0);
+    { const int rc = dev_join_pairs(c->device(), a.data(), b.data(), gap.data(), a.size(), out.data(), ov.data(), &s, c->err); if (rc) return rc; }
+    if (!s.joined) return SAGE2OV_OK;
+    const bool est = c->estimated;
+    c->rmValid = false; c->pairOrdinal.clear(); c->rmstats = sage2ov_readmap_stats{}; c->supports_forget(); c->links_forget(); c->contigs_forget(); c->copycount_forget();
+    c->estimateHeld = est;
+    SimplifiedGraph& g = c->g4;
+    g.downloaded = g.fields = false; g.lists.clear(); g.lists.shrink_to_fit();
+    g.n_half_edges = s.half_edges; g.pairs_alive += s.joined; g.pairs_alive -= std::min<uint64_t>(g.pairs_alive, s.pairs_deleted);
+    g.flow.assign(g.n_half_edges, 0.f);                                                // (flows that were all 0 are an array now: the new edges have 1.0)
+    return dev_flow_get(c->device(), g.flow.data(), g.flow.size(), c->err);
+}
+void sc_counts_add(sage2ov_scaffold_counts& t, const sage2ov_scaffold_counts& r) {
+    t.rows += r.rows; t.below_threshold += r.below_threshold; t.skipped += r.skipped; t.blocked += r.blocked; t.cycles += r.cycles; t.merged += r.merged; t.batches += r.batches;
+    t.overlaps += r.overlaps; t.concatenated += r.concatenated; t.gapped += r.gapped; t.outside_reference += r.outside_reference; t.entries_copied += r.entries_copied;
+    t.pairs_deleted += r.pairs_deleted; t.sweep_ms += r.sweep_ms; t.select_ms += r.select_ms; t.overlap_ms += r.overlap_ms; t.lists_ms += r.lists_ms; t.commit_ms += r.commit_ms;
+}
+// the checks of the two join entry points on internal half-edges: lengths within 32 bits (the longest read has 1018 bases)
+bool join_length_fits(const SimplifiedGraph& g, uint32_t a, uint32_t b, int32_t gap) {
+    const uint64_t add = (uint64_t)std::max<int32_t>(gap, 0) + 2048;
+    return (uint64_t)g.len[a] + g.len[b] + add < (1ull << 32) && (uint64_t)g.len[a ^ 1u] + g.len[b ^ 1u] + add < (1ull << 32);
+}
+}  // namespace
+int sage2ov_graph_join_pairs(sage2ov_ctx* c, const uint32_t* pf, const uint8_t* fr, const uint32_t* ps, const uint8_t* sr, const int32_t* gap, uint64_t n, int32_t* overlap, uint8_t* how) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    if (n && (!pf || !fr || !ps || !sr || !gap)) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_join_pairs: null argument");
+    { const int rc = readmap_check(c, "sage2ov_graph_join_pairs"); if (rc) return rc; }
+    if (n >= (1ull << 30)) return c->fail(SAGE2OV_ERR_LIMIT, "sage2ov_graph_join_pairs: more joins than there can be pairs");
+    { const int rc = dev_simplify_download(c->device(), c->g4, c->err, false); if (rc) return rc; }
+    const SimplifiedGraph& g = c->g4;
+    std::vector<uint32_t> first; g4_save_order(g, first);
+    std::vector<uint32_t> a(n), b(n); std::vector<int32_t> gp(n); std::vector<uint8_t> used(g.n_half_edges / 2 + 1, 0);
+    for (uint64_t i = 0; i < n; i++) {
+        if (pf[i] >= first.size() || ps[i] >= first.size()) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_join_pairs: a pair ordinal beyond the record pairs of the graph");
+        a[i] = first[pf[i]] ^ (fr[i] ? 1u : 0u); b[i] = first[ps[i]] ^ (sr[i] ? 1u : 0u); gp[i] = gap[i];
+        if ((a[i] >> 1) == (b[i] >> 1) || used[a[i] >> 1] || used[b[i] >> 1]) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_join_pairs: a record pair is named twice in the batch");
+        used[a[i] >> 1] = used[b[i] >> 1] = 1;
+        if (!g.cnt[a[i]] || !g.cnt[b[i]]) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_join_pairs: an operand without a read list (the reference joins composite edges only)");
+    }
+    for (uint64_t i = 0; i < n; i++) if (!join_length_fits(g, a[i], b[i], gp[i])) return c->fail(SAGE2OV_ERR_LIMIT, "sage2ov_graph_join_pairs: an edge length beyond 32 bits");
+    std::vector<uint8_t> out; std::vector<int32_t> ov; JoinStats s;
+    { const int rc = join_apply(c, a, b, gp, out, ov, s); if (rc) return rc; }
+    for (uint64_t i = 0; i < n; i++) {
+        if (overlap) { overlap[2 * i] = ov[2 * i]; overlap[2 * i + 1] = ov[2 * i + 1]; }
+        if (how) { how[2 * i] = (out[i] >> 4) & 3u; how[2 * i + 1] = (out[i] >> 6) & 3u; }
+    }
+    return SAGE2OV_OK;
+}
+int sage2ov_scaffold_threshold(uint64_t reads, uint64_t arl, uint64_t genomeSize, uint32_t loop, uint32_t iteration, int* high) {      // scaffolding.cpp:38-94
+    if (!high || !arl || !genomeSize || !iteration || loop < 1 || loop > 5) return SAGE2OV_ERR_ARG;
+    const float coverage = (reads * arl) / genomeSize;
+    if (loop <= 2) *high = (int)ceilf(((iteration > 5 ? 0.05 : 0.10) * coverage) * (100.0 / arl));
+    else *high = loop == 3 ? 2 : 1;
+    return SAGE2OV_OK;
+}
+int sage2ov_scaffold_round(sage2ov_ctx* c, int highTh, int flag, int small, uint64_t* merged) {                        // :774-967, :488-769
+    if (!c) return SAGE2OV_ERR_ARG;
+    if (flag != 1 && flag != 2) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_scaffold_round: flag is 1 or 2");
+    { const int rc = readmap_check(c, "sage2ov_scaffold_round"); if (rc) return rc; }
+    sage2ov_scaffold_counts R{};
+    const bool swept = !(c->linkValid && c->estimated && c->rmValid);
+    { const int rc = links_ensure(c, "sage2ov_scaffold_round"); if (rc) return rc; }
+    { const int rc = links_fetch(c); if (rc) return rc; }                             // (pair_ordinals and the half-edge fields come with it; no read list)
+    if (swept) R.sweep_ms = c->lstats.halves_ms + c->lstats.scan_ms + c->lstats.records_ms + c->lstats.sort_ms + c->lstats.reduce_ms;
+    const auto t0 = std::chrono::steady_clock::now();
+    const std::vector<uint32_t> ordBefore = c->pairOrdinal;
+    std::vector<uint32_t> from = c->g4.from, to = c->g4.to, len = c->g4.len; std::vector<uint8_t> type = c->g4.type, alive = c->g4.alive;
+    std::vector<float> flow = c->g4.flow; flow.resize(from.size(), 0.f);
+    uint32_t nh = (uint32_t)from.size();
+    std::vector<uint32_t> firstOf; g4_save_order(c->g4, firstOf);                      // ordinal -> the half that opens the record pair
+    auto isE = [&](uint32_t h) -> bool { return from[h] < to[h] || (from[h] == to[h] && (h & 1u)); };      // the half the read-to-edge table names; a loop: the higher index
+    // the rows by rule (a) in export order, FEASIBLE from the unfiltered table, SEARCH and the rows filed under their end nodes
+    struct Row { uint32_t e1, e2, sup; int32_t gap; uint64_t lenSum; };
+    std::vector<Row> rows; std::unordered_map<uint32_t, std::vector<uint32_t>> feasible;
+    const int thr = (int)ceilf((float)(100 * ((double)average_read_length(c) / 100.0)));
+    const uint32_t mode = small ? SAGE2OV_LINKS_SMALL : SAGE2OV_LINKS_FINAL;
+    for (uint64_t e = 0; e < c->links.size(); e++) {
+        const sage2ov_link& L = c->links[e]; if (!L.support) continue;
+        const uint32_t a = firstOf[L.pair_a] ^ L.second_a, b = firstOf[L.pair_b] ^ L.second_b;
+        auto& fa = feasible[a >> 1]; if (std::find(fa.begin(), fa.end(), b >> 1) == fa.end()) fa.push_back(b >> 1);
+        auto& fb = feasible[b >> 1]; if (std::find(fb.begin(), fb.end(), a >> 1) == fb.end()) fb.push_back(a >> 1);
+        if (a < b && link_passes(c, e, mode, thr)) rows.push_back(Row{a ^ 1u, b, L.support, L.gap, (uint64_t)len[a ^ 1u] + len[b]});
+    }
+    auto xk = [&](uint32_t h) -> uint64_t { return (uint64_t)(from[h] ^ to[h]); };
+    auto k2 = [&](uint64_t x, uint64_t y) -> uint64_t { return (x << 32) | y; };
+    std::unordered_map<uint64_t, uint32_t> search; std::unordered_multimap<uint32_t, uint64_t> filed;
+    for (const Row& r : rows) {
+        const uint64_t kk = k2(xk(r.e1), xk(r.e2));
+        auto it = search.find(kk);
+        if (it == search.end()) search[kk] = r.sup; else if (r.sup > it->second) it->second = r.sup;
+        for (uint32_t nd : {to[r.e1], from[r.e1], to[r.e2], from[r.e2]}) filed.insert({nd, kk});
+    }
+    std::stable_sort(rows.begin(), rows.end(), [](const Row& x, const Row& y) { return x.sup != y.sup ? x.sup > y.sup : x.lenSum > y.lenSum; });
+    R.rows = rows.size();
+    auto lookup = [&](uint64_t x, uint64_t y) -> int64_t { auto it = search.find(k2(x, y)); if (it == search.end()) it = search.find(k2(y, x)); return it == search.end() ? 0 : (int64_t)it->second; };
+    std::unordered_set<uint32_t> spent, usedPair;
+    std::vector<uint32_t> bA, bB; std::vector<int32_t> bG; std::vector<sage2ov_join> joins; std::vector<uint32_t> newHalf; size_t applied = 0;
+    double selectOut = 0;
+    auto flush = [&]() -> int {
+        if (bA.empty()) return SAGE2OV_OK;
+        const auto f0 = std::chrono::steady_clock::now();
+        std::vector<uint8_t> out; std::vector<int32_t> ov; JoinStats s;
+        { const int rc = join_apply(c, bA, bB, bG, out, ov, s); if (rc) return rc; }
+        if (s.half_edges != nh) return c->fail(SAGE2OV_ERR_INTERNAL, "sage2ov_scaffold_round: the device and the selection disagree on the half-edges");
+        for (size_t i = 0; i < bA.size(); i++) {
+            sage2ov_join& j = joins[applied + i];
+            j.overlap_forward = ov[2 * i]; j.overlap_twin = ov[2 * i + 1]; j.how_forward = (out[i] >> 4) & 3u; j.how_twin = (out[i] >> 6) & 3u;
+            if (j.type != ((out[i] >> 2) & 3u) || j.first_deleted != (out[i] & 1u) || j.second_deleted != ((out[i] >> 1) & 1u))
+                return c->fail(SAGE2OV_ERR_INTERNAL, "sage2ov_scaffold_round: the device and the selection disagree on a join");
+        }
+        applied += bA.size();
+        R.entries_copied += s.entries_copied; R.pairs_deleted += s.pairs_deleted; R.batches++; R.overlaps += s.overlaps; R.concatenated += s.concatenated; R.gapped += s.gapped;
+        R.overlap_ms += s.overlap_ms; R.lists_ms += s.lists_ms; R.commit_ms += s.plan_ms + s.commit_ms;
+        bA.clear(); bB.clear(); bG.clear(); usedPair.clear();
+        selectOut += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - f0).count();
+        return SAGE2OV_OK;
+    };
+    const uint64_t limit = flag == 1 ? 1 : 2;
+    static const std::vector<uint32_t> none;
+    for (const Row& r : rows) {
+        const uint32_t e1 = r.e1, e2 = r.e2;
+        if (!alive[e1] || !alive[e2]) { R.outside_reference = 1; R.skipped++; continue; }      // (d)
+        if (search.find(k2(xk(e1), xk(e2))) == search.end()) { R.skipped++; continue; }
+        if ((int64_t)r.sup < (int64_t)highTh) { R.below_threshold++; continue; }
+        const uint32_t p1 = e1 >> 1, p2 = e2 >> 1;
+        auto feas = [&](uint32_t p) -> const std::vector<uint32_t>& { if (spent.count(p)) return none; auto it = feasible.find(p); return it == feasible.end() ? none : it->second; };
+        uint64_t count1 = 0, count2 = 0; bool cycle = false; std::vector<uint32_t> side2;
+        for (uint32_t q : feas(p1)) {
+            if (spent.count(q) || (q == p2 && isE(e2))) continue;
+            if (lookup(xk(e1), xk(2 * q)) >= (int64_t)highTh) { count2++; side2.push_back(q); }
+        }
+        for (uint32_t q : feas(p2)) {
+            if (spent.count(q) || (q == p1 && isE(e1))) continue;
+            auto it = search.find(k2(xk(2 * q), xk(e2))); if (it == search.end()) it = search.find(k2(xk(e2), xk(2 * q)));
+            if (it != search.end() && (int64_t)it->second >= (int64_t)highTh) { count1++; if (std::find(side2.begin(), side2.end(), q) != side2.end()) cycle = true; }
+        }
+        if (cycle) { R.cycles++; continue; }
+        if (count1 > limit || count2 > limit) { R.blocked++; continue; }
+        if (usedPair.count(p1) || usedPair.count(p2)) { const int rc = flush(); if (rc) return rc; }      // (e): only a kept operand can be named again, the rows are older than the round's edges
+        if ((uint64_t)nh + 2 >= (1ull << 32) - 4096) return c->fail(SAGE2OV_ERR_LIMIT, "sage2ov_scaffold_round: more than 2^32 half-edges");
+        { SimplifiedGraph tmp; tmp.len = {len[e1], len[e1 ^ 1u], len[e2], len[e2 ^ 1u]};
+          if (!join_length_fits(tmp, 0, 2, r.gap)) return c->fail(SAGE2OV_ERR_LIMIT, "sage2ov_scaffold_round: an edge length beyond 32 bits"); }
+        const uint32_t t1 = type[e1], t2 = type[e2], t = ((t1 == 2 || t1 == 3) ? 2u : 0u) | ((t2 == 1 || t2 == 3) ? 1u : 0u), node = to[e1];
+        sage2ov_join m{}; m.from = from[e1]; m.to = to[e2]; m.support = r.sup; m.gap = r.gap; m.type = (uint8_t)t;
+        m.pair_first = ordBefore[p1]; m.pair_second = ordBefore[p2]; m.pair_new = ~0u;
+        m.first_deleted = flow[e1] <= 1.0f; m.second_deleted = flow[e2] <= 1.0f;
+        from.push_back(from[e1]); to.push_back(to[e2]); type.push_back((uint8_t)t); len.push_back(0); alive.push_back(1); flow.push_back(1.0f);
+        from.push_back(to[e2]); to.push_back(from[e1]); type.push_back((uint8_t)flip_type_host((int)t)); len.push_back(0); alive.push_back(1); flow.push_back(1.0f);
+        if (m.first_deleted) alive[e1] = alive[e1 ^ 1u] = 0; else { flow[e1] -= 1.0f; flow[e1 ^ 1u] -= 1.0f; }
+        if (m.second_deleted) alive[e2] = alive[e2 ^ 1u] = 0; else { flow[e2] -= 1.0f; flow[e2 ^ 1u] -= 1.0f; }
+        bA.push_back(e1); bB.push_back(e2); bG.push_back(r.gap); usedPair.insert(p1); usedPair.insert(p2);
+        spent.insert(p1); spent.insert(p2);
+        joins.push_back(m); newHalf.push_back(nh); nh += 2;
+        const uint64_t own = k2(xk(e1), xk(e2)); bool others = false;
+        auto its = filed.equal_range(node);
+        for (auto it = its.first; it != its.second; ++it) if (search.erase(it->second) && it->second != own) others = true;
+        if (m.first_deleted && others) R.outside_reference = 1;                        // (d): the reference reads the erase key from the freed edge_1 (:607)
+    }
+    { const int rc = flush(); if (rc) return rc; }
+    R.merged = joins.size();
+    R.select_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - selectOut;
+    if (!joins.empty()) {
+        { const int rc = pair_ordinals(c); if (rc) return rc; }
+        for (size_t i = 0; i < joins.size(); i++) joins[i].pair_new = (newHalf[i] >> 1) < c->pairOrdinal.size() ? c->pairOrdinal[newHalf[i] >> 1] : ~0u;
+    }
+    c->scjoins = std::move(joins);
+    c->scstats.rounds++; c->scstats.last = R; sc_counts_add(c->scstats.total, R);
+    if (merged) *merged = R.merged;
+    return SAGE2OV_OK;
+}
+int sage2ov_scaffold(sage2ov_ctx* c, uint64_t genomeSize, uint64_t* rounds, uint64_t* merged) {                       // :31-98
+    if (!c) return SAGE2OV_ERR_ARG;
+    { const int rc = readmap_check(c, "sage2ov_scaffold"); if (rc) return rc; }
+    { const int rc = header_hold(c); if (rc) return rc; }
+    const uint64_t gs = genomeSize ? genomeSize : c->hdrGenome, reads = c->hdrReads, arl = average_read_length(c);
+    if (!gs || !arl) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_scaffold: a genome size or an average read length of 0");
+    uint64_t r = 0, total = 0;
+    int low = 0; sage2ov_scaffold_threshold(reads, arl, gs, 1, 6, &low);
+    for (uint32_t loop = 1; loop <= 5; loop++)
+        for (uint32_t it = 1;; it++) {
+            if (r >= 10000) return c->fail(SAGE2OV_ERR_INTERNAL, "sage2ov_scaffold: 10 000 rounds without a fixed point");
+            int high = 0; sage2ov_scaffold_threshold(reads, arl, gs, loop, it, &high);
+            uint64_t m = 0; { const int rc = sage2ov_scaffold_round(c, high, (loop == 2 || loop == 5) ? 2 : 1, loop == 5, &m); if (rc) return rc; }
+            r++; total += m;
+            if (rounds) *rounds = r; if (merged) *merged = total;
+            if (!m && (loop > 2 || high == low)) break;
+        }
+    return SAGE2OV_OK;
+}
+int sage2ov_scaffold_merges_count(const sage2ov_ctx* c, uint64_t* n) { if (!c || !n) return SAGE2OV_ERR_ARG; *n = c->scjoins.size(); return SAGE2OV_OK; }
+int sage2ov_scaffold_merges_export(const sage2ov_ctx* c, sage2ov_join* out, uint64_t cap) {
+    if (!c || cap < c->scjoins.size() || (!out && !c->scjoins.empty())) return SAGE2OV_ERR_ARG;
+    if (!c->scjoins.empty()) memcpy(out, c->scjoins.data(), c->scjoins.size() * sizeof(sage2ov_join));
+    return SAGE2OV_OK;
+}
+int sage2ov_scaffold_stats_get(const sage2ov_ctx* c, sage2ov_scaffold_stats* o) { if (!c || !o) return SAGE2OV_ERR_ARG; *o = c->scstats; return SAGE2OV_OK; }
 
 // ---- OverlapGraph::printGraph / saveContigsToFile (overlapGraph.cpp:507-784); the semantics are stated in sage2ov.h
 namespace {

@@ -169,6 +169,11 @@ int dev_simplify_download(Device* d, SimplifiedGraph& out, std::string& err, boo
 // ContigExtender::mergeEdgesAndUpdate for a batch of edge-disjoint merges over the resident graph (sage2ov_graph_merge_pairs; kernels_merge.inc)
 struct MergeStats { uint64_t merged = 0, entries_copied = 0, pairs_deleted = 0, half_edges = 0, list_entries = 0; double plan_ms = 0, lists_ms = 0, commit_ms = 0; };
 int dev_merge_pairs(Device* d, const uint32_t* a, const uint32_t* b, uint64_t n, int typeOfMerge, uint8_t* out, MergeStats* st, std::string& err);
+// ScaffoldMaker::mergeDisconnectedEdges for a batch of edge-disjoint joins over the resident graph and the read store (sage2ov_graph_join_pairs; DESIGN.md 5.17;
+// kernels_scaffold.inc).  overlap (may be null): 2 n values, what stringOverlapSize returned for the forward and the twin list (-2: equal end nodes, no search)
+struct JoinStats { uint64_t joined = 0, entries_copied = 0, pairs_deleted = 0, half_edges = 0, list_entries = 0, overlaps = 0, concatenated = 0, gapped = 0;
+                   double overlap_ms = 0, plan_ms = 0, lists_ms = 0, commit_ms = 0; };
+int dev_join_pairs(Device* d, const uint32_t* a, const uint32_t* b, const int32_t* gap, uint64_t n, uint8_t* out, int32_t* overlap, JoinStats* st, std::string& err);
 void dev_simplify_release(Device* d);
 int dev_simplify_upload(Device* d, const SimplifiedGraph& in, std::string& err);  // a parsed graph (from .. lists filled) takes the place of step 4's result in HBM
 // MatePair::mapReadsToEdges / mapReadLocations / computeMeanSD on the device (sage2ov_mates_map_reads, _estimate): dev_readmap_build makes the
