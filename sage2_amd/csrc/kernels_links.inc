@@ -8,7 +8,7 @@
 // and nothing else.  LINK(a, b) of include/sage2ov.h is the run of the key a:32 | b:32.
 //   k_ms_nodes, k_ms_unique   uniq[r] = pair + 1 when r has exactly one read-to-edge entry and is no node (kernels_support.inc)
 //   k_sl_halves      the list length of every alive half-edge (the records' work items); (scan)
-//   k_rm_dprev, (scan)   the running sums, as kernels_readmap.inc makes them
+//   k_rm_dprev, (scan)   the running sums (pool_running_sums)
 //   k_sl_records<false / true>   one thread per list entry of an alive half (it finds its half by rm_owner: no thread walks a list).  Out unless the running sum is
 //                    within the bound and the read is unique on the half's pair.  Then the read's mate entries of every valid library, found by binary search in the
 //                    library's sorted keys, and per entry: the mate's pair q (not the thread's own), and for BOTH halves of q the first (x, y) in list order that
@@ -17,10 +17,8 @@
 //   k_sl_gather      the values in sorted order, and one 0 behind them; (scan, mod 2^32): gapSum of a run is the difference of two scanned values
 //   k_mate_heads, (scan) + k_headpos
 //   k_sl_reduce      row e: the key of head e, support = the run's length, gap = (int32_t)gapSum / support (:892)
-// Every count is kept below 2^32 - RS_TILE by the driver.  No kernel uses LDS or scratch; the d1 x d2 loops read the locations from memory, no array is indexed.
+// A library is the MsLib of kernels_support.inc.  Every count is kept below 2^32 - RS_TILE by the driver.  No kernel uses LDS or scratch; the d1 x d2 loops read the locations from memory, no array is indexed.
 // =============================================================================================
-struct SlLib { const u64* key; u64 n; long long thr; u32 gbase, pad; };      // thr = upper[L] + minOverlap - 2 * averageReadLength (:866), 0 for a library that is not valid;
-                                                                             // gbase = Mean[L] - 2 * averageReadLength mod 2^32 (:878)
 constexpr u32 SL_NO_SIGN = 10000000u;                                        // distance_all of an (x, y) that fails the sign test (:854)
 // E of a pair: the half leaving the smaller node; of a loop the half with the higher index (k_rm_records' side 0)
 __device__ __forceinline__ bool sl_is_E(u32 f, u32 t, u32 h) { return f < t || (f == t && (h & 1u)); }
@@ -48,7 +46,7 @@ __device__ __forceinline__ bool sl_first_hit(const int* __restrict__ locs, u32 a
 // entry w from pos[w] on
 template <bool WRITE>
 __global__ void k_sl_records(S4Graph g, u32 nh, const u32* __restrict__ hOff, u32 W, const u32* __restrict__ scan, u64 listUsed, u64 bound, const u32* __restrict__ uniq,
-                             MsTable T, const SlLib* __restrict__ libs, u32 nlib, u32* cnt, const u32* __restrict__ pos, u64* key, u32* val, unsigned long long* ctr) {
+                             MsTable T, const MsLib* __restrict__ libs, u32 nlib, u32* cnt, const u32* __restrict__ pos, u64* key, u32* val, unsigned long long* ctr) {
     const u32 w = blockIdx.x * blockDim.x + threadIdx.x;
     bool inside = false, un = false; u32 c = 0, probed = 0;
     if (w < W) {
@@ -64,7 +62,7 @@ __global__ void k_sl_records(S4Graph g, u32 nh, const u32* __restrict__ hOff, u3
                 const bool E1 = sl_is_E(g.from[h], g.to[h], h);
                 const u32 a1 = T.eLoc[e1] + (E1 ? 0u : nf1), n1 = E1 ? nf1 : T.eNr[e1];
                 for (u32 L = 1; L <= nlib; L++) {
-                    const SlLib lib = libs[L]; if (!lib.n || lib.thr <= 0) continue;
+                    const MsLib lib = libs[L]; if (!lib.n || lib.thr <= 0) continue;
                     u64 lo = 0, hi = lib.n; const u64 want = (u64)m1 << 32;
                     while (lo < hi) { const u64 mid = lo + ((hi - lo) >> 1); if (lib.key[mid] < want) lo = mid + 1; else hi = mid; }
                     for (u64 i = lo; i < lib.n; i++) {

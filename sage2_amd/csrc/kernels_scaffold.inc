@@ -1,11 +1,12 @@
 // sage2_amd/csrc/kernels_scaffold.inc -- ScaffoldMaker::mergeDisconnectedEdges for a batch of edge-disjoint joins (matePair/scaffolding.cpp:281-482,
 // OverlapGraph::getListOfReadsInDisconnectedEdges and stringOverlapSize, overlapGraph.cpp:789-907) over the resident step-4 graph and the 2-bit read store
 // (DESIGN.md 5.17; the contract is JOIN in include/sage2ov.h).
-// Part of sage2ov_device.hip (included inside namespace s2, after kernels_contig.inc: CtReads, ct_slot, ct_len); not a translation unit of its own.
+// Part of sage2ov_device.hip (included inside namespace s2, after kernels_contig.inc: CtReads, ct_slot, ct_len, and kernels_splice.inc); not a translation unit of its own.
 //
 // A join is (a, b, gap): half-edge a = e1 and half-edge b = e2 need not share a node.  Direction 0 of join i is the forward list (first = a, second = b),
 // direction 1 the twin's (first = b ^ 1, second = a ^ 1); node1 = to[first], node2 = from[second].  node1 == node2 holds in both directions or in neither.
-// The new pair of join i is half-edges nh + 2 i, nh + 2 i + 1 (nothing is refused).  No thread walks a list.
+// The new pair of join i is half-edges nh + 2 i, nh + 2 i + 1 (nothing is refused).  This file holds the overlap search and the join's plan kernel; the lists and
+// the commit are the splice's (kernels_splice.inc).
 
 constexpr int SC_WORDS = SLOT_MAX_WORDS + 2;      // a read is at most 32 words of 32 bases; a funnel shift reads one word past the last one
 // bases p .. p + 31 of the stored (forward) read in `slot`, MSB first like the store, positions outside [0, L) as zero bits; p may be negative
@@ -80,25 +81,26 @@ __global__ void __launch_bounds__(64) k_sc_overlap(S4Graph g, CtReads R, const u
     if (lane == 0) ov[s] = found;
 }
 
-struct ScPlan { u32 a, b, lenF, lenT; u32 dNext1[2], dPrev2[2]; uint8_t type, del1, del2, equal; uint8_t how[2], pad[2]; };      // 40 bytes; how: SC_EQUAL .. SC_GAPPED per direction
-constexpr uint8_t SC_EQUAL = 0, SC_OVERLAP = 1, SC_CONCAT = 2, SC_GAPPED = 3;
+constexpr uint8_t SC_EQUAL = 0, SC_OVERLAP = 1, SC_CONCAT = 2, SC_GAPPED = 3;          // SplicePlan::how, per direction
 // one thread per join: the type by the four-way rule (scaffolding.cpp:290-297), delete or keep at flow 1.0 (:301, :344), the distances and both edge lengths
-// (overlapGraph.cpp:827-859; unwrapped: the entry keeps 11 bits, the length all); lens[2 i], lens[2 i + 1]: the lengths of the two new lists
+// (overlapGraph.cpp:827-859; unwrapped: the entry keeps 11 bits, the length all), into the splice record (kernels_splice.inc: nothing is refused, two middle entries
+// unless the end nodes are equal); lens[2 i], lens[2 i + 1]: the lengths of the two new lists
 __global__ void k_sc_plan(S4Graph g, CtReads R, const float* __restrict__ flow, const u32* __restrict__ ha, const u32* __restrict__ hb, const int* __restrict__ gaps,
-                          const int* __restrict__ ov, u32 n, ScPlan* plan, u32* lens) {
+                          const int* __restrict__ ov, u32 n, SplicePlan* plan, u32* lens) {
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x; if (i >= n) return;
     const u32 a = ha[i], b = hb[i]; const int gap = gaps[i];
-    ScPlan p; p.a = a; p.b = b; p.pad[0] = p.pad[1] = 0;
+    SplicePlan p = {}; p.a = a; p.b = b; p.made = 1; p.flow = 1.0f;
     const u32 t1 = g.type[a], t2 = g.type[b];
     p.type = (uint8_t)(((t1 == 2u || t1 == 3u) ? 2u : 0u) | ((t2 == 1u || t2 == 3u) ? 1u : 0u));
     p.del1 = (flow ? flow[a] : 0.f) <= 1.0f; p.del2 = (flow ? flow[b] : 0.f) <= 1.0f;      // flow null: every flow is 0
-    p.equal = g.to[a] == g.from[b];
+    const bool equal = g.to[a] == g.from[b];
+    p.extra = equal ? 1 : 2;
     u32 len[2];
 #pragma unroll
     for (int d = 0; d < 2; d++) {
         const u32 first = d ? (b ^ 1u) : a, second = d ? (a ^ 1u) : b;
         u32 add = 0, d1 = 0, d2 = 0; uint8_t how = SC_EQUAL;
-        if (!p.equal) {
+        if (!equal) {
             const u32 L1 = ct_len(R, ct_slot(R, g.to[first])), L2 = ct_len(R, ct_slot(R, g.from[second]));
             const int o = ov[2 * i + d];
             if (o > 0) { d1 = d2 = (u32)o; how = SC_OVERLAP; }                       // (a shift of 0 is "no overlap" to the reference, :837)
@@ -111,38 +113,6 @@ __global__ void k_sc_plan(S4Graph g, CtReads R, const float* __restrict__ flow, 
     }
     p.lenF = len[0]; p.lenT = len[1];
     plan[i] = p;
-    const u32 l = g.cnt[a] + g.cnt[b] + (p.equal ? 1u : 2u);
+    const u32 l = g.cnt[a] + g.cnt[b] + p.extra;
     lens[2 * i] = l; lens[2 * i + 1] = l;
-}
-// one thread per entry of the new lists, both lists of every join in one launch (overlapGraph.cpp:861-881).  lo: the exclusive scan of lens (2 n values, none 0)
-__global__ void k_sc_lists(S4Graph g, const ScPlan* __restrict__ plan, const u32* __restrict__ lo, u32 n2, u64 total, u32 base) {
-    const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x; if (t >= total) return;
-    u32 l = 0, r = n2;                                                              // the largest j with lo[j] <= t
-    while (r - l > 1) { const u32 m = l + ((r - l) >> 1); if ((u64)lo[m] <= t) l = m; else r = m; }
-    const ScPlan p = plan[l >> 1]; const u32 d = l & 1u;
-    const u32 first = d ? (p.b ^ 1u) : p.a, second = d ? (p.a ^ 1u) : p.b;
-    const u32 c1 = g.cnt[first], x = (u32)(t - lo[l]), extra = p.equal ? 1u : 2u;
-    u64 e;
-    if (x < c1) e = g.lists[(u64)g.off[first] + x];
-    else if (x >= c1 + extra) e = g.lists[(u64)g.off[second] + (x - c1 - extra)];
-    else {
-        const u32 dPrev1 = s4_dnext(g.lists[(u64)g.off[first] + c1 - 1]), dNext2 = s4_dprev(g.lists[(u64)g.off[second]]);      // both operands are composite (checked by the caller)
-        const u32 ty1 = g.type[first], ty2 = g.type[second];
-        const u32 d1 = d ? p.dNext1[1] : p.dNext1[0], d2 = d ? p.dPrev2[1] : p.dPrev2[0];      // (selects: a run-time index would make the plan a private array)
-        if (x == c1) e = s4_entry(g.to[first], (ty1 == 1u || ty1 == 3u) ? 1u : 0u, dPrev1, p.equal ? dNext2 : d1);
-        else e = s4_entry(g.from[second], (ty2 == 2u || ty2 == 3u) ? 1u : 0u, d2, dNext2);
-    }
-    g.lists[(u64)base + t] = e;
-}
-// one thread per join: the new halves (insertEdge with flow 1.0 and the two lengths), then the operands: both halves deleted, or both lose 1.0
-__global__ void k_sc_commit(S4Graph g, float* flow, const ScPlan* __restrict__ plan, const u32* __restrict__ lo, u32 n, u32 nh, u32 base) {
-    const u32 i = blockIdx.x * blockDim.x + threadIdx.x; if (i >= n) return;
-    const ScPlan p = plan[i];
-    const u32 a = p.a, b = p.b, h = nh + 2 * i, c = g.cnt[a] + g.cnt[b] + (p.equal ? 1u : 2u);
-    g.from[h] = g.from[a]; g.to[h] = g.to[b]; g.len[h] = p.lenF; g.cnt[h] = c; g.off[h] = base + lo[2 * i]; g.type[h] = p.type; g.alive[h] = 1;
-    g.from[h + 1] = g.to[b]; g.to[h + 1] = g.from[a]; g.len[h + 1] = p.lenT; g.cnt[h + 1] = c; g.off[h + 1] = base + lo[2 * i + 1];
-    g.type[h + 1] = (uint8_t)s4_rev_type(p.type); g.alive[h + 1] = 1;
-    flow[h] = 1.0f; flow[h + 1] = 1.0f;
-    if (p.del1) { g.alive[a] = 0; g.alive[a ^ 1u] = 0; } else { flow[a] -= 1.0f; flow[a ^ 1u] -= 1.0f; }
-    if (p.del2) { g.alive[b] = 0; g.alive[b ^ 1u] = 0; } else { flow[b] -= 1.0f; flow[b ^ 1u] -= 1.0f; }
 }

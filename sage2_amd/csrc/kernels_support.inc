@@ -11,7 +11,7 @@
 //   k_ms_roles       one thread per half-edge: 1 = in-half (alive, flow >= 1, a list, no loop, type 0 or 1: its twin enters the node), 2 = out-half (type 2 or 3),
 //                    0 = none; the list length of the in-halves (the records' work items); ins and outs per node
 //   k_ms_cand        ins x outs per node (saturating); (scan): the candidate count of the statistics
-//   k_rm_dprev, (scan)   the running sums, as kernels_readmap.inc makes them
+//   k_rm_dprev, (scan)   the running sums (pool_running_sums)
 //   k_ms_records<false / true>   one thread per list entry of an in-half (it finds its half by rm_owner: no thread walks a list).  Out unless the running sum is
 //                    within the bound and the read is unique on the half's pair.  Then the read's mate entries of every library, found by binary search in the
 //                    library's sorted keys (a per-read offset array would cost N + 2 words per library for the few reads that are asked), and per entry: the
@@ -20,7 +20,9 @@
 //   k_ms_reduce      entry e: the key of head e, support = the run's length
 // Every count is kept below 2^32 - RS_TILE by the driver.
 // =============================================================================================
-struct MsLib { const u64* key; u64 n; long long thr; };      // thr = upperBoundOfInsert + minOverlap - 2 * averageReadLength (:1073-1076); 0 for a library that is not valid
+// one library of either sweep's record kernel.  thr = upperBoundOfInsert + minOverlap - 2 * averageReadLength (:1073-1076; scaffolding.cpp:866), 0 for a library that is
+// not valid; gbase = Mean[L] - 2 * averageReadLength mod 2^32 (scaffolding.cpp:878: the link sweep's, 0 here)
+struct MsLib { const u64* key; u64 n; long long thr; u32 gbase, pad; };
 struct MsTable { const u32* readOff; const u32* ePair; const u32* eNf; const u32* eNr; const u32* eLoc; const int* locs; u32 N; };
 constexpr u32 MS_NONE = 0xFFFFFFFFu;
 __global__ void k_ms_nodes(S4Graph g, u32 nh, uint8_t* nodeFlag) { const u32 h = blockIdx.x * blockDim.x + threadIdx.x; if (h < nh && g.alive[h]) nodeFlag[g.from[h]] = 1; }

@@ -231,7 +231,7 @@ static void mem_sample(Device* d) { size_t fr = 0, to = 0; if (hipMemGetInfo(&fr
 #include "kernels_reduce.inc"
 #include "kernels_convert.inc"
 #include "kernels_simplify.inc"
-#include "kernels_merge.inc"
+#include "kernels_splice.inc"
 #include "kernels_find.inc"
 #include "kernels_mates.inc"
 #include "kernels_readmap.inc"
@@ -2138,7 +2138,7 @@ struct S4Mem {                                   // released on every exit path 
 }
 #define S4GET(var, type, n) type* var = mem.get<type>((n), err); if (!var) return SAGE2OV_ERR_NOMEM;
 struct S4Keep { S4Mem mem; S4Graph g; u32 nh = 0; u64 listUsed = 0; float* flow = nullptr;       // flow: one float per half-edge (null: every flow is 0, the state after step 4)
-                u64 capH = 0, listCap = 0, flowCap = 0; };                                       // what the half-edge arrays, the list pool and flow[] hold (dev_merge_pairs grows them)
+                u64 capH = 0, listCap = 0, flowCap = 0; };                                       // what the half-edge arrays, the list pool and flow[] hold (splice_pairs grows them)
 void dev_simplify_release(Device* d) { dev_readmap_release(d); dev_contigs_release(d); dev_copycount_release(d); if (d->s4keep) { hipSetDevice(d->ordinal); delete (S4Keep*)d->s4keep; d->s4keep = nullptr; } }
 
 int dev_simplify(Device* d, SimplifiedGraph& out, std::string& err) {
@@ -2431,109 +2431,94 @@ static int s4_pools_grow(Device* d, S4Keep& K, u64 created, u64 total, std::stri
     }
     return 0;
 }
-// ---- mergeEdgesAndUpdate for a batch (kernels_merge.inc).  a[i], b[i]: the half-edges e1 and e2 of merge i, below K.nh, to[a] == from[b], no pair
-// named twice -- the caller has checked all of it, and the 11-bit limit of a simple operand's length.  out[i]: bit 0 merged, bit 1 e1's pair deleted, bit 2 e2's,
-// bits 4-5 the new type.  Everything made from the graph goes (as in dev_simplify_release), the graph itself stays.
-int dev_merge_pairs(Device* d, const u32* a, const u32* b, uint64_t n, int typeOfMerge, uint8_t* out, MergeStats* st, std::string& err) {
-    HIPCHK(hipSetDevice(d->ordinal));
-    if (!d->s4keep) { err = "merge: no step-4 graph on the device"; return SAGE2OV_ERR_ARG; }
+// ---- a batch of splices (kernels_splice.inc): the sequence that merges and joins share.  a[i], b[i]: the operand half-edges of splice i,
+// below K.nh, no pair named twice -- the caller has checked it.  planStage(da, db, plan, lens, partial, rank, created) runs its plan kernel on the uploaded
+// operands, between lap.start and the scan of lens (its time is plan_ms, less what it laps apart itself), and sets rank and created where it can refuse; left
+// alone, splice i makes pair K.nh / 2 + i.  makesFlow: flows that were all 0 (no array) become an array.  out[i]: the plan of splice i.  Everything made from the
+// graph goes (as in dev_simplify_release), the graph itself stays.
+template <class PlanStage>
+static int splice_pairs(Device* d, DevTmp& B, StreamLap& lap, const std::string& who, const u32* a, const u32* b, u64 n, u64 maxN, bool makesFlow, SplicePlan* out,
+                        SpliceStats* st, std::string& err, PlanStage&& planStage) {
     S4Keep& K = *(S4Keep*)d->s4keep; S4Mem& mem = K.mem; S4Graph& g = K.g; hipStream_t sm = d->stream;
-    *st = MergeStats();
-    if (!n) return 0;
-    if (n >= (1ull << 31) || (u64)K.nh + 2 * n >= (1ull << 32) - RS_TILE) { err = "merge: more than 2^32 half-edges"; return SAGE2OV_ERR_LIMIT; }
-    DevTmp B; StreamLap lap(sm); HIPCHK(lap.create());
+    if (n >= maxN || (u64)K.nh + 2 * n >= (1ull << 32) - RS_TILE) { err = who + ": more than 2^32 half-edges"; return SAGE2OV_ERR_LIMIT; }
     const u32 m = (u32)n;
-    u32* da = B.get<u32>(n); u32* db = B.get<u32>(n); MgPlan* plan = B.get<MgPlan>(n); u32* lens = B.get<u32>(2 * n); u32* lo = B.get<u32>(2 * n); u32* isNew = B.get<u32>(n); u32* rank = B.get<u32>(n);
+    u32* da = B.get<u32>(n); u32* db = B.get<u32>(n); SplicePlan* plan = B.get<SplicePlan>(n); u32* lens = B.get<u32>(2 * n); u32* lo = B.get<u32>(2 * n);
     u64* partial = B.get<u64>(scan_partial_words(2 * n));
-    if (!da || !db || !plan || !lens || !lo || !isNew || !rank || !partial) { err = "merge: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+    if (!da || !db || !plan || !lens || !lo || !partial) { err = who + ": out of device memory"; return SAGE2OV_ERR_NOMEM; }
     HIPCHK(lap.start());
     HIPCHK(hipMemcpyAsync(da, a, n * sizeof(u32), hipMemcpyHostToDevice, sm)); HIPCHK(hipMemcpyAsync(db, b, n * sizeof(u32), hipMemcpyHostToDevice, sm));
-    hipLaunchKernelGGL(k_mg_plan, dim3(grid_for(n, 256)), dim3(256), 0, sm, g, (const float*)K.flow, da, db, m, typeOfMerge, plan, lens, isNew);
-    u64 total = 0, created = 0;
+    u32* rank = nullptr; u64 total = 0, created = n;
+    { const int rc = planStage(da, db, plan, lens, partial, rank, created); if (rc) return rc; }
+    HIPCHK(hipGetLastError());
     { const int rc = scan_u32(d, lens, 2 * n, lo, partial, &total, err); if (rc) return rc; }
-    { const int rc = scan_u32(d, isNew, n, rank, partial, &created, err); if (rc) return rc; }
     HIPCHK(lap.stop(st->plan_ms));
-    if (K.listUsed + total >= (1ull << 32) - RS_TILE) { err = "merge: read lists exceed 2^32 entries"; return SAGE2OV_ERR_LIMIT; }
+    if (K.listUsed + total >= (1ull << 32) - RS_TILE) { err = who + ": read lists exceed 2^32 entries"; return SAGE2OV_ERR_LIMIT; }
     if (created) {
+        if (makesFlow && !K.flow) {                                                    // (every flow was 0: the plan read them as 0; the new edges have 1.0)
+            float* f = mem.get<float>(std::max<u64>(K.capH, 1), err); if (!f) return SAGE2OV_ERR_NOMEM;
+            HIPCHK(hipMemsetAsync(f, 0, std::max<u64>(K.capH, 1) * sizeof(float), sm)); K.flow = f; K.flowCap = std::max<u64>(K.capH, 1);
+        }
         { const int rc = s4_pools_grow(d, K, created, total, err); if (rc) return rc; }
         dev_readmap_release(d); dev_contigs_release(d); dev_copycount_release(d);
         HIPCHK(lap.start());
-        if (total) hipLaunchKernelGGL(k_mg_lists, dim3(grid_for(total, 256)), dim3(256), 0, sm, g, plan, lo, 2 * m, (u64)total, (u32)K.listUsed);
+        hipLaunchKernelGGL(k_sp_lists, dim3(grid_for(total, 256)), dim3(256), 0, sm, g, plan, lo, 2 * m, (u64)total, (u32)K.listUsed);
         HIPCHK(hipGetLastError());
         HIPCHK(lap.stop(st->lists_ms));
         HIPCHK(lap.start());
-        hipLaunchKernelGGL(k_mg_commit, dim3(grid_for(n, 256)), dim3(256), 0, sm, g, K.flow, plan, lo, rank, m, K.nh, (u32)K.listUsed);
+        hipLaunchKernelGGL(k_sp_commit, dim3(grid_for(n, 256)), dim3(256), 0, sm, g, K.flow, plan, lo, rank, m, K.nh, (u32)K.listUsed);
         HIPCHK(hipGetLastError());
         HIPCHK(lap.stop(st->commit_ms));
     }
-    std::vector<MgPlan> hp(n);
-    HIPCHK(hipMemcpy(hp.data(), plan, n * sizeof(MgPlan), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out, plan, n * sizeof(SplicePlan), hipMemcpyDeviceToHost));
     for (u64 i = 0; i < n; i++) {
-        const MgPlan& p = hp[i];
-        out[i] = (uint8_t)(p.merged | (p.del1 << 1) | (p.del2 << 2) | (p.type << 4));
-        st->pairs_deleted += (u64)p.del1 + p.del2;
-    }
-    K.nh += (u32)(2 * created); K.listUsed += total;
-    st->merged = created; st->entries_copied = total; st->half_edges = K.nh; st->list_entries = K.listUsed;
-    return 0;
-}
-
-// ---- mergeDisconnectedEdges for a batch (kernels_scaffold.inc).  a[i], b[i], gap[i]: the half-edges e1 and e2 and the gap of join i, below K.nh,
-// alive, both with a list, no pair named twice, lengths within 32 bits -- the caller has checked all of it.  Nothing is refused: join i makes pair K.nh / 2 + i.
-// out[i]: bit 0 e1's pair deleted, bit 1 e2's, bits 2-3 the new type, bits 4-5 and 6-7 how the forward and the twin list were joined (SC_EQUAL .. SC_GAPPED).
-// Flows that were all 0 (no array) become an array: the new edges have flow 1.0.  Everything made from the graph goes, the graph itself stays.
-static bool contig_reads(Device* d, CtReads& R);
-int dev_join_pairs(Device* d, const u32* a, const u32* b, const int32_t* gap, uint64_t n, uint8_t* out, int32_t* overlap, JoinStats* st, std::string& err) {
-    HIPCHK(hipSetDevice(d->ordinal));
-    if (!d->s4keep) { err = "join: no step-4 graph on the device"; return SAGE2OV_ERR_ARG; }
-    CtReads Rd; if (!contig_reads(d, Rd)) { err = "join: no read store on the device"; return SAGE2OV_ERR_ARG; }
-    S4Keep& K = *(S4Keep*)d->s4keep; S4Mem& mem = K.mem; S4Graph& g = K.g; hipStream_t sm = d->stream;
-    *st = JoinStats();
-    if (!n) return 0;
-    if (n >= (1ull << 30) || (u64)K.nh + 2 * n >= (1ull << 32) - RS_TILE) { err = "join: more than 2^32 half-edges"; return SAGE2OV_ERR_LIMIT; }
-    DevTmp B; StreamLap lap(sm); HIPCHK(lap.create());
-    const u32 m = (u32)n;
-    u32* da = B.get<u32>(n); u32* db = B.get<u32>(n); int* dgap = B.get<int>(n); int* ov = B.get<int>(2 * n); ScPlan* plan = B.get<ScPlan>(n); u32* lens = B.get<u32>(2 * n); u32* lo = B.get<u32>(2 * n);
-    u64* partial = B.get<u64>(scan_partial_words(2 * n));
-    if (!da || !db || !dgap || !ov || !plan || !lens || !lo || !partial) { err = "join: out of device memory"; return SAGE2OV_ERR_NOMEM; }
-    HIPCHK(lap.start());
-    HIPCHK(hipMemcpyAsync(da, a, n * sizeof(u32), hipMemcpyHostToDevice, sm)); HIPCHK(hipMemcpyAsync(db, b, n * sizeof(u32), hipMemcpyHostToDevice, sm));
-    HIPCHK(hipMemcpyAsync(dgap, gap, n * sizeof(int), hipMemcpyHostToDevice, sm));
-    hipLaunchKernelGGL(k_sc_overlap, dim3(2 * m), dim3(64), 0, sm, g, Rd, da, db, 2 * m, ov);
-    HIPCHK(hipGetLastError());
-    HIPCHK(lap.stop(st->overlap_ms));
-    HIPCHK(lap.start());
-    hipLaunchKernelGGL(k_sc_plan, dim3(grid_for(n, 256)), dim3(256), 0, sm, g, Rd, (const float*)K.flow, da, db, dgap, ov, m, plan, lens);
-    HIPCHK(hipGetLastError());
-    u64 total = 0;
-    { const int rc = scan_u32(d, lens, 2 * n, lo, partial, &total, err); if (rc) return rc; }
-    HIPCHK(lap.stop(st->plan_ms));
-    if (K.listUsed + total >= (1ull << 32) - RS_TILE) { err = "join: read lists exceed 2^32 entries"; return SAGE2OV_ERR_LIMIT; }
-    if (!K.flow) {                                                                     // (every flow was 0: the plan read them as 0; the new edges have 1.0)
-        float* f = mem.get<float>(std::max<u64>(K.capH, 1), err); if (!f) return SAGE2OV_ERR_NOMEM;
-        HIPCHK(hipMemsetAsync(f, 0, std::max<u64>(K.capH, 1) * sizeof(float), sm)); K.flow = f; K.flowCap = std::max<u64>(K.capH, 1);
-    }
-    { const int rc = s4_pools_grow(d, K, n, total, err); if (rc) return rc; }
-    dev_readmap_release(d); dev_contigs_release(d); dev_copycount_release(d);
-    HIPCHK(lap.start());
-    hipLaunchKernelGGL(k_sc_lists, dim3(grid_for(total, 256)), dim3(256), 0, sm, g, plan, lo, 2 * m, (u64)total, (u32)K.listUsed);
-    HIPCHK(hipGetLastError());
-    HIPCHK(lap.stop(st->lists_ms));
-    HIPCHK(lap.start());
-    hipLaunchKernelGGL(k_sc_commit, dim3(grid_for(n, 256)), dim3(256), 0, sm, g, K.flow, plan, lo, m, K.nh, (u32)K.listUsed);
-    HIPCHK(hipGetLastError());
-    HIPCHK(lap.stop(st->commit_ms));
-    std::vector<ScPlan> hp(n);
-    HIPCHK(hipMemcpy(hp.data(), plan, n * sizeof(ScPlan), hipMemcpyDeviceToHost));
-    if (overlap) HIPCHK(hipMemcpy(overlap, ov, 2 * n * sizeof(int), hipMemcpyDeviceToHost));
-    for (u64 i = 0; i < n; i++) {
-        const ScPlan& p = hp[i];
-        out[i] = (uint8_t)(p.del1 | (p.del2 << 1) | (p.type << 2) | (p.how[0] << 4) | (p.how[1] << 6));
+        const SplicePlan& p = out[i];
         st->pairs_deleted += (u64)p.del1 + p.del2;
         for (int dI = 0; dI < 2; dI++) { st->overlaps += p.how[dI] == SC_OVERLAP; st->concatenated += p.how[dI] == SC_CONCAT; st->gapped += p.how[dI] == SC_GAPPED; }
     }
-    K.nh += (u32)(2 * n); K.listUsed += total;
-    st->joined = n; st->entries_copied = total; st->half_edges = K.nh; st->list_entries = K.listUsed;
+    K.nh += (u32)(2 * created); K.listUsed += total;
+    st->made = created; st->entries_copied = total; st->half_edges = K.nh; st->list_entries = K.listUsed;
+    return 0;
+}
+// mergeEdgesAndUpdate for a batch: to[a] == from[b], and a simple operand's length within 11 bits -- the caller has checked it.  A merge can be refused (made 0)
+int dev_merge_pairs(Device* d, const u32* a, const u32* b, uint64_t n, int typeOfMerge, SplicePlan* out, SpliceStats* st, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    if (!d->s4keep) { err = "merge: no step-4 graph on the device"; return SAGE2OV_ERR_ARG; }
+    *st = SpliceStats();
+    if (!n) return 0;
+    DevTmp B; StreamLap lap(d->stream); HIPCHK(lap.create());
+    return splice_pairs(d, B, lap, "merge", a, b, n, 1ull << 31, false, out, st, err, [&](const u32* da, const u32* db, SplicePlan* plan, u32* lens, u64* partial, u32*& rank, u64& created) -> int {
+        const S4Keep& K = *(const S4Keep*)d->s4keep;
+        u32* isNew = B.get<u32>(n); rank = B.get<u32>(n);
+        if (!isNew || !rank) { err = "merge: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+        hipLaunchKernelGGL(k_mg_plan, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, K.g, (const float*)K.flow, da, db, (u32)n, typeOfMerge, plan, lens, isNew);
+        return scan_u32(d, isNew, n, rank, partial, &created, err);
+    });
+}
+// mergeDisconnectedEdges for a batch: gap[i] the gap of join i; both operands alive, with a list, lengths within 32 bits -- the caller has checked it.  Nothing is
+// refused.  overlap (may be null): 2 n values.  Flows that were all 0 (no array) become an array: the new edges have flow 1.0
+static bool contig_reads(Device* d, CtReads& R);
+int dev_join_pairs(Device* d, const u32* a, const u32* b, const int32_t* gap, uint64_t n, SplicePlan* out, int32_t* overlap, SpliceStats* st, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    if (!d->s4keep) { err = "join: no step-4 graph on the device"; return SAGE2OV_ERR_ARG; }
+    CtReads Rd; if (!contig_reads(d, Rd)) { err = "join: no read store on the device"; return SAGE2OV_ERR_ARG; }
+    *st = SpliceStats();
+    if (!n) return 0;
+    DevTmp B; StreamLap lap(d->stream); HIPCHK(lap.create());
+    int* ov = nullptr;
+    const int rc = splice_pairs(d, B, lap, "join", a, b, n, 1ull << 30, true, out, st, err, [&](const u32* da, const u32* db, SplicePlan* plan, u32* lens, u64*, u32*&, u64&) -> int {
+        const S4Keep& K = *(const S4Keep*)d->s4keep; hipStream_t sm = d->stream; const u32 m = (u32)n;
+        int* dgap = B.get<int>(n); ov = B.get<int>(2 * n);
+        if (!dgap || !ov) { err = "join: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+        HIPCHK(hipMemcpyAsync(dgap, gap, n * sizeof(int), hipMemcpyHostToDevice, sm));
+        hipLaunchKernelGGL(k_sc_overlap, dim3(2 * m), dim3(64), 0, sm, K.g, Rd, da, db, 2 * m, ov);
+        HIPCHK(hipGetLastError());
+        HIPCHK(lap.stop(st->overlap_ms));
+        HIPCHK(lap.start());
+        hipLaunchKernelGGL(k_sc_plan, dim3(grid_for(n, 256)), dim3(256), 0, sm, K.g, Rd, (const float*)K.flow, da, db, dgap, ov, m, plan, lens);
+        return 0;
+    });
+    if (rc) return rc;
+    if (overlap) HIPCHK(hipMemcpy(overlap, ov, 2 * n * sizeof(int), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -2558,6 +2543,30 @@ static int readmap_passes(u64 N, u64 pairs, int* shifts) {
     for (int p = 0; p < 8; p++) { const int lo = 8 * p; if (lo < 1 + bp || (lo >= 32 && lo < 32 + b)) shifts[np++] = lo; }
     return np;
 }
+// ---- the stages that the sort-and-reduce sweeps over the resident graph share (the read-to-edge table, the supports, the links)
+// sums[i] = the distPrevious of the pool entries in front of i, dead lists included (k_rm_dprev, one scan); nobody keeps them: every sweep makes them again
+static int pool_running_sums(Device* d, DevTmp& B, const u64* lists, u64 nl, u64* partial, u32*& sums, int (*nomem)(std::string&), std::string& err) {
+    u32* dprev = B.get<u32>(nl); sums = B.get<u32>(nl);
+    if (!dprev || !sums) return nomem(err);
+    if (nl) hipLaunchKernelGGL(k_rm_dprev, dim3(grid_for_capped(nl, 256)), dim3(256), 0, d->stream, lists, nl, dprev);
+    { const int rc = scan_u32(d, dprev, nl, sums, partial, nullptr, err); if (rc) return rc; }
+    B.release(dprev);
+    return 0;
+}
+// uniq[r] = pair + 1 when read r has exactly one read-to-edge entry and no alive half-edge leaves node r, else 0 (k_ms_nodes, k_ms_unique); nodeFlag: N + 2 bytes of scratch
+static int unique_reads(Device* d, const S4Graph& g, u32 nh, const MsTable& T, uint8_t* nodeFlag, u32* uniq, std::string& err) {
+    HIPCHK(hipMemsetAsync(nodeFlag, 0, (u64)T.N + 2, d->stream));
+    hipLaunchKernelGGL(k_ms_nodes, dim3(grid_for(nh, 256)), dim3(256), 0, d->stream, g, nh, nodeFlag);
+    hipLaunchKernelGGL(k_ms_unique, dim3(grid_for((u64)T.N + 1, 256)), dim3(256), 0, d->stream, T, nodeFlag, uniq);
+    return 0;
+}
+// the 8-bit digits of a (half:32 | half:32) key that can be non-zero: those below the number of half-edges, in both words
+static int half_pair_passes(u32 nh, int* shifts) {
+    int b = 0; while (((u64)nh >> b) != 0) b++;
+    int np = 0;
+    for (int p = 0; p < 8; p++) { const int lo = 8 * p; if ((lo & 31) < b) shifts[np++] = lo; }
+    return np;
+}
 int dev_readmap_build(Device* d, ReadMapStats* st, std::string& err) {
     HIPCHK(hipSetDevice(d->ordinal));
     if (!d->s4keep) { err = "read-to-edge table: no step-4 graph on the device"; return SAGE2OV_ERR_ARG; }
@@ -2570,11 +2579,10 @@ int dev_readmap_build(Device* d, ReadMapStats* st, std::string& err) {
     M->readOff = readmap_alloc<u32>(d->N + 2); if (!M->readOff) return readmap_nomem(err);
     // ---- locations: one scan of distPrevious over the whole pool
     HIPCHK(lap.start());
-    u32* dprev = B.get<u32>(nl); u32* scan = B.get<u32>(nl); u64* partial = B.get<u64>(scan_partial_words(std::max<u64>(nl, nh)));
+    u32* scan = nullptr; u64* partial = B.get<u64>(scan_partial_words(std::max<u64>(nl, nh)));
     u32* cnt = B.get<u32>(nh); u32* recOff = B.get<u32>(nh);
-    if (!dprev || !scan || !partial || !cnt || !recOff) return readmap_nomem(err);
-    if (nl) hipLaunchKernelGGL(k_rm_dprev, dim3(grid_for_capped(nl, 256)), dim3(256), 0, d->stream, g.lists, nl, dprev);
-    { const int rc = scan_u32(d, dprev, nl, scan, partial, nullptr, err); if (rc) return rc; }
+    if (!partial || !cnt || !recOff) return readmap_nomem(err);
+    { const int rc = pool_running_sums(d, B, g.lists, nl, partial, scan, readmap_nomem, err); if (rc) return rc; }
     HIPCHK(lap.stop(st->scan_ms));
     // ---- records
     HIPCHK(lap.start());
@@ -2591,7 +2599,7 @@ int dev_readmap_build(Device* d, ReadMapStats* st, std::string& err) {
     hipLaunchKernelGGL(k_rm_records, dim3(grid_for(R, 256)), dim3(256), 0, d->stream, g, nh, recOff, (u32)R, scan, nl, key, loc);
     HIPCHK(hipGetLastError());
     HIPCHK(lap.stop(st->records_ms));
-    B.release(dprev); B.release(scan); B.release(cnt); B.release(recOff); B.release(partial);
+    B.release(scan); B.release(cnt); B.release(recOff); B.release(partial);
     // ---- sort by (read, pair, side)
     HIPCHK(lap.start());
     int shifts[8]; const int np = readmap_passes(d->N, nh / 2, shifts);
@@ -2727,12 +2735,11 @@ int dev_support_build(Device* d, const SupportParams& P, SupportStats* st, std::
     unsigned long long* ctr = B.get<unsigned long long>(4); u64* partial = B.get<u64>(scan_partial_words(std::max<u64>(std::max<u64>(nl, nh), (u64)N + 2)));
     MsLib* libs = B.get<MsLib>(128);
     if (!nodeFlag || !uniq || !role || !inCnt || !inOff || !nIn || !nOut || !prod || !prodScan || !ctr || !partial || !libs) return support_nomem(err);
-    HIPCHK(hipMemsetAsync(nodeFlag, 0, (u64)N + 2, sm)); HIPCHK(hipMemsetAsync(nIn, 0, ((u64)N + 2) * sizeof(u32), sm)); HIPCHK(hipMemsetAsync(nOut, 0, ((u64)N + 2) * sizeof(u32), sm));
+    HIPCHK(hipMemsetAsync(nIn, 0, ((u64)N + 2) * sizeof(u32), sm)); HIPCHK(hipMemsetAsync(nOut, 0, ((u64)N + 2) * sizeof(u32), sm));
     HIPCHK(hipMemsetAsync(ctr, 0, 4 * sizeof(unsigned long long), sm));
     const MsTable T = {M->readOff, M->ePair, M->eNf, M->eNr, M->eLoc, M->locs, N};
     const dim3 b256(256);
-    hipLaunchKernelGGL(k_ms_nodes, dim3(grid_for(nh, 256)), b256, 0, sm, g, nh, nodeFlag);
-    hipLaunchKernelGGL(k_ms_unique, dim3(grid_for((u64)N + 1, 256)), b256, 0, sm, T, nodeFlag, uniq);
+    { const int rc = unique_reads(d, g, nh, T, nodeFlag, uniq, err); if (rc) return rc; }
     hipLaunchKernelGGL(k_ms_roles, dim3(grid_for(nh, 256)), b256, 0, sm, g, nh, K.flow, role, inCnt, nIn, nOut, ctr);
     hipLaunchKernelGGL(k_ms_cand, dim3(grid_for((u64)N + 1, 256)), b256, 0, sm, nIn, nOut, N, prod);
     { u64 cand = 0; const int rc = scan_u32(d, prod, (u64)N + 1, prodScan, partial, &cand, err); if (rc) return rc; st->candidates = cand; }
@@ -2743,19 +2750,15 @@ int dev_support_build(Device* d, const SupportParams& P, SupportStats* st, std::
     st->in_halves = hc[0]; st->out_halves = hc[1];
     B.release(nodeFlag); B.release(nIn); B.release(nOut); B.release(prod); B.release(prodScan); B.release(inCnt);
     if (!W || !st->out_halves) { d->support = S.release(); return 0; }
-    // ---- the running sums of the whole pool (as dev_readmap_build makes them; not kept there)
+    // ---- the running sums of the whole pool
     HIPCHK(lap.start());
-    u32* dprev = B.get<u32>(nl); u32* scan = B.get<u32>(nl);
-    if (!dprev || !scan) return support_nomem(err);
-    hipLaunchKernelGGL(k_rm_dprev, dim3(grid_for_capped(nl, 256)), b256, 0, sm, g.lists, nl, dprev);
-    { const int rc = scan_u32(d, dprev, nl, scan, partial, nullptr, err); if (rc) return rc; }
+    u32* scan = nullptr; { const int rc = pool_running_sums(d, B, g.lists, nl, partial, scan, support_nomem, err); if (rc) return rc; }
     HIPCHK(lap.stop(st->scan_ms));
-    B.release(dprev);
     // ---- records: count, scan, write
     HIPCHK(lap.start());
-    MsLib hl[128]; for (auto& x : hl) x = MsLib{nullptr, 0, 0};
+    MsLib hl[128]; for (auto& x : hl) x = MsLib{nullptr, 0, 0, 0, 0};
     const u32 nlib = std::min<u32>(P.libraries, 127);
-    for (u32 L = 1; L <= nlib; L++) if (d->mates && d->mates->lib[L].n && P.thr[L] > 0) hl[L] = MsLib{d->mates->lib[L].key, d->mates->lib[L].n, (long long)P.thr[L]};
+    for (u32 L = 1; L <= nlib; L++) if (d->mates && d->mates->lib[L].n && P.thr[L] > 0) hl[L] = MsLib{d->mates->lib[L].key, d->mates->lib[L].n, (long long)P.thr[L], 0, 0};
     HIPCHK(hipMemcpyAsync(libs, hl, sizeof hl, hipMemcpyHostToDevice, sm));
     u32* cnt = B.get<u32>(W); u32* pos = B.get<u32>(W);
     if (!cnt || !pos) return support_nomem(err);
@@ -2773,7 +2776,7 @@ int dev_support_build(Device* d, const SupportParams& P, SupportStats* st, std::
     B.release(cnt); B.release(pos); B.release(scan); B.release(uniq); B.release(role); B.release(inOff); B.release(partial);
     // ---- sort by (in-half, out-half): the digits below the number of half-edges, in both words
     HIPCHK(lap.start());
-    int shifts[8], np = 0; { int b = 0; while (((u64)nh >> b) != 0) b++; for (int p = 0; p < 8; p++) { const int lo = 8 * p; if ((lo & 31) < b) shifts[np++] = lo; } }
+    int shifts[8]; const int np = half_pair_passes(nh, shifts);
     u64* ks = nullptr; u32* vs = nullptr; MateStats ms;
     { const int rc = mate_sort(d, B, key, (u32)R, shifts, np, &ks, &vs, &ms, err); if (rc) return rc; }
     st->passes = ms.passes;
@@ -2822,32 +2825,27 @@ int dev_links_build(Device* d, const LinkParams& P, LinkStats* st, std::string& 
     HIPCHK(lap.start());
     uint8_t* nodeFlag = B.get<uint8_t>((u64)N + 2); u32* uniq = B.get<u32>((u64)N + 2); u32* hCnt = B.get<u32>(nh); u32* hOff = B.get<u32>(nh);
     unsigned long long* ctr = B.get<unsigned long long>(4); u64* partial = B.get<u64>(scan_partial_words(std::max<u64>(nl, nh) + 1));
-    SlLib* libs = B.get<SlLib>(128);
+    MsLib* libs = B.get<MsLib>(128);
     if (!nodeFlag || !uniq || !hCnt || !hOff || !ctr || !partial || !libs) return links_nomem(err);
-    HIPCHK(hipMemsetAsync(nodeFlag, 0, (u64)N + 2, sm)); HIPCHK(hipMemsetAsync(ctr, 0, 4 * sizeof(unsigned long long), sm));
+    HIPCHK(hipMemsetAsync(ctr, 0, 4 * sizeof(unsigned long long), sm));
     const MsTable T = {M->readOff, M->ePair, M->eNf, M->eNr, M->eLoc, M->locs, N};
     const dim3 b256(256);
-    hipLaunchKernelGGL(k_ms_nodes, dim3(grid_for(nh, 256)), b256, 0, sm, g, nh, nodeFlag);
-    hipLaunchKernelGGL(k_ms_unique, dim3(grid_for((u64)N + 1, 256)), b256, 0, sm, T, nodeFlag, uniq);
+    { const int rc = unique_reads(d, g, nh, T, nodeFlag, uniq, err); if (rc) return rc; }
     hipLaunchKernelGGL(k_sl_halves, dim3(grid_for(nh, 256)), b256, 0, sm, g, nh, hCnt, ctr);
     u64 W = 0; { const int rc = scan_u32(d, hCnt, nh, hOff, partial, &W, err); if (rc) return rc; }
     HIPCHK(lap.stop(st->halves_ms));
     B.release(nodeFlag); B.release(hCnt);
     if (!W) { d->links = S.release(); return 0; }
     if (W >= (1ull << 32) - RS_TILE) { err = "scaffold links: more than 2^32 list entries"; return SAGE2OV_ERR_LIMIT; }
-    // ---- the running sums of the whole pool (as dev_readmap_build makes them; not kept there)
+    // ---- the running sums of the whole pool
     HIPCHK(lap.start());
-    u32* dprev = B.get<u32>(nl); u32* scan = B.get<u32>(nl);
-    if (!dprev || !scan) return links_nomem(err);
-    hipLaunchKernelGGL(k_rm_dprev, dim3(grid_for_capped(nl, 256)), b256, 0, sm, g.lists, nl, dprev);
-    { const int rc = scan_u32(d, dprev, nl, scan, partial, nullptr, err); if (rc) return rc; }
+    u32* scan = nullptr; { const int rc = pool_running_sums(d, B, g.lists, nl, partial, scan, links_nomem, err); if (rc) return rc; }
     HIPCHK(lap.stop(st->scan_ms));
-    B.release(dprev);
     // ---- records: count, scan, write
     HIPCHK(lap.start());
-    SlLib hl[128]; for (auto& x : hl) x = SlLib{nullptr, 0, 0, 0, 0};
+    MsLib hl[128]; for (auto& x : hl) x = MsLib{nullptr, 0, 0, 0, 0};
     const u32 nlib = std::min<u32>(P.libraries, 127);
-    for (u32 L = 1; L <= nlib; L++) if (d->mates && d->mates->lib[L].n && P.thr[L] > 0) hl[L] = SlLib{d->mates->lib[L].key, d->mates->lib[L].n, (long long)P.thr[L], P.gbase[L], 0};
+    for (u32 L = 1; L <= nlib; L++) if (d->mates && d->mates->lib[L].n && P.thr[L] > 0) hl[L] = MsLib{d->mates->lib[L].key, d->mates->lib[L].n, (long long)P.thr[L], P.gbase[L], 0};
     HIPCHK(hipMemcpyAsync(libs, hl, sizeof hl, hipMemcpyHostToDevice, sm));
     u32* cnt = B.get<u32>(W); u32* pos = B.get<u32>(W);
     if (!cnt || !pos) return links_nomem(err);
@@ -2866,7 +2864,7 @@ int dev_links_build(Device* d, const LinkParams& P, LinkStats* st, std::string& 
     B.release(cnt); B.release(pos); B.release(scan); B.release(uniq); B.release(hOff);
     // ---- sort by (a, b): the digits below the number of half-edges, in both words; then the values in sorted order and their running sum
     HIPCHK(lap.start());
-    int shifts[8], np = 0; { int b = 0; while (((u64)nh >> b) != 0) b++; for (int p = 0; p < 8; p++) { const int lo = 8 * p; if ((lo & 31) < b) shifts[np++] = lo; } }
+    int shifts[8]; const int np = half_pair_passes(nh, shifts);
     u64* ks = nullptr; u32* vs = nullptr; MateStats ms;
     { const int rc = mate_sort(d, B, key, (u32)R, shifts, np, &ks, &vs, &ms, err); if (rc) return rc; }
     st->passes = ms.passes;

@@ -2259,21 +2259,130 @@ int header_hold(sage2ov_ctx* c) {
     c->hdrGenome = c->ccstats.genome_size; c->hdrReads = c->ccstats.reads_present; c->hdrHeld = true;
     return SAGE2OV_OK;
 }
-// a batch of internal half-edges through the device; afterwards everything made from the graph is stale, the estimate stands and the host copy of the fields is gone
-int merge_apply(sage2ov_ctx* c, const std::vector<uint32_t>& a, const std::vector<uint32_t>& b, int type, std::vector<uint8_t>& out, MergeStats& s) {
+int link_length_threshold(const sage2ov_ctx* c) { return (int)ceilf((float)(100 * ((double)average_read_length(c) / 100.0))); }      // scaffolding.cpp:20
+// a batch of splices on internal half-edges: merges (mergeEdgesAndUpdate) or joins (mergeDisconnectedEdges; gap, and ov comes back), with what the device planned
+struct SpliceBatch {
+    std::vector<uint32_t> a, b; std::vector<int32_t> gap; std::vector<SplicePlan> plan; std::vector<int32_t> ov; SpliceStats s;
+    void clear() { a.clear(); b.clear(); gap.clear(); }
+};
+// the batch through the device (typeOfMerge 0: joins); afterwards everything made from the graph is stale, the estimate stands and the host copy of the fields is gone.
+// The flows come back when the host had them, and after joins always (flows that were all 0 are an array now: the new edges have 1.0)
+int splice_apply(sage2ov_ctx* c, SpliceBatch& B, int typeOfMerge) {
     { const int rc = header_hold(c); if (rc) return rc; }
-    out.assign(a.size(), 0);
-    { const int rc = dev_merge_pairs(c->device(), a.data(), b.data(), a.size(), type, out.data(), &s, c->err); if (rc) return rc; }
-    if (!s.merged) return SAGE2OV_OK;
+    const bool join = typeOfMerge == 0; const uint64_t n = B.a.size();
+    B.plan.assign(n, SplicePlan{}); B.ov.assign(join ? 2 * n : 0, 0); SpliceStats& s = B.s;
+    { const int rc = join ? dev_join_pairs(c->device(), B.a.data(), B.b.data(), B.gap.data(), n, B.plan.data(), B.ov.data(), &s, c->err)
+                          : dev_merge_pairs(c->device(), B.a.data(), B.b.data(), n, typeOfMerge, B.plan.data(), &s, c->err); if (rc) return rc; }
+    if (!s.made) return SAGE2OV_OK;
     const bool est = c->estimated;
     c->rmValid = false; c->pairOrdinal.clear(); c->rmstats = sage2ov_readmap_stats{}; c->supports_forget(); c->links_forget(); c->contigs_forget(); c->copycount_forget();
     c->estimateHeld = est;
     SimplifiedGraph& g = c->g4;
     g.downloaded = g.fields = false; g.lists.clear(); g.lists.shrink_to_fit();
-    g.n_half_edges = s.half_edges; g.pairs_alive += s.merged; g.pairs_alive -= std::min<uint64_t>(g.pairs_alive, s.pairs_deleted);
-    if (!g.flow.empty()) { g.flow.assign(g.n_half_edges, 0.f); const int rc = dev_flow_get(c->device(), g.flow.data(), g.flow.size(), c->err); if (rc) return rc; }
+    g.n_half_edges = s.half_edges; g.pairs_alive += s.made; g.pairs_alive -= std::min<uint64_t>(g.pairs_alive, s.pairs_deleted);
+    if (!join && g.flow.empty()) return SAGE2OV_OK;
+    g.flow.assign(g.n_half_edges, 0.f);
+    return dev_flow_get(c->device(), g.flow.data(), g.flow.size(), c->err);
+}
+// (pair ordinal, reversed) of the two batch entry points -> the half-edges B.a, B.b, with the checks on what a batch may name.  A join also rejects a == b's pair; a
+// merge lets that through, so that the device refuses it without an error
+int splice_operands(sage2ov_ctx* c, const std::string& who, const uint32_t* pf, const uint8_t* fr, const uint32_t* ps, const uint8_t* sr, uint64_t n, bool join, SpliceBatch& B) {
+    { const int rc = dev_simplify_download(c->device(), c->g4, c->err, false); if (rc) return rc; }
+    const SimplifiedGraph& g = c->g4;
+    std::vector<uint32_t> first; g4_save_order(g, first);                              // ordinal -> the half that opens the record pair (a loop has two ordinals, one per half)
+    B.a.resize(n); B.b.resize(n); std::vector<uint8_t> used(g.n_half_edges / 2 + 1, 0);
+    for (uint64_t i = 0; i < n; i++) {
+        if (pf[i] >= first.size() || ps[i] >= first.size()) return c->fail(SAGE2OV_ERR_ARG, who + ": a pair ordinal beyond the record pairs of the graph");
+        const uint32_t a = B.a[i] = first[pf[i]] ^ (fr[i] ? 1u : 0u), b = B.b[i] = first[ps[i]] ^ (sr[i] ? 1u : 0u);
+        if ((join && (a >> 1) == (b >> 1)) || used[a >> 1] || used[b >> 1])
+            return c->fail(SAGE2OV_ERR_ARG, who + (join ? ": a record pair is named twice in the batch" : ": a record pair is named by two merges of the batch"));
+        used[a >> 1] = used[b >> 1] = 1;
+        if (join && (!g.cnt[a] || !g.cnt[b])) return c->fail(SAGE2OV_ERR_ARG, who + ": an operand without a read list (the reference joins composite edges only)");
+        if (!join && g.to[a] != g.from[b]) return c->fail(SAGE2OV_ERR_ARG, who + ": the first edge does not end where the second begins");
+    }
     return SAGE2OV_OK;
 }
+// what a round of merges or of joins (typeOfMerge 0) keeps around its selection rule: the working copy of the half-edge fields, SEARCH with its keys filed under their
+// end nodes, the batch on its way to the device, and the accounting
+extern "C++" { struct SpliceRound {
+    sage2ov_ctx* c; std::string who; int typeOfMerge;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    std::vector<uint32_t> ordBefore, from, to, len, cnt; std::vector<uint8_t> type, alive; std::vector<float> flow;
+    uint32_t nh, devNh;                                                                // the half-edges of the working copy, and of the device's graph (behind by the batch)
+    std::unordered_map<uint64_t, uint32_t> search; std::unordered_multimap<uint32_t, uint64_t> filed;
+    SpliceBatch batch; std::unordered_set<uint32_t> usedPair;
+    std::vector<uint32_t> newHalf; std::vector<SplicePlan> want, plans; std::vector<int32_t> ov;      // of the whole round, in selection order: want as selected, plans and ov as the device made them
+    SpliceStats sum; uint64_t batches = 0; double deviceMs = 0;                        // deviceMs: time spent in the device batches, not selection
+
+    SpliceRound(sage2ov_ctx* ctx, const char* name, int merge) : c(ctx), who(name), typeOfMerge(merge), ordBefore(ctx->pairOrdinal), from(ctx->g4.from), to(ctx->g4.to), len(ctx->g4.len),
+        cnt(ctx->g4.cnt), type(ctx->g4.type), alive(ctx->g4.alive), flow(ctx->g4.flow) { flow.resize(from.size(), 0.f); nh = devNh = (uint32_t)from.size(); }
+    static uint64_t k2(uint64_t x, uint64_t y) { return (x << 32) | y; }
+    uint64_t xk(uint32_t h) const { return (uint64_t)(from[h] ^ to[h]); }
+    uint64_t key(uint32_t h1, uint32_t h2) const { return k2(xk(h1), xk(h2)); }
+    void insert(uint32_t e1, uint32_t e2, uint32_t sup) {                             // the highest support of a key; the key under the four end nodes
+        const uint64_t kk = key(e1, e2);
+        auto it = search.find(kk);
+        if (it == search.end()) search[kk] = sup; else if (sup > it->second) it->second = sup;
+        for (uint32_t nd : {to[e1], from[e1], to[e2], from[e2]}) filed.insert({nd, kk});
+    }
+    int64_t find(uint64_t kk) const { auto it = search.find(kk); return it == search.end() ? -1 : (int64_t)it->second; }
+    bool erase_at(uint32_t node, uint64_t own) {                                       // every key filed under the node goes; true: one that was still there and is not `own`
+        bool others = false;
+        auto its = filed.equal_range(node);
+        for (auto it = its.first; it != its.second; ++it) if (search.erase(it->second) && it->second != own) others = true;
+        return others;
+    }
+    int flush() {
+        if (batch.a.empty()) return SAGE2OV_OK;
+        const auto f0 = std::chrono::steady_clock::now();
+        { const int rc = splice_apply(c, batch, typeOfMerge); if (rc) return rc; }
+        const SpliceStats& s = batch.s;
+        for (const SplicePlan& p : batch.plan) if (!p.made) return c->fail(SAGE2OV_ERR_INTERNAL, who + ": the device refused a merge the selection made");
+        if (s.half_edges != nh) return c->fail(SAGE2OV_ERR_INTERNAL, who + ": the device and the selection disagree on the half-edges");
+        for (size_t i = 0; i < batch.plan.size(); i++) {
+            const SplicePlan &p = batch.plan[i], &w = want[plans.size() + i];
+            if (p.type != w.type || p.del1 != w.del1 || p.del2 != w.del2) return c->fail(SAGE2OV_ERR_INTERNAL, who + ": the device and the selection disagree on a " + (typeOfMerge ? "merge" : "join"));
+        }
+        plans.insert(plans.end(), batch.plan.begin(), batch.plan.end()); ov.insert(ov.end(), batch.ov.begin(), batch.ov.end());
+        sum.entries_copied += s.entries_copied; sum.pairs_deleted += s.pairs_deleted; sum.overlaps += s.overlaps; sum.concatenated += s.concatenated; sum.gapped += s.gapped;
+        sum.overlap_ms += s.overlap_ms; sum.plan_ms += s.plan_ms; sum.lists_ms += s.lists_ms; sum.commit_ms += s.commit_ms; batches++;
+        batch.clear(); usedPair.clear(); devNh = nh;
+        deviceMs += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - f0).count();
+        return SAGE2OV_OK;
+    }
+    // before (e1, e2) is taken: the batch goes first when it names an operand's pair or made one of the operands; the half-edge limit
+    int make_room(uint32_t e1, uint32_t e2) {
+        if (e1 >= devNh || e2 >= devNh || usedPair.count(e1 >> 1) || usedPair.count(e2 >> 1)) { const int rc = flush(); if (rc) return rc; }
+        if ((uint64_t)nh + 2 >= (1ull << 32) - 4096) return c->fail(SAGE2OV_ERR_LIMIT, who + ": more than 2^32 half-edges");
+        return SAGE2OV_OK;
+    }
+    uint32_t push_pair(uint32_t e1, uint32_t e2, uint8_t t, float f) {                 // insertEdge; the lengths of a round's own edges are not read (a join's are the device's to find)
+        const uint32_t h = nh, n = cnt[e1] + cnt[e2] + (to[e1] == from[e2] ? 1u : 2u);
+        from.push_back(from[e1]); to.push_back(to[e2]); type.push_back(t); len.push_back(0); cnt.push_back(n); alive.push_back(1); flow.push_back(f);
+        from.push_back(to[e2]); to.push_back(from[e1]); type.push_back((uint8_t)flip_type_host(t)); len.push_back(0); cnt.push_back(n); alive.push_back(1); flow.push_back(f);
+        nh += 2; return h;
+    }
+    void retire(uint32_t e, bool deleted, float f) { if (deleted) alive[e] = alive[e ^ 1u] = 0; else { flow[e] -= f; flow[e ^ 1u] -= f; } }
+    // the selected splice on the working copy and into the batch; the new forward half
+    uint32_t splice(uint32_t e1, uint32_t e2, uint8_t t, float f, bool del1, bool del2, int32_t gap) {
+        const uint32_t h = push_pair(e1, e2, t, f);
+        retire(e1, del1, f); retire(e2, del2, f);
+        batch.a.push_back(e1); batch.b.push_back(e2); if (!typeOfMerge) batch.gap.push_back(gap);
+        usedPair.insert(e1 >> 1); usedPair.insert(e2 >> 1);
+        SplicePlan w{}; w.type = t; w.del1 = del1; w.del2 = del2; want.push_back(w); newHalf.push_back(h);
+        return h;
+    }
+    // the end of a round: the last batch, the ordinals of the new pairs in the graph as it is now, the counters both kinds of round have
+    template <class Rec, class Counts> int finish(std::vector<Rec>& recs, Counts& R) {
+        { const int rc = flush(); if (rc) return rc; }
+        R.entries_copied = sum.entries_copied; R.pairs_deleted = sum.pairs_deleted; R.batches = batches; R.lists_ms = sum.lists_ms; R.commit_ms = sum.plan_ms + sum.commit_ms;
+        R.select_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - deviceMs;
+        if (recs.empty()) return SAGE2OV_OK;
+        { const int rc = pair_ordinals(c); if (rc) return rc; }
+        for (size_t i = 0; i < recs.size(); i++) recs[i].pair_new = (newHalf[i] >> 1) < c->pairOrdinal.size() ? c->pairOrdinal[newHalf[i] >> 1] : ~0u;
+        return SAGE2OV_OK;
+    }
+}; }
 void counts_add(sage2ov_extend_counts& t, const sage2ov_extend_counts& r) {
     t.entries += r.entries; t.at_threshold += r.at_threshold; t.refused += r.refused; t.blocked += r.blocked; t.merges += r.merges; t.entries_copied += r.entries_copied;
     t.pairs_deleted += r.pairs_deleted; t.batches += r.batches; t.sweep_ms += r.sweep_ms; t.select_ms += r.select_ms; t.lists_ms += r.lists_ms; t.commit_ms += r.commit_ms;
@@ -2285,24 +2394,15 @@ int sage2ov_graph_merge_pairs(sage2ov_ctx* c, const uint32_t* pf, const uint8_t*
     if (n && (!pf || !fr || !ps || !sr)) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_merge_pairs: null argument");
     { const int rc = readmap_check(c, "sage2ov_graph_merge_pairs"); if (rc) return rc; }
     if (n >= (1ull << 31)) return c->fail(SAGE2OV_ERR_LIMIT, "sage2ov_graph_merge_pairs: more merges than there can be pairs");
-    { const int rc = dev_simplify_download(c->device(), c->g4, c->err, false); if (rc) return rc; }
+    SpliceBatch B;
+    { const int rc = splice_operands(c, "sage2ov_graph_merge_pairs", pf, fr, ps, sr, n, false, B); if (rc) return rc; }
     const SimplifiedGraph& g = c->g4;
-    std::vector<uint32_t> first; g4_save_order(g, first);                              // ordinal -> the half that opens the record pair (a loop has two ordinals, one per half)
-    std::vector<uint32_t> a(n), b(n); std::vector<uint8_t> used(g.n_half_edges / 2 + 1, 0);
-    for (uint64_t i = 0; i < n; i++) {
-        if (pf[i] >= first.size() || ps[i] >= first.size()) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_merge_pairs: a pair ordinal beyond the record pairs of the graph");
-        a[i] = first[pf[i]] ^ (fr[i] ? 1u : 0u); b[i] = first[ps[i]] ^ (sr[i] ? 1u : 0u);
-        if (used[a[i] >> 1] || used[b[i] >> 1]) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_merge_pairs: a record pair is named by two merges of the batch");
-        used[a[i] >> 1] = used[b[i] >> 1] = 1;
-        if (g.to[a[i]] != g.from[b[i]]) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_merge_pairs: the first edge does not end where the second begins");
-    }
     for (uint64_t i = 0; i < n; i++)
-        for (uint32_t h : {a[i], b[i]})
+        for (uint32_t h : {B.a[i], B.b[i]})
             if (g.cnt[h] == 0 && (g.len[h] > 0x7FF || g.len[h ^ 1u] > 0x7FF))
                 return c->fail(SAGE2OV_ERR_LIMIT, "sage2ov_graph_merge_pairs: a simple edge longer than 2047 (the 11-bit field of a list entry)");
-    std::vector<uint8_t> out; MergeStats s;
-    { const int rc = merge_apply(c, a, b, type, out, s); if (rc) return rc; }
-    if (merged) for (uint64_t i = 0; i < n; i++) merged[i] = out[i] & 1u;
+    { const int rc = splice_apply(c, B, type); if (rc) return rc; }
+    if (merged) for (uint64_t i = 0; i < n; i++) merged[i] = B.plan[i].made;
     return SAGE2OV_OK;
 }
 int sage2ov_extend_threshold(uint64_t reads, uint64_t arl, uint64_t genomeSize, uint32_t iteration, int* high) {     // mergeContigs.cpp:43-54
@@ -2325,11 +2425,9 @@ int sage2ov_extend_round(sage2ov_ctx* c, int highTh, int lowTh, uint64_t* merged
     std::vector<uint64_t> key(E); std::vector<uint32_t> sup(E);
     { const int rc = dev_support_export(d, key.data(), sup.data(), c->err); if (rc) return rc; }
     { const int rc = pair_ordinals(c); if (rc) return rc; }                           // (the half-edge fields come with it; no read list)
-    const auto t0 = std::chrono::steady_clock::now();
-    const std::vector<uint32_t> ordBefore = c->pairOrdinal;
-    std::vector<uint32_t> from = c->g4.from, to = c->g4.to, cnt = c->g4.cnt; std::vector<uint8_t> type = c->g4.type, alive = c->g4.alive;
-    std::vector<float> flow = c->g4.flow; flow.resize(from.size(), 0.f);
-    uint32_t nh = (uint32_t)from.size(), devNh = nh;
+    SpliceRound S(c, "sage2ov_extend_round", 1);
+    const std::vector<uint32_t>&ordBefore = S.ordBefore, &from = S.from, &to = S.to, &cnt = S.cnt; const std::vector<uint8_t>&type = S.type, &alive = S.alive; const std::vector<float>& flow = S.flow;
+    const uint32_t nh = S.nh;
     // the node lists as the round finds them (alive halves by ascending index; walked backwards: newest first) and the halves the round adds
     std::vector<uint32_t> offs(c->g4.N + 2, 0), adj;
     for (uint32_t h = 0; h < nh; h++) if (alive[h]) offs[from[h] + 1]++;
@@ -2347,33 +2445,12 @@ int sage2ov_extend_round(sage2ov_ctx* c, int highTh, int lowTh, uint64_t* merged
     std::vector<Ent> list;
     for (uint64_t e = 0; e < E; e++) if (sup[e] > 1) { const uint32_t ia = (uint32_t)(key[e] >> 32), ob = (uint32_t)key[e]; list.push_back(Ent{ia ^ 1u, ob, sup[e], from[ia]}); }
     std::sort(list.begin(), list.end(), [](const Ent& x, const Ent& y) { return x.node != y.node ? x.node < y.node : (x.e1 != y.e1 ? x.e1 > y.e1 : x.e2 > y.e2); });
-    auto xk = [&](uint32_t h) -> uint64_t { return (uint64_t)(from[h] ^ to[h]); };
-    auto k2 = [&](uint32_t h1, uint32_t h2) -> uint64_t { return (xk(h1) << 32) | xk(h2); };
-    std::unordered_map<uint64_t, uint32_t> search; std::unordered_multimap<uint32_t, uint64_t> filed;
-    for (const Ent& en : list) {
-        const uint64_t kk = k2(en.e1, en.e2);
-        auto it = search.find(kk);
-        if (it == search.end()) search[kk] = en.sup; else if (en.sup > it->second) it->second = en.sup;
-        for (uint32_t nd : {to[en.e1], from[en.e1], to[en.e2], from[en.e2]}) filed.insert({nd, kk});
-    }
+    auto k2 = [&](uint32_t h1, uint32_t h2) -> uint64_t { return S.key(h1, h2); };
+    for (const Ent& en : list) S.insert(en.e1, en.e2, en.sup);
     std::stable_sort(list.begin(), list.end(), [](const Ent& x, const Ent& y) { return x.sup > y.sup; });
     R.entries = list.size(); for (const Ent& en : list) R.at_threshold += (int64_t)en.sup >= (int64_t)highTh;
-    auto lookup = [&](uint64_t kk) -> int64_t { auto it = search.find(kk); return it == search.end() ? -1 : (int64_t)it->second; };
-    std::unordered_set<uint32_t> blocked, usedPair;
-    std::vector<uint32_t> bA, bB; std::vector<sage2ov_merge> merges; std::vector<uint32_t> newHalf;
-    double selectOut = 0;                                                              // time spent in the device batches, not selection
-    auto flush = [&]() -> int {
-        if (bA.empty()) return SAGE2OV_OK;
-        const auto f0 = std::chrono::steady_clock::now();
-        std::vector<uint8_t> out; MergeStats s;
-        { const int rc = merge_apply(c, bA, bB, 1, out, s); if (rc) return rc; }
-        for (uint8_t o : out) if (!(o & 1u)) return c->fail(SAGE2OV_ERR_INTERNAL, "sage2ov_extend_round: the device refused a merge the selection made");
-        if (s.half_edges != nh) return c->fail(SAGE2OV_ERR_INTERNAL, "sage2ov_extend_round: the device and the selection disagree on the half-edges");
-        R.entries_copied += s.entries_copied; R.pairs_deleted += s.pairs_deleted; R.batches++; R.lists_ms += s.lists_ms; R.commit_ms += s.plan_ms + s.commit_ms;
-        bA.clear(); bB.clear(); usedPair.clear(); devNh = nh;
-        selectOut += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - f0).count();
-        return SAGE2OV_OK;
-    };
+    auto lookup = [&](uint64_t kk) -> int64_t { return S.find(kk); };
+    std::unordered_set<uint32_t> blocked; std::vector<sage2ov_merge> merges;
     for (const Ent& en : list) {
         const uint32_t e1 = en.e1, e2 = en.e2;
         if (!alive[e1] || !alive[e2]) continue;                                        // (difference 3)
@@ -2395,29 +2472,18 @@ int sage2ov_extend_round(sage2ov_ctx* c, int highTh, int lowTh, uint64_t* merged
         walk(node, [&](uint32_t v) { if (to[v] != from[v]) blocked.insert(to[v]); });
         const int t = combined_type(type[e1], type[e2]);
         if (e1 == e2 || e1 == (e2 ^ 1u) || t < 0) continue;                            // mergeEdgesAndUpdate returns NULL
-        if (e1 >= devNh || e2 >= devNh || usedPair.count(e1 >> 1) || usedPair.count(e2 >> 1)) { const int rc = flush(); if (rc) return rc; }
-        if ((uint64_t)nh + 2 >= (1ull << 32) - 4096) return c->fail(SAGE2OV_ERR_LIMIT, "sage2ov_extend_round: more than 2^32 half-edges");
+        { const int rc = S.make_room(e1, e2); if (rc) return rc; }
         const float f1 = flow[e1], f2 = flow[e2], f = (f1 == 0.f && f2 == 0.f) ? 0.f : 1.f;
         sage2ov_merge m{}; m.node = node; m.from = from[e1]; m.to = to[e2]; m.support = en.sup; m.flow = f; m.type = (uint8_t)t;
         m.pair_in = (e1 >> 1) < ordBefore.size() ? ordBefore[e1 >> 1] : ~0u; m.pair_out = (e2 >> 1) < ordBefore.size() ? ordBefore[e2 >> 1] : ~0u; m.pair_new = ~0u;
         m.in_deleted = f1 <= f; m.out_deleted = f2 <= f;
-        from.push_back(from[e1]); to.push_back(to[e2]); type.push_back((uint8_t)t); cnt.push_back(cnt[e1] + cnt[e2] + 1); alive.push_back(1); flow.push_back(f);
-        from.push_back(to[e2]); to.push_back(from[e1]); type.push_back((uint8_t)flip_type_host(t)); cnt.push_back(cnt[e1] + cnt[e2] + 1); alive.push_back(1); flow.push_back(f);
-        if (m.in_deleted) alive[e1] = alive[e1 ^ 1u] = 0; else { flow[e1] -= f; flow[e1 ^ 1u] -= f; }
-        if (m.out_deleted) alive[e2] = alive[e2 ^ 1u] = 0; else { flow[e2] -= f; flow[e2 ^ 1u] -= f; }
-        added[from[nh]].push_back(nh); added[from[nh + 1]].push_back(nh + 1);
-        bA.push_back(e1); bB.push_back(e2); usedPair.insert(e1 >> 1); usedPair.insert(e2 >> 1); usedPair.insert(nh >> 1);
-        merges.push_back(m); newHalf.push_back(nh); nh += 2;
-        auto its = filed.equal_range(node);                                           // (difference 2: the key is the node)
-        for (auto it = its.first; it != its.second; ++it) search.erase(it->second);
+        const uint32_t h = S.splice(e1, e2, (uint8_t)t, f, m.in_deleted, m.out_deleted, 0);
+        added[from[h]].push_back(h); added[from[h + 1]].push_back(h + 1);
+        merges.push_back(m);
+        S.erase_at(node, 0);                                                           // (difference 2: the key is the node)
     }
-    { const int rc = flush(); if (rc) return rc; }
+    { const int rc = S.finish(merges, R); if (rc) return rc; }
     R.merges = merges.size();
-    R.select_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - selectOut;
-    if (!merges.empty()) {
-        { const int rc = pair_ordinals(c); if (rc) return rc; }
-        for (size_t i = 0; i < merges.size(); i++) merges[i].pair_new = (newHalf[i] >> 1) < c->pairOrdinal.size() ? c->pairOrdinal[newHalf[i] >> 1] : ~0u;
-    }
     c->xmerges = std::move(merges);
     c->xstats.rounds++; c->xstats.last = R; counts_add(c->xstats.total, R);
     if (merged) *merged = R.merges;
@@ -2525,7 +2591,7 @@ int sage2ov_links_count(sage2ov_ctx* c, uint32_t mode, uint32_t min_support, uin
     if (mode > SAGE2OV_LINKS_SMALL) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_links_count: mode is one of SAGE2OV_LINKS_ALL, _FINAL, _SMALL");
     { const int rc = links_ensure(c, "sage2ov_links_count"); if (rc) return rc; }
     { const int rc = links_fetch(c); if (rc) return rc; }
-    const int thr = (int)ceilf((float)(100 * ((double)average_read_length(c) / 100.0)));      // scaffolding.cpp:20
+    const int thr = link_length_threshold(c);
     uint64_t m = 0; for (uint64_t e = 0; e < c->links.size(); e++) m += c->links[e].support >= min_support && link_passes(c, e, mode, thr);
     *n = m; return SAGE2OV_OK;
 }
@@ -2534,7 +2600,7 @@ int sage2ov_links_export(sage2ov_ctx* c, uint32_t mode, uint32_t min_support, sa
     uint64_t m = 0; { const int rc = sage2ov_links_count(c, mode, min_support, &m); if (rc) return rc; }
     if (cap < m) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_links_export: the buffer holds fewer rows than the table (sage2ov_links_count)");
     if (m && !out) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_links_export: null argument");
-    const int thr = (int)ceilf((float)(100 * ((double)average_read_length(c) / 100.0)));
+    const int thr = link_length_threshold(c);
     uint64_t at = 0; for (uint64_t e = 0; e < c->links.size(); e++) if (c->links[e].support >= min_support && link_passes(c, e, mode, thr)) out[at++] = c->links[e];
     return SAGE2OV_OK;
 }
@@ -2543,30 +2609,15 @@ int sage2ov_link_stats_get(const sage2ov_ctx* c, sage2ov_link_stats* o) { if (!c
 // ---- step 7: ScaffoldMaker::makeScaffolds (scaffolding.cpp:31-98, :281-482, :488-769); the semantics are stated in sage2ov.h
 namespace {
 static_assert(sizeof(sage2ov_join) == 48 && sizeof(sage2ov_scaffold_counts) == 144 && sizeof(sage2ov_scaffold_stats) == 304, "the records of the scaffold rounds");
-// a batch of internal half-edges through the device; afterwards everything made from the graph is stale, the estimate stands and the host copy of the fields is gone
-int join_apply(sage2ov_ctx* c, const std::vector<uint32_t>& a, const std::vector<uint32_t>& b, const std::vector<int32_t>& gap, std::vector<uint8_t>& out, std::vector<int32_t>& ov, JoinStats& s) {
-    { const int rc = header_hold(c); if (rc) return rc; }
-    out.assign(a.size(), 0); ov.assign(2 * a.size(), 0);
-    { const int rc = dev_join_pairs(c->device(), a.data(), b.data(), gap.data(), a.size(), out.data(), ov.data(), &s, c->err); if (rc) return rc; }
-    if (!s.joined) return SAGE2OV_OK;
-    const bool est = c->estimated;
-    c->rmValid = false; c->pairOrdinal.clear(); c->rmstats = sage2ov_readmap_stats{}; c->supports_forget(); c->links_forget(); c->contigs_forget(); c->copycount_forget();
-    c->estimateHeld = est;
-    SimplifiedGraph& g = c->g4;
-    g.downloaded = g.fields = false; g.lists.clear(); g.lists.shrink_to_fit();
-    g.n_half_edges = s.half_edges; g.pairs_alive += s.joined; g.pairs_alive -= std::min<uint64_t>(g.pairs_alive, s.pairs_deleted);
-    g.flow.assign(g.n_half_edges, 0.f);                                                // (flows that were all 0 are an array now: the new edges have 1.0)
-    return dev_flow_get(c->device(), g.flow.data(), g.flow.size(), c->err);
-}
 void sc_counts_add(sage2ov_scaffold_counts& t, const sage2ov_scaffold_counts& r) {
     t.rows += r.rows; t.below_threshold += r.below_threshold; t.skipped += r.skipped; t.blocked += r.blocked; t.cycles += r.cycles; t.merged += r.merged; t.batches += r.batches;
     t.overlaps += r.overlaps; t.concatenated += r.concatenated; t.gapped += r.gapped; t.outside_reference += r.outside_reference; t.entries_copied += r.entries_copied;
     t.pairs_deleted += r.pairs_deleted; t.sweep_ms += r.sweep_ms; t.select_ms += r.select_ms; t.overlap_ms += r.overlap_ms; t.lists_ms += r.lists_ms; t.commit_ms += r.commit_ms;
 }
 // the checks of the two join entry points on internal half-edges: lengths within 32 bits (the longest read has 1018 bases)
-bool join_length_fits(const SimplifiedGraph& g, uint32_t a, uint32_t b, int32_t gap) {
+bool join_length_fits(uint32_t lenA, uint32_t lenATwin, uint32_t lenB, uint32_t lenBTwin, int32_t gap) {
     const uint64_t add = (uint64_t)std::max<int32_t>(gap, 0) + 2048;
-    return (uint64_t)g.len[a] + g.len[b] + add < (1ull << 32) && (uint64_t)g.len[a ^ 1u] + g.len[b ^ 1u] + add < (1ull << 32);
+    return (uint64_t)lenA + lenB + add < (1ull << 32) && (uint64_t)lenATwin + lenBTwin + add < (1ull << 32);
 }
 }  // namespace
 int sage2ov_graph_join_pairs(sage2ov_ctx* c, const uint32_t* pf, const uint8_t* fr, const uint32_t* ps, const uint8_t* sr, const int32_t* gap, uint64_t n, int32_t* overlap, uint8_t* how) {
@@ -2574,23 +2625,15 @@ int sage2ov_graph_join_pairs(sage2ov_ctx* c, const uint32_t* pf, const uint8_t* 
     if (n && (!pf || !fr || !ps || !sr || !gap)) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_join_pairs: null argument");
     { const int rc = readmap_check(c, "sage2ov_graph_join_pairs"); if (rc) return rc; }
     if (n >= (1ull << 30)) return c->fail(SAGE2OV_ERR_LIMIT, "sage2ov_graph_join_pairs: more joins than there can be pairs");
-    { const int rc = dev_simplify_download(c->device(), c->g4, c->err, false); if (rc) return rc; }
-    const SimplifiedGraph& g = c->g4;
-    std::vector<uint32_t> first; g4_save_order(g, first);
-    std::vector<uint32_t> a(n), b(n); std::vector<int32_t> gp(n); std::vector<uint8_t> used(g.n_half_edges / 2 + 1, 0);
+    SpliceBatch B;
+    { const int rc = splice_operands(c, "sage2ov_graph_join_pairs", pf, fr, ps, sr, n, true, B); if (rc) return rc; }
+    const SimplifiedGraph& g = c->g4; B.gap.assign(gap, gap + n);
+    for (uint64_t i = 0; i < n; i++) { const uint32_t a = B.a[i], b = B.b[i];
+        if (!join_length_fits(g.len[a], g.len[a ^ 1u], g.len[b], g.len[b ^ 1u], gap[i])) return c->fail(SAGE2OV_ERR_LIMIT, "sage2ov_graph_join_pairs: an edge length beyond 32 bits"); }
+    { const int rc = splice_apply(c, B, 0); if (rc) return rc; }
     for (uint64_t i = 0; i < n; i++) {
-        if (pf[i] >= first.size() || ps[i] >= first.size()) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_join_pairs: a pair ordinal beyond the record pairs of the graph");
-        a[i] = first[pf[i]] ^ (fr[i] ? 1u : 0u); b[i] = first[ps[i]] ^ (sr[i] ? 1u : 0u); gp[i] = gap[i];
-        if ((a[i] >> 1) == (b[i] >> 1) || used[a[i] >> 1] || used[b[i] >> 1]) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_join_pairs: a record pair is named twice in the batch");
-        used[a[i] >> 1] = used[b[i] >> 1] = 1;
-        if (!g.cnt[a[i]] || !g.cnt[b[i]]) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_join_pairs: an operand without a read list (the reference joins composite edges only)");
-    }
-    for (uint64_t i = 0; i < n; i++) if (!join_length_fits(g, a[i], b[i], gp[i])) return c->fail(SAGE2OV_ERR_LIMIT, "sage2ov_graph_join_pairs: an edge length beyond 32 bits");
-    std::vector<uint8_t> out; std::vector<int32_t> ov; JoinStats s;
-    { const int rc = join_apply(c, a, b, gp, out, ov, s); if (rc) return rc; }
-    for (uint64_t i = 0; i < n; i++) {
-        if (overlap) { overlap[2 * i] = ov[2 * i]; overlap[2 * i + 1] = ov[2 * i + 1]; }
-        if (how) { how[2 * i] = (out[i] >> 4) & 3u; how[2 * i + 1] = (out[i] >> 6) & 3u; }
+        if (overlap) { overlap[2 * i] = B.ov[2 * i]; overlap[2 * i + 1] = B.ov[2 * i + 1]; }
+        if (how) { how[2 * i] = B.plan[i].how[0]; how[2 * i + 1] = B.plan[i].how[1]; }
     }
     return SAGE2OV_OK;
 }
@@ -2610,17 +2653,14 @@ int sage2ov_scaffold_round(sage2ov_ctx* c, int highTh, int flag, int small, uint
     { const int rc = links_ensure(c, "sage2ov_scaffold_round"); if (rc) return rc; }
     { const int rc = links_fetch(c); if (rc) return rc; }                             // (pair_ordinals and the half-edge fields come with it; no read list)
     if (swept) R.sweep_ms = c->lstats.halves_ms + c->lstats.scan_ms + c->lstats.records_ms + c->lstats.sort_ms + c->lstats.reduce_ms;
-    const auto t0 = std::chrono::steady_clock::now();
-    const std::vector<uint32_t> ordBefore = c->pairOrdinal;
-    std::vector<uint32_t> from = c->g4.from, to = c->g4.to, len = c->g4.len; std::vector<uint8_t> type = c->g4.type, alive = c->g4.alive;
-    std::vector<float> flow = c->g4.flow; flow.resize(from.size(), 0.f);
-    uint32_t nh = (uint32_t)from.size();
+    SpliceRound S(c, "sage2ov_scaffold_round", 0);
+    const std::vector<uint32_t>&ordBefore = S.ordBefore, &from = S.from, &to = S.to, &len = S.len; const std::vector<uint8_t>&type = S.type, &alive = S.alive; const std::vector<float>& flow = S.flow;
     std::vector<uint32_t> firstOf; g4_save_order(c->g4, firstOf);                      // ordinal -> the half that opens the record pair
     auto isE = [&](uint32_t h) -> bool { return from[h] < to[h] || (from[h] == to[h] && (h & 1u)); };      // the half the read-to-edge table names; a loop: the higher index
     // the rows by rule (a) in export order, FEASIBLE from the unfiltered table, SEARCH and the rows filed under their end nodes
     struct Row { uint32_t e1, e2, sup; int32_t gap; uint64_t lenSum; };
     std::vector<Row> rows; std::unordered_map<uint32_t, std::vector<uint32_t>> feasible;
-    const int thr = (int)ceilf((float)(100 * ((double)average_read_length(c) / 100.0)));
+    const int thr = link_length_threshold(c);
     const uint32_t mode = small ? SAGE2OV_LINKS_SMALL : SAGE2OV_LINKS_FINAL;
     for (uint64_t e = 0; e < c->links.size(); e++) {
         const sage2ov_link& L = c->links[e]; if (!L.support) continue;
@@ -2629,46 +2669,20 @@ int sage2ov_scaffold_round(sage2ov_ctx* c, int highTh, int flag, int small, uint
         auto& fb = feasible[b >> 1]; if (std::find(fb.begin(), fb.end(), a >> 1) == fb.end()) fb.push_back(a >> 1);
         if (a < b && link_passes(c, e, mode, thr)) rows.push_back(Row{a ^ 1u, b, L.support, L.gap, (uint64_t)len[a ^ 1u] + len[b]});
     }
-    auto xk = [&](uint32_t h) -> uint64_t { return (uint64_t)(from[h] ^ to[h]); };
-    auto k2 = [&](uint64_t x, uint64_t y) -> uint64_t { return (x << 32) | y; };
-    std::unordered_map<uint64_t, uint32_t> search; std::unordered_multimap<uint32_t, uint64_t> filed;
-    for (const Row& r : rows) {
-        const uint64_t kk = k2(xk(r.e1), xk(r.e2));
-        auto it = search.find(kk);
-        if (it == search.end()) search[kk] = r.sup; else if (r.sup > it->second) it->second = r.sup;
-        for (uint32_t nd : {to[r.e1], from[r.e1], to[r.e2], from[r.e2]}) filed.insert({nd, kk});
-    }
+    auto xk = [&](uint32_t h) -> uint64_t { return S.xk(h); };
+    auto k2 = [&](uint64_t x, uint64_t y) -> uint64_t { return SpliceRound::k2(x, y); };
+    for (const Row& r : rows) S.insert(r.e1, r.e2, r.sup);
     std::stable_sort(rows.begin(), rows.end(), [](const Row& x, const Row& y) { return x.sup != y.sup ? x.sup > y.sup : x.lenSum > y.lenSum; });
     R.rows = rows.size();
-    auto lookup = [&](uint64_t x, uint64_t y) -> int64_t { auto it = search.find(k2(x, y)); if (it == search.end()) it = search.find(k2(y, x)); return it == search.end() ? 0 : (int64_t)it->second; };
-    std::unordered_set<uint32_t> spent, usedPair;
-    std::vector<uint32_t> bA, bB; std::vector<int32_t> bG; std::vector<sage2ov_join> joins; std::vector<uint32_t> newHalf; size_t applied = 0;
-    double selectOut = 0;
-    auto flush = [&]() -> int {
-        if (bA.empty()) return SAGE2OV_OK;
-        const auto f0 = std::chrono::steady_clock::now();
-        std::vector<uint8_t> out; std::vector<int32_t> ov; JoinStats s;
-        { const int rc = join_apply(c, bA, bB, bG, out, ov, s); if (rc) return rc; }
-        if (s.half_edges != nh) return c->fail(SAGE2OV_ERR_INTERNAL, "sage2ov_scaffold_round: the device and the selection disagree on the half-edges");
-        for (size_t i = 0; i < bA.size(); i++) {
-            sage2ov_join& j = joins[applied + i];
-            j.overlap_forward = ov[2 * i]; j.overlap_twin = ov[2 * i + 1]; j.how_forward = (out[i] >> 4) & 3u; j.how_twin = (out[i] >> 6) & 3u;
-            if (j.type != ((out[i] >> 2) & 3u) || j.first_deleted != (out[i] & 1u) || j.second_deleted != ((out[i] >> 1) & 1u))
-                return c->fail(SAGE2OV_ERR_INTERNAL, "sage2ov_scaffold_round: the device and the selection disagree on a join");
-        }
-        applied += bA.size();
-        R.entries_copied += s.entries_copied; R.pairs_deleted += s.pairs_deleted; R.batches++; R.overlaps += s.overlaps; R.concatenated += s.concatenated; R.gapped += s.gapped;
-        R.overlap_ms += s.overlap_ms; R.lists_ms += s.lists_ms; R.commit_ms += s.plan_ms + s.commit_ms;
-        bA.clear(); bB.clear(); bG.clear(); usedPair.clear();
-        selectOut += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - f0).count();
-        return SAGE2OV_OK;
-    };
+    auto present = [&](uint64_t x, uint64_t y) -> int64_t { const int64_t s = S.find(k2(x, y)); return s < 0 ? S.find(k2(y, x)) : s; };      // in either order; -1: in neither
+    auto lookup = [&](uint64_t x, uint64_t y) -> int64_t { return std::max<int64_t>(present(x, y), 0); };
+    std::unordered_set<uint32_t> spent; std::vector<sage2ov_join> joins;
     const uint64_t limit = flag == 1 ? 1 : 2;
     static const std::vector<uint32_t> none;
     for (const Row& r : rows) {
         const uint32_t e1 = r.e1, e2 = r.e2;
         if (!alive[e1] || !alive[e2]) { R.outside_reference = 1; R.skipped++; continue; }      // (d)
-        if (search.find(k2(xk(e1), xk(e2))) == search.end()) { R.skipped++; continue; }
+        if (S.find(k2(xk(e1), xk(e2))) < 0) { R.skipped++; continue; }
         if ((int64_t)r.sup < (int64_t)highTh) { R.below_threshold++; continue; }
         const uint32_t p1 = e1 >> 1, p2 = e2 >> 1;
         auto feas = [&](uint32_t p) -> const std::vector<uint32_t>& { if (spent.count(p)) return none; auto it = feasible.find(p); return it == feasible.end() ? none : it->second; };
@@ -2679,38 +2693,29 @@ int sage2ov_scaffold_round(sage2ov_ctx* c, int highTh, int flag, int small, uint
         }
         for (uint32_t q : feas(p2)) {
             if (spent.count(q) || (q == p1 && isE(e1))) continue;
-            auto it = search.find(k2(xk(2 * q), xk(e2))); if (it == search.end()) it = search.find(k2(xk(e2), xk(2 * q)));
-            if (it != search.end() && (int64_t)it->second >= (int64_t)highTh) { count1++; if (std::find(side2.begin(), side2.end(), q) != side2.end()) cycle = true; }
+            const int64_t s = present(xk(2 * q), xk(e2));
+            if (s >= 0 && s >= (int64_t)highTh) { count1++; if (std::find(side2.begin(), side2.end(), q) != side2.end()) cycle = true; }
         }
         if (cycle) { R.cycles++; continue; }
         if (count1 > limit || count2 > limit) { R.blocked++; continue; }
-        if (usedPair.count(p1) || usedPair.count(p2)) { const int rc = flush(); if (rc) return rc; }      // (e): only a kept operand can be named again, the rows are older than the round's edges
-        if ((uint64_t)nh + 2 >= (1ull << 32) - 4096) return c->fail(SAGE2OV_ERR_LIMIT, "sage2ov_scaffold_round: more than 2^32 half-edges");
-        { SimplifiedGraph tmp; tmp.len = {len[e1], len[e1 ^ 1u], len[e2], len[e2 ^ 1u]};
-          if (!join_length_fits(tmp, 0, 2, r.gap)) return c->fail(SAGE2OV_ERR_LIMIT, "sage2ov_scaffold_round: an edge length beyond 32 bits"); }
+        { const int rc = S.make_room(e1, e2); if (rc) return rc; }                     // (e): only a kept operand can be named again, the rows are older than the round's edges
+        if (!join_length_fits(len[e1], len[e1 ^ 1u], len[e2], len[e2 ^ 1u], r.gap)) return c->fail(SAGE2OV_ERR_LIMIT, "sage2ov_scaffold_round: an edge length beyond 32 bits");
         const uint32_t t1 = type[e1], t2 = type[e2], t = ((t1 == 2 || t1 == 3) ? 2u : 0u) | ((t2 == 1 || t2 == 3) ? 1u : 0u), node = to[e1];
         sage2ov_join m{}; m.from = from[e1]; m.to = to[e2]; m.support = r.sup; m.gap = r.gap; m.type = (uint8_t)t;
         m.pair_first = ordBefore[p1]; m.pair_second = ordBefore[p2]; m.pair_new = ~0u;
         m.first_deleted = flow[e1] <= 1.0f; m.second_deleted = flow[e2] <= 1.0f;
-        from.push_back(from[e1]); to.push_back(to[e2]); type.push_back((uint8_t)t); len.push_back(0); alive.push_back(1); flow.push_back(1.0f);
-        from.push_back(to[e2]); to.push_back(from[e1]); type.push_back((uint8_t)flip_type_host((int)t)); len.push_back(0); alive.push_back(1); flow.push_back(1.0f);
-        if (m.first_deleted) alive[e1] = alive[e1 ^ 1u] = 0; else { flow[e1] -= 1.0f; flow[e1 ^ 1u] -= 1.0f; }
-        if (m.second_deleted) alive[e2] = alive[e2 ^ 1u] = 0; else { flow[e2] -= 1.0f; flow[e2 ^ 1u] -= 1.0f; }
-        bA.push_back(e1); bB.push_back(e2); bG.push_back(r.gap); usedPair.insert(p1); usedPair.insert(p2);
+        const uint64_t own = k2(xk(e1), xk(e2));
+        S.splice(e1, e2, (uint8_t)t, 1.0f, m.first_deleted, m.second_deleted, r.gap);
         spent.insert(p1); spent.insert(p2);
-        joins.push_back(m); newHalf.push_back(nh); nh += 2;
-        const uint64_t own = k2(xk(e1), xk(e2)); bool others = false;
-        auto its = filed.equal_range(node);
-        for (auto it = its.first; it != its.second; ++it) if (search.erase(it->second) && it->second != own) others = true;
-        if (m.first_deleted && others) R.outside_reference = 1;                        // (d): the reference reads the erase key from the freed edge_1 (:607)
+        joins.push_back(m);
+        if (S.erase_at(node, own) && m.first_deleted) R.outside_reference = 1;        // (d): the reference reads the erase key from the freed edge_1 (:607)
     }
-    { const int rc = flush(); if (rc) return rc; }
-    R.merged = joins.size();
-    R.select_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - selectOut;
-    if (!joins.empty()) {
-        { const int rc = pair_ordinals(c); if (rc) return rc; }
-        for (size_t i = 0; i < joins.size(); i++) joins[i].pair_new = (newHalf[i] >> 1) < c->pairOrdinal.size() ? c->pairOrdinal[newHalf[i] >> 1] : ~0u;
+    { const int rc = S.finish(joins, R); if (rc) return rc; }
+    for (size_t i = 0; i < joins.size(); i++) {
+        sage2ov_join& j = joins[i]; const SplicePlan& p = S.plans[i];
+        j.overlap_forward = S.ov[2 * i]; j.overlap_twin = S.ov[2 * i + 1]; j.how_forward = p.how[0]; j.how_twin = p.how[1];
     }
+    R.merged = joins.size(); R.overlaps = S.sum.overlaps; R.concatenated = S.sum.concatenated; R.gapped = S.sum.gapped; R.overlap_ms = S.sum.overlap_ms;
     c->scjoins = std::move(joins);
     c->scstats.rounds++; c->scstats.last = R; sc_counts_add(c->scstats.total, R);
     if (merged) *merged = R.merged;

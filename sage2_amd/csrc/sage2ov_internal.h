@@ -166,14 +166,21 @@ struct SimplifiedGraph {
 };
 int dev_simplify(Device* d, SimplifiedGraph& out, std::string& err);             // result stays in HBM
 int dev_simplify_download(Device* d, SimplifiedGraph& out, std::string& err, bool withLists = true);    // fills the arrays (once); withLists false: the half-edge fields only
-// ContigExtender::mergeEdgesAndUpdate for a batch of edge-disjoint merges over the resident graph (sage2ov_graph_merge_pairs; kernels_merge.inc)
-struct MergeStats { uint64_t merged = 0, entries_copied = 0, pairs_deleted = 0, half_edges = 0, list_entries = 0; double plan_ms = 0, lists_ms = 0, commit_ms = 0; };
-int dev_merge_pairs(Device* d, const uint32_t* a, const uint32_t* b, uint64_t n, int typeOfMerge, uint8_t* out, MergeStats* st, std::string& err);
-// ScaffoldMaker::mergeDisconnectedEdges for a batch of edge-disjoint joins over the resident graph and the read store (sage2ov_graph_join_pairs; DESIGN.md 5.17;
-// kernels_scaffold.inc).  overlap (may be null): 2 n values, what stringOverlapSize returned for the forward and the twin list (-2: equal end nodes, no search)
-struct JoinStats { uint64_t joined = 0, entries_copied = 0, pairs_deleted = 0, half_edges = 0, list_entries = 0, overlaps = 0, concatenated = 0, gapped = 0;
-                   double overlap_ms = 0, plan_ms = 0, lists_ms = 0, commit_ms = 0; };
-int dev_join_pairs(Device* d, const uint32_t* a, const uint32_t* b, const int32_t* gap, uint64_t n, uint8_t* out, int32_t* overlap, JoinStats* st, std::string& err);
+// A batch of edge-disjoint splices over the resident graph (kernels_splice.inc): a splice makes a new pair of half-edges from the operand
+// half-edges a and b and retires them.  SplicePlan is what the plan kernel of either kind writes for one splice and what the device hands back.
+//   made: 0 for a refused merge, always 1 for a join;  type, del1, del2: the new pair's type, whether a's and b's pair were deleted (else they lost `flow`);
+//   flow: the flow of the new edge;  lenF, lenT: the lengths of the new forward half and its twin;  extra: the entries between the operands' lists (1: a merge, a join
+//   with equal end nodes; 2: a join);  dNext1, dPrev2, how: per direction (forward, twin), the distances between a join's two middle entries and how it was made
+//   (0 equal end nodes, 1 overlap, 2 concatenated, 3 gapped)
+struct SplicePlan { uint32_t a, b; float flow; uint32_t lenF, lenT, dNext1[2], dPrev2[2]; uint8_t type, made, del1, del2, extra, how[2], pad; };
+static_assert(sizeof(SplicePlan) == 44, "the splice record as the device writes it");
+struct SpliceStats { uint64_t made = 0, entries_copied = 0, pairs_deleted = 0, half_edges = 0, list_entries = 0, overlaps = 0, concatenated = 0, gapped = 0;
+                     double overlap_ms = 0, plan_ms = 0, lists_ms = 0, commit_ms = 0; };
+// ContigExtender::mergeEdgesAndUpdate for a batch of merges (sage2ov_graph_merge_pairs; k_mg_plan)
+int dev_merge_pairs(Device* d, const uint32_t* a, const uint32_t* b, uint64_t n, int typeOfMerge, SplicePlan* out, SpliceStats* st, std::string& err);
+// ScaffoldMaker::mergeDisconnectedEdges for a batch of joins over the graph and the read store (sage2ov_graph_join_pairs; kernels_scaffold.inc).  overlap (may be
+// null): 2 n values, what stringOverlapSize returned for the forward and the twin list (-2: equal end nodes, no search)
+int dev_join_pairs(Device* d, const uint32_t* a, const uint32_t* b, const int32_t* gap, uint64_t n, SplicePlan* out, int32_t* overlap, SpliceStats* st, std::string& err);
 void dev_simplify_release(Device* d);
 int dev_simplify_upload(Device* d, const SimplifiedGraph& in, std::string& err);  // a parsed graph (from .. lists filled) takes the place of step 4's result in HBM
 // MatePair::mapReadsToEdges / mapReadLocations / computeMeanSD on the device (sage2ov_mates_map_reads, _estimate): dev_readmap_build makes the

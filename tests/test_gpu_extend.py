@@ -170,8 +170,23 @@ def test_primitive_rows_flows_simple_edges_and_refusals(tmp_path):
     ctx.close()
 
 
+def test_one_batch_with_simple_operands_on_either_side(tmp_path):
+    """one batch whose merges have a simple e1, a simple e2, both and neither among composite ones: the middle entry takes its distances from the neighbouring
+    list entry, or from the length of the operand that has no list"""
+    N, header, recs = chains()
+    ctx, g, hdr = start(N, header, recs, None, tmp_path)
+    js = [5, 0, 6, 2, 11]
+    assert {(CASES[j][4] > 0, CASES[j][5] > 0) for j in js} == {(False, True), (True, False), (False, False), (True, True)}
+    halves = [(4 * j, 4 * j + 2) for j in js]
+    f, s_ = operands(g, halves)
+    want = [0 if g.merge(a, b) is None else 1 for a, b in halves]
+    assert ctx.merge_pairs(f, s_).tolist() == want == [1] * len(js)
+    assert saved6(ctx, tmp_path) == g.text(hdr) and np.array_equal(ctx.graph_flows(), g.flows())
+    ctx.close()
+
+
 def test_a_batch_of_many_blocks(tmp_path):
-    """hundreds of merges in one batch (k_mg_plan and k_mg_commit on several blocks, thousands of list entries): one entering and one leaving half per node, no pair
+    """hundreds of merges in one batch (k_mg_plan and k_sp_commit on several blocks, thousands of list entries): one entering and one leaving half per node, no pair
     twice, whatever their types -- the refused ones stand among the merged ones"""
     N, header, recs = CG.case_a_pairs(1500)
     ctx, g, hdr = start(N, header, recs, None, tmp_path, seed=9)

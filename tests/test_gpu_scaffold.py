@@ -155,6 +155,40 @@ def test_a_batch_that_crosses_a_pool_reallocation_and_ordinals_in_save_order(tmp
     ctx.close()
 
 
+def test_merges_then_joins_on_one_graph_whose_flows_are_all_zero(tmp_path):
+    """a batch of merges, one of them refused (the rank of a new pair is not its index), then a batch of joins on the same context: an operand the merges made,
+    equal end nodes (one middle entry on the join path), a negative and a positive gap.  Every flow is 0: the merged edges have 0, the joined ones 1.0, and every
+    operand goes"""
+    cases = uniform_cases() + [(SH.rnd(60, 30000 + 2 * n), SH.rnd(60, 30001 + 2 * n), None) for n in range(4)]; strings = distinct(cases)
+    nc = len(cases); fillers = [SH.rnd(60, 5000 + i) for i in range(5 * nc + 25)]
+    ctx, seqs, where = chosen_store(list(strings) + fillers, k=40)
+    fid = [where[x][0] for x in fillers]
+    recs = components([(s1, s2_, 0, 0, n) for n, (s1, s2_, _) in enumerate(cases)], where, fid)
+    # five chains u -> v -> w of two composite edges that meet in v: pool halves 4 nc + 4 j (into v) and 4 nc + 4 j + 2 (out of v); (3, 0) is no row of combinedEdgeType
+    for j, (t1, t2) in enumerate([(3, 3), (3, 0), (0, 1), (2, 0), (3, 3)]):
+        u, v, w, r1, r2 = fid[5 * nc + 5 * j:5 * nc + 5 * j + 5]
+        for r in (H.rec(u, v, t1, 90 + j, [(r1, 1, 0, 20, 70 + j)]), H.rec(v, w, t2, 80 + j, [(r2, 0, 0, 11, 69 + j)])):
+            recs += [r, H.twin_of(r)]
+    g, hdr = loaded(ctx, (0, 400, 60), recs, tmp_path)
+    assert not ctx.graph_flows().any()
+    chain = [(4 * nc + 4 * j, 4 * nc + 4 * j + 2) for j in range(5)]
+    f, s_ = operands(g, chain[:4])
+    want = [0 if g.merge(a, b) is None else 1 for a, b in chain[:4]]
+    assert ctx.merge_pairs(f, s_).tolist() == want == [1, 0, 1, 1]
+    assert not ctx.graph_flows().any() and saved6(ctx, tmp_path, "a.graph6") == g.text(hdr)
+    made = len(g.h) - 6                                                               # the pair of chain 0; chain 2's is the second new pair, not the third
+    assert g.h[made + 2]["frm"] == g.h[chain[2][0]]["frm"] and g.h[made + 2]["to"] == g.h[chain[2][1]]["to"]
+    halves = [(made, 4 * 5), chain[4], (4 * 1, 4 * 1 + 2), (4 * 3, 4 * 3 + 2)]; gaps = [0, 3, -1, 12]
+    (ov, how), (mo, mh) = join_both(ctx, g, seqs, halves, gaps)
+    assert ov == mo and how == mh
+    assert ov[1] == [-2, -2] and how[1] == [SM.EQUAL, SM.EQUAL] and (ov[2][0], how[2][0]) == (-1, SM.CONCAT) and (ov[3][0], how[3][0]) == (-1, SM.GAPPED)
+    assert saved6(ctx, tmp_path, "b.graph6") == g.text(hdr)
+    fl = ctx.graph_flows()
+    assert np.array_equal(fl, g.flows()) and set(fl.tolist()) == {0.0, 1.0} and fl.sum() == 8.0 and all(h["flow"] == 1.0 for h in g.h[-8:])
+    assert not any(g.alive[e >> 1] for ab in halves for e in ab) and ctx.simplify_stats().edges == sum(g.alive)
+    ctx.close()
+
+
 # ------------------------------------------------------------------------------------------ rounds
 def hand_start(tmp_path, seed=5, name="h.graph4", **kw):
     N, header, recs, pairs, _ = SH.hand(**kw)
