@@ -557,7 +557,7 @@ int sage2ov_contig_stats_get(const sage2ov_ctx* ctx, sage2ov_contig_stats* out);
 
 /* ---- the first loop of ContigExtender::extendContigs (matePair/mergeContigs.cpp:47-60): findMatepairSupports as a whole (:959-1030) -- the sweep above, the selection
  * of mergeByMatepairSupports (:1112-1255) and mergeEdgesAndUpdate (:1260-1469) applied on the device to the resident step-4 graph -- run until a round
- * merges nothing.  findPathSupports, findPathSupportsNew and mergeShortOverlaps (:62-) are not part of this library.
+ * merges nothing.  findPathSupports and findPathSupportsNew (:62-99) are PATH SUPPORTS, below; mergeShortOverlaps (:101-) is not part of this library.
  *   MERGE (e1, e2), e1 entering a node and e2 leaving it (mergeEdgesAndUpdate, overlapGraph.cpp:165-186, :259-266, :299-336): refused (no error, nothing changes) when
  *   e1 == e2, e1 == e2's twin, either is dead, or combinedEdgeType is -1 -- the valid rows are (e1 type, e2 type) -> (0,0) 0, (1,2) 0, (0,1) 1, (1,3) 1, (2,0) 2, (3,2) 2,
  *   (2,1) 3, (3,3) 3.  isReducible is 1 on every edge the loader, step 4 and a merge make (insertEdge sets it, nothing here clears it): no field is carried.
@@ -589,7 +589,7 @@ int sage2ov_contig_stats_get(const sage2ov_ctx* ctx, sage2ov_contig_stats* out);
  * reference's mergeByMatepairSupports handed the list in this order.  (2) :1233 reads edge1->ID after mergeEdgesAndUpdate may have freed edge1; HERE the erase key is
  * always the node.  Equality is claimed for rounds in which no merge deletes its in-edge while another entry at the same node is still listed.  (3) An entry whose key
  * is listed through an XOR collision but whose edges are dead is skipped (the reference reads freed memory).  (4) The mate flags describe the merged graph after
- * the table is rebuilt; the reference keeps those of meanSdEstimation.  Nothing here reads them after the estimate. */
+ * the table is rebuilt; the reference keeps those of meanSdEstimation.  The first loop does not read them; PATH SUPPORTS, below, reads the copy kept with the estimate. */
 typedef struct sage2ov_merge {         /* one merge of the last round, 40 bytes */
     uint32_t node, from, to;           /* the shared node; the new edge's ends (edge1.from, edge2.to) */
     uint32_t support;
@@ -636,6 +636,82 @@ int sage2ov_extend_stats_get(const sage2ov_ctx* ctx, sage2ov_extend_stats* out);
  * would have written before the first merge (the reference's genomeSize and numberOfReads do not change in step 6); on a graph without a merge it is an alias.
  * It serves after sage2ov_graph_join_pairs and the scaffold rounds too: the resident graph with the same two header lines (the reference has no file for that state). */
 int sage2ov_graph6_save(sage2ov_ctx* ctx, const char* path);
+
+/* ---- PATH SUPPORTS: the second and third loop of ContigExtender::extendContigs (matePair/mergeContigs.cpp:62-99): findPathSupports (:118-353) with mergeByPathSupports
+ * (:794-952) and findPathSupportsNew (:2148-) with mergeByPathSupportsNew (:2388-2546), on the device.  They extend contigs past forks whose branches
+ * are too short to carry their own mates: a mate pair votes for the consecutive edge pairs that every feasible path between its two reads has in common.  All citations
+ * are matePair/mergeContigs.cpp; all quantities are integers except flows.  Equality is with the reference at ONE thread (its flag[] array is raced with more).
+ *   ESTIMATE FLAGS.  MatePairInfo::flag is cleared by mapReadsToEdges when both mates have an entry for one edge (matePair.cpp:461-481) and never set again: after merges it
+ *   still describes the graph of meanSdEstimation.  HERE a copy of every library's flags as of the last sage2ov_mates_estimate is kept with the estimate (it survives
+ *   merges and goes when the estimate goes); sage2ov_mates_flags_export keeps describing the graph as it now is.
+ *   CLAIM (:190-216).  For every alive half-edge h with a list, walk the list with the running sum of distPrevious and stop at the first entry whose sum is above
+ *   maximumUpperBoundOfInsert.  Every entry walked offers its read the node min(from[h], to[h]); claim[r] is the smallest node offered, or none.  No uniqueness test, no flow.
+ *   START NODES of node i (:220-239): both end nodes of every record pair for which a read claimed by i has a read-to-edge entry, each once, HERE in ascending order.
+ *   PATHS of node i (exploreGraph :359-387, checkFlow :403-415, savePath :420-429): a depth-first walk from each start node s.  Level 1 takes the alive halves v leaving s
+ *   that have a list and flow > 0 and saves [v] with length 0.  Level L <= 7 appends an alive v leaving the previous edge's end when matchEdgeType(prev, v) holds, checkFlow
+ *   holds -- with uses = the number of times v or its twin already stands in the path: uses <= flow[v] for a v without a list, uses < flow[v] for one with a list, the flow
+ *   being v's own float -- and len_before(prev) + len[prev] < maximumUpperBoundOfInsert (strict).  Every extension is saved with path length = the summed lengths of all
+ *   its edges but the last.  Adjacency is newest first.  A call at any level returns at once when the node's saved paths so far exceed 1000 (:362); the count is shared by
+ *   all start nodes of i, and a call that has begun still saves one path per remaining sibling.
+ *   PAIR VOTES (:254-300, findPathsBetweenMatepairs :539-670, insertPath :699-743).  A mate entry (m1 -> m2, type1, type2, library L) votes at node i = claim[m1] when its
+ *   estimate flag is 1, L is valid, claim[m2] is none or greater than i (equal claims do not vote; the mirrored entry votes from its side only when claim[m2] < claim[m1]),
+ *   and m1 is UNIQUE ON its pair p1 and m2 on p2 (:1102-1110, as for sage2ov_mates_supports: that includes that neither read is a node with an alive edge).  The four
+ *   combinations are taken in the order of :565-586, edge1 in {E(p1), its twin}, edge2 in {E(p2), its twin}.  For each: d1 = the locations of m1 on the twin of edge1, d2 =
+ *   those of m2 on edge2 (findDistanceOnEdge), both non-empty.  The QUALIFYING PATHS are the saved paths of node i that start at node to[edge1], have a first edge that
+ *   matchEdgeType(edge1, .) accepts and end in the half edge2 itself, and for which some x in d1, y in d2 have lower[L] < D < upper[L] (both strict), D = |x| + |y| + path
+ *   length when s1 * x < 0 and s2 * y < 0, else D = 100 000 (the reference's initial value, :614: it matters only for a library with upper[L] > 100 000).  Each qualifying
+ *   path is read as the edge sequence edge1, path[1..n].  The entry's SURVIVORS are the consecutive pairs (a, b) of the first qualifying path that occur in every other
+ *   qualifying path, over all four combinations, as (a, b) or as (twin of b, twin of a).  No qualifying path, or no survivor: no vote.  Each survivor gets +1, once per
+ *   mate entry whatever its count.
+ *   THE TABLE: one row per ordered pair of halves (a enters a node, b leaves it) with votes >= 1, in ascending (node, a newest first, b newest first).
+ *   A ROUND (variant 0: mergeByPathSupports, 1: mergeByPathSupportsNew).  SEARCH maps the XOR key of :283-284 to the summed support of the rows that share it; every row is
+ *   filed under its four end nodes.  For each row in ORDER: skip when its key has left SEARCH; skip when node = to[a] is BLOCKED; skip (no stop) when support < high;
+ *   otherwise over the node's alive halves v with flow >= 1 and from != to (no list is required, :837): ins = the twins v' != a that match b, outs = the v != b that a
+ *   matches, inSupp / outSupp from SEARCH with the mirrored fall-back of :859-871, uniqueIn / uniqueOut = none above low.  Variant 0 merges when both are unique,
+ *   variant 1 when at least one is (:2504).  A merge blocks the `to` of every alive non-loop half of the node and runs MERGE(a, b, 1) of the first loop; when it is not
+ *   refused, every row filed under the node leaves SEARCH.  The merges of a round go to the device as one batch, as for sage2ov_extend_round; the estimate and its
+ *   flags stand.
+ *   LOOPS (:62-99): rounds with the thresholds of sage2ov_extend_threshold by iteration, low 1, until a round merges <= stop; stop = 10 when genome_size > 10^9, else 0.
+ * DELIBERATE DIFFERENCES, each with a counter that is 0 where equality is claimed: (1) ORDER (order_dependent): the reference walks an unordered_map in bucket order; HERE
+ * rows go by support descending, ties in table order.  Equality is claimed for rounds in which the rows with support >= high sit at pairwise different nodes and none of
+ * those nodes is an end of another such row's halves.  (2) XOR keys (key_collisions = rows - distinct keys): the reference's map holds one entry per key with the edges
+ * of the last writer; HERE rows are exact.  (3) Cap (capped_nodes): the reference explores start nodes in the order of its linked lists, HERE ascending; it matters only
+ * for a node that saves more than 1000 paths (the reference's path array has 2000 rows and no check; HERE the pool is sized by a counting pass).  (4) Mirror (mirrored):
+ * which path comes first follows an unstable quicksort (:434-478) in the reference, HERE enumeration order; the survivors are the same set, their orientation can differ
+ * only when a survivor was matched through its mirrored form: mirrored counts the survivors that some qualifying path held in the mirrored form only. */
+typedef struct sage2ov_path_support {  /* 28 bytes */
+    uint32_t node;                     /* a enters it, b leaves it */
+    uint32_t pair_a, pair_b;           /* ordinals of the record pairs in sage2ov_graph4_save's order, as in sage2ov_read_edge */
+    uint32_t from_a, to_b;             /* the far ends */
+    uint32_t support;
+    uint8_t  second_a, second_b;       /* 0: the half is the record sage2ov_graph4_save writes first of its pair (the first time, for a loop); 1: it is that record's twin */
+    uint8_t  pad[2];
+} sage2ov_path_support;
+typedef struct sage2ov_path_stats {    /* of the last sage2ov_path_supports: they stand until the next sweep, through the merges that drop its table; order_dependent: of the
+                                          last sage2ov_extend_paths_round since that sweep */
+    uint64_t claimed_reads, claiming_nodes, start_nodes;      /* start_nodes: (claiming node, start node) pairs */
+    uint64_t paths, capped_nodes;
+    uint64_t eligible_entries, voting_entries;                /* mate entries that pass the five conditions; of those, the ones with a survivor */
+    uint64_t records, rows;                                   /* survivors (the sum of all supports); distinct (a, b) */
+    uint64_t key_collisions, mirrored, order_dependent;
+    uint32_t sort_passes, reserved;                           /* 8-bit radix passes run */
+    double claim_ms, starts_ms, walk_ms, vote_ms, sort_ms, reduce_ms;      /* HIP events */
+} sage2ov_path_stats;                  /* 152 bytes */
+/* builds the table.  Estimates first when there is no estimate (a rebuilt read-to-edge table after a merge leaves the estimate alone).  SAGE2OV_ERR_ARG without a step-4
+ * graph, SAGE2OV_ERR_DEVICE on a device-less context, SAGE2OV_ERR_LIMIT from 2^32 - 2048 records, paths or start records on, or a maximumUpperBoundOfInsert of 2^31.  The
+ * table goes when the supports table of sage2ov_mates_supports would; _count / _export build it when it is stale.  After sage2ov_graph_simplify every flow is 0: no path
+ * has a first edge, the table is empty, which is no error.  Not sharded: a context with world > 1 behaves as a single one. */
+int sage2ov_path_supports(sage2ov_ctx* ctx);
+int sage2ov_path_supports_count(sage2ov_ctx* ctx, uint32_t min_support, uint64_t* n);
+/* the rows with support >= min_support in table order; cap below their number: SAGE2OV_ERR_ARG, nothing written */
+int sage2ov_path_supports_export(sage2ov_ctx* ctx, uint32_t min_support, sage2ov_path_support* out, uint64_t cap);
+int sage2ov_path_stats_get(const sage2ov_ctx* ctx, sage2ov_path_stats* out);
+/* one round; variant 0 or 1 (else SAGE2OV_ERR_ARG); *merged (may be NULL) = its merges.  It fills the "last round" of sage2ov_extend_merges_count / _export and
+ * sage2ov_extend_stats_get: entries = rows, at_threshold = rows with support >= high, refused, blocked, merges and the batch figures as for sage2ov_extend_round. */
+int sage2ov_extend_paths_round(sage2ov_ctx* ctx, int high_threshold, int low_threshold, int variant, uint64_t* merged);
+/* one of the two loops; *rounds counts the round that ends it too.  genome_size 0, reads and average read length: as for sage2ov_extend_by_supports.  After 10 000
+ * rounds: SAGE2OV_ERR_INTERNAL. */
+int sage2ov_extend_by_paths(sage2ov_ctx* ctx, uint64_t genome_size, int variant, uint64_t* rounds, uint64_t* merged);
 
 /* ---- step 7, ScaffoldMaker::makeScaffolds (matePair/scaffolding.cpp:31-98): the rounds of mergeFinal (:774-967) and mergeFinalSmall (:969-) -- the sweep of
  * sage2ov_links above, the selection of mergeAccordingToSupport (:488-626) / mergeAccordingToSupport2 (:631-769) and mergeDisconnectedEdges (:281-482) applied on the

@@ -99,6 +99,18 @@ class ExtendStats(C.Structure):
     _fields_ = [("rounds", C.c_uint64), ("reserved", C.c_uint64), ("last", ExtendCounts), ("total", ExtendCounts)]
 
 
+# sage2ov_path_support (28 bytes): one (a enters the node, b leaves it) pair of halves with its path support
+PATH_SUPPORT_DTYPE = np.dtype([("node", np.uint32), ("pair_a", np.uint32), ("pair_b", np.uint32), ("from_a", np.uint32), ("to_b", np.uint32), ("support", np.uint32),
+                               ("second_a", np.uint8), ("second_b", np.uint8), ("pad", np.uint8, (2,))])
+
+
+class PathStats(C.Structure):
+    _fields_ = [("claimed_reads", C.c_uint64), ("claiming_nodes", C.c_uint64), ("start_nodes", C.c_uint64), ("paths", C.c_uint64), ("capped_nodes", C.c_uint64),
+                ("eligible_entries", C.c_uint64), ("voting_entries", C.c_uint64), ("records", C.c_uint64), ("rows", C.c_uint64),
+                ("key_collisions", C.c_uint64), ("mirrored", C.c_uint64), ("order_dependent", C.c_uint64), ("sort_passes", C.c_uint32), ("reserved", C.c_uint32),
+                ("claim_ms", C.c_double), ("starts_ms", C.c_double), ("walk_ms", C.c_double), ("vote_ms", C.c_double), ("sort_ms", C.c_double), ("reduce_ms", C.c_double)]
+
+
 # sage2ov_join (48 bytes): one join of the last round of scaffold_round
 JOIN_DTYPE = np.dtype([("from", np.uint32), ("to", np.uint32), ("support", np.uint32), ("gap", np.int32), ("pair_first", np.uint32), ("pair_second", np.uint32),
                        ("pair_new", np.uint32), ("overlap_forward", np.int32), ("overlap_twin", np.int32), ("type", np.uint8), ("first_deleted", np.uint8),
@@ -583,6 +595,36 @@ class Context:
 
     def graph6_save(self, path):
         self._chk(lib().sage2ov_graph6_save(self._h, os.fsencode(path)))
+
+    # ---- the second and third loop of extendContigs (mergeContigs.cpp:62-99): path supports and their merge rounds
+    def path_supports(self, min_support=1) -> np.ndarray:
+        """the rows with support >= min_support (PATH_SUPPORT_DTYPE) in ascending (node, a newest first, b newest first); built when stale"""
+        n = C.c_uint64(0)
+        self._chk(lib().sage2ov_path_supports_count(self._h, C.c_uint32(min_support), C.byref(n)))
+        out = np.zeros(n.value, dtype=PATH_SUPPORT_DTYPE)
+        self._chk(lib().sage2ov_path_supports_export(self._h, C.c_uint32(min_support), C.c_void_p(out.ctypes.data), C.c_uint64(n.value)))
+        return out
+
+    def path_supports_build(self):
+        """builds the table now (path_supports builds it when it is stale)"""
+        self._chk(lib().sage2ov_path_supports(self._h))
+
+    def path_stats(self) -> PathStats:
+        s = PathStats()
+        self._chk(lib().sage2ov_path_stats_get(self._h, C.byref(s)))
+        return s
+
+    def extend_paths_round(self, high, low=1, variant=0) -> int:
+        """one findPathSupports(high) (variant 0) or findPathSupportsNew(high) (1): sweep, selection, merges; returns the number of merges"""
+        n = C.c_uint64(0)
+        self._chk(lib().sage2ov_extend_paths_round(self._h, C.c_int(high), C.c_int(low), C.c_int(variant), C.byref(n)))
+        return int(n.value)
+
+    def extend_by_paths(self, genome_size=0, variant=0):
+        """rounds until one merges no more than the stop value -> (rounds, merges)"""
+        r, m = C.c_uint64(0), C.c_uint64(0)
+        self._chk(lib().sage2ov_extend_by_paths(self._h, C.c_uint64(genome_size), C.c_int(variant), C.byref(r), C.byref(m)))
+        return int(r.value), int(m.value)
 
     # ---- step 7, ScaffoldMaker::makeScaffolds (scaffolding.cpp:31-98): joins of edges that share no node, by the links below
     def join_pairs(self, first, second, gap):

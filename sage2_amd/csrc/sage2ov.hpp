@@ -128,6 +128,16 @@ public:
         std::vector<sage2ov_support> out(n); ctx().check(sage2ov_mates_supports_export(ctx().get(), minSupport, out.data(), n));
         return out;
     }
+    // the sweep of ContigExtender::findPathSupports / findPathSupportsNew (mergeContigs.cpp:118-353): every (a enters a node, b leaves it) pair that mate pairs voted for
+    // through the paths between them; one round of either (variant 0 / 1), and the loops of :62-99
+    std::vector<sage2ov_path_support> pathSupports(uint32_t minSupport = 1) {
+        uint64_t n = 0; ctx().check(sage2ov_path_supports_count(ctx().get(), minSupport, &n));
+        std::vector<sage2ov_path_support> out(n); ctx().check(sage2ov_path_supports_export(ctx().get(), minSupport, out.data(), n));
+        return out;
+    }
+    sage2ov_path_stats pathStats() const { sage2ov_path_stats s{}; ctx().check(sage2ov_path_stats_get(ctx().get(), &s)); return s; }
+    uint64_t findPathSupports(int highTh, int variant = 0, int lowTh = 1) { uint64_t m = 0; ctx().check(sage2ov_extend_paths_round(ctx().get(), highTh, lowTh, variant, &m)); table_ = false; return m; }
+    std::pair<uint64_t, uint64_t> extendByPaths(int variant, uint64_t genomeSize = 0) { uint64_t r = 0, m = 0; ctx().check(sage2ov_extend_by_paths(ctx().get(), genomeSize, variant, &r, &m)); table_ = false; return {r, m}; }
     // the sweep that opens ScaffoldMaker::mergeFinal (mode SAGE2OV_LINKS_FINAL) / mergeFinalSmall (SAGE2OV_LINKS_SMALL), scaffolding.cpp:786-935, :981-1130: support and
     // gap of every ordered pair of half-edges linked by mates, both directions.  The merges stay with the caller
     std::vector<sage2ov_link> scaffoldLinks(uint32_t mode = SAGE2OV_LINKS_ALL, uint32_t minSupport = 1) {

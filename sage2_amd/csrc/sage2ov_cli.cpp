@@ -38,6 +38,7 @@ static void printListOfArgs() {
             "\t--flowSolution <string>\tstep 5 after its solver: apply this output.cs2 to the flows and write <prefix>.graph5\n"
             "\t--extend\t\twith -m 6: load <inputPrefix>.graph5, map the mate pairs of -f|-l, estimate the insert sizes, merge contigs by mate-pair\n"
             "\t\t\tsupport until a round merges nothing (the first loop of extendContigs) and write <prefix>.graph6 [--genomeSize: the estimate on the loaded graph]\n"
+            "\t--paths\t\t\twith -m 6 --extend: after the first loop, the loops of findPathSupports and findPathSupportsNew (merges by path support)\n"
             "\t--scaffold\t\twith -m 7: load <inputPrefix>.graph6, map the mate pairs of -f|-l, estimate the insert sizes, join contigs that share no node by\n"
             "\t\t\tmate-pair links (the five loops of makeScaffolds) and write <prefix>_scaffold.fasta; with -m 6 --extend: go on from the merged graph, no new estimate\n\t-h|--help\n\n";
 }
@@ -46,7 +47,7 @@ static double now() { return chrono::duration<double>(chrono::steady_clock::now(
 
 int main(int argc, char* argv[]) {
     const double tMain = now(); const bool timing = getenv("SAGE2OV_TIMING") != nullptr;
-    int minStep = 1, maxStep = 3, gpu = 0, gpus = 1, failRank = -1; bool shareGpu = false, forceMulti = false; unsigned minOverlap = 0; bool contigs = false, extend = false, scaffold = false, flowNetwork = false, genomeSizeGiven = false, maxGiven = false; string flowSolution; unsigned long long genomeSize = 0; bool saveAll = false, debugging = false, fFlag = false, lFlag = false;
+    int minStep = 1, maxStep = 3, gpu = 0, gpus = 1, failRank = -1; bool shareGpu = false, forceMulti = false; unsigned minOverlap = 0; bool contigs = false, extend = false, paths = false, scaffold = false, flowNetwork = false, genomeSizeGiven = false, maxGiven = false; string flowSolution; unsigned long long genomeSize = 0; bool saveAll = false, debugging = false, fFlag = false, lFlag = false;
     string fileInput, listInput, outputDir, prefixName = "untitled", inputPrefix;
     static struct option opts[] = {{"help", no_argument, 0, 'h'}, {"fileInput", required_argument, 0, 'f'}, {"minOverlap", required_argument, 0, 'k'},
         {"listInput", required_argument, 0, 'l'}, {"outputDir", required_argument, 0, 'o'}, {"prefix", required_argument, 0, 'p'},
@@ -54,7 +55,7 @@ int main(int argc, char* argv[]) {
         {"saveAll", no_argument, 0, 's'}, {"debug", no_argument, 0, 'd'}, {"gpu", required_argument, 0, 'g'}, {"gpus", required_argument, 0, 'G'},
         {"share-gpu", no_argument, 0, 1001},      // rehearsal: all ranks on device `gpu`, exchanges by device copies instead of RCCL (a box with fewer GPUs than ranks)
         {"fail-rank", required_argument, 0, 1003},  // tests: this rank of a multi-GPU run fails before its first step (the run must end non-zero, not hang)
-        {"contigs", no_argument, 0, 1004}, {"genomeSize", required_argument, 0, 1005}, {"flowNetwork", no_argument, 0, 1006}, {"flowSolution", required_argument, 0, 1007}, {"extend", no_argument, 0, 1008}, {"scaffold", no_argument, 0, 1009},
+        {"contigs", no_argument, 0, 1004}, {"genomeSize", required_argument, 0, 1005}, {"flowNetwork", no_argument, 0, 1006}, {"flowSolution", required_argument, 0, 1007}, {"extend", no_argument, 0, 1008}, {"scaffold", no_argument, 0, 1009}, {"paths", no_argument, 0, 1010},
         {"force-multi", no_argument, 0, 1002},    // the multi-GPU code path (RCCL communicator, the four exchanges) even with one GPU
         {0, 0, 0, 0}};
     int c, oi = 0;
@@ -81,6 +82,7 @@ int main(int argc, char* argv[]) {
             case 1006: flowNetwork = true; break;
             case 1007: flowSolution = optarg; break;
             case 1008: extend = true; break;
+            case 1010: paths = true; break;
             case 1009: scaffold = true; break;
             case '?': cout << "\n"; exit(0);
             default: cout << "[ERROR] Wrong command line arguments!\n\n"; exit(0);
@@ -99,6 +101,7 @@ int main(int argc, char* argv[]) {
     if (step5 && maxStep < 4) { cout << "[ERROR] --flowNetwork and --flowSolution need the graph after step 4: run with -M 4 (or -m 5 on the files of such a run).\n"; exit(0); }
     if (minStep > 5 && step5) { cout << "[ERROR] --flowNetwork and --flowSolution work on the graph after step 4 (-m 5 at the most).\n"; exit(0); }
     if (extend && (minStep != 6 || (fileInput == "" && listInput == ""))) { cout << "[ERROR] --extend works on <inputPrefix>.graph5 (-m 6) and needs the mate pairs (-f or -l).\n"; exit(0); }
+    if (paths && !(extend && minStep == 6)) { cout << "[ERROR] --paths goes with -m 6 --extend.\n"; exit(0); }
     if (scaffold && (!(minStep == 7 || (minStep == 6 && extend)) || (fileInput == "" && listInput == ""))) { cout << "[ERROR] --scaffold works on <inputPrefix>.graph6 (-m 7), or after --extend (-m 6), and needs the mate pairs (-f or -l).\n"; exit(0); }
     if (minStep > 4 && !contigs && !step5 && !extend && !scaffold) { cout << "[ERROR] sage2ov implements steps 1-4; continue with: SAGE2 -m " << minStep << " -i " << inputPrefix << " ...\n"; exit(0); }
     (void)debugging;
@@ -191,6 +194,15 @@ int main(int argc, char* argv[]) {
                 logStream << "\tRounds of findMatepairSupports: " << rounds << " (" << xs.total.entries << " supported pairs listed, " << xs.total.refused << " refused, " << xs.total.blocked
                           << " blocked, " << xs.total.pairs_deleted << " edges deleted, " << xs.total.entries_copied << " list entries written)\n";
                 ctx.check(rc);
+                if (paths) {                                                                  // the second and third loop (mergeContigs.cpp:62-99)
+                    static const char* const name[2] = {"findPathSupports", "findPathSupportsNew"};
+                    for (int variant = 0; variant < 2; variant++) {
+                        uint64_t r = 0, m = 0;
+                        const int rc2 = sage2ov_extend_by_paths(ctx.get(), genomeSizeGiven ? genomeSize : 0, variant, &r, &m);
+                        logStream << "\tRounds of " << name[variant] << ": " << r << " (" << m << " merges)\n";
+                        ctx.check(rc2); merged += m;
+                    }
+                }
                 logStream << "\nTotal number of extended contigs: " << merged << "\n";
                 ctx.check(sage2ov_graph6_save(ctx.get(), (outputDir + prefixName + ".graph6").c_str()));
                 logStream << "\t" << prefixName << ".graph6 written\n\tFirst loop of step 6 in " << now() - t6 << " sec.\n";

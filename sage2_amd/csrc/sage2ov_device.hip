@@ -114,6 +114,8 @@ struct Device {
     void* support = nullptr;     // the mate-pair supports of edge pairs (dev_support_build; Support): allocations of its own, dropped with the read-to-edge table and the mate flags
     void* contigs = nullptr;     // the contig table and the spelling buffers (dev_contigs_build; Contigs): allocations of its own, dropped with the graph and the read set
     void* links = nullptr;       // the scaffold links of half-edge pairs (dev_links_build; Links): allocations of its own, dropped with the read-to-edge table and the mate flags
+    void* paths = nullptr;       // the path supports of half-edge pairs (dev_paths_build; PathTable): allocations of its own, dropped with the mate-pair supports
+    void* estflags = nullptr;    // every library's mate flags as of the last estimate (dev_estflags_keep; EstFlags): they outlive the read-to-edge table and go with the graph and the read set
     void* copycount = nullptr;   // step 5 around its solver (dev_copycount_prepare, dev_flownet_build; CopyCount): allocations of its own, dropped with the graph and the read set
     void* s4keep = nullptr;      // step 4: the simplified graph stays in HBM until the next call (S4Keep)
     // step 4: blocks a call released, kept for the next call (it asks for the same ~50 sizes; fresh HBM costs ~50 ms per GB to map, 0.7 s per call at BASELINE
@@ -237,6 +239,7 @@ static void mem_sample(Device* d) { size_t fr = 0, to = 0; if (hipMemGetInfo(&fr
 #include "kernels_readmap.inc"
 #include "kernels_support.inc"
 #include "kernels_links.inc"
+#include "kernels_paths.inc"
 #include "kernels_contig.inc"
 #include "kernels_scaffold.inc"
 #include "kernels_copycount.inc"
@@ -392,6 +395,7 @@ Device* dev_create(int ordinal, const Options& opt, std::string& err) {
 }
 static void mates_release(Device* d);
 static void free_reads(Device* d) {
+    dev_estflags_release(d);                                            // (flags of mate entries that name read ids)
     dev_readmap_release(d);                                             // (read ids again)
     dev_contigs_release(d);                                             // (and the reads the strings are spelled from)
     dev_copycount_release(d);                                           // (the frequencies and the present reads are of this read set)
@@ -2139,7 +2143,7 @@ struct S4Mem {                                   // released on every exit path 
 #define S4GET(var, type, n) type* var = mem.get<type>((n), err); if (!var) return SAGE2OV_ERR_NOMEM;
 struct S4Keep { S4Mem mem; S4Graph g; u32 nh = 0; u64 listUsed = 0; float* flow = nullptr;       // flow: one float per half-edge (null: every flow is 0, the state after step 4)
                 u64 capH = 0, listCap = 0, flowCap = 0; };                                       // what the half-edge arrays, the list pool and flow[] hold (splice_pairs grows them)
-void dev_simplify_release(Device* d) { dev_readmap_release(d); dev_contigs_release(d); dev_copycount_release(d); if (d->s4keep) { hipSetDevice(d->ordinal); delete (S4Keep*)d->s4keep; d->s4keep = nullptr; } }
+void dev_simplify_release(Device* d) { dev_estflags_release(d); dev_readmap_release(d); dev_contigs_release(d); dev_copycount_release(d); if (d->s4keep) { hipSetDevice(d->ordinal); delete (S4Keep*)d->s4keep; d->s4keep = nullptr; } }
 
 int dev_simplify(Device* d, SimplifiedGraph& out, std::string& err) {
     HIPCHK(hipSetDevice(d->ordinal));
@@ -2393,7 +2397,7 @@ int dev_flow_set(Device* d, const float* flow, uint64_t n, std::string& err) {
     HIPCHK(hipSetDevice(d->ordinal));
     if (!d->s4keep) { err = "flows: no step-4 graph on the device"; return SAGE2OV_ERR_ARG; }
     S4Keep& K = *(S4Keep*)d->s4keep; S4Mem& mem = K.mem;
-    dev_support_release(d);
+    dev_support_release(d); dev_paths_release(d);
     if (!flow) { if (K.flow) { mem.drop(K.flow); K.flow = nullptr; K.flowCap = 0; } return 0; }
     if (n != K.nh) { err = "flows: one value per half-edge"; return SAGE2OV_ERR_INTERNAL; }
     if (!K.flow) { S4GET(a, float, K.nh) K.flow = a; K.flowCap = std::max<u64>(K.nh, 1); }
@@ -2531,8 +2535,8 @@ struct ReadMap {
     u32 *eRead = nullptr, *ePair = nullptr, *eNf = nullptr, *eNr = nullptr, *eLoc = nullptr, *readOff = nullptr; int* locs = nullptr; u64 E = 0, R = 0; ReadMapLib lib[128];
     ~ReadMap() { for (auto& L : lib) readmap_drop_join(L); hipFree(eRead); hipFree(ePair); hipFree(eNf); hipFree(eNr); hipFree(eLoc); hipFree(readOff); hipFree(locs); }
 };
-void dev_readmap_drop_joins(Device* d) { dev_support_release(d); dev_links_release(d); if (!d->readmap) return; hipSetDevice(d->ordinal); for (auto& L : ((ReadMap*)d->readmap)->lib) readmap_drop_join(L); }
-void dev_readmap_release(Device* d) { dev_support_release(d); dev_links_release(d); if (d->readmap) { hipSetDevice(d->ordinal); delete (ReadMap*)d->readmap; d->readmap = nullptr; } }
+void dev_readmap_drop_joins(Device* d) { dev_support_release(d); dev_paths_release(d); dev_links_release(d); if (!d->readmap) return; hipSetDevice(d->ordinal); for (auto& L : ((ReadMap*)d->readmap)->lib) readmap_drop_join(L); }
+void dev_readmap_release(Device* d) { dev_support_release(d); dev_paths_release(d); dev_links_release(d); if (d->readmap) { hipSetDevice(d->ordinal); delete (ReadMap*)d->readmap; d->readmap = nullptr; } }
 static int readmap_nomem(std::string& err) { err = "read-to-edge table: out of device memory"; return SAGE2OV_ERR_NOMEM; }
 template <class T> static T* readmap_alloc(u64 n) { return (T*)DevTmp::alloc(std::max<u64>(n, 1) * sizeof(T)); }
 // the 8-bit digits of a record key (read:30 | pair:31 | side:1) that can be non-zero: side and pair end at bit 1 + bits(pairs), the read at 32 + bits(N)
@@ -2899,6 +2903,176 @@ int dev_links_export(Device* d, uint64_t* key, uint32_t* support, int32_t* gap, 
 }
 
 // =============================================================================================
+// the path supports of consecutive half-edge pairs (kernels_paths.inc; the sweep of ContigExtender::findPathSupports / findPathSupportsNew, mergeContigs.cpp:118-353, :359-743)
+// =============================================================================================
+struct EstFlags { unsigned char* f[128] = {}; u64 n[128] = {}; ~EstFlags() { for (unsigned char* p : f) hipFree(p); } };
+void dev_estflags_release(Device* d) { if (d->estflags) { hipSetDevice(d->ordinal); delete (EstFlags*)d->estflags; d->estflags = nullptr; } }
+int dev_estflags_keep(Device* d, int library, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    if (!d->readmap) { err = "estimate flags: the read-to-edge table is not built"; return SAGE2OV_ERR_INTERNAL; }
+    if (!d->estflags) d->estflags = new EstFlags();
+    EstFlags& F = *(EstFlags*)d->estflags; const ReadMapLib& J = ((const ReadMap*)d->readmap)->lib[library];
+    hipFree(F.f[library]); F.f[library] = nullptr; F.n[library] = 0;
+    if (!J.nflag) return 0;
+    F.f[library] = (unsigned char*)DevTmp::alloc(J.nflag);
+    if (!F.f[library]) { err = "estimate flags: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+    HIPCHK(hipMemcpyAsync(F.f[library], J.flag, J.nflag, hipMemcpyDeviceToDevice, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
+    F.n[library] = J.nflag;
+    return 0;
+}
+struct PathTable { u64* key = nullptr; u32* sup = nullptr; u64 E = 0; ~PathTable() { hipFree(key); hipFree(sup); } };
+void dev_paths_release(Device* d) { if (d->paths) { hipSetDevice(d->ordinal); delete (PathTable*)d->paths; d->paths = nullptr; } }
+uint64_t dev_paths_count(Device* d) { const PathTable* S = (const PathTable*)d->paths; return S ? S->E : 0; }
+static int paths_nomem(std::string& err) { err = "path supports: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+static int paths_limit(const char* what, std::string& err) { err = std::string("path supports: more than 2^32 ") + what; return SAGE2OV_ERR_LIMIT; }
+int dev_paths_build(Device* d, const PathParams& P, PathStats* st, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    if (!d->s4keep) { err = "path supports: no step-4 graph on the device"; return SAGE2OV_ERR_ARG; }
+    if (!d->readmap) { err = "path supports: the read-to-edge table is not built"; return SAGE2OV_ERR_INTERNAL; }
+    dev_paths_release(d);
+    const S4Keep& K = *(S4Keep*)d->s4keep; const S4Graph& g = K.g; const u32 nh = K.nh; const u64 nl = K.listUsed; const ReadMap* M = (const ReadMap*)d->readmap;
+    std::unique_ptr<PathTable> S(new PathTable());
+    *st = PathStats();
+    if (!K.flow || !nh || !nl) { d->paths = S.release(); return 0; }                   // every flow is 0 (the graph as step 4 leaves it): no path has a first edge
+    if (P.bound >= (1ull << 31)) { err = "path supports: maximumUpperBoundOfInsert beyond 2^31 (a path's length is a 32-bit value)"; return SAGE2OV_ERR_LIMIT; }
+    const u32 N = (u32)d->N; hipStream_t sm = d->stream; const u64 lim = (1ull << 32) - RS_TILE;
+    DevTmp B; StreamLap lap(sm); HIPCHK(lap.create());
+    const dim3 b256(256);
+    // ---- the claim: unique reads, the list entries of the alive halves, the running sums, the minimum per read
+    HIPCHK(lap.start());
+    uint8_t* nodeFlag = B.get<uint8_t>((u64)N + 2); u32* uniq = B.get<u32>((u64)N + 2); u32* claim = B.get<u32>((u64)N + 2); u32* hCnt = B.get<u32>(nh); u32* hOff = B.get<u32>(nh);
+    unsigned long long* ctr = B.get<unsigned long long>(12); u64* partial = B.get<u64>(scan_partial_words(std::max<u64>(std::max<u64>(nl, nh), (u64)N + 2) + 1));
+    if (!nodeFlag || !uniq || !claim || !hCnt || !hOff || !ctr || !partial) return paths_nomem(err);
+    HIPCHK(hipMemsetAsync(ctr, 0, 12 * sizeof(unsigned long long), sm)); HIPCHK(hipMemsetAsync(claim, 0xFF, ((u64)N + 2) * sizeof(u32), sm));
+    const MsTable T = {M->readOff, M->ePair, M->eNf, M->eNr, M->eLoc, M->locs, N};
+    { const int rc = unique_reads(d, g, nh, T, nodeFlag, uniq, err); if (rc) return rc; }
+    hipLaunchKernelGGL(k_sl_halves, dim3(grid_for(nh, 256)), b256, 0, sm, g, nh, hCnt, ctr + 11);
+    u64 W = 0; { const int rc = scan_u32(d, hCnt, nh, hOff, partial, &W, err); if (rc) return rc; }
+    if (W >= lim) return paths_limit("list entries", err);
+    if (!W) { d->paths = S.release(); return 0; }
+    u32* scan = nullptr; { const int rc = pool_running_sums(d, B, g.lists, nl, partial, scan, paths_nomem, err); if (rc) return rc; }
+    hipLaunchKernelGGL(k_pt_claim, dim3(grid_for(W, 256)), b256, 0, sm, g, nh, hOff, (u32)W, scan, nl, (u64)P.bound, N, claim);
+    HIPCHK(hipGetLastError());
+    HIPCHK(lap.stop(st->claim_ms));
+    B.release(scan); B.release(hCnt); B.release(hOff); B.release(nodeFlag);
+    // ---- the start nodes: (claiming node, end node) records of the claimed reads, distinct and ascending
+    HIPCHK(lap.start());
+    u32* rcnt = B.get<u32>((u64)N + 2); u32* rpos = B.get<u32>((u64)N + 2); if (!rcnt || !rpos) return paths_nomem(err);
+    const dim3 gN(grid_for((u64)N + 1, 256));
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pt_starts<false>), gN, b256, 0, sm, g, T, claim, rcnt, (const u32*)nullptr, (u64*)nullptr, ctr);
+    u64 R0 = 0; { const int rc = scan_u32(d, rcnt, (u64)N + 1, rpos, partial, &R0, err); if (rc) return rc; }
+    unsigned long long hc[12] = {};
+    HIPCHK(hipMemcpy(hc, ctr, sizeof hc, hipMemcpyDeviceToHost));
+    st->claimed_reads = hc[0];
+    if (R0 >= lim) return paths_limit("start records", err);
+    if (!R0) { HIPCHK(lap.stop(st->starts_ms)); d->paths = S.release(); return 0; }
+    u64* skey = B.get<u64>(R0); if (!skey) return paths_nomem(err);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pt_starts<true>), gN, b256, 0, sm, g, T, claim, (u32*)nullptr, (const u32*)rpos, skey, ctr);
+    HIPCHK(hipGetLastError());
+    int shifts[8]; int np = half_pair_passes(N + 1u, shifts);
+    u64* ks = nullptr; u32* vs = nullptr; MateStats ms;
+    { const int rc = mate_sort(d, B, skey, (u32)R0, shifts, np, &ks, &vs, &ms, err); if (rc) return rc; }
+    B.release(vs); B.release(rcnt); B.release(rpos);
+    u32* hp = nullptr; u32 nS = 0;
+    { const int rc = mate_heads(d, B, ks, (u32)R0, &hp, &nS, err); if (rc) return rc; }
+    u32* startNode = B.get<u32>(nS); u32* sflag = B.get<u32>(nS); u32* spos = B.get<u32>(nS); u64* partialS = B.get<u64>(scan_partial_words((u64)nS + 1));
+    if (!startNode || !sflag || !spos || !partialS) return paths_nomem(err);
+    hipLaunchKernelGGL(k_pt_take, dim3(grid_for(nS, 256)), b256, 0, sm, ks, hp, nS, startNode, sflag);
+    u64 C64 = 0; { const int rc = scan_u32(d, sflag, nS, spos, partialS, &C64, err); if (rc) return rc; }
+    const u32 C = (u32)C64;
+    u32* segOff = B.get<u32>((u64)C + 1); u32* segNode = B.get<u32>(C); if (!segOff || !segNode) return paths_nomem(err);
+    { const int rc = head_positions(d, sflag, spos, nS, segOff, C, err); if (rc) return rc; }
+    hipLaunchKernelGGL(k_pt_seg_nodes, dim3(grid_for(C, 256)), b256, 0, sm, ks, hp, segOff, C, segNode);
+    HIPCHK(hipGetLastError());
+    HIPCHK(lap.stop(st->starts_ms));
+    B.release(ks); B.release(hp); B.release(sflag); B.release(spos);
+    st->start_nodes = nS; st->claiming_nodes = C; st->passes = ms.passes;
+    // ---- the walk: adjacency (alive halves of every node, oldest first), count, scan, fill
+    HIPCHK(lap.start());
+    S4Graph ga = g; u32* cursor = B.get<u32>((u64)N + 2);
+    ga.deg = B.get<u32>((u64)N + 2); ga.adjOff = B.get<u32>((u64)N + 2); ga.adj = B.get<u32>(nh);
+    u32* pcnt = B.get<u32>((u64)nS + 1); u32* pathOff = B.get<u32>((u64)nS + 1);
+    if (!cursor || !ga.deg || !ga.adjOff || !ga.adj || !pcnt || !pathOff) return paths_nomem(err);
+    HIPCHK(hipMemsetAsync(ga.deg, 0, ((u64)N + 2) * sizeof(u32), sm)); HIPCHK(hipMemsetAsync(cursor, 0, ((u64)N + 2) * sizeof(u32), sm));
+    HIPCHK(hipMemsetAsync(pcnt, 0, ((u64)nS + 1) * sizeof(u32), sm));
+    hipLaunchKernelGGL(k_s4_degree, dim3(grid_for(nh, 256)), b256, 0, sm, ga, nh);
+    { const int rc = scan_u32(d, ga.deg, (u64)N + 1, ga.adjOff, partial, nullptr, err); if (rc) return rc; }
+    hipLaunchKernelGGL(k_s4_fill, dim3(grid_for(nh, 256)), b256, 0, sm, ga, nh, cursor);
+    hipLaunchKernelGGL(k_s4_sortadj, gN, b256, 0, sm, ga, N);
+    const dim3 gC(grid_for(C, PT_BLOCK)), bW(PT_BLOCK);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pt_walk<false>), gC, bW, 0, sm, ga, (const float*)K.flow, C, (const u32*)segOff, (const u32*)startNode, (u64)P.bound, pcnt, (const u32*)nullptr, (PtPath*)nullptr, (u64)0, ctr);
+    u64 PT = 0; { const int rc = scan_u32(d, pcnt, (u64)nS + 1, pathOff, partialS, &PT, err); if (rc) return rc; }
+    HIPCHK(hipMemcpy(hc, ctr, sizeof hc, hipMemcpyDeviceToHost));
+    st->paths = hc[1]; st->capped_nodes = hc[2];
+    if (PT >= lim) return paths_limit("paths", err);
+    if (PT != hc[1]) { err = "path supports: the count pass and its scan disagree"; return SAGE2OV_ERR_INTERNAL; }
+    if (!PT) { HIPCHK(lap.stop(st->walk_ms)); d->paths = S.release(); return 0; }
+    PtPath* paths = B.get<PtPath>(PT); if (!paths) return paths_nomem(err);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pt_walk<true>), gC, bW, 0, sm, ga, (const float*)K.flow, C, (const u32*)segOff, (const u32*)startNode, (u64)P.bound, (u32*)nullptr, (const u32*)pathOff, paths, (u64)PT, ctr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(lap.stop(st->walk_ms));
+    B.release(cursor); B.release(ga.deg); B.release(ga.adjOff); B.release(ga.adj); B.release(pcnt);
+    // ---- the votes: one lane per mate entry of every valid library, then the survivors as records
+    HIPCHK(lap.start());
+    const EstFlags* F = (const EstFlags*)d->estflags; const u32 nlib = std::min<u32>(P.libraries, 127);
+    u64 Mall = 0;
+    for (u32 L = 1; L <= nlib; L++) {
+        const u64 n = d->mates ? d->mates->lib[L].n : 0; if (!n || !P.valid[L]) continue;
+        if (!F || F->n[L] != n) { err = "path supports: no estimate flags for a library's mate entries"; return SAGE2OV_ERR_INTERNAL; }
+        Mall += n;
+    }
+    if (Mall >= lim) return paths_limit("mate entries", err);
+    if (!Mall) { HIPCHK(lap.stop(st->vote_ms)); d->paths = S.release(); return 0; }
+    u32* first = B.get<u32>(Mall); u32* fe1 = B.get<u32>(Mall); u32* mask = B.get<u32>(Mall); u32* vcnt = B.get<u32>(Mall); u32* vpos = B.get<u32>(Mall);
+    u64* partialM = B.get<u64>(scan_partial_words(Mall));
+    if (!first || !fe1 || !mask || !vcnt || !vpos || !partialM) return paths_nomem(err);
+    const PtIndex X = {segNode, segOff, C, startNode, pathOff, paths};
+    { u64 base = 0;
+      for (u32 L = 1; L <= nlib; L++) {
+          const u64 n = d->mates ? d->mates->lib[L].n : 0; if (!n || !P.valid[L]) continue;
+          const PtLib lib = {d->mates->lib[L].key, F->f[L], n, (long long)P.lower[L], (long long)P.upper[L]};
+          hipLaunchKernelGGL(k_pt_vote, dim3(grid_for(n, 256)), b256, 0, sm, g, nh, T, (const u32*)uniq, (const u32*)claim, lib, X, first + base, fe1 + base, mask + base, vcnt + base, ctr);
+          base += n;
+      } }
+    u64 R = 0; { const int rc = scan_u32(d, vcnt, Mall, vpos, partialM, &R, err); if (rc) return rc; }
+    HIPCHK(hipMemcpy(hc, ctr, sizeof hc, hipMemcpyDeviceToHost));
+    st->eligible = hc[3]; st->voting = hc[4]; st->mirrored = hc[5]; st->records = R;
+    if (R >= lim) return paths_limit("records", err);
+    if (!R) { HIPCHK(lap.stop(st->vote_ms)); d->paths = S.release(); return 0; }
+    u64* key = B.get<u64>(R); if (!key) return paths_nomem(err);
+    hipLaunchKernelGGL(k_pt_emit, dim3(grid_for(Mall, 256)), b256, 0, sm, (const u32*)first, (const u32*)fe1, (const u32*)mask, (const u32*)vpos, (u32)Mall, (const PtPath*)paths, (u64)R, key);
+    HIPCHK(hipGetLastError());
+    HIPCHK(lap.stop(st->vote_ms));
+    B.release(first); B.release(fe1); B.release(mask); B.release(vcnt); B.release(vpos); B.release(partialM); B.release(paths); B.release(pathOff); B.release(startNode);
+    B.release(segOff); B.release(segNode); B.release(uniq); B.release(claim); B.release(partial); B.release(partialS);
+    // ---- sort by (a, b) and reduce: one row per distinct key, its support the length of the run
+    HIPCHK(lap.start());
+    np = half_pair_passes(nh, shifts);
+    MateStats ms2;
+    { const int rc = mate_sort(d, B, key, (u32)R, shifts, np, &ks, &vs, &ms2, err); if (rc) return rc; }
+    st->passes += ms2.passes;
+    HIPCHK(lap.stop(st->sort_ms));
+    B.release(vs);
+    HIPCHK(lap.start());
+    u32 E = 0;
+    { const int rc = mate_heads(d, B, ks, (u32)R, &hp, &E, err); if (rc) return rc; }
+    S->key = (u64*)DevTmp::alloc((u64)E * sizeof(u64)); S->sup = (u32*)DevTmp::alloc((u64)E * sizeof(u32));
+    if (!S->key || !S->sup) return paths_nomem(err);
+    hipLaunchKernelGGL(k_ms_reduce, dim3(grid_for(E, 256)), b256, 0, sm, ks, hp, E, S->key, S->sup, ctr + 8);
+    HIPCHK(hipGetLastError());
+    HIPCHK(lap.stop(st->reduce_ms));
+    S->E = E; st->rows = E;
+    d->paths = S.release();
+    return 0;
+}
+int dev_paths_export(Device* d, uint64_t* key, uint32_t* support, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    const PathTable* S = (const PathTable*)d->paths; if (!S) { err = "path supports: not built"; return SAGE2OV_ERR_INTERNAL; }
+    if (S->E) { HIPCHK(hipMemcpy(key, S->key, S->E * sizeof(u64), hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(support, S->sup, S->E * sizeof(u32), hipMemcpyDeviceToHost)); }
+    return 0;
+}
+
+// =============================================================================================
 // the contig table and the contig strings (kernels_contig.inc; OverlapGraph::printGraph / saveContigsToFile, overlapGraph.cpp:507-784)
 // =============================================================================================
 struct Contigs {
@@ -3177,7 +3351,7 @@ int dev_flow_apply(Device* d, const uint64_t* from, const uint64_t* to, const ui
     if (!dfr || !dto || !dfl || !acc || !ctr) return copycount_nomem(err);
     const bool fresh = !K.flow;
     if (fresh) { S4GET(a, float, nh) K.flow = a; K.flowCap = std::max<u64>(nh, 1); }
-    dev_support_release(d);
+    dev_support_release(d); dev_paths_release(d);
     HIPCHK(lap.start());
     if (fresh && nh) HIPCHK(hipMemsetAsync(K.flow, 0, (u64)nh * sizeof(float), sm));
     if (nh) HIPCHK(hipMemsetAsync(acc, 0, (u64)nh * sizeof(unsigned long long), sm));

@@ -124,6 +124,10 @@ struct sage2ov_ctx {
     bool supValid = false;                             // the table is of the present graph, flows, mates and estimate (it also needs `estimated`)
     sage2ov_support_stats sstats{}; std::vector<sage2ov_support> supports; bool supOnHost = false;
     void supports_forget() { supValid = supOnHost = false; supports.clear(); sstats = sage2ov_support_stats{}; }
+    // ---- the path supports (sage2ov_path_supports): built on the device, kept here in table order with the internal halves (a : 32 | b : 32) of every row; stale
+    // whenever the supports above would be
+    bool pathValid = false; sage2ov_path_stats pstats{}; std::vector<sage2ov_path_support> prows; std::vector<uint64_t> pkeys;
+    void paths_forget() { pathValid = false; prows.clear(); pkeys.clear(); }         // (pstats stays: the figures of the last sweep, until the next one)
     // ---- the scaffold links (sage2ov_links): built on the device, kept here in export order, unfiltered, once a call has asked for them; the flows are read at export
     bool linkValid = false, linkOnHost = false;        // the table is of the present graph, mates and estimate (it also needs `estimated`)
     sage2ov_link_stats lstats{}; std::vector<sage2ov_link> links; std::vector<uint32_t> linkHalves;      // linkHalves: E(pair(a)), E(pair(b)) of every row, internal half-edges
@@ -141,7 +145,7 @@ struct sage2ov_ctx {
     sage2ov_extend_stats xstats{}; std::vector<sage2ov_merge> xmerges;
     sage2ov_scaffold_stats scstats{}; std::vector<sage2ov_join> scjoins;      // the scaffold rounds (sage2ov_scaffold_*)
     void extend_forget() { estimateHeld = hdrHeld = false; hdrGenome = hdrReads = 0; xstats = sage2ov_extend_stats{}; xmerges.clear(); scstats = sage2ov_scaffold_stats{}; scjoins.clear(); }
-    void readmap_forget() { rmValid = estimated = false; extend_forget(); pairOrdinal.clear(); rmstats = sage2ov_readmap_stats{}; supports_forget(); links_forget(); contigs_forget(); copycount_forget(); }      // the graph or the read set goes
+    void readmap_forget() { rmValid = estimated = false; extend_forget(); pairOrdinal.clear(); rmstats = sage2ov_readmap_stats{}; supports_forget(); paths_forget(); links_forget(); contigs_forget(); copycount_forget(); }      // the graph or the read set goes
     void mates_forget(bool readSetGoes = true) {       // the read set goes: its ids mean nothing any more (the device drops its part in free_reads) -- or sage2ov_mates_clear
         if (readSetGoes) { readmap_forget(); readsGen++; } else estimated = estimateHeld = false;
         for (auto& L : mates) L = MateLib();
@@ -1822,7 +1826,7 @@ void readmap_stats_take(sage2ov_ctx* c, const ReadMapStats& s) {
 }
 int readmap_build(sage2ov_ctx* c) {
     c->rmValid = false; if (!c->estimateHeld) c->estimated = false;
-    c->rmstats = sage2ov_readmap_stats{}; c->supports_forget(); c->links_forget();
+    c->rmstats = sage2ov_readmap_stats{}; c->supports_forget(); c->paths_forget(); c->links_forget();
     ReadMapStats s; const int rc = dev_readmap_build(c->device(), &s, c->err); if (rc) return rc;
     readmap_stats_take(c, s); c->rmValid = true; return SAGE2OV_OK;
 }
@@ -1946,12 +1950,13 @@ int sage2ov_mates_distances_export(sage2ov_ctx* c, int library, uint32_t* d, uin
 int sage2ov_mates_estimate(sage2ov_ctx* c) {
     if (!c) return SAGE2OV_ERR_ARG;
     { const int rc = readmap_ensure(c, "sage2ov_mates_estimate"); if (rc) return rc; }
-    c->estimated = c->estimateHeld = false; c->rmstats.rounds = 0; c->rmstats.round_ms = 0; c->supports_forget(); c->links_forget();
+    c->estimated = c->estimateHeld = false; c->rmstats.rounds = 0; c->rmstats.round_ms = 0; c->supports_forget(); c->paths_forget(); c->links_forget();
     const uint64_t arl = average_read_length(c); Device* d = c->device();
     c->minUpper = 1000000; c->maxUpper = 0;                                            // matePair.cpp:292-293
     for (auto& I : c->inserts) I = sage2ov_insert{};
     for (int lib = 1; lib <= (int)c->mateLibraries; lib++) {
         { const int rc = readmap_join(c, lib); if (rc) return rc; }
+        { const int rc = dev_estflags_keep(d, lib, c->err); if (rc) return rc; }         // the flags of this graph: what the path supports read after merges (sage2ov.h, ESTIMATE FLAGS)
         ReadMapStats s; sage2ov_insert& I = c->inserts[lib];
         const int rc = estimate_rounds([&](int64_t mu, uint64_t& count, uint64_t& sum, u128& sq) {
             uint64_t o[4]; const int r = dev_readmap_round(d, lib, mu, 4 * (uint64_t)mu, o, &s, c->err);
@@ -2031,7 +2036,7 @@ int sage2ov_graph_flow_import(sage2ov_ctx* c, const float* flow, uint64_t n) {
     if (n && !flow) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_graph_flow_import: null argument");
     std::vector<float> f(c->g4.n_half_edges, 0.f);
     for (size_t x = 0; x < first.size(); x++) { f[first[x]] = flow[2 * x]; f[first[x] ^ 1u] = flow[2 * x + 1]; }
-    c->supports_forget(); c->contigs_forget();
+    c->supports_forget(); c->paths_forget(); c->contigs_forget();
     { const int rc = dev_flow_set(c->device(), f.data(), f.size(), c->err); if (rc) return rc; }
     c->g4.flow = std::move(f);
     return SAGE2OV_OK;
@@ -2177,7 +2182,7 @@ int sage2ov_flow_solution_apply(sage2ov_ctx* c, const uint64_t* from, const uint
         if ((from[i] == 1 && to[i] == 2) || (from[i] == 2 && to[i] == 1)) tts = flow[i];
     }
     CopyCountStats s;
-    c->supports_forget(); c->contigs_forget();
+    c->supports_forget(); c->paths_forget(); c->contigs_forget();
     { const int rc = dev_flow_apply(c->device(), from, to, flow, n, &s, c->err); if (rc) return rc; }
     std::vector<float> f(c->g4.n_half_edges, 0.f);
     { const int rc = dev_flow_get(c->device(), f.data(), f.size(), c->err); if (rc) return rc; }
@@ -2275,7 +2280,7 @@ int splice_apply(sage2ov_ctx* c, SpliceBatch& B, int typeOfMerge) {
                           : dev_merge_pairs(c->device(), B.a.data(), B.b.data(), n, typeOfMerge, B.plan.data(), &s, c->err); if (rc) return rc; }
     if (!s.made) return SAGE2OV_OK;
     const bool est = c->estimated;
-    c->rmValid = false; c->pairOrdinal.clear(); c->rmstats = sage2ov_readmap_stats{}; c->supports_forget(); c->links_forget(); c->contigs_forget(); c->copycount_forget();
+    c->rmValid = false; c->pairOrdinal.clear(); c->rmstats = sage2ov_readmap_stats{}; c->supports_forget(); c->paths_forget(); c->links_forget(); c->contigs_forget(); c->copycount_forget();
     c->estimateHeld = est;
     SimplifiedGraph& g = c->g4;
     g.downloaded = g.fields = false; g.lists.clear(); g.lists.shrink_to_fit();
@@ -2383,6 +2388,21 @@ extern "C++" { struct SpliceRound {
         return SAGE2OV_OK;
     }
 }; }
+// the node lists as a merge round finds them (alive halves by ascending index; walked backwards: newest first) and the halves the round adds
+extern "C++" { struct NodeLists {
+    const SpliceRound& S; std::vector<uint32_t> offs, adj; std::unordered_map<uint32_t, std::vector<uint32_t>> added;
+    NodeLists(const SpliceRound& round, uint64_t N) : S(round), offs(N + 2, 0) {
+        for (uint32_t h = 0; h < S.nh; h++) if (S.alive[h]) offs[S.from[h] + 1]++;
+        for (uint64_t i = 0; i <= N; i++) offs[i + 1] += offs[i];
+        adj.resize(offs[N + 1]);
+        std::vector<uint32_t> cur(offs.begin(), offs.end() - 1); for (uint32_t h = 0; h < S.nh; h++) if (S.alive[h]) adj[cur[S.from[h]]++] = h;
+    }
+    template <class F> void walk(uint32_t node, F&& fn) const {
+        auto it = added.find(node);
+        if (it != added.end()) for (size_t x = it->second.size(); x-- > 0;) if (S.alive[it->second[x]]) fn(it->second[x]);
+        for (uint32_t x = offs[node + 1]; x-- > offs[node];) if (S.alive[adj[x]]) fn(adj[x]);
+    }
+}; }
 void counts_add(sage2ov_extend_counts& t, const sage2ov_extend_counts& r) {
     t.entries += r.entries; t.at_threshold += r.at_threshold; t.refused += r.refused; t.blocked += r.blocked; t.merges += r.merges; t.entries_copied += r.entries_copied;
     t.pairs_deleted += r.pairs_deleted; t.batches += r.batches; t.sweep_ms += r.sweep_ms; t.select_ms += r.select_ms; t.lists_ms += r.lists_ms; t.commit_ms += r.commit_ms;
@@ -2427,19 +2447,8 @@ int sage2ov_extend_round(sage2ov_ctx* c, int highTh, int lowTh, uint64_t* merged
     { const int rc = pair_ordinals(c); if (rc) return rc; }                           // (the half-edge fields come with it; no read list)
     SpliceRound S(c, "sage2ov_extend_round", 1);
     const std::vector<uint32_t>&ordBefore = S.ordBefore, &from = S.from, &to = S.to, &cnt = S.cnt; const std::vector<uint8_t>&type = S.type, &alive = S.alive; const std::vector<float>& flow = S.flow;
-    const uint32_t nh = S.nh;
-    // the node lists as the round finds them (alive halves by ascending index; walked backwards: newest first) and the halves the round adds
-    std::vector<uint32_t> offs(c->g4.N + 2, 0), adj;
-    for (uint32_t h = 0; h < nh; h++) if (alive[h]) offs[from[h] + 1]++;
-    for (uint64_t i = 0; i <= c->g4.N; i++) offs[i + 1] += offs[i];
-    adj.resize(offs[c->g4.N + 1]);
-    { std::vector<uint32_t> cur(offs.begin(), offs.end() - 1); for (uint32_t h = 0; h < nh; h++) if (alive[h]) adj[cur[from[h]]++] = h; }
-    std::unordered_map<uint32_t, std::vector<uint32_t>> added;
-    auto walk = [&](uint32_t node, auto&& fn) {
-        auto it = added.find(node);
-        if (it != added.end()) for (size_t x = it->second.size(); x-- > 0;) if (alive[it->second[x]]) fn(it->second[x]);
-        for (uint32_t x = offs[node + 1]; x-- > offs[node];) if (alive[adj[x]]) fn(adj[x]);
-    };
+    NodeLists lists(S, c->g4.N); std::unordered_map<uint32_t, std::vector<uint32_t>>& added = lists.added;
+    auto walk = [&](uint32_t node, auto&& fn) { lists.walk(node, fn); };
     // the list in building order (node ascending, in-half newest first, out-half newest first), SEARCH and the entries filed under their end nodes
     struct Ent { uint32_t e1, e2, sup, node; };
     std::vector<Ent> list;
@@ -2517,6 +2526,163 @@ int sage2ov_graph6_save(sage2ov_ctx* c, const char* path) {                     
     if (!c->hdrHeld) return sage2ov_graph5_save(c, path);
     { const int rc = copycount_check(c, "sage2ov_graph6_save"); if (rc) return rc; }
     return save_composite(c, path, true, (unsigned long long)c->hdrGenome, (unsigned long long)c->hdrReads);
+}
+
+// ---- PATH SUPPORTS: the second and third loop of ContigExtender::extendContigs (mergeContigs.cpp:62-99, :118-353, :794-952, :2148-2546); the semantics are stated in sage2ov.h
+namespace {
+static_assert(sizeof(sage2ov_path_support) == 28 && sizeof(sage2ov_path_stats) == 152, "the records of the path supports");
+int paths_ensure(sage2ov_ctx* c, const char* who) {
+    { const int rc = readmap_check(c, who); if (rc) return rc; }
+    if (c->pathValid && c->estimated && c->rmValid) return SAGE2OV_OK;
+    return sage2ov_path_supports(c);
+}
+// the table in table order (node ascending, a newest first, b newest first), on the host, with the number of rows that share their XOR key with an earlier one
+int paths_fetch(sage2ov_ctx* c) {
+    Device* d = c->device(); const uint64_t E = dev_paths_count(d);
+    std::vector<uint64_t> key(E); std::vector<uint32_t> sup(E);
+    { const int rc = dev_paths_export(d, key.data(), sup.data(), c->err); if (rc) return rc; }
+    { const int rc = pair_ordinals(c); if (rc) return rc; }
+    const SimplifiedGraph& g = c->g4; const std::vector<uint32_t>& ord = c->pairOrdinal;
+    std::vector<uint32_t> order, first(g.n_half_edges / 2 + 1, ~0u); g4_save_order(g, order);
+    for (uint32_t h : order) if (first[h >> 1] == ~0u) first[h >> 1] = h;
+    std::vector<uint64_t> at(E); for (uint64_t e = 0; e < E; e++) at[e] = e;
+    std::sort(at.begin(), at.end(), [&](uint64_t x, uint64_t y) {
+        const uint32_t ax = (uint32_t)(key[x] >> 32), bx = (uint32_t)key[x], ay = (uint32_t)(key[y] >> 32), by = (uint32_t)key[y];
+        return g.to[ax] != g.to[ay] ? g.to[ax] < g.to[ay] : (ax != ay ? ax > ay : bx > by); });
+    c->prows.resize(E); c->pkeys.resize(E);
+    std::unordered_set<uint64_t> xors;
+    for (uint64_t e = 0; e < E; e++) {
+        const uint64_t k = key[at[e]]; const uint32_t a = (uint32_t)(k >> 32), b = (uint32_t)k;
+        sage2ov_path_support o{}; o.node = g.to[a]; o.pair_a = ord[a >> 1]; o.pair_b = ord[b >> 1]; o.from_a = g.from[a]; o.to_b = g.to[b]; o.support = sup[at[e]];
+        o.second_a = first[a >> 1] == a ? 0 : 1; o.second_b = first[b >> 1] == b ? 0 : 1;
+        c->prows[e] = o; c->pkeys[e] = k;
+        xors.insert(((uint64_t)(g.from[a] ^ g.to[a]) << 32) | (uint64_t)(g.from[b] ^ g.to[b]));
+    }
+    c->pstats.key_collisions = E - xors.size();
+    return SAGE2OV_OK;
+}
+}  // namespace
+int sage2ov_path_supports(sage2ov_ctx* c) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    { const int rc = readmap_check(c, "sage2ov_path_supports"); if (rc) return rc; }
+    { const int rc = estimate_ensure(c); if (rc) return rc; }
+    c->paths_forget(); c->pstats = sage2ov_path_stats{};
+    PathParams P; P.bound = c->maxUpper; P.libraries = c->mateLibraries;
+    for (int lib = 1; lib <= (int)c->mateLibraries && lib < 128; lib++) { const sage2ov_insert& I = c->inserts[lib]; P.valid[lib] = I.valid ? 1 : 0; P.lower[lib] = I.lower; P.upper[lib] = I.upper; }
+    PathStats s; const int rc = dev_paths_build(c->device(), P, &s, c->err); if (rc) return rc;
+    sage2ov_path_stats& o = c->pstats;
+    o.claimed_reads = s.claimed_reads; o.claiming_nodes = s.claiming_nodes; o.start_nodes = s.start_nodes; o.paths = s.paths; o.capped_nodes = s.capped_nodes;
+    o.eligible_entries = s.eligible; o.voting_entries = s.voting; o.records = s.records; o.rows = s.rows; o.mirrored = s.mirrored; o.sort_passes = s.passes;
+    o.claim_ms = s.claim_ms; o.starts_ms = s.starts_ms; o.walk_ms = s.walk_ms; o.vote_ms = s.vote_ms; o.sort_ms = s.sort_ms; o.reduce_ms = s.reduce_ms;
+    { const int rc2 = paths_fetch(c); if (rc2) return rc2; }
+    c->pathValid = true;
+    return SAGE2OV_OK;
+}
+int sage2ov_path_supports_count(sage2ov_ctx* c, uint32_t min_support, uint64_t* n) {
+    if (!c || !n) return SAGE2OV_ERR_ARG;
+    { const int rc = paths_ensure(c, "sage2ov_path_supports_count"); if (rc) return rc; }
+    uint64_t m = 0; for (const sage2ov_path_support& e : c->prows) m += e.support >= min_support;
+    *n = m; return SAGE2OV_OK;
+}
+int sage2ov_path_supports_export(sage2ov_ctx* c, uint32_t min_support, sage2ov_path_support* out, uint64_t cap) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    uint64_t m = 0; { const int rc = sage2ov_path_supports_count(c, min_support, &m); if (rc) return rc; }
+    if (cap < m) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_path_supports_export: the buffer holds fewer rows than the table (sage2ov_path_supports_count)");
+    if (m && !out) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_path_supports_export: null argument");
+    uint64_t at = 0; for (const sage2ov_path_support& e : c->prows) if (e.support >= min_support) out[at++] = e;
+    return SAGE2OV_OK;
+}
+int sage2ov_path_stats_get(const sage2ov_ctx* c, sage2ov_path_stats* o) { if (!c || !o) return SAGE2OV_ERR_ARG; *o = c->pstats; return SAGE2OV_OK; }
+int sage2ov_extend_paths_round(sage2ov_ctx* c, int highTh, int lowTh, int variant, uint64_t* merged) {              // :794-952, :2388-2546
+    if (!c) return SAGE2OV_ERR_ARG;
+    if (variant != 0 && variant != 1) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_extend_paths_round: variant is 0 (mergeByPathSupports) or 1 (mergeByPathSupportsNew)");
+    { const int rc = readmap_check(c, "sage2ov_extend_paths_round"); if (rc) return rc; }
+    sage2ov_extend_counts R{};
+    const bool swept = !(c->pathValid && c->estimated && c->rmValid);
+    { const int rc = paths_ensure(c, "sage2ov_extend_paths_round"); if (rc) return rc; }
+    if (swept) R.sweep_ms = c->pstats.claim_ms + c->pstats.starts_ms + c->pstats.walk_ms + c->pstats.vote_ms + c->pstats.sort_ms + c->pstats.reduce_ms;
+    { const int rc = pair_ordinals(c); if (rc) return rc; }                           // (the half-edge fields come with it; no read list)
+    const std::vector<uint64_t> keys = c->pkeys; std::vector<uint32_t> sup(keys.size());
+    for (size_t e = 0; e < keys.size(); e++) sup[e] = c->prows[e].support;
+    SpliceRound S(c, "sage2ov_extend_paths_round", 1);
+    const std::vector<uint32_t>&ordBefore = S.ordBefore, &from = S.from, &to = S.to; const std::vector<uint8_t>&type = S.type, &alive = S.alive; const std::vector<float>& flow = S.flow;
+    NodeLists lists(S, c->g4.N);
+    // SEARCH holds the summed support of the rows that share a key; every row is filed under its four end nodes.  ORDER: support descending, ties in table order
+    struct Row { uint32_t a, b, sup; };
+    std::vector<Row> rows(keys.size());
+    for (size_t e = 0; e < keys.size(); e++) {
+        rows[e] = Row{(uint32_t)(keys[e] >> 32), (uint32_t)keys[e], sup[e]};
+        const uint64_t kk = S.key(rows[e].a, rows[e].b);
+        S.search[kk] += sup[e];
+        for (uint32_t nd : {to[rows[e].a], from[rows[e].a], to[rows[e].b], from[rows[e].b]}) S.filed.insert({nd, kk});
+    }
+    std::stable_sort(rows.begin(), rows.end(), [](const Row& x, const Row& y) { return x.sup > y.sup; });
+    R.entries = rows.size(); bool dependent = false;
+    {   // difference 1: no decision depends on the order when the rows at the threshold sit at pairwise different nodes, none of them an end of another such row's halves
+        std::unordered_map<uint32_t, uint32_t> at; std::vector<const Row*> top;
+        for (const Row& r : rows) if ((int64_t)r.sup >= (int64_t)highTh) { R.at_threshold++; top.push_back(&r); at[to[r.a]]++; }
+        for (const Row* r : top) {
+            if (at[to[r->a]] > 1) dependent = true;
+            for (uint32_t nd : {from[r->a], to[r->b]}) if (nd != to[r->a] && at.count(nd)) dependent = true;
+        }
+    }
+    std::unordered_set<uint32_t> blocked; std::vector<sage2ov_merge> merges;
+    for (const Row& r : rows) {
+        const uint32_t e1 = r.a, e2 = r.b;
+        if (!alive[e1] || !alive[e2]) continue;
+        if (S.find(S.key(e1, e2)) < 0) continue;
+        const uint32_t node = to[e1];
+        if (blocked.count(node)) { R.blocked++; continue; }
+        if ((int64_t)r.sup < (int64_t)highTh) continue;                                // (:831: no stop)
+        bool uniqueIn = true, uniqueOut = true;
+        lists.walk(node, [&](uint32_t v) {
+            if (!(flow[v] >= 1.f) || to[v] == from[v]) return;                         // :837 (no list is asked for)
+            if ((v ^ 1u) != e1 && combined_type(type[v ^ 1u], type[e2]) >= 0) {
+                int64_t s = S.find(S.key(v ^ 1u, e2)); if (s < 0) s = S.find(S.key(e2 ^ 1u, v)); if (s > lowTh) uniqueIn = false;
+            }
+            if (v != e2 && combined_type(type[e1], type[v]) >= 0) {
+                int64_t s = S.find(S.key(e1, v)); if (s < 0) s = S.find(S.key(v ^ 1u, e1 ^ 1u)); if (s > lowTh) uniqueOut = false;
+            }
+        });
+        if (variant == 0 ? !(uniqueIn && uniqueOut) : !(uniqueIn || uniqueOut)) { R.refused++; continue; }
+        lists.walk(node, [&](uint32_t v) { if (to[v] != from[v]) blocked.insert(to[v]); });
+        const int t = combined_type(type[e1], type[e2]);
+        if (e1 == e2 || e1 == (e2 ^ 1u) || t < 0) continue;                            // mergeEdgesAndUpdate returns NULL
+        { const int rc = S.make_room(e1, e2); if (rc) return rc; }
+        const float f1 = flow[e1], f2 = flow[e2], f = (f1 == 0.f && f2 == 0.f) ? 0.f : 1.f;
+        sage2ov_merge m{}; m.node = node; m.from = from[e1]; m.to = to[e2]; m.support = r.sup; m.flow = f; m.type = (uint8_t)t;
+        m.pair_in = (e1 >> 1) < ordBefore.size() ? ordBefore[e1 >> 1] : ~0u; m.pair_out = (e2 >> 1) < ordBefore.size() ? ordBefore[e2 >> 1] : ~0u; m.pair_new = ~0u;
+        m.in_deleted = f1 <= f; m.out_deleted = f2 <= f;
+        const uint32_t h = S.splice(e1, e2, (uint8_t)t, f, m.in_deleted, m.out_deleted, 0);
+        lists.added[from[h]].push_back(h); lists.added[from[h + 1]].push_back(h + 1);
+        merges.push_back(m);
+        S.erase_at(node, 0);
+    }
+    { const int rc = S.finish(merges, R); if (rc) return rc; }
+    R.merges = merges.size();
+    c->xmerges = std::move(merges);
+    c->xstats.rounds++; c->xstats.last = R; counts_add(c->xstats.total, R);
+    c->pstats.order_dependent = dependent ? 1 : 0;
+    if (merged) *merged = R.merges;
+    return SAGE2OV_OK;
+}
+int sage2ov_extend_by_paths(sage2ov_ctx* c, uint64_t genomeSize, int variant, uint64_t* rounds, uint64_t* merged) {   // :62-99
+    if (!c) return SAGE2OV_ERR_ARG;
+    if (variant != 0 && variant != 1) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_extend_by_paths: variant is 0 (findPathSupports) or 1 (findPathSupportsNew)");
+    { const int rc = readmap_check(c, "sage2ov_extend_by_paths"); if (rc) return rc; }
+    { const int rc = header_hold(c); if (rc) return rc; }
+    const uint64_t gs = genomeSize ? genomeSize : c->hdrGenome, reads = c->hdrReads, arl = average_read_length(c);
+    if (!gs || !arl) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_extend_by_paths: a genome size or an average read length of 0");
+    const uint64_t stop = gs > 1000000000 ? 10 : 0;
+    uint64_t r = 0, total = 0;
+    for (uint32_t it = 1; it <= 10000; it++) {
+        int high = 0; sage2ov_extend_threshold(reads, arl, gs, it, &high);
+        uint64_t m = 0; { const int rc = sage2ov_extend_paths_round(c, high, 1, variant, &m); if (rc) return rc; }
+        r++; total += m;
+        if (rounds) *rounds = r; if (merged) *merged = total;
+        if (m <= stop) return SAGE2OV_OK;
+    }
+    return c->fail(SAGE2OV_ERR_INTERNAL, "sage2ov_extend_by_paths: 10 000 rounds without a fixed point");
 }
 
 // ---- the sweep that opens ScaffoldMaker::mergeFinal / mergeFinalSmall (scaffolding.cpp:786-935, :981-1130); the semantics are stated in sage2ov.h

@@ -218,6 +218,18 @@ int dev_links_build(Device* d, const LinkParams& P, LinkStats* st, std::string& 
 uint64_t dev_links_count(Device* d);
 int dev_links_export(Device* d, uint64_t* key, uint32_t* support, int32_t* gap, std::string& err);
 void dev_links_release(Device* d);
+// the sweep of ContigExtender::findPathSupports / findPathSupportsNew on the device (sage2ov_path_supports; kernels_paths.inc): needs the read-to-edge
+// table, the mate tables, the insert bounds and the mate flags as of the estimate (dev_estflags_keep: a copy per library that outlives the read-to-edge table of the
+// graph it was made on).  The table (key = half a:32 | half b:32, a entering the node b leaves; support) stays in HBM as long as the mate-pair supports would.
+struct PathParams { uint64_t bound = 0; int64_t lower[128] = {}, upper[128] = {}; uint8_t valid[128] = {}; uint32_t libraries = 0; };      // bound: maximumUpperBoundOfInsert
+struct PathStats { uint64_t claimed_reads = 0, claiming_nodes = 0, start_nodes = 0, paths = 0, capped_nodes = 0, eligible = 0, voting = 0, records = 0, rows = 0, mirrored = 0;
+                   uint32_t passes = 0; double claim_ms = 0, starts_ms = 0, walk_ms = 0, vote_ms = 0, sort_ms = 0, reduce_ms = 0; };
+int dev_estflags_keep(Device* d, int library, std::string& err);      // after dev_readmap_join of the library
+void dev_estflags_release(Device* d);
+int dev_paths_build(Device* d, const PathParams& P, PathStats* st, std::string& err);
+uint64_t dev_paths_count(Device* d);
+int dev_paths_export(Device* d, uint64_t* key, uint32_t* support, std::string& err);
+void dev_paths_release(Device* d);
 // OverlapGraph::printGraph / saveContigsToFile on the device (sage2ov_contigs_*).  dev_contigs_build selects, orders and lays out the rows: they stay
 // in HBM with the running distPrevious of the list pool and come back in table order.  dev_contigs_spell_begin spells the strings of a range of rows into one of two
 // buffers -- 16-byte chunks, every row from a chunk boundary -- and copies them to a pinned host image; dev_contigs_spell_wait hands that image out.  The table goes
