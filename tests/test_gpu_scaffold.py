@@ -14,7 +14,7 @@ import test_links_host as LH
 import test_scaffold_host as SH
 from test_gpu_mate_estimate import add_mates, random_store, load_text
 from test_gpu_extend import saved6, operands, table_set
-from test_scaffold_host import components, pinned_cases, distinct
+from test_scaffold_host import components, pinned_cases, pinned_cases_long, distinct
 
 pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("minimiser_groups_on")]
 K = LH.HAND_K
@@ -96,6 +96,101 @@ def test_a_seeded_batch_of_512_searches_with_mixed_lengths(tmp_path):
     ctx.close()
 
 
+# ------------------------------------------------------------------------------------------ the 16- and 32-word read layouts (252 to 504 and 505 to 1018 bases)
+LONG_WORDS = {504: 16, 1018: 32}
+LONG_GAPS = (-3, 0, 5, 1030, 2000)
+# (case, gap, read length, edge length, distance in the entry) of one join without an overlap per layout whose gap + L passes 2047: 1030 + 1018 = 2048 is 0 in the
+# entry's 11 bits, 2000 + 503 = 2503 is 455; X has 300 + n % 7 bases and Y 250 + n % 5 (components)
+LONG_WRAP = {504: (29, 2000, 503, 301 + 254 + 2503, 455), 1018: (43, 1030, 1018, 301 + 253 + 2048, 0)}
+
+
+def found_in(ov):
+    return [o for pair in ov for o in pair]
+
+
+@pytest.mark.parametrize("top", sorted(LONG_WORDS))
+def test_overlap_search_on_the_long_layouts(top, tmp_path):
+    """every long pinned case of a layout (tests/test_scaffold_host.py: the middle, the last and the first shift at the word and layout edges, several passing lane
+    rounds, unequal lengths) in one store with 60-base fillers, all four type combinations, gaps that wrap the entry's 11 bits"""
+    cases = pinned_cases_long(top=top); strings = distinct(cases); nc = len(cases)
+    fillers = [SH.rnd(60, 5000 + i) for i in range(5 * nc)]
+    ctx, seqs, where = chosen_store(list(strings) + fillers)
+    st = ctx.reads_stats(); assert (st.words_per_read, st.max_read_length) == (LONG_WORDS[top], top)
+    recs = components([(s1, s2_, 1, 1, n) for n, (s1, s2_, _) in enumerate(cases)], where, [where[x][0] for x in fillers])
+    g, hdr = loaded(ctx, (0, 400, 60), recs, tmp_path)
+    halves = [(4 * n, 4 * n + 2) for n in range(nc)]; gaps = [LONG_GAPS[n % 5] for n in range(nc)]
+    (ov, how), (mo, mh) = join_both(ctx, g, seqs, halves, gaps)
+    assert [o[0] for o in mo] == [want for _, _, want in cases]                        # the model's forward search is the pinned value
+    assert ov == mo and how == mh
+    # (the model alone says so: not vacuous) a hit in the layout's last word of 32 shifts, directions that differ, every distance case
+    assert any(o >= 32 * (LONG_WORDS[top] - 1) for o in found_in(mo)) and (top != 1018 or any(o >= 960 for o in found_in(mo)))
+    assert any(o[0] != o[1] for o in mo) and {h for hw in mh for h in hw} == {SM.OVERLAP, SM.CONCAT, SM.GAPPED}
+    n, gap, L, length, entry = LONG_WRAP[top]; new = g.h[len(g.h) - 2 * (nc - n)]
+    assert (gaps[n], len(cases[n][0]), len(cases[n][1]), mo[n], mh[n]) == (gap, L, L, [-1, -1], [SM.GAPPED, SM.GAPPED])
+    assert new["len"] == length and gap + L > 2047 and new["list"][2][4] == new["list"][3][3] == entry == (gap + L) & 0x7FF      # the wrap is in the entry only
+    assert saved6(ctx, tmp_path) == g.text(hdr) and np.array_equal(ctx.graph_flows(), g.flows())
+    ctx.close()
+
+
+@pytest.mark.parametrize("top", sorted(LONG_WORDS))
+def test_a_seeded_batch_on_the_long_layouts(top, tmp_path):
+    """128 joins, 256 searches: reads of more than half the layout's longest, a quarter of the second reads of 11 to 150 bases, planted shifts in every lane round"""
+    rng = np.random.default_rng(19 + top); cases = SH.long_batch(top); strings = distinct(cases); nc = len(cases)
+    fillers = [SH.rnd(60, 5000 + i) for i in range(5 * nc)]
+    ctx, seqs, where = chosen_store(list(strings) + fillers)
+    st = ctx.reads_stats(); assert st.words_per_read == LONG_WORDS[top] and top - 28 <= st.max_read_length == max(len(s) for s in strings) <= top
+    recs = components([(s1, s2_, 1 + n % 3, (n % 5) / 2, n) for n, (s1, s2_, _) in enumerate(cases)], where, [where[x][0] for x in fillers])
+    g, hdr = loaded(ctx, (0, 400, 60), recs, tmp_path)
+    halves = [(4 * n, 4 * n + 2) for n in range(nc)]; gaps = [int(v) for v in rng.integers(-50, 2100, size=nc)]
+    (ov, how), (mo, mh) = join_both(ctx, g, seqs, halves, gaps)
+    assert nc == 128 and SH.batch_conditions(top, found_in(mo))                        # (the model alone says so: not vacuous)
+    assert ov == mo and how == mh
+    assert saved6(ctx, tmp_path) == g.text(hdr) and np.array_equal(ctx.graph_flows(), g.flows())
+    ctx.close()
+
+
+def on_the_locality_route(ctx, seqs, diet):
+    """memory-diet mode releases the id-ordered store in the index build and nowhere else: with `diet` the index is built, and one id looked up shows which store
+    a reader finds (tests/test_gpu_contigs.py) -> whether the locality-ordered one"""
+    if diet:
+        ctx.index_build()
+    q = np.frombuffer(seqs[1].encode(), dtype=np.uint8)
+    assert ctx.reads_find_ids(q, np.array([0, len(q)], dtype=np.uint64)).tolist() == [1]
+    return ctx.reads_find_stats().route == s2.FIND_ROUTE_LOCALITY
+
+
+def uniform_long_cases():
+    """1018 bases throughout: shifts in the first word, on either side of a word and of half the read, in the last lane round and the last one of all, each with the
+    allowed mismatches or fewer; and a pair without an overlap"""
+    out = []
+    for n, (shift, mism) in enumerate([(1, 102), (31, 50), (32, 0), (511, 51), (512, 3), (960, 6), (1007, 2)]):
+        s1, s2_ = SH.planted(1018, 1018, shift, mism, 600 + n); out.append((s1, s2_, shift))
+    return out + [(SH.rnd(1018, 700), SH.rnd(1018, 701), -1)]
+
+
+@pytest.mark.parametrize("diet", [0, 1])
+def test_uniform_long_reads_on_both_store_routes(diet, tmp_path, monkeypatch):
+    """every read has 1018 bases: no length is read out of a slot, and the last word's bits below the bases are zero.  With SAGE2OV_MEMORY_DIET and an index built
+    the id-ordered store is gone: the search reads the locality-ordered one through posOf"""
+    if diet:
+        monkeypatch.setenv("SAGE2OV_MEMORY_DIET", "1")
+    else:
+        monkeypatch.delenv("SAGE2OV_MEMORY_DIET", raising=False)
+    cases = uniform_long_cases(); strings = distinct(cases); nc = len(cases)
+    fillers = [SH.rnd(1018, 5000 + i) for i in range(5 * nc)]
+    ctx, seqs, where = chosen_store(list(strings) + fillers, k=40)
+    st = ctx.reads_stats(); assert (st.words_per_read, st.max_read_length, {len(s) for s in seqs.values()}) == (32, 1018, {1018})
+    assert on_the_locality_route(ctx, seqs, diet) == bool(diet)                        # before the join: which store it will read
+    recs = components([(s1, s2_, (1, 2, 0.5)[n % 3], (3, 1)[n % 2], n) for n, (s1, s2_, _) in enumerate(cases)], where, [where[x][0] for x in fillers])
+    g, hdr = loaded(ctx, (0, 400, 60), recs, tmp_path)
+    halves = [(4 * n, 4 * n + 2) for n in range(nc)]; gaps = [0, -1, 7, 1990, 3, 1030, 12, 5]
+    (ov, how), (mo, mh) = join_both(ctx, g, seqs, halves, gaps)
+    assert [o[0] for o in mo] == [want for _, _, want in cases] == [1, 31, 32, 511, 512, 960, 1007, -1]
+    assert ov == mo and how == mh
+    assert saved6(ctx, tmp_path) == g.text(hdr) and np.array_equal(ctx.graph_flows(), g.flows())
+    ctx.close()
+
+
 def uniform_cases():
     out = []
     for n, (shift, mism) in enumerate([(1, 6), (1, 7), (25, 4), (25, 5), (49, 2), (49, 3), (0, 7), (30, 0)]):
@@ -105,13 +200,18 @@ def uniform_cases():
 
 @pytest.mark.parametrize("diet", [0, 1])
 def test_both_store_routes_and_the_distance_cases(diet, tmp_path, monkeypatch):
-    """reads of one length: with SAGE2OV_MEMORY_DIET the id-ordered store is gone and the search reads the locality-ordered one through posOf.  Also equal end
-    nodes, the 11-bit wrap, kept operands, and the argument errors that leave everything as it was"""
+    """reads of one length: with SAGE2OV_MEMORY_DIET and an index built the id-ordered store is gone and the search reads the locality-ordered one through posOf
+    (reads_organize alone releases nothing: the route is asserted).  Also equal end nodes, the 11-bit wrap, kept operands, and the argument errors that leave
+    everything as it was"""
     if diet:
         monkeypatch.setenv("SAGE2OV_MEMORY_DIET", "1")
+    else:
+        monkeypatch.delenv("SAGE2OV_MEMORY_DIET", raising=False)
     cases = uniform_cases(); strings = distinct(cases)
     fillers = [SH.rnd(60, 5000 + i) for i in range(5 * len(cases) + 12)]
     ctx, seqs, where = chosen_store(list(strings) + fillers, k=40)
+    assert ctx.reads_stats().words_per_read == 4
+    assert on_the_locality_route(ctx, seqs, diet) == bool(diet)                        # before the joins: which store they will read
     fid = [where[x][0] for x in fillers]
     recs = components([(s1, s2_, (1, 2, 0.5)[n % 3], (3, 1)[n % 2], n) for n, (s1, s2_, _) in enumerate(cases)], where, fid)
     nc = len(cases)

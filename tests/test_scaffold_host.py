@@ -81,6 +81,56 @@ def distinct(cases):
     return seen
 
 
+# the two read-store layouts above 8 words (tests/test_gpu_edges.py LAYOUT_TOPS): 16 words hold 252 to 504 bases, 32 words 505 to 1018; the lengths sit on the
+# layouts' ends and on either side of a 32-base word, of the last word (992 = 31 * 32) and of half a layout
+LONG_TOPS = {504: [252, 253, 256, 257, 503, 504], 1018: [505, 512, 513, 991, 992, 993, 1017, 1018]}
+LONG_LENGTHS = LONG_TOPS[504] + LONG_TOPS[1018]
+
+
+def long_rows(L):
+    """(shift, planted mismatches, seed, pinned result) of the six cases of one length: the middle shift, the last one and shift 1, each with exactly the allowed
+    mismatches and with one more (shift 1 at 1018 bases: 102 and 103 mismatches, the largest count there is)"""
+    mid = (L - 10) // 2
+    return [(mid, (L - mid) // 10 + 1, 100 + L, mid), (mid, (L - mid) // 10 + 2, 1100 + L, -1), (L - 11, 2, 2200 + L, L - 11), (L - 11, 3, 3200 + L, -1),
+            (1, (L - 1) // 10 + 1, 4100 + L, 1), (1, (L - 1) // 10 + 2, 5100 + L, -1)]
+
+
+def periodic_cases(top):
+    """reads of period 300 as long as the layout allows: (s1, s2, the shifts that pass one by one); the first of them is the pinned result.  70 bases in front: 70, 370
+    and at 1018 bases 670 and 970 as well (lane rounds 1, 5, 10 and 15); top - 318 in front: 700 and 1000 at 1018 bases (rounds 10 and 15), 186 and 486 at 504"""
+    unit = rnd(300, 7 + top); per = (unit * 4)[:top]
+    return [(rnd(70, 8 + top) + per[:top - 70], per, list(range(70, top - 10, 300))), (rnd(top - 318, 9 + top) + per[:318], per[:top - 1] + other(per[top - 1]), [top - 318, top - 18])]
+
+
+def unequal_cases(top):
+    """(s1, s2, pinned forward result) of reads of two lengths, in one layout by the longer: a short read against the longest and the other way round, half the
+    layout against all of it, one base and 118 bases over, and a read whose first 18 bases are the long one's last.  Where s2 is the shorter by more than 10, a
+    single facing base may mismatch (1 <= 1 / 10 + 1), so some shift below L2 always passes: a tail of a few bases decides before the empty comparison at i == L2
+    is reached, at a shift the seeds fix.  The results are what both restatements say (test_unequal_lengths_on_the_long_layouts)"""
+    half = 252 if top == 504 else 504                                                  # 252 against 504: the 16-word layout's own ends; 504 against 1018: two layouts' tops
+    tails = {504: (37, 251, 31), 1018: (36, 502, 30)}[top]
+    s = rnd(top, 60 + top); t = rnd(top, 61 + top); u = rnd(top, 62 + top); v = rnd(33, 63 + top); x = rnd(top, 64 + top); y = rnd(top - 8, 65 + top)
+    return [(rnd(40, 50 + top), rnd(top, 51 + top), -1),                               # L2 - L1 = top - 40 positions of s2 face nothing: never passes
+            (rnd(top, 52 + top), rnd(40, 53 + top), tails[0]),                         # a tail of s2 passes in lane round 1
+            (rnd(half, 54 + top), rnd(top, 55 + top), -1), (rnd(top, 56 + top), rnd(half, 57 + top), tails[1]),      # a tail again: the last shift before s2 runs out
+            (s[:top - 1], s, 0),                                                       # one base over, a hit at shift 0: the gap branch
+            (t[:top - 118], t, -1),                                                    # 118 over: more than top / 10 + 1
+            (u[:top - 18] + v[:18], v, tails[2]),                                      # 33 bases sit at s1's far end, but a tail passes before: forward early, the twin direction none
+            (x[:top - 18] + y[:18], y, top - 18)]                                      # s2 is 8 bases shorter: forward passes in the last lane round, 10 bases facing 18; the twin has L2 > L1
+
+
+def pinned_cases_long(lengths=None, top=None):
+    """(s1, s2, expected forward overlap) on the 16- and 32-word layouts.  `lengths`: the six rows of long_rows() for each; `top` (504 or 1018): that layout's
+    lengths and its periodic and unequal cases as well"""
+    out = []
+    for L in (lengths if lengths is not None else LONG_TOPS[top] if top else LONG_LENGTHS):
+        for shift, mism, seed, want in long_rows(L):
+            s1, s2_ = planted(L, L, shift, mism, seed); out.append((s1, s2_, want))
+    if top is not None:
+        out += [(s1, s2_, passing[0]) for s1, s2_, passing in periodic_cases(top)] + unequal_cases(top)
+    return out
+
+
 
 # ------------------------------------------------------------------------------------------ stringOverlapSize
 @pytest.mark.parametrize("L", LENGTHS)
@@ -145,6 +195,86 @@ def test_the_two_restatements_agree_on_seeded_pairs(seed):
         else:
             s1 = rnd(L1, int(rng.integers(1 << 30)))
         assert SM.overlap_size(s1, s2_) == SM.overlap_rule(s1, s2_)
+
+
+# ------------------------------------------------------------------------------------------ stringOverlapSize on reads of 252 to 1018 bases
+@pytest.mark.parametrize("L", LONG_LENGTHS)
+def test_long_reads_at_the_middle_the_last_and_the_first_shift(L):
+    """six planted pairs per length: the allowed number of mismatches passes at the planted shift, one more passes nowhere"""
+    rows = long_rows(L)
+    assert [(r[0], r[3]) for r in rows] == [((L - 10) // 2, (L - 10) // 2), ((L - 10) // 2, -1), (L - 11, L - 11), (L - 11, -1), (1, 1), (1, -1)]
+    assert L != 1018 or [(r[0], r[1]) for r in rows] == [(504, 52), (504, 53), (1007, 2), (1007, 3), (1, 102), (1, 103)]
+    for (shift, mism, seed, want), (s1, s2_, pinned) in zip(rows, pinned_cases_long([L])):
+        assert len(s1) == len(s2_) == L and pinned == want
+        assert SM.overlap_size(s1, s2_) == SM.overlap_rule(s1, s2_) == want, (L, shift, mism)
+
+
+@pytest.mark.parametrize("top", sorted(LONG_TOPS))
+def test_the_smallest_of_several_passing_lane_rounds_wins_on_the_long_layouts(top):
+    (a1, a2, pa), (b1, b2, pb) = periodic_cases(top)
+    assert (pa, pb) == {504: ([70, 370], [186, 486]), 1018: ([70, 370, 670, 970], [700, 1000])}[top]
+    for s1, s2_, passing in ((a1, a2, pa), (b1, b2, pb)):
+        assert len(s1) == len(s2_) == top
+        assert all(SM.overlap_rule(s1[i:] + "N" * i, s2_[:top - i]) == 0 for i in passing)      # each of them passes on its own
+        assert SM.overlap_size(s1, s2_) == SM.overlap_rule(s1, s2_) == passing[0]
+    assert {i >> 6 for i in pa + pb} == ({1, 5, 2, 7} if top == 504 else {1, 5, 10, 15})       # the groups of 64 shifts they lie in
+
+
+@pytest.mark.parametrize("top", sorted(LONG_TOPS))
+def test_unequal_lengths_on_the_long_layouts(top):
+    cases = unequal_cases(top)
+    assert [(len(a), len(b)) for a, b, _ in cases] == [(40, top), (top, 40), (top // 2 if top == 504 else 504, top), (top, top // 2 if top == 504 else 504),
+                                                        (top - 1, top), (top - 118, top), (top, 33), (top, top - 8)]
+    for s1, s2_, want in cases:
+        assert SM.overlap_size(s1, s2_) == SM.overlap_rule(s1, s2_) == want, (len(s1), len(s2_))
+    assert [w for _, _, w in cases] == {504: [-1, 37, -1, 251, 0, -1, 31, 486], 1018: [-1, 36, -1, 502, 0, -1, 30, 1000]}[top]
+    assert all(0 < cases[n][2] < len(cases[n][1]) for n in (1, 3, 6))                  # the tails: below L2, before the empty comparison
+    # the twin direction of the last two differs from the forward one
+    for s1, s2_, want in cases[6:]:
+        t = SM.overlap_size(SM.revcomp(s2_), SM.revcomp(s1))
+        assert t == SM.overlap_rule(SM.revcomp(s2_), SM.revcomp(s1)) and t != want
+
+
+@pytest.mark.parametrize("top", sorted(LONG_TOPS))
+def test_the_long_cases_are_distinct_reads(top):
+    cases = pinned_cases_long(top=top)
+    assert len(cases) == 6 * len(LONG_TOPS[top]) + 2 + 8 and len(distinct(cases)) == 2 * len(cases)
+    assert max(len(s) for c in cases for s in c[:2]) == top and min(len(s) for c in cases[:6 * len(LONG_TOPS[top])] for s in c[:2]) == (252 if top == 504 else 505)
+    assert len(distinct(pinned_cases_long(LONG_LENGTHS))) == 2 * 6 * len(LONG_LENGTHS)
+
+
+def long_batch(top, joins=128):
+    """(s1, s2, None) of a seeded batch on one long layout: s1 of top // 2 + 1 to top bases; s2 as long, every fourth of 11 to 150 bases (the longer read decides
+    the layout, the shorter one's words end early), every eighth as long as s1 with the planted shift in s1's last 58 bases; s1 random (every fourth) or s2's prefix
+    behind `shift` bases with 0 to 8 flipped bases"""
+    rng = np.random.default_rng(31 + top); cases = []
+    for n in range(joins):
+        L1 = int(rng.integers(top - 28, top + 1)) if n % 8 == 1 else int(rng.integers(top // 2 + 1, top + 1))
+        L2 = L1 if n % 8 == 1 else int(rng.integers(11, 151)) if n % 4 == 3 else int(rng.integers(top // 2 + 1, top + 1))
+        s2_ = rnd(L2, 50000 + 7 * top + n)
+        if n % 4 == 0:
+            s1 = rnd(L1, 60000 + 7 * top + n)
+        else:
+            sh = int(rng.integers(L1 - 58 if n % 8 == 1 else 0, L1 - 10)); body = list((s2_ + rnd(L1, 70000 + 7 * top + n))[:L1])
+            for x in rng.integers(0, max(1, min(L1 - sh, L2)), size=int(rng.integers(0, 9))):
+                body[int(x)] = other(body[int(x)])
+            s1 = (rnd(sh, 80000 + 7 * top + n) + "".join(body))[:L1]
+        cases.append((s1, s2_, None))
+    return cases
+
+
+def batch_conditions(top, found):
+    """what a batch on a long layout has to hold, by the model's values of both directions: hits, misses, hits from lane round 4 on and, with 1018 bases, hits in
+    the last round, where the words past the read are read"""
+    return sum(o > 0 for o in found) > 50 and sum(o == -1 for o in found) > 10 and sum(o > 191 for o in found) > 10 and (top != 1018 or sum(o >= 960 for o in found) > 3)
+
+
+@pytest.mark.parametrize("top", sorted(LONG_TOPS))
+def test_the_seeded_long_batch_is_not_vacuous(top):
+    cases = long_batch(top); distinct(cases)
+    found = [o for s1, s2_, _ in cases for o in (SM.overlap_size(s1, s2_), SM.overlap_size(SM.revcomp(s2_), SM.revcomp(s1)))]
+    assert len(found) == 256 and batch_conditions(top, found), [sum(o > 0 for o in found), sum(o == -1 for o in found), sum(o > 191 for o in found), sum(o >= 960 for o in found)]
+    assert max(len(s1) for s1, _, _ in cases) > (251 if top == 504 else 504)           # the layout the batch is meant for
 
 
 # ------------------------------------------------------------------------------------------ JOIN on chosen reads

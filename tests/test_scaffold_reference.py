@@ -196,6 +196,42 @@ def test_string_overlap_size_on_seeded_pairs(driver, tmp_path):
     ctx.close()
 
 
+def long_seeded_pairs():
+    """150 pairs with L1 in [252, 1018] and L2 <= L1: every second pair of equal lengths (a shorter s2 always passes on a tail of a few bases; -1 needs s2 to reach
+    s1's end), every tenth with s1 of 990 bases and more and its shift in the last lane round; planted with 0 to 8 flipped bases, or random"""
+    rng = np.random.default_rng(29); prs = []
+    for n in range(150):
+        L1 = int(rng.integers(990, 1019)) if n % 10 == 0 else int(rng.integers(252, 1019)); L2 = L1 if n % 2 or n % 10 == 0 else int(rng.integers(11, L1 + 1))
+        s2_ = SH.rnd(L2, 40000 + n)
+        if n % 3 == 1 and n % 10:
+            s1 = SH.rnd(L1, 41000 + n)
+        else:
+            sh = int(rng.integers(960 if n % 10 == 0 else 0, L1 - 10)); bodyl = list((s2_ + SH.rnd(L1, 42000 + n))[:L1])
+            for x in rng.integers(0, max(1, min(L1 - sh, L2)), size=int(rng.integers(0, 9))):
+                bodyl[int(x)] = SH.other(bodyl[int(x)])
+            s1 = (SH.rnd(sh, 43000 + n) + "".join(bodyl))[:L1]
+        prs.append((s1, s2_))
+    return prs
+
+
+def test_string_overlap_size_on_the_long_layouts(driver, tmp_path):
+    """the model at the lengths of the 16- and 32-word read layouts, 252 to 1018 bases: every long pinned case of tests/test_scaffold_host.py with L2 <= L1 (beyond
+    that the reference reads past its string) and 150 seeded pairs.  The counts are conditions on what the model alone says"""
+    pinned = [c for top in sorted(SH.LONG_TOPS) for c in SH.pinned_cases_long(top=top) if len(c[1]) <= len(c[0])]
+    prs = [(a, b) for a, b, _ in pinned] + long_seeded_pairs()
+    want = [SM.overlap_size(a, b) for a, b in prs]
+    assert want[:len(pinned)] == [w for _, _, w in pinned] and len(pinned) == 6 * len(SH.LONG_LENGTHS) + 2 * (2 + 4) and len(prs) == len(pinned) + 150
+    assert all(252 <= len(a) <= 1018 and len(b) <= len(a) for a, b in prs)
+    seeded = want[len(pinned):]
+    assert sum(v > 0 for v in want) > 50 and sum(v == -1 for v in want) > 20 and sum(v >= 960 for v in want) >= 5
+    assert sum(v > 0 for v in seeded) > 50 and sum(v == -1 for v in seeded) > 20 and sum(v >= 960 for v in seeded) >= 5      # (the seeded pairs meet them on their own)
+    ctx, text = tiny()
+    out, _, _ = call(driver, tmp_path, "overlap", ctx, LH.HAND_K, text, "".join("%s %s\n" % p for p in prs))
+    got = [int(x.split()[1]) for x in out if x.startswith("o ")]
+    assert got == want
+    ctx.close()
+
+
 def test_merge_disconnected_edges_on_chosen_reads(driver, tmp_path):
     """the pinned cases of the GPU test as two-edge components over a store of exactly those reads; only pairs of equal read length, since of two unequal reads one
     direction has L2 > L1; gaps negative, zero, positive and beyond the 11-bit field"""
