@@ -557,7 +557,7 @@ int sage2ov_contig_stats_get(const sage2ov_ctx* ctx, sage2ov_contig_stats* out);
 
 /* ---- the first loop of ContigExtender::extendContigs (matePair/mergeContigs.cpp:47-60): findMatepairSupports as a whole (:959-1030) -- the sweep above, the selection
  * of mergeByMatepairSupports (:1112-1255) and mergeEdgesAndUpdate (:1260-1469) applied on the device to the resident step-4 graph -- run until a round
- * merges nothing.  findPathSupports and findPathSupportsNew (:62-99) are PATH SUPPORTS, below; mergeShortOverlaps (:101-) is not part of this library.
+ * merges nothing.  findPathSupports and findPathSupportsNew (:62-99) are PATH SUPPORTS, below; mergeShortOverlaps (:101-110) is SHORT OVERLAPS, after step 7's block, whose selection it shares.
  *   MERGE (e1, e2), e1 entering a node and e2 leaving it (mergeEdgesAndUpdate, overlapGraph.cpp:165-186, :259-266, :299-336): refused (no error, nothing changes) when
  *   e1 == e2, e1 == e2's twin, either is dead, or combinedEdgeType is -1 -- the valid rows are (e1 type, e2 type) -> (0,0) 0, (1,2) 0, (0,1) 1, (1,3) 1, (2,0) 2, (3,2) 2,
  *   (2,1) 3, (3,3) 3.  isReducible is 1 on every edge the loader, step 4 and a merge make (insertEdge sets it, nothing here clears it): no field is carried.
@@ -798,6 +798,43 @@ int sage2ov_scaffold(sage2ov_ctx* ctx, uint64_t genome_size, uint64_t* rounds, u
 int sage2ov_scaffold_merges_count(const sage2ov_ctx* ctx, uint64_t* n);
 int sage2ov_scaffold_merges_export(const sage2ov_ctx* ctx, sage2ov_join* out, uint64_t cap);
 int sage2ov_scaffold_stats_get(const sage2ov_ctx* ctx, sage2ov_scaffold_stats* out);
+
+/* ---- SHORT OVERLAPS: the fourth loop of ContigExtender::extendContigs (matePair/mergeContigs.cpp:101-110): mergeShortOverlaps (:1474-1648) with mergeShortOverlap
+ * (:1788-1908) and mergeDisconnectedEdges1 (:1913-2114), on the device.  It joins contigs whose mates say that they overlap (a summed gap of at
+ * most 0) but whose overlap the graph does not hold.  All citations without a file are matePair/mergeContigs.cpp.  Its sweep (:1494-1635) is the sweep of
+ * sage2ov_links, its merge is JOIN of step 7, its selection is step 7's with the three changes below; only the raw gap sum is new.
+ *   GAPSUM.  The sweep adds Mean[lib] - (distance + 2 averageReadLength) per supporting mate into an int32_t (:1577) that wraps like the reference's; LINK.gap is
+ *   gapSum / support truncated towards zero (:1592), so a gapSum of +1 over support 2 has gap 0 and yet fails :1587.  The table keeps both.
+ *   A ROUND (high): ROWS = for every LINK(a, b) of the unfiltered table with a < b as half-edge pool indices (rule (a) of step 7, for :1527), flow of E(pair(a)) and
+ *   of E(pair(b)) both > 0 (from the host copy, as SAGE2OV_LINKS_FINAL reads them; a graph without flows has no rows), both lengths strictly above
+ *   contigLengthThreshold = (int)ceilf(100 * (averageReadLength / 100.0)) (:21, :1500: there is no "> 200" alternative here) and gapSum <= 0 (:1587):
+ *   {edge_1 = a's twin, edge_2 = b, support, gap = gapSum / support}, in the table's export order.  SEARCH, the filing under four end nodes, the sort (:2119-2142),
+ *   SKIPPED, BELOW, FEASIBLE from the unfiltered table, SPENT, count1, count2 and rules (b)-(e) are those of step 7's ROUND.  A row joins iff count1 == 0 and
+ *   count2 == 0 (:1858-1878: any rival at or above high on either side); there is no cycle test, a rival on both sides is BLOCKED like any other and `cycles` stays 0.
+ *   JOIN(edge_1, edge_2, gap) then runs as a batch on the device.  gapSum <= 0 gives gap <= 0: without an overlap a negative gap concatenates and a gap of 0
+ *   takes the `gap >= 0` branch of getListOfReadsInDisconnectedEdges: SAGE2OV_JOIN_GAPPED with D1 = L1, D2 = L2, no N.
+ *   Equality with the reference is claimed for high >= 1, under the conditions of step 7's contract (outside_reference 0, no ties of the sort).  For high <= 0
+ *   the round does what sage2ov_scaffold_round does with such a value: no row is BELOW, and a missing SEARCH entry counts as a rival of support 0 on edge_1's side
+ *   (count2) while it is no rival on edge_2's side; the reference's own loop passes no negative value, and 0 only when the coverage quotient is 0.
+ *   THE LOOP (:101-110): rounds at high = (int)ceilf((0.05 * coverage) * (100.0 / averageReadLength)), coverage as in sage2ov_extend_threshold, whatever the genome
+ *   size, until a round joins nothing.
+ * The records and totals of these rounds are kept apart from step 7's: sage2ov_scaffold_merges_* and sage2ov_scaffold_stats_get do not see them. */
+/* gapSum of exactly the rows sage2ov_links_export(mode, min_support) returns, in the same order.  Errors as for that call; builds the table when it is stale. */
+int sage2ov_links_gap_sums(sage2ov_ctx* ctx, uint32_t mode, uint32_t min_support, int32_t* out, uint64_t cap);
+/* high of THE LOOP.  Host only.  genome_size or average_read_length 0: SAGE2OV_ERR_ARG. */
+int sage2ov_extend_short_threshold(uint64_t reads, uint64_t average_read_length, uint64_t genome_size, int* high);
+/* one round, mergeShortOverlaps(k, high); *merged (may be NULL) = its joins.  Errors as for sage2ov_scaffold_round. */
+int sage2ov_extend_short_round(sage2ov_ctx* ctx, int high, uint64_t* merged);
+/* THE LOOP; *rounds counts the empty round that ends it too.  genome_size 0, reads and average read length: as for sage2ov_extend_by_supports.  After 10 000
+ * rounds: SAGE2OV_ERR_INTERNAL. */
+int sage2ov_extend_by_short_overlaps(sage2ov_ctx* ctx, uint64_t genome_size, uint64_t* rounds, uint64_t* merged);
+/* ContigExtender::extendContigs as a whole (:37-113): sage2ov_extend_by_supports, sage2ov_extend_by_paths variant 0, then variant 1, then
+ * sage2ov_extend_by_short_overlaps; rounds[i] and merged[i] (either may be NULL) are those of loop i, 0 for a loop an error kept from running. */
+int sage2ov_extend_contigs(sage2ov_ctx* ctx, uint64_t genome_size, uint64_t rounds[4], uint64_t merged[4]);
+/* the joins of the last short-overlap round in selection order, and the counters of these rounds (cycles is always 0) */
+int sage2ov_extend_short_merges_count(const sage2ov_ctx* ctx, uint64_t* n);
+int sage2ov_extend_short_merges_export(const sage2ov_ctx* ctx, sage2ov_join* out, uint64_t cap);
+int sage2ov_extend_short_stats_get(const sage2ov_ctx* ctx, sage2ov_scaffold_stats* out);
 
 /* diagnostic: table census {occupied, inline, claimed-but-unfilled, zero-tag, entries in short CSR buckets} */
 int sage2ov_debug_table(sage2ov_ctx* ctx, uint64_t* out5);

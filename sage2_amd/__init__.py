@@ -303,6 +303,15 @@ def scaffold_threshold(reads, average_read_length, genome_size, loop, iteration=
     return int(out.value)
 
 
+def extend_short_threshold(reads, average_read_length, genome_size) -> int:
+    """highTh of the fourth loop of ContigExtender::extendContigs (mergeContigs.cpp:43, :102), on the host: no context, no GPU"""
+    out = C.c_int(0)
+    rc = lib().sage2ov_extend_short_threshold(C.c_uint64(reads), C.c_uint64(average_read_length), C.c_uint64(genome_size), C.byref(out))
+    if rc:
+        raise Sage2ovError(rc, "extend_short_threshold")
+    return int(out.value)
+
+
 class Context:
     """One overlap-detection job on one GPU (sage2ov_ctx).  Method names follow include/sage2ov.h."""
 
@@ -667,6 +676,41 @@ class Context:
         self._chk(lib().sage2ov_scaffold_stats_get(self._h, C.byref(s)))
         return s
 
+    # ---- the fourth loop of extendContigs (mergeContigs.cpp:101-110): mergeShortOverlaps, joins of contigs whose mates give a summed gap of at most 0
+    extend_short_threshold = staticmethod(extend_short_threshold)
+
+    def extend_short_round(self, high) -> int:
+        """one mergeShortOverlaps(k, high): sweep, selection, joins; returns the number of joins"""
+        n = C.c_uint64(0)
+        self._chk(lib().sage2ov_extend_short_round(self._h, C.c_int(high), C.byref(n)))
+        return int(n.value)
+
+    def extend_by_short_overlaps(self, genome_size=0):
+        """rounds until one joins nothing -> (rounds, joins)"""
+        r, m = C.c_uint64(0), C.c_uint64(0)
+        self._chk(lib().sage2ov_extend_by_short_overlaps(self._h, C.c_uint64(genome_size), C.byref(r), C.byref(m)))
+        return int(r.value), int(m.value)
+
+    def extend_contigs(self, genome_size=0):
+        """the four loops of extendContigs in the reference's order -> ([rounds of each loop], [merges of each loop])"""
+        r, m = (C.c_uint64 * 4)(), (C.c_uint64 * 4)()
+        self._chk(lib().sage2ov_extend_contigs(self._h, C.c_uint64(genome_size), r, m))
+        return [int(x) for x in r], [int(x) for x in m]
+
+    def extend_short_merges(self) -> np.ndarray:
+        """the joins of the last short-overlap round (JOIN_DTYPE) in selection order"""
+        n = C.c_uint64(0)
+        self._chk(lib().sage2ov_extend_short_merges_count(self._h, C.byref(n)))
+        out = np.zeros(n.value, dtype=JOIN_DTYPE)
+        self._chk(lib().sage2ov_extend_short_merges_export(self._h, C.c_void_p(out.ctypes.data), C.c_uint64(n.value)))
+        return out
+
+    def extend_short_stats(self) -> ScaffoldStats:
+        """the counters of the short-overlap rounds; the scaffold's own (scaffold_stats) do not see them"""
+        s = ScaffoldStats()
+        self._chk(lib().sage2ov_extend_short_stats_get(self._h, C.byref(s)))
+        return s
+
     # ---- the sweep that opens ScaffoldMaker::mergeFinal / mergeFinalSmall (scaffolding.cpp:786-935, :981-1130): support and gap of half-edge pairs linked by mates
     def links(self, mode=0, min_support=1) -> np.ndarray:
         """the rows (LINK_DTYPE) that pass the filter (LINKS_ALL / LINKS_FINAL / LINKS_SMALL) with support >= min_support, in ascending
@@ -675,6 +719,14 @@ class Context:
         self._chk(lib().sage2ov_links_count(self._h, C.c_uint32(mode), C.c_uint32(min_support), C.byref(n)))
         out = np.zeros(n.value, dtype=LINK_DTYPE)
         self._chk(lib().sage2ov_links_export(self._h, C.c_uint32(mode), C.c_uint32(min_support), C.c_void_p(out.ctypes.data), C.c_uint64(n.value)))
+        return out
+
+    def links_gap_sums(self, mode=0, min_support=1) -> np.ndarray:
+        """the int32 gapSum of the rows links(mode, min_support) returns, in the same order (a row's gap is gapSum / support, truncated towards zero)"""
+        n = C.c_uint64(0)
+        self._chk(lib().sage2ov_links_count(self._h, C.c_uint32(mode), C.c_uint32(min_support), C.byref(n)))
+        out = np.zeros(n.value, dtype=np.int32)
+        self._chk(lib().sage2ov_links_gap_sums(self._h, C.c_uint32(mode), C.c_uint32(min_support), C.c_void_p(out.ctypes.data), C.c_uint64(n.value)))
         return out
 
     def links_build(self):

@@ -16,7 +16,7 @@
 //   k_mate_iota, radix_sort_pairs   only the passes whose digit can be non-zero
 //   k_sl_gather      the values in sorted order, and one 0 behind them; (scan, mod 2^32): gapSum of a run is the difference of two scanned values
 //   k_mate_heads, (scan) + k_headpos
-//   k_sl_reduce      row e: the key of head e, support = the run's length, gap = (int32_t)gapSum / support (:892)
+//   k_sl_reduce      row e: the key of head e, support = the run's length, gap = (int32_t)gapSum / support (:892), and gapSum itself (mergeContigs.cpp:1587 reads it)
 // A library is the MsLib of kernels_support.inc.  Every count is kept below 2^32 - RS_TILE by the driver.  No kernel uses LDS or scratch; the d1 x d2 loops read the locations from memory, no array is indexed.
 // =============================================================================================
 constexpr u32 SL_NO_SIGN = 10000000u;                                        // distance_all of an (x, y) that fails the sign test (:854)
@@ -97,9 +97,10 @@ __global__ void k_sl_gather(const u32* __restrict__ idx, const u32* __restrict__
     out[i] = i < n ? val[idx[i]] : 0u;
 }
 // sc: the exclusive scan, mod 2^32, of the n + 1 gathered values
-__global__ void k_sl_reduce(const u64* __restrict__ keys, const u32* __restrict__ hp, const u32* __restrict__ sc, u32 E, u64* outKey, u32* outSup, int* outGap) {
+__global__ void k_sl_reduce(const u64* __restrict__ keys, const u32* __restrict__ hp, const u32* __restrict__ sc, u32 E, u64* outKey, u32* outSup, int* outGap, int* outSum) {
     const u32 e = blockIdx.x * blockDim.x + threadIdx.x; if (e >= E) return;
     const u32 i = hp[e], j = hp[e + 1], s = j - i;
     const int sum = (int)(sc[j] - sc[i]);                                              // int32_t gapSum (:782, :878)
     outKey[e] = keys[i]; outSup[e] = s; outGap[e] = (int)((long long)sum / (long long)s);      // :892 (s >= 1; the division truncates towards zero)
+    outSum[e] = sum;
 }

@@ -153,6 +153,13 @@ public:
         std::vector<sage2ov_join> out(n); ctx().check(sage2ov_scaffold_merges_export(ctx().get(), out.data(), n));
         return out;
     }
+    // the raw int32_t gapSum of the rows scaffoldLinks(mode, minSupport) returns, in the same order (mergeContigs.cpp:1587 reads it; a row's gap is its quotient)
+    std::vector<int32_t> scaffoldLinkGapSums(uint32_t mode = SAGE2OV_LINKS_ALL, uint32_t minSupport = 1) {
+        uint64_t n = 0; ctx().check(sage2ov_links_count(ctx().get(), mode, minSupport, &n));
+        std::vector<int32_t> out(n); ctx().check(sage2ov_links_gap_sums(ctx().get(), mode, minSupport, out.data(), n));
+        return out;
+    }
+    void graphChanged() { table_ = false; }              // a merge or join made outside this object: the cached read-to-edge table is stale
     ReadLoader* loaderObj;
 private:
     Context& ctx() const { return loaderObj->context(); }
@@ -165,6 +172,33 @@ private:
     }
     std::vector<sage2ov_mate> entries_; std::vector<uint64_t> offsets_; int cachedLibrary_ = 0;
     std::vector<sage2ov_read_edge> edges_; std::vector<int32_t> locations_; std::vector<uint64_t> edgeOffsets_; bool table_ = false;
+};
+
+// ContigExtender (mergeContigs.h): the fourth loop of extendContigs and the whole function, on the resident graph (the first three loops are also MatePair's
+// findMatepairSupports sweep with sage2ov_extend_round, findPathSupports and extendByPaths above)
+class ContigExtender {
+public:
+    explicit ContigExtender(MatePair* mate1) : mateObj(mate1) {}
+    // mergeShortOverlaps (mergeContigs.cpp:1474-1648): one round.  The sweep uses the context's k, as every sweep here does: minOverlap is not read
+    uint64_t mergeShortOverlaps(uint16_t /*minOverlap*/, int highTh) {
+        uint64_t m = 0; ctx().check(sage2ov_extend_short_round(ctx().get(), highTh, &m)); mateObj->graphChanged(); return m;
+    }
+    std::vector<sage2ov_join> shortOverlapJoins() {
+        uint64_t n = 0; ctx().check(sage2ov_extend_short_merges_count(ctx().get(), &n));
+        std::vector<sage2ov_join> out(n); ctx().check(sage2ov_extend_short_merges_export(ctx().get(), out.data(), n));
+        return out;
+    }
+    sage2ov_scaffold_stats shortOverlapStats() const { sage2ov_scaffold_stats s{}; ctx().check(sage2ov_extend_short_stats_get(ctx().get(), &s)); return s; }
+    // extendContigs (:37-113): the four loops; returns the total number of merges (sum_node_resolved); rounds / merged (may be null): four values each
+    uint64_t extendContigs(uint16_t /*minOverlap*/, uint64_t genomeSize = 0, uint64_t* rounds = nullptr, uint64_t* merged = nullptr) {
+        uint64_t r[4] = {0, 0, 0, 0}, m[4] = {0, 0, 0, 0};
+        const int rc = sage2ov_extend_contigs(ctx().get(), genomeSize, r, m); mateObj->graphChanged();
+        for (int i = 0; i < 4; i++) { if (rounds) rounds[i] = r[i]; if (merged) merged[i] = m[i]; }
+        ctx().check(rc); return m[0] + m[1] + m[2] + m[3];
+    }
+    MatePair* mateObj;
+private:
+    Context& ctx() const { return mateObj->loaderObj->context(); }
 };
 
 // HashTable (hashTable.h:20-43)

@@ -37,8 +37,10 @@ static void printListOfArgs() {
             "\t--flowNetwork\t\tstep 5 up to its solver: estimate the genome size and write <outputDir>input.cs2 (after step 4, or with -m 5 from <inputPrefix>.graph4)\n"
             "\t--flowSolution <string>\tstep 5 after its solver: apply this output.cs2 to the flows and write <prefix>.graph5\n"
             "\t--extend\t\twith -m 6: load <inputPrefix>.graph5, map the mate pairs of -f|-l, estimate the insert sizes, merge contigs by mate-pair\n"
-            "\t\t\tsupport until a round merges nothing (the first loop of extendContigs) and write <prefix>.graph6 [--genomeSize: the estimate on the loaded graph]\n"
+            "\t\t\tsupport until a round merges nothing (the first loop of extendContigs; --paths and --shortOverlaps add the others) and write <prefix>.graph6 [--genomeSize: the estimate on the loaded graph]\n"
             "\t--paths\t\t\twith -m 6 --extend: after the first loop, the loops of findPathSupports and findPathSupportsNew (merges by path support)\n"
+            "\t--shortOverlaps\t\twith -m 6 --extend: after those, the loop of mergeShortOverlaps (joins of contigs whose mates give a summed gap of at most 0);\n"
+            "\t\t\t--extend --paths --shortOverlaps is the whole extendContigs\n"
             "\t--scaffold\t\twith -m 7: load <inputPrefix>.graph6, map the mate pairs of -f|-l, estimate the insert sizes, join contigs that share no node by\n"
             "\t\t\tmate-pair links (the five loops of makeScaffolds) and write <prefix>_scaffold.fasta; with -m 6 --extend: go on from the merged graph, no new estimate\n\t-h|--help\n\n";
 }
@@ -47,7 +49,7 @@ static double now() { return chrono::duration<double>(chrono::steady_clock::now(
 
 int main(int argc, char* argv[]) {
     const double tMain = now(); const bool timing = getenv("SAGE2OV_TIMING") != nullptr;
-    int minStep = 1, maxStep = 3, gpu = 0, gpus = 1, failRank = -1; bool shareGpu = false, forceMulti = false; unsigned minOverlap = 0; bool contigs = false, extend = false, paths = false, scaffold = false, flowNetwork = false, genomeSizeGiven = false, maxGiven = false; string flowSolution; unsigned long long genomeSize = 0; bool saveAll = false, debugging = false, fFlag = false, lFlag = false;
+    int minStep = 1, maxStep = 3, gpu = 0, gpus = 1, failRank = -1; bool shareGpu = false, forceMulti = false; unsigned minOverlap = 0; bool contigs = false, extend = false, paths = false, shortOverlaps = false, scaffold = false, flowNetwork = false, genomeSizeGiven = false, maxGiven = false; string flowSolution; unsigned long long genomeSize = 0; bool saveAll = false, debugging = false, fFlag = false, lFlag = false;
     string fileInput, listInput, outputDir, prefixName = "untitled", inputPrefix;
     static struct option opts[] = {{"help", no_argument, 0, 'h'}, {"fileInput", required_argument, 0, 'f'}, {"minOverlap", required_argument, 0, 'k'},
         {"listInput", required_argument, 0, 'l'}, {"outputDir", required_argument, 0, 'o'}, {"prefix", required_argument, 0, 'p'},
@@ -55,7 +57,7 @@ int main(int argc, char* argv[]) {
         {"saveAll", no_argument, 0, 's'}, {"debug", no_argument, 0, 'd'}, {"gpu", required_argument, 0, 'g'}, {"gpus", required_argument, 0, 'G'},
         {"share-gpu", no_argument, 0, 1001},      // rehearsal: all ranks on device `gpu`, exchanges by device copies instead of RCCL (a box with fewer GPUs than ranks)
         {"fail-rank", required_argument, 0, 1003},  // tests: this rank of a multi-GPU run fails before its first step (the run must end non-zero, not hang)
-        {"contigs", no_argument, 0, 1004}, {"genomeSize", required_argument, 0, 1005}, {"flowNetwork", no_argument, 0, 1006}, {"flowSolution", required_argument, 0, 1007}, {"extend", no_argument, 0, 1008}, {"scaffold", no_argument, 0, 1009}, {"paths", no_argument, 0, 1010},
+        {"contigs", no_argument, 0, 1004}, {"genomeSize", required_argument, 0, 1005}, {"flowNetwork", no_argument, 0, 1006}, {"flowSolution", required_argument, 0, 1007}, {"extend", no_argument, 0, 1008}, {"scaffold", no_argument, 0, 1009}, {"paths", no_argument, 0, 1010}, {"shortOverlaps", no_argument, 0, 1011},
         {"force-multi", no_argument, 0, 1002},    // the multi-GPU code path (RCCL communicator, the four exchanges) even with one GPU
         {0, 0, 0, 0}};
     int c, oi = 0;
@@ -83,6 +85,7 @@ int main(int argc, char* argv[]) {
             case 1007: flowSolution = optarg; break;
             case 1008: extend = true; break;
             case 1010: paths = true; break;
+            case 1011: shortOverlaps = true; break;
             case 1009: scaffold = true; break;
             case '?': cout << "\n"; exit(0);
             default: cout << "[ERROR] Wrong command line arguments!\n\n"; exit(0);
@@ -102,6 +105,7 @@ int main(int argc, char* argv[]) {
     if (minStep > 5 && step5) { cout << "[ERROR] --flowNetwork and --flowSolution work on the graph after step 4 (-m 5 at the most).\n"; exit(0); }
     if (extend && (minStep != 6 || (fileInput == "" && listInput == ""))) { cout << "[ERROR] --extend works on <inputPrefix>.graph5 (-m 6) and needs the mate pairs (-f or -l).\n"; exit(0); }
     if (paths && !(extend && minStep == 6)) { cout << "[ERROR] --paths goes with -m 6 --extend.\n"; exit(0); }
+    if (shortOverlaps && !(extend && minStep == 6)) { cout << "[ERROR] --shortOverlaps goes with -m 6 --extend.\n"; exit(0); }
     if (scaffold && (!(minStep == 7 || (minStep == 6 && extend)) || (fileInput == "" && listInput == ""))) { cout << "[ERROR] --scaffold works on <inputPrefix>.graph6 (-m 7), or after --extend (-m 6), and needs the mate pairs (-f or -l).\n"; exit(0); }
     if (minStep > 4 && !contigs && !step5 && !extend && !scaffold) { cout << "[ERROR] sage2ov implements steps 1-4; continue with: SAGE2 -m " << minStep << " -i " << inputPrefix << " ...\n"; exit(0); }
     (void)debugging;
@@ -181,7 +185,7 @@ int main(int argc, char* argv[]) {
             OverlapGraph graphObj(&loaderObj);
             graphObj.loadCompositeGraphFromFile(outputDir + inputPrefix + ".graph" + to_string(minStep - 1));
             copyCounts();
-            if (extend) {                                                                     // main.cpp:236-244, the first loop of extendContigs (mergeContigs.cpp:47-60)
+            if (extend) {                                                                     // main.cpp:236-244, extendContigs (mergeContigs.cpp:37-113): its first loop, the others by --paths and --shortOverlaps
                 double t6 = now();
                 logStream << "STEP 6: map mate pairs & merge by mate-pair support\n";
                 if (listInput != "") ctx.check(sage2ov_mates_add_list(ctx.get(), listInput.c_str()));
@@ -203,9 +207,18 @@ int main(int argc, char* argv[]) {
                         ctx.check(rc2); merged += m;
                     }
                 }
+                if (shortOverlaps) {                                                          // the fourth loop (mergeContigs.cpp:101-110)
+                    uint64_t r = 0, m = 0;
+                    const int rc2 = sage2ov_extend_by_short_overlaps(ctx.get(), genomeSizeGiven ? genomeSize : 0, &r, &m);
+                    sage2ov_scaffold_stats ss{}; ctx.check(sage2ov_extend_short_stats_get(ctx.get(), &ss));
+                    logStream << "\tRounds of mergeShortOverlaps: " << r << " (" << ss.total.rows << " rows, " << ss.total.below_threshold << " below the threshold, " << ss.total.skipped << " skipped, "
+                              << ss.total.blocked << " blocked; lists joined by overlap " << ss.total.overlaps << ", concatenated " << ss.total.concatenated
+                              << ", with a gap " << ss.total.gapped << "; " << m << " merges)\n";
+                    ctx.check(rc2); merged += m;
+                }
                 logStream << "\nTotal number of extended contigs: " << merged << "\n";
                 ctx.check(sage2ov_graph6_save(ctx.get(), (outputDir + prefixName + ".graph6").c_str()));
-                logStream << "\t" << prefixName << ".graph6 written\n\tFirst loop of step 6 in " << now() - t6 << " sec.\n";
+                logStream << "\t" << prefixName << ".graph6 written\n\t" << (paths && shortOverlaps ? "Step 6" : paths ? "Loops 1-3 of step 6" : shortOverlaps ? "Loops 1 and 4 of step 6" : "First loop of step 6") << " in " << now() - t6 << " sec.\n";
             }
             if (contigs) writeContigs(graphObj);
             if (scaffold) {                                                                   // main.cpp:263-290, makeScaffolds (scaffolding.cpp:31-98)

@@ -2810,7 +2810,7 @@ int dev_support_export(Device* d, uint64_t* key, uint32_t* support, std::string&
 // =============================================================================================
 // the scaffold links of ordered half-edge pairs (kernels_links.inc; the sweep that opens ScaffoldMaker::mergeFinal / mergeFinalSmall, scaffolding.cpp:786-935, :981-1130)
 // =============================================================================================
-struct Links { u64* key = nullptr; u32* sup = nullptr; int* gap = nullptr; u64 E = 0; ~Links() { hipFree(key); hipFree(sup); hipFree(gap); } };
+struct Links { u64* key = nullptr; u32* sup = nullptr; int* gap = nullptr; int* sum = nullptr; u64 E = 0; ~Links() { hipFree(key); hipFree(sup); hipFree(gap); hipFree(sum); } };
 void dev_links_release(Device* d) { if (d->links) { hipSetDevice(d->ordinal); delete (Links*)d->links; d->links = nullptr; } }
 uint64_t dev_links_count(Device* d) { const Links* S = (const Links*)d->links; return S ? S->E : 0; }
 static int links_nomem(std::string& err) { err = "scaffold links: out of device memory"; return SAGE2OV_ERR_NOMEM; }
@@ -2883,21 +2883,21 @@ int dev_links_build(Device* d, const LinkParams& P, LinkStats* st, std::string& 
     // ---- reduce: one row per distinct key
     u32* hp = nullptr; u32 E = 0;
     { const int rc = mate_heads(d, B, ks, (u32)R, &hp, &E, err); if (rc) return rc; }
-    S->key = (u64*)DevTmp::alloc((u64)E * sizeof(u64)); S->sup = (u32*)DevTmp::alloc((u64)E * sizeof(u32)); S->gap = (int*)DevTmp::alloc((u64)E * sizeof(int));
-    if (!S->key || !S->sup || !S->gap) return links_nomem(err);
-    hipLaunchKernelGGL(k_sl_reduce, dim3(grid_for(E, 256)), b256, 0, sm, ks, hp, sc, E, S->key, S->sup, S->gap);
+    S->key = (u64*)DevTmp::alloc((u64)E * sizeof(u64)); S->sup = (u32*)DevTmp::alloc((u64)E * sizeof(u32)); S->gap = (int*)DevTmp::alloc((u64)E * sizeof(int)); S->sum = (int*)DevTmp::alloc((u64)E * sizeof(int));
+    if (!S->key || !S->sup || !S->gap || !S->sum) return links_nomem(err);
+    hipLaunchKernelGGL(k_sl_reduce, dim3(grid_for(E, 256)), b256, 0, sm, ks, hp, sc, E, S->key, S->sup, S->gap, S->sum);
     HIPCHK(hipGetLastError());
     HIPCHK(lap.stop(st->reduce_ms));
     S->E = E; st->keys = E;
     d->links = S.release();
     return 0;
 }
-int dev_links_export(Device* d, uint64_t* key, uint32_t* support, int32_t* gap, std::string& err) {
+int dev_links_export(Device* d, uint64_t* key, uint32_t* support, int32_t* gap, int32_t* gapSum, std::string& err) {
     HIPCHK(hipSetDevice(d->ordinal));
     const Links* S = (const Links*)d->links; if (!S) { err = "scaffold links: not built"; return SAGE2OV_ERR_INTERNAL; }
     if (S->E) {
         HIPCHK(hipMemcpy(key, S->key, S->E * sizeof(u64), hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(support, S->sup, S->E * sizeof(u32), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(gap, S->gap, S->E * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(gap, S->gap, S->E * sizeof(int), hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(gapSum, S->sum, S->E * sizeof(int), hipMemcpyDeviceToHost));
     }
     return 0;
 }

@@ -11,6 +11,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <parallel/algorithm>
 #include <string>
 #include <thread>
@@ -131,7 +132,8 @@ struct sage2ov_ctx {
     // ---- the scaffold links (sage2ov_links): built on the device, kept here in export order, unfiltered, once a call has asked for them; the flows are read at export
     bool linkValid = false, linkOnHost = false;        // the table is of the present graph, mates and estimate (it also needs `estimated`)
     sage2ov_link_stats lstats{}; std::vector<sage2ov_link> links; std::vector<uint32_t> linkHalves;      // linkHalves: E(pair(a)), E(pair(b)) of every row, internal half-edges
-    void links_forget() { linkValid = linkOnHost = false; links.clear(); linkHalves.clear(); lstats = sage2ov_link_stats{}; }
+    std::vector<int32_t> linkSums;                     // the raw int32_t gapSum of every row (mergeContigs.cpp:1587 reads it; links[e].gap is its quotient)
+    void links_forget() { linkValid = linkOnHost = false; links.clear(); linkHalves.clear(); linkSums.clear(); lstats = sage2ov_link_stats{}; }
     // ---- the contigs (sage2ov_contigs_*): rows and layout are built on the device and kept here in table order; threshold and genome size as the last build was asked
     bool ctgValid = false; uint32_t ctgThreshold = 0, ctgThresholdUsed = 0; uint64_t ctgGenome = 0; sage2ov_contig_stats cstats{};
     std::vector<ContigRow> ctgRows; std::vector<uint64_t> ctgChunk;      // ctgChunk[r]: 16-byte chunks of the device buffer in front of row r (every row begins at a chunk); R + 1 values
@@ -144,7 +146,8 @@ struct sage2ov_ctx {
     bool estimateHeld = false, hdrHeld = false; uint64_t hdrGenome = 0, hdrReads = 0;
     sage2ov_extend_stats xstats{}; std::vector<sage2ov_merge> xmerges;
     sage2ov_scaffold_stats scstats{}; std::vector<sage2ov_join> scjoins;      // the scaffold rounds (sage2ov_scaffold_*)
-    void extend_forget() { estimateHeld = hdrHeld = false; hdrGenome = hdrReads = 0; xstats = sage2ov_extend_stats{}; xmerges.clear(); scstats = sage2ov_scaffold_stats{}; scjoins.clear(); }
+    sage2ov_scaffold_stats sostats{}; std::vector<sage2ov_join> sojoins;      // the short-overlap rounds of step 6 (sage2ov_extend_short_*), kept apart from step 7's
+    void extend_forget() { estimateHeld = hdrHeld = false; hdrGenome = hdrReads = 0; xstats = sage2ov_extend_stats{}; xmerges.clear(); scstats = sage2ov_scaffold_stats{}; scjoins.clear(); sostats = sage2ov_scaffold_stats{}; sojoins.clear(); }
     void readmap_forget() { rmValid = estimated = false; extend_forget(); pairOrdinal.clear(); rmstats = sage2ov_readmap_stats{}; supports_forget(); paths_forget(); links_forget(); contigs_forget(); copycount_forget(); }      // the graph or the read set goes
     void mates_forget(bool readSetGoes = true) {       // the read set goes: its ids mean nothing any more (the device drops its part in free_reads) -- or sage2ov_mates_clear
         if (readSetGoes) { readmap_forget(); readsGen++; } else estimated = estimateHeld = false;
@@ -2697,8 +2700,8 @@ int links_ensure(sage2ov_ctx* c, const char* who) {
 int links_fetch(sage2ov_ctx* c) {
     if (c->linkOnHost) return SAGE2OV_OK;
     Device* d = c->device(); const uint64_t E = dev_links_count(d);
-    std::vector<uint64_t> key(E); std::vector<uint32_t> sup(E); std::vector<int32_t> gap(E);
-    { const int rc = dev_links_export(d, key.data(), sup.data(), gap.data(), c->err); if (rc) return rc; }
+    std::vector<uint64_t> key(E); std::vector<uint32_t> sup(E); std::vector<int32_t> gap(E), sum(E);
+    { const int rc = dev_links_export(d, key.data(), sup.data(), gap.data(), sum.data(), c->err); if (rc) return rc; }
     { const int rc = pair_ordinals(c); if (rc) return rc; }
     const SimplifiedGraph& g = c->g4; const std::vector<uint32_t>& ord = c->pairOrdinal;
     std::vector<uint32_t> order, first(g.n_half_edges / 2 + 1, ~0u); g4_save_order(g, order);      // first[pair]: the half that opens the pair's record in the save (a loop: the first time)
@@ -2719,8 +2722,8 @@ int links_fetch(sage2ov_ctx* c) {
         if (p.second_a != q.second_a) return p.second_a < q.second_a;
         if (p.pair_b != q.pair_b) return p.pair_b < q.pair_b;
         return p.second_b < q.second_b; });
-    c->links.resize(E); c->linkHalves.resize(2 * E);
-    for (uint64_t e = 0; e < E; e++) { c->links[e] = rows[at[e]]; c->linkHalves[2 * e] = halves[2 * at[e]]; c->linkHalves[2 * e + 1] = halves[2 * at[e] + 1]; }
+    c->links.resize(E); c->linkHalves.resize(2 * E); c->linkSums.resize(E);
+    for (uint64_t e = 0; e < E; e++) { c->links[e] = rows[at[e]]; c->linkHalves[2 * e] = halves[2 * at[e]]; c->linkHalves[2 * e + 1] = halves[2 * at[e] + 1]; c->linkSums[e] = sum[at[e]]; }
     c->linkOnHost = true;
     return SAGE2OV_OK;
 }
@@ -2732,6 +2735,13 @@ bool link_passes(const sage2ov_ctx* c, uint64_t e, uint32_t mode, int threshold)
     const std::vector<float>& f = c->g4.flow;
     const float f1 = f.empty() ? 0.f : f[c->linkHalves[2 * e]], f2 = f.empty() ? 0.f : f[c->linkHalves[2 * e + 1]];
     return (len1 > 200 && len2 > 200) || ((f1 > 0 && len1 > threshold) && (f2 > 0 && len2 > threshold));
+}
+// mergeContigs.cpp:1500 and :1587 on row e: both flows and lengths, no "> 200" alternative, and the raw gap sum
+bool short_passes(const sage2ov_ctx* c, uint64_t e, int threshold) {
+    const sage2ov_link& r = c->links[e]; const int64_t len1 = r.len_a, len2 = r.len_b;
+    const std::vector<float>& f = c->g4.flow; if (f.empty()) return false;
+    const float f1 = f[c->linkHalves[2 * e]], f2 = f[c->linkHalves[2 * e + 1]];
+    return (f1 > 0 && len1 > threshold) && (f2 > 0 && len2 > threshold) && c->linkSums[e] <= 0;
 }
 }  // namespace
 int sage2ov_links(sage2ov_ctx* c) {
@@ -2768,6 +2778,15 @@ int sage2ov_links_export(sage2ov_ctx* c, uint32_t mode, uint32_t min_support, sa
     if (m && !out) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_links_export: null argument");
     const int thr = link_length_threshold(c);
     uint64_t at = 0; for (uint64_t e = 0; e < c->links.size(); e++) if (c->links[e].support >= min_support && link_passes(c, e, mode, thr)) out[at++] = c->links[e];
+    return SAGE2OV_OK;
+}
+int sage2ov_links_gap_sums(sage2ov_ctx* c, uint32_t mode, uint32_t min_support, int32_t* out, uint64_t cap) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    uint64_t m = 0; { const int rc = sage2ov_links_count(c, mode, min_support, &m); if (rc) return rc; }
+    if (cap < m) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_links_gap_sums: the buffer holds fewer rows than the table (sage2ov_links_count)");
+    if (m && !out) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_links_gap_sums: null argument");
+    const int thr = link_length_threshold(c);
+    uint64_t at = 0; for (uint64_t e = 0; e < c->links.size(); e++) if (c->links[e].support >= min_support && link_passes(c, e, mode, thr)) out[at++] = c->linkSums[e];
     return SAGE2OV_OK;
 }
 int sage2ov_link_stats_get(const sage2ov_ctx* c, sage2ov_link_stats* o) { if (!c || !o) return SAGE2OV_ERR_ARG; *o = c->lstats; return SAGE2OV_OK; }
@@ -2810,30 +2829,30 @@ int sage2ov_scaffold_threshold(uint64_t reads, uint64_t arl, uint64_t genomeSize
     else *high = loop == 3 ? 2 : 1;
     return SAGE2OV_OK;
 }
-int sage2ov_scaffold_round(sage2ov_ctx* c, int highTh, int flag, int small, uint64_t* merged) {                        // :774-967, :488-769
-    if (!c) return SAGE2OV_ERR_ARG;
-    if (flag != 1 && flag != 2) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_scaffold_round: flag is 1 or 2");
-    { const int rc = readmap_check(c, "sage2ov_scaffold_round"); if (rc) return rc; }
+namespace {
+// one round of joins on the link table: the selection of mergeAccordingToSupport / mergeAccordingToSupport2 (scaffolding.cpp:488-769) and of mergeShortOverlap
+// (mergeContigs.cpp:1788-1908) differ in three things: which rows of the table are ROWS (filter: the row's index in export order), how many rivals at or above
+// highTh each side may have (limit), and whether a rival counted on both sides makes the row a CYCLE (cycleTest).  The round's records go to `stats` and `out`.
+int join_round(sage2ov_ctx* c, const char* who, int highTh, const std::function<bool(uint64_t)>& filter, uint64_t limit, bool cycleTest, sage2ov_scaffold_stats& stats, std::vector<sage2ov_join>& out, uint64_t* merged) {
+    { const int rc = readmap_check(c, who); if (rc) return rc; }
     sage2ov_scaffold_counts R{};
     const bool swept = !(c->linkValid && c->estimated && c->rmValid);
-    { const int rc = links_ensure(c, "sage2ov_scaffold_round"); if (rc) return rc; }
+    { const int rc = links_ensure(c, who); if (rc) return rc; }
     { const int rc = links_fetch(c); if (rc) return rc; }                             // (pair_ordinals and the half-edge fields come with it; no read list)
     if (swept) R.sweep_ms = c->lstats.halves_ms + c->lstats.scan_ms + c->lstats.records_ms + c->lstats.sort_ms + c->lstats.reduce_ms;
-    SpliceRound S(c, "sage2ov_scaffold_round", 0);
+    SpliceRound S(c, who, 0);
     const std::vector<uint32_t>&ordBefore = S.ordBefore, &from = S.from, &to = S.to, &len = S.len; const std::vector<uint8_t>&type = S.type, &alive = S.alive; const std::vector<float>& flow = S.flow;
     std::vector<uint32_t> firstOf; g4_save_order(c->g4, firstOf);                      // ordinal -> the half that opens the record pair
     auto isE = [&](uint32_t h) -> bool { return from[h] < to[h] || (from[h] == to[h] && (h & 1u)); };      // the half the read-to-edge table names; a loop: the higher index
     // the rows by rule (a) in export order, FEASIBLE from the unfiltered table, SEARCH and the rows filed under their end nodes
     struct Row { uint32_t e1, e2, sup; int32_t gap; uint64_t lenSum; };
     std::vector<Row> rows; std::unordered_map<uint32_t, std::vector<uint32_t>> feasible;
-    const int thr = link_length_threshold(c);
-    const uint32_t mode = small ? SAGE2OV_LINKS_SMALL : SAGE2OV_LINKS_FINAL;
     for (uint64_t e = 0; e < c->links.size(); e++) {
         const sage2ov_link& L = c->links[e]; if (!L.support) continue;
         const uint32_t a = firstOf[L.pair_a] ^ L.second_a, b = firstOf[L.pair_b] ^ L.second_b;
         auto& fa = feasible[a >> 1]; if (std::find(fa.begin(), fa.end(), b >> 1) == fa.end()) fa.push_back(b >> 1);
         auto& fb = feasible[b >> 1]; if (std::find(fb.begin(), fb.end(), a >> 1) == fb.end()) fb.push_back(a >> 1);
-        if (a < b && link_passes(c, e, mode, thr)) rows.push_back(Row{a ^ 1u, b, L.support, L.gap, (uint64_t)len[a ^ 1u] + len[b]});
+        if (a < b && filter(e)) rows.push_back(Row{a ^ 1u, b, L.support, L.gap, (uint64_t)len[a ^ 1u] + len[b]});
     }
     auto xk = [&](uint32_t h) -> uint64_t { return S.xk(h); };
     auto k2 = [&](uint64_t x, uint64_t y) -> uint64_t { return SpliceRound::k2(x, y); };
@@ -2843,7 +2862,6 @@ int sage2ov_scaffold_round(sage2ov_ctx* c, int highTh, int flag, int small, uint
     auto present = [&](uint64_t x, uint64_t y) -> int64_t { const int64_t s = S.find(k2(x, y)); return s < 0 ? S.find(k2(y, x)) : s; };      // in either order; -1: in neither
     auto lookup = [&](uint64_t x, uint64_t y) -> int64_t { return std::max<int64_t>(present(x, y), 0); };
     std::unordered_set<uint32_t> spent; std::vector<sage2ov_join> joins;
-    const uint64_t limit = flag == 1 ? 1 : 2;
     static const std::vector<uint32_t> none;
     for (const Row& r : rows) {
         const uint32_t e1 = r.e1, e2 = r.e2;
@@ -2862,10 +2880,10 @@ int sage2ov_scaffold_round(sage2ov_ctx* c, int highTh, int flag, int small, uint
             const int64_t s = present(xk(2 * q), xk(e2));
             if (s >= 0 && s >= (int64_t)highTh) { count1++; if (std::find(side2.begin(), side2.end(), q) != side2.end()) cycle = true; }
         }
-        if (cycle) { R.cycles++; continue; }
+        if (cycle && cycleTest) { R.cycles++; continue; }
         if (count1 > limit || count2 > limit) { R.blocked++; continue; }
         { const int rc = S.make_room(e1, e2); if (rc) return rc; }                     // (e): only a kept operand can be named again, the rows are older than the round's edges
-        if (!join_length_fits(len[e1], len[e1 ^ 1u], len[e2], len[e2 ^ 1u], r.gap)) return c->fail(SAGE2OV_ERR_LIMIT, "sage2ov_scaffold_round: an edge length beyond 32 bits");
+        if (!join_length_fits(len[e1], len[e1 ^ 1u], len[e2], len[e2 ^ 1u], r.gap)) return c->fail(SAGE2OV_ERR_LIMIT, std::string(who) + ": an edge length beyond 32 bits");
         const uint32_t t1 = type[e1], t2 = type[e2], t = ((t1 == 2 || t1 == 3) ? 2u : 0u) | ((t2 == 1 || t2 == 3) ? 1u : 0u), node = to[e1];
         sage2ov_join m{}; m.from = from[e1]; m.to = to[e2]; m.support = r.sup; m.gap = r.gap; m.type = (uint8_t)t;
         m.pair_first = ordBefore[p1]; m.pair_second = ordBefore[p2]; m.pair_new = ~0u;
@@ -2882,10 +2900,18 @@ int sage2ov_scaffold_round(sage2ov_ctx* c, int highTh, int flag, int small, uint
         j.overlap_forward = S.ov[2 * i]; j.overlap_twin = S.ov[2 * i + 1]; j.how_forward = p.how[0]; j.how_twin = p.how[1];
     }
     R.merged = joins.size(); R.overlaps = S.sum.overlaps; R.concatenated = S.sum.concatenated; R.gapped = S.sum.gapped; R.overlap_ms = S.sum.overlap_ms;
-    c->scjoins = std::move(joins);
-    c->scstats.rounds++; c->scstats.last = R; sc_counts_add(c->scstats.total, R);
+    out = std::move(joins);
+    stats.rounds++; stats.last = R; sc_counts_add(stats.total, R);
     if (merged) *merged = R.merged;
     return SAGE2OV_OK;
+}
+}  // namespace
+int sage2ov_scaffold_round(sage2ov_ctx* c, int highTh, int flag, int small, uint64_t* merged) {                        // :774-967, :488-769
+    if (!c) return SAGE2OV_ERR_ARG;
+    if (flag != 1 && flag != 2) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_scaffold_round: flag is 1 or 2");
+    const int thr = link_length_threshold(c);
+    const uint32_t mode = small ? SAGE2OV_LINKS_SMALL : SAGE2OV_LINKS_FINAL;
+    return join_round(c, "sage2ov_scaffold_round", highTh, [&](uint64_t e) { return link_passes(c, e, mode, thr); }, flag == 1 ? 1 : 2, true, c->scstats, c->scjoins, merged);
 }
 int sage2ov_scaffold(sage2ov_ctx* c, uint64_t genomeSize, uint64_t* rounds, uint64_t* merged) {                       // :31-98
     if (!c) return SAGE2OV_ERR_ARG;
@@ -2913,6 +2939,52 @@ int sage2ov_scaffold_merges_export(const sage2ov_ctx* c, sage2ov_join* out, uint
     return SAGE2OV_OK;
 }
 int sage2ov_scaffold_stats_get(const sage2ov_ctx* c, sage2ov_scaffold_stats* o) { if (!c || !o) return SAGE2OV_ERR_ARG; *o = c->scstats; return SAGE2OV_OK; }
+
+// ---- the fourth loop of ContigExtender::extendContigs: mergeShortOverlaps (mergeContigs.cpp:101-110, :1474-1648, :1788-1908); the semantics are stated in sage2ov.h
+int sage2ov_extend_short_threshold(uint64_t reads, uint64_t arl, uint64_t genomeSize, int* high) {                     // :43, :102
+    if (!high || !arl || !genomeSize) return SAGE2OV_ERR_ARG;
+    const float coverage = (reads * arl) / genomeSize;
+    *high = (int)ceilf((0.05 * coverage) * (100.0 / arl));
+    return SAGE2OV_OK;
+}
+int sage2ov_extend_short_round(sage2ov_ctx* c, int highTh, uint64_t* merged) {                                         // :1474-1648, :1788-1908
+    if (!c) return SAGE2OV_ERR_ARG;
+    const int thr = link_length_threshold(c);                                          // (mergeContigs.cpp:21 is scaffolding.cpp:20)
+    return join_round(c, "sage2ov_extend_short_round", highTh, [&](uint64_t e) { return short_passes(c, e, thr); }, 0, false, c->sostats, c->sojoins, merged);
+}
+int sage2ov_extend_by_short_overlaps(sage2ov_ctx* c, uint64_t genomeSize, uint64_t* rounds, uint64_t* merged) {        // :101-110
+    if (!c) return SAGE2OV_ERR_ARG;
+    { const int rc = readmap_check(c, "sage2ov_extend_by_short_overlaps"); if (rc) return rc; }
+    { const int rc = header_hold(c); if (rc) return rc; }
+    const uint64_t gs = genomeSize ? genomeSize : c->hdrGenome, reads = c->hdrReads, arl = average_read_length(c);
+    if (!gs || !arl) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_extend_by_short_overlaps: a genome size or an average read length of 0");
+    int high = 0; sage2ov_extend_short_threshold(reads, arl, gs, &high);
+    uint64_t r = 0, total = 0;
+    for (uint32_t it = 1; it <= 10000; it++) {
+        uint64_t m = 0; { const int rc = sage2ov_extend_short_round(c, high, &m); if (rc) return rc; }
+        r++; total += m;
+        if (rounds) *rounds = r; if (merged) *merged = total;
+        if (!m) return SAGE2OV_OK;
+    }
+    return c->fail(SAGE2OV_ERR_INTERNAL, "sage2ov_extend_by_short_overlaps: 10 000 rounds without a fixed point");
+}
+int sage2ov_extend_contigs(sage2ov_ctx* c, uint64_t genomeSize, uint64_t rounds[4], uint64_t merged[4]) {              // :37-113
+    if (!c) return SAGE2OV_ERR_ARG;
+    uint64_t r[4] = {0, 0, 0, 0}, m[4] = {0, 0, 0, 0};
+    int rc = sage2ov_extend_by_supports(c, genomeSize, &r[0], &m[0]);
+    if (!rc) rc = sage2ov_extend_by_paths(c, genomeSize, 0, &r[1], &m[1]);
+    if (!rc) rc = sage2ov_extend_by_paths(c, genomeSize, 1, &r[2], &m[2]);
+    if (!rc) rc = sage2ov_extend_by_short_overlaps(c, genomeSize, &r[3], &m[3]);
+    for (int i = 0; i < 4; i++) { if (rounds) rounds[i] = r[i]; if (merged) merged[i] = m[i]; }
+    return rc;
+}
+int sage2ov_extend_short_merges_count(const sage2ov_ctx* c, uint64_t* n) { if (!c || !n) return SAGE2OV_ERR_ARG; *n = c->sojoins.size(); return SAGE2OV_OK; }
+int sage2ov_extend_short_merges_export(const sage2ov_ctx* c, sage2ov_join* out, uint64_t cap) {
+    if (!c || cap < c->sojoins.size() || (!out && !c->sojoins.empty())) return SAGE2OV_ERR_ARG;
+    if (!c->sojoins.empty()) memcpy(out, c->sojoins.data(), c->sojoins.size() * sizeof(sage2ov_join));
+    return SAGE2OV_OK;
+}
+int sage2ov_extend_short_stats_get(const sage2ov_ctx* c, sage2ov_scaffold_stats* o) { if (!c || !o) return SAGE2OV_ERR_ARG; *o = c->sostats; return SAGE2OV_OK; }
 
 // ---- OverlapGraph::printGraph / saveContigsToFile (overlapGraph.cpp:507-784); the semantics are stated in sage2ov.h
 namespace {

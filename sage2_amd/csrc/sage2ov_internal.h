@@ -216,7 +216,7 @@ struct LinkStats { uint64_t halves = 0, entries_within = 0, unique_entries = 0, 
                    double halves_ms = 0, scan_ms = 0, records_ms = 0, sort_ms = 0, reduce_ms = 0; };
 int dev_links_build(Device* d, const LinkParams& P, LinkStats* st, std::string& err);
 uint64_t dev_links_count(Device* d);
-int dev_links_export(Device* d, uint64_t* key, uint32_t* support, int32_t* gap, std::string& err);
+int dev_links_export(Device* d, uint64_t* key, uint32_t* support, int32_t* gap, int32_t* gapSum, std::string& err);
 void dev_links_release(Device* d);
 // the sweep of ContigExtender::findPathSupports / findPathSupportsNew on the device (sage2ov_path_supports; kernels_paths.inc): needs the read-to-edge
 // table, the mate tables, the insert bounds and the mate flags as of the estimate (dev_estflags_keep: a copy per library that outlives the read-to-edge table of the
