@@ -330,8 +330,8 @@ int sage2ov_graph_flow_export(sage2ov_ctx* ctx, float* flow, uint64_t cap);
 int sage2ov_graph_flow_import(sage2ov_ctx* ctx, const float* flow, uint64_t n);
 
 /* ---- step 5 around its solver (CopyCountEstimator, overlapGraph/copycountEstimator.cpp): the genome-size estimate (:29-100), the flow network as
- * input.cs2 (computeMinCostFlow, :105-355) and a solver's output.cs2 back onto the flows (:362-403), over the resident step-4 graph.  The solver itself (CS2, :359)
- * is not part of the library: the caller runs any min-cost-flow solver on the file or the arc records.  computeMinCostFlow_new (:422-) is never called by main.cpp.
+ * input.cs2 (computeMinCostFlow, :105-355) and a solver's output.cs2 back onto the flows (:362-403), over the resident step-4 graph.  The solver (CS2, :359) has its
+ * own section below (sage2ov_flow_solve); a caller may still run any min-cost-flow solver on the file or the arc records.  computeMinCostFlow_new (:422-) is never called by main.cpp.
  *
  * State restated: the reference's after `-m 5` loads the files this library writes -- loadOverlapGraphFromFile (overlapGraph.cpp:371-443) of what
  * sage2ov_graph4_save would write.  insertIntoList puts the newest edge first, so a node's edge list is the reverse of file order over the records that start at the
@@ -401,6 +401,51 @@ int sage2ov_flow_solution_apply(sage2ov_ctx* ctx, const uint64_t* from, const ui
 int sage2ov_flow_solution_load(sage2ov_ctx* ctx, const char* path);                     /* output.cs2: whitespace-separated triples; anything else: SAGE2OV_ERR_IO */
 int sage2ov_graph5_save(sage2ov_ctx* ctx, const char* path);
 int sage2ov_copycount_stats_get(const sage2ov_ctx* ctx, sage2ov_copycount_stats* out);
+
+/* ---- step 5's solver (main_cs2, copycountEstimator.cpp:359; cs2/cs2.cpp, cs2/parser_cs2.h): min-cost flow on the device, by Goldberg-Tarjan cost
+ * scaling with round-synchronous push-relabel.  The contract is OPTIMAL, NOT IDENTICAL: the total cost is the optimum any exact solver finds; the flows are the
+ * reference's only where the optimum is unique.  Integers only; solving the same network twice gives the same flows and prices, bit for bit.
+ *   the problem       a circulation: nodes 1..n without supplies (the `n` lines of input.cs2 say 0), arcs with lower <= flow <= upper, sum of flow * cost minimal.
+ *                     parser_cs2.h:257 reads a cost with %lld: the integer prefix of the printed text, truncation towards zero (`-691.348000` is -691, `-0.7` is 0).
+ *   scale             costs are multiplied by n + 1: a flow that is 1-optimal in scaled units is optimal.  Prices are in scaled units.
+ *   the certificate   lower <= flow <= upper; every node conserved; cost * scale + price[from] - price[to] >= -1 wherever flow < upper, <= 1 wherever flow > lower.
+ *   limits            SAGE2OV_ERR_LIMIT, nothing solved: (n + 1) * max |cost| or the lowest price the method can reach do not fit +-2^62 (checked before any launch
+ *                     and again before every price update) -- about 10.3 * (n + 1)^2 * max |cost| < 2^62: some 211 000 nodes with step 5's costs of 10^7; 2^31 - 2048 arcs or more; the round budget spent (max_rounds; 0: SAGE2OV_MCF_DEFAULT_ROUNDS) -- then
+ *                     the statistics are filled in, nothing is applied and the graph, the network and any earlier solution stay as they were.
+ *   SAGE2OV_ERR_ARG   from == to, a node number outside 1..n, lower > upper, a negative bound; an infeasible network ("infeasible" in sage2ov_last_error): excess
+ *                     that no residual path carries to a deficit, or a price below the bound of the method.
+ * SAGE2OV_ERR_DEVICE on a device-less context. */
+#define SAGE2OV_MCF_DEFAULT_ROUNDS (1ull << 22)
+#define SAGE2OV_MCF_PHASES 24               /* epsilon phases whose rounds and times the statistics keep (2^62 needs 21) */
+#define SAGE2OV_MCF_FORM_LDS 1              /* one workgroup, the network in LDS: at most 512 nodes and 1024 arcs */
+#define SAGE2OV_MCF_FORM_LAUNCHES 2         /* two launches per round, the rounds counted on the host */
+typedef struct sage2ov_mcf_arc { uint32_t from, to; int32_t lower, upper; int64_t cost; } sage2ov_mcf_arc;      /* cs2/parser_cs2.h:232-262: `a from to lower upper cost` */
+typedef struct sage2ov_mcf_stats {
+    uint64_t nodes, arcs, scale;                       /* scale = nodes + 1 */
+    uint64_t phases, rounds, pushes, relabels, price_updates;
+    int64_t  total_cost;                               /* sum of flow * cost, unscaled */
+    uint32_t form, reserved;                           /* SAGE2OV_MCF_FORM_* */
+    double   build_ms, solve_ms;                       /* HIP-event times: layout, rounds */
+    uint64_t refine_rounds[SAGE2OV_MCF_PHASES];        /* the launches form: per epsilon phase */
+    double   refine_ms[SAGE2OV_MCF_PHASES];
+} sage2ov_mcf_stats;
+/* any network; needs a device context and no reads.  flow_out: m words, the full flow (lower bound included, cs2.cpp:1872) in input order; price_out: n words or NULL */
+int sage2ov_mcf_solve(sage2ov_ctx* ctx, uint64_t n_nodes, const sage2ov_mcf_arc* arcs, uint64_t m, uint64_t max_rounds, int64_t* flow_out, int64_t* price_out, sage2ov_mcf_stats* stats);
+/* the resident network of sage2ov_flow_network_build (before it: SAGE2OV_ERR_ARG); an arc's cost is the truncation towards zero of the float in its record, a NaN or
+ * an infinity there SAGE2OV_ERR_ARG (the reference's parser would refuse the line).  The solution stays resident and goes with the network.  stats may be NULL */
+int sage2ov_flow_solve(sage2ov_ctx* ctx, uint64_t max_rounds, sage2ov_mcf_stats* stats);
+/* flow: one word per arc of sage2ov_flow_network_export, price: one per network node; a cap below the count with the array given: SAGE2OV_ERR_ARG, nothing written;
+ * a NULL array is skipped.  Without a solution: SAGE2OV_ERR_ARG */
+int sage2ov_flow_solution_export(sage2ov_ctx* ctx, int64_t* flow, uint64_t cap_flow, int64_t* price, uint64_t cap_price, uint64_t* scale);
+/* `from to flow` for the arcs with upper > 0 (cs2.cpp prints no other).  The ORDER IS OURS, not the reference's: by tail, then input order.  sage2ov_flow_solution_load
+ * of the file gives the flows sage2ov_flow_solution_commit gives */
+int sage2ov_flow_solution_save(sage2ov_ctx* ctx, const char* path);
+/* the resident flows onto the graph by the apply path of sage2ov_flow_solution_apply (:365-403), no file and no host copy of the lines; what that call says about
+ * adding onto the flows present and about the supports and contigs holds here */
+int sage2ov_flow_solution_commit(sage2ov_ctx* ctx);
+/* the whole of step 5 (main.cpp -m 5; computeMinCostFlow, :105-417): estimate, build, solve, commit */
+int sage2ov_copy_counts(sage2ov_ctx* ctx, uint64_t* genome_size);
+int sage2ov_mcf_stats_get(const sage2ov_ctx* ctx, sage2ov_mcf_stats* out);              /* of the last solve */
 
 /* ---- the sweep of ContigExtender::findMatepairSupports (matePair/mergeContigs.cpp:959-1030): getSupportOfEdges (:1032-1097) over isUniqueInEdge (:1102-1110) for every
  * incoming x outgoing pair of composite edges of every node, on the device; all quantities are integers.  The merge that follows it in the

@@ -161,11 +161,20 @@ class LinkStats(C.Structure):
 # sage2ov_flow_arc (20 bytes): one arc of the flow network, cost as input.cs2 prints it
 FLOW_ARC_DTYPE = np.dtype([("from", np.uint32), ("to", np.uint32), ("lower", np.int32), ("upper", np.int32), ("cost", np.float32)])
 GENOME_ROUNDS = 10
+MCF_ARC_DTYPE = np.dtype([("from", np.uint32), ("to", np.uint32), ("lower", np.int32), ("upper", np.int32), ("cost", np.int64)])      # sage2ov_mcf_arc
+MCF_PHASES = 24
+MCF_FORM_LDS, MCF_FORM_LAUNCHES = 1, 2
 
 
 class GenomeEstimate(C.Structure):
     _fields_ = [("genome_size", C.c_uint64), ("estimate", C.c_uint64 * GENOME_ROUNDS), ("delta_sum", C.c_uint64 * GENOME_ROUNDS), ("k_sum", C.c_uint64 * GENOME_ROUNDS),
                 ("rounds", C.c_uint32), ("degenerate", C.c_uint32), ("agreed", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class McfStats(C.Structure):
+    _fields_ = [("nodes", C.c_uint64), ("arcs", C.c_uint64), ("scale", C.c_uint64), ("phases", C.c_uint64), ("rounds", C.c_uint64), ("pushes", C.c_uint64),
+                ("relabels", C.c_uint64), ("price_updates", C.c_uint64), ("total_cost", C.c_int64), ("form", C.c_uint32), ("reserved", C.c_uint32),
+                ("build_ms", C.c_double), ("solve_ms", C.c_double), ("refine_rounds", C.c_uint64 * MCF_PHASES), ("refine_ms", C.c_double * MCF_PHASES)]
 
 
 class CopyCountStats(C.Structure):
@@ -538,6 +547,48 @@ class Context:
 
     def graph5_save(self, path):
         self._chk(lib().sage2ov_graph5_save(self._h, os.fsencode(path)))
+
+    # ---- step 5's solver (main_cs2): min-cost flow on the device
+    def mcf_solve(self, n, arcs, max_rounds=0):
+        """solves the circulation over nodes 1..n with the arcs (MCF_ARC_DTYPE); returns (flow per arc, price per node in scaled units, McfStats).  A failed
+        solve raises Sage2ovError; mcf_stats() still tells how far it got"""
+        a = np.ascontiguousarray(arcs, dtype=MCF_ARC_DTYPE)
+        flow = np.zeros(len(a), dtype=np.int64); price = np.zeros(int(n), dtype=np.int64); st = McfStats()
+        self._chk(lib().sage2ov_mcf_solve(self._h, C.c_uint64(int(n)), C.c_void_p(a.ctypes.data), C.c_uint64(len(a)), C.c_uint64(int(max_rounds)),
+                                          C.c_void_p(flow.ctypes.data), C.c_void_p(price.ctypes.data), C.byref(st)))
+        return flow, price, st
+
+    def flow_solve(self, max_rounds=0) -> McfStats:
+        """solves the resident flow network; the solution stays on the device"""
+        st = McfStats()
+        self._chk(lib().sage2ov_flow_solve(self._h, C.c_uint64(int(max_rounds)), C.byref(st)))
+        return st
+
+    def flow_solution(self):
+        """(flow per arc of flow_network(), price per network node in scaled units, scale) of the resident solution"""
+        nodes, arcs, scale = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._chk(lib().sage2ov_flow_network_count(self._h, C.byref(nodes), C.byref(arcs)))
+        flow = np.zeros(arcs.value, dtype=np.int64); price = np.zeros(nodes.value, dtype=np.int64)
+        self._chk(lib().sage2ov_flow_solution_export(self._h, C.c_void_p(flow.ctypes.data), C.c_uint64(arcs.value), C.c_void_p(price.ctypes.data), C.c_uint64(nodes.value), C.byref(scale)))
+        return flow, price, int(scale.value)
+
+    def flow_solution_save(self, path):
+        self._chk(lib().sage2ov_flow_solution_save(self._h, os.fsencode(path)))
+
+    def flow_commit(self):
+        """the resident solution onto the flows of the graph, as flow_load of its file would"""
+        self._chk(lib().sage2ov_flow_solution_commit(self._h))
+
+    def copy_counts(self) -> int:
+        """the whole of step 5: estimate, network, solve, commit; returns the genome size"""
+        n = C.c_uint64(0)
+        self._chk(lib().sage2ov_copy_counts(self._h, C.byref(n)))
+        return int(n.value)
+
+    def mcf_stats(self) -> McfStats:
+        s = McfStats()
+        self._chk(lib().sage2ov_mcf_stats_get(self._h, C.byref(s)))
+        return s
 
     def copycount_stats(self) -> CopyCountStats:
         s = CopyCountStats()

@@ -1,0 +1,368 @@
+// sage2_amd/csrc/kernels_flow.inc -- step 5's solver (main_cs2, copycountEstimator.cpp:359; cs2/): min-cost flow by Goldberg-Tarjan cost scaling with
+// round-synchronous push-relabel (DESIGN.md 5.20; tests/flow_model.py is the same method in numpy).  Part of sage2ov_device.hip (included inside namespace s2).
+//
+// Integers only: 64-bit prices, excesses and scaled costs, 32-bit residual capacities.  Nodes are 1..n; arrays per node have n + 2 words.
+// Entry 2 i is arc i forwards (residual upper - lower, cost * scale), entry 2 i + 1 backwards (residual 0, -cost * scale); the entries are sorted stably by
+// tail (the project's radix sort), so a node's list is start[v] .. start[v + 1] in ascending entry number; sis[s] is the position of the entry's sister.
+//   k_mf_from_cc     the resident network's records: the float cost truncated towards zero, as `%lld` reads the printed text (parser_cs2.h:257)
+//   k_mf_check       bad arcs and max |cost| into the counter block
+//   k_mf_keys        the sort keys (the tails) and the excess of the lower bounds
+//   k_mf_pos, k_mf_entries, k_mf_starts   the sorted layout
+//   k_mf_saturate    start of a refine: every entry with residual > 0 and negative reduced cost is saturated
+//   k_mf_push        every node with excess > 0 walks its list in order and pushes min(residual, what is left of the excess it had when the phase began) along
+//                    every admissible entry.  What a node receives goes to delta[], not to excess[]: no decision depends on another node's pushes of the same phase.
+//                    Lists of up to MF_LANE_DEG entries: a lane per node.  Longer lists: the workgroup walks the list MF_BLOCK entries at a time, an exclusive
+//                    scan of the admissible residuals clipped to the excess -- the same amounts as the serial walk.
+//   k_mf_relabel     excess += delta.  A node with excess > 0 and no admissible entry: p = max over residual entries of p(head) - cost - eps, read from the prices
+//                    of the phase's start and written to the other price buffer (every node writes its price there).  Below the floor: the infeasible flag.
+//   k_mf_pu_init, k_mf_pu_relax, k_mf_pu_apply   the price update: distances to the nodes with excess < 0, one thread per entry and an integer atomic min
+//                    per improvement, launched until a launch changes nothing; the distances are unique, so the order of the improvements does not matter.
+//   k_mf_lds         the whole solve by one workgroup between __syncthreads(), for networks of at most MF_LDS_NODES nodes and MF_LDS_ENTRIES entries; the same
+//                    rounds and price updates; the round budget is its loop bound.
+//   k_mf_flows, k_mf_triples   flow per arc (lower + residual of the backward entry); the `from to flow` lines for k_cc_apply
+// No kernel waits for another workgroup; every loop is bounded by a list length, an argument or the round budget.
+// =============================================================================================
+
+struct McfArc { u32 from, to; int lower, upper; long long cost; };                    // = sage2ov_mcf_arc
+constexpr u32 MF_BLOCK = 256, MF_LANE_DEG = 64;
+constexpr u32 MF_LDS_NODES = 512, MF_LDS_ENTRIES = 2048;
+constexpr int MF_ALPHA = 8;
+constexpr u32 MF_PERIOD = 64;                                                          // rounds of a refine between two price updates; the first precedes its first round
+constexpr u32 MF_BATCH = 32;                                                           // rounds between two reads of the counter block
+// the counter block
+constexpr u32 MF_ACT = 0, MF_PUSHES = MF_BATCH, MF_RELABELS = MF_BATCH + 1, MF_FLAGS = MF_BATCH + 2, MF_MAXC = MF_BATCH + 3, MF_ROUNDS = MF_BATCH + 4, MF_PHASES = MF_BATCH + 5,
+              MF_TTS = MF_BATCH + 6, MF_UPDATES = MF_BATCH + 7, MF_CTRS = MF_BATCH + 8;
+constexpr unsigned long long MF_F_BADARC = 1, MF_F_NAN = 2, MF_F_INFEASIBLE = 4, MF_F_RANGE = 8, MF_F_LIMIT = 16;
+constexpr long long MF_INF = 1ll << 62;
+
+struct MfNet {                   // the sorted layout and the state of a solve
+    const u32 *head, *sis, *tail, *start; const long long* cost; int* rcap;
+    long long *excess, *delta; u32 n, M;
+};
+
+__global__ void k_mf_from_cc(const CcArc* __restrict__ in, u64 m, McfArc* out, unsigned long long* ctr) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; if (i >= m) return;
+    const CcArc a = in[i]; long long c = 0;
+    if (!(fabsf(a.cost) < 4.0e18f)) atomicOr(&ctr[MF_FLAGS], a.cost != a.cost || fabsf(a.cost) > 3.0e38f ? MF_F_NAN : MF_F_RANGE);
+    else c = (long long)a.cost;                                                        // truncation towards zero
+    out[i] = McfArc{a.from, a.to, a.lower, a.upper, c};
+}
+__global__ void k_mf_check(const McfArc* __restrict__ a, u64 m, u32 n, unsigned long long* ctr) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long mx = 0; bool bad = false;
+    if (i < m) {
+        const McfArc x = a[i];
+        bad = x.from < 1 || x.from > n || x.to < 1 || x.to > n || x.from == x.to || x.lower < 0 || x.lower > x.upper;
+        mx = x.cost < 0 ? 0ull - (unsigned long long)x.cost : (unsigned long long)x.cost;
+    }
+    for (int d = 32; d >= 1; d >>= 1) { const unsigned long long t = __shfl_down(mx, d); mx = t > mx ? t : mx; }
+    const u64 anyBad = __ballot(bad);
+    if (lane_id() == 0) { if (mx) atomicMax(&ctr[MF_MAXC], mx); if (anyBad) atomicOr(&ctr[MF_FLAGS], MF_F_BADARC); }
+}
+// (after k_mf_check has passed: every node number is inside 1..n)
+__global__ void k_mf_keys(const McfArc* __restrict__ a, u64 m, u64* key, long long* excess) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; if (i >= m) return;
+    const McfArc x = a[i];
+    key[2 * i] = x.from; key[2 * i + 1] = x.to;
+    if (x.lower) { atomicAdd((unsigned long long*)&excess[x.from], 0ull - (unsigned long long)x.lower); atomicAdd((unsigned long long*)&excess[x.to], (unsigned long long)x.lower); }
+}
+__global__ void k_mf_pos(const u32* __restrict__ idx, u32 M, u32* pos) { const u32 s = blockIdx.x * blockDim.x + threadIdx.x; if (s < M) pos[idx[s]] = s; }
+__global__ void k_mf_entries(const McfArc* __restrict__ a, const u32* __restrict__ idx, const u32* __restrict__ pos, const u64* __restrict__ ks, u32 M, long long scale,
+                             u32* head, u32* sis, u32* tail, long long* cost, int* rcap) {
+    const u32 s = blockIdx.x * blockDim.x + threadIdx.x; if (s >= M) return;
+    const u32 e = idx[s]; const McfArc x = a[e >> 1]; const bool back = e & 1u;
+    head[s] = back ? x.from : x.to; tail[s] = (u32)ks[s]; sis[s] = pos[e ^ 1u];
+    cost[s] = (back ? -x.cost : x.cost) * scale; rcap[s] = back ? 0 : x.upper - x.lower;
+}
+// start[v], v = 0 .. n + 1: the first sorted entry whose tail is v or more
+__global__ void k_mf_starts(const u64* __restrict__ ks, u32 M, u32 n, u32* start) {
+    const u64 v = (u64)blockIdx.x * blockDim.x + threadIdx.x; if (v > (u64)n + 1) return;
+    u32 lo = 0, hi = M;
+    while (lo < hi) { const u32 mid = lo + ((hi - lo) >> 1); if (ks[mid] < v) lo = mid + 1; else hi = mid; }
+    start[v] = lo;
+}
+
+__device__ __forceinline__ void mf_add(long long* p, long long x) { atomicAdd((unsigned long long*)p, (unsigned long long)x); }
+
+__global__ void k_mf_saturate(MfNet N, const long long* __restrict__ p) {
+    const u32 s = blockIdx.x * blockDim.x + threadIdx.x; if (s >= N.M) return;
+    const int r = N.rcap[s]; if (r <= 0) return;
+    const u32 v = N.tail[s], w = N.head[s];
+    if (N.cost[s] + p[v] - p[w] >= 0) return;
+    N.rcap[s] = 0; N.rcap[N.sis[s]] += r;                                              // (the sister's reduced cost is positive: its own thread leaves it alone)
+    mf_add(&N.excess[v], -(long long)r); mf_add(&N.excess[w], (long long)r);
+}
+
+// exclusive scan of x over the MF_BLOCK threads of the workgroup; *total: the sum.  wsum: MF_BLOCK / 64 words of LDS
+__device__ __forceinline__ long long mf_block_scan(long long x, long long* wsum, long long* total) {
+    const u32 lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    long long inc = x;
+    for (int d = 1; d < 64; d <<= 1) { const long long t = __shfl_up(inc, d); if (lane >= (u32)d) inc += t; }
+    if (lane == 63u) wsum[w] = inc;
+    __syncthreads();
+    long long base = 0, tot = 0;
+    for (u32 i = 0; i < MF_BLOCK / 64; i++) { const long long s = wsum[i]; if (i < w) base += s; tot += s; }
+    __syncthreads();
+    *total = tot; return base + inc - x;
+}
+
+__global__ void __launch_bounds__(MF_BLOCK) k_mf_push(MfNet N, const long long* __restrict__ p, unsigned long long* ctr) {
+    __shared__ u32 hv[MF_BLOCK]; __shared__ u32 nhv, sPush; __shared__ long long wsum[MF_BLOCK / 64];
+    const u32 tid = threadIdx.x; const u64 v64 = (u64)blockIdx.x * MF_BLOCK + tid + 1;
+    if (tid == 0) { nhv = 0; sPush = 0; }
+    __syncthreads();
+    u32 np = 0;
+    if (v64 <= N.n) {
+        const u32 v = (u32)v64; long long e = N.excess[v];
+        if (e > 0) {
+            const u32 s0 = N.start[v], s1 = N.start[v + 1];
+            if (s1 - s0 > MF_LANE_DEG) hv[atomicAdd(&nhv, 1u)] = v;
+            else {
+                const long long pv = p[v];
+                for (u32 s = s0; s < s1 && e > 0; s++) {
+                    const int r = N.rcap[s]; if (r <= 0) continue;
+                    const u32 w = N.head[s];
+                    if (N.cost[s] + pv - p[w] >= 0) continue;
+                    const long long d = (long long)r < e ? (long long)r : e;
+                    N.rcap[s] = r - (int)d; N.rcap[N.sis[s]] += (int)d;                // (only this node writes either: the sister is not admissible)
+                    mf_add(&N.delta[w], d); e -= d; np++;
+                }
+                N.excess[v] = e;
+            }
+        }
+    }
+    __syncthreads();
+    const u32 cnt = nhv;
+    for (u32 k = 0; k < cnt; k++) {                                                    // the long lists of this workgroup's nodes, one after the other
+        const u32 v = hv[k]; const long long e = N.excess[v], pv = p[v]; const u32 s0 = N.start[v], s1 = N.start[v + 1];
+        long long carry = 0;
+        for (u32 b = s0; b < s1 && carry < e; b += MF_BLOCK) {
+            const u32 s = b + tid; long long amt = 0; u32 w = 0; int r = 0;
+            if (s < s1) { r = N.rcap[s]; if (r > 0) { w = N.head[s]; if (N.cost[s] + pv - p[w] < 0) amt = r; } }
+            long long tot; const long long ex = mf_block_scan(amt, wsum, &tot);
+            const long long room = e - (carry + ex); long long d = amt < room ? amt : room; if (d < 0) d = 0;
+            if (d > 0) { N.rcap[s] = r - (int)d; N.rcap[N.sis[s]] += (int)d; mf_add(&N.delta[w], d); np++; }
+            carry += tot;
+        }
+        __syncthreads();
+        if (tid == 0) N.excess[v] = e - (carry < e ? carry : e);
+    }
+    if (np) atomicAdd(&sPush, np);
+    __syncthreads();
+    if (tid == 0 && sPush) atomicAdd(&ctr[MF_PUSHES], (unsigned long long)sPush);
+}
+
+// act: the word that counts the nodes with excess > 0 of this round
+__global__ void __launch_bounds__(MF_BLOCK) k_mf_relabel(MfNet N, const long long* __restrict__ p, long long* pn, long long eps, long long floor, unsigned long long* act, unsigned long long* ctr) {
+    __shared__ u32 hv[MF_BLOCK]; __shared__ u32 nhv, sAct, sRel, sBad; __shared__ long long wbest[MF_BLOCK / 64]; __shared__ u32 wadm[MF_BLOCK / 64];
+    const u32 tid = threadIdx.x; const u64 v64 = (u64)blockIdx.x * MF_BLOCK + tid + 1;
+    if (tid == 0) { nhv = 0; sAct = 0; sRel = 0; sBad = 0; }
+    __syncthreads();
+    if (v64 <= N.n) {
+        const u32 v = (u32)v64; const long long dl = N.delta[v]; long long e = N.excess[v];
+        if (dl) { e += dl; N.excess[v] = e; N.delta[v] = 0; }
+        long long pv = p[v];
+        if (e > 0) {
+            atomicAdd(&sAct, 1u);
+            const u32 s0 = N.start[v], s1 = N.start[v + 1];
+            if (s1 - s0 > MF_LANE_DEG) hv[atomicAdd(&nhv, 1u)] = v;
+            else {
+                bool adm = false; long long best = -MF_INF;
+                for (u32 s = s0; s < s1; s++) {
+                    if (N.rcap[s] <= 0) continue;
+                    const long long pw = p[N.head[s]], c = N.cost[s];
+                    if (c + pv - pw < 0) { adm = true; break; }
+                    const long long x = pw - c - eps; best = x > best ? x : best;
+                }
+                if (!adm) { if (best < floor) atomicOr(&sBad, 1u); else { pv = best; atomicAdd(&sRel, 1u); } }
+            }
+        }
+        pn[v] = pv;                                                                    // (a long list's node: overwritten below when it is relabelled)
+    }
+    __syncthreads();
+    const u32 cnt = nhv;
+    for (u32 k = 0; k < cnt; k++) {
+        const u32 v = hv[k]; const long long pv = p[v]; const u32 s0 = N.start[v], s1 = N.start[v + 1];
+        bool adm = false; long long best = -MF_INF;
+        for (u32 s = s0 + tid; s < s1; s += MF_BLOCK) {
+            if (N.rcap[s] <= 0) continue;
+            const long long pw = p[N.head[s]], c = N.cost[s];
+            if (c + pv - pw < 0) { adm = true; break; }
+            const long long x = pw - c - eps; best = x > best ? x : best;
+        }
+        for (int d = 32; d >= 1; d >>= 1) { const long long t = __shfl_down(best, d); best = t > best ? t : best; }
+        const u64 anyAdm = __ballot(adm);
+        if ((tid & 63u) == 0) { wbest[tid >> 6] = best; wadm[tid >> 6] = anyAdm ? 1u : 0u; }
+        __syncthreads();
+        if (tid == 0) {
+            bool a = false; long long b = -MF_INF;
+            for (u32 i = 0; i < MF_BLOCK / 64; i++) { a = a || wadm[i]; b = wbest[i] > b ? wbest[i] : b; }
+            if (!a) { if (b < floor) sBad = 1u; else { pn[v] = b; sRel += 1u; } }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        if (sAct) atomicAdd(act, (unsigned long long)sAct);
+        if (sRel) atomicAdd(&ctr[MF_RELABELS], (unsigned long long)sRel);
+        if (sBad) atomicOr(&ctr[MF_FLAGS], MF_F_INFEASIBLE);
+    }
+}
+
+// ---- the price update
+__global__ void k_mf_pu_init(const long long* __restrict__ excess, u32 n, long long* dist) {
+    const u64 v = (u64)blockIdx.x * blockDim.x + threadIdx.x; if (v > (u64)n + 1) return;
+    dist[v] = (v >= 1 && v <= n && excess[v] < 0) ? 0 : MF_INF;
+}
+// one pass over the entries; changed: the improvements of this launch
+__global__ void k_mf_pu_relax(MfNet N, const long long* __restrict__ p, long long eps, long long cap, long long* dist, unsigned long long* changed) {
+    const u32 s = blockIdx.x * blockDim.x + threadIdx.x;
+    bool ch = false;
+    if (s < N.M && N.rcap[s] > 0) {
+        const u32 v = N.tail[s], w = N.head[s];
+        const long long dw = dist[w];
+        if (dw < cap) {
+            const long long cp = N.cost[s] + p[v] - p[w];
+            long long len = 0; if (cp >= 0) { len = cp / eps + 1; if (len > cap) len = cap; }
+            const long long c = dw + len;
+            if (c < dist[v]) { atomicMin((unsigned long long*)&dist[v], (unsigned long long)c); ch = true; }      // (distances are never negative)
+        }
+    }
+    const u64 m = __ballot(ch);
+    if (lane_id() == 0 && m) atomicAdd(changed, (unsigned long long)__popcll(m));
+}
+__global__ void k_mf_pu_apply(const long long* __restrict__ excess, const long long* __restrict__ dist, u32 n, long long eps, long long cap, long long* p, unsigned long long* ctr) {
+    const u64 v = (u64)blockIdx.x * blockDim.x + threadIdx.x; if (v < 1 || v > n) return;
+    long long d = dist[v];
+    if (d >= MF_INF && excess[v] > 0) atomicOr(&ctr[MF_FLAGS], MF_F_INFEASIBLE);       // excess that reaches no deficit
+    if (d > cap) d = cap;
+    p[v] -= eps * d;
+}
+
+// ---- the single-workgroup form
+struct MfLdsArgs { long long cmax, scale; unsigned long long maxRounds; u32 period; };
+__global__ void __launch_bounds__(MF_BLOCK) k_mf_lds(MfNet N, long long* pOut, MfLdsArgs A, unsigned long long* ctr) {
+    __shared__ long long cost[MF_LDS_ENTRIES]; __shared__ int rcap[MF_LDS_ENTRIES]; __shared__ unsigned short head[MF_LDS_ENTRIES], sis[MF_LDS_ENTRIES], tail[MF_LDS_ENTRIES];
+    __shared__ long long price[2][MF_LDS_NODES + 2], excess[MF_LDS_NODES + 2], delta[MF_LDS_NODES + 2]; __shared__ u32 start[MF_LDS_NODES + 3];
+    __shared__ long long dist[MF_LDS_NODES + 2];
+    __shared__ u32 sAct, sBad, sChg; __shared__ unsigned long long sPush, sRel;
+    const u32 tid = threadIdx.x, n = N.n, M = N.M;
+    if (n > MF_LDS_NODES || M > MF_LDS_ENTRIES) return;                                 // (the host does not launch it then)
+    for (u32 s = tid; s < M; s += MF_BLOCK) { cost[s] = N.cost[s]; rcap[s] = N.rcap[s]; head[s] = (unsigned short)N.head[s]; sis[s] = (unsigned short)N.sis[s]; tail[s] = (unsigned short)N.tail[s]; }
+    for (u32 v = tid; v <= n + 1; v += MF_BLOCK) { price[0][v] = 0; price[1][v] = 0; excess[v] = N.excess[v]; delta[v] = 0; start[v] = N.start[v]; }
+    if (tid == 0) { sAct = 0; sBad = 0; sChg = 0; sPush = 0; sRel = 0; }
+    __syncthreads();
+    const long long cap = (long long)(1 + MF_ALPHA) * A.scale;
+    unsigned long long rounds = 0, phases = 0, flags = 0, updates = 0; u32 cur = 0; long long floor = 0;
+    for (long long eps = A.cmax;;) {
+        phases++; floor -= (long long)(1 + MF_ALPHA) * A.scale * eps;
+        {
+            const long long* p = price[cur];
+            for (u32 s = tid; s < M; s += MF_BLOCK) {
+                const int r = rcap[s]; if (r <= 0) continue;
+                const u32 v = tail[s], w = head[s];
+                if (cost[s] + p[v] - p[w] >= 0) continue;
+                rcap[s] = 0; rcap[sis[s]] += r; mf_add(&excess[v], -(long long)r); mf_add(&excess[w], (long long)r);
+            }
+        }
+        __syncthreads();
+        u32 since = A.period;
+        for (;;) {
+            if (rounds == A.maxRounds) { flags |= MF_F_LIMIT; break; }
+            if (A.period && since >= A.period) {                                       // the price update (k_mf_pu_*)
+                since = 0; floor -= cap * eps;
+                if (floor < -(MF_INF - 2 * A.cmax - 1)) { flags |= MF_F_RANGE; break; }
+                long long* pc = price[cur];
+                for (u32 v = tid; v <= n + 1; v += MF_BLOCK) dist[v] = (v >= 1 && v <= n && excess[v] < 0) ? 0 : MF_INF;
+                __syncthreads();
+                for (u32 it = 0; it <= n + 1; it++) {                                  // (a shortest path has at most n - 1 entries)
+                    bool ch = false;
+                    for (u32 s = tid; s < M; s += MF_BLOCK) {
+                        if (rcap[s] <= 0) continue;
+                        const u32 v = tail[s], w = head[s]; const long long dw = dist[w]; if (dw >= cap) continue;
+                        const long long cp = cost[s] + pc[v] - pc[w];
+                        long long len = 0; if (cp >= 0) { len = cp / eps + 1; if (len > cap) len = cap; }
+                        const long long c = dw + len;
+                        if (c < dist[v]) { atomicMin((unsigned long long*)&dist[v], (unsigned long long)c); ch = true; }
+                    }
+                    if (ch) atomicOr(&sChg, 1u);
+                    __syncthreads();
+                    const u32 c = sChg;
+                    __syncthreads();
+                    if (tid == 0) sChg = 0;
+                    if (!c) break;
+                }
+                for (u32 v = 1 + tid; v <= n; v += MF_BLOCK) {
+                    long long d = dist[v];
+                    if (d >= MF_INF && excess[v] > 0) atomicOr(&sBad, 1u);
+                    if (d > cap) d = cap;
+                    pc[v] -= eps * d;
+                }
+                updates++;
+                __syncthreads();
+                if (sBad) { flags |= MF_F_INFEASIBLE; break; }
+            }
+            since++;
+            rounds++;
+            const long long* p = price[cur]; long long* pn = price[cur ^ 1u];
+            u32 np = 0, nr = 0;
+            for (u32 v = 1 + tid; v <= n; v += MF_BLOCK) {                             // push
+                long long e = excess[v]; if (e <= 0) continue;
+                const long long pv = p[v];
+                for (u32 s = start[v], s1 = start[v + 1]; s < s1 && e > 0; s++) {
+                    const int r = rcap[s]; if (r <= 0) continue;
+                    const u32 w = head[s];
+                    if (cost[s] + pv - p[w] >= 0) continue;
+                    const long long d = (long long)r < e ? (long long)r : e;
+                    rcap[s] = r - (int)d; rcap[sis[s]] += (int)d; mf_add(&delta[w], d); e -= d; np++;
+                }
+                excess[v] = e;
+            }
+            __syncthreads();
+            for (u32 v = 1 + tid; v <= n; v += MF_BLOCK) {                             // relabel
+                const long long e = excess[v] + delta[v]; excess[v] = e; delta[v] = 0;
+                long long pv = p[v];
+                if (e > 0) {
+                    atomicAdd(&sAct, 1u);
+                    bool adm = false; long long best = -MF_INF;
+                    for (u32 s = start[v], s1 = start[v + 1]; s < s1; s++) {
+                        if (rcap[s] <= 0) continue;
+                        const long long pw = p[head[s]], c = cost[s];
+                        if (c + pv - pw < 0) { adm = true; break; }
+                        const long long x = pw - c - eps; best = x > best ? x : best;
+                    }
+                    if (!adm) { if (best < floor) atomicOr(&sBad, 1u); else { pv = best; nr++; } }
+                }
+                pn[v] = pv;
+            }
+            if (np) atomicAdd(&sPush, (unsigned long long)np);
+            if (nr) atomicAdd(&sRel, (unsigned long long)nr);
+            __syncthreads();
+            const u32 act = sAct, bad = sBad;
+            __syncthreads();
+            if (tid == 0) sAct = 0;
+            cur ^= 1u;
+            if (bad) { flags |= MF_F_INFEASIBLE; break; }
+            if (!act) break;
+        }
+        if (flags || eps == 1) break;
+        eps = eps / MF_ALPHA; if (eps < 1) eps = 1;
+    }
+    __syncthreads();
+    for (u32 s = tid; s < M; s += MF_BLOCK) N.rcap[s] = rcap[s];
+    for (u32 v = tid; v <= n + 1; v += MF_BLOCK) pOut[v] = price[cur][v];
+    if (tid == 0) { ctr[MF_ROUNDS] = rounds; ctr[MF_PHASES] = phases; ctr[MF_PUSHES] = sPush; ctr[MF_RELABELS] = sRel; ctr[MF_UPDATES] = updates; if (flags) atomicOr(&ctr[MF_FLAGS], flags); }
+}
+
+// flow[i] = lower + what the backward entry holds
+__global__ void k_mf_flows(const McfArc* __restrict__ a, const u32* __restrict__ pos, const int* __restrict__ rcap, u64 m, long long* flow) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; if (i >= m) return;
+    flow[i] = (long long)a[i].lower + (long long)rcap[pos[2 * i + 1]];
+}
+// the lines of output.cs2 for k_cc_apply: arcs with upper > 0 (cs2.cpp prints no other); an arc without a line becomes `1 1 0`, which the apply path skips as
+// it skips every line on node 1.  ctr[MF_TTS]: the flow of the `2 1` arc
+__global__ void k_mf_triples(const McfArc* __restrict__ a, const long long* __restrict__ flow, u64 m, u64* fr, u64* to, u64* fl, unsigned long long* ctr) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; if (i >= m) return;
+    const McfArc x = a[i]; const bool line = x.upper > 0;
+    fr[i] = line ? x.from : 1; to[i] = line ? x.to : 1; fl[i] = line ? (u64)flow[i] : 0;
+    if (line && ((x.from == 2 && x.to == 1) || (x.from == 1 && x.to == 2))) ctr[MF_TTS] = (unsigned long long)flow[i];
+}

@@ -254,8 +254,23 @@ public:
         ctx_->check(sage2ov_contigs_sequences(ctx_->get(), first, count, &out[0], need, offsets.data())); return out;
     }
     EconomyGraph* economyObj;
+    Context& context() const { return *ctx_; }
 private:
     Context* ctx_;
+};
+
+// CopyCountEstimator (copycountEstimator.h): step 5 over the graph the context holds
+class CopyCountEstimator {
+public:
+    explicit CopyCountEstimator(OverlapGraph* graph1) : graphObj(graph1) {}
+    // genomeSizeEstimation (copycountEstimator.cpp:29-54)
+    uint64_t genomeSizeEstimation() { uint64_t g = 0; ctx().check(sage2ov_genome_size_estimate(ctx().get(), &g)); return g; }
+    // computeMinCostFlow (:105-417): the network, the solve (main_cs2, :359 -- here on the device) and the flows onto the graph; returns the genome size
+    uint64_t computeMinCostFlow() { uint64_t g = 0; ctx().check(sage2ov_copy_counts(ctx().get(), &g)); return g; }
+    sage2ov_mcf_stats solverStats() const { sage2ov_mcf_stats s{}; ctx().check(sage2ov_mcf_stats_get(ctx().get(), &s)); return s; }
+    OverlapGraph* graphObj;
+private:
+    Context& ctx() const { return graphObj->context(); }
 };
 
 }  // namespace sage2ov

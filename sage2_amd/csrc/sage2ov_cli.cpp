@@ -2,7 +2,8 @@
 // Mimics the SAGE2 command line for steps 1-3 (main.cpp:384-521): -f | -l, -k, -o, -p, -i, -m, -M, -s, -d, -h.
 // Continue with the unchanged reference:  SAGE2 -f reads.fa -k K -o out -p P -i P -m 4      (main.cpp:141-148)
 // --flowNetwork writes <outdir>/input.cs2 (step 5's flow network, with the genome-size estimate) and --flowSolution FILE applies a solver's output.cs2 and writes
-// <prefix>.graph5: after step 4, or with -m 5 from <inputPrefix>.reads and <inputPrefix>.graph4.  No solver is started here.
+// <prefix>.graph5: after step 4, or with -m 5 from <inputPrefix>.reads and <inputPrefix>.graph4.  No outside solver is started here; --flowSolve is the whole of step 5 with
+// the library's own solver on the device (with -s it leaves input.cs2 and its output.cs2 too).
 // --contigs [--genomeSize G] also writes <prefix>_contig.fasta, printGraph's file (main.cpp:246), for the graph after step 4 or a P.graph4 / 5 / 6 (-m 5 | 6 | 7).
 #include <getopt.h>
 #include <sys/stat.h>
@@ -36,6 +37,7 @@ static void printListOfArgs() {
             "\t--genomeSize <int>\tgenome size for the N50 / N90 of --contigs [0; with --flowNetwork or --flowSolution: the estimate]\n"
             "\t--flowNetwork\t\tstep 5 up to its solver: estimate the genome size and write <outputDir>input.cs2 (after step 4, or with -m 5 from <inputPrefix>.graph4)\n"
             "\t--flowSolution <string>\tstep 5 after its solver: apply this output.cs2 to the flows and write <prefix>.graph5\n"
+            "\t--flowSolve\t\tthe whole of step 5 with the solver on the device: write <prefix>.graph5 (with -s also <outputDir>input.cs2 and output.cs2)\n"
             "\t--extend\t\twith -m 6: load <inputPrefix>.graph5, map the mate pairs of -f|-l, estimate the insert sizes, merge contigs by mate-pair\n"
             "\t\t\tsupport until a round merges nothing (the first loop of extendContigs; --paths and --shortOverlaps add the others) and write <prefix>.graph6 [--genomeSize: the estimate on the loaded graph]\n"
             "\t--paths\t\t\twith -m 6 --extend: after the first loop, the loops of findPathSupports and findPathSupportsNew (merges by path support)\n"
@@ -49,7 +51,7 @@ static double now() { return chrono::duration<double>(chrono::steady_clock::now(
 
 int main(int argc, char* argv[]) {
     const double tMain = now(); const bool timing = getenv("SAGE2OV_TIMING") != nullptr;
-    int minStep = 1, maxStep = 3, gpu = 0, gpus = 1, failRank = -1; bool shareGpu = false, forceMulti = false; unsigned minOverlap = 0; bool contigs = false, extend = false, paths = false, shortOverlaps = false, scaffold = false, flowNetwork = false, genomeSizeGiven = false, maxGiven = false; string flowSolution; unsigned long long genomeSize = 0; bool saveAll = false, debugging = false, fFlag = false, lFlag = false;
+    int minStep = 1, maxStep = 3, gpu = 0, gpus = 1, failRank = -1; bool shareGpu = false, forceMulti = false; unsigned minOverlap = 0; bool contigs = false, extend = false, paths = false, shortOverlaps = false, scaffold = false, flowNetwork = false, flowSolve = false, genomeSizeGiven = false, maxGiven = false; string flowSolution; unsigned long long genomeSize = 0; bool saveAll = false, debugging = false, fFlag = false, lFlag = false;
     string fileInput, listInput, outputDir, prefixName = "untitled", inputPrefix;
     static struct option opts[] = {{"help", no_argument, 0, 'h'}, {"fileInput", required_argument, 0, 'f'}, {"minOverlap", required_argument, 0, 'k'},
         {"listInput", required_argument, 0, 'l'}, {"outputDir", required_argument, 0, 'o'}, {"prefix", required_argument, 0, 'p'},
@@ -57,7 +59,7 @@ int main(int argc, char* argv[]) {
         {"saveAll", no_argument, 0, 's'}, {"debug", no_argument, 0, 'd'}, {"gpu", required_argument, 0, 'g'}, {"gpus", required_argument, 0, 'G'},
         {"share-gpu", no_argument, 0, 1001},      // rehearsal: all ranks on device `gpu`, exchanges by device copies instead of RCCL (a box with fewer GPUs than ranks)
         {"fail-rank", required_argument, 0, 1003},  // tests: this rank of a multi-GPU run fails before its first step (the run must end non-zero, not hang)
-        {"contigs", no_argument, 0, 1004}, {"genomeSize", required_argument, 0, 1005}, {"flowNetwork", no_argument, 0, 1006}, {"flowSolution", required_argument, 0, 1007}, {"extend", no_argument, 0, 1008}, {"scaffold", no_argument, 0, 1009}, {"paths", no_argument, 0, 1010}, {"shortOverlaps", no_argument, 0, 1011},
+        {"contigs", no_argument, 0, 1004}, {"genomeSize", required_argument, 0, 1005}, {"flowNetwork", no_argument, 0, 1006}, {"flowSolution", required_argument, 0, 1007}, {"extend", no_argument, 0, 1008}, {"scaffold", no_argument, 0, 1009}, {"paths", no_argument, 0, 1010}, {"shortOverlaps", no_argument, 0, 1011}, {"flowSolve", no_argument, 0, 1012},
         {"force-multi", no_argument, 0, 1002},    // the multi-GPU code path (RCCL communicator, the four exchanges) even with one GPU
         {0, 0, 0, 0}};
     int c, oi = 0;
@@ -83,6 +85,7 @@ int main(int argc, char* argv[]) {
             case 1005: genomeSize = strtoull(optarg, nullptr, 10); genomeSizeGiven = true; break;
             case 1006: flowNetwork = true; break;
             case 1007: flowSolution = optarg; break;
+            case 1012: flowSolve = true; break;
             case 1008: extend = true; break;
             case 1010: paths = true; break;
             case 1011: shortOverlaps = true; break;
@@ -92,7 +95,8 @@ int main(int argc, char* argv[]) {
         }
     }
     if (fFlag && lFlag) { cout << "[ERROR] Options -f|--fileInput and -l|--listInput are mutually exclusive!\n\n"; exit(0); }
-    const bool step5 = flowNetwork || flowSolution != "";
+    if (flowSolve && flowSolution != "") { cout << "[ERROR] Options --flowSolve and --flowSolution are mutually exclusive!\n\n"; exit(0); }
+    const bool step5 = flowNetwork || flowSolve || flowSolution != "";
     if (step5 && !maxGiven && maxStep < minStep) maxStep = minStep;                          // (`-m 5 --flowSolution FILE` needs no -M)
     bool allSet = true;                                                                     // main.cpp:498-521
     if (fileInput == "" && listInput == "" && minStep <= 1) { cout << "[ERROR] One of the options -f|--fileInput or -l|--listInput is required.\n"; allSet = false; }
@@ -168,8 +172,21 @@ int main(int argc, char* argv[]) {
                 ctx.check(sage2ov_graph5_save(ctx.get(), (outputDir + prefixName + ".graph5").c_str()));
                 logStream << "\t" << prefixName << ".graph5 written\n";
             }
+            if (flowSolve) {                                                                  // main.cpp:199-203 with main_cs2 (copycountEstimator.cpp:359) on the device
+                ctx.check(sage2ov_flow_network_build(ctx.get()));
+                if (saveAll) ctx.check(sage2ov_flow_network_save(ctx.get(), (outputDir + "input.cs2").c_str()));
+                sage2ov_mcf_stats ms{}; ctx.check(sage2ov_flow_solve(ctx.get(), 0, &ms));
+                if (saveAll) ctx.check(sage2ov_flow_solution_save(ctx.get(), (outputDir + "output.cs2").c_str()));
+                ctx.check(sage2ov_flow_solution_commit(ctx.get()));
+                ctx.check(sage2ov_copycount_stats_get(ctx.get(), &cs));
+                logStream << "\tMin-cost flow: " << ms.nodes << " nodes, " << ms.arcs << " arcs, cost " << ms.total_cost << "; " << ms.phases << " phases, " << ms.rounds << " rounds, "
+                          << ms.pushes << " pushes, " << ms.relabels << " relabels, " << ms.price_updates << " price updates in " << (ms.build_ms + ms.solve_ms) / 1000.0 << " sec.\n"
+                          << "\t         Flow from T to S: " << cs.t_to_s_flow << "\n\t  Flow different in edges: " << cs.flow_different << "\n";
+                ctx.check(sage2ov_graph5_save(ctx.get(), (outputDir + prefixName + ".graph5").c_str()));
+                logStream << "\t" << prefixName << ".graph5 written\n";
+            }
             if (!genomeSizeGiven) genomeSize = est;
-            logStream << "\tStep 5 (without its solver) in " << now() - t5 << " sec.\n";
+            logStream << "\tStep 5 (" << (flowSolve ? "with" : "without") << " its solver) in " << now() - t5 << " sec.\n";
         };
         auto step4 = [&](OverlapGraph& graphObj) {                                            // main.cpp:134-181
             double t4 = now();

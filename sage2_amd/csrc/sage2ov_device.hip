@@ -243,6 +243,7 @@ static void mem_sample(Device* d) { size_t fr = 0, to = 0; if (hipMemGetInfo(&fr
 #include "kernels_contig.inc"
 #include "kernels_scaffold.inc"
 #include "kernels_copycount.inc"
+#include "kernels_flow.inc"
 
 // =============================================================================================
 // host primitives: what the launchers below share (grids, counters, transient buffers, a stream timer, scan, radix sort, heads)
@@ -3195,7 +3196,9 @@ int dev_contigs_spell_wait(Device* d, int which, const char** image, double* ms,
 struct CopyCount {
     unsigned short* freq = nullptr; unsigned long long* kPair = nullptr; u64 present = 0;      // of dev_copycount_prepare
     u32 *adj = nullptr, *hp = nullptr, *nodeOf = nullptr; CcArc* arcs = nullptr; u64 F = 0, E = 0, nArcs = 0; bool net = false;      // of dev_flownet_build
-    void drop_net() { hipFree(adj); hipFree(hp); hipFree(nodeOf); hipFree(arcs); adj = hp = nodeOf = nullptr; arcs = nullptr; F = E = nArcs = 0; net = false; }
+    long long *solFlow = nullptr, *solPrice = nullptr; u64 solScale = 0; bool solved = false;      // of dev_flow_solve: a flow per arc, a price per network node (words 1..n of n + 2)
+    void drop_solution() { hipFree(solFlow); hipFree(solPrice); solFlow = solPrice = nullptr; solScale = 0; solved = false; }
+    void drop_net() { drop_solution(); hipFree(adj); hipFree(hp); hipFree(nodeOf); hipFree(arcs); adj = hp = nodeOf = nullptr; arcs = nullptr; F = E = nArcs = 0; net = false; }
     ~CopyCount() { drop_net(); hipFree(freq); hipFree(kPair); }
 };
 static_assert(sizeof(CcArc) == sizeof(FlowArc) && sizeof(CcArc) == 20, "an arc record is five 32-bit words");
@@ -3340,15 +3343,14 @@ int dev_flownet_export(Device* d, FlowArc* out, std::string& err) {
     HIPCHK(hipMemcpy(out, S->arcs, S->nArcs * sizeof(CcArc), hipMemcpyDeviceToHost));
     return 0;
 }
-// the lines of a solution onto the flows of the resident graph (the caller has checked every node number against the network); the supports go, as in dev_flow_set
-int dev_flow_apply(Device* d, const uint64_t* from, const uint64_t* to, const uint64_t* flow, uint64_t n, CopyCountStats* st, std::string& err) {
-    HIPCHK(hipSetDevice(d->ordinal));
+// the lines of a solution onto the flows of the resident graph (the caller has checked every node number against the network); the supports go, as in dev_flow_set.
+// dfr, dto, dfl: the lines in device memory
+static int flow_apply_lines(Device* d, const u64* dfr, const u64* dto, const u64* dfl, uint64_t n, CopyCountStats* st, std::string& err) {
     const CopyCount* S = (const CopyCount*)d->copycount;
-    if (!d->s4keep || !S || !S->net) { err = "flow solution: no flow network"; return SAGE2OV_ERR_INTERNAL; }
     S4Keep& K = *(S4Keep*)d->s4keep; S4Mem& mem = K.mem; const u32 nh = K.nh; hipStream_t sm = d->stream;
     DevTmp B; StreamLap lap(sm); HIPCHK(lap.create());
-    u64* dfr = B.get<u64>(n); u64* dto = B.get<u64>(n); u64* dfl = B.get<u64>(n); unsigned long long* acc = B.get<unsigned long long>(nh); unsigned long long* ctr = B.get<unsigned long long>(2);
-    if (!dfr || !dto || !dfl || !acc || !ctr) return copycount_nomem(err);
+    unsigned long long* acc = B.get<unsigned long long>(nh); unsigned long long* ctr = B.get<unsigned long long>(2);
+    if (!acc || !ctr) return copycount_nomem(err);
     const bool fresh = !K.flow;
     if (fresh) { S4GET(a, float, nh) K.flow = a; K.flowCap = std::max<u64>(nh, 1); }
     dev_support_release(d); dev_paths_release(d);
@@ -3356,11 +3358,7 @@ int dev_flow_apply(Device* d, const uint64_t* from, const uint64_t* to, const ui
     if (fresh && nh) HIPCHK(hipMemsetAsync(K.flow, 0, (u64)nh * sizeof(float), sm));
     if (nh) HIPCHK(hipMemsetAsync(acc, 0, (u64)nh * sizeof(unsigned long long), sm));
     HIPCHK(hipMemsetAsync(ctr, 0, 2 * sizeof(unsigned long long), sm));
-    if (n) {
-        HIPCHK(hipMemcpyAsync(dfr, from, n * sizeof(u64), hipMemcpyHostToDevice, sm)); HIPCHK(hipMemcpyAsync(dto, to, n * sizeof(u64), hipMemcpyHostToDevice, sm));
-        HIPCHK(hipMemcpyAsync(dfl, flow, n * sizeof(u64), hipMemcpyHostToDevice, sm));
-        if (S->F) hipLaunchKernelGGL(k_cc_apply, dim3(grid_for(n, 256)), dim3(256), 0, sm, K.g, S->adj, S->hp, S->nodeOf, (u32)S->E, dfr, dto, dfl, (u64)n, acc, ctr);
-    }
+    if (n && S->F) hipLaunchKernelGGL(k_cc_apply, dim3(grid_for(n, 256)), dim3(256), 0, sm, K.g, S->adj, S->hp, S->nodeOf, (u32)S->E, dfr, dto, dfl, (u64)n, acc, ctr);
     if (nh) hipLaunchKernelGGL(k_cc_average, dim3(grid_for((u64)nh / 2 + 1, 256)), dim3(256), 0, sm, K.g, nh, acc, K.flow, ctr);
     HIPCHK(hipGetLastError());
     unsigned long long hc[2] = {0, 0};
@@ -3368,6 +3366,19 @@ int dev_flow_apply(Device* d, const uint64_t* from, const uint64_t* to, const ui
     HIPCHK(lap.stop(st->apply_ms));
     st->applied = hc[0]; st->different = hc[1];
     return 0;
+}
+int dev_flow_apply(Device* d, const uint64_t* from, const uint64_t* to, const uint64_t* flow, uint64_t n, CopyCountStats* st, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    const CopyCount* S = (const CopyCount*)d->copycount;
+    if (!d->s4keep || !S || !S->net) { err = "flow solution: no flow network"; return SAGE2OV_ERR_INTERNAL; }
+    DevTmp B; hipStream_t sm = d->stream;
+    u64* dfr = B.get<u64>(n); u64* dto = B.get<u64>(n); u64* dfl = B.get<u64>(n);
+    if (!dfr || !dto || !dfl) return copycount_nomem(err);
+    if (n) {
+        HIPCHK(hipMemcpyAsync(dfr, from, n * sizeof(u64), hipMemcpyHostToDevice, sm)); HIPCHK(hipMemcpyAsync(dto, to, n * sizeof(u64), hipMemcpyHostToDevice, sm));
+        HIPCHK(hipMemcpyAsync(dfl, flow, n * sizeof(u64), hipMemcpyHostToDevice, sm));
+    }
+    return flow_apply_lines(d, dfr, dto, dfl, n, st, err);
 }
 int dev_flow_get(Device* d, float* flow, uint64_t n, std::string& err) {
     HIPCHK(hipSetDevice(d->ordinal));
@@ -3377,6 +3388,199 @@ int dev_flow_get(Device* d, float* flow, uint64_t n, std::string& err) {
     if (!K.flow) { std::fill(flow, flow + n, 0.f); return 0; }
     if (n) HIPCHK(hipMemcpy(flow, K.flow, n * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
+}
+
+// =============================================================================================
+// step 5's solver (kernels_flow.inc; main_cs2, copycountEstimator.cpp:359)
+// =============================================================================================
+static int mcf_nomem(std::string& err) { err = "min-cost flow: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+// the epsilon of every phase, and whether the lowest price the phases can reach -- with room for one reduced cost -- stays inside +-2^62
+static bool mcf_phases(u64 scale, u64 maxc, long long* cmaxOut, std::vector<long long>& eps) {
+    const unsigned __int128 lim = (unsigned __int128)1 << 62;
+    unsigned __int128 cmax = (unsigned __int128)scale * maxc; if (cmax < 1) cmax = 1;
+    if (cmax >= lim) return false;
+    unsigned __int128 floor = 0;
+    for (long long e = (long long)cmax;;) { eps.push_back(e); floor += (unsigned __int128)(1 + MF_ALPHA) * scale * (unsigned __int128)e; if (floor >= lim) return false; if (e == 1) break; e = std::max<long long>(1, e / MF_ALPHA); }
+    if (floor + 2 * cmax + 1 >= lim) return false;
+    *cmaxOut = (long long)cmax;
+    return true;
+}
+static int mcf_flag_error(unsigned long long flags, std::string& err) {
+    if (flags & MF_F_NAN) { err = "min-cost flow: a cost that is no number"; return SAGE2OV_ERR_ARG; }
+    if (flags & MF_F_BADARC) { err = "min-cost flow: a bad arc (from == to, a node number outside 1..n, lower > upper or a negative bound)"; return SAGE2OV_ERR_ARG; }
+    if (flags & MF_F_RANGE) { err = "min-cost flow: costs and prices beyond the 64-bit range of the method"; return SAGE2OV_ERR_LIMIT; }
+    if (flags & MF_F_INFEASIBLE) { err = "min-cost flow: the network is infeasible (excess that no residual path can carry to a deficit)"; return SAGE2OV_ERR_ARG; }
+    if (flags & MF_F_LIMIT) { err = "min-cost flow: the round budget is spent"; return SAGE2OV_ERR_LIMIT; }
+    return 0;
+}
+// dArcs: m records in device memory.  On success *flowOut (m words) and *priceOut (n + 2 words, node v at word v) are allocations the caller frees; on any
+// error nothing is handed out.  st is filled as far as the solve got.
+static int mcf_solve_device(Device* d, const McfArc* dArcs, u64 m, u32 n, u64 maxRounds, long long** flowOut, long long** priceOut, McfStats* st, std::string& err) {
+    *flowOut = nullptr; *priceOut = nullptr;
+    if (m >= (1ull << 31) - RS_TILE) { err = "min-cost flow: 2^31 - 2048 arcs or more"; return SAGE2OV_ERR_LIMIT; }
+    if (n >= 0xFFFFFFF0u) { err = "min-cost flow: too many nodes"; return SAGE2OV_ERR_LIMIT; }
+    if (!maxRounds) maxRounds = SAGE2OV_MCF_DEFAULT_ROUNDS;
+    hipStream_t sm = d->stream; const dim3 b256(256); const u32 M = (u32)(2 * m); const u64 scale = (u64)n + 1;
+    st->nodes = n; st->arcs = m; st->scale = scale;
+    DevTmp B; StreamLap lap(sm); HIPCHK(lap.create());
+    unsigned long long* ctr = B.get<unsigned long long>(MF_CTRS); if (!ctr) return mcf_nomem(err);
+    unsigned long long hc[MF_CTRS];
+    HIPCHK(lap.start());
+    HIPCHK(hipMemsetAsync(ctr, 0, MF_CTRS * sizeof(unsigned long long), sm));
+    if (m) hipLaunchKernelGGL(k_mf_check, dim3(grid_for(m, 256)), b256, 0, sm, dArcs, m, n, ctr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(hc, ctr, sizeof hc, hipMemcpyDeviceToHost, sm)); HIPCHK(hipStreamSynchronize(sm));
+    { const int rc = mcf_flag_error(hc[MF_FLAGS], err); if (rc) return rc; }
+    long long cmax = 1; std::vector<long long> epsList;
+    if (!mcf_phases(scale, hc[MF_MAXC], &cmax, epsList)) { err = "min-cost flow: (n + 1) * max |cost| and the price range of the method do not fit 64 bits"; return SAGE2OV_ERR_LIMIT; }
+    // ---- the layout
+    long long* excess = B.get<long long>((u64)n + 2); long long* delta = B.get<long long>((u64)n + 2); long long* dist = B.get<long long>((u64)n + 2);
+    long long* price[2] = {(long long*)DevTmp::alloc(((u64)n + 2) * sizeof(long long)), B.get<long long>((u64)n + 2)};
+    struct Free { void* p; ~Free() { hipFree(p); } } fp0{price[0]};                   // handed out on success only
+    long long* flow = (long long*)DevTmp::alloc(std::max<u64>(m, 1) * sizeof(long long)); Free ff{flow};
+    u32* head = B.get<u32>(M); u32* sis = B.get<u32>(M); u32* tail = B.get<u32>(M); u32* start = B.get<u32>((u64)n + 3); u32* pos = B.get<u32>(M);
+    long long* cost = B.get<long long>(M); int* rcap = B.get<int>(M); u64* key = B.get<u64>(M);
+    if (!excess || !delta || !dist || !price[0] || !price[1] || !flow || !head || !sis || !tail || !start || !pos || !cost || !rcap || !key) return mcf_nomem(err);
+    HIPCHK(hipMemsetAsync(excess, 0, ((u64)n + 2) * sizeof(long long), sm)); HIPCHK(hipMemsetAsync(delta, 0, ((u64)n + 2) * sizeof(long long), sm));
+    HIPCHK(hipMemsetAsync(price[0], 0, ((u64)n + 2) * sizeof(long long), sm)); HIPCHK(hipMemsetAsync(price[1], 0, ((u64)n + 2) * sizeof(long long), sm));
+    if (m) {
+        hipLaunchKernelGGL(k_mf_keys, dim3(grid_for(m, 256)), b256, 0, sm, dArcs, m, key, excess);
+        int shifts[4]; const int np = copycount_passes(n, shifts);
+        u64* ks = nullptr; u32* idx = nullptr; MateStats ms;
+        { const int rc = mate_sort(d, B, key, M, shifts, np, &ks, &idx, &ms, err); if (rc) return rc; }
+        hipLaunchKernelGGL(k_mf_pos, dim3(grid_for(M, 256)), b256, 0, sm, idx, M, pos);
+        hipLaunchKernelGGL(k_mf_entries, dim3(grid_for(M, 256)), b256, 0, sm, dArcs, idx, pos, ks, M, (long long)scale, head, sis, tail, cost, rcap);
+        hipLaunchKernelGGL(k_mf_starts, dim3(grid_for((u64)n + 2, 256)), b256, 0, sm, ks, M, n, start);
+    } else HIPCHK(hipMemsetAsync(start, 0, ((u64)n + 3) * sizeof(u32), sm));
+    HIPCHK(hipGetLastError());
+    HIPCHK(lap.stop(st->build_ms));
+    const MfNet N = {head, sis, tail, start, cost, rcap, excess, delta, n, M};
+    const u32 nodeGrid = grid_for(n, MF_BLOCK), entryGrid = grid_for(M, 256);
+    // (SAGE2OV_TEST_MCF_LDS=0: tests only -- a network that fits the single-workgroup form takes the launches all the same)
+    const bool lds = m && n <= MF_LDS_NODES && M <= MF_LDS_ENTRIES && d->opt.num("SAGE2OV_TEST_MCF_LDS", 1) != 0;
+    st->form = lds ? SAGE2OV_MCF_FORM_LDS : SAGE2OV_MCF_FORM_LAUNCHES;
+    u32 cur = 0; unsigned long long flags = 0;
+    HIPCHK(lap.start());
+    if (lds) {
+        const MfLdsArgs A = {cmax, (long long)scale, maxRounds, MF_PERIOD};
+        hipLaunchKernelGGL(k_mf_lds, dim3(1), dim3(MF_BLOCK), 0, sm, N, price[0], A, ctr);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(hc, ctr, sizeof hc, hipMemcpyDeviceToHost, sm)); HIPCHK(hipStreamSynchronize(sm));
+        st->phases = hc[MF_PHASES]; st->rounds = hc[MF_ROUNDS]; st->pushes = hc[MF_PUSHES]; st->relabels = hc[MF_RELABELS]; st->updates = hc[MF_UPDATES]; flags = hc[MF_FLAGS];
+    } else if (m) {
+        const long long cap = (long long)(1 + MF_ALPHA) * (long long)scale;
+        long long floor = 0; u64 rounds = 0, updates = 0;
+        hipEvent_t e0 = nullptr, e1 = nullptr; HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+        struct Ev { hipEvent_t a, b; ~Ev() { hipEventDestroy(a); hipEventDestroy(b); } } evs{e0, e1};
+        for (size_t ph = 0; ph < epsList.size() && !flags; ph++) {
+            const long long eps = epsList[ph];
+            floor -= cap * eps; st->phases++;
+            const u64 r0 = rounds;
+            HIPCHK(hipEventRecord(e0, sm));
+            hipLaunchKernelGGL(k_mf_saturate, dim3(entryGrid), b256, 0, sm, N, price[cur]);
+            u64 since = MF_PERIOD;
+            for (bool done = false; !done && !flags;) {
+                const u64 left = maxRounds - rounds;
+                if (!left) { flags |= MF_F_LIMIT; break; }
+                if (since >= MF_PERIOD) {                                               // the price update: relax until a launch improves nothing
+                    since = 0; floor -= cap * eps;
+                    if (floor < -(MF_INF - 2 * cmax - 1)) { flags |= MF_F_RANGE; break; }
+                    hipLaunchKernelGGL(k_mf_pu_init, dim3(grid_for((u64)n + 2, 256)), b256, 0, sm, excess, n, dist);
+                    bool settled = false;
+                    for (u64 it = 0; it <= (u64)n + MF_BATCH && !settled; it += MF_BATCH) {      // (a shortest path has at most n - 1 entries)
+                        HIPCHK(hipMemsetAsync(ctr + MF_ACT, 0, MF_BATCH * sizeof(unsigned long long), sm));
+                        for (u32 k = 0; k < MF_BATCH; k++) hipLaunchKernelGGL(k_mf_pu_relax, dim3(entryGrid), b256, 0, sm, N, price[cur], eps, cap, dist, ctr + MF_ACT + k);
+                        HIPCHK(hipGetLastError());
+                        HIPCHK(hipMemcpyAsync(hc, ctr, MF_BATCH * sizeof(unsigned long long), hipMemcpyDeviceToHost, sm)); HIPCHK(hipStreamSynchronize(sm));
+                        for (u32 k = 0; k < MF_BATCH; k++) if (!hc[MF_ACT + k]) settled = true;
+                    }
+                    if (!settled) { err = "min-cost flow: the price update did not settle"; return SAGE2OV_ERR_INTERNAL; }
+                    hipLaunchKernelGGL(k_mf_pu_apply, dim3(grid_for((u64)n + 1, 256)), b256, 0, sm, excess, dist, n, eps, cap, price[cur], ctr);
+                    updates++;
+                }
+                const u32 K = (u32)std::min<u64>(MF_BATCH, left);
+                HIPCHK(hipMemsetAsync(ctr + MF_ACT, 0, MF_BATCH * sizeof(unsigned long long), sm));
+                for (u32 k = 0; k < K; k++) {
+                    hipLaunchKernelGGL(k_mf_push, dim3(nodeGrid), dim3(MF_BLOCK), 0, sm, N, price[cur], ctr);
+                    hipLaunchKernelGGL(k_mf_relabel, dim3(nodeGrid), dim3(MF_BLOCK), 0, sm, N, price[cur], price[cur ^ 1u], eps, floor, ctr + MF_ACT + k, ctr);
+                    cur ^= 1u;
+                }
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipMemcpyAsync(hc, ctr, sizeof hc, hipMemcpyDeviceToHost, sm)); HIPCHK(hipStreamSynchronize(sm));
+                flags |= hc[MF_FLAGS];
+                u32 used = K;
+                for (u32 k = 0; k < K; k++) if (!hc[MF_ACT + k]) { used = k + 1; done = true; break; }      // (the rounds behind it found nothing to do)
+                rounds += used; since += used;
+            }
+            HIPCHK(hipEventRecord(e1, sm)); HIPCHK(hipEventSynchronize(e1));
+            if (ph < SAGE2OV_MCF_PHASES) { float t = 0; hipEventElapsedTime(&t, e0, e1); st->refine_ms[ph] = t; st->refine_rounds[ph] = rounds - r0; }
+            st->rounds = rounds; st->updates = updates; st->pushes = hc[MF_PUSHES]; st->relabels = hc[MF_RELABELS];
+        }
+    }
+    HIPCHK(lap.stop(st->solve_ms));
+    { const int rc = mcf_flag_error(flags, err); if (rc) return rc; }
+    if (m) hipLaunchKernelGGL(k_mf_flows, dim3(grid_for(m, 256)), b256, 0, sm, dArcs, pos, rcap, m, flow);
+    HIPCHK(hipGetLastError());
+    if (cur == 1) HIPCHK(hipMemcpyAsync(price[0], price[1], ((u64)n + 2) * sizeof(long long), hipMemcpyDeviceToDevice, sm));
+    HIPCHK(hipStreamSynchronize(sm));
+    *flowOut = flow; *priceOut = price[0]; ff.p = nullptr; fp0.p = nullptr;
+    return 0;
+}
+int dev_mcf_solve(Device* d, const void* arcs, uint64_t m, uint32_t n, uint64_t maxRounds, int64_t* flow, int64_t* price, McfStats* st, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    static_assert(sizeof(McfArc) == 24, "an arc is 24 bytes");
+    DevTmp B; McfArc* dA = B.get<McfArc>(m); if (!dA) return mcf_nomem(err);
+    if (m) HIPCHK(hipMemcpyAsync(dA, arcs, m * sizeof(McfArc), hipMemcpyHostToDevice, d->stream));
+    long long *dF = nullptr, *dP = nullptr;
+    { const int rc = mcf_solve_device(d, dA, m, n, maxRounds, &dF, &dP, st, err); if (rc) return rc; }
+    hipError_t e = hipSuccess;
+    if (m) e = hipMemcpy(flow, dF, m * sizeof(long long), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && price && n) e = hipMemcpy(price, dP + 1, (u64)n * sizeof(long long), hipMemcpyDeviceToHost);
+    hipFree(dF); hipFree(dP);
+    HIPCHK(e);
+    return 0;
+}
+// the resident network of dev_flownet_build; the earlier solution stays unless this one succeeds
+int dev_flow_solve(Device* d, uint64_t maxRounds, McfStats* st, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    CopyCount* S = (CopyCount*)d->copycount;
+    if (!d->s4keep || !S || !S->net) { err = "flow solve: no flow network"; return SAGE2OV_ERR_ARG; }
+    const u64 m = S->nArcs; const u64 nn = 4 * S->E + 2;
+    DevTmp B; McfArc* dA = B.get<McfArc>(m); unsigned long long* ctr = B.get<unsigned long long>(MF_CTRS); if (!dA || !ctr) return mcf_nomem(err);
+    HIPCHK(hipMemsetAsync(ctr, 0, MF_CTRS * sizeof(unsigned long long), d->stream));
+    hipLaunchKernelGGL(k_mf_from_cc, dim3(grid_for(m, 256)), dim3(256), 0, d->stream, S->arcs, m, dA, ctr);
+    HIPCHK(hipGetLastError());
+    unsigned long long fl = 0; HIPCHK(hipMemcpyAsync(&fl, ctr + MF_FLAGS, sizeof fl, hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
+    { const int rc = mcf_flag_error(fl, err); if (rc) return rc; }
+    long long *dF = nullptr, *dP = nullptr;
+    { const int rc = mcf_solve_device(d, dA, m, (u32)nn, maxRounds, &dF, &dP, st, err); if (rc) return rc; }
+    S->drop_solution(); S->solFlow = dF; S->solPrice = dP; S->solScale = nn + 1; S->solved = true;
+    return 0;
+}
+bool dev_flow_solved(Device* d) { const CopyCount* S = (const CopyCount*)d->copycount; return S && S->net && S->solved; }
+// flow: one word per arc; price: one per network node (either may be null)
+int dev_flow_solution_get(Device* d, int64_t* flow, int64_t* price, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    const CopyCount* S = (const CopyCount*)d->copycount; if (!S || !S->net || !S->solved) { err = "flow solution: none"; return SAGE2OV_ERR_ARG; }
+    if (flow) HIPCHK(hipMemcpy(flow, S->solFlow, S->nArcs * sizeof(long long), hipMemcpyDeviceToHost));
+    if (price) HIPCHK(hipMemcpy(price, S->solPrice + 1, (4 * S->E + 2) * sizeof(long long), hipMemcpyDeviceToHost));
+    return 0;
+}
+// the resident flows through k_cc_apply / k_cc_average: the lines are made on the device and never leave it.  *tts: the flow of the `2 1` arc
+int dev_flow_commit(Device* d, CopyCountStats* st, uint64_t* tts, uint64_t* lines, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    const CopyCount* S = (const CopyCount*)d->copycount;
+    if (!d->s4keep || !S || !S->net || !S->solved) { err = "flow commit: no solution of the present network"; return SAGE2OV_ERR_ARG; }
+    const u64 m = S->nArcs; hipStream_t sm = d->stream;
+    DevTmp B; McfArc* dA = B.get<McfArc>(m); u64* dfr = B.get<u64>(m); u64* dto = B.get<u64>(m); u64* dfl = B.get<u64>(m); unsigned long long* ctr = B.get<unsigned long long>(MF_CTRS);
+    if (!dA || !dfr || !dto || !dfl || !ctr) return mcf_nomem(err);
+    HIPCHK(hipMemsetAsync(ctr, 0, MF_CTRS * sizeof(unsigned long long), sm));
+    hipLaunchKernelGGL(k_mf_from_cc, dim3(grid_for(m, 256)), dim3(256), 0, sm, S->arcs, m, dA, ctr);
+    hipLaunchKernelGGL(k_mf_triples, dim3(grid_for(m, 256)), dim3(256), 0, sm, dA, S->solFlow, m, dfr, dto, dfl, ctr);
+    HIPCHK(hipGetLastError());
+    unsigned long long t = 0; HIPCHK(hipMemcpyAsync(&t, ctr + MF_TTS, sizeof t, hipMemcpyDeviceToHost, sm)); HIPCHK(hipStreamSynchronize(sm));
+    *tts = t; *lines = m;
+    return flow_apply_lines(d, dfr, dto, dfl, m, st, err);
 }
 
 }  // namespace s2

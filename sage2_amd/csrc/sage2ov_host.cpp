@@ -140,6 +140,7 @@ struct sage2ov_ctx {
     void contigs_forget() { ctgValid = false; ctgRows.clear(); ctgChunk.clear(); cstats = sage2ov_contig_stats{}; }
     // ---- step 5 around its solver (sage2ov_genome_size_estimate, sage2ov_flow_*): the estimate and the network are of the present graph and read set; the data live on the device
     bool gsValid = false, netValid = false; sage2ov_copycount_stats ccstats{};
+    sage2ov_mcf_stats mcfstats{};                                                      // of the last solve (sage2ov_mcf_solve, sage2ov_flow_solve)
     void copycount_forget() { gsValid = netValid = false; ccstats = sage2ov_copycount_stats{}; }
     // ---- the merge rounds (sage2ov_graph_merge_pairs, sage2ov_extend_*): the estimate outlives a merge (estimateHeld: a rebuilt table leaves it alone); the header
     // values of P.graph6 are those from before the first merge
@@ -2218,6 +2219,105 @@ int sage2ov_graph5_save(sage2ov_ctx* c, const char* path) {                     
     return save_composite(c, path, true, (unsigned long long)c->ccstats.genome_size, (unsigned long long)c->ccstats.reads_present);
 }
 int sage2ov_copycount_stats_get(const sage2ov_ctx* c, sage2ov_copycount_stats* o) { if (!c || !o) return SAGE2OV_ERR_ARG; *o = c->ccstats; return SAGE2OV_OK; }
+// ---- step 5's solver (main_cs2, :359)
+namespace {
+void mcf_stats_set(sage2ov_ctx* c, const McfStats& s) {
+    sage2ov_mcf_stats o{};
+    o.nodes = s.nodes; o.arcs = s.arcs; o.scale = s.scale; o.phases = s.phases; o.rounds = s.rounds; o.pushes = s.pushes; o.relabels = s.relabels; o.price_updates = s.updates;
+    o.form = s.form; o.build_ms = s.build_ms; o.solve_ms = s.solve_ms;
+    for (int i = 0; i < SAGE2OV_MCF_PHASES; i++) { o.refine_rounds[i] = s.refine_rounds[i]; o.refine_ms[i] = s.refine_ms[i]; }
+    c->mcfstats = o;
+}
+// sum of flow * cost; false when it leaves int64
+extern "C++" { template <class Cost>
+bool mcf_total_cost(const int64_t* flow, uint64_t m, Cost&& cost, int64_t* out) {
+    __int128 t = 0;
+    for (uint64_t i = 0; i < m; i++) t += (__int128)flow[i] * (__int128)cost(i);
+    if (t > (__int128)INT64_MAX || t < (__int128)INT64_MIN) return false;
+    *out = (int64_t)t; return true;
+} }
+// the cost the solver sees of a record's float: truncation towards zero (k_mf_from_cc)
+int64_t mcf_trunc(float c) { return (int64_t)c; }
+}  // namespace
+int sage2ov_mcf_solve(sage2ov_ctx* c, uint64_t n, const sage2ov_mcf_arc* arcs, uint64_t m, uint64_t max_rounds, int64_t* flow, int64_t* price, sage2ov_mcf_stats* stats) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    if (m && (!arcs || !flow)) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_mcf_solve: null argument");
+    if (!c->device()) return c->fail(SAGE2OV_ERR_DEVICE, c->gpu() ? c->devErr : "sage2ov_mcf_solve: this context has no GPU");
+    if (n >= 0xFFFFFFF0ull) return c->fail(SAGE2OV_ERR_LIMIT, "sage2ov_mcf_solve: too many nodes");
+    McfStats s;
+    const int rc = dev_mcf_solve(c->device(), arcs, m, (uint32_t)n, max_rounds, flow, price, &s, c->err);
+    mcf_stats_set(c, s);
+    int out = rc;
+    if (!rc && !mcf_total_cost(flow, m, [&](uint64_t i) { return arcs[i].cost; }, &c->mcfstats.total_cost)) out = c->fail(SAGE2OV_ERR_LIMIT, "sage2ov_mcf_solve: the total cost does not fit 64 bits");
+    if (stats) *stats = c->mcfstats;
+    return out;
+}
+int sage2ov_flow_solve(sage2ov_ctx* c, uint64_t max_rounds, sage2ov_mcf_stats* stats) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    { const int rc = copycount_check(c, "sage2ov_flow_solve"); if (rc) return rc; }
+    if (!c->netValid) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_flow_solve: build the flow network first (sage2ov_flow_network_build)");
+    McfStats s;
+    const int rc = dev_flow_solve(c->device(), max_rounds, &s, c->err);
+    mcf_stats_set(c, s);
+    int out = rc;
+    if (!rc) {
+        std::vector<FlowArc> arcs(c->ccstats.network_arcs); std::vector<int64_t> flow(arcs.size());
+        out = dev_flownet_export(c->device(), arcs.data(), c->err);
+        if (!out) out = dev_flow_solution_get(c->device(), flow.data(), nullptr, c->err);
+        if (!out && !mcf_total_cost(flow.data(), flow.size(), [&](uint64_t i) { return mcf_trunc(arcs[i].cost); }, &c->mcfstats.total_cost))
+            out = c->fail(SAGE2OV_ERR_LIMIT, "sage2ov_flow_solve: the total cost does not fit 64 bits");
+    }
+    if (stats) *stats = c->mcfstats;
+    return out;
+}
+int sage2ov_flow_solution_export(sage2ov_ctx* c, int64_t* flow, uint64_t cap_flow, int64_t* price, uint64_t cap_price, uint64_t* scale) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    { const int rc = copycount_check(c, "sage2ov_flow_solution_export"); if (rc) return rc; }
+    if (!c->netValid || !dev_flow_solved(c->device())) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_flow_solution_export: no solution of the present network (sage2ov_flow_solve)");
+    if ((flow && cap_flow < c->ccstats.network_arcs) || (price && cap_price < c->ccstats.network_nodes)) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_flow_solution_export: a buffer is too small");
+    if (scale) *scale = c->ccstats.network_nodes + 1;
+    return dev_flow_solution_get(c->device(), flow, price, c->err);
+}
+int sage2ov_flow_solution_save(sage2ov_ctx* c, const char* path) {
+    if (!c || !path) return SAGE2OV_ERR_ARG;
+    { const int rc = copycount_check(c, "sage2ov_flow_solution_save"); if (rc) return rc; }
+    if (!c->netValid || !dev_flow_solved(c->device())) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_flow_solution_save: no solution of the present network (sage2ov_flow_solve)");
+    std::vector<FlowArc> arcs(c->ccstats.network_arcs); std::vector<int64_t> flow(arcs.size());
+    { const int rc = dev_flownet_export(c->device(), arcs.data(), c->err); if (rc) return rc; }
+    { const int rc = dev_flow_solution_get(c->device(), flow.data(), nullptr, c->err); if (rc) return rc; }
+    std::vector<uint32_t> order; order.reserve(arcs.size());
+    for (uint64_t i = 0; i < arcs.size(); i++) if (arcs[i].upper > 0) order.push_back((uint32_t)i);
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return arcs[a].from < arcs[b].from; });      // by tail, then input order
+    FILE* f = fopen(path, "w"); if (!f) return c->fail(SAGE2OV_ERR_IO, std::string("cannot open ") + path);
+    std::vector<char> io(1 << 22); setvbuf(f, io.data(), _IOFBF, io.size());
+    for (uint32_t i : order) fprintf(f, "%u %u %lld\n", arcs[i].from, arcs[i].to, (long long)flow[i]);
+    const bool bad = ferror(f) != 0;
+    if (fclose(f) != 0 || bad) return c->fail(SAGE2OV_ERR_IO, std::string("cannot write ") + path);
+    return SAGE2OV_OK;
+}
+int sage2ov_flow_solution_commit(sage2ov_ctx* c) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    { const int rc = copycount_check(c, "sage2ov_flow_solution_commit"); if (rc) return rc; }
+    if (!c->netValid || !dev_flow_solved(c->device())) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_flow_solution_commit: no solution of the present network (sage2ov_flow_solve)");
+    CopyCountStats s; uint64_t tts = 0, lines = 0;
+    c->supports_forget(); c->paths_forget(); c->contigs_forget();
+    { const int rc = dev_flow_commit(c->device(), &s, &tts, &lines, c->err); if (rc) return rc; }
+    std::vector<float> f(c->g4.n_half_edges, 0.f);
+    { const int rc = dev_flow_get(c->device(), f.data(), f.size(), c->err); if (rc) return rc; }
+    c->g4.flow = std::move(f);
+    sage2ov_copycount_stats& o = c->ccstats;
+    o.t_to_s_flow = tts; o.flow_different = s.different; o.solution_lines = lines; o.lines_applied = s.applied;
+    copycount_times(c, s);
+    return SAGE2OV_OK;
+}
+int sage2ov_copy_counts(sage2ov_ctx* c, uint64_t* genome_size) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    { const int rc = sage2ov_genome_size_estimate(c, genome_size); if (rc) return rc; }
+    { const int rc = sage2ov_flow_network_build(c); if (rc) return rc; }
+    { const int rc = sage2ov_flow_solve(c, 0, nullptr); if (rc) return rc; }
+    return sage2ov_flow_solution_commit(c);
+}
+int sage2ov_mcf_stats_get(const sage2ov_ctx* c, sage2ov_mcf_stats* o) { if (!c || !o) return SAGE2OV_ERR_ARG; *o = c->mcfstats; return SAGE2OV_OK; }
 int sage2ov_mates_supports(sage2ov_ctx* c) {
     if (!c) return SAGE2OV_ERR_ARG;
     { const int rc = readmap_check(c, "sage2ov_mates_supports"); if (rc) return rc; }
