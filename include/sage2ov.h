@@ -409,14 +409,20 @@ int sage2ov_copycount_stats_get(const sage2ov_ctx* ctx, sage2ov_copycount_stats*
  *                     parser_cs2.h:257 reads a cost with %lld: the integer prefix of the printed text, truncation towards zero (`-691.348000` is -691, `-0.7` is 0).
  *   scale             costs are multiplied by n + 1: a flow that is 1-optimal in scaled units is optimal.  Prices are in scaled units.
  *   the certificate   lower <= flow <= upper; every node conserved; cost * scale + price[from] - price[to] >= -1 wherever flow < upper, <= 1 wherever flow > lower.
- *   limits            SAGE2OV_ERR_LIMIT, nothing solved: (n + 1) * max |cost| or the lowest price the method can reach do not fit +-2^62 (checked before any launch
- *                     and again before every price update) -- about 10.3 * (n + 1)^2 * max |cost| < 2^62: some 211 000 nodes with step 5's costs of 10^7; 2^31 - 2048 arcs or more; the round budget spent (max_rounds; 0: SAGE2OV_MCF_DEFAULT_ROUNDS) -- then
+ *   price width       prices, scaled and reduced costs, epsilon and the price floor are 64-bit integers (sage2ov_mcf_solve) or 128-bit ones (sage2ov_mcf_solve_wide);
+ *                     the method, and on a network both admit every flow, price and counter, are the same.  The lowest price the method can reach, with room for one
+ *                     reduced cost -- about 10.3 * (n + 1)^2 * max |cost| -- must stay inside +-2^62 or +-2^126: 64 bits carry some 211 000 nodes with step 5's costs
+ *                     of 10^7, 128 bits any network whose nodes are 32-bit numbers and whose costs stay below about 2^58 -- every resident network.  The calls on the
+ *                     resident network (sage2ov_flow_solve, sage2ov_copy_counts) take 64 bits where that guard admits the network and 128 bits where it does not.
+ *                     A 128-bit price is two uint64_t words, the low one first, two's complement.
+ *   limits            SAGE2OV_ERR_LIMIT, nothing solved: the guard of the width refuses (checked before any launch of the solve, and again before every price
+ *                     update); 2^31 - 2048 arcs or more; the round budget spent (max_rounds; 0: SAGE2OV_MCF_DEFAULT_ROUNDS) -- then
  *                     the statistics are filled in, nothing is applied and the graph, the network and any earlier solution stay as they were.
  *   SAGE2OV_ERR_ARG   from == to, a node number outside 1..n, lower > upper, a negative bound; an infeasible network ("infeasible" in sage2ov_last_error): excess
  *                     that no residual path carries to a deficit, or a price below the bound of the method.
  * SAGE2OV_ERR_DEVICE on a device-less context. */
 #define SAGE2OV_MCF_DEFAULT_ROUNDS (1ull << 22)
-#define SAGE2OV_MCF_PHASES 24               /* epsilon phases whose rounds and times the statistics keep (2^62 needs 21) */
+#define SAGE2OV_MCF_PHASES 24               /* epsilon phases whose rounds and times the statistics keep (2^62 needs 21; 128-bit prices can need more: the first 24 are kept) */
 #define SAGE2OV_MCF_FORM_LDS 1              /* one workgroup, the network in LDS: at most 512 nodes and 1024 arcs */
 #define SAGE2OV_MCF_FORM_LAUNCHES 2         /* two launches per round, the rounds counted on the host */
 typedef struct sage2ov_mcf_arc { uint32_t from, to; int32_t lower, upper; int64_t cost; } sage2ov_mcf_arc;      /* cs2/parser_cs2.h:232-262: `a from to lower upper cost` */
@@ -424,19 +430,25 @@ typedef struct sage2ov_mcf_stats {
     uint64_t nodes, arcs, scale;                       /* scale = nodes + 1 */
     uint64_t phases, rounds, pushes, relabels, price_updates;
     int64_t  total_cost;                               /* sum of flow * cost, unscaled */
-    uint32_t form, reserved;                           /* SAGE2OV_MCF_FORM_* */
+    uint32_t form, price_words;                        /* SAGE2OV_MCF_FORM_*; 64-bit words of a price: 1 or 2 */
     double   build_ms, solve_ms;                       /* HIP-event times: layout, rounds */
     uint64_t refine_rounds[SAGE2OV_MCF_PHASES];        /* the launches form: per epsilon phase */
     double   refine_ms[SAGE2OV_MCF_PHASES];
 } sage2ov_mcf_stats;
 /* any network; needs a device context and no reads.  flow_out: m words, the full flow (lower bound included, cs2.cpp:1872) in input order; price_out: n words or NULL */
 int sage2ov_mcf_solve(sage2ov_ctx* ctx, uint64_t n_nodes, const sage2ov_mcf_arc* arcs, uint64_t m, uint64_t max_rounds, int64_t* flow_out, int64_t* price_out, sage2ov_mcf_stats* stats);
+/* the same with 128-bit prices, whatever the network (statistics: price_words 2, form SAGE2OV_MCF_FORM_LAUNCHES); price_out: 2 n words or NULL, node v's low word at
+ * 2 (v - 1).  The guard against +-2^126 is held on the arcs given before anything is allocated on the device */
+int sage2ov_mcf_solve_wide(sage2ov_ctx* ctx, uint64_t n_nodes, const sage2ov_mcf_arc* arcs, uint64_t m, uint64_t max_rounds, int64_t* flow_out, uint64_t* price_out, sage2ov_mcf_stats* stats);
 /* the resident network of sage2ov_flow_network_build (before it: SAGE2OV_ERR_ARG); an arc's cost is the truncation towards zero of the float in its record, a NaN or
  * an infinity there SAGE2OV_ERR_ARG (the reference's parser would refuse the line).  The solution stays resident and goes with the network.  stats may be NULL */
 int sage2ov_flow_solve(sage2ov_ctx* ctx, uint64_t max_rounds, sage2ov_mcf_stats* stats);
 /* flow: one word per arc of sage2ov_flow_network_export, price: one per network node; a cap below the count with the array given: SAGE2OV_ERR_ARG, nothing written;
  * a NULL array is skipped.  Without a solution: SAGE2OV_ERR_ARG */
 int sage2ov_flow_solution_export(sage2ov_ctx* ctx, int64_t* flow, uint64_t cap_flow, int64_t* price, uint64_t cap_price, uint64_t* scale);
+/* the same for a solution of either width (sage2ov_mcf_stats.price_words of the solve): price has two words per network node (cap_price counts nodes), 64-bit prices
+ * sign-extended.  sage2ov_flow_solution_export with a price array on a solution of 128-bit prices: SAGE2OV_ERR_LIMIT, nothing written; without one it serves both */
+int sage2ov_flow_solution_export_wide(sage2ov_ctx* ctx, int64_t* flow, uint64_t cap_flow, uint64_t* price, uint64_t cap_price, uint64_t* scale);
 /* `from to flow` for the arcs with upper > 0 (cs2.cpp prints no other).  The ORDER IS OURS, not the reference's: by tail, then input order.  sage2ov_flow_solution_load
  * of the file gives the flows sage2ov_flow_solution_commit gives */
 int sage2ov_flow_solution_save(sage2ov_ctx* ctx, const char* path);

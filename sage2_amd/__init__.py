@@ -166,6 +166,13 @@ MCF_PHASES = 24
 MCF_FORM_LDS, MCF_FORM_LAUNCHES = 1, 2
 
 
+def wide_prices(words):
+    """128-bit prices as the library hands them out (two uint64 words per node, the low one first, two's complement) as Python integers"""
+    if words is None: return []
+    lo, hi = words[0::2].tolist(), words[1::2].tolist()
+    return [((h << 64) | l) - ((h >> 63) << 128) for l, h in zip(lo, hi)]
+
+
 class GenomeEstimate(C.Structure):
     _fields_ = [("genome_size", C.c_uint64), ("estimate", C.c_uint64 * GENOME_ROUNDS), ("delta_sum", C.c_uint64 * GENOME_ROUNDS), ("k_sum", C.c_uint64 * GENOME_ROUNDS),
                 ("rounds", C.c_uint32), ("degenerate", C.c_uint32), ("agreed", C.c_uint32), ("reserved", C.c_uint32)]
@@ -173,7 +180,7 @@ class GenomeEstimate(C.Structure):
 
 class McfStats(C.Structure):
     _fields_ = [("nodes", C.c_uint64), ("arcs", C.c_uint64), ("scale", C.c_uint64), ("phases", C.c_uint64), ("rounds", C.c_uint64), ("pushes", C.c_uint64),
-                ("relabels", C.c_uint64), ("price_updates", C.c_uint64), ("total_cost", C.c_int64), ("form", C.c_uint32), ("reserved", C.c_uint32),
+                ("relabels", C.c_uint64), ("price_updates", C.c_uint64), ("total_cost", C.c_int64), ("form", C.c_uint32), ("price_words", C.c_uint32),
                 ("build_ms", C.c_double), ("solve_ms", C.c_double), ("refine_rounds", C.c_uint64 * MCF_PHASES), ("refine_ms", C.c_double * MCF_PHASES)]
 
 
@@ -549,10 +556,16 @@ class Context:
         self._chk(lib().sage2ov_graph5_save(self._h, os.fsencode(path)))
 
     # ---- step 5's solver (main_cs2): min-cost flow on the device
-    def mcf_solve(self, n, arcs, max_rounds=0):
+    def mcf_solve(self, n, arcs, max_rounds=0, wide=False):
         """solves the circulation over nodes 1..n with the arcs (MCF_ARC_DTYPE); returns (flow per arc, price per node in scaled units, McfStats).  A failed
-        solve raises Sage2ovError; mcf_stats() still tells how far it got"""
+        solve raises Sage2ovError; mcf_stats() still tells how far it got.  wide: 128-bit prices on the device; they come back as a list of Python integers"""
         a = np.ascontiguousarray(arcs, dtype=MCF_ARC_DTYPE)
+        if wide:
+            flow = np.zeros(len(a), dtype=np.int64); st = McfStats()
+            words = np.zeros(2 * int(n), dtype=np.uint64) if int(n) < (1 << 28) else None      # (beyond 2^28 nodes no prices are fetched: [])
+            self._chk(lib().sage2ov_mcf_solve_wide(self._h, C.c_uint64(int(n)), C.c_void_p(a.ctypes.data), C.c_uint64(len(a)), C.c_uint64(int(max_rounds)),
+                                                   C.c_void_p(flow.ctypes.data), C.c_void_p(words.ctypes.data if words is not None else None), C.byref(st)))
+            return flow, wide_prices(words), st
         flow = np.zeros(len(a), dtype=np.int64); price = np.zeros(int(n), dtype=np.int64); st = McfStats()
         self._chk(lib().sage2ov_mcf_solve(self._h, C.c_uint64(int(n)), C.c_void_p(a.ctypes.data), C.c_uint64(len(a)), C.c_uint64(int(max_rounds)),
                                           C.c_void_p(flow.ctypes.data), C.c_void_p(price.ctypes.data), C.byref(st)))
@@ -571,6 +584,14 @@ class Context:
         flow = np.zeros(arcs.value, dtype=np.int64); price = np.zeros(nodes.value, dtype=np.int64)
         self._chk(lib().sage2ov_flow_solution_export(self._h, C.c_void_p(flow.ctypes.data), C.c_uint64(arcs.value), C.c_void_p(price.ctypes.data), C.c_uint64(nodes.value), C.byref(scale)))
         return flow, price, int(scale.value)
+
+    def flow_solution_wide(self):
+        """flow_solution() for a solution of either price width: the prices are a list of Python integers"""
+        nodes, arcs, scale = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._chk(lib().sage2ov_flow_network_count(self._h, C.byref(nodes), C.byref(arcs)))
+        flow = np.zeros(arcs.value, dtype=np.int64); words = np.zeros(2 * nodes.value, dtype=np.uint64)
+        self._chk(lib().sage2ov_flow_solution_export_wide(self._h, C.c_void_p(flow.ctypes.data), C.c_uint64(arcs.value), C.c_void_p(words.ctypes.data), C.c_uint64(nodes.value), C.byref(scale)))
+        return flow, wide_prices(words), int(scale.value)
 
     def flow_solution_save(self, path):
         self._chk(lib().sage2ov_flow_solution_save(self._h, os.fsencode(path)))

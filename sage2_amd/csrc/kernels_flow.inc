@@ -2,6 +2,9 @@
 // round-synchronous push-relabel (DESIGN.md 5.20; tests/flow_model.py is the same method in numpy).  Part of sage2ov_device.hip (included inside namespace s2).
 //
 // Integers only: 64-bit prices, excesses and scaled costs, 32-bit residual capacities.  Nodes are 1..n; arrays per node have n + 2 words.
+// The kernels of the rounds and of the price update are templates on the price type P: long long, or __int128 for networks whose prices leave +-2^62 (prices,
+// reduced costs, eps and the floor are P; excess, delta, distances and residuals keep their widths).  With P = __int128 an entry's cost stays the unscaled 64-bit
+// cost and is multiplied by scale (< 2^32) where it is read, so that the entry arrays streamed every round do not grow; a price is one aligned 16-byte load.
 // Entry 2 i is arc i forwards (residual upper - lower, cost * scale), entry 2 i + 1 backwards (residual 0, -cost * scale); the entries are sorted stably by
 // tail (the project's radix sort), so a node's list is start[v] .. start[v + 1] in ascending entry number; sis[s] is the position of the entry's sister.
 //   k_mf_from_cc     the resident network's records: the float cost truncated towards zero, as `%lld` reads the printed text (parser_cs2.h:257)
@@ -18,7 +21,7 @@
 //   k_mf_pu_init, k_mf_pu_relax, k_mf_pu_apply   the price update: distances to the nodes with excess < 0, one thread per entry and an integer atomic min
 //                    per improvement, launched until a launch changes nothing; the distances are unique, so the order of the improvements does not matter.
 //   k_mf_lds         the whole solve by one workgroup between __syncthreads(), for networks of at most MF_LDS_NODES nodes and MF_LDS_ENTRIES entries; the same
-//                    rounds and price updates; the round budget is its loop bound.
+//                    rounds and price updates; the round budget is its loop bound.  64-bit prices only: its LDS does not double into a workgroup's share.
 //   k_mf_flows, k_mf_triples   flow per arc (lower + residual of the backward entry); the `from to flow` lines for k_cc_apply
 // No kernel waits for another workgroup; every loop is bounded by a list length, an argument or the round budget.
 // =============================================================================================
@@ -33,12 +36,35 @@ constexpr u32 MF_BATCH = 32;                                                    
 constexpr u32 MF_ACT = 0, MF_PUSHES = MF_BATCH, MF_RELABELS = MF_BATCH + 1, MF_FLAGS = MF_BATCH + 2, MF_MAXC = MF_BATCH + 3, MF_ROUNDS = MF_BATCH + 4, MF_PHASES = MF_BATCH + 5,
               MF_TTS = MF_BATCH + 6, MF_UPDATES = MF_BATCH + 7, MF_CTRS = MF_BATCH + 8;
 constexpr unsigned long long MF_F_BADARC = 1, MF_F_NAN = 2, MF_F_INFEASIBLE = 4, MF_F_RANGE = 8, MF_F_LIMIT = 16;
-constexpr long long MF_INF = 1ll << 62;
+constexpr long long MF_INF = 1ll << 62;                                                // the distance of a node that reaches no deficit; the bound of 64-bit prices
+typedef __int128 i128;
+template <class P> __host__ __device__ constexpr P mf_inf() { return (P)1 << (8 * sizeof(P) - 2); }      // the bound of the prices: 2^62, 2^126
 
-struct MfNet {                   // the sorted layout and the state of a solve
+struct MfNet {                   // the sorted layout and the state of a solve.  cost: scaled for 64-bit prices, unscaled for 128-bit ones (scale: the factor)
     const u32 *head, *sis, *tail, *start; const long long* cost; int* rcap;
-    long long *excess, *delta; u32 n, M;
+    long long *excess, *delta; u32 n, M; long long scale;
 };
+template <class P> __device__ __forceinline__ P mf_cost(const MfNet& N, u32 s) {
+    if constexpr (sizeof(P) == 16) return (P)N.cost[s] * (P)N.scale; else return N.cost[s];
+}
+__device__ __forceinline__ long long mf_shfl_down(long long x, int d) { return __shfl_down(x, d); }
+__device__ __forceinline__ i128 mf_shfl_down(i128 x, int d) {                          // as two 64-bit halves
+    const unsigned long long lo = __shfl_down((unsigned long long)x, d); const long long hi = __shfl_down((long long)(x >> 64), d);
+    return ((i128)hi << 64) | (i128)lo;
+}
+// the length of an entry in the price update, for cp >= 0: min(cp / eps + 1, cap), exactly.  capEps = cap * eps
+__device__ __forceinline__ long long mf_len(long long cp, long long eps, long long, long long cap) { const long long len = cp / eps + 1; return len > cap ? cap : len; }
+// 128 bits: at cap * eps or above the length is cap.  Below it the quotient is under cap < 2^36: a quotient of doubles (relative error below 2^-49, so off by
+// less than one) is within one of it, and the remainder says which way; two steps either way are allowed for.  q * eps <= cp + 2 eps: no overflow.
+__device__ __forceinline__ long long mf_len(i128 cp, i128 eps, i128 capEps, long long cap) {
+    if (cp >= capEps) return cap;
+    const double two64 = 18446744073709551616.0;
+    const double a = (double)(unsigned long long)(cp >> 64) * two64 + (double)(unsigned long long)cp, b = (double)(unsigned long long)(eps >> 64) * two64 + (double)(unsigned long long)eps;
+    long long q = (long long)(a / b);
+    i128 r = cp - (i128)q * eps;
+    for (int i = 0; i < 2; i++) { if (r < 0) { q--; r += eps; } else if (r >= eps) { q++; r -= eps; } }
+    return q + 1;                                                                      // (q < cap)
+}
 
 __global__ void k_mf_from_cc(const CcArc* __restrict__ in, u64 m, McfArc* out, unsigned long long* ctr) {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; if (i >= m) return;
@@ -84,11 +110,11 @@ __global__ void k_mf_starts(const u64* __restrict__ ks, u32 M, u32 n, u32* start
 
 __device__ __forceinline__ void mf_add(long long* p, long long x) { atomicAdd((unsigned long long*)p, (unsigned long long)x); }
 
-__global__ void k_mf_saturate(MfNet N, const long long* __restrict__ p) {
+template <class P> __global__ void k_mf_saturate(MfNet N, const P* __restrict__ p) {
     const u32 s = blockIdx.x * blockDim.x + threadIdx.x; if (s >= N.M) return;
     const int r = N.rcap[s]; if (r <= 0) return;
     const u32 v = N.tail[s], w = N.head[s];
-    if (N.cost[s] + p[v] - p[w] >= 0) return;
+    if (mf_cost<P>(N, s) + p[v] - p[w] >= 0) return;
     N.rcap[s] = 0; N.rcap[N.sis[s]] += r;                                              // (the sister's reduced cost is positive: its own thread leaves it alone)
     mf_add(&N.excess[v], -(long long)r); mf_add(&N.excess[w], (long long)r);
 }
@@ -106,7 +132,7 @@ __device__ __forceinline__ long long mf_block_scan(long long x, long long* wsum,
     *total = tot; return base + inc - x;
 }
 
-__global__ void __launch_bounds__(MF_BLOCK) k_mf_push(MfNet N, const long long* __restrict__ p, unsigned long long* ctr) {
+template <class P> __global__ void __launch_bounds__(MF_BLOCK) k_mf_push(MfNet N, const P* __restrict__ p, unsigned long long* ctr) {
     __shared__ u32 hv[MF_BLOCK]; __shared__ u32 nhv, sPush; __shared__ long long wsum[MF_BLOCK / 64];
     const u32 tid = threadIdx.x; const u64 v64 = (u64)blockIdx.x * MF_BLOCK + tid + 1;
     if (tid == 0) { nhv = 0; sPush = 0; }
@@ -118,11 +144,11 @@ __global__ void __launch_bounds__(MF_BLOCK) k_mf_push(MfNet N, const long long* 
             const u32 s0 = N.start[v], s1 = N.start[v + 1];
             if (s1 - s0 > MF_LANE_DEG) hv[atomicAdd(&nhv, 1u)] = v;
             else {
-                const long long pv = p[v];
+                const P pv = p[v];
                 for (u32 s = s0; s < s1 && e > 0; s++) {
                     const int r = N.rcap[s]; if (r <= 0) continue;
                     const u32 w = N.head[s];
-                    if (N.cost[s] + pv - p[w] >= 0) continue;
+                    if (mf_cost<P>(N, s) + pv - p[w] >= 0) continue;
                     const long long d = (long long)r < e ? (long long)r : e;
                     N.rcap[s] = r - (int)d; N.rcap[N.sis[s]] += (int)d;                // (only this node writes either: the sister is not admissible)
                     mf_add(&N.delta[w], d); e -= d; np++;
@@ -134,11 +160,11 @@ __global__ void __launch_bounds__(MF_BLOCK) k_mf_push(MfNet N, const long long* 
     __syncthreads();
     const u32 cnt = nhv;
     for (u32 k = 0; k < cnt; k++) {                                                    // the long lists of this workgroup's nodes, one after the other
-        const u32 v = hv[k]; const long long e = N.excess[v], pv = p[v]; const u32 s0 = N.start[v], s1 = N.start[v + 1];
+        const u32 v = hv[k]; const long long e = N.excess[v]; const P pv = p[v]; const u32 s0 = N.start[v], s1 = N.start[v + 1];
         long long carry = 0;
         for (u32 b = s0; b < s1 && carry < e; b += MF_BLOCK) {
             const u32 s = b + tid; long long amt = 0; u32 w = 0; int r = 0;
-            if (s < s1) { r = N.rcap[s]; if (r > 0) { w = N.head[s]; if (N.cost[s] + pv - p[w] < 0) amt = r; } }
+            if (s < s1) { r = N.rcap[s]; if (r > 0) { w = N.head[s]; if (mf_cost<P>(N, s) + pv - p[w] < 0) amt = r; } }
             long long tot; const long long ex = mf_block_scan(amt, wsum, &tot);
             const long long room = e - (carry + ex); long long d = amt < room ? amt : room; if (d < 0) d = 0;
             if (d > 0) { N.rcap[s] = r - (int)d; N.rcap[N.sis[s]] += (int)d; mf_add(&N.delta[w], d); np++; }
@@ -153,26 +179,26 @@ __global__ void __launch_bounds__(MF_BLOCK) k_mf_push(MfNet N, const long long* 
 }
 
 // act: the word that counts the nodes with excess > 0 of this round
-__global__ void __launch_bounds__(MF_BLOCK) k_mf_relabel(MfNet N, const long long* __restrict__ p, long long* pn, long long eps, long long floor, unsigned long long* act, unsigned long long* ctr) {
-    __shared__ u32 hv[MF_BLOCK]; __shared__ u32 nhv, sAct, sRel, sBad; __shared__ long long wbest[MF_BLOCK / 64]; __shared__ u32 wadm[MF_BLOCK / 64];
+template <class P> __global__ void __launch_bounds__(MF_BLOCK) k_mf_relabel(MfNet N, const P* __restrict__ p, P* pn, P eps, P floor, unsigned long long* act, unsigned long long* ctr) {
+    __shared__ u32 hv[MF_BLOCK]; __shared__ u32 nhv, sAct, sRel, sBad; __shared__ P wbest[MF_BLOCK / 64]; __shared__ u32 wadm[MF_BLOCK / 64];
     const u32 tid = threadIdx.x; const u64 v64 = (u64)blockIdx.x * MF_BLOCK + tid + 1;
     if (tid == 0) { nhv = 0; sAct = 0; sRel = 0; sBad = 0; }
     __syncthreads();
     if (v64 <= N.n) {
         const u32 v = (u32)v64; const long long dl = N.delta[v]; long long e = N.excess[v];
         if (dl) { e += dl; N.excess[v] = e; N.delta[v] = 0; }
-        long long pv = p[v];
+        P pv = p[v];
         if (e > 0) {
             atomicAdd(&sAct, 1u);
             const u32 s0 = N.start[v], s1 = N.start[v + 1];
             if (s1 - s0 > MF_LANE_DEG) hv[atomicAdd(&nhv, 1u)] = v;
             else {
-                bool adm = false; long long best = -MF_INF;
+                bool adm = false; P best = -mf_inf<P>();
                 for (u32 s = s0; s < s1; s++) {
                     if (N.rcap[s] <= 0) continue;
-                    const long long pw = p[N.head[s]], c = N.cost[s];
+                    const P pw = p[N.head[s]], c = mf_cost<P>(N, s);
                     if (c + pv - pw < 0) { adm = true; break; }
-                    const long long x = pw - c - eps; best = x > best ? x : best;
+                    const P x = pw - c - eps; best = x > best ? x : best;
                 }
                 if (!adm) { if (best < floor) atomicOr(&sBad, 1u); else { pv = best; atomicAdd(&sRel, 1u); } }
             }
@@ -182,20 +208,20 @@ __global__ void __launch_bounds__(MF_BLOCK) k_mf_relabel(MfNet N, const long lon
     __syncthreads();
     const u32 cnt = nhv;
     for (u32 k = 0; k < cnt; k++) {
-        const u32 v = hv[k]; const long long pv = p[v]; const u32 s0 = N.start[v], s1 = N.start[v + 1];
-        bool adm = false; long long best = -MF_INF;
+        const u32 v = hv[k]; const P pv = p[v]; const u32 s0 = N.start[v], s1 = N.start[v + 1];
+        bool adm = false; P best = -mf_inf<P>();
         for (u32 s = s0 + tid; s < s1; s += MF_BLOCK) {
             if (N.rcap[s] <= 0) continue;
-            const long long pw = p[N.head[s]], c = N.cost[s];
+            const P pw = p[N.head[s]], c = mf_cost<P>(N, s);
             if (c + pv - pw < 0) { adm = true; break; }
-            const long long x = pw - c - eps; best = x > best ? x : best;
+            const P x = pw - c - eps; best = x > best ? x : best;
         }
-        for (int d = 32; d >= 1; d >>= 1) { const long long t = __shfl_down(best, d); best = t > best ? t : best; }
+        for (int d = 32; d >= 1; d >>= 1) { const P t = mf_shfl_down(best, d); best = t > best ? t : best; }
         const u64 anyAdm = __ballot(adm);
         if ((tid & 63u) == 0) { wbest[tid >> 6] = best; wadm[tid >> 6] = anyAdm ? 1u : 0u; }
         __syncthreads();
         if (tid == 0) {
-            bool a = false; long long b = -MF_INF;
+            bool a = false; P b = -mf_inf<P>();
             for (u32 i = 0; i < MF_BLOCK / 64; i++) { a = a || wadm[i]; b = wbest[i] > b ? wbest[i] : b; }
             if (!a) { if (b < floor) sBad = 1u; else { pn[v] = b; sRel += 1u; } }
         }
@@ -214,15 +240,15 @@ __global__ void k_mf_pu_init(const long long* __restrict__ excess, u32 n, long l
     dist[v] = (v >= 1 && v <= n && excess[v] < 0) ? 0 : MF_INF;
 }
 // one pass over the entries; changed: the improvements of this launch
-__global__ void k_mf_pu_relax(MfNet N, const long long* __restrict__ p, long long eps, long long cap, long long* dist, unsigned long long* changed) {
+template <class P> __global__ void k_mf_pu_relax(MfNet N, const P* __restrict__ p, P eps, P capEps, long long cap, long long* dist, unsigned long long* changed) {
     const u32 s = blockIdx.x * blockDim.x + threadIdx.x;
     bool ch = false;
     if (s < N.M && N.rcap[s] > 0) {
         const u32 v = N.tail[s], w = N.head[s];
         const long long dw = dist[w];
         if (dw < cap) {
-            const long long cp = N.cost[s] + p[v] - p[w];
-            long long len = 0; if (cp >= 0) { len = cp / eps + 1; if (len > cap) len = cap; }
+            const P cp = mf_cost<P>(N, s) + p[v] - p[w];
+            long long len = 0; if (cp >= 0) len = mf_len(cp, eps, capEps, cap);
             const long long c = dw + len;
             if (c < dist[v]) { atomicMin((unsigned long long*)&dist[v], (unsigned long long)c); ch = true; }      // (distances are never negative)
         }
@@ -230,12 +256,12 @@ __global__ void k_mf_pu_relax(MfNet N, const long long* __restrict__ p, long lon
     const u64 m = __ballot(ch);
     if (lane_id() == 0 && m) atomicAdd(changed, (unsigned long long)__popcll(m));
 }
-__global__ void k_mf_pu_apply(const long long* __restrict__ excess, const long long* __restrict__ dist, u32 n, long long eps, long long cap, long long* p, unsigned long long* ctr) {
+template <class P> __global__ void k_mf_pu_apply(const long long* __restrict__ excess, const long long* __restrict__ dist, u32 n, P eps, long long cap, P* p, unsigned long long* ctr) {
     const u64 v = (u64)blockIdx.x * blockDim.x + threadIdx.x; if (v < 1 || v > n) return;
     long long d = dist[v];
     if (d >= MF_INF && excess[v] > 0) atomicOr(&ctr[MF_FLAGS], MF_F_INFEASIBLE);       // excess that reaches no deficit
     if (d > cap) d = cap;
-    p[v] -= eps * d;
+    p[v] -= eps * (P)d;
 }
 
 // ---- the single-workgroup form

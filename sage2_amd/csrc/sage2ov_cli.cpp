@@ -180,7 +180,7 @@ int main(int argc, char* argv[]) {
                 ctx.check(sage2ov_flow_solution_commit(ctx.get()));
                 ctx.check(sage2ov_copycount_stats_get(ctx.get(), &cs));
                 logStream << "\tMin-cost flow: " << ms.nodes << " nodes, " << ms.arcs << " arcs, cost " << ms.total_cost << "; " << ms.phases << " phases, " << ms.rounds << " rounds, "
-                          << ms.pushes << " pushes, " << ms.relabels << " relabels, " << ms.price_updates << " price updates in " << (ms.build_ms + ms.solve_ms) / 1000.0 << " sec.\n"
+                          << ms.pushes << " pushes, " << ms.relabels << " relabels, " << ms.price_updates << " price updates, " << 64 * ms.price_words << "-bit prices, in "<< (ms.build_ms + ms.solve_ms) / 1000.0 << " sec.\n"
                           << "\t         Flow from T to S: " << cs.t_to_s_flow << "\n\t  Flow different in edges: " << cs.flow_different << "\n";
                 ctx.check(sage2ov_graph5_save(ctx.get(), (outputDir + prefixName + ".graph5").c_str()));
                 logStream << "\t" << prefixName << ".graph5 written\n";

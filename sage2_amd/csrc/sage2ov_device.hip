@@ -3196,8 +3196,8 @@ int dev_contigs_spell_wait(Device* d, int which, const char** image, double* ms,
 struct CopyCount {
     unsigned short* freq = nullptr; unsigned long long* kPair = nullptr; u64 present = 0;      // of dev_copycount_prepare
     u32 *adj = nullptr, *hp = nullptr, *nodeOf = nullptr; CcArc* arcs = nullptr; u64 F = 0, E = 0, nArcs = 0; bool net = false;      // of dev_flownet_build
-    long long *solFlow = nullptr, *solPrice = nullptr; u64 solScale = 0; bool solved = false;      // of dev_flow_solve: a flow per arc, a price per network node (words 1..n of n + 2)
-    void drop_solution() { hipFree(solFlow); hipFree(solPrice); solFlow = solPrice = nullptr; solScale = 0; solved = false; }
+    long long* solFlow = nullptr; void* solPrice = nullptr; u32 solWords = 0; u64 solScale = 0; bool solved = false;      // of dev_flow_solve: a flow per arc, a price of solWords 64-bit words per network node (nodes 1..n of n + 2)
+    void drop_solution() { hipFree(solFlow); hipFree(solPrice); solFlow = nullptr; solPrice = nullptr; solWords = 0; solScale = 0; solved = false; }
     void drop_net() { drop_solution(); hipFree(adj); hipFree(hp); hipFree(nodeOf); hipFree(arcs); adj = hp = nodeOf = nullptr; arcs = nullptr; F = E = nArcs = 0; net = false; }
     ~CopyCount() { drop_net(); hipFree(freq); hipFree(kPair); }
 };
@@ -3394,29 +3394,35 @@ int dev_flow_get(Device* d, float* flow, uint64_t n, std::string& err) {
 // step 5's solver (kernels_flow.inc; main_cs2, copycountEstimator.cpp:359)
 // =============================================================================================
 static int mcf_nomem(std::string& err) { err = "min-cost flow: out of device memory"; return SAGE2OV_ERR_NOMEM; }
-// the epsilon of every phase, and whether the lowest price the phases can reach -- with room for one reduced cost -- stays inside +-2^62
-static bool mcf_phases(u64 scale, u64 maxc, long long* cmaxOut, std::vector<long long>& eps) {
-    const unsigned __int128 lim = (unsigned __int128)1 << 62;
+// the epsilon of every phase, and whether the lowest price the phases can reach -- with room for one reduced cost -- stays inside +-2^62 (P = long long) or
+// +-2^126 (P = __int128).  Nothing here wraps in 128 unsigned bits: scale < 2^32 and maxc <= 2^63, so cmax < 2^95; cmax is then held against lim / ((1 + alpha) *
+// scale) before the first product, so that every term (1 + alpha) * scale * e, e <= cmax, is at most lim <= 2^126; the sum is below lim before a term is added, so
+// below 2^127 after it; and floor + 2 cmax + 1 < 2^126 + 2^96 + 1.
+template <class P> static bool mcf_phases(u64 scale, u64 maxc, P* cmaxOut, std::vector<P>& eps) {
+    const unsigned __int128 lim = (unsigned __int128)mf_inf<P>(), step = (unsigned __int128)(1 + MF_ALPHA) * scale;
     unsigned __int128 cmax = (unsigned __int128)scale * maxc; if (cmax < 1) cmax = 1;
-    if (cmax >= lim) return false;
+    if (cmax >= lim || cmax > lim / step) return false;                                // (beyond lim / step the first term alone passes lim)
     unsigned __int128 floor = 0;
-    for (long long e = (long long)cmax;;) { eps.push_back(e); floor += (unsigned __int128)(1 + MF_ALPHA) * scale * (unsigned __int128)e; if (floor >= lim) return false; if (e == 1) break; e = std::max<long long>(1, e / MF_ALPHA); }
+    for (P e = (P)cmax;;) { eps.push_back(e); floor += step * (unsigned __int128)e; if (floor >= lim) return false; if (e == 1) break; e = std::max<P>(1, e / MF_ALPHA); }
     if (floor + 2 * cmax + 1 >= lim) return false;
-    *cmaxOut = (long long)cmax;
+    *cmaxOut = (P)cmax;
     return true;
 }
+bool mcf_wide_guard(uint64_t n, uint64_t maxc) { i128 c; std::vector<i128> e; return mcf_phases<i128>(n + 1, maxc, &c, e); }
 static int mcf_flag_error(unsigned long long flags, std::string& err) {
     if (flags & MF_F_NAN) { err = "min-cost flow: a cost that is no number"; return SAGE2OV_ERR_ARG; }
     if (flags & MF_F_BADARC) { err = "min-cost flow: a bad arc (from == to, a node number outside 1..n, lower > upper or a negative bound)"; return SAGE2OV_ERR_ARG; }
-    if (flags & MF_F_RANGE) { err = "min-cost flow: costs and prices beyond the 64-bit range of the method"; return SAGE2OV_ERR_LIMIT; }
+    if (flags & MF_F_RANGE) { err = "min-cost flow: costs and prices beyond the range of the method's integers"; return SAGE2OV_ERR_LIMIT; }
     if (flags & MF_F_INFEASIBLE) { err = "min-cost flow: the network is infeasible (excess that no residual path can carry to a deficit)"; return SAGE2OV_ERR_ARG; }
     if (flags & MF_F_LIMIT) { err = "min-cost flow: the round budget is spent"; return SAGE2OV_ERR_LIMIT; }
     return 0;
 }
 // dArcs: m records in device memory.  On success *flowOut (m words) and *priceOut (n + 2 words, node v at word v) are allocations the caller frees; on any
-// error nothing is handed out.  st is filled as far as the solve got.
-static int mcf_solve_device(Device* d, const McfArc* dArcs, u64 m, u32 n, u64 maxRounds, long long** flowOut, long long** priceOut, McfStats* st, std::string& err) {
-    *flowOut = nullptr; *priceOut = nullptr;
+// error nothing is handed out.  st is filled as far as the solve got.  P: the price type (kernels_flow.inc); *range: the failure was P's range -- the guard before
+// the layout or the one before a price update -- and nothing else.
+template <class P> static int mcf_solve_device(Device* d, const McfArc* dArcs, u64 m, u32 n, u64 maxRounds, long long** flowOut, P** priceOut, McfStats* st, bool* range, std::string& err) {
+    constexpr bool wide = sizeof(P) == 16;
+    *flowOut = nullptr; *priceOut = nullptr; *range = false; *st = McfStats(); st->priceWords = wide ? 2 : 1;
     if (m >= (1ull << 31) - RS_TILE) { err = "min-cost flow: 2^31 - 2048 arcs or more"; return SAGE2OV_ERR_LIMIT; }
     if (n >= 0xFFFFFFF0u) { err = "min-cost flow: too many nodes"; return SAGE2OV_ERR_LIMIT; }
     if (!maxRounds) maxRounds = SAGE2OV_MCF_DEFAULT_ROUNDS;
@@ -3431,78 +3437,83 @@ static int mcf_solve_device(Device* d, const McfArc* dArcs, u64 m, u32 n, u64 ma
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(hc, ctr, sizeof hc, hipMemcpyDeviceToHost, sm)); HIPCHK(hipStreamSynchronize(sm));
     { const int rc = mcf_flag_error(hc[MF_FLAGS], err); if (rc) return rc; }
-    long long cmax = 1; std::vector<long long> epsList;
-    if (!mcf_phases(scale, hc[MF_MAXC], &cmax, epsList)) { err = "min-cost flow: (n + 1) * max |cost| and the price range of the method do not fit 64 bits"; return SAGE2OV_ERR_LIMIT; }
+    P cmax = 1; std::vector<P> epsList;
+    if (!mcf_phases<P>(scale, hc[MF_MAXC], &cmax, epsList)) {
+        *range = true; err = wide ? "min-cost flow: (n + 1) * max |cost| and the price range of the method do not fit 128 bits" : "min-cost flow: (n + 1) * max |cost| and the price range of the method do not fit 64 bits";
+        return SAGE2OV_ERR_LIMIT;
+    }
     // ---- the layout
     long long* excess = B.get<long long>((u64)n + 2); long long* delta = B.get<long long>((u64)n + 2); long long* dist = B.get<long long>((u64)n + 2);
-    long long* price[2] = {(long long*)DevTmp::alloc(((u64)n + 2) * sizeof(long long)), B.get<long long>((u64)n + 2)};
+    P* price[2] = {(P*)DevTmp::alloc(((u64)n + 2) * sizeof(P)), B.get<P>((u64)n + 2)};                      // (device allocations are aligned to 256 bytes: a 128-bit price is one load)
     struct Free { void* p; ~Free() { hipFree(p); } } fp0{price[0]};                   // handed out on success only
     long long* flow = (long long*)DevTmp::alloc(std::max<u64>(m, 1) * sizeof(long long)); Free ff{flow};
     u32* head = B.get<u32>(M); u32* sis = B.get<u32>(M); u32* tail = B.get<u32>(M); u32* start = B.get<u32>((u64)n + 3); u32* pos = B.get<u32>(M);
     long long* cost = B.get<long long>(M); int* rcap = B.get<int>(M); u64* key = B.get<u64>(M);
     if (!excess || !delta || !dist || !price[0] || !price[1] || !flow || !head || !sis || !tail || !start || !pos || !cost || !rcap || !key) return mcf_nomem(err);
     HIPCHK(hipMemsetAsync(excess, 0, ((u64)n + 2) * sizeof(long long), sm)); HIPCHK(hipMemsetAsync(delta, 0, ((u64)n + 2) * sizeof(long long), sm));
-    HIPCHK(hipMemsetAsync(price[0], 0, ((u64)n + 2) * sizeof(long long), sm)); HIPCHK(hipMemsetAsync(price[1], 0, ((u64)n + 2) * sizeof(long long), sm));
+    HIPCHK(hipMemsetAsync(price[0], 0, ((u64)n + 2) * sizeof(P), sm)); HIPCHK(hipMemsetAsync(price[1], 0, ((u64)n + 2) * sizeof(P), sm));
     if (m) {
         hipLaunchKernelGGL(k_mf_keys, dim3(grid_for(m, 256)), b256, 0, sm, dArcs, m, key, excess);
         int shifts[4]; const int np = copycount_passes(n, shifts);
         u64* ks = nullptr; u32* idx = nullptr; MateStats ms;
         { const int rc = mate_sort(d, B, key, M, shifts, np, &ks, &idx, &ms, err); if (rc) return rc; }
         hipLaunchKernelGGL(k_mf_pos, dim3(grid_for(M, 256)), b256, 0, sm, idx, M, pos);
-        hipLaunchKernelGGL(k_mf_entries, dim3(grid_for(M, 256)), b256, 0, sm, dArcs, idx, pos, ks, M, (long long)scale, head, sis, tail, cost, rcap);
+        hipLaunchKernelGGL(k_mf_entries, dim3(grid_for(M, 256)), b256, 0, sm, dArcs, idx, pos, ks, M, wide ? 1ll : (long long)scale, head, sis, tail, cost, rcap);      // (128-bit prices: the entries keep the unscaled cost)
         hipLaunchKernelGGL(k_mf_starts, dim3(grid_for((u64)n + 2, 256)), b256, 0, sm, ks, M, n, start);
     } else HIPCHK(hipMemsetAsync(start, 0, ((u64)n + 3) * sizeof(u32), sm));
     HIPCHK(hipGetLastError());
     HIPCHK(lap.stop(st->build_ms));
-    const MfNet N = {head, sis, tail, start, cost, rcap, excess, delta, n, M};
+    const MfNet N = {head, sis, tail, start, cost, rcap, excess, delta, n, M, (long long)scale};
     const u32 nodeGrid = grid_for(n, MF_BLOCK), entryGrid = grid_for(M, 256);
     // (SAGE2OV_TEST_MCF_LDS=0: tests only -- a network that fits the single-workgroup form takes the launches all the same)
-    const bool lds = m && n <= MF_LDS_NODES && M <= MF_LDS_ENTRIES && d->opt.num("SAGE2OV_TEST_MCF_LDS", 1) != 0;
+    bool lds = false;
+    if constexpr (!wide) lds = m && n <= MF_LDS_NODES && M <= MF_LDS_ENTRIES && d->opt.num("SAGE2OV_TEST_MCF_LDS", 1) != 0;
     st->form = lds ? SAGE2OV_MCF_FORM_LDS : SAGE2OV_MCF_FORM_LAUNCHES;
     u32 cur = 0; unsigned long long flags = 0;
     HIPCHK(lap.start());
-    if (lds) {
+    if constexpr (!wide) if (lds) {
         const MfLdsArgs A = {cmax, (long long)scale, maxRounds, MF_PERIOD};
         hipLaunchKernelGGL(k_mf_lds, dim3(1), dim3(MF_BLOCK), 0, sm, N, price[0], A, ctr);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(hc, ctr, sizeof hc, hipMemcpyDeviceToHost, sm)); HIPCHK(hipStreamSynchronize(sm));
         st->phases = hc[MF_PHASES]; st->rounds = hc[MF_ROUNDS]; st->pushes = hc[MF_PUSHES]; st->relabels = hc[MF_RELABELS]; st->updates = hc[MF_UPDATES]; flags = hc[MF_FLAGS];
-    } else if (m) {
+    }
+    if (!lds && m) {
         const long long cap = (long long)(1 + MF_ALPHA) * (long long)scale;
-        long long floor = 0; u64 rounds = 0, updates = 0;
+        P floor = 0; u64 rounds = 0, updates = 0;
         hipEvent_t e0 = nullptr, e1 = nullptr; HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
         struct Ev { hipEvent_t a, b; ~Ev() { hipEventDestroy(a); hipEventDestroy(b); } } evs{e0, e1};
         for (size_t ph = 0; ph < epsList.size() && !flags; ph++) {
-            const long long eps = epsList[ph];
-            floor -= cap * eps; st->phases++;
+            const P eps = epsList[ph], capEps = (P)cap * eps;                           // (below the bound: mcf_phases)
+            floor -= capEps; st->phases++;
             const u64 r0 = rounds;
             HIPCHK(hipEventRecord(e0, sm));
-            hipLaunchKernelGGL(k_mf_saturate, dim3(entryGrid), b256, 0, sm, N, price[cur]);
+            hipLaunchKernelGGL(k_mf_saturate<P>, dim3(entryGrid), b256, 0, sm, N, (const P*)price[cur]);
             u64 since = MF_PERIOD;
             for (bool done = false; !done && !flags;) {
                 const u64 left = maxRounds - rounds;
                 if (!left) { flags |= MF_F_LIMIT; break; }
                 if (since >= MF_PERIOD) {                                               // the price update: relax until a launch improves nothing
-                    since = 0; floor -= cap * eps;
-                    if (floor < -(MF_INF - 2 * cmax - 1)) { flags |= MF_F_RANGE; break; }
+                    since = 0; floor -= capEps;                                         // (the floor was above -bound, capEps is below bound: no wrap)
+                    if (floor < -(mf_inf<P>() - 2 * cmax - 1)) { flags |= MF_F_RANGE; *range = true; break; }
                     hipLaunchKernelGGL(k_mf_pu_init, dim3(grid_for((u64)n + 2, 256)), b256, 0, sm, excess, n, dist);
                     bool settled = false;
                     for (u64 it = 0; it <= (u64)n + MF_BATCH && !settled; it += MF_BATCH) {      // (a shortest path has at most n - 1 entries)
                         HIPCHK(hipMemsetAsync(ctr + MF_ACT, 0, MF_BATCH * sizeof(unsigned long long), sm));
-                        for (u32 k = 0; k < MF_BATCH; k++) hipLaunchKernelGGL(k_mf_pu_relax, dim3(entryGrid), b256, 0, sm, N, price[cur], eps, cap, dist, ctr + MF_ACT + k);
+                        for (u32 k = 0; k < MF_BATCH; k++) hipLaunchKernelGGL(k_mf_pu_relax<P>, dim3(entryGrid), b256, 0, sm, N, (const P*)price[cur], eps, capEps, cap, dist, ctr + MF_ACT + k);
                         HIPCHK(hipGetLastError());
                         HIPCHK(hipMemcpyAsync(hc, ctr, MF_BATCH * sizeof(unsigned long long), hipMemcpyDeviceToHost, sm)); HIPCHK(hipStreamSynchronize(sm));
                         for (u32 k = 0; k < MF_BATCH; k++) if (!hc[MF_ACT + k]) settled = true;
                     }
                     if (!settled) { err = "min-cost flow: the price update did not settle"; return SAGE2OV_ERR_INTERNAL; }
-                    hipLaunchKernelGGL(k_mf_pu_apply, dim3(grid_for((u64)n + 1, 256)), b256, 0, sm, excess, dist, n, eps, cap, price[cur], ctr);
+                    hipLaunchKernelGGL(k_mf_pu_apply<P>, dim3(grid_for((u64)n + 1, 256)), b256, 0, sm, (const long long*)excess, (const long long*)dist, n, eps, cap, price[cur], ctr);
                     updates++;
                 }
                 const u32 K = (u32)std::min<u64>(MF_BATCH, left);
                 HIPCHK(hipMemsetAsync(ctr + MF_ACT, 0, MF_BATCH * sizeof(unsigned long long), sm));
                 for (u32 k = 0; k < K; k++) {
-                    hipLaunchKernelGGL(k_mf_push, dim3(nodeGrid), dim3(MF_BLOCK), 0, sm, N, price[cur], ctr);
-                    hipLaunchKernelGGL(k_mf_relabel, dim3(nodeGrid), dim3(MF_BLOCK), 0, sm, N, price[cur], price[cur ^ 1u], eps, floor, ctr + MF_ACT + k, ctr);
+                    hipLaunchKernelGGL(k_mf_push<P>, dim3(nodeGrid), dim3(MF_BLOCK), 0, sm, N, (const P*)price[cur], ctr);
+                    hipLaunchKernelGGL(k_mf_relabel<P>, dim3(nodeGrid), dim3(MF_BLOCK), 0, sm, N, (const P*)price[cur], price[cur ^ 1u], eps, floor, ctr + MF_ACT + k, ctr);
                     cur ^= 1u;
                 }
                 HIPCHK(hipGetLastError());
@@ -3521,26 +3532,30 @@ static int mcf_solve_device(Device* d, const McfArc* dArcs, u64 m, u32 n, u64 ma
     { const int rc = mcf_flag_error(flags, err); if (rc) return rc; }
     if (m) hipLaunchKernelGGL(k_mf_flows, dim3(grid_for(m, 256)), b256, 0, sm, dArcs, pos, rcap, m, flow);
     HIPCHK(hipGetLastError());
-    if (cur == 1) HIPCHK(hipMemcpyAsync(price[0], price[1], ((u64)n + 2) * sizeof(long long), hipMemcpyDeviceToDevice, sm));
+    if (cur == 1) HIPCHK(hipMemcpyAsync(price[0], price[1], ((u64)n + 2) * sizeof(P), hipMemcpyDeviceToDevice, sm));
     HIPCHK(hipStreamSynchronize(sm));
     *flowOut = flow; *priceOut = price[0]; ff.p = nullptr; fp0.p = nullptr;
     return 0;
 }
-int dev_mcf_solve(Device* d, const void* arcs, uint64_t m, uint32_t n, uint64_t maxRounds, int64_t* flow, int64_t* price, McfStats* st, std::string& err) {
+// price: n words, or 2 n with wide (a node's low word first), or null
+int dev_mcf_solve(Device* d, const void* arcs, uint64_t m, uint32_t n, uint64_t maxRounds, bool wide, int64_t* flow, void* price, McfStats* st, std::string& err) {
     HIPCHK(hipSetDevice(d->ordinal));
     static_assert(sizeof(McfArc) == 24, "an arc is 24 bytes");
     DevTmp B; McfArc* dA = B.get<McfArc>(m); if (!dA) return mcf_nomem(err);
     if (m) HIPCHK(hipMemcpyAsync(dA, arcs, m * sizeof(McfArc), hipMemcpyHostToDevice, d->stream));
-    long long *dF = nullptr, *dP = nullptr;
-    { const int rc = mcf_solve_device(d, dA, m, n, maxRounds, &dF, &dP, st, err); if (rc) return rc; }
+    long long* dF = nullptr; void* dP = nullptr; bool range = false; const size_t w = wide ? sizeof(i128) : sizeof(long long);
+    if (wide) { i128* q = nullptr; const int rc = mcf_solve_device<i128>(d, dA, m, n, maxRounds, &dF, &q, st, &range, err); if (rc) return rc; dP = q; }
+    else { long long* q = nullptr; const int rc = mcf_solve_device<long long>(d, dA, m, n, maxRounds, &dF, &q, st, &range, err); if (rc) return rc; dP = q; }
     hipError_t e = hipSuccess;
     if (m) e = hipMemcpy(flow, dF, m * sizeof(long long), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && price && n) e = hipMemcpy(price, dP + 1, (u64)n * sizeof(long long), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && price && n) e = hipMemcpy(price, (const char*)dP + w, (u64)n * w, hipMemcpyDeviceToHost);
     hipFree(dF); hipFree(dP);
     HIPCHK(e);
     return 0;
 }
-// the resident network of dev_flownet_build; the earlier solution stays unless this one succeeds
+// the resident network of dev_flownet_build; the earlier solution stays unless this one succeeds.  64-bit prices where their guard admits the network, 128-bit ones
+// where it does not, and from the start again where a 64-bit solve met the guard on the way (nothing was applied; the statistics are the second solve's).
+// SAGE2OV_TEST_MCF_WIDE (tests only): 0 never wide, 1 always
 int dev_flow_solve(Device* d, uint64_t maxRounds, McfStats* st, std::string& err) {
     HIPCHK(hipSetDevice(d->ordinal));
     CopyCount* S = (CopyCount*)d->copycount;
@@ -3552,18 +3567,23 @@ int dev_flow_solve(Device* d, uint64_t maxRounds, McfStats* st, std::string& err
     HIPCHK(hipGetLastError());
     unsigned long long fl = 0; HIPCHK(hipMemcpyAsync(&fl, ctr + MF_FLAGS, sizeof fl, hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
     { const int rc = mcf_flag_error(fl, err); if (rc) return rc; }
-    long long *dF = nullptr, *dP = nullptr;
-    { const int rc = mcf_solve_device(d, dA, m, (u32)nn, maxRounds, &dF, &dP, st, err); if (rc) return rc; }
-    S->drop_solution(); S->solFlow = dF; S->solPrice = dP; S->solScale = nn + 1; S->solved = true;
+    const long long mode = d->opt.num("SAGE2OV_TEST_MCF_WIDE", -1);
+    long long* dF = nullptr; void* dP = nullptr; u32 words = 1; bool range = false; int rc = 0;
+    if (mode != 1) { long long* q = nullptr; rc = mcf_solve_device<long long>(d, dA, m, (u32)nn, maxRounds, &dF, &q, st, &range, err); dP = q; }
+    if (mode == 1 || (rc && range && mode != 0)) { i128* q = nullptr; words = 2; rc = mcf_solve_device<i128>(d, dA, m, (u32)nn, maxRounds, &dF, &q, st, &range, err); dP = q; }
+    if (rc) return rc;
+    S->drop_solution(); S->solFlow = dF; S->solPrice = dP; S->solWords = words; S->solScale = nn + 1; S->solved = true;
     return 0;
 }
 bool dev_flow_solved(Device* d) { const CopyCount* S = (const CopyCount*)d->copycount; return S && S->net && S->solved; }
-// flow: one word per arc; price: one per network node (either may be null)
-int dev_flow_solution_get(Device* d, int64_t* flow, int64_t* price, std::string& err) {
+uint32_t dev_flow_price_words(Device* d) { const CopyCount* S = (const CopyCount*)d->copycount; return S && S->net && S->solved ? S->solWords : 0; }
+// flow: one word per arc; price: dev_flow_price_words() words per network node (either may be null)
+int dev_flow_solution_get(Device* d, int64_t* flow, void* price, std::string& err) {
     HIPCHK(hipSetDevice(d->ordinal));
     const CopyCount* S = (const CopyCount*)d->copycount; if (!S || !S->net || !S->solved) { err = "flow solution: none"; return SAGE2OV_ERR_ARG; }
     if (flow) HIPCHK(hipMemcpy(flow, S->solFlow, S->nArcs * sizeof(long long), hipMemcpyDeviceToHost));
-    if (price) HIPCHK(hipMemcpy(price, S->solPrice + 1, (4 * S->E + 2) * sizeof(long long), hipMemcpyDeviceToHost));
+    const size_t w = S->solWords * sizeof(long long);
+    if (price) HIPCHK(hipMemcpy(price, (const char*)S->solPrice + w, (4 * S->E + 2) * w, hipMemcpyDeviceToHost));
     return 0;
 }
 // the resident flows through k_cc_apply / k_cc_average: the lines are made on the device and never leave it.  *tts: the flow of the `2 1` arc

@@ -2224,7 +2224,7 @@ namespace {
 void mcf_stats_set(sage2ov_ctx* c, const McfStats& s) {
     sage2ov_mcf_stats o{};
     o.nodes = s.nodes; o.arcs = s.arcs; o.scale = s.scale; o.phases = s.phases; o.rounds = s.rounds; o.pushes = s.pushes; o.relabels = s.relabels; o.price_updates = s.updates;
-    o.form = s.form; o.build_ms = s.build_ms; o.solve_ms = s.solve_ms;
+    o.form = s.form; o.price_words = s.priceWords; o.build_ms = s.build_ms; o.solve_ms = s.solve_ms;
     for (int i = 0; i < SAGE2OV_MCF_PHASES; i++) { o.refine_rounds[i] = s.refine_rounds[i]; o.refine_ms[i] = s.refine_ms[i]; }
     c->mcfstats = o;
 }
@@ -2245,10 +2245,28 @@ int sage2ov_mcf_solve(sage2ov_ctx* c, uint64_t n, const sage2ov_mcf_arc* arcs, u
     if (!c->device()) return c->fail(SAGE2OV_ERR_DEVICE, c->gpu() ? c->devErr : "sage2ov_mcf_solve: this context has no GPU");
     if (n >= 0xFFFFFFF0ull) return c->fail(SAGE2OV_ERR_LIMIT, "sage2ov_mcf_solve: too many nodes");
     McfStats s;
-    const int rc = dev_mcf_solve(c->device(), arcs, m, (uint32_t)n, max_rounds, flow, price, &s, c->err);
+    const int rc = dev_mcf_solve(c->device(), arcs, m, (uint32_t)n, max_rounds, false, flow, price, &s, c->err);
     mcf_stats_set(c, s);
     int out = rc;
     if (!rc && !mcf_total_cost(flow, m, [&](uint64_t i) { return arcs[i].cost; }, &c->mcfstats.total_cost)) out = c->fail(SAGE2OV_ERR_LIMIT, "sage2ov_mcf_solve: the total cost does not fit 64 bits");
+    if (stats) *stats = c->mcfstats;
+    return out;
+}
+int sage2ov_mcf_solve_wide(sage2ov_ctx* c, uint64_t n, const sage2ov_mcf_arc* arcs, uint64_t m, uint64_t max_rounds, int64_t* flow, uint64_t* price, sage2ov_mcf_stats* stats) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    if (m && (!arcs || !flow)) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_mcf_solve_wide: null argument");
+    if (n >= 0xFFFFFFF0ull) return c->fail(SAGE2OV_ERR_LIMIT, "sage2ov_mcf_solve_wide: too many nodes");
+    // the guard on the host's copy of the costs, before the device is touched (the solve holds the device's maximum against it again)
+    uint64_t maxc = 0;
+    for (uint64_t i = 0; i < m; i++) maxc = std::max<uint64_t>(maxc, arcs[i].cost < 0 ? 0ull - (uint64_t)arcs[i].cost : (uint64_t)arcs[i].cost);
+    McfStats s; s.nodes = n; s.arcs = m; s.scale = n + 1; s.priceWords = 2;
+    int rc = 0;
+    if (!mcf_wide_guard(n, maxc)) rc = c->fail(SAGE2OV_ERR_LIMIT, "min-cost flow: (n + 1) * max |cost| and the price range of the method do not fit 128 bits");
+    else if (!c->device()) rc = c->fail(SAGE2OV_ERR_DEVICE, c->gpu() ? c->devErr : "sage2ov_mcf_solve_wide: this context has no GPU");
+    else rc = dev_mcf_solve(c->device(), arcs, m, (uint32_t)n, max_rounds, true, flow, price, &s, c->err);
+    mcf_stats_set(c, s);
+    int out = rc;
+    if (!rc && !mcf_total_cost(flow, m, [&](uint64_t i) { return arcs[i].cost; }, &c->mcfstats.total_cost)) out = c->fail(SAGE2OV_ERR_LIMIT, "sage2ov_mcf_solve_wide: the total cost does not fit 64 bits");
     if (stats) *stats = c->mcfstats;
     return out;
 }
@@ -2275,8 +2293,22 @@ int sage2ov_flow_solution_export(sage2ov_ctx* c, int64_t* flow, uint64_t cap_flo
     { const int rc = copycount_check(c, "sage2ov_flow_solution_export"); if (rc) return rc; }
     if (!c->netValid || !dev_flow_solved(c->device())) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_flow_solution_export: no solution of the present network (sage2ov_flow_solve)");
     if ((flow && cap_flow < c->ccstats.network_arcs) || (price && cap_price < c->ccstats.network_nodes)) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_flow_solution_export: a buffer is too small");
+    if (price && dev_flow_price_words(c->device()) != 1) return c->fail(SAGE2OV_ERR_LIMIT, "sage2ov_flow_solution_export: the solution has 128-bit prices (sage2ov_flow_solution_export_wide)");
     if (scale) *scale = c->ccstats.network_nodes + 1;
     return dev_flow_solution_get(c->device(), flow, price, c->err);
+}
+int sage2ov_flow_solution_export_wide(sage2ov_ctx* c, int64_t* flow, uint64_t cap_flow, uint64_t* price, uint64_t cap_price, uint64_t* scale) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    { const int rc = copycount_check(c, "sage2ov_flow_solution_export_wide"); if (rc) return rc; }
+    if (!c->netValid || !dev_flow_solved(c->device())) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_flow_solution_export_wide: no solution of the present network (sage2ov_flow_solve)");
+    const uint64_t nn = c->ccstats.network_nodes;
+    if ((flow && cap_flow < c->ccstats.network_arcs) || (price && cap_price < nn)) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_flow_solution_export_wide: a buffer is too small");
+    if (scale) *scale = nn + 1;
+    if (!price || dev_flow_price_words(c->device()) == 2) return dev_flow_solution_get(c->device(), flow, price, c->err);
+    std::vector<int64_t> p(nn);                                                        // 64-bit prices: sign-extended
+    { const int rc = dev_flow_solution_get(c->device(), flow, p.data(), c->err); if (rc) return rc; }
+    for (uint64_t v = 0; v < nn; v++) { price[2 * v] = (uint64_t)p[v]; price[2 * v + 1] = p[v] < 0 ? ~0ull : 0ull; }
+    return SAGE2OV_OK;
 }
 int sage2ov_flow_solution_save(sage2ov_ctx* c, const char* path) {
     if (!c || !path) return SAGE2OV_ERR_ARG;
