@@ -164,6 +164,23 @@ typedef struct sage2ov_mate_stats {
 #define SAGE2OV_MATE_ROUTE_HOST   0u
 #define SAGE2OV_MATE_ROUTE_DEVICE 1u
 int sage2ov_mates_stats_get(const sage2ov_ctx* ctx, sage2ov_mate_stats* out);   /* of the last add call */
+/* The mate table of the reads a context organised, without a second pass over the input: step 1 already knows the id and the orientation of
+ * every read it staged, and with pairing on the context also remembers which input record each staged read was.
+ * sage2ov_reads_pair_library: 0 switches pairing off (the default: step 1 then does exactly what it does without this call); 1 .. 127 makes every later
+ *   sage2ov_reads_add_ascii / sage2ov_reads_add_file call ALSO one mates call for that library, by the rules above: the call's records are numbered 0 .. n-1 in
+ *   input order (two files: alternating, file 1 first), its pairs are (2j, 2j+1), a trailing odd record is dropped, pairs never span two calls.  With pairing on
+ *   sage2ov_reads_add_list numbers its datasets itself, dataset i is library i as in sage2ov_mates_add_list (the value given here only has to be non-zero; more
+ *   than 127 datasets: SAGE2OV_ERR_ARG).  A call of 2^32 - 2048 input records or more with pairing on: SAGE2OV_ERR_LIMIT.  After sage2ov_reads_organize, or a
+ *   library outside 0 .. 127: SAGE2OV_ERR_ARG.  sage2ov_reads_add_synth is never a mates call.
+ * sage2ov_mates_from_reads: adds to the mate tables exactly what the matching sequence of sage2ov_mates_add_* calls would add at that moment -- every entry of
+ *   every library field for field, `first` continuing from whatever earlier add calls left, sage2ov_mate_stats as after the last of those calls with
+ *   pairs_not_found 0 by construction (a good read is always in the store it was organised into).  Needs organised reads that were staged with pairing on, else
+ *   SAGE2OV_ERR_ARG and nothing changes; once per organised read set (a second call: SAGE2OV_ERR_ARG).  It reads neither the input nor the read store, so it works
+ *   at any point after sage2ov_reads_organize, memory-diet mode after an index build included.  What pairing remembers (4 bytes per staged read on the host until
+ *   the organiser has run, 4 bytes per staged read -- per input record on the ASCII route of a GPU context -- on the device after it) is released by this call, by
+ *   sage2ov_mates_clear and with the read set. */
+int sage2ov_reads_pair_library(sage2ov_ctx* ctx, int library);
+int sage2ov_mates_from_reads(sage2ov_ctx* ctx);
 
 /* ---- STEP 2: HashTable (economyGraph/hashTable.h:20-43) ---- */
 typedef struct sage2ov_index_stats {

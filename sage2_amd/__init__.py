@@ -455,6 +455,16 @@ class Context:
     def mates_clear(self):
         self._chk(lib().sage2ov_mates_clear(self._h))
 
+    def reads_pair_library(self, library):
+        """0: pairing off (the default); 1 .. 127: every later reads_add_ascii / reads_add_file call is also one mates call for that library
+        (reads_add_list: dataset i is library i), to be turned into the mate table by mates_from_reads() after reads_organize()"""
+        self._chk(lib().sage2ov_reads_pair_library(self._h, C.c_int(library)))
+
+    def mates_from_reads(self):
+        """the mate table of the reads this context organised with pairing on: what the matching mates_add_* calls would add, without reading the
+        input again or searching the read store; once per organised read set"""
+        self._chk(lib().sage2ov_mates_from_reads(self._h))
+
     def mates_stats(self) -> MateStats:
         s = MateStats()
         self._chk(lib().sage2ov_mates_stats_get(self._h, C.byref(s)))

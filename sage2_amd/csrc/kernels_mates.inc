@@ -50,6 +50,31 @@ __global__ void k_mate_records(const long long* __restrict__ ids, const u32* __r
     key[o] = mate_key(id1, id2, t1, t2); ord[o] = ord0 + 2ull * j;
     key[o + 1] = mate_key(id2, id1, t2, t1); ord[o + 1] = ord0 + 2ull * j + 1ull;
 }
+// ---- the pairs of one reads_add_* call from step 1's own by-products (sage2ov_mates_from_reads, DESIGN.md 5.21): no file is read and no store searched.
+//   k_pair_slots   slotOf[ordinal] = staging index + 1, scattered from the ordinals the host kept per staged read (slotOf zeroed before: 0 = not staged)
+//   k_pair_keep    one thread per pair p of a chunk: the ids of records rec0 + 2 p and rec0 + 2 p + 1 (through slotOf, or -- slotOf null, the ASCII route --
+//                  straight from the per-record ids), laid out per pair as k_find_search leaves them; 2 records when both were staged, else the pair is one
+//                  with a mate that is not a good read (only such a read is not staged).  k_mate_records then writes the records.
+// Ordinals inside a call stay below 2^32 - 2048 (the host refuses more); the record ordinals k_mate_records writes are 64-bit.
+__global__ void k_pair_slots(const u32* __restrict__ ord, u64 n, u32 first, u32* slotOf) {
+    const u64 x = (u64)blockIdx.x * blockDim.x + threadIdx.x; if (x < n) slotOf[ord[x]] = first + (u32)x + 1u;
+}
+__device__ __forceinline__ int pair_id(const int* __restrict__ idOf, const u32* __restrict__ slotOf, u64 o) {
+    if (!slotOf) return idOf[o];
+    const u32 s = slotOf[o]; return s ? idOf[s - 1u] : 0;
+}
+__global__ void k_pair_keep(const int* __restrict__ idOf, const u32* __restrict__ slotOf, u64 rec0, u32 npairs, long long* ids, u32* keep, unsigned long long* cnt) {
+    const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
+    bool bad = false;
+    if (j < npairs) {
+        const u64 o = rec0 + 2ull * j;
+        const int a = pair_id(idOf, slotOf, o), b = pair_id(idOf, slotOf, o + 1ull);
+        bad = a == 0 || b == 0;
+        ids[2ull * j] = a; ids[2ull * j + 1ull] = b; keep[j] = bad ? 0u : 2u;
+    }
+    const u64 mb = __ballot(bad);
+    if (lane_id() == 0 && mb) atomicAdd(&cnt[0], (unsigned long long)__popcll(mb));
+}
 __global__ void k_mate_iota(u32* v, u32 n) { const u32 i = blockIdx.x * blockDim.x + threadIdx.x; if (i < n) v[i] = i; }
 __global__ void k_mate_heads(const u64* __restrict__ keys, u32 n, u32* flag) {
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x; if (i >= n) return;

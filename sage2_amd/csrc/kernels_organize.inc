@@ -14,7 +14,8 @@
 //   k_org_gather  the HBM read store in id order (slot 0 = zeros)
 // =============================================================================================
 constexpr int RS_TILE = 2048;
-__global__ void k_org_canon(const u64* __restrict__ pool, const u64* __restrict__ off, const unsigned short* __restrict__ len, u64 n, int S, u64* img, u64* key0, u32* val) {
+// fwd (pairing, DESIGN.md 5.21; else null): fwd[i] = the read as staged is its canonical form -- the sign of its id (k_org_ids)
+__global__ void k_org_canon(const u64* __restrict__ pool, const u64* __restrict__ off, const unsigned short* __restrict__ len, u64 n, int S, u64* img, u64* key0, u32* val, unsigned char* fwd) {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; if (i >= n) return;
     const int L = len[i], nw = (L + 31) / 32; const u64* f = pool + off[i];
     u64 fw[SLOT_MAX_WORDS + 1], rw[SLOT_MAX_WORDS];
@@ -33,6 +34,7 @@ __global__ void k_org_canon(const u64* __restrict__ pool, const u64* __restrict_
 #pragma unroll 1
     for (int c = 0; c < S; c++) { u64 v = c < nw ? (useF ? fw[c] : rw[c]) : 0ull; if (c == S - 1) v |= (u64)L; o[c] = v; if (c == 0) key0[i] = v; }
     val[i] = (u32)i;
+    if (fwd) fwd[i] = useF ? 1 : 0;
 }
 // ---- ASCII front end (sage2ov_reads_add_ascii on a GPU context): filter + 2-bit pack + canonical orientation on the device.
 //   k_org_classify  isGoodRead (utils.cpp:144-166: longer than minOverlap, only ACGTacgt) -> flag; counters: [0] longest good read, [1] good
@@ -94,12 +96,13 @@ __device__ __forceinline__ bool org_pack_slot(const unsigned char* __restrict__ 
     return useF;
 }
 __global__ void k_org_pack(const unsigned char* __restrict__ bases, const u64* __restrict__ off, u64 n, const u32* __restrict__ flag, const u32* __restrict__ pos, int S,
-                           u64* img, u64* key0, u32* val) {
+                           u64* img, u64* key0, u32* val, unsigned char* fwd) {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; if (i >= n || !flag[i]) return;
     const u64 a = off[i]; const int L = (int)(off[i + 1] - a);
     const u64 o0 = pos[i]; u64 w0 = 0;
-    org_pack_slot(bases, a, L, S, img + o0 * S, w0);
+    const bool useF = org_pack_slot(bases, a, L, S, img + o0 * S, w0);
     key0[o0] = w0; val[o0] = (u32)o0;
+    if (fwd) fwd[o0] = useF ? 1 : 0;
 }
 __global__ __launch_bounds__(64) void k_rs_hist(const u64* __restrict__ keys, u64 n, int shift, u32* hist, u32 nb) {
     __shared__ u32 h[256];
@@ -170,6 +173,20 @@ __global__ void k_headpos(const u32* __restrict__ flag, const u32* __restrict__ 
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n && flag[i]) hp[pos[i]] = (u32)i;
     if (i == 0) hp[E] = (u32)n;
+}
+// ---- pairing (sage2ov_reads_pair_library, DESIGN.md 5.21): the id of every STAGED read, from what the pass above has already made.  One thread per sorted position
+// j: uid is the exclusive scan of the head flags, so the read at j has id uid[j] + flag[j] (a head is the first of its id; the others count the heads up to
+// theirs) -- whichever way the runs were ordered (k_org_ties or the full sort).  The sign is that of sage2ov_reads_find_ids: + when the read as given is strictly
+// smaller than its reverse complement (fwd, from k_org_canon / k_org_pack).  k_org_ids_raw (ASCII route): the same per raw input record, back through the scan
+// of k_org_classify's flags; 0 for a record that was not staged.
+__global__ void k_org_ids(const u32* __restrict__ vals, const u32* __restrict__ flag, const u32* __restrict__ uid, u64 n, const unsigned char* __restrict__ fwd, int* idOf) {
+    const u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x; if (j >= n) return;
+    const u32 v = vals[j]; const int id = (int)(uid[j] + flag[j]);
+    idOf[v] = fwd[v] ? id : -id;
+}
+__global__ void k_org_ids_raw(const u32* __restrict__ gflag, const u32* __restrict__ gpos, u64 nin, const int* __restrict__ idOf, int* rawId) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; if (i >= nin) return;
+    rawId[i] = gflag[i] ? idOf[gpos[i]] : 0;
 }
 __global__ void k_org_gather(const u32* __restrict__ vals, const u32* __restrict__ headPos, u64 N, const u64* __restrict__ img, int S, u64* reads, unsigned short* freq) {
     // grid-stride: a launch of more than 2^32 threads is cut down to its size modulo 2^32 WITHOUT an error (found at 1.02 G reads x 8 words: the last 2^29

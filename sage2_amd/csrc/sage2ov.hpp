@@ -66,6 +66,9 @@ public:
         ctx().check(sage2ov_mates_add_file(ctx().get(), mateFile1.c_str(), mateFile2.empty() ? nullptr : mateFile2.c_str(), library)); cachedLibrary_ = 0;
     }
     void mapMatePairsFromList(const std::string& listPath) { ctx().check(sage2ov_mates_add_list(ctx().get(), listPath.c_str())); cachedLibrary_ = 0; }
+    // the same table from step 1's own pass (no second pass over the input): pairLibrary before the loader reads its input, mapMatePairsFromReads after organizeReads
+    void pairLibrary(int library) { ctx().check(sage2ov_reads_pair_library(ctx().get(), library)); }
+    void mapMatePairsFromReads() { ctx().check(sage2ov_mates_from_reads(ctx().get())); cachedLibrary_ = 0; }
     void processMatePairs(const std::vector<std::string>& readsArray, int library) {
         std::string bases; std::vector<uint64_t> off(readsArray.size() + 1, 0);
         for (size_t r = 0; r < readsArray.size(); r++) { bases += readsArray[r]; off[r + 1] = bases.size(); }

@@ -1,6 +1,7 @@
-// sage2_amd/csrc/sage2ov_cli.cpp -- `sage2ov`: drop-in producer of <outdir>/<prefix>.reads and <prefix>.graph3.
-// Mimics the SAGE2 command line for steps 1-3 (main.cpp:384-521): -f | -l, -k, -o, -p, -i, -m, -M, -s, -d, -h.
-// Continue with the unchanged reference:  SAGE2 -f reads.fa -k K -o out -p P -i P -m 4      (main.cpp:141-148)
+// sage2_amd/csrc/sage2ov_cli.cpp -- `sage2ov`: the SAGE2 command line (main.cpp:384-521): -f | -l, -k, -o, -p, -i, -m, -M, -s, -d, -h.
+// -M 3 (the default) writes <outdir>/<prefix>.reads and <prefix>.graph3, which the unchanged reference continues from (SAGE2 ... -i P -m 4, main.cpp:141-148);
+// -m 1..4 with -M 5 | 6 | 7 is the whole assembly in one process on the graph that stays resident: step 5 with the library's solver, step 6 (extendContigs,
+// <prefix>_contig.fasta) and step 7 (makeScaffolds, <prefix>_scaffold.fasta).
 // --flowNetwork writes <outdir>/input.cs2 (step 5's flow network, with the genome-size estimate) and --flowSolution FILE applies a solver's output.cs2 and writes
 // <prefix>.graph5: after step 4, or with -m 5 from <inputPrefix>.reads and <inputPrefix>.graph4.  No outside solver is started here; --flowSolve is the whole of step 5 with
 // the library's own solver on the device (with -s it leaves input.cs2 and its output.cs2 too).
@@ -29,7 +30,8 @@ static void printUsage() {
 static void printListOfArgs() {
     cout << "\t-f|--fileInput <string>\tinterleaved FASTA/FASTQ(.gz)\n\t-l|--listInput <string>\tlist file (f1=/f2=/f=)\n"
             "\t-k|--minOverlap <int>\tminimum overlap (required)\n\t-o|--outputDir <string>\n\t-p|--prefix <string>\t[untitled]\n"
-            "\t-i|--inputPrefix <string>\t[prefix]\n\t-m|--minStep <int>\t[1]\n\t-M|--maxStep <int>\t[3] (4 = simplified graph P.graph4; steps 5-7: run SAGE2 -m 5 on the files written here)\n"
+            "\t-i|--inputPrefix <string>\t[prefix]\n\t-m|--minStep <int>\t[1]\n\t-M|--maxStep <int>\t[3] (4 = simplified graph P.graph4; 5 = copy counts, P.graph5; 6 = extended contigs, P_contig.fasta and P.graph6;\n"
+            "\t\t\t7 = scaffolds, P_scaffold.fasta: with -m 1..4 the whole run in one process, the graph stays on the device; steps 6-7 need -f or -l)\n"
             "\t-s|--saveAll\n\t-d|--debug\n\t-g|--gpu <int>\tHIP device ordinal [0]\n"
             "\t-G|--gpus <int>\tsteps 2-3 on this many GPUs of the node (devices gpu .. gpu+G-1): reads and index replicated, probe pass\n"
             "\t\t\trange-partitioned, records / flags / edge and survivor buckets exchanged with RCCL over xGMI [1]\n"
@@ -96,6 +98,10 @@ int main(int argc, char* argv[]) {
     }
     if (fFlag && lFlag) { cout << "[ERROR] Options -f|--fileInput and -l|--listInput are mutually exclusive!\n\n"; exit(0); }
     if (flowSolve && flowSolution != "") { cout << "[ERROR] Options --flowSolve and --flowSolution are mutually exclusive!\n\n"; exit(0); }
+    // the whole run: -m 1..4 through -M 5 | 6 | 7 on one context.  A run that crosses step 5 solves the flow itself (an outside solver cannot run in the middle)
+    const bool through5 = minStep <= 4 && maxStep >= 6, ends5 = minStep <= 4 && maxStep == 5 && !flowNetwork && flowSolution == "";
+    if (through5 && (flowNetwork || flowSolution != "")) { cout << "[ERROR] -M " << maxStep << " runs step 5 with the solver on the device: --flowNetwork and --flowSolution stop at step 5 (-M 5), an outside solver cannot run in the middle.\n"; exit(0); }
+    if (through5 || ends5) flowSolve = true;
     const bool step5 = flowNetwork || flowSolve || flowSolution != "";
     if (step5 && !maxGiven && maxStep < minStep) maxStep = minStep;                          // (`-m 5 --flowSolution FILE` needs no -M)
     bool allSet = true;                                                                     // main.cpp:498-521
@@ -107,16 +113,17 @@ int main(int argc, char* argv[]) {
     if (!allSet) { cout << "\n"; printUsage(); cout << "(For more information run sage2ov -h)\n\n"; exit(0); }
     if (step5 && maxStep < 4) { cout << "[ERROR] --flowNetwork and --flowSolution need the graph after step 4: run with -M 4 (or -m 5 on the files of such a run).\n"; exit(0); }
     if (minStep > 5 && step5) { cout << "[ERROR] --flowNetwork and --flowSolution work on the graph after step 4 (-m 5 at the most).\n"; exit(0); }
+    if (through5 && fileInput == "" && listInput == "") { cout << "[ERROR] -M " << maxStep << " maps the mate pairs in step 6 and needs the mate pairs (-f or -l).\n"; exit(0); }
     if (extend && (minStep != 6 || (fileInput == "" && listInput == ""))) { cout << "[ERROR] --extend works on <inputPrefix>.graph5 (-m 6) and needs the mate pairs (-f or -l).\n"; exit(0); }
     if (paths && !(extend && minStep == 6)) { cout << "[ERROR] --paths goes with -m 6 --extend.\n"; exit(0); }
     if (shortOverlaps && !(extend && minStep == 6)) { cout << "[ERROR] --shortOverlaps goes with -m 6 --extend.\n"; exit(0); }
     if (scaffold && (!(minStep == 7 || (minStep == 6 && extend)) || (fileInput == "" && listInput == ""))) { cout << "[ERROR] --scaffold works on <inputPrefix>.graph6 (-m 7), or after --extend (-m 6), and needs the mate pairs (-f or -l).\n"; exit(0); }
-    if (minStep > 4 && !contigs && !step5 && !extend && !scaffold) { cout << "[ERROR] sage2ov implements steps 1-4; continue with: SAGE2 -m " << minStep << " -i " << inputPrefix << " ...\n"; exit(0); }
+    if (minStep > 4 && !contigs && !step5 && !extend && !scaffold) { cout << "[ERROR] A run that starts at step " << minStep << " says what it does: --flowSolve | --flowNetwork | --flowSolution (-m 5), --extend (-m 6), --scaffold (-m 7) or --contigs; the whole run is -m 1..4 with -M 5 | 6 | 7.\n"; exit(0); }
     (void)debugging;
     if (outputDir != "") { string cmd = "mkdir -p " + outputDir; if (system(cmd.c_str())) {} }     // utils.cpp:45
     ofstream logStream((outputDir + prefixName + ".log").c_str());
     logStream << "***********************************************************************************************************\n"
-              << "\tEXECUTING PROGRAM: sage2ov (MI355X-native SAGE2 steps 1-4), " << sage2ov_version() << "\n"
+              << "\tEXECUTING PROGRAM: sage2ov (MI355X-native SAGE2), " << sage2ov_version() << "\n"
               << (listInput != "" ? "\t  INPUT LIST PATH: " + listInput : "\t  INPUT FILE PATH: " + fileInput) << "\n"
               << "\t OUTPUT DIRECTORY: " << outputDir << "\n\t    OUTPUT PREFIX: " << prefixName << "\n\t  MINIMUM OVERLAP: " << minOverlap << "\n"
               << "\t       START STEP: " << minStep << "\n\t         END STEP: " << maxStep << "\n\t   SAVE ALL FILES: " << (saveAll ? "TRUE" : "FALSE") << "\n"
@@ -129,6 +136,9 @@ int main(int argc, char* argv[]) {
         ReadLoader loaderObj(ctx);
         double t0 = now();
         if (timing) fprintf(stderr, "[cli] start-up (context, device) %8.1f ms\n", 1e3 * (t0 - tMain));
+        // the whole run from step 1: the mate table of step 6 comes from step 1's own pass (-f: library 1; -l: the list's own numbering)
+        const bool pairFromReads = minStep <= 1 && through5;
+        if (pairFromReads) ctx.check(sage2ov_reads_pair_library(ctx.get(), 1));
         if (minStep <= 1) {                                                                  // main.cpp:37-61
             logStream << "STEP 1: organizing reads\n";
             if (listInput != "") loaderObj.loadFromList(listInput); else loaderObj.readDatasetInBytes(fileInput);
@@ -182,11 +192,73 @@ int main(int argc, char* argv[]) {
                 logStream << "\tMin-cost flow: " << ms.nodes << " nodes, " << ms.arcs << " arcs, cost " << ms.total_cost << "; " << ms.phases << " phases, " << ms.rounds << " rounds, "
                           << ms.pushes << " pushes, " << ms.relabels << " relabels, " << ms.price_updates << " price updates, " << 64 * ms.price_words << "-bit prices, in "<< (ms.build_ms + ms.solve_ms) / 1000.0 << " sec.\n"
                           << "\t         Flow from T to S: " << cs.t_to_s_flow << "\n\t  Flow different in edges: " << cs.flow_different << "\n";
-                ctx.check(sage2ov_graph5_save(ctx.get(), (outputDir + prefixName + ".graph5").c_str()));
-                logStream << "\t" << prefixName << ".graph5 written\n";
+                if (!through5 || saveAll) {                                                   // (a run that goes on writes it with -s only, as the reference does)
+                    ctx.check(sage2ov_graph5_save(ctx.get(), (outputDir + prefixName + ".graph5").c_str()));
+                    logStream << "\t" << prefixName << ".graph5 written\n";
+                }
             }
             if (!genomeSizeGiven) genomeSize = est;
             logStream << "\tStep 5 (" << (flowSolve ? "with" : "without") << " its solver) in " << now() - t5 << " sec.\n";
+        };
+        // the mate pairs of -f | -l and the insert sizes (main.cpp:236-240, :265-270).  fromReads: the table comes from step 1's own pass (the context staged the input with
+        // pairing on: neither a second pass over the file nor a search of the read store); else the input is read again, as the restart routes do
+        auto mapMates = [&](bool fromReads) {
+            double tm = now();
+            if (fromReads) ctx.check(sage2ov_mates_from_reads(ctx.get()));
+            else if (listInput != "") ctx.check(sage2ov_mates_add_list(ctx.get(), listInput.c_str()));
+            else ctx.check(sage2ov_mates_add_file(ctx.get(), fileInput.c_str(), nullptr, 1));
+            if (timing) fprintf(stderr, "[cli] mate table (%s) %8.1f ms\n", fromReads ? "from step 1's pass" : "second pass over the input", 1e3 * (now() - tm));
+            ctx.check(sage2ov_mates_estimate(ctx.get()));
+        };
+        auto step6 = [&](bool fromReads, bool doPaths, bool doShort, bool saveGraph6) {        // main.cpp:236-244, extendContigs (mergeContigs.cpp:37-113): its first loop, the others by doPaths and doShort
+            double t6 = now();
+            logStream << "STEP 6: map mate pairs & merge by mate-pair support\n";
+            mapMates(fromReads);
+            logStream << "\nIn function mergeContigs().\n";
+            uint64_t rounds = 0, merged = 0;
+            const int rc = sage2ov_extend_by_supports(ctx.get(), genomeSizeGiven ? genomeSize : 0, &rounds, &merged);
+            sage2ov_extend_stats xs{}; ctx.check(sage2ov_extend_stats_get(ctx.get(), &xs));
+            logStream << "\tRounds of findMatepairSupports: " << rounds << " (" << xs.total.entries << " supported pairs listed, " << xs.total.refused << " refused, " << xs.total.blocked
+                      << " blocked, " << xs.total.pairs_deleted << " edges deleted, " << xs.total.entries_copied << " list entries written)\n";
+            ctx.check(rc);
+            if (doPaths) {                                                                  // the second and third loop (mergeContigs.cpp:62-99)
+                static const char* const name[2] = {"findPathSupports", "findPathSupportsNew"};
+                for (int variant = 0; variant < 2; variant++) {
+                    uint64_t r = 0, m = 0;
+                    const int rc2 = sage2ov_extend_by_paths(ctx.get(), genomeSizeGiven ? genomeSize : 0, variant, &r, &m);
+                    logStream << "\tRounds of " << name[variant] << ": " << r << " (" << m << " merges)\n";
+                    ctx.check(rc2); merged += m;
+                }
+            }
+            if (doShort) {                                                          // the fourth loop (mergeContigs.cpp:101-110)
+                uint64_t r = 0, m = 0;
+                const int rc2 = sage2ov_extend_by_short_overlaps(ctx.get(), genomeSizeGiven ? genomeSize : 0, &r, &m);
+                sage2ov_scaffold_stats ss{}; ctx.check(sage2ov_extend_short_stats_get(ctx.get(), &ss));
+                logStream << "\tRounds of mergeShortOverlaps: " << r << " (" << ss.total.rows << " rows, " << ss.total.below_threshold << " below the threshold, " << ss.total.skipped << " skipped, "
+                          << ss.total.blocked << " blocked; lists joined by overlap " << ss.total.overlaps << ", concatenated " << ss.total.concatenated
+                          << ", with a gap " << ss.total.gapped << "; " << m << " merges)\n";
+                ctx.check(rc2); merged += m;
+            }
+            logStream << "\nTotal number of extended contigs: " << merged << "\n";
+            if (saveGraph6) { ctx.check(sage2ov_graph6_save(ctx.get(), (outputDir + prefixName + ".graph6").c_str())); logStream << "\t" << prefixName << ".graph6 written\n"; }
+            logStream << "\t" << (doPaths && doShort ? "Step 6" : doPaths ? "Loops 1-3 of step 6" : doShort ? "Loops 1 and 4 of step 6" : "First loop of step 6") << " in " << now() - t6 << " sec.\n";
+        };
+        auto step7 = [&](OverlapGraph& graphObj, bool mapFirst) {                             // main.cpp:263-290, makeScaffolds (scaffolding.cpp:31-98)
+            double t7 = now();
+            logStream << "STEP 7: merge contigs to get scaffolds\n";
+            if (mapFirst) mapMates(false);                                                // (after step 6 its mates and its estimate stand, main.cpp:270)
+            logStream << "\nIn function makeScaffolds().\n";
+            uint64_t rounds = 0, merged = 0;
+            const int rc = sage2ov_scaffold(ctx.get(), genomeSizeGiven ? genomeSize : 0, &rounds, &merged);
+            sage2ov_scaffold_stats ss{}; ctx.check(sage2ov_scaffold_stats_get(ctx.get(), &ss));
+            logStream << "\tRounds of mergeFinal: " << rounds << " (" << ss.total.rows << " rows, " << ss.total.below_threshold << " below the threshold, " << ss.total.skipped << " skipped, "
+                      << ss.total.blocked << " blocked, " << ss.total.cycles << " cycles; lists joined by overlap " << ss.total.overlaps << ", concatenated " << ss.total.concatenated
+                      << ", with a gap " << ss.total.gapped << ")\n";
+            ctx.check(rc);
+            logStream << "\nTotal number of merged scaffolds: " << merged << "\n";
+            double tw = now();
+            auto cs = graphObj.printGraph(outputDir + prefixName + "_scaffold", true, genomeSize);
+            logStream << "\t" << prefixName << "_scaffold.fasta written in " << now() - tw << " sec.\n\t  Number of Scaffolds: " << cs.contigs << " (" << cs.written << " in the file)\n\tStep 7 in " << now() - t7 << " sec.\n";
         };
         auto step4 = [&](OverlapGraph& graphObj) {                                            // main.cpp:134-181
             double t4 = now();
@@ -196,69 +268,17 @@ int main(int argc, char* argv[]) {
                       << " sec (device " << ss.device_ms / 1000.0 << ").\n";
             { double tw = now(); graphObj.saveSimplifiedGraphInFile(outputDir + prefixName + ".graph4"); logStream << "\t" << prefixName << ".graph4 written in " << now() - tw << " sec.\n"; }   // the file step 5 loads (main.cpp:196)
             copyCounts();
-            if (contigs) writeContigs(graphObj);
+            if (contigs && maxStep < 6) writeContigs(graphObj);
+            if (maxStep >= 6) { step6(pairFromReads, true, true, maxStep == 6 || saveAll); writeContigs(graphObj); }      // (main.cpp:246: printGraph after step 6)
+            if (maxStep >= 7) step7(graphObj, false);
         };
         if (minStep > 4) {                                                                    // --contigs on the graph an earlier run or the reference left: P.graph4 / 5 / 6
             OverlapGraph graphObj(&loaderObj);
             graphObj.loadCompositeGraphFromFile(outputDir + inputPrefix + ".graph" + to_string(minStep - 1));
             copyCounts();
-            if (extend) {                                                                     // main.cpp:236-244, extendContigs (mergeContigs.cpp:37-113): its first loop, the others by --paths and --shortOverlaps
-                double t6 = now();
-                logStream << "STEP 6: map mate pairs & merge by mate-pair support\n";
-                if (listInput != "") ctx.check(sage2ov_mates_add_list(ctx.get(), listInput.c_str()));
-                else ctx.check(sage2ov_mates_add_file(ctx.get(), fileInput.c_str(), nullptr, 1));
-                ctx.check(sage2ov_mates_estimate(ctx.get()));
-                logStream << "\nIn function mergeContigs().\n";
-                uint64_t rounds = 0, merged = 0;
-                const int rc = sage2ov_extend_by_supports(ctx.get(), genomeSizeGiven ? genomeSize : 0, &rounds, &merged);
-                sage2ov_extend_stats xs{}; ctx.check(sage2ov_extend_stats_get(ctx.get(), &xs));
-                logStream << "\tRounds of findMatepairSupports: " << rounds << " (" << xs.total.entries << " supported pairs listed, " << xs.total.refused << " refused, " << xs.total.blocked
-                          << " blocked, " << xs.total.pairs_deleted << " edges deleted, " << xs.total.entries_copied << " list entries written)\n";
-                ctx.check(rc);
-                if (paths) {                                                                  // the second and third loop (mergeContigs.cpp:62-99)
-                    static const char* const name[2] = {"findPathSupports", "findPathSupportsNew"};
-                    for (int variant = 0; variant < 2; variant++) {
-                        uint64_t r = 0, m = 0;
-                        const int rc2 = sage2ov_extend_by_paths(ctx.get(), genomeSizeGiven ? genomeSize : 0, variant, &r, &m);
-                        logStream << "\tRounds of " << name[variant] << ": " << r << " (" << m << " merges)\n";
-                        ctx.check(rc2); merged += m;
-                    }
-                }
-                if (shortOverlaps) {                                                          // the fourth loop (mergeContigs.cpp:101-110)
-                    uint64_t r = 0, m = 0;
-                    const int rc2 = sage2ov_extend_by_short_overlaps(ctx.get(), genomeSizeGiven ? genomeSize : 0, &r, &m);
-                    sage2ov_scaffold_stats ss{}; ctx.check(sage2ov_extend_short_stats_get(ctx.get(), &ss));
-                    logStream << "\tRounds of mergeShortOverlaps: " << r << " (" << ss.total.rows << " rows, " << ss.total.below_threshold << " below the threshold, " << ss.total.skipped << " skipped, "
-                              << ss.total.blocked << " blocked; lists joined by overlap " << ss.total.overlaps << ", concatenated " << ss.total.concatenated
-                              << ", with a gap " << ss.total.gapped << "; " << m << " merges)\n";
-                    ctx.check(rc2); merged += m;
-                }
-                logStream << "\nTotal number of extended contigs: " << merged << "\n";
-                ctx.check(sage2ov_graph6_save(ctx.get(), (outputDir + prefixName + ".graph6").c_str()));
-                logStream << "\t" << prefixName << ".graph6 written\n\t" << (paths && shortOverlaps ? "Step 6" : paths ? "Loops 1-3 of step 6" : shortOverlaps ? "Loops 1 and 4 of step 6" : "First loop of step 6") << " in " << now() - t6 << " sec.\n";
-            }
+            if (extend) step6(false, paths, shortOverlaps, true);
             if (contigs) writeContigs(graphObj);
-            if (scaffold) {                                                                   // main.cpp:263-290, makeScaffolds (scaffolding.cpp:31-98)
-                double t7 = now();
-                logStream << "STEP 7: merge contigs to get scaffolds\n";
-                if (!extend) {                                                                // (after --extend the mates and the estimate of step 6 stand, main.cpp:270)
-                    if (listInput != "") ctx.check(sage2ov_mates_add_list(ctx.get(), listInput.c_str()));
-                    else ctx.check(sage2ov_mates_add_file(ctx.get(), fileInput.c_str(), nullptr, 1));
-                    ctx.check(sage2ov_mates_estimate(ctx.get()));
-                }
-                logStream << "\nIn function makeScaffolds().\n";
-                uint64_t rounds = 0, merged = 0;
-                const int rc = sage2ov_scaffold(ctx.get(), genomeSizeGiven ? genomeSize : 0, &rounds, &merged);
-                sage2ov_scaffold_stats ss{}; ctx.check(sage2ov_scaffold_stats_get(ctx.get(), &ss));
-                logStream << "\tRounds of mergeFinal: " << rounds << " (" << ss.total.rows << " rows, " << ss.total.below_threshold << " below the threshold, " << ss.total.skipped << " skipped, "
-                          << ss.total.blocked << " blocked, " << ss.total.cycles << " cycles; lists joined by overlap " << ss.total.overlaps << ", concatenated " << ss.total.concatenated
-                          << ", with a gap " << ss.total.gapped << ")\n";
-                ctx.check(rc);
-                logStream << "\nTotal number of merged scaffolds: " << merged << "\n";
-                double tw = now();
-                auto cs = graphObj.printGraph(outputDir + prefixName + "_scaffold", true, genomeSize);
-                logStream << "\t" << prefixName << "_scaffold.fasta written in " << now() - tw << " sec.\n\t  Number of Scaffolds: " << cs.contigs << " (" << cs.written << " in the file)\n\tStep 7 in " << now() - t7 << " sec.\n";
-            }
+            if (scaffold) step7(graphObj, !extend);
         } else if (minStep == 4) {                                                            // main.cpp:141-148
             OverlapGraph graphObj(&loaderObj);
             graphObj.loadOverlapGraphFromFile(outputDir + inputPrefix + ".graph3");
@@ -323,10 +343,6 @@ int main(int argc, char* argv[]) {
             }
         }
         if (timing) fprintf(stderr, "[cli] until the last file is written %8.1f ms\n", 1e3 * (now() - tMain));
-        if (maxStep > 4 && minStep <= 4) {
-            cout << "sage2ov: steps 1-4 done; continue with the reference: SAGE2 " << (listInput != "" ? "-l " + listInput : "-f " + fileInput) << " -k " << minOverlap
-                 << " -o " << (outputDir == "" ? "." : outputDir) << " -p " << prefixName << " -i " << prefixName << " -m 5 -M " << maxStep << "\n";
-        }
         // every file is written and closed: leave without tearing down gigabytes of host vectors and the HIP runtime one allocation at a time
         // (0.25 s on a 10 M-read run; the kernel reclaims host and device memory of an exiting process at once)
         logStream.flush(); logStream.close(); cout.flush(); fflush(nullptr);

@@ -80,6 +80,9 @@ struct Device {
     u64* d_runStarts = nullptr; u64* h_runStarts = nullptr; hipEvent_t evRunStarts = nullptr; bool runStartsValid = false; double runStartFrac = 0.0;      // share of the reads without a predecessor in the locality order (counted by k_loc_index into d_runStarts)
     u64* reads = nullptr;        // (N+1)*S words, slot i = read id i
     Mates* mates = nullptr;      // the mate-pair table (dev_mates_add): allocations of its own, dropped with the read set
+    // pairing (dev_organize_reads(..., pairing)): +-id of the pairN staged reads -- pairRaw: of the pairN raw records of the ASCII route, 0 for one
+    // that was not staged --, an allocation of its own, dropped by dev_pairing_release and with the read set
+    int* pairId = nullptr; u64 pairN = 0; bool pairRaw = false, pairValid = false;
     void* readmap = nullptr;     // the read-to-edge table, the mate flags and the distances (dev_readmap_build; ReadMap): allocations of its own, dropped with the graph and the read set
     u32* findDir = nullptr; int findDirBits = 0;      // read-id lookup (dev_find_ids): first id per value of the top bits of word 0, built by the first call, dropped with the read set
     // the same reads in LOCALITY order (slot p = the read at position p of the order by global minimiser): what the index entries point at and
@@ -404,6 +407,7 @@ static void free_reads(Device* d) {
     hipFree(d->reads);
     hipFree(d->findDir); d->findDir = nullptr; d->findDirBits = 0;      // (the lookup directory describes the read set that goes)
     mates_release(d);                                                   // (so do the ids of the mate table)
+    dev_pairing_release(d);                                             // (and the ids of the staged reads)
     if (!d->resCarved) { hipFree(d->right); hipFree(d->left); hipFree(d->conn); hipFree(d->cflag); hipFree(d->status); hipFree(d->cand); }     // slots / csr / final_edges live in the workspace arena
     ph_release(d);                                                              // (diet mode: the phase block and what was carved out of it)
     for (auto& b : d->ws) { if (b.p && !b.epoch) hipFree(b.p); b.p = nullptr; b.cap = 0; b.epoch = 0; }
@@ -461,8 +465,9 @@ static int partition_by_window(Device* d, PtBufs& B, int keyw, u32 n, int shiftW
 // Step 1 on the device: see k_org_canon.  On return the read store is resident exactly as after dev_upload_reads, and the
 // host receives the image (for the .reads writer, lengths) and the frequencies.
 int dev_organize_reads(Device* d, const uint64_t* pool, uint64_t pool_words, const uint64_t* off, const uint16_t* len, uint64_t n, int S, int minL, int maxL, int k,
-                       uint64_t* N_out, RawU64& words_out, RawU16& freq_out, std::string& err, OrgAscii* ascii) {
+                       uint64_t* N_out, RawU64& words_out, RawU16& freq_out, std::string& err, OrgAscii* ascii, bool pairing) {
     HIPCHK(hipSetDevice(d->ordinal));
+    DevTmp PB; unsigned char* fwd = nullptr; int* pairId = nullptr; u64 pairN = 0;      // pairing: nothing of it is allocated or launched when it is off
     StreamLap whole(d->stream); HIPCHK(whole.create());
     const bool timing = d->opt.get("SAGE2OV_TIMING") != nullptr; auto tp = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) { if (!timing) return; hipStreamSynchronize(d->stream); auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[step 1/device] %-30s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(t - tp).count()); tp = t; };
@@ -494,7 +499,8 @@ int dev_organize_reads(Device* d, const uint64_t* pool, uint64_t pool_words, con
         WS(img, u64, WS_ORG_IMG, n * S); WS(k0, u64, WS_ORG_K0, n); WS(k1, u64, WS_ORG_K1, n); WS(v0, u32, WS_ORG_V0, n); WS(v1, u32, WS_ORG_V1, n);
         WS(hist, u32, WS_ORG_HIST, rs_hist_words(n)); WS(hscan, u32, WS_ORG_HSCAN, rs_hist_words(n)); WS(flag, u32, WS_ORG_FLAG, n + 2); WS(uid, u32, WS_ORG_UID, n + 2);
         WS(partial, u64, WS_PARTIAL, scan_partial_words(std::max<u64>(n, rs_hist_words(n))));      // (the sort's scans and the one over the heads)
-        if (ascii) hipLaunchKernelGGL(k_org_pack, dim3(grid_for(ascii->n_in, 256)), dim3(256), 0, d->stream, dbases, doffA, (u64)ascii->n_in, gflag, gpos, S, img, k0, v0);
+        if (pairing) { fwd = PB.get<unsigned char>(n); if (!fwd) { err = "pairing: out of device memory"; return SAGE2OV_ERR_NOMEM; } }
+        if (ascii) hipLaunchKernelGGL(k_org_pack, dim3(grid_for(ascii->n_in, 256)), dim3(256), 0, d->stream, dbases, doffA, (u64)ascii->n_in, gflag, gpos, S, img, k0, v0, fwd);
         else {
             WS(dpool, u64, WS_ORG_POOL, pool_words + 17); WS(doff, u64, WS_ORG_OFF, n); WS(dlen, unsigned short, WS_ORG_LEN, n);
             HIPCHK(hipMemcpyAsync(dpool, pool, pool_words * sizeof(u64), hipMemcpyHostToDevice, d->stream));
@@ -502,7 +508,7 @@ int dev_organize_reads(Device* d, const uint64_t* pool, uint64_t pool_words, con
             HIPCHK(hipMemcpyAsync(doff, off, n * sizeof(u64), hipMemcpyHostToDevice, d->stream));
             HIPCHK(hipMemcpyAsync(dlen, len, n * sizeof(uint16_t), hipMemcpyHostToDevice, d->stream));
             lap("work space + upload");
-            hipLaunchKernelGGL(k_org_canon, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, dpool, doff, dlen, (u64)n, S, img, k0, v0);
+            hipLaunchKernelGGL(k_org_canon, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, dpool, doff, dlen, (u64)n, S, img, k0, v0, fwd);
         }
         static_assert(RS_ALL_N % 2 == 0, "an even number of passes: every sort below leaves the pairs where it found them, in k0 / v0");
         const RsBufs B = {{k0, k1}, {v0, v1}, hist, hscan, partial}; int side = 0; u64* const ka = k0; u32* const va = v0;
@@ -525,12 +531,23 @@ int dev_organize_reads(Device* d, const uint64_t* pool, uint64_t pool_words, con
         WS(headPos, u32, WS_ORG_HEAD, N + 2);
         { int rc = head_positions(d, flag, uid, n, headPos, N, err); if (rc) return rc; }
         lap("canonical, sort, heads");
+        if (pairing) {                                                      // the ids of the staged reads, while flag / uid / va still stand
+            int* idOf = PB.get<int>(n); if (!idOf) { err = "pairing: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+            hipLaunchKernelGGL(k_org_ids, dim3(grid_for(n, 256)), dim3(256), 0, d->stream, va, flag, uid, (u64)n, fwd, idOf);
+            pairId = idOf; pairN = n;
+        }
         HIPCHK(hipMalloc(&reads, (N + 1) * S * sizeof(u64))); HIPCHK(hipMalloc(&dfreq, (N + 1) * sizeof(unsigned short)));
         HIPCHK(hipMemsetAsync(reads, 0, S * sizeof(u64), d->stream)); HIPCHK(hipMemsetAsync(dfreq, 0, sizeof(unsigned short), d->stream));
         hipLaunchKernelGGL(k_org_gather, dim3(grid_for_capped(N * S, 256)), dim3(256), 0, d->stream, va, headPos, (u64)N, img, S, reads, dfreq);
     } else {
         HIPCHK(hipMalloc(&reads, S * sizeof(u64))); HIPCHK(hipMalloc(&dfreq, sizeof(unsigned short)));
         HIPCHK(hipMemsetAsync(reads, 0, S * sizeof(u64), d->stream)); HIPCHK(hipMemsetAsync(dfreq, 0, sizeof(unsigned short), d->stream));
+    }
+    if (pairing && ascii) {                                                 // ASCII route: per raw record, back through the scan of the classifier's flags
+        const u64 nin = ascii->n_in; int* rawId = PB.get<int>(nin); if (!rawId) { err = "pairing: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+        if (n) hipLaunchKernelGGL(k_org_ids_raw, dim3(grid_for(nin, 256)), dim3(256), 0, d->stream, gflag, gpos, (u64)nin, pairId, rawId);
+        else if (nin) HIPCHK(hipMemsetAsync(rawId, 0, nin * sizeof(int), d->stream));
+        pairId = rawId; pairN = nin;                                        // (the by-staging-index ids go with PB)
     }
     HIPCHK(hipGetLastError());
     HIPCHK(whole.end());
@@ -547,6 +564,7 @@ int dev_organize_reads(Device* d, const uint64_t* pool, uint64_t pool_words, con
     // the organised store becomes the context's read store (same state as after dev_upload_reads)
     free_reads(d);
     d->N = N; d->S = S; d->maxL = maxL; d->k = k; d->h = k > 64 ? 64 : k; d->reads = reads; d->uniL = (N && minL == maxL) ? maxL : 0;
+    if (pairing) { PB.keep(pairId); d->pairId = pairId; d->pairN = pairN; d->pairRaw = ascii != nullptr; d->pairValid = true; }
     mem_sample(d);
     // the organiser's work space (the staged reads, their slot image, the sort's key / value pairs: ~180 bytes per read) is not needed again
     for (int id : {WS_ORG_POOL, WS_ORG_OFF, WS_ORG_LEN, WS_ORG_IMG, WS_ORG_K0, WS_ORG_K1, WS_ORG_V0, WS_ORG_V1, WS_ORG_HIST, WS_ORG_HSCAN, WS_ORG_FLAG, WS_ORG_UID, WS_ORG_HEAD, WS_ORG_GFLAG, WS_ORG_GPOS}) ws_free(d, id);
@@ -1922,6 +1940,18 @@ int dev_mates_flush(Device* d, int library, MateStats* st, std::string& err) {
     B.keep(nk); B.keep(nc); B.keep(nf); L.key = nk; L.cnt = nc; L.first = nf; L.n = E2;
     return 0;
 }
+// room for nrec more records in the pending buffer (its records are kept)
+static int mates_pending_reserve(Device* d, Mates* M, u64 nrec, u64 bound, std::string& err) {
+    if (M->pn + nrec <= M->pcap) return 0;
+    const u64 cap = std::max<u64>(M->pn + nrec, std::min<u64>(2 * M->pcap, bound + (1ull << 22)));
+    u64 *nk = nullptr, *no = nullptr;
+    if (hipMalloc(&nk, cap * sizeof(u64)) != hipSuccess || hipMalloc(&no, cap * sizeof(u64)) != hipSuccess) { (void)hipGetLastError(); hipFree(nk); err = "mate table: out of device memory"; return SAGE2OV_ERR_NOMEM; }
+    if (M->pn) { hipMemcpyAsync(nk, M->pkey, M->pn * sizeof(u64), hipMemcpyDeviceToDevice, d->stream); hipMemcpyAsync(no, M->pord, M->pn * sizeof(u64), hipMemcpyDeviceToDevice, d->stream); }
+    hipError_t e = hipStreamSynchronize(d->stream);
+    hipFree(M->pkey); hipFree(M->pord); M->pkey = nk; M->pord = no; M->pcap = cap;
+    if (e != hipSuccess) { err = std::string("mate table: ") + hipGetErrorString(e); return SAGE2OV_ERR_DEVICE; }
+    return 0;
+}
 // One readsArray of processMatePairs: reads [0, n) of the call, n even (the caller drops a trailing odd read), pair0 = ordinal of the call's first pair in
 // its library.  The chunks hold an even number of queries, so a pair is never cut from its ids.  Records collect in the pending buffer, which is flushed at
 // MATE_FLUSH_RECORDS (SAGE2OV_TEST_MATE_FLUSH: a bound for tests); the caller ends its call with dev_mates_flush.  Returns 1 (and does nothing) when no
@@ -1953,21 +1983,65 @@ int dev_mates_add(Device* d, const char* bases, const uint64_t* off, uint64_t n,
         u64 nrec = 0; { const int rc = scan_u32(d, keep, np, pos, partial, &nrec, err); if (rc) return rc; }
         u64 hk[2]; HIPCHK(hipMemcpyAsync(hk, kinds, sizeof hk, hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
         st->seen += np; st->not_good += hk[0]; st->not_found += hk[1]; st->added += nrec / 2;
-        if (M->pn + nrec > M->pcap) {                                                // grow the pending buffer (its records are kept)
-            const u64 cap = std::max<u64>(M->pn + nrec, std::min<u64>(2 * M->pcap, bound + (1ull << 22)));
-            u64 *nk = nullptr, *no = nullptr;
-            if (hipMalloc(&nk, cap * sizeof(u64)) != hipSuccess || hipMalloc(&no, cap * sizeof(u64)) != hipSuccess) { (void)hipGetLastError(); hipFree(nk); err = "mate table: out of device memory"; return SAGE2OV_ERR_NOMEM; }
-            if (M->pn) { hipMemcpyAsync(nk, M->pkey, M->pn * sizeof(u64), hipMemcpyDeviceToDevice, d->stream); hipMemcpyAsync(no, M->pord, M->pn * sizeof(u64), hipMemcpyDeviceToDevice, d->stream); }
-            hipError_t e = hipStreamSynchronize(d->stream);
-            hipFree(M->pkey); hipFree(M->pord); M->pkey = nk; M->pord = no; M->pcap = cap;
-            if (e != hipSuccess) { err = std::string("mate table: ") + hipGetErrorString(e); return SAGE2OV_ERR_DEVICE; }
-        }
+        { const int rc = mates_pending_reserve(d, M, nrec, bound, err); if (rc) return rc; }
         if (nrec) hipLaunchKernelGGL(k_mate_records, dim3(grid_for(np, 256)), dim3(256), 0, d->stream, C.dids, keep, pos, np, 2ull * (pair0 + r0 / 2), M->pkey + M->pn, M->pord + M->pn);
         HIPCHK(hipGetLastError());
         HIPCHK(lap.stop(st->records_ms));
         M->pn += nrec;
         if (M->pn >= bound) { const int rc = dev_mates_flush(d, library, st, err); if (rc) return rc; }
         r0 = r1;
+    }
+    return 0;
+}
+// One reads_add_* call as one mates call, from the ids dev_organize_reads kept (sage2ov_mates_from_reads; k_pair_slots, k_pair_keep): see
+// sage2ov_internal.h.  Chunks of 2^22 pairs bound the transient ids; the records collect in the pending buffer exactly as dev_mates_add's do, flush bound included.
+void dev_pairing_release(Device* d) { if (d->pairId) { hipSetDevice(d->ordinal); hipFree(d->pairId); } d->pairId = nullptr; d->pairN = 0; d->pairRaw = d->pairValid = false; }
+int dev_mates_pair_call(Device* d, bool raw, const uint32_t* ord, uint64_t nStaged, uint64_t first, uint64_t records, int library, uint64_t pair0, MateStats* st, std::string& err) {
+    HIPCHK(hipSetDevice(d->ordinal));
+    if (raw) ord = nullptr;
+    if (!d->pairValid || d->pairRaw != raw || (!raw && nStaged && !ord)) { err = "pairing: the organiser kept no ids of this kind"; return SAGE2OV_ERR_ARG; }
+    if (d->N >= (1ull << 30)) { err = "mate table: read ids beyond 2^30 - 1"; return SAGE2OV_ERR_LIMIT; }
+    if (records >= (1ull << 32) - RS_TILE) { err = "pairing: too many input records in one call"; return SAGE2OV_ERR_LIMIT; }
+    // every index the kernels form stays inside its array: the staged range (or the raw range) inside the ids, every ordinal inside the call's records
+    if (!raw ? (first > d->pairN || nStaged > d->pairN - first) : (first > d->pairN || records > d->pairN - first)) { err = "pairing: a call outside the staged reads"; return SAGE2OV_ERR_INTERNAL; }
+    if (!raw) for (u64 x = 0; x < nStaged; x++) if (ord[x] >= records) { err = "pairing: a record ordinal outside its call"; return SAGE2OV_ERR_INTERNAL; }
+    const u64 npAll = records / 2; if (!npAll) return 0;
+    const long long forced = d->opt.num("SAGE2OV_TEST_MATE_FLUSH", 0);
+    const u64 bound = forced > 0 ? (u64)forced : MATE_FLUSH_RECORDS;
+    Mates* M = mates_of(d); StreamLap lap(d->stream); HIPCHK(lap.create());
+    DevTmp B; u32* slotOf = nullptr;
+    HIPCHK(lap.start());
+    if (!raw) {
+        slotOf = B.get<u32>(records); u32* dord = B.get<u32>(nStaged); if (!slotOf || !dord) return mate_nomem(err);
+        HIPCHK(hipMemsetAsync(slotOf, 0, records * sizeof(u32), d->stream));
+        if (nStaged) {
+            HIPCHK(hipMemcpyAsync(dord, ord, nStaged * sizeof(u32), hipMemcpyHostToDevice, d->stream));
+            hipLaunchKernelGGL(k_pair_slots, dim3(grid_for(nStaged, 256)), dim3(256), 0, d->stream, dord, (u64)nStaged, (u32)first, slotOf);
+        }
+        HIPCHK(hipStreamSynchronize(d->stream)); B.release(dord);
+    }
+    const int* idOf = raw ? d->pairId + first : d->pairId;
+    const long long fb = d->opt.num("SAGE2OV_TEST_FIND_BATCH", 0);                   // (tests: records per chunk, as the look-up chunks of dev_mates_add)
+    const u64 CH = fb > 0 ? (u64)((fb + 1) / 2) : 1ull << 22, npc = std::min(CH, npAll);
+    long long* ids = B.get<long long>(2 * npc); u32* keep = B.get<u32>(npc); u32* pos = B.get<u32>(npc); u64* partial = B.get<u64>(scan_partial_words(npc));
+    unsigned long long* kinds = (unsigned long long*)B.get<u64>(1);
+    if (!ids || !keep || !pos || !partial || !kinds) return mate_nomem(err);
+    HIPCHK(lap.stop(st->find_ms));
+    for (u64 p0 = 0; p0 < npAll; p0 += CH) {
+        const u32 np = (u32)std::min(CH, npAll - p0);
+        st->chunks++;
+        HIPCHK(lap.start());
+        HIPCHK(hipMemsetAsync(kinds, 0, sizeof(u64), d->stream));
+        hipLaunchKernelGGL(k_pair_keep, dim3(grid_for(np, 256)), dim3(256), 0, d->stream, idOf, slotOf, 2 * p0, np, ids, keep, kinds);
+        u64 nrec = 0; { const int rc = scan_u32(d, keep, np, pos, partial, &nrec, err); if (rc) return rc; }
+        u64 hk = 0; HIPCHK(hipMemcpyAsync(&hk, kinds, sizeof hk, hipMemcpyDeviceToHost, d->stream)); HIPCHK(hipStreamSynchronize(d->stream));
+        st->seen += np; st->not_good += hk; st->added += nrec / 2;
+        { const int rc = mates_pending_reserve(d, M, nrec, bound, err); if (rc) return rc; }
+        if (nrec) hipLaunchKernelGGL(k_mate_records, dim3(grid_for(np, 256)), dim3(256), 0, d->stream, ids, keep, pos, np, 2ull * (pair0 + p0), M->pkey + M->pn, M->pord + M->pn);
+        HIPCHK(hipGetLastError());
+        HIPCHK(lap.stop(st->records_ms));
+        M->pn += nrec;
+        if (M->pn >= bound) { const int rc = dev_mates_flush(d, library, st, err); if (rc) return rc; }
     }
     return 0;
 }

@@ -150,7 +150,15 @@ struct sage2ov_ctx {
     sage2ov_scaffold_stats sostats{}; std::vector<sage2ov_join> sojoins;      // the short-overlap rounds of step 6 (sage2ov_extend_short_*), kept apart from step 7's
     void extend_forget() { estimateHeld = hdrHeld = false; hdrGenome = hdrReads = 0; xstats = sage2ov_extend_stats{}; xmerges.clear(); scstats = sage2ov_scaffold_stats{}; scjoins.clear(); sostats = sage2ov_scaffold_stats{}; sojoins.clear(); }
     void readmap_forget() { rmValid = estimated = false; extend_forget(); pairOrdinal.clear(); rmstats = sage2ov_readmap_stats{}; supports_forget(); paths_forget(); links_forget(); contigs_forget(); copycount_forget(); }      // the graph or the read set goes
+    // ---- pairing (sage2ov_reads_pair_library / sage2ov_mates_from_reads): which input record every staged read was.  A call of reads_add_* made
+    // with pairing on is one PairCall: `records` input records, numbered in input order.  raw: the call's records are entries [first, first + records) of the raw ASCII
+    // staging (their ordinal is their index); else its staged reads are entries [first, first + count) of the pool and pairOrd[ordAt + x] is the ordinal of the x-th.
+    // After the organiser: pairIds (host organiser: +-id of every staged read) or the device's copy (pairOnDevice).  Nothing of this is touched with pairing off.
+    struct PairCall { int lib; bool raw; uint64_t records, first, count, ordAt; };
+    int pairLib = 0; std::vector<PairCall> pairCalls; std::vector<uint32_t> pairOrd; std::vector<int32_t> pairIds; bool pairReady = false, pairOnDevice = false;
+    void pairing_forget() { pairLib = 0; pairReady = pairOnDevice = false; std::vector<PairCall>().swap(pairCalls); std::vector<uint32_t>().swap(pairOrd); std::vector<int32_t>().swap(pairIds); }
     void mates_forget(bool readSetGoes = true) {       // the read set goes: its ids mean nothing any more (the device drops its part in free_reads) -- or sage2ov_mates_clear
+        if (pairReady) pairing_forget();               // (the pairing of an organised set goes with it; what is staged for the next organiser stays)
         if (readSetGoes) { readmap_forget(); readsGen++; } else estimated = estimateHeld = false;
         for (auto& L : mates) L = MateLib();
         for (int i = 0; i < 128; i++) { mateOnDevice[i] = false; matePairs[i] = 0; }
@@ -217,13 +225,17 @@ inline int stage_ascii(sage2ov_ctx* c, const char* b, size_t Ls, VP& pool, VP& o
     good++; bp += L;
     return 0;
 }
-inline void canonicalise_words(uint64_t* f, int L) {        // readLoader.cpp:195: read < revcomp ? read : revcomp (tie: revcomp, same bytes)
+inline bool canonicalise_words(uint64_t* f, int L) {        // readLoader.cpp:195: read < revcomp ? read : revcomp (tie: revcomp, same bytes); true: the read as given stays
     const int nw = (L + 31) / 32; uint64_t r[34];
     revcomp_words(f, nw, L, r);
     bool useF = false;
     for (int w = 0; w < nw; w++) { if (f[w] != r[w]) { useF = f[w] < r[w]; break; } }
     if (!useF) for (int w = 0; w < nw; w++) f[w] = r[w];
+    return useF;
 }
+// pairing: a call's record ordinals are kept in 32 bits and its dense slot table has one word per record
+constexpr uint64_t PAIR_CALL_RECORDS_MAX = (1ull << 32) - 2048;
+static int pair_call_limit(sage2ov_ctx* c) { return c->fail(SAGE2OV_ERR_LIMIT, "pairing: 2^32 - 2048 input records or more in one call"); }
 // worker threads of the host-side I/O helpers: the configured number, else what OpenMP and the CPU affinity allow, at most 16
 // (many short parallel regions on an oversubscribed CPU share cost more than they give)
 static int io_threads(const sage2ov_ctx* c) {
@@ -331,8 +343,10 @@ struct SeqFile {
 // the line two below starts with '+', and every chunk is parsed strictly as four-line records (equal sequence and quality lengths).
 // Anything else -- multi-line FASTQ, a file that is neither, a chunk that does not parse -- returns false and the sequential reader
 // below takes the whole file.
-struct StagePart { RawU64 pool, off; RawU16 lens; uint64_t good = 0, bp = 0, small = 0, records = 0; };      // what one thread staged
-static bool parse_plain_file_parallel(sage2ov_ctx* c, const char* path, std::vector<StagePart>& parts) {
+struct StagePart { RawU64 pool, off; RawU16 lens; uint64_t good = 0, bp = 0, small = 0, records = 0; std::vector<uint32_t> ord; };      // what one thread staged (ord: with pairing, the file ordinal of every staged read)
+// track (pairing): the chunks are handed out dynamically, so every thread notes per chunk where its staged reads begin and their ordinals inside the
+// chunk, every chunk its record count; a prefix sum over the chunks then makes file ordinals of them
+static bool parse_plain_file_parallel(sage2ov_ctx* c, const char* path, std::vector<StagePart>& parts, bool track = false) {
     const int fd = ::open(path, O_RDONLY); if (fd < 0) return false;
     struct stat sb; if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode) || sb.st_size < (1 << 20)) { ::close(fd); return false; }
     const size_t size = (size_t)sb.st_size;
@@ -361,13 +375,16 @@ static bool parse_plain_file_parallel(sage2ov_ctx* c, const char* path, std::vec
     for (size_t x = 1; x < nchunks; x++) cut[x] = std::max(cut[x - 1], boundary((size * x) / nchunks));
     using Part = StagePart;
     parts.clear(); parts.resize(nt); bool bad = false;
+    std::vector<uint64_t> chunkRec(track ? nchunks + 1 : 0, 0); std::vector<std::vector<std::pair<size_t, size_t>>> segs(track ? nt : 0);      // segs: (chunk, index into the thread's ord)
     #pragma omp parallel num_threads(nt)
     {
         Part& P = parts[omp_get_thread_num()]; std::string seq; std::vector<uint8_t> codes;
         #pragma omp for schedule(dynamic, 1)
         for (int64_t x = 0; x < (int64_t)nchunks; x++) {
             if (cut[x] >= cut[x + 1]) continue;
-            auto stage = [&](const char* b, size_t L) { codes.resize(L); for (size_t i = 0; i < L; i++) codes[i] = g_code[(unsigned char)b[i]]; stage_codes(c, codes.data(), (int)L, P.pool, P.off, P.lens, P.good, P.bp, P.small); P.records++; };
+            const uint64_t rec0 = P.records; if (track) segs[omp_get_thread_num()].emplace_back((size_t)x, P.ord.size());
+            auto note = [&](size_t before) { if (track && P.lens.size() > before) P.ord.push_back((uint32_t)(P.records - rec0)); };      // (before the record is counted)
+            auto stage = [&](const char* b, size_t L) { codes.resize(L); for (size_t i = 0; i < L; i++) codes[i] = g_code[(unsigned char)b[i]]; const size_t at = P.lens.size(); stage_codes(c, codes.data(), (int)L, P.pool, P.off, P.lens, P.good, P.bp, P.small); note(at); P.records++; };
             if (kind == '>') {
                 // records of one header line + one sequence line, packed straight from the mapping (eight bases per step); the first record that
                 // is anything else -- a second sequence line, white space inside the line, the last record of the chunk -- hands the rest of the chunk to the general reader
@@ -377,9 +394,10 @@ static bool parse_plain_file_parallel(sage2ov_ctx* c, const char* path, std::vec
                     const char* sq = nl1 + 1; const char* nl2 = (const char*)memchr(sq, '\n', (size_t)(m + e - sq)); if (!nl2 || nl2 + 1 >= m + e || nl2[1] != '>') break;
                     size_t n = (size_t)(nl2 - sq); if (n && sq[n - 1] == '\r') n--;
                     if (n == 0) break;
+                    const size_t at = P.lens.size();
                     const int st = stage_ascii(c, sq, n, P.pool, P.off, P.lens, P.good, P.bp, P.small);
                     if (st < 0) break;                                                                   // white space inside the line
-                    P.records++; p = (size_t)(nl2 + 1 - m);
+                    note(at); P.records++; p = (size_t)(nl2 + 1 - m);
                 }
                 if (p < e) {
                     SeqFile f; f.open_range(m + p, e - p); size_t len = 0;
@@ -397,19 +415,30 @@ static bool parse_plain_file_parallel(sage2ov_ctx* c, const char* path, std::vec
                         bad = true;
                         break;
                     }
-                    if (stage_ascii(c, m + l1, ns, P.pool, P.off, P.lens, P.good, P.bp, P.small) < 0) stage(m + l1, ns); else P.records++;     // (eight bases per step; longer than the 32-word layout: the table form)
+                    const size_t at = P.lens.size();
+                    if (stage_ascii(c, m + l1, ns, P.pool, P.off, P.lens, P.good, P.bp, P.small) < 0) stage(m + l1, ns); else { note(at); P.records++; }     // (eight bases per step; longer than the 32-word layout: the table form)
                     p = l4;
                 }
             }
+            if (track) chunkRec[x] = P.records - rec0;
         }
     }
     if (bad) return false;
+    if (track) {
+        uint64_t run = 0; for (size_t x = 0; x <= nchunks; x++) { const uint64_t r = chunkRec[x]; chunkRec[x] = run; run += r; }      // records in front of every chunk
+        if (run < PAIR_CALL_RECORDS_MAX) for (int t = 0; t < nt; t++) for (size_t g = 0; g < segs[t].size(); g++) {
+            const size_t e = g + 1 < segs[t].size() ? segs[t][g + 1].second : parts[t].ord.size(); const uint32_t base = (uint32_t)chunkRec[segs[t][g].first];
+            for (size_t i = segs[t][g].second; i < e; i++) parts[t].ord[i] += base;
+        }
+    }
     lap("split + filter + pack (threads)");
     return true;
 }
 // the threads' pools, one behind the other at the end of the context's staging arrays (each thread copies its own: the arrays are sized without being written)
-static void commit_parts(sage2ov_ctx* c, std::vector<StagePart>& parts) {
+// track: the parts' file ordinals o go behind the context's as o * mul + add (two mate files: 2 j and 2 j + 1)
+static void commit_parts(sage2ov_ctx* c, std::vector<StagePart>& parts, bool track = false, uint32_t mul = 1, uint32_t add = 0) {
     using Part = StagePart; const int nt = (int)parts.size(); HostLap lap(c, "input");
+    if (track) for (Part& P : parts) { for (uint32_t o : P.ord) c->pairOrd.push_back(o * mul + add); std::vector<uint32_t>().swap(P.ord); }      // (in the order the pools are laid down below)
     std::vector<uint64_t> wordBase(nt + 1), readBase(nt + 1); wordBase[0] = c->pool.size(); readBase[0] = c->poolOff.size();
     for (int t = 0; t < nt; t++) { wordBase[t + 1] = wordBase[t] + parts[t].pool.size(); readBase[t + 1] = readBase[t] + parts[t].off.size(); }
     c->pool.resize(wordBase[nt]); c->poolOff.resize(readBase[nt]); c->poolLen.resize(readBase[nt]);
@@ -425,29 +454,38 @@ static void commit_parts(sage2ov_ctx* c, std::vector<StagePart>& parts) {
     for (Part& P : parts) { c->goodReads += P.good; c->totalBP += P.bp; c->smallReads += P.small; c->totalReads += P.records; }
     lap("concatenation of the threads' pools");
 }
-static bool add_plain_file_parallel(sage2ov_ctx* c, const char* path) {
-    std::vector<StagePart> parts; if (!parse_plain_file_parallel(c, path, parts)) return false;
-    commit_parts(c, parts); return true;
+static bool add_plain_file_parallel(sage2ov_ctx* c, const char* path, bool track, uint64_t* records) {
+    std::vector<StagePart> parts; if (!parse_plain_file_parallel(c, path, parts, track)) return false;
+    *records = 0; for (auto& P : parts) *records += P.records;
+    commit_parts(c, parts, track && *records < PAIR_CALL_RECORDS_MAX); return true;
 }
 // Two mate files are read alternately, file 1 first, until the file whose turn it is has no record left (inputReader.cpp:26-49): with n1 = n2 or n1 = n2 + 1 records
 // that is every record of both files, and since the ids are ranks after the sort the order they are staged in is free -- both files then go through the parallel
 // reader one after the other.  Any other pair of counts (or a file the parallel reader does not take) is the sequential reader's business.
-static bool add_mate_files_parallel(sage2ov_ctx* c, const char* p1, const char* p2) {
-    std::vector<StagePart> a, b; if (!parse_plain_file_parallel(c, p1, a) || !parse_plain_file_parallel(c, p2, b)) return false;
+static bool add_mate_files_parallel(sage2ov_ctx* c, const char* p1, const char* p2, bool track, uint64_t* records) {
+    std::vector<StagePart> a, b; if (!parse_plain_file_parallel(c, p1, a, track) || !parse_plain_file_parallel(c, p2, b, track)) return false;
     uint64_t n1 = 0, n2 = 0; for (auto& P : a) n1 += P.records; for (auto& P : b) n2 += P.records;
     if (n1 != n2 && n1 != n2 + 1) return false;
-    commit_parts(c, a); commit_parts(c, b); return true;
+    *records = n1 + n2; track = track && *records < PAIR_CALL_RECORDS_MAX;
+    commit_parts(c, a, track, 2, 0); commit_parts(c, b, track, 2, 1); return true;      // (record j of file 1 is record 2 j of the alternating stream, record j of file 2 is 2 j + 1)
 }
 
 // records are split sequentially (cheap: memchr), filtered and packed by all threads in batches
-int add_files(sage2ov_ctx* c, const char* p1, const char* p2) {
-    if (!c->opt.get("SAGE2OV_SEQUENTIAL_READER") && ((p2 && *p2) ? add_mate_files_parallel(c, p1, p2) : add_plain_file_parallel(c, p1))) return SAGE2OV_OK;
+// pairLib != 0 (pairing): the call is also one mates call of that library -- the ordinal of every staged read is noted
+int add_files(sage2ov_ctx* c, const char* p1, const char* p2, int pairLib = 0) {
+    const bool track = pairLib != 0; const uint64_t first0 = c->poolLen.size(), ordAt0 = c->pairOrd.size(); uint64_t records = 0;
+    auto pair_done = [&]() -> int {                                   // the call as sage2ov_mates_from_reads will see it
+        if (!track) return SAGE2OV_OK;
+        if (records >= PAIR_CALL_RECORDS_MAX) return pair_call_limit(c);
+        c->pairCalls.push_back({pairLib, false, records, first0, c->poolLen.size() - first0, ordAt0}); return SAGE2OV_OK;
+    };
+    if (!c->opt.get("SAGE2OV_SEQUENTIAL_READER") && ((p2 && *p2) ? add_mate_files_parallel(c, p1, p2, track, &records) : add_plain_file_parallel(c, p1, track, &records))) return pair_done();
     SeqFile f1, f2; if (!f1.open(p1)) return c->fail(SAGE2OV_ERR_IO, std::string("cannot open ") + p1);
     const bool two = p2 && *p2; if (two && !f2.open(p2)) return c->fail(SAGE2OV_ERR_IO, std::string("cannot open ") + p2);
     const int nt = io_threads(c);
     const size_t BATCH = 1 << 19;
     std::string flat; std::vector<uint64_t> boff; uint64_t inFile = 0; bool more = true;
-    std::vector<std::vector<uint64_t>> pools(nt), offs(nt); std::vector<std::vector<uint16_t>> lens(nt);
+    std::vector<std::vector<uint64_t>> pools(nt), offs(nt); std::vector<std::vector<uint16_t>> lens(nt); std::vector<std::vector<uint32_t>> ords(track ? nt : 0);
     while (more) {
         flat.clear(); boff.clear(); boff.push_back(0);
         while (boff.size() <= BATCH) {                             // inputReader.cpp:26-49: alternate by parity
@@ -458,7 +496,8 @@ int add_files(sage2ov_ctx* c, const char* p1, const char* p2) {
         }
         const int64_t nb = (int64_t)boff.size() - 1; if (nb == 0) break;
         std::vector<uint64_t> good(nt, 0), bp(nt, 0), small(nt, 0);
-        for (int t = 0; t < nt; t++) { pools[t].clear(); offs[t].clear(); lens[t].clear(); }
+        for (int t = 0; t < nt; t++) { pools[t].clear(); offs[t].clear(); lens[t].clear(); if (track) ords[t].clear(); }
+        const uint64_t batch0 = inFile - (uint64_t)nb;                // records in front of this batch: the reader stages in input order and only has to count
         #pragma omp parallel num_threads(nt)
         {
             const int t = omp_get_thread_num(); const int64_t chunk = (nb + nt - 1) / nt, a = t * chunk, b = std::min<int64_t>(nb, a + chunk);
@@ -467,7 +506,9 @@ int add_files(sage2ov_ctx* c, const char* p1, const char* p2) {
                 const size_t L = boff[r + 1] - boff[r]; codes.resize(L);
                 const unsigned char* sq = (const unsigned char*)flat.data() + boff[r];
                 for (size_t i = 0; i < L; i++) codes[i] = g_code[sq[i]];
+                const size_t at = lens[t].size();
                 stage_codes(c, codes.data(), (int)L, pools[t], offs[t], lens[t], good[t], bp[t], small[t]);
+                if (track && lens[t].size() > at) ords[t].push_back((uint32_t)(batch0 + (uint64_t)r));
             }
         }
         for (int t = 0; t < nt; t++) {                              // concatenate in file order (thread t holds a contiguous slice)
@@ -475,15 +516,17 @@ int add_files(sage2ov_ctx* c, const char* p1, const char* p2) {
             c->pool.insert(c->pool.end(), pools[t].begin(), pools[t].end());
             for (uint64_t o : offs[t]) c->poolOff.push_back(base + o);
             c->poolLen.insert(c->poolLen.end(), lens[t].begin(), lens[t].end());
+            if (track) c->pairOrd.insert(c->pairOrd.end(), ords[t].begin(), ords[t].end());
             c->goodReads += good[t]; c->totalBP += bp[t]; c->smallReads += small[t];
         }
         c->totalReads += (uint64_t)nb;
     }
+    records = inFile;
     for (SeqFile* f : {&f1, &f2}) if (f->ioError) {
         int en = 0; const char* m = f->fp ? gzerror(f->fp, &en) : nullptr;
         return c->fail(SAGE2OV_ERR_IO, std::string("read error in ") + (f == &f1 ? p1 : p2) + ": " + (m && *m ? m : "corrupt or truncated input"));
     }
-    return SAGE2OV_OK;
+    return pair_done();
 }
 std::string trim(const std::string& s) { size_t a = s.find_first_not_of(" \t\r\n"), b = s.find_last_not_of(" \t\r\n"); return a == std::string::npos ? "" : s.substr(a, b - a + 1); }
 
@@ -663,27 +706,38 @@ int sage2ov_options_reload(sage2ov_ctx* c) { if (!c) return SAGE2OV_ERR_ARG; c->
 int sage2ov_reads_add_ascii(sage2ov_ctx* c, const char* bases, const uint64_t* off, uint64_t n) {
     if (!c || !bases || !off) return SAGE2OV_ERR_ARG;
     if (c->organized) return c->fail(SAGE2OV_ERR_ARG, "reads already organised");
+    if (c->pairLib && n >= PAIR_CALL_RECORDS_MAX) return pair_call_limit(c);
     if (c->gpu() && !c->opt.get("SAGE2OV_HOST_PACK") && !c->opt.get("SAGE2OV_HOST_ORGANIZE")) {        // staged as they come: the device filters and packs them
         if (c->asciiOff.empty()) c->asciiOff.push_back(0);
         const uint64_t base = c->ascii.size(), first = off[0], bytes = off[n] - first;
         c->ascii.insert(c->ascii.end(), bases + first, bases + first + bytes);
+        if (c->pairLib) c->pairCalls.push_back({c->pairLib, true, n, (uint64_t)c->asciiOff.size() - 1, 0, 0});      // (raw input: a record's ordinal is its index)
         for (uint64_t r = 1; r <= n; r++) c->asciiOff.push_back(base + (off[r] - first));
         c->totalReads += n;
         return SAGE2OV_OK;
     }
-    std::vector<uint8_t> codes;
+    std::vector<uint8_t> codes; const uint64_t first0 = c->poolLen.size(), ordAt0 = c->pairOrd.size();
     for (uint64_t r = 0; r < n; r++) {
         const int L = (int)(off[r + 1] - off[r]); codes.resize(L);
         for (int i = 0; i < L; i++) codes[i] = g_code[(unsigned char)bases[off[r] + i]];
+        const size_t at = c->poolLen.size();
         stage_codes(c, codes.data(), L, c->pool, c->poolOff, c->poolLen, c->goodReads, c->totalBP, c->smallReads);
+        if (c->pairLib && c->poolLen.size() > at) c->pairOrd.push_back((uint32_t)r);
         c->totalReads++;
     }
+    if (c->pairLib) c->pairCalls.push_back({c->pairLib, false, n, first0, c->poolLen.size() - first0, ordAt0});
     return SAGE2OV_OK;
 }
 int sage2ov_reads_add_file(sage2ov_ctx* c, const char* p1, const char* p2) {
     if (!c || !p1) return SAGE2OV_ERR_ARG;
     if (c->organized) return c->fail(SAGE2OV_ERR_ARG, "reads already organised");
-    return add_files(c, p1, p2);
+    return add_files(c, p1, p2, c->pairLib);
+}
+int sage2ov_reads_pair_library(sage2ov_ctx* c, int library) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    if (c->organized) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_reads_pair_library: reads already organised");
+    if (library < 0 || library > 127) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_reads_pair_library: the library must be 0 (off) or 1 .. 127");
+    c->pairLib = library; return SAGE2OV_OK;
 }
 int sage2ov_reads_add_list(sage2ov_ctx* c, const char* lp) {                         // readLoader.cpp:73-131
     if (!c || !lp) return SAGE2OV_ERR_ARG;
@@ -695,9 +749,11 @@ int sage2ov_reads_add_list(sage2ov_ctx* c, const char* lp) {                    
         size_t p = line.find('=');
         if (p == std::string::npos) { rc = c->fail(SAGE2OV_ERR_IO, "list of input files in a wrong format"); break; }
         std::string var = trim(line.substr(0, p)), val = trim(line.substr(p + 1));
+        const int lib = c->pairLib ? (int)(mate / 2) + 1 : 0;                            // with pairing: dataset i is library i (matePair.cpp:102, :107)
+        if (lib > 127 && (var == "f" || var == "f2")) { rc = c->fail(SAGE2OV_ERR_ARG, "sage2ov_reads_add_list: more than 127 datasets with pairing on"); break; }
         if (mate % 2 == 0 && var == "f1") val1 = val;
-        else if (mate % 2 == 0 && var == "f") { rc = add_files(c, val.c_str(), nullptr); mate++; }
-        else if (mate % 2 == 1 && var == "f2") rc = add_files(c, val1.c_str(), val.c_str());
+        else if (mate % 2 == 0 && var == "f") { rc = add_files(c, val.c_str(), nullptr, lib); mate++; }
+        else if (mate % 2 == 1 && var == "f2") rc = add_files(c, val1.c_str(), val.c_str(), lib);
         else { rc = c->fail(SAGE2OV_ERR_IO, "list of input files in a wrong format"); }
         if (rc) break;
         mate++;
@@ -758,14 +814,22 @@ int sage2ov_reads_organize(sage2ov_ctx* c) {                                    
     const int nthr = io_threads(c);                                                   // (clauses, not omp_set_num_threads: a library call must not change the host's OpenMP state)
     if (!c->asciiOff.empty() && !c->poolLen.empty()) {                                // both kinds of input staged: pack the ASCII here and organise one pool
         std::vector<uint8_t> codes; const uint64_t na = c->asciiOff.size() - 1;
-        for (uint64_t r = 0; r < na; r++) { const int L = (int)(c->asciiOff[r + 1] - c->asciiOff[r]); codes.resize(L); for (int i = 0; i < L; i++) codes[i] = g_code[(unsigned char)c->ascii[c->asciiOff[r] + i]];
-            stage_codes(c, codes.data(), L, c->pool, c->poolOff, c->poolLen, c->goodReads, c->totalBP, c->smallReads); }
+        auto stage_raw = [&](uint64_t r) { const int L = (int)(c->asciiOff[r + 1] - c->asciiOff[r]); codes.resize(L); for (int i = 0; i < L; i++) codes[i] = g_code[(unsigned char)c->ascii[c->asciiOff[r] + i]];
+            stage_codes(c, codes.data(), L, c->pool, c->poolOff, c->poolLen, c->goodReads, c->totalBP, c->smallReads); };
+        uint64_t r = 0;
+        for (auto& P : c->pairCalls) if (P.raw) {                                      // (pairing: a raw call becomes a pool call; the raw calls are disjoint and ascend, and the staging order is free)
+            for (; r < P.first; r++) stage_raw(r);
+            const uint64_t first0 = c->poolLen.size(), ordAt0 = c->pairOrd.size();
+            for (; r < P.first + P.records; r++) { const size_t at = c->poolLen.size(); stage_raw(r); if (c->poolLen.size() > at) c->pairOrd.push_back((uint32_t)(r - P.first)); }
+            P.raw = false; P.first = first0; P.count = c->poolLen.size() - first0; P.ordAt = ordAt0;
+        }
+        for (; r < na; r++) stage_raw(r);
         std::vector<char>().swap(c->ascii); std::vector<uint64_t>().swap(c->asciiOff);
     }
     if (!c->asciiOff.empty()) {                                                       // ASCII only: step 1 entirely on the device
         OrgAscii A{c->ascii.data(), c->ascii.size(), c->asciiOff.data(), c->asciiOff.size() - 1};
         uint64_t N = 0;
-        int rc = dev_organize_reads(c->device(), nullptr, 0, nullptr, nullptr, 0, 0, 0, 0, (int)c->cfg.min_overlap, &N, c->words, c->freq, c->err, &A);
+        int rc = dev_organize_reads(c->device(), nullptr, 0, nullptr, nullptr, 0, 0, 0, 0, (int)c->cfg.min_overlap, &N, c->words, c->freq, c->err, &A, !c->pairCalls.empty());
         if (rc) return rc;
         c->goodReads += A.good; c->totalBP += A.total_bp; c->smallReads += A.small; c->maxL = A.maxL; c->S = A.S;
         c->N = N; c->len.assign(N + 1, 0);
@@ -773,6 +837,7 @@ int sage2ov_reads_organize(sage2ov_ctx* c) {                                    
         for (uint64_t i = 1; i <= N; i++) c->len[i] = (uint16_t)(c->words[i * c->S + c->S - 1] & SLOT_LEN_MASK);
         std::vector<char>().swap(c->ascii); std::vector<uint64_t>().swap(c->asciiOff);
         c->organized = true; c->mates_forget(); c->indexBuilt = c->probed = c->reciprocalDone = c->reduced = c->converted = false;
+        c->pairReady = c->pairOnDevice = !c->pairCalls.empty();
         return SAGE2OV_OK;
     }
     const uint64_t n = c->poolLen.size(); HostLap lap(c, "step 1");
@@ -786,7 +851,7 @@ int sage2ov_reads_organize(sage2ov_ctx* c) {                                    
         int minL = n ? 0xFFFF : 0; for (uint64_t i = 0; i < n; i++) minL = std::min<int>(minL, c->poolLen[i]);
         lap("length scans");
         int rc = dev_organize_reads(c->device(), c->pool.data(), c->pool.size(), c->poolOff.data(), c->poolLen.data(), n, c->S, minL, c->maxL, (int)c->cfg.min_overlap,
-                                    &N, c->words, c->freq, c->err);
+                                    &N, c->words, c->freq, c->err, nullptr, !c->pairCalls.empty());
         if (rc) return rc;
         lap("device organiser (incl. transfers)");
         c->N = N; c->len.assign(N + 1, 0);
@@ -795,10 +860,12 @@ int sage2ov_reads_organize(sage2ov_ctx* c) {                                    
         RawU64().swap(c->pool); RawU64().swap(c->poolOff); RawU16().swap(c->poolLen);
         lap("lengths + release of the staging");
         c->organized = true; c->mates_forget(); c->indexBuilt = c->probed = c->reciprocalDone = c->reduced = c->converted = false;
+        c->pairReady = c->pairOnDevice = !c->pairCalls.empty();
         return SAGE2OV_OK;
     }
+    const bool pairing = !c->pairCalls.empty(); std::vector<uint8_t> fwd(pairing ? n : 0);      // pairing: whether every staged read stayed as given (the sign of its id)
     #pragma omp parallel for num_threads(nthr)
-    for (uint64_t i = 0; i < n; i++) canonicalise_words(&c->pool[c->poolOff[i]], c->poolLen[i]);
+    for (uint64_t i = 0; i < n; i++) { const bool f = canonicalise_words(&c->pool[c->poolOff[i]], c->poolLen[i]); if (pairing) fwd[i] = f; }
     std::vector<uint32_t> ord(n);
     #pragma omp parallel for num_threads(nthr)
     for (uint64_t i = 0; i < n; i++) ord[i] = (uint32_t)i;
@@ -819,9 +886,11 @@ int sage2ov_reads_organize(sage2ov_ctx* c) {                                    
     __gnu_parallel::sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return cmp(a, b) < 0; }, __gnu_parallel::default_parallel_tag(nthr));   // readLoader.cpp:221
     // unique + frequency (readLoader.cpp:225-235)
     std::vector<uint32_t> firstOf; firstOf.reserve(n); std::vector<uint16_t> fr; fr.reserve(n);
+    if (pairing) c->pairIds.assign(n, 0);
     for (uint64_t x = 0; x < n; x++) {
         if (x == 0 || cmp(ord[x - 1], ord[x]) != 0) { firstOf.push_back(ord[x]); fr.push_back(0); }
         fr.back()++;                                                                  // u16 wrap like the reference
+        if (pairing) { const int32_t id = (int32_t)firstOf.size(); c->pairIds[ord[x]] = fwd[ord[x]] ? id : -id; }      // the sign of sage2ov_reads_find_ids
     }
     const uint64_t N = firstOf.size(); const int S = c->S;
     c->N = N; c->words.assign((N + 1) * S, 0); c->len.assign(N + 1, 0); c->freq.assign(N + 1, 0);
@@ -834,7 +903,9 @@ int sage2ov_reads_organize(sage2ov_ctx* c) {                                    
         c->len[i] = (uint16_t)L; c->freq[i] = fr[i - 1];
     }
     RawU64().swap(c->pool); RawU64().swap(c->poolOff); RawU16().swap(c->poolLen);
-    return upload(c);
+    const int rc = upload(c);
+    if (rc == SAGE2OV_OK) c->pairReady = pairing; else std::vector<int32_t>().swap(c->pairIds);
+    return rc;
 }
 
 int sage2ov_reads_stats(const sage2ov_ctx* c, sage2ov_read_stats* o) {
@@ -1248,8 +1319,48 @@ int sage2ov_mates_export(sage2ov_ctx* c, int library, sage2ov_mate* out, uint64_
 }
 int sage2ov_mates_clear(sage2ov_ctx* c) {
     if (!c) return SAGE2OV_ERR_ARG;
-    if (Device* d = c->device()) { dev_mates_clear(d); dev_readmap_drop_joins(d); }    // (the read-to-edge table describes the graph, not the mates: it stays)
+    if (Device* d = c->device()) { dev_mates_clear(d); dev_readmap_drop_joins(d); dev_pairing_release(d); }    // (the read-to-edge table describes the graph, not the mates: it stays)
     c->mates_forget(false); return SAGE2OV_OK;
+}
+// The mate table of the reads this context organised, from step 1's own by-products: every reads_add_* call made with pairing on is one mates
+// call.  Per call a dense slotOf[ordinal] = staging index + 1 (0: the record was not staged), then per pair both ids or a skip; the records and everything behind
+// them are those of the mates_add_* route (mates_end / dev_mates_flush).
+int sage2ov_mates_from_reads(sage2ov_ctx* c) {
+    if (!c) return SAGE2OV_ERR_ARG;
+    if (!c->organized) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_mates_from_reads: organise the reads first");
+    if (!c->pairReady) return c->fail(SAGE2OV_ERR_ARG, "sage2ov_mates_from_reads: the reads were not staged with pairing on (sage2ov_reads_pair_library), or their pairing was used or cleared");
+    if (c->gpu() && !c->device()) return c->fail(SAGE2OV_ERR_DEVICE, c->devErr);
+    int rc = SAGE2OV_OK;
+    for (const auto& P : c->pairCalls) {
+        const int lib = P.lib; MateCall M; rc = mates_begin(c, lib, M);
+        const uint64_t pair0 = c->matePairs[lib], np = P.records / 2;                   // (a trailing odd record has no mate, matePair.cpp:172)
+        if (rc == SAGE2OV_OK && c->pairOnDevice) {
+            rc = mates_place(c, lib, true); M.routeKnown = M.onDevice = rc == SAGE2OV_OK;
+            if (rc == SAGE2OV_OK) rc = dev_mates_pair_call(c->device(), P.raw, P.raw ? nullptr : c->pairOrd.data() + P.ordAt, P.count, P.first, P.records, lib, pair0, &M.ds, c->err);
+        } else if (rc == SAGE2OV_OK && P.raw) rc = c->fail(SAGE2OV_ERR_INTERNAL, "pairing: a raw call without the device's ids");
+        else if (rc == SAGE2OV_OK) {
+            if (c->device() && c->mateOnDevice[lib]) rc = mates_place(c, lib, false);
+            M.routeKnown = true;
+            std::vector<uint32_t> slotOf(P.records, 0);
+            for (uint64_t x = 0; x < P.count; x++) slotOf[c->pairOrd[P.ordAt + x]] = (uint32_t)(P.first + x + 1);
+            for (uint64_t j = 0; rc == SAGE2OV_OK && j < np; j++) {
+                const uint32_t sa = slotOf[2 * j], sb = slotOf[2 * j + 1];
+                M.ds.seen++;
+                if (!sa || !sb) { M.ds.not_good++; continue; }                         // only a read that is not good is not staged: "not in the store" cannot happen
+                const int64_t a = c->pairIds[sa - 1], b = c->pairIds[sb - 1];
+                const uint64_t id1 = (uint64_t)llabs(a), id2 = (uint64_t)llabs(b), t1 = a > 0, t2 = b > 0, o = 2 * (pair0 + j);
+                M.rec.emplace_back((id1 << 32) | (id2 << 2) | (t1 << 1) | t2, o);
+                M.rec.emplace_back((id2 << 32) | (id1 << 2) | (t2 << 1) | t1, o + 1);
+                M.ds.added++;
+            }
+        }
+        if (rc == SAGE2OV_OK) c->matePairs[lib] += np;
+        rc = mates_end(c, M, rc);
+        if (rc) break;
+    }
+    if (Device* d = c->device()) dev_pairing_release(d);
+    c->pairing_forget();
+    return rc;
 }
 int sage2ov_mates_stats_get(const sage2ov_ctx* c, sage2ov_mate_stats* o) { if (!c || !o) return SAGE2OV_ERR_ARG; *o = c->mstats; return SAGE2OV_OK; }
 int sage2ov_reads_set_totals(sage2ov_ctx* c, uint64_t good, uint64_t bp) { if (!c) return SAGE2OV_ERR_ARG; c->goodReads = good; c->totalBP = bp; return SAGE2OV_OK; }

@@ -125,7 +125,14 @@ inline void touch_pages(void* p, size_t bytes, int nt) {
 // ASCII input of step 1 (sage2ov_reads_add_ascii): raw bases + offsets in, filter / pack / canonical orientation on the device; the counters come back
 struct OrgAscii { const char* bases; uint64_t nbytes; const uint64_t* off; uint64_t n_in; uint64_t good = 0, total_bp = 0, small = 0; int maxL = 0, minL = 0, S = 0; };
 int dev_organize_reads(Device* d, const uint64_t* pool, uint64_t pool_words, const uint64_t* off, const uint16_t* len, uint64_t n, int S, int minL, int maxL, int k,
-                       uint64_t* N_out, RawU64& words_out, RawU16& freq_out, std::string& err, OrgAscii* ascii = nullptr);
+                       uint64_t* N_out, RawU64& words_out, RawU16& freq_out, std::string& err, OrgAscii* ascii = nullptr, bool pairing = false);
+// pairing (sage2ov_reads_pair_library): dev_organize_reads(..., pairing) also leaves +-id of every staged read on the device (of every raw record on
+// the ASCII route, 0 for one that was not staged), 4 bytes each, until dev_pairing_release or the read set goes.  dev_mates_pair_call: one reads_add_* call as one
+// mates call -- `records` input records; ord: the call's staged reads are entries [first, first + nStaged) of the staging and ord[x] < records is the ordinal of the
+// x-th; raw: the call's records are raw records [first, first + records).  Its records go to the pending buffer as dev_mates_add's do; dev_mates_flush ends the call.
+struct MateStats;
+int dev_mates_pair_call(Device* d, bool raw, const uint32_t* ord, uint64_t nStaged, uint64_t first, uint64_t records, int library, uint64_t pair0, MateStats* st, std::string& err);
+void dev_pairing_release(Device* d);
 // which way the last dev_reduce_device went (the words of sage2ov_reduce_stats_get)
 void dev_reduce_stats(Device* d, uint64_t out[SAGE2OV_REDUCE_STATS]);
 int dev_reduce_device(Device* d, uint64_t min_unresolved, uint64_t* n_unresolved, uint64_t* n_hits, uint64_t* inserted, uint64_t* removed, int* done, std::string& err,
