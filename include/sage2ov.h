@@ -441,7 +441,8 @@ int sage2ov_copycount_stats_get(const sage2ov_ctx* ctx, sage2ov_copycount_stats*
 #define SAGE2OV_MCF_DEFAULT_ROUNDS (1ull << 22)
 #define SAGE2OV_MCF_PHASES 24               /* epsilon phases whose rounds and times the statistics keep (2^62 needs 21; 128-bit prices can need more: the first 24 are kept) */
 #define SAGE2OV_MCF_FORM_LDS 1              /* one workgroup, the network in LDS: at most 512 nodes and 1024 arcs */
-#define SAGE2OV_MCF_FORM_LAUNCHES 2         /* two launches per round, the rounds counted on the host */
+#define SAGE2OV_MCF_FORM_LAUNCHES 2         /* two launches per round (six where the network has hub nodes), the rounds counted on the host */
+#define SAGE2OV_MCF_HUB_DEG 65536           /* the launches form: a node whose list (arcs out and in) is longer is a hub -- its list is walked by a workgroup per tile of its entries, not by the node's own */
 typedef struct sage2ov_mcf_arc { uint32_t from, to; int32_t lower, upper; int64_t cost; } sage2ov_mcf_arc;      /* cs2/parser_cs2.h:232-262: `a from to lower upper cost` */
 typedef struct sage2ov_mcf_stats {
     uint64_t nodes, arcs, scale;                       /* scale = nodes + 1 */
@@ -475,6 +476,10 @@ int sage2ov_flow_solution_commit(sage2ov_ctx* ctx);
 /* the whole of step 5 (main.cpp -m 5; computeMinCostFlow, :105-417): estimate, build, solve, commit */
 int sage2ov_copy_counts(sage2ov_ctx* ctx, uint64_t* genome_size);
 int sage2ov_mcf_stats_get(const sage2ov_ctx* ctx, sage2ov_mcf_stats* out);              /* of the last solve */
+/* the hub form in the last solve: out[0] the threshold in force (0: off -- the single-workgroup form, or no solve yet), out[1] the entries of a tile, out[2] hub nodes,
+ * out[3] tiles, out[4] entries the hub form pushed along (they are among sage2ov_mcf_stats.pushes), out[5] relabels it made (among .relabels).  The flows, prices
+ * and counters of a solve do not depend on the threshold.  SAGE2OV_ERR_DEVICE on a device-less context */
+int sage2ov_mcf_hub_stats_get(const sage2ov_ctx* ctx, uint64_t out[6]);
 
 /* ---- the sweep of ContigExtender::findMatepairSupports (matePair/mergeContigs.cpp:959-1030): getSupportOfEdges (:1032-1097) over isUniqueInEdge (:1102-1110) for every
  * incoming x outgoing pair of composite edges of every node, on the device; all quantities are integers.  The merge that follows it in the

@@ -164,6 +164,7 @@ GENOME_ROUNDS = 10
 MCF_ARC_DTYPE = np.dtype([("from", np.uint32), ("to", np.uint32), ("lower", np.int32), ("upper", np.int32), ("cost", np.int64)])      # sage2ov_mcf_arc
 MCF_PHASES = 24
 MCF_FORM_LDS, MCF_FORM_LAUNCHES = 1, 2
+MCF_HUB_DEG = 65536                      # SAGE2OV_MCF_HUB_DEG: lists longer than this take the hub form of the launches
 
 
 def wide_prices(words):
@@ -620,6 +621,12 @@ class Context:
         s = McfStats()
         self._chk(lib().sage2ov_mcf_stats_get(self._h, C.byref(s)))
         return s
+
+    def mcf_hub_stats(self) -> dict:
+        """the hub form in the last solve: the threshold in force (0: off), the entries of a tile, hub nodes, tiles, entries pushed along and relabels by the hub form"""
+        out = (C.c_uint64 * 6)()
+        self._chk(lib().sage2ov_mcf_hub_stats_get(self._h, out))
+        return dict(zip(("hub_deg", "tile", "hubs", "tiles", "hub_pushes", "hub_relabels"), (int(x) for x in out)))
 
     def copycount_stats(self) -> CopyCountStats:
         s = CopyCountStats()

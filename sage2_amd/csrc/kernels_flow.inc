@@ -15,9 +15,18 @@
 //   k_mf_push        every node with excess > 0 walks its list in order and pushes min(residual, what is left of the excess it had when the phase began) along
 //                    every admissible entry.  What a node receives goes to delta[], not to excess[]: no decision depends on another node's pushes of the same phase.
 //                    Lists of up to MF_LANE_DEG entries: a lane per node.  Longer lists: the workgroup walks the list MF_BLOCK entries at a time, an exclusive
-//                    scan of the admissible residuals clipped to the excess -- the same amounts as the serial walk.
+//                    scan of the admissible residuals clipped to the excess -- the same amounts as the serial walk.  Lists longer than hubDeg (an argument;
+//                    SAGE2OV_MCF_HUB_DEG) are left to the hub form below.
 //   k_mf_relabel     excess += delta.  A node with excess > 0 and no admissible entry: p = max over residual entries of p(head) - cost - eps, read from the prices
 //                    of the phase's start and written to the other price buffer (every node writes its price there).  Below the floor: the infeasible flag.
+//   k_mf_hub_count, k_mf_hub_mark, k_mf_hub_tables   the hubs of a solve -- the nodes whose list is longer than hubDeg -- found once behind k_mf_starts: counted,
+//                    then ranked by the project's scan (ascending node number, the same tables on every run): per hub its node and its first tile, per tile of
+//                    MF_HUB_TILE consecutive entries its hub and its first entry.
+//   k_mf_hub_sum, k_mf_hub_push   the push of a hub's list by a workgroup per tile, in two launches over the tile table: per tile the sum of its admissible
+//                    residuals and per hub a snapshot of its excess; then every tile adds up the sums of the hub's earlier tiles (its base), and clips its entries'
+//                    amounts against the snapshot behind that base -- the serial walk's amounts, number for number.
+//   k_mf_hub_rel, k_mf_hub_rel_fin   the relabel of a hub with excess > 0, behind k_mf_relabel: per tile the pair (any admissible entry, max of p(head) - cost - eps
+//                    over residual entries), then a workgroup per hub combines the pairs and writes as k_mf_relabel does.
 //   k_mf_pu_init, k_mf_pu_relax, k_mf_pu_apply   the price update: distances to the nodes with excess < 0, one thread per entry and an integer atomic min
 //                    per improvement, launched until a launch changes nothing; the distances are unique, so the order of the improvements does not matter.
 //   k_mf_lds         the whole solve by one workgroup between __syncthreads(), for networks of at most MF_LDS_NODES nodes and MF_LDS_ENTRIES entries; the same
@@ -28,13 +37,17 @@
 
 struct McfArc { u32 from, to; int lower, upper; long long cost; };                    // = sage2ov_mcf_arc
 constexpr u32 MF_BLOCK = 256, MF_LANE_DEG = 64;
+constexpr u32 MF_HUB_TILE = 2048;                                                      // entries of a hub's list per workgroup of the hub form
+static_assert(MF_HUB_TILE % MF_BLOCK == 0, "a tile is whole chunks of the workgroup's walk");
+constexpr u32 MF_NO_HUBS = 0xFFFFFFFFu;                                                // hubDeg of the round kernels when the hub form is off: no list is longer
 constexpr u32 MF_LDS_NODES = 512, MF_LDS_ENTRIES = 2048;
 constexpr int MF_ALPHA = 8;
 constexpr u32 MF_PERIOD = 64;                                                          // rounds of a refine between two price updates; the first precedes its first round
 constexpr u32 MF_BATCH = 32;                                                           // rounds between two reads of the counter block
 // the counter block
 constexpr u32 MF_ACT = 0, MF_PUSHES = MF_BATCH, MF_RELABELS = MF_BATCH + 1, MF_FLAGS = MF_BATCH + 2, MF_MAXC = MF_BATCH + 3, MF_ROUNDS = MF_BATCH + 4, MF_PHASES = MF_BATCH + 5,
-              MF_TTS = MF_BATCH + 6, MF_UPDATES = MF_BATCH + 7, MF_CTRS = MF_BATCH + 8;
+              MF_TTS = MF_BATCH + 6, MF_UPDATES = MF_BATCH + 7, MF_HUBS = MF_BATCH + 8, MF_HUB_TILES = MF_BATCH + 9, MF_HUB_PUSHES = MF_BATCH + 10, MF_HUB_RELABELS = MF_BATCH + 11,
+              MF_CTRS = MF_BATCH + 12;
 constexpr unsigned long long MF_F_BADARC = 1, MF_F_NAN = 2, MF_F_INFEASIBLE = 4, MF_F_RANGE = 8, MF_F_LIMIT = 16;
 constexpr long long MF_INF = 1ll << 62;                                                // the distance of a node that reaches no deficit; the bound of 64-bit prices
 typedef __int128 i128;
@@ -132,7 +145,7 @@ __device__ __forceinline__ long long mf_block_scan(long long x, long long* wsum,
     *total = tot; return base + inc - x;
 }
 
-template <class P> __global__ void __launch_bounds__(MF_BLOCK) k_mf_push(MfNet N, const P* __restrict__ p, unsigned long long* ctr) {
+template <class P> __global__ void __launch_bounds__(MF_BLOCK) k_mf_push(MfNet N, const P* __restrict__ p, u32 hubDeg, unsigned long long* ctr) {
     __shared__ u32 hv[MF_BLOCK]; __shared__ u32 nhv, sPush; __shared__ long long wsum[MF_BLOCK / 64];
     const u32 tid = threadIdx.x; const u64 v64 = (u64)blockIdx.x * MF_BLOCK + tid + 1;
     if (tid == 0) { nhv = 0; sPush = 0; }
@@ -142,7 +155,7 @@ template <class P> __global__ void __launch_bounds__(MF_BLOCK) k_mf_push(MfNet N
         const u32 v = (u32)v64; long long e = N.excess[v];
         if (e > 0) {
             const u32 s0 = N.start[v], s1 = N.start[v + 1];
-            if (s1 - s0 > MF_LANE_DEG) hv[atomicAdd(&nhv, 1u)] = v;
+            if (s1 - s0 > MF_LANE_DEG) { if (s1 - s0 <= hubDeg) hv[atomicAdd(&nhv, 1u)] = v; }      // (a hub: k_mf_hub_sum / k_mf_hub_push)
             else {
                 const P pv = p[v];
                 for (u32 s = s0; s < s1 && e > 0; s++) {
@@ -179,7 +192,7 @@ template <class P> __global__ void __launch_bounds__(MF_BLOCK) k_mf_push(MfNet N
 }
 
 // act: the word that counts the nodes with excess > 0 of this round
-template <class P> __global__ void __launch_bounds__(MF_BLOCK) k_mf_relabel(MfNet N, const P* __restrict__ p, P* pn, P eps, P floor, unsigned long long* act, unsigned long long* ctr) {
+template <class P> __global__ void __launch_bounds__(MF_BLOCK) k_mf_relabel(MfNet N, const P* __restrict__ p, P* pn, P eps, P floor, u32 hubDeg, unsigned long long* act, unsigned long long* ctr) {
     __shared__ u32 hv[MF_BLOCK]; __shared__ u32 nhv, sAct, sRel, sBad; __shared__ P wbest[MF_BLOCK / 64]; __shared__ u32 wadm[MF_BLOCK / 64];
     const u32 tid = threadIdx.x; const u64 v64 = (u64)blockIdx.x * MF_BLOCK + tid + 1;
     if (tid == 0) { nhv = 0; sAct = 0; sRel = 0; sBad = 0; }
@@ -191,7 +204,7 @@ template <class P> __global__ void __launch_bounds__(MF_BLOCK) k_mf_relabel(MfNe
         if (e > 0) {
             atomicAdd(&sAct, 1u);
             const u32 s0 = N.start[v], s1 = N.start[v + 1];
-            if (s1 - s0 > MF_LANE_DEG) hv[atomicAdd(&nhv, 1u)] = v;
+            if (s1 - s0 > MF_LANE_DEG) { if (s1 - s0 <= hubDeg) hv[atomicAdd(&nhv, 1u)] = v; }      // (a hub: k_mf_hub_rel / k_mf_hub_rel_fin)
             else {
                 bool adm = false; P best = -mf_inf<P>();
                 for (u32 s = s0; s < s1; s++) {
@@ -203,7 +216,7 @@ template <class P> __global__ void __launch_bounds__(MF_BLOCK) k_mf_relabel(MfNe
                 if (!adm) { if (best < floor) atomicOr(&sBad, 1u); else { pv = best; atomicAdd(&sRel, 1u); } }
             }
         }
-        pn[v] = pv;                                                                    // (a long list's node: overwritten below when it is relabelled)
+        pn[v] = pv;                                                                    // (a long list's node: overwritten below, a hub's by k_mf_hub_rel_fin, when it is relabelled)
     }
     __syncthreads();
     const u32 cnt = nhv;
@@ -231,6 +244,142 @@ template <class P> __global__ void __launch_bounds__(MF_BLOCK) k_mf_relabel(MfNe
         if (sAct) atomicAdd(act, (unsigned long long)sAct);
         if (sRel) atomicAdd(&ctr[MF_RELABELS], (unsigned long long)sRel);
         if (sBad) atomicOr(&ctr[MF_FLAGS], MF_F_INFEASIBLE);
+    }
+}
+
+// ---- the hub form: lists longer than hubDeg, a workgroup per tile of MF_HUB_TILE entries.  The method and every number it produces are k_mf_push's and
+// k_mf_relabel's; what differs is who walks the list.  As everywhere in this file no workgroup waits for another: what one launch hands to the next goes through
+// memory and the order of the launches in the stream.
+struct MfHubs {                  // node[h]: the h-th hub in ascending node number; tile0[h] .. tile0[h + 1]: its tiles; tileHub[t], tileBeg[t]: a tile's hub, its first entry
+    const u32 *node, *tile0, *tileHub, *tileBeg; long long *snap, *tsum; u32 H, T;
+};
+__device__ __forceinline__ u32 mf_hub_tiles(u32 deg) { return (deg + MF_HUB_TILE - 1) / MF_HUB_TILE; }
+// the two counts, for the host to size the tables by (sums of integers: the same on every run)
+__global__ void k_mf_hub_count(const u32* __restrict__ start, u32 n, u32 hubDeg, unsigned long long* ctr) {
+    const u64 v = (u64)blockIdx.x * blockDim.x + threadIdx.x + 1;
+    u32 tiles = 0;
+    if (v <= n) { const u32 deg = start[v + 1] - start[v]; if (deg > hubDeg) tiles = mf_hub_tiles(deg); }
+    const u64 hubs = __ballot(tiles != 0);
+    u32 t = tiles; for (int d = 32; d >= 1; d >>= 1) t += __shfl_down(t, d);
+    if (lane_id() == 0 && hubs) { atomicAdd(&ctr[MF_HUBS], (unsigned long long)__popcll(hubs)); atomicAdd(&ctr[MF_HUB_TILES], (unsigned long long)t); }
+}
+// isHub[v - 1], nTiles[v - 1]: the inputs of the two scans
+__global__ void k_mf_hub_mark(const u32* __restrict__ start, u32 n, u32 hubDeg, u32* isHub, u32* nTiles) {
+    const u64 v = (u64)blockIdx.x * blockDim.x + threadIdx.x + 1; if (v > n) return;
+    const u32 deg = start[v + 1] - start[v]; const bool hub = deg > hubDeg;
+    isHub[v - 1] = hub ? 1u : 0u; nTiles[v - 1] = hub ? mf_hub_tiles(deg) : 0u;
+}
+// rank, tileRank: the exclusive scans of the two.  A hub's thread fills its own tiles: at most list length / MF_HUB_TILE + 1 of them
+__global__ void k_mf_hub_tables(const u32* __restrict__ start, u32 n, u32 hubDeg, const u32* __restrict__ rank, const u32* __restrict__ tileRank, u32 H, u32 T,
+                                u32* node, u32* tile0, u32* tileHub, u32* tileBeg) {
+    const u64 v = (u64)blockIdx.x * blockDim.x + threadIdx.x + 1; if (v > n) return;
+    if (v == 1) tile0[H] = T;
+    const u32 s0 = start[v], deg = start[v + 1] - s0; if (deg <= hubDeg) return;
+    const u32 h = rank[v - 1], t0 = tileRank[v - 1], nt = mf_hub_tiles(deg);
+    if (h >= H || t0 > T || nt > T - t0) return;                                       // (the counts the tables were sized by are sums of the same numbers)
+    node[h] = (u32)v; tile0[h] = t0;
+    for (u32 t = 0; t < nt; t++) { tileHub[t0 + t] = h; tileBeg[t0 + t] = s0 + t * MF_HUB_TILE; }
+}
+
+// the sum of x over the workgroup, in every thread.  wsum: MF_BLOCK / 64 words of LDS
+__device__ __forceinline__ long long mf_block_sum(long long x, long long* wsum) {
+    for (int d = 32; d >= 1; d >>= 1) x += __shfl_down(x, d);
+    if ((threadIdx.x & 63u) == 0) wsum[threadIdx.x >> 6] = x;
+    __syncthreads();
+    long long tot = 0; for (u32 i = 0; i < MF_BLOCK / 64; i++) tot += wsum[i];
+    __syncthreads();
+    return tot;
+}
+// The push over a hub, first launch (grid: the tiles).  tsum[t]: the admissible residuals of tile t (residual > 0, reduced cost < 0, the prices of the round's
+// start); snap[h]: the hub's excess as this round found it.  Tiles of a hub without excess write no sum: nobody reads it.
+template <class P> __global__ void __launch_bounds__(MF_BLOCK) k_mf_hub_sum(MfNet N, MfHubs Hb, const P* __restrict__ p) {
+    __shared__ long long wsum[MF_BLOCK / 64];
+    const u32 b = blockIdx.x, tid = threadIdx.x; if (b >= Hb.T) return;
+    const u32 h = Hb.tileHub[b], v = Hb.node[h];
+    const long long e = N.excess[v];                                                   // (nobody writes it in this launch)
+    if (tid == 0 && b == Hb.tile0[h]) Hb.snap[h] = e;
+    if (e <= 0) return;
+    const P pv = p[v]; const u32 t0 = Hb.tileBeg[b], end = N.start[v + 1], s1 = end - t0 > MF_HUB_TILE ? t0 + MF_HUB_TILE : end;
+    long long sum = 0;
+    for (u32 s = t0 + tid; s < s1; s += MF_BLOCK) { const int r = N.rcap[s]; if (r > 0 && mf_cost<P>(N, s) + pv - p[N.head[s]] < 0) sum += r; }
+    sum = mf_block_sum(sum, wsum);
+    if (tid == 0) Hb.tsum[b] = sum;
+}
+// Second launch (grid: the tiles).  A tile's base is the sum of its hub's earlier tile sums, added up by the tile's own workgroup; behind that base the tile walks its
+// entries as k_mf_push walks a long list: the amounts are the serial walk's.  Two things make this exact:
+//  1. every tile clips against the snapshot, never against excess[v], which one thread of this same launch -- the hub's last tile -- overwrites;
+//  2. both launches see the same admissible set.  An entry admissible for the hub has a sister of positive reduced cost, which nobody pushes along, so its residual
+//     word has no writer in the round but the tile that owns it here, whatever k_mf_push does to the hub's other entries through their sisters.
+template <class P> __global__ void __launch_bounds__(MF_BLOCK) k_mf_hub_push(MfNet N, MfHubs Hb, const P* __restrict__ p, unsigned long long* ctr) {
+    __shared__ long long wsum[MF_BLOCK / 64]; __shared__ u32 sPush;
+    const u32 b = blockIdx.x, tid = threadIdx.x; if (b >= Hb.T) return;
+    const u32 h = Hb.tileHub[b], v = Hb.node[h];
+    const long long e = Hb.snap[h]; if (e <= 0) return;
+    if (tid == 0) sPush = 0;
+    const u32 first = Hb.tile0[h], last = Hb.tile0[h + 1] - 1;
+    long long base = 0;
+    for (u32 t = first + tid; t < b; t += MF_BLOCK) base += Hb.tsum[t];
+    base = mf_block_sum(base, wsum);
+    if (tid == 0 && b == last) { const long long total = base + Hb.tsum[b]; N.excess[v] = e - (total < e ? total : e); }
+    if (base >= e) return;                                                             // the excess ends in front of this tile
+    const P pv = p[v]; const u32 t0 = Hb.tileBeg[b], end = N.start[v + 1], s1 = end - t0 > MF_HUB_TILE ? t0 + MF_HUB_TILE : end;
+    long long carry = base; u32 np = 0;
+    for (u32 c = t0; c < s1 && carry < e; c += MF_BLOCK) {
+        const u32 s = c + tid; long long amt = 0; u32 w = 0; int r = 0;
+        if (s < s1) { r = N.rcap[s]; if (r > 0) { w = N.head[s]; if (mf_cost<P>(N, s) + pv - p[w] < 0) amt = r; } }
+        long long tot; const long long ex = mf_block_scan(amt, wsum, &tot);
+        const long long room = e - (carry + ex); long long d = amt < room ? amt : room; if (d < 0) d = 0;
+        if (d > 0) { N.rcap[s] = r - (int)d; N.rcap[N.sis[s]] += (int)d; mf_add(&N.delta[w], d); np++; }
+        carry += tot;
+    }
+    if (np) atomicAdd(&sPush, np);
+    __syncthreads();
+    if (tid == 0 && sPush) { atomicAdd(&ctr[MF_PUSHES], (unsigned long long)sPush); atomicAdd(&ctr[MF_HUB_PUSHES], (unsigned long long)sPush); }
+}
+// The relabel over a hub, behind k_mf_relabel (which has added delta to the excess and written pn[v] = p[v]).  First launch (grid: the tiles): k_mf_relabel's pair per
+// tile.  Tiles of a hub without excess write nothing.
+template <class P> __global__ void __launch_bounds__(MF_BLOCK) k_mf_hub_rel(MfNet N, MfHubs Hb, const P* __restrict__ p, P eps, P* tbest, u32* tadm) {
+    __shared__ P wbest[MF_BLOCK / 64]; __shared__ u32 wadm[MF_BLOCK / 64];
+    const u32 b = blockIdx.x, tid = threadIdx.x; if (b >= Hb.T) return;
+    const u32 h = Hb.tileHub[b], v = Hb.node[h];
+    if (N.excess[v] <= 0) return;
+    const P pv = p[v]; const u32 t0 = Hb.tileBeg[b], end = N.start[v + 1], s1 = end - t0 > MF_HUB_TILE ? t0 + MF_HUB_TILE : end;
+    bool adm = false; P best = -mf_inf<P>();
+    for (u32 s = t0 + tid; s < s1; s += MF_BLOCK) {
+        if (N.rcap[s] <= 0) continue;
+        const P pw = p[N.head[s]], c = mf_cost<P>(N, s);
+        if (c + pv - pw < 0) { adm = true; break; }
+        const P x = pw - c - eps; best = x > best ? x : best;
+    }
+    for (int d = 32; d >= 1; d >>= 1) { const P t = mf_shfl_down(best, d); best = t > best ? t : best; }      // (128 bits: as two halves)
+    const u64 anyAdm = __ballot(adm);
+    if ((tid & 63u) == 0) { wbest[tid >> 6] = best; wadm[tid >> 6] = anyAdm ? 1u : 0u; }
+    __syncthreads();
+    if (tid == 0) {
+        bool a = false; P m = -mf_inf<P>();
+        for (u32 i = 0; i < MF_BLOCK / 64; i++) { a = a || wadm[i]; m = wbest[i] > m ? wbest[i] : m; }
+        tbest[b] = m; tadm[b] = a ? 1u : 0u;
+    }
+}
+// Second launch (grid: the hubs): the pairs of a hub's tiles combined, and the result written as k_mf_relabel writes it
+template <class P> __global__ void __launch_bounds__(MF_BLOCK) k_mf_hub_rel_fin(MfNet N, MfHubs Hb, const P* __restrict__ tbest, const u32* __restrict__ tadm, P floor, P* pn, unsigned long long* ctr) {
+    __shared__ P wbest[MF_BLOCK / 64]; __shared__ u32 wadm[MF_BLOCK / 64];
+    const u32 h = blockIdx.x, tid = threadIdx.x; if (h >= Hb.H) return;
+    const u32 v = Hb.node[h];
+    if (N.excess[v] <= 0) return;
+    bool adm = false; P best = -mf_inf<P>();
+    for (u32 t = Hb.tile0[h] + tid, t1 = Hb.tile0[h + 1]; t < t1; t += MF_BLOCK) { adm = adm || tadm[t]; const P x = tbest[t]; best = x > best ? x : best; }
+    for (int d = 32; d >= 1; d >>= 1) { const P t = mf_shfl_down(best, d); best = t > best ? t : best; }
+    const u64 anyAdm = __ballot(adm);
+    if ((tid & 63u) == 0) { wbest[tid >> 6] = best; wadm[tid >> 6] = anyAdm ? 1u : 0u; }
+    __syncthreads();
+    if (tid == 0) {
+        bool a = false; P m = -mf_inf<P>();
+        for (u32 i = 0; i < MF_BLOCK / 64; i++) { a = a || wadm[i]; m = wbest[i] > m ? wbest[i] : m; }
+        if (!a) {
+            if (m < floor) atomicOr(&ctr[MF_FLAGS], MF_F_INFEASIBLE);
+            else { pn[v] = m; atomicAdd(&ctr[MF_RELABELS], 1ull); atomicAdd(&ctr[MF_HUB_RELABELS], 1ull); }
+        }
     }
 }
 

@@ -3535,14 +3535,42 @@ template <class P> static int mcf_solve_device(Device* d, const McfArc* dArcs, u
         hipLaunchKernelGGL(k_mf_entries, dim3(grid_for(M, 256)), b256, 0, sm, dArcs, idx, pos, ks, M, wide ? 1ll : (long long)scale, head, sis, tail, cost, rcap);      // (128-bit prices: the entries keep the unscaled cost)
         hipLaunchKernelGGL(k_mf_starts, dim3(grid_for((u64)n + 2, 256)), b256, 0, sm, ks, M, n, start);
     } else HIPCHK(hipMemsetAsync(start, 0, ((u64)n + 3) * sizeof(u32), sm));
-    HIPCHK(hipGetLastError());
-    HIPCHK(lap.stop(st->build_ms));
-    const MfNet N = {head, sis, tail, start, cost, rcap, excess, delta, n, M, (long long)scale};
-    const u32 nodeGrid = grid_for(n, MF_BLOCK), entryGrid = grid_for(M, 256);
     // (SAGE2OV_TEST_MCF_LDS=0: tests only -- a network that fits the single-workgroup form takes the launches all the same)
     bool lds = false;
     if constexpr (!wide) lds = m && n <= MF_LDS_NODES && M <= MF_LDS_ENTRIES && d->opt.num("SAGE2OV_TEST_MCF_LDS", 1) != 0;
     st->form = lds ? SAGE2OV_MCF_FORM_LDS : SAGE2OV_MCF_FORM_LAUNCHES;
+    // the hub form (the launches only): lists longer than hubDeg.  SAGE2OV_TEST_MCF_HUB_DEG (tests only): 0 off, d >= 64 the threshold (below 64 a lane walks the list)
+    u32 hubDeg = 0;
+    if (!lds && m) { const long long v = d->opt.num("SAGE2OV_TEST_MCF_HUB_DEG", SAGE2OV_MCF_HUB_DEG); hubDeg = v <= 0 ? 0 : (u32)std::min<long long>(std::max<long long>(v, MF_LANE_DEG), MF_NO_HUBS - 1); }
+    st->hub[0] = hubDeg; st->hub[1] = MF_HUB_TILE;
+    unsigned long long hubCounts[2] = {0, 0};
+    if (hubDeg) {                                                                       // the two counts come back with the layout's own synchronisation
+        hipLaunchKernelGGL(k_mf_hub_count, dim3(grid_for(n, 256)), b256, 0, sm, (const u32*)start, n, hubDeg, ctr);
+        HIPCHK(hipMemcpyAsync(hubCounts, ctr + MF_HUBS, sizeof hubCounts, hipMemcpyDeviceToHost, sm));
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(lap.stop(st->build_ms));
+    const MfNet N = {head, sis, tail, start, cost, rcap, excess, delta, n, M, (long long)scale};
+    const u32 nodeGrid = grid_for(n, MF_BLOCK), entryGrid = grid_for(M, 256);
+    // the tables of the hubs, when there are any: ranks by the project's scan, so ascending node number and the same tables on every run
+    MfHubs Hb = {}; P* tbest = nullptr; u32* tadm = nullptr;
+    if (hubCounts[0]) {
+        const u32 H = (u32)hubCounts[0], T = (u32)hubCounts[1];
+        HIPCHK(lap.start());
+        u32* isHub = B.get<u32>(n); u32* nTiles = B.get<u32>(n); u32* rank = B.get<u32>(n); u32* tileRank = B.get<u32>(n); u64* partial = B.get<u64>(scan_partial_words(n));
+        u32* hnode = B.get<u32>(H); u32* tile0 = B.get<u32>((u64)H + 1); u32* tileHub = B.get<u32>(T); u32* tileBeg = B.get<u32>(T);
+        long long* snap = B.get<long long>(H); long long* tsum = B.get<long long>(T); tbest = B.get<P>(T); tadm = B.get<u32>(T);
+        if (!isHub || !nTiles || !rank || !tileRank || !partial || !hnode || !tile0 || !tileHub || !tileBeg || !snap || !tsum || !tbest || !tadm) return mcf_nomem(err);
+        hipLaunchKernelGGL(k_mf_hub_mark, dim3(grid_for(n, 256)), b256, 0, sm, (const u32*)start, n, hubDeg, isHub, nTiles);
+        { const int rc = scan_u32(d, isHub, n, rank, partial, nullptr, err); if (rc) return rc; }
+        { const int rc = scan_u32(d, nTiles, n, tileRank, partial, nullptr, err); if (rc) return rc; }
+        hipLaunchKernelGGL(k_mf_hub_tables, dim3(grid_for(n, 256)), b256, 0, sm, (const u32*)start, n, hubDeg, (const u32*)rank, (const u32*)tileRank, H, T, hnode, tile0, tileHub, tileBeg);
+        HIPCHK(hipGetLastError());
+        HIPCHK(lap.stop(st->build_ms));
+        Hb = MfHubs{hnode, tile0, tileHub, tileBeg, snap, tsum, H, T};
+        st->hub[2] = H; st->hub[3] = T;
+    }
+    const u32 roundHubDeg = hubDeg ? hubDeg : MF_NO_HUBS;
     u32 cur = 0; unsigned long long flags = 0;
     HIPCHK(lap.start());
     if constexpr (!wide) if (lds) {
@@ -3586,8 +3614,16 @@ template <class P> static int mcf_solve_device(Device* d, const McfArc* dArcs, u
                 const u32 K = (u32)std::min<u64>(MF_BATCH, left);
                 HIPCHK(hipMemsetAsync(ctr + MF_ACT, 0, MF_BATCH * sizeof(unsigned long long), sm));
                 for (u32 k = 0; k < K; k++) {
-                    hipLaunchKernelGGL(k_mf_push<P>, dim3(nodeGrid), dim3(MF_BLOCK), 0, sm, N, (const P*)price[cur], ctr);
-                    hipLaunchKernelGGL(k_mf_relabel<P>, dim3(nodeGrid), dim3(MF_BLOCK), 0, sm, N, (const P*)price[cur], price[cur ^ 1u], eps, floor, ctr + MF_ACT + k, ctr);
+                    hipLaunchKernelGGL(k_mf_push<P>, dim3(nodeGrid), dim3(MF_BLOCK), 0, sm, N, (const P*)price[cur], roundHubDeg, ctr);
+                    if (Hb.H) {
+                        hipLaunchKernelGGL(k_mf_hub_sum<P>, dim3(Hb.T), dim3(MF_BLOCK), 0, sm, N, Hb, (const P*)price[cur]);
+                        hipLaunchKernelGGL(k_mf_hub_push<P>, dim3(Hb.T), dim3(MF_BLOCK), 0, sm, N, Hb, (const P*)price[cur], ctr);
+                    }
+                    hipLaunchKernelGGL(k_mf_relabel<P>, dim3(nodeGrid), dim3(MF_BLOCK), 0, sm, N, (const P*)price[cur], price[cur ^ 1u], eps, floor, roundHubDeg, ctr + MF_ACT + k, ctr);
+                    if (Hb.H) {
+                        hipLaunchKernelGGL(k_mf_hub_rel<P>, dim3(Hb.T), dim3(MF_BLOCK), 0, sm, N, Hb, (const P*)price[cur], eps, tbest, tadm);
+                        hipLaunchKernelGGL(k_mf_hub_rel_fin<P>, dim3(Hb.H), dim3(MF_BLOCK), 0, sm, N, Hb, (const P*)tbest, (const u32*)tadm, floor, price[cur ^ 1u], ctr);
+                    }
                     cur ^= 1u;
                 }
                 HIPCHK(hipGetLastError());
@@ -3600,6 +3636,7 @@ template <class P> static int mcf_solve_device(Device* d, const McfArc* dArcs, u
             HIPCHK(hipEventRecord(e1, sm)); HIPCHK(hipEventSynchronize(e1));
             if (ph < SAGE2OV_MCF_PHASES) { float t = 0; hipEventElapsedTime(&t, e0, e1); st->refine_ms[ph] = t; st->refine_rounds[ph] = rounds - r0; }
             st->rounds = rounds; st->updates = updates; st->pushes = hc[MF_PUSHES]; st->relabels = hc[MF_RELABELS];
+            st->hub[4] = hc[MF_HUB_PUSHES]; st->hub[5] = hc[MF_HUB_RELABELS];
         }
     }
     HIPCHK(lap.stop(st->solve_ms));

@@ -141,6 +141,7 @@ struct sage2ov_ctx {
     // ---- step 5 around its solver (sage2ov_genome_size_estimate, sage2ov_flow_*): the estimate and the network are of the present graph and read set; the data live on the device
     bool gsValid = false, netValid = false; sage2ov_copycount_stats ccstats{};
     sage2ov_mcf_stats mcfstats{};                                                      // of the last solve (sage2ov_mcf_solve, sage2ov_flow_solve)
+    uint64_t mcfhub[6] = {};                                                           // sage2ov_mcf_hub_stats_get, of the same solve
     void copycount_forget() { gsValid = netValid = false; ccstats = sage2ov_copycount_stats{}; }
     // ---- the merge rounds (sage2ov_graph_merge_pairs, sage2ov_extend_*): the estimate outlives a merge (estimateHeld: a rebuilt table leaves it alone); the header
     // values of P.graph6 are those from before the first merge
@@ -2338,6 +2339,7 @@ void mcf_stats_set(sage2ov_ctx* c, const McfStats& s) {
     o.form = s.form; o.price_words = s.priceWords; o.build_ms = s.build_ms; o.solve_ms = s.solve_ms;
     for (int i = 0; i < SAGE2OV_MCF_PHASES; i++) { o.refine_rounds[i] = s.refine_rounds[i]; o.refine_ms[i] = s.refine_ms[i]; }
     c->mcfstats = o;
+    for (int i = 0; i < 6; i++) c->mcfhub[i] = s.hub[i];
 }
 // sum of flow * cost; false when it leaves int64
 extern "C++" { template <class Cost>
@@ -2461,6 +2463,12 @@ int sage2ov_copy_counts(sage2ov_ctx* c, uint64_t* genome_size) {
     return sage2ov_flow_solution_commit(c);
 }
 int sage2ov_mcf_stats_get(const sage2ov_ctx* c, sage2ov_mcf_stats* o) { if (!c || !o) return SAGE2OV_ERR_ARG; *o = c->mcfstats; return SAGE2OV_OK; }
+int sage2ov_mcf_hub_stats_get(const sage2ov_ctx* c, uint64_t out[6]) {
+    if (!c || !out) return SAGE2OV_ERR_ARG;
+    if (!c->device()) return SAGE2OV_ERR_DEVICE;
+    for (int i = 0; i < 6; i++) out[i] = c->mcfhub[i];
+    return SAGE2OV_OK;
+}
 int sage2ov_mates_supports(sage2ov_ctx* c) {
     if (!c) return SAGE2OV_ERR_ARG;
     { const int rc = readmap_check(c, "sage2ov_mates_supports"); if (rc) return rc; }

@@ -265,7 +265,8 @@ void dev_copycount_release(Device* d);
 // step 5's solver on the device (sage2ov_mcf_solve, sage2ov_flow_solve, sage2ov_flow_solution_*; kernels_flow.inc).  dev_mcf_solve: any network, host
 // arrays in and out (arcs: sage2ov_mcf_arc records; price may be null).  dev_flow_solve: the resident network; its solution stays on the device with the network.
 struct McfStats { uint64_t nodes = 0, arcs = 0, scale = 0, phases = 0, rounds = 0, pushes = 0, relabels = 0, updates = 0; uint32_t form = 0, priceWords = 0; double build_ms = 0, solve_ms = 0;
-                  uint64_t refine_rounds[SAGE2OV_MCF_PHASES] = {}; double refine_ms[SAGE2OV_MCF_PHASES] = {}; };
+                  uint64_t refine_rounds[SAGE2OV_MCF_PHASES] = {}; double refine_ms[SAGE2OV_MCF_PHASES] = {};
+                  uint64_t hub[6] = {}; };             // sage2ov_mcf_hub_stats_get: threshold in force, MF_HUB_TILE, hubs, tiles, entries pushed along and relabels by the hub form
 // wide: 128-bit prices (price: two words per node, the low one first).  dev_flow_solve chooses the width itself; dev_flow_price_words: 1 or 2, of the resident solution
 // (0: none).  mcf_wide_guard: whether n nodes with that largest |cost| stay inside +-2^126 (host arithmetic only).
 int dev_mcf_solve(Device* d, const void* arcs, uint64_t m, uint32_t n, uint64_t maxRounds, bool wide, int64_t* flow, void* price, McfStats* st, std::string& err);
